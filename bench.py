@@ -4,6 +4,14 @@
 Metric (BASELINE.json): inferences/sec (whole node) + p50 cold-start ms, ResNet-50 bs=1 at
 1/2/4/8 GPU. One process per GPU (torchrun); every rank is a serving replica.
 
+A plain run (``bench.py --gpus N --steps K --warmup W``) does what the headline ``value`` needs and
+nothing else: it writes the random-init checkpoint if missing, builds the engine, runs W warmup and
+K timed steps, writes ``--dump-outputs DIR`` if asked and prints the result line. ``--full`` adds
+every other figure described below (cold starts over fresh processes and in-process, single-request
+latency, the other serving mode, the sustained window, dynamic batching, HTTP serving, the DP and
+BASELINE config figures, ``--compare-torch``); without it their options are ignored and their
+fields are null or absent.
+
 cold start (headline ``cold_start_ms_p50``): measured FIRST, before this process touches a GPU,
   as the p50 over ``--cold-trials`` FRESH child processes of spawn -> first logits
   (hipzap/coldstart.py) from the deploy artifact a serverless replica starts from: the
@@ -105,7 +113,37 @@ def parse():
     ap.add_argument("--input", choices=["uint8", "fp32"], default=os.environ.get("HIPZAP_BENCH_INPUT", "uint8"),
                     help="request payload: uint8 HWC images (decoded-JPEG format, ImageNet mean/std applied on "
                          "device by the preprocess kernel) or pre-normalised fp32 NCHW tensors")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: fresh-process and in-process cold starts, "
+                         "single-request latency, the other serving mode, the sustained window, dynamic batching, "
+                         "HTTP serving, the DP and BASELINE config figures, --compare-torch. Without it only the "
+                         "K timed steps are measured and the options of those figures are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the logits a caller of every "
+                         "request stream receives) to DIR/logits.npy as float32 (rank 0)")
+    args = ap.parse_args()
+    if not args.full:  # the plain run: set up, warm up, time the K steps, print the result line
+        args.cold_trials = args.cold_runs = args.dyn_batch = args.http_clients = 0
+        args.bert_cold = args.lm_cold = args.dp_figures = args.config_figures = 0
+        args.sustained_s = 0.0
+        args.compare_torch = False
+    return args
+
+
+def dump_outputs(path: str, **arrays) -> None:
+    """--dump-outputs: one ``<name>.npy`` per array, float32 (float64 kept), at most 64 MB in all
+    (a larger array is cut to a fixed, seeded sample of its rows)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = (64 << 20) // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = (a if a.dtype == torch.float64 else a.float()).numpy()
+        if a.nbytes > budget:
+            a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, budget // max(1, a[0].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(keep, a.shape[0]), replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def run_scatter(args, rank, world, device, adapter, ckpt, tuned=None):
@@ -124,6 +162,7 @@ def run_scatter(args, rank, world, device, adapter, ckpt, tuned=None):
     params, arch_kw = broadcast_params(params, lambda kw: adapter.meta_params(**kw), device, arch_kw=arch_kw)
     eng = Engine(args.model, params, device, batch=shard, num_contexts=1, arch_kw=arch_kw, host_io=False,
                  tuned=tuned)
+    torch.manual_seed(0)  # the same global batch in every run
     x_in = adapter.example_input(shard)
     in_shape = tuple(eng.contexts[0].input.shape[1:])
     out_shape = tuple(eng.contexts[0].output.shape[1:])
@@ -140,14 +179,17 @@ def run_scatter(args, rank, world, device, adapter, ckpt, tuned=None):
         dist.barrier()
     torch.cuda.synchronize(device)
     t1 = time.perf_counter()
+    y = None
     for _ in range(args.steps):
-        ex.step(xg)
+        y = ex.step(xg)
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t1
     if is_dist():
         dist.barrier()
     dt = max_over_ranks(dt, device)
     del x_in
+    if rank == 0 and args.dump_outputs and y is not None:
+        dump_outputs(args.dump_outputs, logits=y)
     if rank == 0:
         value = args.global_batch * args.steps / dt
         print(json.dumps({
@@ -581,7 +623,9 @@ def _plumbing_figure() -> dict:
 
 
 def request_input(args, adapter):
-    """One request's payload: a decoded uint8 HWC image (default) or an fp32 NCHW tensor."""
+    """One request's payload: a decoded uint8 HWC image (default) or an fp32 NCHW tensor; seeded,
+    so every run sends the same one."""
+    torch.manual_seed(0)
     if args.input == "uint8" and args.model.startswith("resnet"):
         return torch.randint(0, 256, (args.batch, 224, 224, 3), dtype=torch.uint8)
     return adapter.example_input(args.batch)
@@ -697,8 +741,10 @@ def main():
             dev_index = local % max(1, torch.cuda.device_count()) if os.environ.get("HIPZAP_SHARE_GPU") == "1" \
                 else local
             fresh = fresh_cold_start(args, dev_index, world)
-        else:
+        elif args.full:
             prepare_artifacts(args.model, args.ckpt_dir)
+        elif not os.path.exists(os.path.join(args.ckpt_dir, f"{args.model}_seed0.pth")):
+            write_checkpoint(os.path.join(args.ckpt_dir, f"{args.model}_seed0.pth"), args.model)  # all a plain run loads
 
     from hipzap.engine.engine import Engine
     from hipzap.models import registry
@@ -818,17 +864,22 @@ def main():
     deferred_ms = eng.ensure_contexts()
     # single-request latency, one request at a time (round-robin over the contexts), p50/p99
     x = request_input(args, adapter)
-    lat = []
-    for i in range(210):
-        t = time.perf_counter()
-        eng.infer(x)
-        lat.append((time.perf_counter() - t) * 1e3)
-    lat = sorted(lat[10:])
-    lat_p50, lat_p99 = statistics.median(lat), lat[min(len(lat) - 1, int(0.99 * len(lat)))]
+    lat_p50 = lat_p99 = None
+    if args.full:
+        lat = []
+        for i in range(210):
+            t = time.perf_counter()
+            eng.infer(x)
+            lat.append((time.perf_counter() - t) * 1e3)
+        lat = sorted(lat[10:])
+        lat_p50, lat_p99 = statistics.median(lat), lat[min(len(lat) - 1, int(0.99 * len(lat)))]
 
     def pct(v, q):
         v = sorted(v)
         return v[min(len(v) - 1, int(q * len(v)))]
+
+    def per_s(n, seconds):
+        return round(n / seconds, 2) if seconds else None
 
     # 3. throughput: W warmup steps, then K timed steps; a step = one request on every stream
     payload = x.reshape(eng.contexts[0].host_input.shape)
@@ -852,6 +903,10 @@ def main():
     if is_dist():
         dist.barrier()
     dt = max_over_ranks(dt, device)
+    if args.dump_outputs and rank == 0:
+        # every stream's last replay left its logits in the context's pinned output, which a caller
+        # receives a copy of (Engine.infer): one row per request stream
+        dump_outputs(args.dump_outputs, logits=torch.stack([eng._post(c.host_output.clone()) for c in eng.contexts]))
     # a longer self-timed window of the same serving loop (>= --sustained-s), so box noise over the
     # driver's short K-step region is not mistaken for kernel wins (same on every rank: dt is the max)
     sustained = None
@@ -867,15 +922,18 @@ def main():
         sustained = {"inf_s": round(world * args.streams * args.batch * n_long / dt_l, 2), "steps": n_long,
                      "window_s": round(dt_l, 3)}
     # the other serving mode, untimed for the headline (same K), for reference
-    dt_other, lat_other = run(args.steps * rps, other)
-    dt_other = max_over_ranks(dt_other, device)
+    dt_other = lat_other = t_single = None
+    if args.full:
+        dt_other, lat_other = run(args.steps * rps, other)
+        dt_other = max_over_ranks(dt_other, device)
     lat_closed = lat_load if args.serve != "pipelined" else lat_other
     inf = world * args.streams * args.batch * args.steps * rps
     value = inf / dt
-    # strict single-stream throughput (one context, replays back to back)
-    single = eng.contexts[0]
-    from hipzap.engine.program import bench_contexts
-    t_single = bench_contexts([single], [eng.streams[0]], 200)
+    if args.full:
+        # strict single-stream throughput (one context, replays back to back)
+        single = eng.contexts[0]
+        from hipzap.engine.program import bench_contexts
+        t_single = bench_contexts([single], [eng.streams[0]], 200)
     dyn = dynamic_batching(args, eng, device, world) if args.dyn_batch > 1 and args.batch == 1 else None
     http = http_figure(args, world, rank) if args.http_clients > 0 and args.batch == 1 else None
     dpf = dp_figures(args, eng, device, world, rank, native_comm) \
@@ -941,13 +999,15 @@ def main():
             "cold_start_inprocess_packed_ms_p50": round(statistics.median(colds_packed), 2) if colds_packed else None,
             "cold_start_inprocess_packed_breakdown_ms": {k: round(v, 2) for k, v in breakdown_packed.items()},
             "deferred_contexts_ms": round(deferred_ms, 2),
-            "served_closed_loop_inf_s": round(inf / (dt if args.serve != "pipelined" else dt_other), 2),
-            "device_pipelined_inf_s": round(inf / (dt if args.serve == "pipelined" else dt_other), 2),
-            "latency_ms_under_load_p50": round(pct(lat_closed, 0.5), 4),
-            "latency_ms_under_load_p99": round(pct(lat_closed, 0.99), 4),
-            "latency_ms_p50_single": round(lat_p50, 4),
-            "latency_ms_p99_single": round(lat_p99, 4),
-            "single_stream_inf_s": round(200 / t_single, 2),
+            # the figures of the serving mode that was not timed, the one-request-at-a-time latencies and
+            # the single-stream rate take runs of their own: --full (None without it)
+            "served_closed_loop_inf_s": per_s(inf, dt if args.serve != "pipelined" else dt_other),
+            "device_pipelined_inf_s": per_s(inf, dt if args.serve == "pipelined" else dt_other),
+            "latency_ms_under_load_p50": round(pct(lat_closed, 0.5), 4) if lat_closed else None,
+            "latency_ms_under_load_p99": round(pct(lat_closed, 0.99), 4) if lat_closed else None,
+            "latency_ms_p50_single": round(lat_p50, 4) if lat_p50 is not None else None,
+            "latency_ms_p99_single": round(lat_p99, 4) if lat_p99 is not None else None,
+            "single_stream_inf_s": per_s(200, t_single),
             "baseline_note": "vs_baseline against BASELINE.md sandbox-CPU ResNet-50 bs=1 (27.2 inf/s); "
                              "no published numbers exist",
         }

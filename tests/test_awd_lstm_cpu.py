@@ -1,48 +1,44 @@
 """AWD-LSTM: checkpoint compatibility with the reference module, W_hh quirk, stateful API."""
-import importlib.util
 import os
-import sys
 
+import numpy as np
 import pytest
 import torch
 
 from hipzap.models.awd_lstm import get_language_model
 
-REF = "/root/reference/pytorch_models/awd_lstm.py"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _ref_module():
-    if not os.path.exists(REF):
-        pytest.skip("reference not mounted")
-    spec = importlib.util.spec_from_file_location("ref_awd_lstm", REF)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+def _ref(name):
+    """The reference module's recorded run (scripts/make_golden_awd_lstm.py): its random-init
+    state_dict, the token batches it was fed and the decoded outputs it returned in eval mode."""
+    z = np.load(os.path.join(GOLDEN, f"{name}.npz"))
+    sd = {k[3:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd/")}
+    return sd, torch.from_numpy(z["x"]), torch.from_numpy(z["y"])
 
 
 KW = dict(vocab_sz=120, emb_sz=40, n_hid=48, n_layers=3, pad_token=1, tie_weights=True, bias=True, qrnn=False)
 
 
 def test_state_dict_keys_match_reference():
-    ref = _ref_module().get_language_model(**KW)
+    ref_sd = _ref("awd_lstm_ref")[0]
     ours = get_language_model(**KW)
-    assert set(ref.state_dict()) == set(ours.state_dict())
-    for k, v in ref.state_dict().items():
+    assert set(ref_sd) == set(ours.state_dict())
+    for k, v in ref_sd.items():
         assert ours.state_dict()[k].shape == v.shape, k
 
 
 def test_forward_matches_reference_eval():
-    ref = _ref_module().get_language_model(**KW)
+    sd, xs, ys = _ref("awd_lstm_ref")
     ours = get_language_model(**KW)
-    sd = ref.state_dict()
     ours.load_state_dict(sd)
-    ref.eval(); ours.eval()
-    ref.reset(); ours.reset()
-    torch.manual_seed(0)
-    for step in range(5):
-        x = torch.randint(0, 120, (3, 2))
+    ours.eval()
+    ours.reset()
+    assert len(xs) == 5
+    for step, (x, a) in enumerate(zip(xs, ys)):
+        assert x.shape == (3, 2)
         with torch.no_grad():
-            a, ra, oa = ref(x)
             b, rb, ob = ours(x)
         assert a.shape == b.shape == (6, 120)
         assert torch.allclose(a, b, atol=1e-5), step
@@ -79,18 +75,19 @@ def test_qrnn_unsupported():
 def test_bidirectional_core_matches_reference():
     """bidir=True (reference awd_lstm.py:57,69-70,95): same keys and shapes, same eval forward."""
     kw = dict(KW, bidir=True)
-    ref = _ref_module().get_language_model(**kw)
+    sd, xs, ys = _ref("awd_lstm_ref_bidir")
     ours = get_language_model(**kw)
-    assert set(ref.state_dict()) == set(ours.state_dict())
-    sd = ref.state_dict()
+    assert set(sd) == set(ours.state_dict())
+    for k, v in sd.items():
+        assert ours.state_dict()[k].shape == v.shape, k
     ours.load_state_dict(sd)
-    ref.eval(); ours.eval()
-    ref.reset(); ours.reset()
-    x = torch.randint(0, KW["vocab_sz"], (7, 3))
+    ours.eval()
+    ours.reset()
+    x, a = xs[0], ys[0]
+    assert x.shape == (7, 3)
     with torch.no_grad():
-        a = ref(x)[0]
         b = ours(x)[0]
-    assert torch.allclose(a, b, atol=1e-5)
+    assert a.shape == b.shape and torch.allclose(a, b, atol=1e-5)
     assert ours[0].hidden[0][0].shape == (2, 3, KW["n_hid"] // 2)
 
 

@@ -1,21 +1,23 @@
 """bench.py's output contract on the GPU (the driver parses it every round): one JSON line with
 BASELINE.json's metric, the requested steps / warmup, a positive whole-job value and the
-fields the judge checks. A short run with every secondary figure disabled."""
+fields the judge checks, and ``--dump-outputs``: the logits of the last timed step. A short plain
+run (no ``--full``: the headline only)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_prints_one_contract_line():
+def test_bench_prints_one_contract_line(tmp_path):
     cmd = [sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--streams", "2", "--cold-trials", "0",
            "--cold-runs", "0", "--http-clients", "0", "--dp-figures", "0", "--dyn-batch", "0", "--bert-cold", "0",
-           "--lm-cold", "0"]
+           "--lm-cold", "0", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -35,3 +37,7 @@ def test_bench_prints_one_contract_line():
     rps = d["config"]["requests_per_stream_per_step"]
     assert rps >= 1
     assert abs(d["value"] - 2 * rps * 1e3 / d["ms_per_step"]) / d["value"] < 0.01
+    # --dump-outputs: what the last timed step computed, one row of logits per request stream
+    assert sorted(os.listdir(tmp_path / "out")) == ["logits.npy"]
+    y = np.load(tmp_path / "out" / "logits.npy")
+    assert y.dtype == np.float32 and y.shape == (2, 1, 1000) and np.isfinite(y).all() and np.abs(y).max() > 0

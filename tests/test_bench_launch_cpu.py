@@ -58,3 +58,21 @@ def test_missing_gpus_fail_before_spawning():
                        timeout=120, env=_env(), cwd=ROOT)
     assert r.returncode != 0
     assert "needs 2 GPUs" in r.stderr and not _json_lines(r.stdout)
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """Without ``--full`` every secondary figure is off, whatever its option says; ``--full`` keeps
+    the options as given."""
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    secondary = ("cold_trials", "cold_runs", "dyn_batch", "http_clients", "bert_cold", "lm_cold", "dp_figures",
+                 "config_figures", "sustained_s", "compare_torch")
+    argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--cold-trials", "4", "--compare-torch"]
+    monkeypatch.setattr(sys, "argv", argv)
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert not any(getattr(a, k) for k in secondary)
+    monkeypatch.setattr(sys, "argv", argv + ["--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.cold_trials == 4 and a.compare_torch
+    assert a.cold_runs == 3 and a.dyn_batch == 16 and a.dp_figures and a.config_figures and a.sustained_s == 2.0

@@ -4,6 +4,8 @@ are scattered/gathered through the sequencer from any rank, health all-reduces r
 worker dies the survivors reform and keep serving batches (SURVEY.md §4.2 T-comm-fake, §5)."""
 import multiprocessing as mp
 import os
+import shutil
+import tempfile
 import time
 
 import numpy as np
@@ -51,13 +53,25 @@ def _worker(rank, world, rdzv, conn, join=False):
 
 
 @pytest.fixture()
-def cluster(tmp_path):
+def rdzv():
+    """Rendezvous directory for the AF_UNIX sockets. A socket path holds at most 107 bytes
+    (sun_path), which pytest's tmp_path under a deep base directory exceeds: use the default
+    temporary directory while the longest socket name still fits, else the system one."""
+    longest = len(os.path.join("hz_cluster_XXXXXXXX", "c99.r9.sock")) + 1
+    base = tempfile.gettempdir()
+    d = tempfile.mkdtemp(prefix="hz_cluster_", dir=base if len(base) + longest < 100 else "/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture()
+def cluster(rdzv):
     ctx = mp.get_context("spawn")
     world = 3
     pipes, procs = [], []
     for r in range(world):
         a, b = ctx.Pipe()
-        p = ctx.Process(target=_worker, args=(r, world, str(tmp_path), b), daemon=True)
+        p = ctx.Process(target=_worker, args=(r, world, rdzv, b), daemon=True)
         p.start()
         pipes.append(a)
         procs.append(p)
@@ -131,7 +145,7 @@ def test_abandoned_submit_still_joins_the_collectives(cluster):
 
 
 @pytest.mark.timeout(240)
-def test_members_rejoin_a_restarted_sequencer(cluster, tmp_path):
+def test_members_rejoin_a_restarted_sequencer(cluster, rdzv):
     """rank 0 (the sequencer's host) dies and is restarted with join: the other
     members reconnect to the new coordinator and batched DP works again over all three."""
     pipes, procs = cluster
@@ -139,7 +153,7 @@ def test_members_rejoin_a_restarted_sequencer(cluster, tmp_path):
     procs[0].join(10)
     ctx = mp.get_context("spawn")
     a, b = ctx.Pipe()
-    p = ctx.Process(target=_worker, args=(0, 3, str(tmp_path), b, True), daemon=True)
+    p = ctx.Process(target=_worker, args=(0, 3, rdzv, b, True), daemon=True)
     p.start()
     procs.append(p)
     assert a.poll(60) and a.recv() == "ready"
