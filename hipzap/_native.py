@@ -26,6 +26,33 @@ _lib = None
 c_void_p, c_int, c_long, c_double = C.c_void_p, C.c_int, C.c_long, C.c_double
 c_float_p = C.POINTER(C.c_float)
 
+# the kernel table (csrc/hipzap.h HZ_KERNELS): the ONE place a kind's number appears in Python; also
+# module attributes (N.HZ_K_CONV, ...). tests/test_kinds_cpu.py compares it with the library's table.
+KINDS = {
+    "HZ_K_CONV": 1, "HZ_K_LAYERNORM": 2, "HZ_K_EMBED": 3, "HZ_K_ATTENTION": 4, "HZ_K_VIT_TOKENS": 5,
+    "HZ_K_LSTM": 6, "HZ_K_DECODER": 7, "HZ_K_SAMPLER": 8, "HZ_K_MAXPOOL": 9, "HZ_K_QUANT": 10,
+    "HZ_K_GEMM_FP8": 11, "HZ_K_SOFTMAX": 12, "HZ_K_POOL_FC": 13, "HZ_K_LMB_LAYER": 14, "HZ_K_LMB_DEC": 15,
+    "HZ_K_LMB_ADMIT": 16, "HZ_K_STEM": 18, "HZ_K_BNECK": 19, "HZ_K_SEAM": 20, "HZ_K_KCONV": 21,
+    "HZ_K_QKVATT": 22, "HZ_K_CONV2": 23, "HZ_K_AVGPOOL": 24, "HZ_K_PREPROCESS": 25, "HZ_K_STEP_BUMP": 26,
+    "HZ_K_DIAG": 27,
+}
+globals().update(KINDS)
+KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct
+
+
+def params_of(name: str):
+    """Class decorator: this ctypes.Structure mirrors the parameter struct of kind ``name``."""
+    def reg(cls):
+        KIND_STRUCT[KINDS[name]] = cls
+        return cls
+    return reg
+
+
+def prog_add(lib, prog, kind: int, prm, slot: int, what: str) -> None:
+    """Append one launch of ``kind`` to a program (``lib``: the native library or a PlanRecorder)."""
+    assert type(prm) is KIND_STRUCT[kind], (what, type(prm).__name__)
+    check(lib.hz_prog_add_kernel(prog, kind, C.byref(prm), C.sizeof(prm), slot), what)
+
 
 class ConvParams(C.Structure):
     _fields_ = [
@@ -49,12 +76,24 @@ class LnFold(C.Structure):
                 ("ld_stats", c_int), ("inv_d", C.c_float), ("eps_in", C.c_float), ("eps_res", C.c_float)]
 
 
+@params_of("HZ_K_CONV")
+class ConvOp(C.Structure):
+    _fields_ = [("p", ConvParams), ("cfg", c_int), ("pad_", c_int)]
+
+
+@params_of("HZ_K_CONV2")
+class Conv2Op(C.Structure):
+    _fields_ = [("a", ConvParams), ("b", ConvParams), ("cfg", c_int), ("pad_", c_int)]
+
+
+@params_of("HZ_K_MAXPOOL")
 class PoolParams(C.Structure):
     _fields_ = [("x", c_void_p), ("out", c_void_p),
                 ("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("P", c_int), ("Q", c_int),
                 ("k", c_int), ("stride", c_int), ("pad", c_int)]
 
 
+@params_of("HZ_K_LSTM")
 class LstmParams(C.Structure):
     _fields_ = [("w", c_void_p), ("bias", c_void_p), ("emb", c_void_p), ("lde", c_int), ("tok_seq", c_void_p),
                 ("x_state", c_void_p), ("h_state", c_void_p), ("c_state", c_void_p), ("step", c_void_p),
@@ -64,6 +103,7 @@ class LstmParams(C.Structure):
                 ("h0_state", c_void_p), ("c0_state", c_void_p), ("H0", c_int), ("pad0", c_int)]
 
 
+@params_of("HZ_K_SAMPLER")
 class SamplerParams(C.Structure):
     _fields_ = [("keys", c_void_p), ("tok_seq", c_void_p), ("step", c_void_p), ("step_off", c_int), ("draws", c_void_p),
                 ("n_forced", c_void_p), ("V", c_int), ("n_exclude", c_int), ("exclude", c_int * 8),
@@ -71,6 +111,7 @@ class SamplerParams(C.Structure):
                 ("bacc_val", c_void_p), ("bacc_idx", c_void_p)]
 
 
+@params_of("HZ_K_DECODER")
 class DecoderParams(C.Structure):
     _fields_ = [("w", c_void_p), ("bias", c_void_p), ("h_state", c_void_p), ("step", c_void_p),
                 ("step_off", c_int), ("logits", c_void_p), ("V", c_int), ("H", c_int), ("ldk", c_int), ("keys", c_void_p),
@@ -80,11 +121,24 @@ class DecoderParams(C.Structure):
                 ("hh_b", c_void_p * 4), ("hh_h", c_void_p * 4), ("hh_out", c_void_p * 4), ("hh_H", c_int * 4),
                 ("hh_ld", c_int * 4), ("hh_blk", c_int * 5)]
 
+
+@params_of("HZ_K_STEP_BUMP")
+class StepBumpArgs(C.Structure):
+    _fields_ = [("step", c_void_p), ("n", c_int), ("pad_", c_int)]
+
+
+@params_of("HZ_K_DIAG")
+class DiagArgs(C.Structure):  # hz_diag_launch: kind 0 = no-op kernel, 1 = copy `bytes` from a to b
+    _fields_ = [("kind", c_int), ("blocks", c_int), ("threads", c_int), ("pad_", c_int), ("a", c_void_p),
+                ("b", c_void_p), ("bytes", c_long)]
+
+
 # batched AWD-LSTM decode (csrc/lmbatch.hip, csrc/lmserve.cpp)
 class LmbCtl(C.Structure):
     _fields_ = [("tok", c_int), ("out", c_int), ("dec_t", c_int), ("rec", c_int)]
 
 
+@params_of("HZ_K_LMB_LAYER")
 class LmbLayerParams(C.Structure):
     _fields_ = [("w", c_void_p), ("bias", c_void_p), ("h", c_void_p), ("x", c_void_p), ("c", c_void_p),
                 ("gpar", c_void_p), ("ctl", c_void_p), ("H", c_int), ("Kh", c_int), ("Kx", c_int), ("R", c_int),
@@ -97,6 +151,7 @@ class LmbEmbProjParams(C.Structure):
                 ("Vp", c_int)]
 
 
+@params_of("HZ_K_LMB_DEC")
 class LmbDecParams(C.Structure):
     _fields_ = [("w", c_void_p), ("bias", c_void_p), ("h", c_void_p), ("gpar", c_void_p), ("ctl", c_void_p),
                 ("seed", c_void_p), ("dbest", c_void_p), ("logits", c_void_p), ("V", c_int), ("Vp", c_int),
@@ -104,13 +159,13 @@ class LmbDecParams(C.Structure):
                 ("nb_act", c_int), ("exclude", c_int * 8)]
 
 
+@params_of("HZ_K_LMB_ADMIT")
 class LmbAdmitParams(C.Structure):
     _fields_ = [("block", c_void_p), ("ctl", c_void_p), ("seed", c_void_p), ("outp", c_void_p), ("gpar", c_void_p),
                 ("Bp", c_int), ("U", c_int), ("n_layers", c_int), ("pad_", c_int), ("h", c_void_p * 4),
                 ("c", c_void_p * 4), ("Kh", c_int * 4), ("H", c_int * 4)]
 
 
-HZ_K_LMB_LAYER, HZ_K_LMB_DEC, HZ_K_LMB_ADMIT = 14, 15, 16
 class PackConvParams(C.Structure):  # csrc/pack.hip (torch-free checkpoint cold start)
     _fields_ = [("w", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("mean", c_void_p), ("var", c_void_p),
                 ("bias_in", c_void_p), ("wf", c_void_p), ("bias_out", c_void_p), ("cout", c_int), ("cin", c_int),
@@ -146,11 +201,6 @@ def _load():
     _sig(lib, "hz_prog_create", P)
     _sig(lib, "hz_prog_destroy", None, P)
     _sig(lib, "hz_prog_num_ops", c_int, P)
-    _sig(lib, "hz_prog_add_conv", c_int, P, C.POINTER(ConvParams), c_int, c_int)
-    _sig(lib, "hz_prog_add_conv2", c_int, P, C.POINTER(ConvParams), C.POINTER(ConvParams), c_int, c_int)
-    _sig(lib, "hz_prog_add_maxpool", c_int, P, C.POINTER(PoolParams), c_int)
-    _sig(lib, "hz_prog_add_avgpool", c_int, P, P, P, c_int, c_int, c_int, c_int, c_int)
-    _sig(lib, "hz_prog_add_preprocess", c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int)
     _sig(lib, "hz_prog_add_memcpy", c_int, P, P, P, C.c_size_t, c_int)
     _sig(lib, "hz_prog_add_fork", c_int, P, c_int)
     _sig(lib, "hz_prog_add_join", c_int, P, c_int)
@@ -166,19 +216,16 @@ def _load():
     _sig(lib, "hz_serve_bench", c_int, PP, PP, PP, PP, C.c_uint64, PP, PP, C.c_uint64, c_int, c_int,
          C.POINTER(c_double), C.POINTER(c_double))
     _sig(lib, "hz_diag_launch", c_int, c_int, c_int, c_int, P, P, c_long, P)
-    _sig(lib, "hz_prog_add_diag", c_int, P, c_int, c_int, c_int, P, P, c_long, c_int)
     _sig(lib, "hz_prog_replay_n", c_int, P, P, c_int)
     _sig(lib, "hz_launch_kernel", c_int, c_int, P, P)
     _sig(lib, "hz_experiments", c_int)
     _sig(lib, "hz_prog_add_kernel", c_int, P, c_int, P, C.c_size_t, c_int)
+    _sig(lib, "hz_kernel_param_size", C.c_size_t, c_int)
+    _sig(lib, "hz_kernel_name", C.c_char_p, c_int)
     _sig(lib, "hz_lstm_cell_launch", c_int, C.POINTER(LstmParams), P)
     _sig(lib, "hz_decoder_launch", c_int, C.POINTER(DecoderParams), P)
     _sig(lib, "hz_sampler_launch", c_int, C.POINTER(SamplerParams), P)
     _sig(lib, "hz_decoder_geometry", None, c_int, C.POINTER(c_int), C.POINTER(c_int))
-    _sig(lib, "hz_prog_add_lstm", c_int, P, C.POINTER(LstmParams), c_int)
-    _sig(lib, "hz_prog_add_decoder", c_int, P, C.POINTER(DecoderParams), c_int)
-    _sig(lib, "hz_prog_add_sampler", c_int, P, C.POINTER(SamplerParams), c_int)
-    _sig(lib, "hz_prog_add_step_bump", c_int, P, P, c_int, c_int)
     _sig(lib, "hz_step_bump_launch", c_int, P, c_int, P)
     # plan images (csrc/plan.cpp; hipzap/lite.py is the torch-free client)
     U64, D = C.c_uint64, c_double

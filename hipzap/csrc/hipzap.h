@@ -59,9 +59,6 @@ int hz_gemm_lds_launch(const HzConvParams* p, int cfg, hipStream_t st);
 // two independent convs with one shared (cfg, kw) in one launch (grouped; conv.hip conv2_kernel)
 int hz_conv2_launch(const HzConvParams* a, const HzConvParams* b, int cfg, hipStream_t st);
 
-// (kind 17, the persistent dependent-conv chain, was removed in round 5: measured negative in
-// round 3, profiles/r3_chain)
-
 typedef struct HzPoolParams {
   const unsigned short* x;  // NHWC bf16
   unsigned short* out;      // NHWC bf16
@@ -500,33 +497,90 @@ int hz_seam_launch(const HzSeamParams* p, hipStream_t st);
 int hz_kconv_launch(const HzKconvParams* p, hipStream_t st);
 int hz_block_code_warm(void);
 
-// generic program op: kind selects the launcher, params are copied into the program
-enum { HZ_K_CONV = 1, HZ_K_LAYERNORM = 2, HZ_K_EMBED = 3, HZ_K_ATTENTION = 4, HZ_K_VIT_TOKENS = 5,
-       HZ_K_LSTM = 6, HZ_K_DECODER = 7, HZ_K_SAMPLER = 8, HZ_K_MAXPOOL = 9, HZ_K_QUANT = 10, HZ_K_GEMM_FP8 = 11,
-       HZ_K_SOFTMAX = 12, HZ_K_POOL_FC = 13, HZ_K_LMB_LAYER = 14, HZ_K_LMB_DEC = 15,
-       HZ_K_LMB_ADMIT = 16, /* 17: removed */ HZ_K_STEM = 18, HZ_K_BNECK = 19, HZ_K_SEAM = 20, HZ_K_KCONV = 21,
-       HZ_K_QKVATT = 22 };
+// ---- the kernel table: every launch a program can hold ----
+// argument records of the launchers that take scalars or a cfg beside their parameter struct
+typedef struct HzConvOp {
+  HzConvParams p;
+  int cfg, pad_;
+} HzConvOp;
+typedef struct HzConv2Op {
+  HzConvParams a, b;
+  int cfg, pad_;
+} HzConv2Op;
+typedef struct HzAvgpoolArgs {
+  const unsigned short* x;
+  unsigned short* out;
+  int N, HW, C, blocked;
+} HzAvgpoolArgs;
+typedef struct HzPreprocessArgs {
+  const void* src;
+  unsigned short* dst;
+  const float* mean;
+  const float* inv_std;
+  int N, Cin, H, W, Cpad, mode;
+} HzPreprocessArgs;
+typedef struct HzStepBumpArgs {
+  int* step;
+  int n, pad_;
+} HzStepBumpArgs;
+typedef struct HzDiagArgs {  // hz_diag_launch (csrc/diag.hip)
+  int kind, blocks, threads, pad_;
+  void* a;
+  void* b;
+  long bytes;
+} HzDiagArgs;
+// translation units holding device code (hz_plan_open warms the ones a plan's kernels live in)
+enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORMER = 8, HZ_UNIT_FP8 = 16,
+       HZ_UNIT_PACK = 32, HZ_UNIT_BLOCK = 64, HZ_UNIT_LSTM = 128, HZ_UNIT_LMBATCH = 256, HZ_UNIT_DIAG = 512 };
+// X(NAME, value, parameter struct, launcher, code unit): the ONE list of kinds. A launcher is
+// `int f(const Params*, hipStream_t)`; the *_op launchers are the adapters in runtime.cpp that unpack
+// an argument record. hz_launch_kernel, hz_kernel_param_size, hz_kernel_name, hz_kernel_code_unit and
+// the struct sizes in hz_abi_version are generated from it; hipzap/_native.py KINDS mirrors the values
+// (tests/test_kinds_cpu.py compares the two). Values are never reused: 17 (the persistent
+// dependent-conv chain) was removed in round 5, measured negative in round 3 (profiles/r3_chain).
+#define HZ_KERNELS(X)                                                     \
+  X(CONV, 1, HzConvOp, hz_conv_op, CONV)                                  \
+  X(LAYERNORM, 2, HzLayerNormParams, hz_layernorm_launch, TRANSFORMER)    \
+  X(EMBED, 3, HzEmbedParams, hz_embed_ln_launch, TRANSFORMER)             \
+  X(ATTENTION, 4, HzAttentionParams, hz_attention_launch, TRANSFORMER)    \
+  X(VIT_TOKENS, 5, HzVitTokensParams, hz_vit_tokens_launch, TRANSFORMER)  \
+  X(LSTM, 6, HzLstmParams, hz_lstm_cell_launch, LSTM)                     \
+  X(DECODER, 7, HzDecoderParams, hz_decoder_launch, LSTM)                 \
+  X(SAMPLER, 8, HzSamplerParams, hz_sampler_launch, LSTM)                 \
+  X(MAXPOOL, 9, HzPoolParams, hz_maxpool_launch, VISION)                  \
+  X(QUANT, 10, HzQuantParams, hz_quant_launch, FP8)                       \
+  X(GEMM_FP8, 11, HzGemmFp8Params, hz_gemm_fp8_launch, FP8)               \
+  X(SOFTMAX, 12, HzSoftmaxParams, hz_softmax_launch, TRANSFORMER)         \
+  X(POOL_FC, 13, HzPoolFcParams, hz_pool_fc_launch, VISION)               \
+  X(LMB_LAYER, 14, HzLmbLayerParams, hz_lmb_layer_launch, LMBATCH)        \
+  X(LMB_DEC, 15, HzLmbDecParams, hz_lmb_dec_launch, LMBATCH)              \
+  X(LMB_ADMIT, 16, HzLmbAdmitParams, hz_lmb_admit_launch, LMBATCH)        \
+  X(STEM, 18, HzStemParams, hz_stem_launch, BLOCK)                        \
+  X(BNECK, 19, HzBneckParams, hz_bneck_launch, BLOCK)                     \
+  X(SEAM, 20, HzSeamParams, hz_seam_launch, BLOCK)                        \
+  X(KCONV, 21, HzKconvParams, hz_kconv_launch, BLOCK)                     \
+  X(QKVATT, 22, HzQkvAttParams, hz_qkvatt_launch, TRANSFORMER)            \
+  X(CONV2, 23, HzConv2Op, hz_conv2_op, CONV)                              \
+  X(AVGPOOL, 24, HzAvgpoolArgs, hz_avgpool_op, VISION)                    \
+  X(PREPROCESS, 25, HzPreprocessArgs, hz_preprocess_op, VISION)           \
+  X(STEP_BUMP, 26, HzStepBumpArgs, hz_step_bump_op, LSTM)                 \
+  X(DIAG, 27, HzDiagArgs, hz_diag_op, DIAG)
+#define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
+enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
+#undef HZ_KERNEL_ENUM
 int hz_launch_kernel(int kind, const void* params, hipStream_t st);
 int hz_experiments(void);  // 1: built with HZ_EXPERIMENTS (measured-negative kernel variants)
 size_t hz_kernel_param_size(int kind);  // 0: unknown kind
-int hz_prog_add_kernel(HzProgram p, int kind, const void* params, size_t size, int slot);
+const char* hz_kernel_name(int kind);   // "HZ_K_<NAME>", NULL: unknown kind
+unsigned hz_kernel_code_unit(int kind); // HZ_UNIT_* of the kind's device code, 0: unknown kind
 
 // ---- runtime: static op programs, graph capture / replay ----
 HzProgram hz_prog_create(void);
 void hz_prog_destroy(HzProgram p);
 int hz_prog_num_ops(HzProgram p);
-int hz_prog_add_conv(HzProgram p, const HzConvParams* cp, int cfg, int slot);
-int hz_prog_add_conv2(HzProgram p, const HzConvParams* a, const HzConvParams* b, int cfg, int slot);
-int hz_prog_add_maxpool(HzProgram p, const HzPoolParams* pp, int slot);
-int hz_prog_add_avgpool(HzProgram p, const unsigned short* x, unsigned short* out, int N, int HW, int C, int blocked,
-                        int slot);
-int hz_prog_add_preprocess(HzProgram p, const void* src, unsigned short* dst, int N, int Cin, int H, int W,
-                           int Cpad, int mode, const float* mean, const float* inv_std, int slot);
+// a launch of `kind`: the parameter block (at least hz_kernel_param_size(kind) bytes) is copied
+int hz_prog_add_kernel(HzProgram p, int kind, const void* params, size_t size, int slot);
 int hz_prog_add_memcpy(HzProgram p, void* dst, const void* src, size_t bytes, int slot);  // any direction (UVA)
-int hz_prog_add_lstm(HzProgram p, const HzLstmParams* lp, int slot);
-int hz_prog_add_decoder(HzProgram p, const HzDecoderParams* dp, int slot);
-int hz_prog_add_sampler(HzProgram p, const HzSamplerParams* sp, int slot);
-int hz_prog_add_step_bump(HzProgram p, int* step, int n, int slot);
 int hz_prog_add_fork(HzProgram p, int slot);   // side stream `slot` waits for main
 int hz_prog_add_join(HzProgram p, int slot);   // main waits for side stream `slot`
 int hz_prog_run(HzProgram p, hipStream_t st);  // eager launch of every op
@@ -546,27 +600,12 @@ int hz_serve_bench(HzProgram* progs, hipStream_t* streams, void** in_dst, void**
                    double* wall_us);
 // diagnostics (csrc/diag.hip): kind 0 = no-op kernel, 1 = copy `bytes` from a to b
 int hz_diag_launch(int kind, int blocks, int threads, void* a, void* b, long bytes, hipStream_t st);
-int hz_prog_add_diag(HzProgram p, int kind, int blocks, int threads, void* a, void* b, long bytes, int slot);
 
 // ---- plan images (csrc/plan.cpp, engine/plan.py): serialised bound programs ----
 // bump HZ_ABI_EPOCH when a kernel's parameter SEMANTICS change without a size change
 #define HZ_ABI_EPOCH 2
-enum { HZ_PLAN_OP_CONV = 1, HZ_PLAN_OP_CONV2 = 2, HZ_PLAN_OP_MAXPOOL = 3, HZ_PLAN_OP_AVGPOOL = 4,
-       HZ_PLAN_OP_PREPROCESS = 5, HZ_PLAN_OP_MEMCPY = 6, HZ_PLAN_OP_KERNEL = 7, HZ_PLAN_OP_FORK = 8,
-       HZ_PLAN_OP_JOIN = 9 };
-// argument records of the ops whose hz_prog_add_* takes scalars
-typedef struct HzAvgpoolArgs {
-  const unsigned short* x;
-  unsigned short* out;
-  int N, HW, C, blocked;
-} HzAvgpoolArgs;
-typedef struct HzPreprocessArgs {
-  const void* src;
-  unsigned short* dst;
-  const float* mean;
-  const float* inv_std;
-  int N, Cin, H, W, Cpad, mode;
-} HzPreprocessArgs;
+// op types of a plan image (1..5 were the per-op types of format version 1)
+enum { HZ_PLAN_OP_MEMCPY = 6, HZ_PLAN_OP_KERNEL = 7, HZ_PLAN_OP_FORK = 8, HZ_PLAN_OP_JOIN = 9 };
 typedef struct HzMemcpyArgs {
   void* dst;
   const void* src;

@@ -27,12 +27,13 @@
 
 namespace {
 
-constexpr uint32_t kPlanVersion = 1;
+// 2: every launch is a KERNEL op of the kernel table (version 1 had per-op types for the convs, pools
+// and preprocess, with the conv cfg in the op header)
+constexpr uint32_t kPlanVersion = 2;
 // flags: the file carries no weight bytes (a template: engine/plan.py export_template); the blob
 // is filled by the caller, e.g. by packing a .pth checkpoint on the device (csrc/pack.hip)
 constexpr uint64_t kFlagWeightless = 1;
 constexpr char kMagic[8] = {'H', 'Z', 'P', 'L', 'A', 'N', '0', '1'};
-enum : unsigned { kUnitConv = 1, kUnitVision = 2, kUnitGemm = 4, kUnitTransformer = 8, kUnitFp8 = 16, kUnitPack = 32, kUnitBlock = 64 };
 
 // file header: magic + 15 little-endian u64 fields (see plan.py PlanHeader)
 struct FileHeader {
@@ -48,7 +49,7 @@ static_assert(sizeof(FileHeader) == 128, "plan header is 128 bytes");
 
 struct OpHeader {  // followed by plen param bytes (padded to 8) and nrel relocations
   uint32_t type;
-  int32_t arg;   // conv cfg or kernel kind
+  int32_t arg;   // KERNEL: the kind (HZ_K_*)
   int32_t slot;
   uint32_t plen;
   uint32_t nrel;
@@ -202,33 +203,11 @@ struct Plan {
   unsigned code_units() const {
     unsigned u = 0;
     for (const PlanOp& op : ops) {
-      switch (op.h.type) {
-        case HZ_PLAN_OP_CONV: u |= op.h.arg >= 16 ? kUnitGemm : kUnitConv; break;
-        case HZ_PLAN_OP_CONV2: u |= kUnitConv; break;
-        case HZ_PLAN_OP_MAXPOOL:
-        case HZ_PLAN_OP_AVGPOOL:
-        case HZ_PLAN_OP_PREPROCESS: u |= kUnitVision; break;
-        case HZ_PLAN_OP_KERNEL:
-          switch (op.h.arg) {
-            case HZ_K_LAYERNORM:
-            case HZ_K_EMBED:
-            case HZ_K_ATTENTION:
-            case HZ_K_QKVATT:
-            case HZ_K_VIT_TOKENS:
-            case HZ_K_SOFTMAX: u |= kUnitTransformer; break;
-            case HZ_K_GEMM_FP8:
-            case HZ_K_QUANT: u |= kUnitFp8; break;
-            case HZ_K_MAXPOOL:
-            case HZ_K_POOL_FC: u |= kUnitVision; break;
-            case HZ_K_STEM:
-            case HZ_K_BNECK:
-            case HZ_K_SEAM:
-            case HZ_K_KCONV: u |= kUnitBlock; break;
-            default: break;
-          }
-          break;
-        default: break;
-      }
+      if (op.h.type != HZ_PLAN_OP_KERNEL) continue;
+      // the one data-dependent case: a conv on an LDS tile (cfg >= 16) is gemm.hip's
+      int cfg = 0;
+      if (op.h.arg == HZ_K_CONV) std::memcpy(&cfg, op.prm + offsetof(HzConvOp, cfg), sizeof(cfg));
+      u |= cfg >= 16 ? HZ_UNIT_GEMM : hz_kernel_code_unit(op.h.arg);
     }
     return u;
   }
@@ -261,11 +240,6 @@ struct Plan {
       // every op reads a whole parameter struct from its record
       size_t need = 0;
       switch (op.h.type) {
-        case HZ_PLAN_OP_CONV: need = sizeof(HzConvParams); break;
-        case HZ_PLAN_OP_CONV2: need = 2 * sizeof(HzConvParams); break;
-        case HZ_PLAN_OP_MAXPOOL: need = sizeof(HzPoolParams); break;
-        case HZ_PLAN_OP_AVGPOOL: need = sizeof(HzAvgpoolArgs); break;
-        case HZ_PLAN_OP_PREPROCESS: need = sizeof(HzPreprocessArgs); break;
         case HZ_PLAN_OP_MEMCPY: need = sizeof(HzMemcpyArgs); break;
         case HZ_PLAN_OP_KERNEL: need = hz_kernel_param_size(op.h.arg); break;
         case HZ_PLAN_OP_FORK:
@@ -369,28 +343,6 @@ struct Plan {
       const void* prm = buf.data();
       int rc = 0;
       switch (op.h.type) {
-        case HZ_PLAN_OP_CONV:
-          rc = hz_prog_add_conv(c.prog, static_cast<const HzConvParams*>(prm), op.h.arg, op.h.slot);
-          break;
-        case HZ_PLAN_OP_CONV2: {
-          const HzConvParams* a = static_cast<const HzConvParams*>(prm);
-          rc = hz_prog_add_conv2(c.prog, a, a + 1, op.h.arg, op.h.slot);
-          break;
-        }
-        case HZ_PLAN_OP_MAXPOOL:
-          rc = hz_prog_add_maxpool(c.prog, static_cast<const HzPoolParams*>(prm), op.h.slot);
-          break;
-        case HZ_PLAN_OP_AVGPOOL: {
-          const HzAvgpoolArgs* a = static_cast<const HzAvgpoolArgs*>(prm);
-          rc = hz_prog_add_avgpool(c.prog, a->x, a->out, a->N, a->HW, a->C, a->blocked, op.h.slot);
-          break;
-        }
-        case HZ_PLAN_OP_PREPROCESS: {
-          const HzPreprocessArgs* a = static_cast<const HzPreprocessArgs*>(prm);
-          rc = hz_prog_add_preprocess(c.prog, a->src, a->dst, a->N, a->Cin, a->H, a->W, a->Cpad, a->mode, a->mean,
-                                      a->inv_std, op.h.slot);
-          break;
-        }
         case HZ_PLAN_OP_MEMCPY: {
           const HzMemcpyArgs* a = static_cast<const HzMemcpyArgs*>(prm);
           rc = hz_prog_add_memcpy(c.prog, a->dst, a->src, a->bytes, op.h.slot);
@@ -487,31 +439,14 @@ int capture_ctx_prog(Plan* p, const PlanCtx& c) {
 extern "C" {
 
 uint64_t hz_abi_version(void) {
-  // FNV-1a over the plan format version and every struct a plan serialises: a library whose
-  // parameter layouts changed refuses old plans instead of launching garbage
+  // FNV-1a over the plan format version and every struct a plan serialises (each kind's value and
+  // parameter struct, from the kernel table): a library whose parameter layouts changed refuses old
+  // plans instead of launching garbage
   const uint64_t parts[] = {kPlanVersion,
-                            sizeof(HzConvParams),
-                            sizeof(HzPoolParams),
-                            sizeof(HzPoolFcParams),
-                            sizeof(HzLayerNormParams),
-                            sizeof(HzEmbedParams),
-                            sizeof(HzAttentionParams),
-                            sizeof(HzVitTokensParams),
-                            sizeof(HzSoftmaxParams),
-                            sizeof(HzQuantParams),
-                            sizeof(HzGemmFp8Params),
-                            sizeof(HzLstmParams),
-                            sizeof(HzDecoderParams),
-                            sizeof(HzSamplerParams),
-                            sizeof(HzAvgpoolArgs),
-                            sizeof(HzPreprocessArgs),
-                            sizeof(HzMemcpyArgs),
-                            sizeof(HzStemParams),
-                            sizeof(HzBneckParams),
-                            sizeof(HzSeamParams),
-                            sizeof(HzKconvParams),
-                            sizeof(HzQkvAttParams),
-                            HZ_ABI_EPOCH};
+#define X(NAME, value, T, fn, unit) value, sizeof(T),
+                            HZ_KERNELS(X)
+#undef X
+                            sizeof(HzMemcpyArgs), HZ_ABI_EPOCH};
   uint64_t x = 1469598103934665603ull;
   for (uint64_t v : parts) {
     x ^= v;
@@ -590,18 +525,18 @@ void* hz_plan_open(const char* path, int device, int read_blob, double* timings)
   const bool warm_on = !(cw && cw[0] == '0');
   const bool warm_early = !(wo && std::strcmp(wo, "stream") == 0);
   auto start_warm = [&]() {
-    const unsigned units = p->code_units() | ((p->h.flags & kFlagWeightless) ? kUnitPack : 0u);
+    const unsigned units = p->code_units() | ((p->h.flags & kFlagWeightless) ? HZ_UNIT_PACK : 0u);
     double* t_warm = &p->t[HZ_PLAN_T_WARM_THREAD];  // written by the thread, read after the join
     p->warm = std::thread([device, units, t_warm] {
       const double w0 = now_ms();
       if (hipSetDevice(device) != hipSuccess) return;
-      if (units & kUnitConv) (void)hz_conv_code_warm();
-      if (units & kUnitVision) (void)hz_vision_code_warm();
-      if (units & kUnitGemm) (void)hz_gemm_code_warm();
-      if (units & kUnitTransformer) (void)hz_transformer_code_warm();
-      if (units & kUnitFp8) (void)hz_fp8_code_warm();
-      if (units & kUnitPack) (void)hz_pack_code_warm();
-      if (units & kUnitBlock) (void)hz_block_code_warm();
+      if (units & HZ_UNIT_CONV) (void)hz_conv_code_warm();
+      if (units & HZ_UNIT_VISION) (void)hz_vision_code_warm();
+      if (units & HZ_UNIT_GEMM) (void)hz_gemm_code_warm();
+      if (units & HZ_UNIT_TRANSFORMER) (void)hz_transformer_code_warm();
+      if (units & HZ_UNIT_FP8) (void)hz_fp8_code_warm();
+      if (units & HZ_UNIT_PACK) (void)hz_pack_code_warm();
+      if (units & HZ_UNIT_BLOCK) (void)hz_block_code_warm();
       *t_warm = now_ms() - w0;
     });
   };

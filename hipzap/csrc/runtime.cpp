@@ -13,8 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <memory>
 #include <thread>
 #include <vector>
 
@@ -25,8 +23,9 @@ namespace {
 
 struct Op {
   int slot;  // 0 = main stream, k>0 = side stream k
-  enum Kind { LAUNCH, FORK, JOIN } kind;
-  std::function<int(hipStream_t)> fn;
+  enum Type { KERNEL, MEMCPY, FORK, JOIN } type;
+  int kind;               // KERNEL: HZ_K_*
+  std::vector<char> prm;  // KERNEL: the kind's parameter block; MEMCPY: HzMemcpyArgs (captured by value)
 };
 
 struct Program {
@@ -57,7 +56,7 @@ struct Program {
     // HIP object on the host side, which is what the host-sanitizer test relies on)
     while (fork_ev.size() < ops.size()) {
       hipEvent_t e = nullptr;
-      if (ops[fork_ev.size()].kind != Op::LAUNCH &&
+      if (ops[fork_ev.size()].type >= Op::FORK &&
           hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
         return -1;
       fork_ev.push_back(e);
@@ -71,19 +70,31 @@ struct Program {
       Op& op = ops[i];
       hipStream_t s = op.slot == 0 ? main : side[op.slot - 1];
       int rc = 0;
-      switch (op.kind) {
-        case Op::LAUNCH: rc = op.fn(s); break;
+      const char* what = "";
+      switch (op.type) {
+        case Op::KERNEL:
+          what = hz_kernel_name(op.kind);
+          rc = hz_launch_kernel(op.kind, op.prm.data(), s);
+          break;
+        case Op::MEMCPY: {
+          const HzMemcpyArgs* m = reinterpret_cast<const HzMemcpyArgs*>(op.prm.data());
+          what = "memcpy";
+          rc = (int)hipMemcpyAsync(m->dst, m->src, m->bytes, hipMemcpyDefault, s);
+          break;
+        }
         case Op::FORK:  // side waits for main
+          what = "fork";
           rc = (int)hipEventRecord(fork_ev[i], main);
           if (!rc) rc = (int)hipStreamWaitEvent(side[op.slot - 1], fork_ev[i], 0);
           break;
         case Op::JOIN:  // main waits for side
+          what = "join";
           rc = (int)hipEventRecord(fork_ev[i], side[op.slot - 1]);
           if (!rc) rc = (int)hipStreamWaitEvent(main, fork_ev[i], 0);
           break;
       }
       if (rc) {
-        fprintf(stderr, "hipzap: program op %zu failed rc=%d\n", i, rc);
+        fprintf(stderr, "hipzap: program op %zu (%s) failed rc=%d\n", i, what, rc);
         return rc;
       }
     }
@@ -111,65 +122,33 @@ HzProgram hz_prog_create(void) { return new Program(); }
 void hz_prog_destroy(HzProgram p) { delete static_cast<Program*>(p); }
 int hz_prog_num_ops(HzProgram p) { return (int)static_cast<Program*>(p)->ops.size(); }
 
-static int add_op(Program* P, int slot, Op::Kind kind, std::function<int(hipStream_t)> fn) {
+static int add_op(Program* P, int slot, Op::Type type, int kind = 0, const void* prm = nullptr, size_t size = 0) {
   if (P->exec) return -3;  // frozen after capture
   if (slot < 0 || slot > 8) return -4;
   if (slot > P->max_slot) P->max_slot = slot;
-  P->ops.push_back(Op{slot, kind, std::move(fn)});
+  const char* b = static_cast<const char*>(prm);
+  P->ops.push_back(Op{slot, type, kind, std::vector<char>(b, b + size)});
   return 0;
 }
 
-int hz_prog_add_conv(HzProgram h, const HzConvParams* cp, int cfg, int slot) {
-  HzConvParams c = *cp;
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH,
-                [c, cfg](hipStream_t s) { return hz_conv_launch(&c, cfg, s); });
-}
-int hz_prog_add_conv2(HzProgram h, const HzConvParams* a, const HzConvParams* b, int cfg, int slot) {
-  HzConvParams c0 = *a, c1 = *b;
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH,
-                [c0, c1, cfg](hipStream_t s) { return hz_conv2_launch(&c0, &c1, cfg, s); });
-}
-int hz_prog_add_maxpool(HzProgram h, const HzPoolParams* pp, int slot) {
-  HzPoolParams c = *pp;
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH, [c](hipStream_t s) { return hz_maxpool_launch(&c, s); });
-}
-int hz_prog_add_avgpool(HzProgram h, const unsigned short* x, unsigned short* out, int N, int HW, int C, int blocked,
-                        int slot) {
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH,
-                [=](hipStream_t s) { return hz_avgpool_launch(x, out, N, HW, C, blocked, s); });
-}
-int hz_prog_add_preprocess(HzProgram h, const void* src, unsigned short* dst, int N, int Cin, int H, int W, int Cpad,
-                           int mode, const float* mean, const float* inv_std, int slot) {
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH, [=](hipStream_t s) {
-    return hz_preprocess_launch(src, dst, N, Cin, H, W, Cpad, mode, mean, inv_std, s);
-  });
+int hz_prog_add_kernel(HzProgram h, int kind, const void* params, size_t size, int slot) {
+  // the launcher reads a whole parameter struct: refuse unknown kinds and short records (a plan
+  // image's op record, for instance) instead of reading past them when the op is replayed
+  const size_t need = hz_kernel_param_size(kind);
+  if (!need || size < need) return -101;
+  return add_op(static_cast<Program*>(h), slot, Op::KERNEL, kind, params, size);
 }
 int hz_prog_add_memcpy(HzProgram h, void* dst, const void* src, size_t bytes, int slot) {
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH,
-                [=](hipStream_t s) { return (int)hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, s); });
-}
-int hz_prog_add_lstm(HzProgram h, const HzLstmParams* lp, int slot) {
-  HzLstmParams c = *lp;
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH, [c](hipStream_t s) { return hz_lstm_cell_launch(&c, s); });
-}
-int hz_prog_add_decoder(HzProgram h, const HzDecoderParams* dp, int slot) {
-  HzDecoderParams c = *dp;
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH, [c](hipStream_t s) { return hz_decoder_launch(&c, s); });
-}
-int hz_prog_add_sampler(HzProgram h, const HzSamplerParams* sp, int slot) {
-  HzSamplerParams c = *sp;
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH, [c](hipStream_t s) { return hz_sampler_launch(&c, s); });
-}
-int hz_prog_add_step_bump(HzProgram h, int* step, int n, int slot) {
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH, [=](hipStream_t s) { return hz_step_bump_launch(step, n, s); });
+  const HzMemcpyArgs m = {dst, src, bytes};
+  return add_op(static_cast<Program*>(h), slot, Op::MEMCPY, 0, &m, sizeof(m));
 }
 int hz_prog_add_fork(HzProgram h, int slot) {
   if (slot < 1) return -4;
-  return add_op(static_cast<Program*>(h), slot, Op::FORK, nullptr);
+  return add_op(static_cast<Program*>(h), slot, Op::FORK);
 }
 int hz_prog_add_join(HzProgram h, int slot) {
   if (slot < 1) return -4;
-  return add_op(static_cast<Program*>(h), slot, Op::JOIN, nullptr);
+  return add_op(static_cast<Program*>(h), slot, Op::JOIN);
 }
 
 int hz_prog_run(HzProgram h, hipStream_t st) { return static_cast<Program*>(h)->run(st); }
@@ -220,11 +199,6 @@ double hz_prog_bench(HzProgram* progs, hipStream_t* streams, int n, int iters) {
     if (hipStreamSynchronize(streams[i]) != hipSuccess) return -2.0;
   auto t1 = std::chrono::steady_clock::now();
   return std::chrono::duration<double, std::micro>(t1 - t0).count();
-}
-
-int hz_prog_add_diag(HzProgram h, int kind, int blocks, int threads, void* a, void* b, long bytes, int slot) {
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH,
-                [=](hipStream_t s) { return hz_diag_launch(kind, blocks, threads, a, b, bytes, s); });
 }
 
 // out[0] = host submission time (us), out[1] = submission + drain (us).
@@ -299,28 +273,27 @@ extern "C" int hz_prog_replay_n(HzProgram h, hipStream_t st, int n) {
   return 0;
 }
 
+// adapters: the kinds whose launcher takes scalars or a cfg beside its parameter struct
+static int hz_conv_op(const HzConvOp* o, hipStream_t st) { return hz_conv_launch(&o->p, o->cfg, st); }
+static int hz_conv2_op(const HzConv2Op* o, hipStream_t st) { return hz_conv2_launch(&o->a, &o->b, o->cfg, st); }
+static int hz_avgpool_op(const HzAvgpoolArgs* a, hipStream_t st) {
+  return hz_avgpool_launch(a->x, a->out, a->N, a->HW, a->C, a->blocked, st);
+}
+static int hz_preprocess_op(const HzPreprocessArgs* a, hipStream_t st) {
+  return hz_preprocess_launch(a->src, a->dst, a->N, a->Cin, a->H, a->W, a->Cpad, a->mode, a->mean, a->inv_std, st);
+}
+static int hz_step_bump_op(const HzStepBumpArgs* a, hipStream_t st) { return hz_step_bump_launch(a->step, a->n, st); }
+static int hz_diag_op(const HzDiagArgs* a, hipStream_t st) {
+  return hz_diag_launch(a->kind, a->blocks, a->threads, a->a, a->b, a->bytes, st);
+}
+
+// everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {
   switch (kind) {
-    case HZ_K_LAYERNORM: return hz_layernorm_launch(static_cast<const HzLayerNormParams*>(prm), st);
-    case HZ_K_EMBED: return hz_embed_ln_launch(static_cast<const HzEmbedParams*>(prm), st);
-    case HZ_K_ATTENTION: return hz_attention_launch(static_cast<const HzAttentionParams*>(prm), st);
-    case HZ_K_VIT_TOKENS: return hz_vit_tokens_launch(static_cast<const HzVitTokensParams*>(prm), st);
-    case HZ_K_LSTM: return hz_lstm_cell_launch(static_cast<const HzLstmParams*>(prm), st);
-    case HZ_K_DECODER: return hz_decoder_launch(static_cast<const HzDecoderParams*>(prm), st);
-    case HZ_K_SAMPLER: return hz_sampler_launch(static_cast<const HzSamplerParams*>(prm), st);
-    case HZ_K_MAXPOOL: return hz_maxpool_launch(static_cast<const HzPoolParams*>(prm), st);
-    case HZ_K_QUANT: return hz_quant_launch(static_cast<const HzQuantParams*>(prm), st);
-    case HZ_K_GEMM_FP8: return hz_gemm_fp8_launch(static_cast<const HzGemmFp8Params*>(prm), st);
-    case HZ_K_SOFTMAX: return hz_softmax_launch(static_cast<const HzSoftmaxParams*>(prm), st);
-    case HZ_K_POOL_FC: return hz_pool_fc_launch(static_cast<const HzPoolFcParams*>(prm), st);
-    case HZ_K_LMB_LAYER: return hz_lmb_layer_launch(static_cast<const HzLmbLayerParams*>(prm), st);
-    case HZ_K_LMB_DEC: return hz_lmb_dec_launch(static_cast<const HzLmbDecParams*>(prm), st);
-    case HZ_K_LMB_ADMIT: return hz_lmb_admit_launch(static_cast<const HzLmbAdmitParams*>(prm), st);
-    case HZ_K_QKVATT: return hz_qkvatt_launch(static_cast<const HzQkvAttParams*>(prm), st);
-    case HZ_K_STEM: return hz_stem_launch(static_cast<const HzStemParams*>(prm), st);
-    case HZ_K_BNECK: return hz_bneck_launch(static_cast<const HzBneckParams*>(prm), st);
-    case HZ_K_SEAM: return hz_seam_launch(static_cast<const HzSeamParams*>(prm), st);
-    case HZ_K_KCONV: return hz_kconv_launch(static_cast<const HzKconvParams*>(prm), st);
+#define X(NAME, value, T, fn, unit) \
+  case value: return fn(static_cast<const T*>(prm), st);
+    HZ_KERNELS(X)
+#undef X
     default: return -100;
   }
 }
@@ -328,36 +301,30 @@ extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {
 // bytes of the parameter struct hz_launch_kernel reads for `kind` (0: unknown kind)
 extern "C" size_t hz_kernel_param_size(int kind) {
   switch (kind) {
-    case HZ_K_LAYERNORM: return sizeof(HzLayerNormParams);
-    case HZ_K_EMBED: return sizeof(HzEmbedParams);
-    case HZ_K_ATTENTION: return sizeof(HzAttentionParams);
-    case HZ_K_VIT_TOKENS: return sizeof(HzVitTokensParams);
-    case HZ_K_LSTM: return sizeof(HzLstmParams);
-    case HZ_K_DECODER: return sizeof(HzDecoderParams);
-    case HZ_K_SAMPLER: return sizeof(HzSamplerParams);
-    case HZ_K_MAXPOOL: return sizeof(HzPoolParams);
-    case HZ_K_QUANT: return sizeof(HzQuantParams);
-    case HZ_K_GEMM_FP8: return sizeof(HzGemmFp8Params);
-    case HZ_K_SOFTMAX: return sizeof(HzSoftmaxParams);
-    case HZ_K_POOL_FC: return sizeof(HzPoolFcParams);
-    case HZ_K_LMB_LAYER: return sizeof(HzLmbLayerParams);
-    case HZ_K_LMB_DEC: return sizeof(HzLmbDecParams);
-    case HZ_K_LMB_ADMIT: return sizeof(HzLmbAdmitParams);
-    case HZ_K_QKVATT: return sizeof(HzQkvAttParams);
-    case HZ_K_STEM: return sizeof(HzStemParams);
-    case HZ_K_BNECK: return sizeof(HzBneckParams);
-    case HZ_K_SEAM: return sizeof(HzSeamParams);
-    case HZ_K_KCONV: return sizeof(HzKconvParams);
+#define X(NAME, value, T, fn, unit) \
+  case value: return sizeof(T);
+    HZ_KERNELS(X)
+#undef X
     default: return 0;
   }
 }
 
-extern "C" int hz_prog_add_kernel(HzProgram h, int kind, const void* params, size_t size, int slot) {
-  // the launcher reads a whole parameter struct: refuse unknown kinds and short records (a plan
-  // image's op record, for instance) instead of reading past them when the op is replayed
-  const size_t need = hz_kernel_param_size(kind);
-  if (!need || size < need) return -101;
-  auto buf = std::make_shared<std::vector<char>>(static_cast<const char*>(params), static_cast<const char*>(params) + size);
-  return add_op(static_cast<Program*>(h), slot, Op::LAUNCH,
-                [buf, kind](hipStream_t s) { return hz_launch_kernel(kind, buf->data(), s); });
+extern "C" const char* hz_kernel_name(int kind) {
+  switch (kind) {
+#define X(NAME, value, T, fn, unit) \
+  case value: return "HZ_K_" #NAME;
+    HZ_KERNELS(X)
+#undef X
+    default: return nullptr;
+  }
+}
+
+extern "C" unsigned hz_kernel_code_unit(int kind) {
+  switch (kind) {
+#define X(NAME, value, T, fn, unit) \
+  case value: return HZ_UNIT_##unit;
+    HZ_KERNELS(X)
+#undef X
+    default: return 0;
+  }
 }

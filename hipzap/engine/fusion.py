@@ -46,7 +46,7 @@ import numpy as np
 
 from .. import _native as N
 
-HZ_K_STEM, HZ_K_BNECK, HZ_K_SEAM, HZ_K_KCONV = 18, 19, 20, 21
+HZ_K_STEM, HZ_K_BNECK, HZ_K_SEAM, HZ_K_KCONV = N.HZ_K_STEM, N.HZ_K_BNECK, N.HZ_K_SEAM, N.HZ_K_KCONV
 KINDS = ("stem", "convpool", "bneck", "bneck2", "seam", "kconv", "tail", "xseam", "dsseam")
 # measured default (profiles/r4_fuse/README.md: served 11.3k -> 13.4k inf/s on one box; round 5
 # adds the layer3/layer4 seams + K-split 3x3 convs: 13.5-13.6k -> 14.2k same box, and the pooling
@@ -55,6 +55,7 @@ KINDS = ("stem", "convpool", "bneck", "bneck2", "seam", "kconv", "tail", "xseam"
 DEFAULT = "convpool,bneck,bneck2,seam,kconv,tail,xseam"
 
 
+@N.params_of("HZ_K_STEM")
 class StemParams(C.Structure):  # HzStemParams (csrc/hipzap.h)
     _fields_ = [("src", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
                 ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("mode", C.c_int),
@@ -62,6 +63,7 @@ class StemParams(C.Structure):  # HzStemParams (csrc/hipzap.h)
                 ("norm", C.c_int), ("pad_", C.c_int), ("mean", C.c_float * 4), ("inv_std", C.c_float * 4)]
 
 
+@N.params_of("HZ_K_BNECK")
 class BneckParams(C.Structure):  # HzBneckParams
     _fields_ = [("x", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p),
                 ("b2", C.c_void_p), ("w3", C.c_void_p), ("b3", C.c_void_p), ("wd", C.c_void_p),
@@ -69,6 +71,7 @@ class BneckParams(C.Structure):  # HzBneckParams
                 ("Cin", C.c_int), ("Cmid", C.c_int), ("Cout", C.c_int), ("tile_h", C.c_int), ("imgs", C.c_int)]
 
 
+@N.params_of("HZ_K_SEAM")
 class SeamParams(C.Structure):  # HzSeamParams
     _fields_ = [("t2", C.c_void_p), ("w3", C.c_void_p), ("b3", C.c_void_p), ("res", C.c_void_p),
                 ("y", C.c_void_p), ("w1", C.c_void_p), ("z", C.c_void_p), ("N", C.c_int), ("HW", C.c_int),
@@ -78,6 +81,7 @@ class SeamParams(C.Structure):  # HzSeamParams
                 ("xd_H", C.c_int), ("xd_W", C.c_int)]
 
 
+@N.params_of("HZ_K_KCONV")
 class KconvParams(C.Structure):  # HzKconvParams
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("out", C.c_void_p), ("zinit", C.c_void_p),
                 ("zbias", C.c_void_p), ("z_C", C.c_int), ("z_HW", C.c_int), ("N", C.c_int), ("H", C.c_int),
@@ -692,7 +696,7 @@ def add_fused(prog, g, params, f: Fused, addr, lib, fused: dict | None = None) -
         prm, kind = kconv_params(g, params, f, addr, fused or {}), HZ_K_KCONV
     else:
         prm, kind = bneck_params(g, params, f, addr), HZ_K_BNECK
-    N.check(lib.hz_prog_add_kernel(prog, kind, C.byref(prm), C.sizeof(prm), f.nodes[0].slot), f"add_{f.kind}")
+    N.prog_add(lib, prog, kind, prm, f.nodes[0].slot, f"add_{f.kind}")
     names = "+".join(str(n.attrs.get("name", n.kind)) for n in f.nodes)
     return (names, f"fused:{f.kind}", -1, 0)
 

@@ -227,9 +227,9 @@ class LMEngine:
                 self._final = N.SamplerParams.from_buffer_copy(s)
                 self._final.step_off = -1
             # one step's ops in order (diagnostics: scripts/diag_lm.py)
-            self._ops = [("lstm", prm) for prm in lstm_prms] + [("decoder", d)]
+            self._ops = [(N.HZ_K_LSTM, prm) for prm in lstm_prms] + [(N.HZ_K_DECODER, d)]
             if not self.fused_sampler:
-                self._ops.append(("sampler", s))
+                self._ops.append((N.HZ_K_SAMPLER, s))
 
             def build(reps):
                 prog = lib.hz_prog_create()
@@ -237,10 +237,8 @@ class LMEngine:
                     for kind, prm in self._ops:
                         q = type(prm).from_buffer_copy(prm)
                         q.step_off = u
-                        add = {"lstm": lib.hz_prog_add_lstm, "decoder": lib.hz_prog_add_decoder,
-                               "sampler": lib.hz_prog_add_sampler}[kind]
-                        N.check(add(prog, C.byref(q), 0), "add_" + kind)
-                N.check(lib.hz_prog_add_step_bump(prog, self.step.data_ptr(), reps, 0), "add_step_bump")
+                        N.prog_add(lib, prog, kind, q, 0, f"add lm kernel {kind}")
+                N.prog_add(lib, prog, N.HZ_K_STEP_BUMP, N.StepBumpArgs(self.step.data_ptr(), reps), 0, "add_step_bump")
                 if capture:
                     N.check(lib.hz_prog_capture(prog, self.stream.cuda_stream), "capture")
                 return prog

@@ -244,14 +244,14 @@ class LmbCore:
             prog = lib.hz_prog_create()
             ak = N.LmbAdmitParams.from_buffer_copy(a)
             ak.block = self.blocks[k]
-            N.check(lib.hz_prog_add_kernel(prog, N.HZ_K_LMB_ADMIT, C.byref(ak), C.sizeof(ak), 0), "add lmb admit")
+            N.prog_add(lib, prog, N.HZ_K_LMB_ADMIT, ak, 0, "add lmb admit")
             for u in range(U):
                 for kind, prm in self._ops:
                     q = type(prm).from_buffer_copy(prm)
                     q.step_off, q.nb_act = u, nb_act
                     if kind == N.HZ_K_LMB_DEC and self.logits_bufs:
                         q.logits = self.logits_bufs[k]
-                    N.check(lib.hz_prog_add_kernel(prog, kind, C.byref(q), C.sizeof(q), 0), f"add lmb kernel {kind}")
+                    N.prog_add(lib, prog, kind, q, 0, f"add lmb kernel {kind}")
             return prog
 
         self._admit = a

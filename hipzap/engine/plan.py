@@ -29,30 +29,20 @@ import struct
 import torch
 
 from .. import _native as N
+from ..lite import PLAN_VERSION
 from ..models import registry
 from .engine import add_softmax_head, load_tuning
 from .program import ExecContext
 
 PLAN_SUFFIX = ".hzplan"
 MAGIC = b"HZPLAN01"
-VERSION = 1
+VERSION = PLAN_VERSION
 HEADER = struct.Struct("<8s15Q")  # csrc/plan.cpp FileHeader
 OPHDR = struct.Struct("<IiiIII")   # OpHeader
 RELOC = struct.Struct("<IIQ")      # Reloc
-OP_CONV, OP_CONV2, OP_MAXPOOL, OP_AVGPOOL, OP_PREPROCESS, OP_MEMCPY, OP_KERNEL, OP_FORK, OP_JOIN = range(1, 10)
+OP_MEMCPY, OP_KERNEL, OP_FORK, OP_JOIN = 6, 7, 8, 9  # csrc/hipzap.h HZ_PLAN_OP_*
 BLOB_ALIGN = 4096
 FLAG_WEIGHTLESS = 1  # csrc/plan.cpp kFlagWeightless
-
-
-class AvgpoolArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("N", C.c_int), ("HW", C.c_int), ("C", C.c_int),
-                ("blocked", C.c_int)]
-
-
-class PreprocessArgs(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("mean", C.c_void_p), ("inv_std", C.c_void_p),
-                ("N", C.c_int), ("Cin", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cpad", C.c_int),
-                ("mode", C.c_int)]
 
 
 class MemcpyArgs(C.Structure):
@@ -90,21 +80,6 @@ class PlanRecorder:
         self.ops.append((t, int(arg), int(slot), [_obj(s) for s in structs]))
         return 0
 
-    def hz_prog_add_conv(self, prog, prm, cfg, slot):
-        return self._add(OP_CONV, cfg, slot, prm)
-
-    def hz_prog_add_conv2(self, prog, a, b, cfg, slot):
-        return self._add(OP_CONV2, cfg, slot, a, b)
-
-    def hz_prog_add_maxpool(self, prog, prm, slot):
-        return self._add(OP_MAXPOOL, 0, slot, prm)
-
-    def hz_prog_add_avgpool(self, prog, x, out, n, hw, c, blocked, slot):
-        return self._add(OP_AVGPOOL, 0, slot, AvgpoolArgs(x, out, n, hw, c, blocked))
-
-    def hz_prog_add_preprocess(self, prog, src, dst, n, cin, h, w, cpad, mode, mean, inv_std, slot):
-        return self._add(OP_PREPROCESS, 0, slot, PreprocessArgs(src, dst, mean, inv_std, n, cin, h, w, cpad, mode))
-
     def hz_prog_add_memcpy(self, prog, dst, src, nbytes, slot):
         return self._add(OP_MEMCPY, 0, slot, MemcpyArgs(dst, src, nbytes))
 
@@ -121,13 +96,16 @@ class PlanRecorder:
 
 
 def _pointer_fields(st) -> list[tuple[int, int]]:
-    """[(byte offset, value)] of every pointer-typed field of a ctypes struct."""
+    """[(byte offset, value)] of every pointer-typed field of a ctypes struct, nested structs
+    (``Conv2Op``: two ``ConvParams``) included."""
     out = []
     for name, ty in st._fields_:
-        if ty is C.c_void_p or (isinstance(ty, type) and issubclass(ty, C._Pointer)):
-            v = getattr(st, name)
+        off, v = getattr(type(st), name).offset, getattr(st, name)
+        if ty is C.c_void_p or issubclass(ty, C._Pointer):
             v = v if isinstance(v, int) or v is None else C.cast(v, C.c_void_p).value
-            out.append((getattr(type(st), name).offset, v or 0))
+            out.append((off, v or 0))
+        elif issubclass(ty, C.Structure):
+            out += [(off + o, p) for o, p in _pointer_fields(v)]
     return out
 
 

@@ -213,7 +213,7 @@ class ExecContext:
                               self._addr(att.outputs[0]), a["B"], a["L"], a["heads"], D, pc.ksteps,
                               gm.attrs.get("ldx") or g.shape(gm.inputs[0])[-1], g.shape(att.outputs[0])[-1], 0.125)
         self.configs.append((f"{gm.attrs.get('name', '')}+attention", "fused:qkvatt", -1, 0))
-        tx.prog_add(self.prog, tx.K_QKVATT, prm, gm.slot, lib=lib)
+        N.prog_add(lib, self.prog, N.HZ_K_QKVATT, prm, gm.slot, "add_qkvatt")
 
     def _conv_plans(self, g: Graph, params: dict, tuned: dict | None) -> list:
         """(cfg, kw, tuning key) of every conv / GEMM node, None for other nodes."""
@@ -287,7 +287,7 @@ class ExecContext:
         if kf is not None:  # the pair presets the stage's first K-split 3x3 conv's accumulator
             self._set_kconv_preset(pa, kf)
         self.configs.append((a.attrs.get("name", "") + "+" + b.attrs.get("name", ""), key, cfg, kw))
-        N.check(lib.hz_prog_add_conv2(self.prog, C.byref(pa), C.byref(pb), cfg, a.slot), "add_conv2")
+        N.prog_add(lib, self.prog, N.HZ_K_CONV2, N.Conv2Op(pa, pb, cfg), a.slot, "add_conv2")
 
     def _ln_fold(self, n, pc, cfg: int, M: int) -> int:
         """Device copy of this GEMM's HzLnFold (csrc/hipzap.h); returns its address. Producers run
@@ -352,7 +352,7 @@ class ExecContext:
                 prm.z_C, prm.z_HW = c1, h1 * w1
                 assert nb1 == nb
             self.configs.append((n.attrs.get("name", ""), key, cfg, kw))
-            N.check(lib.hz_prog_add_conv(self.prog, C.byref(prm), cfg, n.slot), "add_conv")
+            N.prog_add(lib, self.prog, N.HZ_K_CONV, N.ConvOp(prm, cfg), n.slot, "add_conv")
         elif n.kind == "maxpool":
             nb, h, w, c = g.shape(n.inputs[0])
             _, p, q, _ = g.shape(n.outputs[0])
@@ -360,11 +360,11 @@ class ExecContext:
             if conv_ops.is_blocked(c):  # [N][C/32][H][W][32] == NHWC with N*C/32 images of 32 ch
                 nb, c = nb * c // 32, 32
             prm = N.PoolParams(addr(n.inputs[0]), addr(n.outputs[0]), nb, h, w, c, p, q, a["k"], a["stride"], a["pad"])
-            N.check(lib.hz_prog_add_maxpool(self.prog, C.byref(prm), n.slot), "add_maxpool")
+            N.prog_add(lib, self.prog, N.HZ_K_MAXPOOL, prm, n.slot, "add_maxpool")
         elif n.kind == "avgpool":
             nb, h, w, c = g.shape(n.inputs[0])
-            N.check(lib.hz_prog_add_avgpool(self.prog, addr(n.inputs[0]), addr(n.outputs[0]), nb, h * w, c,
-                                            int(conv_ops.is_blocked(c)), n.slot), "add_avgpool")
+            prm = vision.AvgpoolArgs(addr(n.inputs[0]), addr(n.outputs[0]), nb, h * w, c, int(conv_ops.is_blocked(c)))
+            N.prog_add(lib, self.prog, N.HZ_K_AVGPOOL, prm, n.slot, "add_avgpool")
         elif n.kind == "preprocess":
             src = g.tensors[n.inputs[0]]
             if src.dtype == torch.uint8:
@@ -379,8 +379,9 @@ class ExecContext:
                 mean = torch.tensor(n.attrs["mean"], dtype=torch.float32, device=self.device)
                 std = 1.0 / torch.tensor(n.attrs["std"], dtype=torch.float32, device=self.device)
                 self._keep += [mean, std]
-            N.check(lib.hz_prog_add_preprocess(self.prog, addr(n.inputs[0]), addr(n.outputs[0]), nb, cin, h, w,
-                                               cpad, mode, N.ptr(mean), N.ptr(std), n.slot), "add_preprocess")
+            prm = vision.PreprocessArgs(addr(n.inputs[0]), addr(n.outputs[0]), N.ptr(mean), N.ptr(std), nb, cin, h, w,
+                                        cpad, mode)
+            N.prog_add(lib, self.prog, N.HZ_K_PREPROCESS, prm, n.slot, "add_preprocess")
         elif n.kind == "patchify":  # preprocess mode 2: fp32 NCHW -> bf16 patch rows (Cpad = patch)
             nb, cin, h, w = g.tensors[n.inputs[0]].shape
             mean = std = None
@@ -388,8 +389,9 @@ class ExecContext:
                 mean = torch.tensor(n.attrs["mean"], dtype=torch.float32, device=self.device)
                 std = 1.0 / torch.tensor(n.attrs["std"], dtype=torch.float32, device=self.device)
                 self._keep += [mean, std]
-            N.check(lib.hz_prog_add_preprocess(self.prog, addr(n.inputs[0]), addr(n.outputs[0]), nb, cin, h, w,
-                                               n.attrs["patch"], 2, N.ptr(mean), N.ptr(std), n.slot), "add_patchify")
+            prm = vision.PreprocessArgs(addr(n.inputs[0]), addr(n.outputs[0]), N.ptr(mean), N.ptr(std), nb, cin, h, w,
+                                        n.attrs["patch"], 2)
+            N.prog_add(lib, self.prog, N.HZ_K_PREPROCESS, prm, n.slot, "add_patchify")
         elif n.kind == "gemm":
             pc = self.params[n.attrs["w"]]
             cfg, kw, key = plan
@@ -403,11 +405,11 @@ class ExecContext:
             if _ln_folded(n):
                 prm.lnf = self._ln_fold(n, pc, cfg, M)
             self.configs.append((n.attrs.get("name", ""), key, cfg, kw))
-            N.check(lib.hz_prog_add_conv(self.prog, C.byref(prm), cfg, n.slot), "add_gemm")
+            N.prog_add(lib, self.prog, N.HZ_K_CONV, N.ConvOp(prm, cfg), n.slot, "add_gemm")
         elif n.kind == "quant":
             rows, D = g.shape(n.inputs[0])
             prm = fp8.QuantParams(addr(n.inputs[0]), addr(n.outputs[0]), addr(n.outputs[1]), rows, D, D, D)
-            tx.prog_add(self.prog, fp8.K_QUANT, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_QUANT, prm, n.slot, "add_quant")
         elif n.kind == "gemm_fp8":
             pw = self.params[n.attrs["w"]]
             cfg, kw, key = plan
@@ -421,7 +423,7 @@ class ExecContext:
                                   out8_ptr=addr(n.outputs[0]) if o_mx else 0,
                                   os8_ptr=addr(n.outputs[1]) if o_mx else 0)
             self.configs.append((n.attrs.get("name", ""), key, cfg, kw))
-            tx.prog_add(self.prog, fp8.K_GEMM_FP8, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_GEMM_FP8, prm, n.slot, "add_gemm_fp8")
         elif n.kind == "layernorm":
             npar = self.params[n.attrs["p"]]
             res = n.inputs[1] if len(n.inputs) > 1 else None
@@ -434,7 +436,7 @@ class ExecContext:
                                      npar.gamma.data_ptr(), npar.beta.data_ptr(), n.attrs["rows"], D,
                                      n.attrs.get("ldx") or D, D, D, npar.eps, addr(outs[0]) if q8 else 0,
                                      addr(outs[1]) if q8 else 0)
-            tx.prog_add(self.prog, tx.K_LAYERNORM, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_LAYERNORM, prm, n.slot, "add_layernorm")
         elif n.kind == "attention":
             a = n.attrs
             qkv = n.inputs[0]
@@ -444,20 +446,20 @@ class ExecContext:
             prm = tx.AttentionParams(addr(qkv), addr(mask), 0 if mx else addr(n.outputs[0]), a["B"], a["L"],
                                      a["heads"], 64, g.shape(qkv)[-1], D, 2 * D, D, 0.125,
                                      addr(n.outputs[0]) if mx else 0, addr(n.outputs[1]) if mx else 0)
-            tx.prog_add(self.prog, tx.K_ATTENTION, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_ATTENTION, prm, n.slot, "add_attention")
         elif n.kind == "embed_ln":
             tab, ln = self.params[n.attrs["emb"]], self.params[n.attrs["ln"]]
             rows, D = g.shape(n.outputs[0])
             prm = tx.EmbedParams(addr(n.inputs[0]), addr(n.inputs[1]), tab.word.data_ptr(), tab.pos.data_ptr(),
                                  tab.type.data_ptr(), ln.gamma.data_ptr(), ln.beta.data_ptr(), addr(n.outputs[0]),
                                  rows, n.attrs["L"], D, ln.eps, tab.word.shape[0], tab.type.shape[0])
-            tx.prog_add(self.prog, tx.K_EMBED, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_EMBED, prm, n.slot, "add_embed")
         elif n.kind == "vit_tokens":
             a = n.attrs
             D = g.shape(n.outputs[0])[-1]
             prm = tx.VitTokensParams(addr(n.inputs[0]), self.params[a["cls"]].data_ptr(),
                                      self.params[a["pos"]].data_ptr(), addr(n.outputs[0]), a["B"], a["np"], D)
-            tx.prog_add(self.prog, tx.K_VIT_TOKENS, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_VIT_TOKENS, prm, n.slot, "add_vit_tokens")
         elif n.kind == "pool_fc":
             pc = self.params[n.attrs["w"]]
             nb, h, w, c = g.shape(n.inputs[0])
@@ -465,7 +467,7 @@ class ExecContext:
             prm = vision.PoolFcParams(addr(n.inputs[0]), pc.wf.data_ptr(), pc.bias.data_ptr(), addr(n.outputs[0]),
                                       nb, c, h * w, pc.cout, g.shape(n.outputs[0])[-1],
                                       int(id(n) in self.pooled_readers))
-            tx.prog_add(self.prog, vision.K_POOL_FC, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_POOL_FC, prm, n.slot, "add_pool_fc")
         elif n.kind == "softmax":
             ishape = g.shape(n.inputs[0])
             rows, ld = ishape[0], int(torch.tensor(ishape[1:]).prod())
@@ -473,7 +475,7 @@ class ExecContext:
             D = n.attrs.get("D") or ld
             prm = tx.SoftmaxParams(addr(n.inputs[0]), 0, addr(n.outputs[0]), rows, D, ld, g.shape(n.outputs[0])[-1],
                                    int(src.dtype == torch.bfloat16), float(n.attrs.get("scale", 1.0)))
-            tx.prog_add(self.prog, tx.K_SOFTMAX, prm, n.slot, lib=lib)
+            N.prog_add(lib, self.prog, N.HZ_K_SOFTMAX, prm, n.slot, "add_softmax")
         elif n.kind == "fork":
             N.check(lib.hz_prog_add_fork(self.prog, n.slot), "fork")
         elif n.kind == "join":

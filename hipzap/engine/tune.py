@@ -66,9 +66,9 @@ def _capture(lib, prm, cfg, stream):
     prog = lib.hz_prog_create()
     for _ in range(REPS):
         if isinstance(prm, fp8_ops.GemmFp8Params):
-            N.check(lib.hz_prog_add_kernel(prog, fp8_ops.K_GEMM_FP8, C.byref(prm), C.sizeof(prm), 0), "add_fp8")
+            N.prog_add(lib, prog, N.HZ_K_GEMM_FP8, prm, 0, "add_fp8")
         else:
-            N.check(lib.hz_prog_add_conv(prog, C.byref(prm), cfg, 0), "add_conv")
+            N.prog_add(lib, prog, N.HZ_K_CONV, N.ConvOp(prm, cfg), 0, "add_conv")
     N.check(lib.hz_prog_capture(prog, stream.cuda_stream), "capture")
     return prog
 
@@ -167,7 +167,7 @@ def _time_pair(lib, sa, sb, cand, bufs, stream) -> float:
     prog = lib.hz_prog_create()
     try:
         for _ in range(REPS):
-            N.check(lib.hz_prog_add_conv2(prog, C.byref(prms[0]), C.byref(prms[1]), cfg, 0), "add_conv2")
+            N.prog_add(lib, prog, N.HZ_K_CONV2, N.Conv2Op(prms[0], prms[1], cfg), 0, "add_conv2")
         N.check(lib.hz_prog_capture(prog, stream.cuda_stream), "capture")
         torch.cuda.synchronize()
         best = float("inf")

@@ -23,6 +23,7 @@ import time
 from . import _native as N
 
 HEADER = struct.Struct("<8s15Q")
+PLAN_VERSION = 2  # csrc/plan.cpp kPlanVersion
 PHASES = ("parse_ms", "hip_init_ms", "upload_ms", "ctx_alloc_ms", "bind_ms", "capture_ms", "blob_alloc_ms",
           "first_copy_ms",
           # upload_ms = stream_ms + upload_dma_ms + warm_wait_ms; warm_thread_ms runs beside them
@@ -49,14 +50,15 @@ def read_meta(path: str) -> dict:
         meta_off, meta_len = fields[4], fields[5]
         f.seek(meta_off)
         meta = json.loads(f.read(meta_len))
-    meta["abi"] = fields[2]
+    meta["version"], meta["abi"] = fields[1], fields[2]
     return meta
 
 
 def plan_usable(path: str) -> bool:
-    """True if ``path`` is a plan image this library build can load (same native ABI)."""
+    """True if ``path`` is a plan image this library build can load (same format version and native ABI)."""
     try:
-        return read_meta(path)["abi"] == lib().hz_abi_version()
+        meta = read_meta(path)
+        return meta["version"] == PLAN_VERSION and meta["abi"] == lib().hz_abi_version()
     except (OSError, PlanError, ValueError, KeyError):
         return False
 

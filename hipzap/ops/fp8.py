@@ -15,15 +15,17 @@ import torch
 from .. import _native as N
 from .conv import PackedConv, choose_config, fragment_major
 
-K_QUANT, K_GEMM_FP8 = 10, 11
+K_QUANT, K_GEMM_FP8 = N.HZ_K_QUANT, N.HZ_K_GEMM_FP8
 FP8_MAX = 448.0
 
 
+@N.params_of("HZ_K_QUANT")
 class QuantParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_void_p), ("rows", C.c_int), ("D", C.c_int),
                 ("ldx", C.c_int), ("ldo", C.c_int)]
 
 
+@N.params_of("HZ_K_GEMM_FP8")
 class GemmFp8Params(C.Structure):
     _fields_ = [("x", C.c_void_p), ("sx", C.c_void_p), ("w", C.c_void_p), ("sw", C.c_void_p), ("bias", C.c_void_p),
                 ("res", C.c_void_p), ("out", C.c_void_p), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),

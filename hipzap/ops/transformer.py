@@ -10,22 +10,24 @@ import torch.nn.functional as F
 
 from .. import _native as N
 
-K_LAYERNORM, K_EMBED, K_ATTENTION, K_VIT_TOKENS = 2, 3, 4, 5
-K_SOFTMAX = 12
-K_QKVATT = 22
+K_LAYERNORM, K_EMBED, K_ATTENTION, K_VIT_TOKENS = N.HZ_K_LAYERNORM, N.HZ_K_EMBED, N.HZ_K_ATTENTION, N.HZ_K_VIT_TOKENS
+K_SOFTMAX, K_QKVATT = N.HZ_K_SOFTMAX, N.HZ_K_QKVATT
 
 
+@N.params_of("HZ_K_SOFTMAX")
 class SoftmaxParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_int), ("D", C.c_int),
                 ("ldx", C.c_int), ("ldo", C.c_int), ("x_bf16", C.c_int), ("scale", C.c_float)]
 
 
+@N.params_of("HZ_K_LAYERNORM")
 class LayerNormParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("res", C.c_void_p), ("out", C.c_void_p), ("gamma", C.c_void_p),
                 ("beta", C.c_void_p), ("rows", C.c_int), ("D", C.c_int), ("ldx", C.c_int), ("ldr", C.c_int),
                 ("ldo", C.c_int), ("eps", C.c_float), ("out8", C.c_void_p), ("scale8", C.c_void_p)]
 
 
+@N.params_of("HZ_K_EMBED")
 class EmbedParams(C.Structure):
     _fields_ = [("ids", C.c_void_p), ("types", C.c_void_p), ("word", C.c_void_p), ("pos", C.c_void_p),
                 ("type", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("out", C.c_void_p),
@@ -33,6 +35,7 @@ class EmbedParams(C.Structure):
                 ("vocab", C.c_int), ("ntypes", C.c_int)]
 
 
+@N.params_of("HZ_K_ATTENTION")
 class AttentionParams(C.Structure):
     _fields_ = [("qkv", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("L", C.c_int),
                 ("heads", C.c_int), ("head_dim", C.c_int), ("ldqkv", C.c_int), ("k_off", C.c_int),
@@ -40,12 +43,14 @@ class AttentionParams(C.Structure):
                 ("os8", C.c_void_p)]
 
 
+@N.params_of("HZ_K_QKVATT")
 class QkvAttParams(C.Structure):  # HzQkvAttParams: QKV projection + attention in one launch
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p),
                 ("B", C.c_int), ("L", C.c_int), ("heads", C.c_int), ("D", C.c_int), ("ksteps", C.c_int),
                 ("ldx", C.c_int), ("ldo", C.c_int), ("scale", C.c_float)]
 
 
+@N.params_of("HZ_K_VIT_TOKENS")
 class VitTokensParams(C.Structure):
     _fields_ = [("patches", C.c_void_p), ("cls", C.c_void_p), ("pos", C.c_void_p), ("out", C.c_void_p),
                 ("B", C.c_int), ("np", C.c_int), ("D", C.c_int)]
@@ -53,11 +58,6 @@ class VitTokensParams(C.Structure):
 
 def launch(kind: int, prm, stream=None):
     N.check(N.lib().hz_launch_kernel(kind, C.byref(prm), N.stream_ptr(stream)), f"kernel {kind}")
-
-
-def prog_add(prog, kind: int, prm=None, slot: int = 0, lib=None):
-    lib = lib if lib is not None else N.lib()
-    N.check(lib.hz_prog_add_kernel(prog, kind, C.byref(prm), C.sizeof(prm), slot), f"prog_add {kind}")
 
 
 @dataclass

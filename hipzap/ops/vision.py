@@ -7,13 +7,28 @@ import torch
 
 from .. import _native as N
 
-K_POOL_FC = 13
+K_POOL_FC = N.HZ_K_POOL_FC
 
 
+@N.params_of("HZ_K_POOL_FC")
 class PoolFcParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int),
                 ("C", C.c_int), ("HW", C.c_int), ("N", C.c_int), ("ldo", C.c_int),
                 ("pooled", C.c_int), ("pad_", C.c_int)]
+
+
+@N.params_of("HZ_K_AVGPOOL")
+class AvgpoolArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("N", C.c_int), ("HW", C.c_int), ("C", C.c_int),
+                ("blocked", C.c_int)]
+
+
+@N.params_of("HZ_K_PREPROCESS")
+class PreprocessArgs(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("mean", C.c_void_p), ("inv_std", C.c_void_p),
+                ("N", C.c_int), ("Cin", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cpad", C.c_int),
+                ("mode", C.c_int)]
+
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)

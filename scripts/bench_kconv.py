@@ -7,7 +7,6 @@ on 4 concurrent streams (throughput, the served regime); us per launch, best of 
 
     python scripts/bench_kconv.py
 """
-import ctypes as C
 import json
 import os
 import sys
@@ -21,7 +20,7 @@ from hipzap import _native as N  # noqa: E402
 from hipzap.ops import conv as CV  # noqa: E402
 
 REPS = 64
-from hipzap.engine.fusion import HZ_K_KCONV, KconvParams  # noqa: E402  (the struct the launcher reads)
+from hipzap.engine.fusion import KconvParams  # noqa: E402  (the struct the launcher reads)
 
 
 def prog_of(add, reps=REPS):
@@ -64,14 +63,14 @@ def main():
                     bufs[i] = bufs[i] + (xb,)
                     prm, _, _ = CV.make_params(xb.data_ptr(), pc, 1, h, h, bufs[i][2].data_ptr(), 0, "relu", False, 3, 16)
                     prm.x_f32 = xf
-                    N.check(lib.hz_prog_add_conv(p, C.byref(prm), 3, 0), "add_conv")
+                    N.prog_add(lib, p, N.HZ_K_CONV, N.ConvOp(prm, 3), 0, "add_conv")
                 variants[f"conv_cfg3_kw16{'_f32in' if xf else ''}"] = add_conv
             for ck in cks:
                 def add_k(lib, p, i, ck=ck):
                     prm = KconvParams()
                     prm.x, prm.w, prm.out = bufs[i][0].data_ptr(), pc.wf.data_ptr(), bufs[i][1].data_ptr()
                     prm.N, prm.H, prm.W, prm.C, prm.Cout, prm.x_f32, prm.ck = 1, h, h, c, c, 1, ck
-                    N.check(lib.hz_prog_add_kernel(p, HZ_K_KCONV, C.byref(prm), C.sizeof(prm), 0), "add_kconv")
+                    N.prog_add(lib, p, N.HZ_K_KCONV, prm, 0, "add_kconv")
                 variants[f"kconv_ck{ck}"] = add_k
             for name, add in variants.items():
                 progs = [prog_of(lambda lib, p, i=i: add(lib, p, i)) for i in range(conc)]

@@ -33,7 +33,8 @@ def graphs(kind, S, nk, blocks, nbytes):
         p = lib.hz_prog_create()
         for i in range(nk):
             src, dst = (a, b) if i % 2 == 0 else (b, a)
-            N.check(lib.hz_prog_add_diag(p, kind, blocks, 256, src.data_ptr(), dst.data_ptr(), nbytes, 0), "diag")
+            N.prog_add(lib, p, N.HZ_K_DIAG, N.DiagArgs(kind, blocks, 256, 0, src.data_ptr(), dst.data_ptr(), nbytes), 0,
+                       "diag")
         s = torch.cuda.Stream()
         N.check(lib.hz_prog_capture(p, s.cuda_stream), "cap")
         progs.append(p)

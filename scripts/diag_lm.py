@@ -40,19 +40,17 @@ def main():
     lib = N.lib()
     ops = eng._ops  # (kind, params) in step order; the sampler is fused into layer 0
     res_final = None if eng._final is None else \
-        timed(lambda p: N.check(lib.hz_prog_add_sampler(p, C.byref(eng._final), 0), "final"))
+        timed(lambda p: N.prog_add(lib, p, N.HZ_K_SAMPLER, eng._final, 0, "final"))
     res = {"V": V, "standalone_argmax_sampler_us": res_final}
     for k, (kind, prm) in enumerate(ops):
-        add = {"lstm": lib.hz_prog_add_lstm, "decoder": lib.hz_prog_add_decoder,
-               "sampler": lib.hz_prog_add_sampler}[kind]
-        res[f"{k}_{kind}_us"] = timed(lambda p, add=add, prm=prm: N.check(add(p, C.byref(prm), 0), kind))
+        name = lib.hz_kernel_name(kind).decode()[len("HZ_K_"):].lower()  # lstm, decoder, sampler
+        res[f"{k}_{name}_us"] = timed(
+            lambda p, kind=kind, prm=prm, name=name: N.prog_add(lib, p, kind, prm, 0, name))
 
     def step(p):
         for kind, prm in ops:
-            add = {"lstm": lib.hz_prog_add_lstm, "decoder": lib.hz_prog_add_decoder,
-                   "sampler": lib.hz_prog_add_sampler}[kind]
-            N.check(add(p, C.byref(prm), 0), kind)
-        N.check(lib.hz_prog_add_step_bump(p, eng.step.data_ptr(), 1, 0), "bump")
+            N.prog_add(lib, p, kind, prm, 0, "step")
+        N.prog_add(lib, p, N.HZ_K_STEP_BUMP, N.StepBumpArgs(eng.step.data_ptr(), 1), 0, "bump")
     res["step_us"] = timed(step, reps=8)
     print(json.dumps(res))
 

@@ -32,7 +32,8 @@ def chain(kind, nk, blocks, nbytes):
     prog = lib.hz_prog_create()
     for i in range(nk):
         src, dst = (a, b) if i % 2 == 0 else (b, a)
-        N.check(lib.hz_prog_add_diag(prog, kind, blocks, 256, src.data_ptr(), dst.data_ptr(), nbytes, 0), "diag")
+        N.prog_add(lib, prog, N.HZ_K_DIAG, N.DiagArgs(kind, blocks, 256, 0, src.data_ptr(), dst.data_ptr(), nbytes), 0,
+                   "diag")
     s = torch.cuda.Stream()
     N.check(lib.hz_prog_capture(prog, s.cuda_stream), "cap")
     bench2([prog], [s], 5)

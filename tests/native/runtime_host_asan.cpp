@@ -87,18 +87,23 @@ int main() {
     g_calls.clear();
     g_vals.clear();
     HzProgram p = hz_prog_create();
-    HzConvParams c;
+    HzConvOp c;
     memset(&c, 0, sizeof(c));
-    c.K = 576;
-    CHECK(hz_prog_add_conv(p, &c, 3, 0) == 0);
-    c.K = 1;  // the program captured the params by value at add time
-    HzConvParams d = c;
-    d.K = 64;
-    CHECK(hz_prog_add_conv2(p, &c, &d, 2, 0) == 0);
+    c.p.K = 576;
+    c.cfg = 3;
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV, &c, sizeof(c), 0) == 0);
+    c.p.K = 1;  // the program captured the params by value at add time
+    HzConv2Op cd;
+    memset(&cd, 0, sizeof(cd));
+    cd.a = c.p;
+    cd.b = c.p;
+    cd.b.K = 64;
+    cd.cfg = 2;
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV2, &cd, sizeof(cd), 0) == 0);
     HzLstmParams l;
     memset(&l, 0, sizeof(l));
     l.H = 1150;
-    CHECK(hz_prog_add_lstm(p, &l, 0) == 0);
+    CHECK(hz_prog_add_kernel(p, HZ_K_LSTM, &l, sizeof(l), 0) == 0);
     HzLayerNormParams ln;
     memset(&ln, 0, sizeof(ln));
     ln.rows = 2048;
@@ -106,7 +111,10 @@ int main() {
     ln.rows = -5;  // generic kernels also copy their parameter block
     std::vector<char> big(4096, 0);  // a parameter block larger than any struct
     CHECK(hz_prog_add_kernel(p, 9999, big.data(), big.size(), 0) == -101);  // unknown kind: refused at add
+    CHECK(hz_prog_add_kernel(p, 17, big.data(), big.size(), 0) == -101);    // the retired kind too
     CHECK(hz_prog_add_kernel(p, HZ_K_LAYERNORM, &ln, sizeof(ln) - 8, 0) == -101);  // short record: refused
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV, &c, sizeof(c) - 4, 0) == -101);  // (a bare HzConvParams, say)
+    CHECK(strcmp(hz_kernel_name(HZ_K_CONV2), "HZ_K_CONV2") == 0 && hz_kernel_name(9999) == nullptr);
     HzSoftmaxParams sm;
     memset(&sm, 0, sizeof(sm));
     sm.rows = -7;
@@ -115,17 +123,18 @@ int main() {
     CHECK(hz_prog_num_ops(p) == 5);
     hz_prog_destroy(p);  // (discard: rebuild with the failing softmax as op 4)
     p = hz_prog_create();
-    c.K = 576;
-    CHECK(hz_prog_add_conv(p, &c, 3, 0) == 0);
-    c.K = 1;
-    CHECK(hz_prog_add_conv2(p, &c, &d, 2, 0) == 0);
-    CHECK(hz_prog_add_lstm(p, &l, 0) == 0);
+    c.p.K = 576;
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV, &c, sizeof(c), 0) == 0);
+    c.p.K = 1;
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV2, &cd, sizeof(cd), 0) == 0);
+    CHECK(hz_prog_add_kernel(p, HZ_K_LSTM, &l, sizeof(l), 0) == 0);
     ln.rows = 2048;
     CHECK(hz_prog_add_kernel(p, HZ_K_LAYERNORM, &ln, sizeof(ln), 0) == 0);
     CHECK(hz_prog_add_kernel(p, HZ_K_SOFTMAX, big.data(), big.size(), 0) == 0);  // fails at run
-    CHECK(hz_prog_add_avgpool(p, nullptr, nullptr, 7, 49, 2048, 1, 0) == 0);
-    CHECK(hz_prog_add_conv(p, &c, 0, -1) == -4);  // slot out of range
-    CHECK(hz_prog_add_conv(p, &c, 0, 9) == -4);
+    HzAvgpoolArgs ap = {nullptr, nullptr, 7, 49, 2048, 1};
+    CHECK(hz_prog_add_kernel(p, HZ_K_AVGPOOL, &ap, sizeof(ap), 0) == 0);
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV, &c, sizeof(c), -1) == -4);  // slot out of range
+    CHECK(hz_prog_add_kernel(p, HZ_K_CONV, &c, sizeof(c), 9) == -4);
     CHECK(hz_prog_add_fork(p, 0) == -4);
     CHECK(hz_prog_num_ops(p) == 6);
     CHECK(hz_prog_is_captured(p) == 0);
@@ -141,7 +150,10 @@ int main() {
     hz_prog_destroy(p);
 
     HzProgram q = hz_prog_create();
-    for (int i = 0; i < 64; ++i) CHECK(hz_prog_add_avgpool(q, nullptr, nullptr, i, 1, 1, 0, 0) == 0);
+    for (int i = 0; i < 64; ++i) {
+      ap = {nullptr, nullptr, i, 1, 1, 0};
+      CHECK(hz_prog_add_kernel(q, HZ_K_AVGPOOL, &ap, sizeof(ap), 0) == 0);
+    }
     g_calls.clear();
     g_vals.clear();
     CHECK(hz_prog_replay_n(q, nullptr, 3) == 0);  // not captured: eager runs

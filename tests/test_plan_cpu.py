@@ -135,6 +135,22 @@ def test_read_meta_and_abi_gate(tmp_path, r18):
         lite.read_meta(__file__)  # not a plan image
 
 
+def test_old_format_version_is_refused(tmp_path, r18):
+    """A version-1 image (per-op types, conv cfg in the op header) is refused by its version, never
+    parsed as the current format -- even one forged to carry the current ABI hash."""
+    from hipzap import lite
+    a, params, kw = r18
+    path = str(tmp_path / "r18.hzplan")
+    P.export_plan("resnet18", params, kw, path)
+    assert P.VERSION == 2 and decode(path)[0]["version"] == 2
+    raw = bytearray(open(path, "rb").read())
+    raw[8:16] = (1).to_bytes(8, "little")  # version field
+    old = tmp_path / "old.hzplan"
+    old.write_bytes(bytes(raw))
+    assert not lite.plan_usable(str(old))
+    assert "unsupported version 1" in _plan_open_error(old)
+
+
 def test_sampled_digest_detects_same_size_replacement(tmp_path):
     from hipzap.engine.packfile import source_stamp
     p = tmp_path / "m.pth"
