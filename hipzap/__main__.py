@@ -65,7 +65,7 @@ def cmd_plan(a):
     from .engine.plan import export_from_checkpoint
     from .lite import read_meta
     out = export_from_checkpoint(a.model, a.ckpt, a.out, batch=a.batch, contexts=a.contexts, probs=a.probs,
-                                 dp_shard=a.dp_shard)
+                                 dp_shard=a.dp_shard, seq_len=a.seq_len)
     m = read_meta(out)
     print(json.dumps({"out": out, "ops": m["n_ops"], "blob_bytes": m["blob_bytes"], "source": m["source"]}))
 
@@ -124,6 +124,8 @@ def main(argv=None):
     pl.add_argument("--batch", type=int, default=1)
     pl.add_argument("--contexts", type=int, default=1, help="request concurrency the launch configs are tuned for")
     pl.add_argument("--probs", action="store_true", help="softmax head on device")
+    pl.add_argument("--seq-len", type=int, default=None,
+                    help="text models: captured sequence length (default 128, at most the checkpoint's positions)")
     pl.add_argument("--dp-shard", type=int, default=None,
                     help="also write <ckpt>.dp<S>.hzplan: the per-GPU shard program of batched DP requests")
     t = sub.add_parser("tune")

@@ -6,7 +6,9 @@
 //   * attention  — fused softmax(Q K^T * scale + mask) V per (batch, head, 64-query block),
 //                  K and V^T staged in LDS, S kept in MFMA accumulators, row softmax via
 //                  16-lane shuffles, P written once to LDS as bf16 and re-read as the A
-//                  operand of P.V. L <= 256, head dim 64 (BERT L=128, ViT L=197).
+//                  operand of P.V. Head dim 64. attention_kernel: L <= 256, one pass, every key
+//                  in LDS (BERT L=128, ViT L=197); attention_stream_kernel: any L, K/V streamed
+//                  in 64-key tiles with the online softmax (BERT L=512, ViT-384 L=577).
 //   * patch_tokens — ViT: CLS token + position embedding add around the patch-embed GEMM.
 #include <cstdlib>
 
@@ -197,7 +199,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const HzEmbedParams p) {
 
 // --------------------------------------------------------------------------- attention
 // softmax(Q K^T * scale + mask) V per (batch, head, block of 16*NW queries); one wave owns 16
-// queries and all keys (L <= 256). Keys live on the MFMA lane (cdna_hip_programming.md §3 'An
+// queries and all keys (attention_kernel: L <= 256; longer: attention_stream_kernel). Keys live on the MFMA lane (cdna_hip_programming.md §3 'An
 // accumulator tile as the next MFMA's operand'):
 //   S^T = K Q^T   (A = K rows from LDS, B = Q^T from global): lane (q = l&15, g = l>>4) holds
 //                 the scores of query q for keys kt*16 + 4g + i, i < 4;
@@ -349,6 +351,195 @@ __global__ __launch_bounds__(64 * NW) void attention_kernel(const HzAttentionPar
     }
   }
   // lane holds O[q0 + lq][dt*16 + 4g + i]
+  const int q = q0 + lq;
+  if (p.out8) {  // MX8 output: head dims [0,32) = dt 0,1 and [32,64) = dt 2,3 are two E8M0 blocks
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      float amax = 0.f;
+#pragma unroll
+      for (int d = 0; d < 2; ++d)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) amax = fmaxf(amax, fabsf(o[2 * hb + d][i]));
+      amax = fmaxf(amax, __shfl_xor(amax, 16, 64));
+      amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
+      const int ex = mx_exp(amax);
+      if (q < p.L) {
+        unsigned char* o8 = p.out8 + (row0 + q) * p.ldo + h * ATT_D + hb * 32;
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+          float x[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) x[i] = fminf(fmaxf(ldexpf(o[2 * hb + d][i], -ex), -448.f), 448.f);
+          *reinterpret_cast<unsigned*>(o8 + d * 16 + 4 * g) = pack4_fp8(x[0], x[1], x[2], x[3]);
+        }
+        if (g == 0) p.os8[(row0 + q) * (p.ldo >> 5) + h * 2 + hb] = (unsigned char)(ex + 127);
+      }
+    }
+    return;
+  }
+  if (q < p.L) {
+    bf16_t* out = p.out + (row0 + q) * p.ldo + h * ATT_D + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+      *reinterpret_cast<u32x2*>(out + dt * 16) = u32x2{pack_bf16x2(o[dt][0], o[dt][1]), pack_bf16x2(o[dt][2], o[dt][3])};
+  }
+}
+
+// --------------------------------------------------------------------------- streamed attention
+// The same product for any L: the keys are walked in tiles of ATS_T with the online softmax, so
+// neither the LDS nor the registers grow with L (attention_kernel keeps all L keys in LDS and all
+// L/16 score tiles in registers, hence its L <= 256). Same layout as attention_kernel -- a wave owns
+// 16 queries, S^T = K Q^T, the P accumulators are the B operand of O^T = V^T P^T, V read with
+// ds_read_b64_tr_b16 from a row-major image, 160-B rows -- so query lq's running max m and running
+// sum l live in the four lanes (lq, g = 0..3):
+//   per tile   s = scale * S + mask; m' = max(m, tile max) (2 shuffles); alpha = exp(m - m');
+//              p = exp(s - m') in (0, 1], bf16 UNNORMALISED into the P.V MFMAs; o *= alpha;
+//              l = l * alpha + (this lane's sum of the fp32 p) -- alpha is equal in the four lanes,
+//              so l stays a per-lane partial and is reduced once, after the last tile;
+//   epilogue   o /= l in fp32, then attention_kernel's bf16 or MX8 store.
+// A workgroup of 8 waves = 128 queries of one (batch, head). The K and V tile images are double
+// buffered and register staged, split as in cdna_hip_programming.md T14: tile t+1's global loads
+// are issued before tile t's QK^T and written to the other buffer after its P.V; one barrier per
+// tile (it orders both "tile t+1 is written" and "tile t is no longer read"). 512 threads x one
+// 16-B K chunk and one 16-B V chunk = exactly one 64-key tile. ceil(L / ATS_T) tiles, so every tile
+// holds a real key; the last tile's padding keys re-read row L-1 (finite) and are masked to -inf.
+// While every key seen so far is -inf (a caller's -inf mask over whole tiles) m' is -inf: then
+// p = 0 and alpha = 1 instead of exp(-inf - -inf) = NaN. A row whose keys are ALL -inf is undefined
+// (0 / 0), as in attention_kernel.
+constexpr int ATS_T = 64;                  // keys per tile (a multiple of 32)
+constexpr int ATS_NW = 8;                  // waves = 16-query groups per workgroup
+constexpr int ATS_IMG = ATS_T * ATT_KST;   // bf16 elements of one K or V tile image
+static_assert(ATS_T * 8 == 64 * ATS_NW, "one 16-B K chunk and one V chunk per thread and tile");
+static_assert(ATS_T % 32 == 0 && ATS_T <= 64 * ATS_NW, "32-key MFMA steps; one mask value per thread");
+
+__global__ __launch_bounds__(64 * ATS_NW) void attention_stream_kernel(const HzAttentionParams p) {
+  __shared__ __attribute__((aligned(16))) bf16_t KV[2][2 * ATS_IMG];  // [buffer][K image | V image]
+  __shared__ __attribute__((aligned(16))) float Ms[2][ATS_T];        // additive mask of the tile's keys
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x;
+  const int b = bh / p.heads, h = bh - b * p.heads;
+  const long row0 = (long)b * p.L;
+  const bf16_t* Q = p.qkv + row0 * p.ldqkv + h * ATT_D;
+  const bf16_t* K = Q + p.k_off;
+  const bf16_t* V = Q + p.v_off;
+  // debug contracts (uniform per block, before any barrier): attention_kernel's, without its L bound
+  if (!HZ_DCHECK(b < p.B && h * ATT_D + max(0, max(p.k_off, p.v_off)) + ATT_D <= p.ldqkv && h * ATT_D + ATT_D <= p.ldo))
+    return;
+  const int q0 = blockIdx.y * 16 * ATS_NW + wave * 16;
+  const bool live = q0 < p.L;  // wave-uniform: a wave past L only stages and meets the barriers
+  const int lq = lane & 15, g = lane >> 4;
+  bf16x8 qb[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+    qb[ks] = *reinterpret_cast<const bf16x8*>(Q + (long)min(q0 + lq, p.L - 1) * p.ldqkv + ks * 32 + g * 8);
+  // this thread's chunk of every tile: key skey of the tile, head dims sc .. sc+7
+  const int skey = tid >> 3, sc = (tid & 7) * 8;
+  const int soff = skey * ATT_KST + sc;
+  u32x4 kr, vr;
+  float mr = 0.f;
+  auto stage_load = [&](int t) {
+    const int key = min(t * ATS_T + skey, p.L - 1);
+    kr = *reinterpret_cast<const u32x4*>(K + (long)key * p.ldqkv + sc);
+    vr = *reinterpret_cast<const u32x4*>(V + (long)key * p.ldqkv + sc);
+    if (tid < ATS_T) {
+      const int k = t * ATS_T + tid;
+      mr = k < p.L ? (p.mask ? p.mask[row0 + k] : 0.f) : -INFINITY;
+    }
+  };
+  auto stage_write = [&](int buf) {
+    *reinterpret_cast<u32x4*>(&KV[buf][soff]) = kr;
+    *reinterpret_cast<u32x4*>(&KV[buf][ATS_IMG + soff]) = vr;
+    if (tid < ATS_T) Ms[buf][tid] = mr;
+  };
+  const int nt = (p.L + ATS_T - 1) / ATS_T;
+  stage_load(0);
+  stage_write(0);
+  __syncthreads();
+  float m = -INFINITY, l = 0.f;  // running max (equal in the query's four lanes), this lane's part of the sum
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int tr_row = (lane & 15) >> 2, tr_col = (lane & 3) * 4;  // attention_kernel's transposed-read address
+  for (int t = 0; t < nt; ++t) {
+    const int cur = t & 1;
+    const bool more = t + 1 < nt;
+    if (more) stage_load(t + 1);
+    if (live) {
+      const bf16_t* Ks = KV[cur];
+      const bf16_t* Vs = KV[cur] + ATS_IMG;
+      // ---- S^T = K Q^T: s[kt][i] = score(query q0+lq, key t*ATS_T + kt*16 + 4g + i) ----
+      f32x4 s[ATS_T / 16];
+#pragma unroll
+      for (int kt = 0; kt < ATS_T / 16; ++kt) {
+        s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const bf16x8 ka = *reinterpret_cast<const bf16x8*>(Ks + (kt * 16 + lq) * ATT_KST + ks * 32 + g * 8);
+          s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qb[ks], s[kt], 0, 0, 0);
+        }
+      }
+      // ---- scale + mask, the new running max, the rescale factor ----
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kt = 0; kt < ATS_T / 16; ++kt) {
+        const f32x4 madd = *reinterpret_cast<const f32x4*>(&Ms[cur][kt * 16 + 4 * g]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          s[kt][i] = s[kt][i] * p.scale + madd[i];
+          mx = fmaxf(mx, s[kt][i]);
+        }
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mn = fmaxf(m, mx);
+      const bool none = mn == -INFINITY;  // no finite score yet: contribute 0, keep the accumulators
+      const float msub = none ? 0.f : mn;
+      const float alpha = none ? 1.f : __expf(m - mn);
+      m = mn;
+      float sum = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < ATS_T / 16; ++kt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float e = __expf(s[kt][i] - msub);
+          s[kt][i] = e;
+          sum += e;
+        }
+      l = l * alpha + sum;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[dt][i] *= alpha;
+      // ---- O^T += V^T P^T over the tile's 32-key steps ----
+#pragma unroll
+      for (int c = 0; c < ATS_T / 32; ++c) {
+        const f32x4 pa = s[2 * c], pb = s[2 * c + 1];
+        const u32x4 pw = u32x4{pack_bf16x2(pa[0], pa[1]), pack_bf16x2(pa[2], pa[3]),
+                               pack_bf16x2(pb[0], pb[1]), pack_bf16x2(pb[2], pb[3])};
+        const bf16x8 pfrag = *reinterpret_cast<const bf16x8*>(&pw);
+        const int r_lo = 32 * c + 4 * g + tr_row, r_hi = r_lo + 16;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Vs + r_lo * ATT_VST + dt * 16 + tr_col));
+          const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Vs + r_hi * ATT_VST + dt * 16 + tr_col));
+          const short vv8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          const bf16x8 va = *reinterpret_cast<const bf16x8*>(vv8);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pfrag, o[dt], 0, 0, 0);
+        }
+      }
+    }
+    if (more) stage_write(cur ^ 1);
+    __syncthreads();
+  }
+  if (!live) return;  // whole waves only, after the last barrier
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[dt][i] *= inv;
+  // lane holds O[q0 + lq][dt*16 + 4g + i]: attention_kernel's stores
   const int q = q0 + lq;
   if (p.out8) {  // MX8 output: head dims [0,32) = dt 0,1 and [32,64) = dt 2,3 are two E8M0 blocks
 #pragma unroll
@@ -681,9 +872,17 @@ extern "C" int hz_embed_ln_launch(const HzEmbedParams* pp, hipStream_t st) {
 
 extern "C" int hz_attention_launch(const HzAttentionParams* pp, hipStream_t st) {
   const HzAttentionParams& p = *pp;
-  if (p.head_dim != ATT_D || p.L > ATT_LMAX || p.L < 1) return -1;
+  if (p.head_dim != ATT_D || p.L < 1) return -1;
   if (p.out8 && (!p.os8 || p.ldo % 32)) return -1;
   if (p.ldqkv % 8 || p.k_off % 8 || p.v_off % 8 || p.ldo % 4) return -1;  // 16-B staging, 8-B stores
+  // L > ATT_LMAX: the streamed kernel (any L). HIPZAP_ATT_STREAM=1 sends every L to it, so tests
+  // and A/Bs can run both kernels on the same input
+  static const bool stream = getenv("HIPZAP_ATT_STREAM") && atoi(getenv("HIPZAP_ATT_STREAM")) != 0;
+  if (stream || p.L > ATT_LMAX) {
+    hipLaunchKernelGGL(attention_stream_kernel, dim3(p.B * p.heads, (p.L + 16 * ATS_NW - 1) / (16 * ATS_NW)),
+                       dim3(64 * ATS_NW), 0, st, p);
+    return (int)hipGetLastError();
+  }
   const int Lp = (p.L + 31) & ~31;
   const size_t lds = (size_t)Lp * (ATT_KST + ATT_VST) * sizeof(bf16_t) + (size_t)Lp * sizeof(float);
   // 8 waves (128 queries) per workgroup for long sequences: K/V staged half as often

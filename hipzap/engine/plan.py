@@ -305,9 +305,11 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
 
 
 def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch: int = 1, contexts: int = 1,
-                           input_uint8: bool | None = None, dp_shard: int | None = None, **kw) -> str:
+                           input_uint8: bool | None = None, dp_shard: int | None = None,
+                           seq_len: int | None = None, **kw) -> str:
     """``torch.load`` the checkpoint, pack it on the CPU and write its plan image (deploy time,
-    ``hipzap plan``); the plan is keyed to the checkpoint's identity (size, mtime, sampled hash)."""
+    ``hipzap plan``); the plan is keyed to the checkpoint's identity (size, mtime, sampled hash).
+    ``seq_len``: the captured sequence length of a text model (default: the adapter's, 128)."""
     from .packfile import source_stamp
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
@@ -315,6 +317,10 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
     adapter = registry.get(model)
     params, arch_kw = adapter.pack(sd, "cpu")
     arch_kw = dict(arch_kw)
+    if seq_len is not None:
+        if "seq_len" not in arch_kw:
+            raise ValueError(f"{model} has no sequence length to set")
+        arch_kw["seq_len"] = int(seq_len)
     if input_uint8 is None:
         input_uint8 = model.startswith("resnet")
     if input_uint8 and model.startswith("resnet"):

@@ -94,12 +94,17 @@ def pack_bert(sd: dict, device="cpu", eps: float = 1e-12, ln_fold: bool | None =
 
 
 def build_graph(batch: int, seq_len: int = 128, layers: int = 12, hidden: int = 768, heads: int = 12,
-                ffn: int = 3072, num_labels: int = 2, ln_fold: bool = False, weights: str = "bf16", **_) -> Graph:
+                ffn: int = 3072, num_labels: int = 2, ln_fold: bool = False, weights: str = "bf16",
+                max_pos: int | None = None, **_) -> Graph:
     """``ln_fold`` (must match pack_bert's cfg): no standalone encoder LayerNorm. The O-proj and
     FFN2 GEMMs emit per-row (sum, sumsq) slabs of their raw output y; FFN1 and the next layer's
     QKV run on y with gamma/beta folded into their weights and normalise in the epilogue; the
     residual reads of y are normalised in the epilogue too (HzLnFold, csrc/hipzap.h). Only the
-    B CLS rows get a real LayerNorm, for the pooler. 5 kernels per layer instead of 7."""
+    B CLS rows get a real LayerNorm, for the pooler. 5 kernels per layer instead of 7.
+    ``max_pos``: rows of the checkpoint's position table (pack_bert's cfg); a longer ``seq_len``
+    would gather past it."""
+    if seq_len < 1 or (max_pos is not None and seq_len > max_pos):
+        raise ValueError(f"seq_len {seq_len} is outside the checkpoint's position table (1..{max_pos} positions)")
     B, L, D = batch, seq_len, hidden
     T = B * L
     g = Graph(f"bert_bs{B}_L{L}")

@@ -91,15 +91,15 @@ class TextClassifierAdapter:
     def pack(self, sd: dict, device):
         from .bert import pack_bert
         params, cfg = pack_bert(sd, device, weights=self.weights)
-        cfg["seq_len"] = self.seq_len
+        cfg.setdefault("seq_len", self.seq_len)  # the default; a requested length (arch_kw) overrides it
         return params, cfg
 
-    def meta_params(self, num_labels=2, ln_fold=None, **arch):
+    def meta_params(self, num_labels=2, ln_fold=None, seq_len=None, **arch):
         from .bert import make_model, pack_bert
         with torch.device("meta"):
             m = make_model(num_labels, **_hf_arch(arch, max_pos="max_position_embeddings"))
         params, cfg = pack_bert(m.state_dict(), "meta", ln_fold=ln_fold, weights=self.weights)
-        cfg["seq_len"] = self.seq_len
+        cfg["seq_len"] = seq_len or self.seq_len  # the source rank's length, not the default
         return params, cfg
 
     def build_graph(self, batch=1, **kw):

@@ -129,6 +129,8 @@ def softmax_ref(x: torch.Tensor, cols: int | None = None, scale: float = 1.0, ma
 
 def attention(qkv: torch.Tensor, B: int, L: int, heads: int, mask: torch.Tensor | None = None,
               out: torch.Tensor | None = None) -> torch.Tensor:
+    """softmax(Q K^T / 8 + mask) V for any L >= 1: the one-pass kernel up to L = 256, the streamed
+    (online-softmax) kernel beyond, or for every L with ``HIPZAP_ATT_STREAM=1``."""
     D = heads * 64
     out = out if out is not None else torch.empty(B * L, D, dtype=torch.bfloat16, device=qkv.device)
     prm = AttentionParams(qkv.data_ptr(), N.ptr(mask), out.data_ptr(), B, L, heads, 64, qkv.stride(0), D, 2 * D,
@@ -150,6 +152,43 @@ def attention_ref(qkv, B, L, heads, mask=None):
     if mask is not None:
         s = s + mask.float().reshape(B, 1, 1, L)
     return (torch.softmax(s, -1) @ v).permute(0, 2, 1, 3).reshape(B * L, D)
+
+
+def attention_stream_ref(qkv, B, L, heads, mask=None, tile: int = 64):
+    """CPU emulation of ``attention_stream_kernel``'s arithmetic (csrc/transformer.hip), not an
+    oracle: the keys are walked in tiles of ``tile`` with a running max ``m`` and running sum ``l``
+    per query; each tile's ``p = exp(s - m)`` is summed into ``l`` in fp32 and rounded to bf16
+    UNNORMALISED for the fp32-accumulated P.V; the accumulators are rescaled by
+    ``exp(m_old - m_new)`` and divided by ``l`` once at the end. Padding keys of the last tile are
+    ``-inf``; while no finite score has been seen the tile contributes 0 and nothing is rescaled.
+
+    Returns ``(out fp32 [B*L, heads*64], raised int32 [B, heads, L, tiles], growth fp32 [same])``:
+    ``raised`` marks the tiles that raised a query's running max and ``growth`` is by how much, in
+    score units (tile 0 always raises it, from ``-inf``: growth ``inf``)."""
+    D = heads * 64
+    q, k, v = qkv.float().reshape(B, L, 3, heads, 64).permute(2, 0, 3, 1, 4)  # bf16-exact operands
+    nt = (L + tile - 1) // tile
+    madd = torch.zeros(B, L) if mask is None else mask.float().reshape(B, L)
+    m = torch.full((B, heads, L), float("-inf"))
+    l = torch.zeros(B, heads, L)
+    o = torch.zeros(B, heads, L, 64)
+    raised = torch.zeros(B, heads, L, nt, dtype=torch.int32)
+    growth = torch.zeros(B, heads, L, nt)
+    for t in range(nt):
+        ks = slice(t * tile, min((t + 1) * tile, L))
+        s = (q @ k[:, :, ks].transpose(-1, -2)) * 0.125 + madd[:, None, None, ks]
+        mn = torch.maximum(m, s.amax(-1))
+        none = torch.isinf(mn) & (mn < 0)
+        msub = torch.where(none, torch.zeros_like(mn), mn)
+        alpha = torch.where(none, torch.ones_like(mn), torch.exp(m - msub))
+        p = torch.exp(s - msub[..., None])
+        l = l * alpha + p.sum(-1)
+        o = o * alpha[..., None] + p.to(torch.bfloat16).float() @ v[:, :, ks]
+        raised[..., t] = (mn > m).int()
+        growth[..., t] = torch.where(mn > m, mn - m, torch.zeros_like(mn))
+        m = mn
+    out = (o / l[..., None]).permute(0, 2, 1, 3).reshape(B * L, D)
+    return out, raised, growth
 
 
 def embed_ref(ids, types, tab: EmbedTables, np_: NormParams, L):

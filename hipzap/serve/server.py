@@ -117,7 +117,10 @@ class TextBackend:
         self.adapter = registry.get(name)
         self.seq_len = int(spec.extra.get("seq_len", 128))
         if backend == "gpu":
-            self.engine = _gpu_engine(name, sd, device, batch=spec.batch, num_contexts=spec.contexts, capture=capture)
+            # "seq_len" in the model's settings block is the captured length (default: the adapter's)
+            akw = {"seq_len": self.seq_len} if "seq_len" in spec.extra else None
+            self.engine = _gpu_engine(name, sd, device, batch=spec.batch, num_contexts=spec.contexts, capture=capture,
+                                      arch_kw=akw)
             self.model = None
         else:
             from ..models.bert import config_from_sd, make_model
