@@ -3,6 +3,7 @@
     python -m hipzap serve --port 8082            # local dev server (reference: main.py:115-127)
     python -m hipzap pack --model resnet50 --ckpt m.pth --out m.hzpack
     python -m hipzap plan --model resnet50 --ckpt m.pth [--contexts 24]  # torch-free cold-start image
+    python -m hipzap plan --model resnet50 --ckpt m.pth --resize 256 [--max-image 1024x1024]  # any-size images
     python -m hipzap tune --model resnet50 --batch 1 --concurrent 1 8
     python -m hipzap upload --models-dir ./models  # scripts/upload_models.py parity
     python -m hipzap info
@@ -32,7 +33,8 @@ def cmd_serve(a):
         # everything else through the Flask app (serve/native_http.py)
         from .serve.native_http import NativeHTTPServer, listening_socket
         be = srv.vision(st.default_model)  # cold start before the port opens
-        fast = be if isinstance(be, PlanVisionBackend) else None
+        # (a resize plan's requests are encoded images of any size: they take the Flask route)
+        fast = be if isinstance(be, PlanVisionBackend) and be.resize is None else None
         if os.environ.get("HIPZAP_LM_PRELOAD", "0") == "1":
             srv.lm()  # GET /inference backend before the port opens (else on its first request)
         http = NativeHTTPServer(app, listening_socket(host, port), fast=fast, server=srv)
@@ -63,11 +65,16 @@ def cmd_pack(a):
 
 def cmd_plan(a):
     from .engine.plan import export_from_checkpoint
+    from .imgeom import resize_spec
     from .lite import read_meta
+    from .models import registry
+    crop = a.crop or getattr(registry.get(a.model), "image", 224)
     out = export_from_checkpoint(a.model, a.ckpt, a.out, batch=a.batch, contexts=a.contexts, probs=a.probs,
-                                 dp_shard=a.dp_shard, seq_len=a.seq_len)
+                                 dp_shard=a.dp_shard, seq_len=a.seq_len,
+                                 resize=resize_spec(a.resize, crop, a.max_image))
     m = read_meta(out)
-    print(json.dumps({"out": out, "ops": m["n_ops"], "blob_bytes": m["blob_bytes"], "source": m["source"]}))
+    print(json.dumps({"out": out, "ops": m["n_ops"], "blob_bytes": m["blob_bytes"], "source": m["source"],
+                      **({"resize": m["resize"]} if m.get("resize") else {})}))
 
 
 def cmd_tune(a):
@@ -128,6 +135,12 @@ def main(argv=None):
                     help="text models: captured sequence length (default 128, at most the checkpoint's positions)")
     pl.add_argument("--dp-shard", type=int, default=None,
                     help="also write <ckpt>.dp<S>.hzplan: the per-GPU shard program of batched DP requests")
+    pl.add_argument("--resize", type=int, default=None,
+                    help="vision models: write a RESIZE plan -- requests are uint8 images of any size, the shorter "
+                         "side resized to this (antialiased bilinear), centre-cropped and normalised on the GPU")
+    pl.add_argument("--crop", type=int, default=None, help="with --resize: crop size (default: the model's image size)")
+    pl.add_argument("--max-image", default=None,
+                    help="with --resize: largest request image, HEIGHTxWIDTH (default 1024x1024)")
     t = sub.add_parser("tune")
     t.add_argument("--model", default="resnet50")
     t.add_argument("--batch", type=int, nargs="+", default=[1])

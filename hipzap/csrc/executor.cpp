@@ -280,14 +280,14 @@ struct Exec {
     return rc;
   }
 
-  int submit_wait(const void* const* in, void* out, double* lat_us, int m = 1) {
+  int submit_wait(const void* const* in, void* out, double* lat_us, int m = 1, const uint64_t* nbytes = nullptr) {
     {
       std::lock_guard<std::mutex> g(mu);
       if (stop) return -10;
       ++active;
     }
     const int rc = rows > 1 ? (m > 1 ? submit_rows(in, m, out, lat_us) : submit_batched(in, out, lat_us))
-                            : submit_one(in, out, lat_us);
+                            : submit_one(in, out, lat_us, nbytes);
     {
       std::lock_guard<std::mutex> g(mu);
       if (--active == 0 && stop) cv_work.notify_all();
@@ -295,7 +295,8 @@ struct Exec {
     return rc;
   }
 
-  int submit_one(const void* const* in, void* out, double* lat_us) {
+  // nbytes (optional): bytes of input k to copy, <= in_bytes[k] (checked by hz_exec_submit_sized)
+  int submit_one(const void* const* in, void* out, double* lat_us, const uint64_t* nbytes = nullptr) {
     const double t0 = now_us();
     int s;
     {
@@ -307,7 +308,7 @@ struct Exec {
     }
     Slot& sl = slots[s];
     for (int k = 0; k < n_in; ++k)
-      if (in && in[k] && in_bytes[k]) std::memcpy(sl.in[k], in[k], in_bytes[k]);
+      if (in && in[k] && in_bytes[k]) std::memcpy(sl.in[k], in[k], nbytes ? nbytes[k] : in_bytes[k]);
     int rc;
     bool spin;
     {
@@ -412,6 +413,16 @@ void hz_exec_batches(void* h, uint64_t* batches) {
 
 int hz_exec_submit(void* h, const void* const* in, void* out, double* lat_us) {
   return static_cast<Exec*>(h)->submit_wait(in, out, lat_us);
+}
+
+// per-request executor only: like hz_exec_submit, copying nbytes[k] (<= in_bytes[k]) of input k; the rest
+// of the pinned input keeps whatever an earlier request left there
+int hz_exec_submit_sized(void* h, const void* const* in, const uint64_t* nbytes, void* out, double* lat_us) {
+  Exec* e = static_cast<Exec*>(h);
+  if (e->rows != 1 || !nbytes) return -1;
+  for (int k = 0; k < e->n_in; ++k)
+    if (nbytes[k] > e->in_bytes[k]) return -2;
+  return e->submit_wait(in, out, lat_us, 1, nbytes);
 }
 
 // dynamic-batching executor only: one request of m (1..rows) consecutive rows, in[k] / out holding

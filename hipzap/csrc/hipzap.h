@@ -87,6 +87,21 @@ int hz_pool_fc_launch(const HzPoolFcParams* p, hipStream_t st);
 int hz_preprocess_launch(const void* src, unsigned short* dst, int N, int Cin, int H, int W, int Cpad,
                          int mode, const float* mean, const float* inv_std, hipStream_t st);
 
+// resize + centre crop + normalise in one launch (vision.hip resize_preprocess_kernel): a uint8 HWC image
+// of any size up to maxH x maxW -> bf16 NHWC8 [B][crop][crop][8]. The resize is torch's antialiased
+// bilinear (triangle filter of support max(in/out, 1), weights normalised by their sum, fp32). The grid
+// depends on B and crop only: the per-request geometry is read from `dims` at run time, so one captured
+// graph serves every image size. Every index is clamped: no header makes a read leave its row of `image`.
+typedef struct HzResizeParams {
+  const unsigned char* image;  // [B][cap_bytes] uint8, a tightly packed H x W x 3 image at each row's start
+  const int* dims;             // [B][8] {H, W, rh, rw, top, left, 0, 0}: source size, resized size, crop origin
+  unsigned short* out;         // [B][crop][crop][8] bf16, channels 3..7 zero
+  int B, crop, maxH, maxW;
+  long long cap_bytes;         // bytes per row of `image`: >= maxH * maxW * 3, a multiple of 16
+  float mean[4], inv_std[4];   // (x / 255 - mean) * inv_std
+} HzResizeParams;
+int hz_resize_preprocess_launch(const HzResizeParams* p, hipStream_t st);
+
 // elementwise helpers
 int hz_cast_f32_bf16(const float* x, unsigned short* y, long n, hipStream_t st);
 int hz_cast_bf16_f32(const unsigned short* x, float* y, long n, hipStream_t st);
@@ -564,7 +579,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(AVGPOOL, 24, HzAvgpoolArgs, hz_avgpool_op, VISION)                    \
   X(PREPROCESS, 25, HzPreprocessArgs, hz_preprocess_op, VISION)           \
   X(STEP_BUMP, 26, HzStepBumpArgs, hz_step_bump_op, LSTM)                 \
-  X(DIAG, 27, HzDiagArgs, hz_diag_op, DIAG)
+  X(DIAG, 27, HzDiagArgs, hz_diag_op, DIAG)                               \
+  X(RESIZE_PREPROCESS, 28, HzResizeParams, hz_resize_preprocess_op, VISION)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM
@@ -652,6 +668,9 @@ void* hz_exec_create_batched(HzProgram* progs, hipStream_t* streams, void** host
 void hz_exec_batches(void* exec, uint64_t* batches);
 int hz_exec_submit(void* exec, const void* const* in, void* out, double* lat_us);
 int hz_exec_submit_rows(void* exec, const void* const* in, int m, void* out, double* lat_us);
+// like hz_exec_submit (per-request executors only), copying nbytes[k] <= in_bytes[k] of input k: a
+// request smaller than its pinned input (an image below the resize plan's maximum) pays for its own bytes
+int hz_exec_submit_sized(void* exec, const void* const* in, const uint64_t* nbytes, void* out, double* lat_us);
 void hz_exec_stats(void* exec, uint64_t* served, uint64_t* polls);
 void hz_exec_destroy(void* exec);
 int hz_exec_bench(void* exec, int clients, int iters, const void* const* in, double* lat_us, double* wall_us);

@@ -287,6 +287,14 @@ static int hz_diag_op(const HzDiagArgs* a, hipStream_t st) {
   return hz_diag_launch(a->kind, a->blocks, a->threads, a->a, a->b, a->bytes, st);
 }
 
+// The resize launcher is referenced weakly: a host-only program that links runtime.cpp with its own
+// stub launchers (tests/native/runtime_host_asan.cpp) need not define it; the library always does
+// (vision.hip), and a missing launcher is an error, not a skipped launch.
+extern "C" __attribute__((weak)) int hz_resize_preprocess_launch(const HzResizeParams* p, hipStream_t st);
+static int hz_resize_preprocess_op(const HzResizeParams* p, hipStream_t st) {
+  return hz_resize_preprocess_launch ? hz_resize_preprocess_launch(p, st) : -102;
+}
+
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {
   switch (kind) {

@@ -287,6 +287,135 @@ __global__ __launch_bounds__(256) void preprocess_u8c3_kernel(const unsigned* __
   }
 }
 
+// ---- resize + centre crop + normalise (HzResizeParams) ----
+// The taps of one output index of torch's antialiased bilinear resize (align_corners = false): source
+// indices [lo, hi), weight(j) = max(0, 1 - |(j - center + 0.5) * inv|), normalised by their sum. Both
+// ends are clamped into [0, in], so a tap index is a valid source index whatever the geometry says.
+struct RszTaps {
+  float center, inv;
+  int lo, hi;
+};
+__device__ __forceinline__ int rsz_index(float v, int lo, int hi) {
+  return min(max((int)fminf(fmaxf(v, 0.f), 1.0e9f), lo), hi);
+}
+__device__ __forceinline__ RszTaps rsz_taps(int i, float scale, int in) {
+  const float support = scale >= 1.f ? scale : 1.f;
+  RszTaps t;
+  t.center = scale * ((float)i + 0.5f);
+  t.inv = scale >= 1.f ? 1.f / scale : 1.f;
+  t.lo = rsz_index(t.center - support + 0.5f, 0, in);
+  t.hi = rsz_index(t.center + support + 0.5f, t.lo, in);
+  return t;
+}
+__device__ __forceinline__ float rsz_weight(const RszTaps& t, int j) {
+  return fmaxf(0.f, 1.f - fabsf(((float)j - t.center + 0.5f) * t.inv));
+}
+__device__ __forceinline__ float rsz_inv_total(const RszTaps& t) {
+  float s = 0.f;
+  for (int j = t.lo; j < t.hi; ++j) s += rsz_weight(t, j);
+  return s > 0.f ? 1.f / s : 0.f;
+}
+
+#define HZ_RSZ_ROWS 8   // output rows per workgroup
+#define HZ_RSZ_UNITS 8  // 16-B staging loads per thread per chunk: 256 * 8 * 16 B = 32 KiB of LDS
+// A workgroup owns HZ_RSZ_ROWS output rows of one image, thread x one output column (3 channels). It
+// walks the source rows the band's vertical taps cover: a chunk of rows is staged in LDS by aligned
+// 16-B loads of only the columns the crop's horizontal taps cover (the request is read zero-copy from
+// pinned host memory: wide requests, each byte once per band), the next chunk's loads are issued into
+// registers before the staged one is consumed. Per source row a thread forms its horizontally filtered
+// pixel from LDS and adds it into the band's output rows with their vertical weights (fp32 throughout;
+// no intermediate image). Geometry comes from dims[b] and is wave-uniform except the thread's own column.
+__global__ __launch_bounds__(256) void resize_preprocess_kernel(const HzResizeParams p) {
+  __shared__ __attribute__((aligned(16))) u32x4 stage[256 * HZ_RSZ_UNITS];
+  constexpr int R = HZ_RSZ_ROWS, U = HZ_RSZ_UNITS;
+  const int t = threadIdx.x, b = blockIdx.y, oy0 = blockIdx.x * R;
+  const int* d = p.dims + (long)b * 8;
+  const int H = min(max(d[0], 1), p.maxH), W = min(max(d[1], 1), p.maxW);
+  const int rh = min(max(d[2], 1), 1 << 16), rw = min(max(d[3], 1), 1 << 16);
+  const int top = min(max(d[4], 0), 1 << 16), left = min(max(d[5], 0), 1 << 16);
+  const float sy = (float)H / (float)rh, sx = (float)W / (float)rw;
+  const unsigned char* img = p.image + (long)b * p.cap_bytes;
+
+  RszTaps ty[R];
+  float ity[R];
+  int yhi = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    ty[r] = rsz_taps(top + oy0 + r, sy, H);
+    if (r > 0 && oy0 + r >= p.crop) ty[r].lo = ty[r].hi = ty[r - 1].hi;  // past the last output row: no taps
+    ity[r] = rsz_inv_total(ty[r]);
+    yhi = max(yhi, ty[r].hi);
+  }
+  const int ylo = ty[0].lo;
+  const RszTaps tx = rsz_taps(left + min(t, p.crop - 1), sx, W);
+  const float itx = rsz_inv_total(tx);
+  // the columns any thread reads: [xlo, xhi) pixels; a staged row holds them from the 16-B boundary below
+  const int xlo = rsz_taps(left, sx, W).lo;
+  const int xhi = max(rsz_taps(left + p.crop - 1, sx, W).hi, xlo);
+  const int upr = ((xhi - xlo) * 3 + 30) >> 4;  // 16-B units per staged row (launcher: <= 256 * U)
+  const int NR = (256 * U) / upr;                // rows per chunk
+  const long row_bytes = (long)W * 3;
+
+  float acc[R][3];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.f;
+
+  u32x4 reg[U];
+  auto fetch = [&](int y0) {
+    const int nr = min(NR, yhi - y0);
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+      const int u = t + 256 * i;
+      const int row = u / upr, cu = u - row * upr;
+      reg[i] = u32x4{0u, 0u, 0u, 0u};
+      if (row < nr) {
+        const long a = (((long)(y0 + row) * row_bytes + (long)xlo * 3) & ~15L) + (long)cu * 16;
+        if (a + 16 <= p.cap_bytes) reg[i] = *reinterpret_cast<const u32x4*>(img + a);
+      }
+    }
+  };
+  if (ylo < yhi) fetch(ylo);
+  const unsigned char* lds = reinterpret_cast<const unsigned char*>(stage);
+  for (int y0 = ylo; y0 < yhi; y0 += NR) {
+#pragma unroll
+    for (int i = 0; i < U; ++i) stage[t + 256 * i] = reg[i];
+    __syncthreads();
+    if (y0 + NR < yhi) fetch(y0 + NR);
+    const int nr = min(NR, yhi - y0);
+    for (int row = 0; row < nr; ++row) {
+      const int y = y0 + row;
+      const int off = (int)(((long)y * row_bytes + (long)xlo * 3) & 15L);
+      const unsigned char* s = lds + row * upr * 16 + off + (tx.lo - xlo) * 3;
+      float h0 = 0.f, h1 = 0.f, h2 = 0.f;
+      for (int j = tx.lo; j < tx.hi; ++j, s += 3) {
+        const float w = rsz_weight(tx, j);
+        h0 += w * (float)s[0];
+        h1 += w * (float)s[1];
+        h2 += w * (float)s[2];
+      }
+      h0 *= itx, h1 *= itx, h2 *= itx;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const float wy = (y >= ty[r].lo && y < ty[r].hi) ? rsz_weight(ty[r], y) * ity[r] : 0.f;
+        acc[r][0] += wy * h0;
+        acc[r][1] += wy * h1;
+        acc[r][2] += wy * h2;
+      }
+    }
+    __syncthreads();
+  }
+  if (t >= p.crop) return;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int oy = oy0 + r;
+    if (oy >= p.crop) break;
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (acc[r][c] * (1.0f / 255.0f) - p.mean[c]) * p.inv_std[c];
+    *reinterpret_cast<u32x4*>(p.out + (((long)b * p.crop + oy) * p.crop + t) * 8) = pack8(v);
+  }
+}
+
 // mode 2 (ViT patch embedding as a plain GEMM): src fp32 NCHW -> bf16 patch rows
 // [N * (H/P) * (W/P)][Cin * P * P], column (c, ky, kx) = the flattened [D][Cin][P][P] conv weight's
 // K order, so the patch projection is a row-major GEMM with K = Cin * P * P (768 at P = 16, Cin = 3)
@@ -401,6 +530,18 @@ extern "C" int hz_preprocess_launch(const void* src, unsigned short* dst, int N,
   }
   HZ_LAUNCH(preprocess_kernel, dim3((total + 255) / 256), dim3(256), 0, st, src, dst, N, Cin, H, W, Cpad,
                      mode, mean, inv_std);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_resize_preprocess_launch(const HzResizeParams* pp, hipStream_t st) {
+  const HzResizeParams& p = *pp;
+  if (p.B < 1 || p.crop < 1 || p.crop > 256 || p.maxH < 1 || p.maxW < 1 || !p.image || !p.dims || !p.out) return -1;
+  // a staged row (maxW * 3 bytes + alignment slack) must fit the kernel's LDS chunk
+  if (((long)p.maxW * 3 + 30) >> 4 > 256 * HZ_RSZ_UNITS) return -1;
+  if (p.cap_bytes % 16 || (long long)p.maxH * p.maxW * 3 > p.cap_bytes) return -1;
+  if (((uintptr_t)p.image & 15) || ((uintptr_t)p.out & 15) || ((uintptr_t)p.dims & 3)) return -1;
+  const dim3 grid((p.crop + HZ_RSZ_ROWS - 1) / HZ_RSZ_ROWS, p.B);
+  HZ_LAUNCH(resize_preprocess_kernel, grid, dim3(256), 0, st, p);
   return (int)hipGetLastError();
 }
 

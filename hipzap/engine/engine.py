@@ -285,6 +285,35 @@ class Engine:
             kcheck.check(f"{self.model} infer")
         return self._post(out)
 
+    @property
+    def resize(self) -> dict | None:
+        """{"resize", "crop", "max_h", "max_w"} of a resize engine (``arch_kw["resize"]``), else None."""
+        return (getattr(self.graph, "meta", None) or {}).get("resize")
+
+    def infer_image(self, img) -> torch.Tensor:
+        """One request of a RESIZE engine: ``img`` is a uint8 [H, W, 3] image of any size within the
+        engine's maximum (tensor or array), or a list of up to ``batch`` of them. The geometry header
+        is built here; only the image's own bytes are copied into the pinned request slot."""
+        rz = self.resize
+        if rz is None:
+            raise RuntimeError("infer_image needs a resize engine (arch_kw resize=(resize, crop, max_h, max_w))")
+        from ..ops.vision import pack_images, resize_dims
+        imgs = list(img) if isinstance(img, (list, tuple)) else [img]
+        n = len(imgs)
+        ex = self.executor() if self.batch == 1 else None
+        if ex is not None and n == 1:
+            im = torch.as_tensor(imgs[0])
+            if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[-1] != 3:
+                raise ValueError(f"an image is uint8 [H, W, 3], got {im.dtype} {tuple(im.shape)}")
+            im = im.cpu().contiguous()
+            dims = torch.tensor(resize_dims(im.shape[0], im.shape[1], rz["resize"], rz["crop"], rz["max_h"],
+                                            rz["max_w"]), dtype=torch.int32)
+            out = torch.empty_like(self.contexts[0].host_output)
+            ex.submit_sized([im.data_ptr(), dims.data_ptr()], [im.numel(), 32], out.data_ptr())
+            return self._post(out)
+        buf, dims = pack_images(imgs, rz["resize"], rz["crop"], rz["max_h"], rz["max_w"], batch=self.batch)
+        return self.infer([buf, dims])[:n]
+
     def _post(self, out):
         takes_meta = getattr(self, "_post_meta", None)
         if takes_meta is None:  # decided once (a TypeError per request cost ~1 us)

@@ -256,6 +256,9 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
         "ctx_dev_bytes": regs.size[1], "ctx_host_bytes": regs.size[2], "blob_bytes": blob_len,
         "arena_bytes": ctx.arena_bytes,
     }
+    rz = (getattr(g, "meta", None) or {}).get("resize")
+    if rz:  # a resize plan: inputs are the packed image bytes and the geometry header (lite.PlanEngine.infer_image)
+        meta["resize"] = dict(rz)
     emb = params.get("emb")
     if emb is not None and hasattr(emb, "word"):  # BERT-style text plan: inputs ids / types / additive mask
         meta.update({"kind": "text", "seq_len": int(g.shape(g.inputs[0])[0]) // batch,
@@ -306,10 +309,12 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
 
 def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch: int = 1, contexts: int = 1,
                            input_uint8: bool | None = None, dp_shard: int | None = None,
-                           seq_len: int | None = None, **kw) -> str:
+                           seq_len: int | None = None, resize=None, **kw) -> str:
     """``torch.load`` the checkpoint, pack it on the CPU and write its plan image (deploy time,
     ``hipzap plan``); the plan is keyed to the checkpoint's identity (size, mtime, sampled hash).
-    ``seq_len``: the captured sequence length of a text model (default: the adapter's, 128)."""
+    ``seq_len``: the captured sequence length of a text model (default: the adapter's, 128).
+    ``resize``: ``(resize, crop, max_h, max_w)`` writes a RESIZE plan (``<ckpt>.rz.hzplan`` by default):
+    requests are uint8 images of any size up to the maximum (models/resnet.py build_graph)."""
     from .packfile import source_stamp
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
@@ -321,6 +326,12 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
         if "seq_len" not in arch_kw:
             raise ValueError(f"{model} has no sequence length to set")
         arch_kw["seq_len"] = int(seq_len)
+    if resize is not None:
+        if not model.startswith("resnet"):
+            raise ValueError(f"resize plans cover the ResNet family, not {model}")
+        arch_kw["resize"] = [int(v) for v in resize]
+        input_uint8 = False
+        path = path or plan_path(ckpt, "rz")
     if input_uint8 is None:
         input_uint8 = model.startswith("resnet")
     if input_uint8 and model.startswith("resnet"):

@@ -382,6 +382,14 @@ class ExecContext:
             prm = vision.PreprocessArgs(addr(n.inputs[0]), addr(n.outputs[0]), N.ptr(mean), N.ptr(std), nb, cin, h, w,
                                         cpad, mode)
             N.prog_add(lib, self.prog, N.HZ_K_PREPROCESS, prm, n.slot, "add_preprocess")
+        elif n.kind == "resize_preprocess":  # any-size uint8 image + geometry header -> bf16 NHWC8 crop
+            a = n.attrs
+            nb, crop, _, cpad = g.shape(n.outputs[0])
+            assert cpad == 8 and crop == a["crop"] and g.shape(n.inputs[0]) == (
+                nb, vision.resize_cap_bytes(a["max_h"], a["max_w"])) and g.shape(n.inputs[1]) == (nb, 8)
+            prm = vision.resize_params(addr(n.inputs[0]), addr(n.inputs[1]), addr(n.outputs[0]), nb, crop,
+                                       a["max_h"], a["max_w"], a.get("mean"), a.get("std"))
+            N.prog_add(lib, self.prog, N.HZ_K_RESIZE_PREPROCESS, prm, n.slot, "add_resize_preprocess")
         elif n.kind == "patchify":  # preprocess mode 2: fp32 NCHW -> bf16 patch rows (Cpad = patch)
             nb, cin, h, w = g.tensors[n.inputs[0]].shape
             mean = std = None

@@ -54,6 +54,17 @@ def run_graph_reference(g: Graph, params: dict, inputs: list, bf16_acts: bool = 
             if n.attrs.get("mean") is not None:
                 x = (x - torch.tensor(n.attrs["mean"])) / torch.tensor(n.attrs["std"])
             store(n.outputs[0], F.pad(x, (0, cpad - x.shape[-1])))
+        elif k == "resize_preprocess":
+            from ..ops.vision import resize_preprocess_reference
+            a = n.attrs
+            image, dims = vals[n.inputs[0]], vals[n.inputs[1]]
+            rows = []
+            for b in range(image.shape[0]):
+                H, W = int(dims[b, 0]), int(dims[b, 1])
+                img = image[b, : H * W * 3].reshape(H, W, 3)
+                rows.append(resize_preprocess_reference(img, a.get("mean"), a.get("std"), a["resize"], a["crop"],
+                                                        g.shape(n.outputs[0])[-1]))
+            store(n.outputs[0], torch.stack(rows))
         elif k == "patchify":
             x = vals[n.inputs[0]].float()
             if n.attrs.get("mean") is not None:

@@ -50,6 +50,20 @@ class Executor:
             raise RuntimeError(f"executor request failed ({rc})")
         return lat.value * 1e-3
 
+    def submit_sized(self, in_ptrs: list, nbytes: list, out_ptr: int) -> float:
+        """Like :meth:`submit`, copying only ``nbytes[k]`` (<= the pinned input's size) of input k: a
+        request smaller than the plan's input (an image below a resize plan's maximum). Per-request
+        executors only. Returns latency in ms."""
+        if self.rows != 1 or len(nbytes) != self.n_in or any(int(b) > cap for b, cap in zip(nbytes, self.in_bytes)):
+            raise ValueError(f"submit_sized: {list(nbytes)} bytes for inputs of {self.in_bytes} (rows {self.rows})")
+        arr = (C.c_void_p * self.n_in)(*in_ptrs)
+        nb = (C.c_uint64 * self.n_in)(*[int(b) for b in nbytes])
+        lat = C.c_double()
+        rc = N.lib().hz_exec_submit_sized(self._h, arr, nb, out_ptr, C.byref(lat))
+        if rc:
+            raise RuntimeError(f"executor request failed ({rc})")
+        return lat.value * 1e-3
+
     def submit_rows(self, in_ptrs: list, m: int, out_ptr: int) -> float:
         """Dynamic batching only: one request of ``m`` (1..rows) consecutive rows from this one
         thread (``in_ptrs[k]`` holds m rows of input k, ``out_ptr`` receives m output rows); the

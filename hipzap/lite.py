@@ -492,6 +492,71 @@ class PlanEngine:
         self._check(rc, "infer")
         return out
 
+    @property
+    def resize(self) -> dict | None:
+        """{"resize", "crop", "max_h", "max_w"} of a resize plan, else None (plans without the key
+        take exactly their input's bytes, as before)."""
+        return self.meta.get("resize")
+
+    def infer_image(self, img, ctx: int | None = None) -> array.array:
+        """One request of a RESIZE plan: ``img`` is a uint8 [H, W, 3] image of any size within the
+        plan's maximum (numpy array or CPU tensor; or ``(buffer, H, W)`` for raw bytes), or a list of
+        up to ``batch`` of them for a batch plan. Builds the geometry header the kernel reads,
+        copies only the images' own bytes into the pinned request slot and returns the flat float32
+        logits of the submitted images. Larger images are refused with the limit in the message."""
+        rz = self.resize
+        if rz is None:
+            raise PlanError(f"{self.path}: not a resize plan (export it with `hipzap plan --resize`)")
+        from .imgeom import resize_dims
+        imgs = list(img) if isinstance(img, list) else [img]
+        batch = int(self.in_specs[0]["shape"][0])
+        if not 1 <= len(imgs) <= batch:
+            raise PlanError(f"{len(imgs)} images for a plan of batch {batch}")
+        bufs, heads = [], []
+        for im in imgs:
+            if isinstance(im, tuple):
+                raw, H, W = im
+            else:
+                shape = tuple(im.shape)
+                if len(shape) != 3 or shape[2] != 3 or "uint8" not in str(im.dtype):
+                    raise PlanError(f"an image is uint8 [H, W, 3], got {im.dtype} {shape}")
+                raw, (H, W) = im, shape[:2]
+            try:
+                heads.append(resize_dims(H, W, rz["resize"], rz["crop"], rz["max_h"], rz["max_w"]))
+            except ValueError as e:
+                raise PlanError(str(e)) from None
+            addr, nb, keep = _in_buffer(raw)
+            if nb != H * W * 3:
+                raise PlanError(f"image buffer is {nb} bytes, {H}x{W}x3 is {H * W * 3}")
+            bufs.append((addr, nb, keep))
+        while len(heads) < batch:  # a partial batch: the padding rows re-read the last header's (stale) row
+            heads.append(heads[-1])
+        dims = array.array("i", [v for h in heads for v in h])
+        daddr, _ = dims.buffer_info()
+        out = array.array(_TYPECODE[self.out_spec["dtype"]], bytes(self.out_spec["bytes"]))
+        oaddr, _ = out.buffer_info()
+        img_spec, dim_spec = self.in_specs
+        ex = self.executor() if ctx is None and batch == 1 else None
+        if ex is not None:
+            ex.submit_sized([bufs[0][0], daddr], [bufs[0][1], 32], oaddr)
+        else:
+            if getattr(self, "_bexec", None) is not None:
+                raise PlanError("this plan engine serves through the dynamic-batching executor")
+            i = self._pick() if ctx is None else ctx
+            cap = img_spec["bytes"] // batch
+            with self._locks[i]:
+                host = lib().hz_plan_host(self._h, i)
+                for r, (addr, nb, _) in enumerate(bufs):
+                    C.memmove(host + img_spec["off"] + r * cap, addr, nb)
+                C.memmove(host + dim_spec["off"], daddr, 32 * batch)
+                rc = lib().hz_plan_infer(self._h, i, None, 0, 0, oaddr, self.out_spec["off"], self.out_spec["bytes"])
+            self._check(rc, "infer")
+        del bufs
+        if len(imgs) < batch:
+            per = len(out) // batch
+            out = out[: per * len(imgs)]
+        return out
+
     def infer(self, x, ctx: int | None = None):
         """Like :meth:`infer_raw`, shaped ``[batch, classes]`` as a numpy array when numpy is
         importable (it is not needed on the cold path: import happens on first use)."""

@@ -239,24 +239,46 @@ def _conv_stride_pad(name: str, wshape, bottleneck: bool) -> tuple[int, int]:
 
 
 def build_graph(arch: str, batch: int, num_classes: int = 1000, image: int = 224,
-                input_uint8: bool = False, side_stream: bool = False, fuse_head: bool = True) -> Graph:
+                input_uint8: bool = False, side_stream: bool = False, fuse_head: bool = True,
+                resize=None) -> Graph:
     """Lower ResNet to a static kernel graph for a fixed batch size.
 
     ``side_stream`` puts the downsample conv on a forked stream. Off by default: measured on
     MI355X (scripts/diag_runtime.py), a multi-stream hipGraph costs ~370 us of host
     submission per replay vs ~30 us single-stream, which dwarfs the overlap it buys.
+
+    ``resize``: None, or ``(resize, crop, max_h, max_w)`` for a RESIZE graph: the request is a uint8
+    HWC image of any size up to max_h x max_w (input ``image``: [batch, cap_bytes] bytes with the image
+    packed at the start of its row, input ``dims``: [batch, 8] int32 geometry header, see
+    ``ops/vision.py pack_images``), and the first node resizes the shorter side to ``resize``
+    (antialiased bilinear), centre-crops ``crop`` x ``crop`` and normalises, in one launch
+    (csrc/vision.hip resize_preprocess_kernel). Everything after it is the fixed-shape graph.
     """
     block, layers = ARCHS[arch]
     g = Graph(f"{arch}_bs{batch}")
-    if input_uint8:
+    if resize is not None:
+        from ..imgeom import resize_cap_bytes
+        rs, crop, max_h, max_w = (int(v) for v in resize)
+        if crop != image:
+            raise ValueError(f"resize plan crops {crop}, the model takes {image}")
+        x_in = g.tensor((batch, resize_cap_bytes(max_h, max_w)), torch.uint8, "image", external=True)
+        dims = g.tensor((batch, 8), torch.int32, "dims", external=True)
+        g.inputs += [x_in, dims]
+        x = g.tensor((batch, image, image, 8), name="nhwc")
+        g.add("resize_preprocess", [x_in, dims], [x], mean=IMAGENET_MEAN, std=IMAGENET_STD, resize=rs, crop=crop,
+              max_h=max_h, max_w=max_w)
+        g.meta = dict(getattr(g, "meta", None) or {}, resize={"resize": rs, "crop": crop, "max_h": max_h,
+                                                               "max_w": max_w})
+    elif input_uint8:
         x_in = g.tensor((batch, image, image, 3), torch.uint8, "image", external=True)
         mean, std = IMAGENET_MEAN, IMAGENET_STD
     else:
         x_in = g.tensor((batch, 3, image, image), torch.float32, "input", external=True)
         mean = std = None
-    g.inputs.append(x_in)
-    x = g.tensor((batch, image, image, 8), name="nhwc")
-    g.add("preprocess", [x_in], [x], mean=mean, std=std)
+    if resize is None:
+        g.inputs.append(x_in)
+        x = g.tensor((batch, image, image, 8), name="nhwc")
+        g.add("preprocess", [x_in], [x], mean=mean, std=std)
 
     def conv(src, name, cout, k, stride, pad, act="relu", res=None, slot=0, out_f32=False, ext=False):
         nb, h, w, _ = g.shape(src)

@@ -6,6 +6,7 @@ import ctypes as C
 import torch
 
 from .. import _native as N
+from ..imgeom import resize_cap_bytes, resize_dims, resize_geometry  # noqa: F401  (the shared, torch-free geometry)
 
 K_POOL_FC = N.HZ_K_POOL_FC
 
@@ -30,8 +31,81 @@ class PreprocessArgs(C.Structure):
                 ("mode", C.c_int)]
 
 
+@N.params_of("HZ_K_RESIZE_PREPROCESS")
+class ResizeParams(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("dims", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("crop", C.c_int),
+                ("maxH", C.c_int), ("maxW", C.c_int), ("cap_bytes", C.c_longlong), ("mean", C.c_float * 4),
+                ("inv_std", C.c_float * 4)]
+
+
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+# ---------------------------------------------------------------- resize + centre crop + normalise
+def resize_preprocess_reference(img_u8: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize: int = 256,
+                                crop: int = 224, cpad: int = 8) -> torch.Tensor:
+    """fp32 oracle of the resize kernel: one uint8 [H, W, 3] image -> [crop, crop, cpad] float32.
+    Antialiased bilinear resize of the float image on the CPU, centre crop, / 255, (x - mean) / std,
+    channels zero-padded to ``cpad``."""
+    img = torch.as_tensor(img_u8)
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[-1] == 3, tuple(img.shape)
+    H, W = img.shape[:2]
+    rh, rw, top, left = resize_geometry(H, W, resize, crop)
+    x = img.cpu().permute(2, 0, 1).float()[None]
+    y = torch.nn.functional.interpolate(x, size=(rh, rw), mode="bilinear", antialias=True, align_corners=False)
+    y = y[0, :, top: top + crop, left: left + crop].permute(1, 2, 0) / 255.0
+    if mean is not None:
+        y = (y - torch.tensor(mean, dtype=torch.float32)) / torch.tensor(std, dtype=torch.float32)
+    return torch.nn.functional.pad(y, (0, cpad - 3))
+
+
+def resize_params(image_ptr: int, dims_ptr: int, out_ptr: int, batch: int, crop: int, max_h: int, max_w: int,
+                  mean=None, std=None) -> ResizeParams:
+    """Bound HzResizeParams; the normalisation constants are the standalone preprocess kernel's
+    (inv_std = 1 / std in fp32)."""
+    prm = ResizeParams(image_ptr, dims_ptr, out_ptr, batch, crop, max_h, max_w, resize_cap_bytes(max_h, max_w))
+    mu = torch.tensor(mean if mean is not None else (0.0, 0.0, 0.0), dtype=torch.float32)
+    inv = 1.0 / torch.tensor(std if std is not None else (1.0, 1.0, 1.0), dtype=torch.float32)
+    for c in range(3):
+        prm.mean[c], prm.inv_std[c] = float(mu[c]), float(inv[c])
+    prm.inv_std[3] = 1.0
+    return prm
+
+
+def pack_images(images, resize: int, crop: int, max_h: int, max_w: int, batch: int | None = None):
+    """uint8 [H, W, 3] images (tensors or arrays, any sizes within the maximum) -> the resize plan's two
+    request inputs on the host: ``image`` [B, cap_bytes] uint8 with each image packed at its row's
+    start, ``dims`` [B, 8] int32. Rows beyond ``len(images)`` repeat the last header over an unwritten
+    row (a partial batch)."""
+    imgs = [torch.as_tensor(im) for im in images]
+    b = batch or len(imgs)
+    if not 1 <= len(imgs) <= b:
+        raise ValueError(f"{len(imgs)} images for a batch of {b}")
+    buf = torch.zeros(b, resize_cap_bytes(max_h, max_w), dtype=torch.uint8)
+    dims = torch.zeros(b, 8, dtype=torch.int32)
+    for i in range(b):
+        im = imgs[min(i, len(imgs) - 1)]
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[-1] != 3:
+            raise ValueError(f"an image is uint8 [H, W, 3], got {im.dtype} {tuple(im.shape)}")
+        dims[i] = torch.tensor(resize_dims(im.shape[0], im.shape[1], resize, crop, max_h, max_w), dtype=torch.int32)
+        if i < len(imgs):
+            buf[i, : im.numel()] = im.reshape(-1)
+    return buf, dims
+
+
+def resize_preprocess(image: torch.Tensor, dims: torch.Tensor, crop: int, max_h: int, max_w: int, mean=None,
+                      std=None) -> torch.Tensor:
+    """Eager launch of the resize kernel: ``image`` [B, cap_bytes] uint8 and ``dims`` [B, 8] int32 on
+    the device (or pinned host memory) -> bf16 [B, crop, crop, 8]."""
+    b = image.shape[0]
+    assert image.dtype == torch.uint8 and image.shape == (b, resize_cap_bytes(max_h, max_w)), tuple(image.shape)
+    assert dims.dtype == torch.int32 and dims.shape == (b, 8) and image.is_contiguous() and dims.is_contiguous()
+    dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty(b, crop, crop, 8, device=dev, dtype=torch.bfloat16)
+    prm = resize_params(image.data_ptr(), dims.data_ptr(), out.data_ptr(), b, crop, max_h, max_w, mean, std)
+    N.check(N.lib().hz_launch_kernel(N.HZ_K_RESIZE_PREPROCESS, C.byref(prm), N.stream_ptr()), "resize_preprocess")
+    return out
 
 
 def maxpool_nhwc(x: torch.Tensor, k=3, stride=2, pad=1) -> torch.Tensor:

@@ -142,36 +142,78 @@ def inference():
     return _json({"response": {"text": text}})
 
 
+IMAGE_TYPES = ("image/jpeg", "image/png")
+
+
+def decode_image(data: bytes):
+    """An encoded image file (JPEG, PNG, ...) -> uint8 [H, W, 3] RGB array. PIL is imported here, on
+    the first such request; without it the answer is 415."""
+    try:
+        from PIL import Image
+    except ImportError:
+        from werkzeug.exceptions import UnsupportedMediaType
+        raise UnsupportedMediaType("encoded images need Pillow on the server; send image_b64 + shape") from None
+    try:
+        with Image.open(io.BytesIO(data)) as im:
+            return np.asarray(im.convert("RGB"), dtype=np.uint8)
+    except Exception as e:  # noqa: BLE001 - PIL raises several types for a body that is no image
+        raise ValueError(f"request body is not a decodable image: {e}") from None
+
+
 def decode_input(req):
     """-> (model, numpy array). Accepted request bodies:
+    * ``image/jpeg`` / ``image/png``: an encoded image file of any size (decoded with PIL to RGB);
+    * JSON ``{"image": base64 of an encoded image file}``: the same;
     * ``application/octet-stream``: a ``.npy`` array (``np.save``; no pickles);
     * JSON ``{"inputs": nested list, "model": ...}`` (float tensor, NCHW or CHW);
     * JSON ``{"image_b64": base64 uint8 HWC bytes, "shape": [H, W, 3]}`` (or [N, H, W, 3]);
     * JSON ``{"tensor_b64": base64 float32 bytes, "shape": [...]}``.
     uint8 arrays are images (HWC / NHWC), served as is by plan-backed models (normalised on
-    device) and normalised to NCHW float for the others (:func:`to_model_input`)."""
+    device; a resize plan takes any size) and normalised to NCHW float for the others
+    (:func:`to_model_input`, which first resizes and crops an image of another size on the host)."""
     model = req.args.get("model")
-    if req.mimetype == "application/octet-stream":
+    if req.mimetype in IMAGE_TYPES:
+        arr = decode_image(req.get_data())
+    elif req.mimetype == "application/octet-stream":
         arr = np.load(io.BytesIO(req.get_data()), allow_pickle=False)
     else:
         body = req.get_json(force=True, silent=False)
         model = body.get("model", model)
-        if "inputs" in body:
+        if "image" in body:
+            arr = decode_image(base64.b64decode(body["image"]))
+        elif "inputs" in body:
             arr = np.asarray(body["inputs"], dtype=np.float32)
         elif "tensor_b64" in body:
             arr = np.frombuffer(base64.b64decode(body["tensor_b64"]), dtype=np.float32).reshape(body["shape"])
         elif "image_b64" in body:
             arr = np.frombuffer(base64.b64decode(body["image_b64"]), dtype=np.uint8).reshape(body["shape"])
         else:
-            raise ValueError("request needs one of: inputs, tensor_b64, image_b64 (or an .npy body)")
+            raise ValueError("request needs one of: image, inputs, tensor_b64, image_b64 (or an image / .npy body)")
     if arr.dtype == np.uint8 and arr.ndim == 3:
         arr = arr[None]
     return model or get_server().settings.default_model, arr
 
 
-def to_model_input(arr):
-    """numpy request array -> float32 NCHW torch tensor for the torch-built backends."""
+def check_image_size(arr, rz) -> None:
+    """ValueError (-> 400) naming the limit for uint8 images above ``rz``'s maximum."""
+    _, _, max_h, max_w = rz
+    if arr.shape[1] > max_h or arr.shape[2] > max_w:
+        raise ValueError(f"image {arr.shape[1]}x{arr.shape[2]} exceeds the maximum of {max_h}x{max_w} "
+                         f"(height x width) this model is served with")
+
+
+def to_model_input(arr, rz=None):
+    """numpy request array -> float32 NCHW torch tensor for the torch-built backends. ``rz``
+    (resize, crop, max_h, max_w): uint8 images that are not crop x crop already go through the
+    resize oracle on the host (ops/vision.py resize_preprocess_reference), the same transform a
+    resize plan runs on the GPU."""
     import torch
+    if arr.dtype == np.uint8 and rz is not None and arr.ndim == 4 and tuple(arr.shape[1:3]) != (rz[1], rz[1]):
+        from ..ops.vision import resize_preprocess_reference
+        check_image_size(arr, rz)
+        x = torch.stack([resize_preprocess_reference(torch.from_numpy(np.array(a)), resize=rz[0],
+                                                     crop=rz[1])[..., :3] for a in arr])
+        return x.permute(0, 3, 1, 2).contiguous()
     if arr.dtype == np.uint8:  # NHWC image bytes -> normalised NCHW float
         # in numpy: torch's multi-threaded elementwise ops on this request thread would start an
         # OpenMP team per WSGI thread, spinning against the model's own thread pool
@@ -252,7 +294,11 @@ def predict():
         logits = None if backend.probs else out
         probs = out if backend.probs else softmax_np(out)
     else:
-        x = to_model_input(arr)
+        prz = getattr(backend, "resize", None)  # a resize plan refused the image: above its maximum
+        if prz is not None and arr.dtype == np.uint8 and arr.ndim == 4:
+            check_image_size(arr, (prz["resize"], prz["crop"], prz["max_h"], prz["max_w"]))
+        with phase("preprocess"):
+            x = to_model_input(arr, s.resize_spec(model))
         with phase("infer"):
             lg = backend(x)
         logits = lg.float().numpy()

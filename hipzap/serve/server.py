@@ -250,6 +250,16 @@ class ModelServer:
     def spec(self, name: str) -> ModelSpec:
         return self.settings.models.get(name) or ModelSpec(name=name)
 
+    def resize_spec(self, name: str) -> tuple:
+        """(resize, crop, max_h, max_w) that uint8 images of another size than the model's go through:
+        ``extra.resize`` of the model's settings block (an int, or {"resize", "crop", "max_image"}), else
+        the ImageNet evaluation transform (256 -> 224) up to 1024 x 1024."""
+        from ..imgeom import resize_spec
+        rz = self.spec(name).extra.get("resize") or 256
+        if isinstance(rz, dict):
+            return resize_spec(rz.get("resize", 256), rz.get("crop", 224), rz.get("max_image"))
+        return resize_spec(rz, 224, None)
+
     def _load_sd(self, spec: ModelSpec):
         """A state_dict (random-init demo weights) or the local path of the fetched checkpoint
         (backends torch.load it, or use its packed copy on the GPU)."""
@@ -316,11 +326,13 @@ class ModelServer:
         from ..lite import plan_usable, read_meta
         from ..engine.packfile import same_source
         ckpt = self.store.fetch(spec.key)
-        path = ckpt + ".hzplan"
+        # "resize" in the model's settings block: the resize plan (`hipzap plan --resize`, <ckpt>.rz.hzplan)
+        suffix = ".rz.hzplan" if spec.extra.get("resize") else ".hzplan"
+        path = ckpt + suffix
         fetched = False
         if not os.path.exists(path):
             try:  # published next to the checkpoint in the store (its cache path is <ckpt>.hzplan)
-                path = self.store.fetch(spec.key + ".hzplan")
+                path = self.store.fetch(spec.key + suffix)
                 fetched = True
             except Exception:  # noqa: BLE001 - no plan in the store: the checkpoint path serves
                 return None
@@ -440,7 +452,9 @@ class PlanVisionBackend:
         self.engine = PlanEngine(plan, device=device, contexts=max(1, spec.contexts), eager_contexts=1,
                                  read_blob=comm is None or comm.rank == 0, fill_blob=fill, capture="lazy")
         self.meta = self.engine.meta
-        self.in_shape = tuple(self.meta["inputs"][0]["shape"])  # [B, H, W, 3] uint8
+        # a resize plan (`hipzap plan --resize`): requests are uint8 images of any size up to its maximum
+        self.resize = self.meta.get("resize")
+        self.in_shape = tuple(self.meta["inputs"][0]["shape"])  # [B, H, W, 3] uint8 ([B, cap_bytes]: resize plan)
         self.batch = self.in_shape[0]
         self.probs = bool(self.meta.get("probs"))
         self.num_labels = self.meta["output"].get("num_labels") or self.meta["output"]["shape"][-1]
@@ -452,11 +466,27 @@ class PlanVisionBackend:
         threading.Thread(target=self.engine.ensure_contexts, daemon=True, name=f"{name}-contexts").start()
 
     def accepts_u8(self, shape) -> bool:
+        if self.resize is not None:  # any [N, H, W, 3] within the plan's maximum
+            return len(shape) == 4 and shape[3] == 3 and 1 <= shape[1] <= self.resize["max_h"] \
+                and 1 <= shape[2] <= self.resize["max_w"]
         return len(shape) == 4 and tuple(shape[1:]) == self.in_shape[1:]
 
-    def infer_u8(self, imgs):
-        """``imgs``: uint8 numpy array [N, H, W, 3] -> numpy [N, classes] (logits or probs)."""
+    def _infer_images(self, imgs):
         import numpy as np
+        n, B = len(imgs), self.batch
+        out = np.empty((n, self.num_labels), np.float32)
+        for i in range(0, n, B):
+            chunk = [np.ascontiguousarray(im) for im in imgs[i: i + B]]
+            y = np.frombuffer(self.engine.infer_image(chunk if B > 1 else chunk[0]), np.float32)
+            out[i: i + len(chunk)] = y.reshape(len(chunk), -1)[:, : self.num_labels]
+        return out
+
+    def infer_u8(self, imgs):
+        """``imgs``: uint8 numpy array [N, H, W, 3] -> numpy [N, classes] (logits or probs). With a
+        resize plan also a list of [H, W, 3] arrays of different sizes."""
+        import numpy as np
+        if self.resize is not None:
+            return self._infer_images(list(imgs))
         n = imgs.shape[0]
         out = np.empty((n, self.num_labels), np.float32)
         B = self.batch
@@ -474,7 +504,7 @@ class PlanVisionBackend:
         checkpoint (the plan's source), built on first use."""
         with self._torch_lock:
             if self._torch is None:
-                ckpt = self.plan[: -len(".hzplan")]
+                ckpt = self.plan[: -len(".rz.hzplan" if self.plan.endswith(".rz.hzplan") else ".hzplan")]
                 if not os.path.exists(ckpt):
                     raise ValueError(f"{self.name} is served from a plan image: send uint8 HWC images "
                                      f"{list(self.in_shape[1:])} (image_b64 or a uint8 .npy)")
