@@ -251,6 +251,12 @@ def _load():
     PP_ = C.POINTER(c_void_p)
     _sig(lib, "hz_exec_create", P, PP_, PP_, PP_, C.POINTER(U64), c_int, PP_, U64, c_int)
     _sig(lib, "hz_exec_create_batched", P, PP_, PP_, PP_, C.POINTER(U64), c_int, PP_, U64, c_int, c_int, D, c_int)
+    _sig(lib, "hz_exec_set_input_kind", c_int, P, c_int, c_int)
+    _sig(lib, "hz_reqslot_probe", c_int)
+    _sig(lib, "hz_reqslot_alloc", c_int, U64, PP_, PP_, C.POINTER(c_int))
+    _sig(lib, "hz_reqslot_free", c_int, P, c_int)
+    _sig(lib, "hz_reqslot_write", None, P, P, U64, U64)
+    _sig(lib, "hz_reqslot_copy_bench", c_int, PP_, P, U64, c_int, c_int, c_int, C.POINTER(D))
     _sig(lib, "hz_exec_batches", None, P, C.POINTER(U64))
     _sig(lib, "hz_exec_submit", c_int, P, PP_, P, C.POINTER(D))
     _sig(lib, "hz_exec_submit_rows", c_int, P, PP_, c_int, P, C.POINTER(D))
@@ -316,6 +322,24 @@ def experiments() -> bool:
     """The loaded library carries the HZ_EXPERIMENTS kernels (M32 / LN-fold GEMM tiles, LM ring variants):
     ``python -m hipzap.build --experiments``, ``HIPZAP_LIB=.../libhipzap_exp.so``."""
     return bool(lib().hz_experiments())
+
+
+REQSLOT_PINNED, REQSLOT_DEVICE = 0, 1  # HZ_REQSLOT_* (csrc/hipzap.h)
+
+
+def reqslot_alloc(nbytes: int):
+    """A context's request slot (csrc/runtime.cpp ``hz_reqslot_alloc``): ``(dev, host, kind)`` --
+    the address kernels read, the address the CPU writes, ``REQSLOT_DEVICE`` (host-writable device
+    memory) or ``REQSLOT_PINNED`` (the fallback: pinned host memory, dev == host). None when
+    neither could be allocated (no HIP device)."""
+    dev, host, kind = c_void_p(), c_void_p(), c_int(0)
+    if lib().hz_reqslot_alloc(int(nbytes), C.byref(dev), C.byref(host), C.byref(kind)) != 0 or not dev.value:
+        return None
+    return dev.value, host.value, kind.value
+
+
+def reqslot_free(dev: int, kind: int) -> None:
+    lib().hz_reqslot_free(dev, kind)
 
 
 def check(rc: int, what: str) -> None:

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "hipzap.h"
+#include "reqcopy.h"
 
 namespace {
 
@@ -65,6 +66,9 @@ struct Exec {
   std::vector<Slot> slots;
   int n_in = 1;
   uint64_t in_bytes[kMaxIn] = {};
+  // input k lives in device-resident request slots (HZ_REQSLOT_DEVICE): Slot::in[k] is the slot's
+  // host address, written with the streaming copy and never read
+  bool in_dev[kMaxIn] = {};
   uint64_t out_bytes = 0;
   std::mutex mu;
   std::condition_variable cv_free, cv_work;
@@ -95,6 +99,19 @@ struct Exec {
     slots[s].cv.notify_all();
     served += rows == 1 ? 1 : slots[s].claimed;
     ++batches;
+  }
+
+  // The one copy of a request's bytes into a slot (per-request, sized and batched-rows paths). A
+  // device-resident slot takes write-only 16-byte streaming stores (reqcopy.h; cap = bytes of the
+  // slot from dst on) and a store fence, so the bytes have left this core's write-combining buffers
+  // before the slot is queued to the worker under `mu`; a pinned slot takes a memcpy, as ever.
+  void put(int k, void* dst, const void* src, uint64_t n, uint64_t cap) const {
+    if (!in_dev[k]) {
+      std::memcpy(dst, src, n);
+      return;
+    }
+    hz_reqcopy(dst, src, (size_t)n, (size_t)cap);
+    hz_reqcopy_fence();
   }
 
   // mu held: a sealed slot whose claimed rows are all copied goes to the launch queue
@@ -170,6 +187,13 @@ struct Exec {
     }
   }
 
+  // bytes a copy may write from its destination on: a whole slot is allocated in 16-byte units
+  // (hz_reqslot_alloc); rows [r, r + m) of a batched slot end where row r + m begins, except the last
+  uint64_t slot_cap(int k) const { return (in_bytes[k] + 15) & ~uint64_t(15); }
+  uint64_t row_cap(int k, int r, int m) const {
+    return r + m == rows ? slot_cap(k) - r * row_in[k] : m * row_in[k];
+  }
+
   int submit_batched(const void* const* in, void* out, double* lat_us) {
     const double t0 = now_us();
     int s, r;
@@ -198,7 +222,8 @@ struct Exec {
     }
     Slot& sl = slots[s];
     for (int k = 0; k < n_in; ++k)
-      if (in && in[k] && row_in[k]) std::memcpy(static_cast<char*>(sl.in[k]) + r * row_in[k], in[k], row_in[k]);
+      if (in && in[k] && row_in[k])
+        put(k, static_cast<char*>(sl.in[k]) + r * row_in[k], in[k], row_in[k], row_cap(k, r, 1));
     int rc;
     {
       std::unique_lock<std::mutex> lk(mu);
@@ -255,8 +280,8 @@ struct Exec {
       Slot& sl = slots[s];
       for (int q = 0; q < n_in; ++q)
         if (in && in[q] && row_in[q])
-          std::memcpy(static_cast<char*>(sl.in[q]) + r * row_in[q], static_cast<const char*>(in[q]) + done * row_in[q],
-                      k * row_in[q]);
+          put(q, static_cast<char*>(sl.in[q]) + r * row_in[q], static_cast<const char*>(in[q]) + done * row_in[q],
+              k * row_in[q], row_cap(q, r, k));
       {
         std::unique_lock<std::mutex> lk(mu);
         sl.copied += k;
@@ -308,7 +333,8 @@ struct Exec {
     }
     Slot& sl = slots[s];
     for (int k = 0; k < n_in; ++k)
-      if (in && in[k] && in_bytes[k]) std::memcpy(sl.in[k], in[k], nbytes ? nbytes[k] : in_bytes[k]);
+      // (a sized request owns its own bytes only: what follows them stays as an earlier request left it)
+      if (in && in[k] && in_bytes[k]) put(k, sl.in[k], in[k], nbytes ? nbytes[k] : in_bytes[k], nbytes ? nbytes[k] : slot_cap(k));
     int rc;
     bool spin;
     {
@@ -403,6 +429,14 @@ void* hz_exec_create_batched(HzProgram* progs, hipStream_t* streams, void** host
     e->row_out = out_bytes / rows;
   }
   return e;
+}
+
+int hz_exec_set_input_kind(void* h, int k, int kind) {
+  Exec* e = static_cast<Exec*>(h);
+  if (k < 0 || k >= e->n_in) return -1;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->in_dev[k] = kind == HZ_REQSLOT_DEVICE;
+  return 0;
 }
 
 void hz_exec_batches(void* h, uint64_t* batches) {

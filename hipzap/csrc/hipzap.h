@@ -614,6 +614,26 @@ int hz_prog_bench2(HzProgram* progs, hipStream_t* streams, int n, int iters, int
 int hz_serve_bench(HzProgram* progs, hipStream_t* streams, void** in_dst, void** in_src, uint64_t in_bytes,
                    void** out_src, void** out_dst, uint64_t out_bytes, int n, int iters, double* lat_us,
                    double* wall_us);
+// ---- request slots: a context's INPUT buffer, device-resident where the host can write it ----
+// HZ_REQSLOT_DEVICE: fine-grained device memory the CPU writes through the PCIe BAR (large-BAR
+// systems): the request is in HBM before the replay starts. HZ_REQSLOT_PINNED: pinned host memory the
+// kernels read over PCIe (zero-copy), the fallback when the device is not host-writable.
+enum { HZ_REQSLOT_PINNED = 0, HZ_REQSLOT_DEVICE = 1 };
+// 1: this device's memory is host-writable (large BAR, and the runtime reports a host address for a
+// test allocation). Never dereferences anything; cached per device. HIPZAP_REQSLOT=host: always 0.
+int hz_reqslot_probe(void);
+// *dev = the address kernels read, *host = the address the CPU writes (write-only for a device slot:
+// hz_reqslot_write), *kind = HZ_REQSLOT_*. A device slot when the probe says yes and the allocation's
+// own host address is reported; else a pinned buffer (dev == host). Zero-filled. 0 or a HIP error.
+int hz_reqslot_alloc(uint64_t bytes, void** dev, void** host, int* kind);
+int hz_reqslot_free(void* dev, int kind);
+// streaming, write-only copy of n bytes to a device slot's host address (csrc/reqcopy.h) + store
+// fence; cap = bytes of the slot from dst on. The executor's copy for device-resident inputs.
+void hz_reqslot_write(void* dst, const void* src, uint64_t n, uint64_t cap);
+// host cost of one payload copy (us: out[0] best, out[1] median of `iters`), `threads` at once, each
+// into its own slot[t]; streaming = hz_reqslot_write, else memcpy (profiles/reqslot)
+int hz_reqslot_copy_bench(void** slots, const void* src, uint64_t n, int threads, int iters, int streaming,
+                          double* out);
 // diagnostics (csrc/diag.hip): kind 0 = no-op kernel, 1 = copy `bytes` from a to b
 int hz_diag_launch(int kind, int blocks, int threads, void* a, void* b, long bytes, hipStream_t st);
 
@@ -665,6 +685,9 @@ void* hz_exec_create(HzProgram* progs, hipStream_t* streams, void** host_in, con
 void* hz_exec_create_batched(HzProgram* progs, hipStream_t* streams, void** host_in, const uint64_t* in_bytes,
                              int n_in, void** host_out, uint64_t out_bytes, int n, int rows, double max_wait_us,
                              int min_inflight);
+// input k of every slot is a device-resident request slot (HZ_REQSLOT_DEVICE; host_in = its host
+// address): payloads go in with the streaming write-only copy instead of memcpy. Before any submit.
+int hz_exec_set_input_kind(void* exec, int k, int kind);
 void hz_exec_batches(void* exec, uint64_t* batches);
 int hz_exec_submit(void* exec, const void* const* in, void* out, double* lat_us);
 int hz_exec_submit_rows(void* exec, const void* const* in, int m, void* out, double* lat_us);

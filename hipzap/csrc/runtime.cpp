@@ -8,6 +8,10 @@
 // invocation captured as a hipGraph"). Nothing here allocates or synchronises inside the
 // launch sequence, so capture is always legal (cdna_hip_programming.md §6 Guideline 9).
 #include <hip/hip_runtime.h>
+#include <hsa/hsa.h>
+#include <hsa/hsa_ext_amd.h>
+#include <dlfcn.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -18,6 +22,7 @@
 
 #include "common.h"
 #include "hipzap.h"
+#include "reqcopy.h"
 
 namespace {
 
@@ -261,6 +266,124 @@ int hz_serve_bench(HzProgram* progs, hipStream_t* streams, void** in_dst, void**
 }
 
 }  // extern "C"
+
+// ---- request slots (hipzap.h): device-resident, host-writable input buffers ----
+//
+// On a large-BAR system the whole of device memory is mapped into the process, and the runtime's
+// pointer query reports the host address of a fine-grained device allocation. A request thread then
+// writes its payload straight into HBM (write-combined PCIe writes, reqcopy.h) and the first kernel
+// of the replay reads it at memory speed instead of pulling it over PCIe inside the launch chain
+// (profiles/reqslot). No managed memory, no page migration, no command on any GPU queue.
+namespace {
+
+// the runtime's pointer query, found in the already loaded runtime (no link-time dependency; a
+// host-only build without it simply has no device slots)
+using PointerInfoFn = hsa_status_t (*)(const void*, hsa_amd_pointer_info_t*, void* (*)(size_t), uint32_t*,
+                                       hsa_agent_t**);
+
+// host address of a device allocation as the runtime reports it, or nullptr. Asks; never dereferences.
+void* reported_host_address(void* dev) {
+  static const PointerInfoFn fn = reinterpret_cast<PointerInfoFn>(dlsym(RTLD_DEFAULT, "hsa_amd_pointer_info"));
+  if (!fn || !dev) return nullptr;
+  hsa_amd_pointer_info_t pi;
+  memset(&pi, 0, sizeof(pi));
+  pi.size = sizeof(pi);
+  if (fn(dev, &pi, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS) return nullptr;
+  if (pi.type != HSA_EXT_POINTER_TYPE_HSA || !pi.hostBaseAddress || !pi.agentBaseAddress) return nullptr;
+  const char* base = static_cast<const char*>(pi.agentBaseAddress);
+  const char* p = static_cast<const char*>(dev);
+  if (p < base || p >= base + pi.sizeInBytes) return nullptr;
+  return static_cast<char*>(pi.hostBaseAddress) + (p - base);
+}
+
+bool reqslot_disabled() {
+  const char* e = getenv("HIPZAP_REQSLOT");
+  return e && (!strcmp(e, "host") || !strcmp(e, "0") || !strcmp(e, "off"));
+}
+
+}  // namespace
+
+extern "C" int hz_reqslot_probe(void) {
+  static std::atomic<int> cache[64];  // 0 unknown, 1 no, 2 yes
+  if (reqslot_disabled()) return 0;
+  int d = -1, large_bar = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 0;
+  if (const int c = cache[d].load()) return c - 1;
+  int yes = 0;
+  if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, d) == hipSuccess && large_bar) {
+    void* p = nullptr;
+    if (hipExtMallocWithFlags(&p, 4096, hipDeviceMallocFinegrained) == hipSuccess) {
+      yes = reported_host_address(p) != nullptr;
+      (void)hipFree(p);
+    }
+  }
+  (void)hipGetLastError();
+  cache[d].store(yes + 1);
+  return yes;
+}
+
+extern "C" int hz_reqslot_alloc(uint64_t bytes, void** dev, void** host, int* kind) {
+  if (!dev || !host || !kind) return -1;
+  *dev = *host = nullptr;
+  *kind = HZ_REQSLOT_PINNED;
+  // whole 16-byte units: the streaming copy may round a payload's last unit up (reqcopy.h)
+  const size_t cap = bytes ? (size_t(bytes) + 15) & ~size_t(15) : 256;
+  if (hz_reqslot_probe()) {
+    void* p = nullptr;
+    if (hipExtMallocWithFlags(&p, cap, hipDeviceMallocFinegrained) == hipSuccess) {
+      void* h = reported_host_address(p);
+      if (h && hipMemset(p, 0, cap) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
+        *dev = p;
+        *host = h;
+        *kind = HZ_REQSLOT_DEVICE;
+        return 0;
+      }
+      (void)hipFree(p);
+    }
+    (void)hipGetLastError();  // fall back to pinned host memory
+  }
+  void* p = nullptr;
+  const hipError_t e = hipHostMalloc(&p, cap, hipHostMallocDefault);
+  if (e != hipSuccess) return (int)e;
+  memset(p, 0, cap);
+  *dev = *host = p;
+  return 0;
+}
+
+extern "C" int hz_reqslot_free(void* dev, int kind) {
+  if (!dev) return 0;
+  return (int)(kind == HZ_REQSLOT_DEVICE ? hipFree(dev) : hipHostFree(dev));
+}
+
+extern "C" void hz_reqslot_write(void* dst, const void* src, uint64_t n, uint64_t cap) {
+  hz_reqcopy(dst, src, (size_t)n, (size_t)cap);
+  hz_reqcopy_fence();
+}
+
+extern "C" int hz_reqslot_copy_bench(void** slots, const void* src, uint64_t n, int threads, int iters,
+                                     int streaming, double* out) {
+  if (threads < 1 || iters < 1 || !slots || !src || !out) return -1;
+  std::vector<std::vector<double>> v(threads);
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; ++t)
+    th.emplace_back([&, t] {
+      for (int it = 0; it < iters; ++it) {
+        const auto a = std::chrono::steady_clock::now();
+        if (streaming)
+          hz_reqslot_write(slots[t], src, n, (n + 15) & ~uint64_t(15));
+        else
+          memcpy(slots[t], src, n);
+        v[t].push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count());
+      }
+    });
+  for (auto& t : th) t.join();
+  std::vector<double> all;
+  for (auto& x : v) all.insert(all.end(), x.begin(), x.end());
+  std::sort(all.begin(), all.end());
+  out[0] = all.front();
+  out[1] = all[all.size() / 2];
+  return 0;
+}
 
 // 1 when this library was built with the measured-negative experiment kernels (HZ_EXPERIMENTS)
 extern "C" int hz_experiments(void) { return HZ_EXPERIMENTS; }

@@ -237,7 +237,8 @@ class Engine:
                         [[c.host_inputs[k].data_ptr() for c in cs] for k in range(len(cs[0].host_inputs))],
                         [h.numel() * h.element_size() for h in cs[0].host_inputs],
                         [c.host_output.data_ptr() for c in cs],
-                        cs[0].host_output.numel() * cs[0].host_output.element_size())
+                        cs[0].host_output.numel() * cs[0].host_output.element_size(),
+                        in_kinds=[cs[0].input_kind] * len(cs[0].host_inputs))
                 finally:
                     for lk in self._locks:
                         lk.release()
@@ -270,8 +271,8 @@ class Engine:
         ctx, s = self.contexts[i], self.streams[i]
         with self._locks[i], torch.cuda.device(self.device), torch.cuda.stream(s):
             if self.host_io:  # transfers are inside the captured graph
-                for hb, xi in zip(ctx.host_inputs, xs):
-                    hb.copy_(xi.reshape(hb.shape))
+                for k, xi in enumerate(xs[:len(ctx.host_inputs)]):
+                    ctx.write_input(k, xi)
                 ctx.replay(s)
                 s.synchronize()
                 out = ctx.host_output.clone()
@@ -375,7 +376,8 @@ class Engine:
                     [h.numel() * h.element_size() for h in cs[0].host_inputs],
                     [c.host_output.data_ptr() for c in cs],
                     cs[0].host_output.numel() * cs[0].host_output.element_size(),
-                    rows=self.batch, max_wait_us=max_wait_us, min_inflight=min_inflight)
+                    rows=self.batch, max_wait_us=max_wait_us, min_inflight=min_inflight,
+                    in_kinds=[cs[0].input_kind] * len(cs[0].host_inputs))
         return self._bexec
 
     def serve_bench(self, iters: int, payload=None, clients: int | None = None,

@@ -6,8 +6,9 @@ bind as ONE fused kernel instead:
 
 * ``stem``: preprocess -> conv1 (7x7/2, BN folded, ReLU) -> maxpool 3x3/2 -> ``hz_stem_launch``;
 * ``convpool``: the same kernel after a standalone preprocess (conv1 + maxpool only, bf16 NHWC8
-  input): the default, since a zero-copy request read inside the 98-workgroup stem cost served
-  throughput (profiles/r4_fuse/README.md);
+  input): the default for a request in pinned host memory, since a zero-copy request read inside
+  the 98-workgroup stem cost served throughput (profiles/r4_fuse/README.md); a uint8 request in a
+  device-resident slot binds ``stem`` (:func:`default_kinds`, profiles/reqslot/README.md);
 * ``bneck``: a layer1-geometry bottleneck (1x1 Cin -> 64, 3x3 64 -> 64, 1x1 64 -> 256 + residual,
   optionally with its 1x1 downsample) -> ``hz_bneck_launch``;
 * ``bneck2``: a layer2 bottleneck (1x1 512 -> 128, 3x3 128 -> 128, 1x1 128 -> 512 + residual;
@@ -119,6 +120,18 @@ def enabled_kinds(spec: str | None = None) -> set:
     if v in ("1", "all", "on"):
         return {"stem", "bneck", "bneck2"}
     return {k for k in v.split(",") if k in KINDS}
+
+
+def default_kinds(device_u8_request: bool) -> set:
+    """The kinds a context binds when its caller names none. ``HIPZAP_FUSE`` decides when set. Else
+    the measured default, with ``stem`` ahead of ``convpool`` when the request is uint8 bytes in a
+    device-resident slot (engine/program.py): the row staging of ``stem_kernel`` mode 1 then reads
+    HBM, not PCIe, which is what cost the fused stem its round-4 A/B (profiles/reqslot/README.md),
+    and the standalone preprocess launch goes: 28 launches per ResNet-50 request instead of 29. A
+    pinned-host request keeps ``convpool`` exactly as before."""
+    if "HIPZAP_FUSE" in os.environ or not device_u8_request:
+        return enabled_kinds()
+    return enabled_kinds(DEFAULT) | {"stem"}
 
 
 def _conv(n, kind="conv"):

@@ -176,6 +176,9 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
         add_softmax_head(g)
     if tuned is None:
         tuned = load_tuning(model, batch, contexts)
+    if zero_copy == "dev":
+        raise ValueError("plan images keep their request slots in the context's pinned host block: "
+                         "zero_copy='dev' (device-resident request slots) is an Engine option")
     rec = PlanRecorder()
     ctx = ExecContext(g, params, torch.device("cpu"), tuned, host_io=host_io, zero_copy=zero_copy if host_io else "",
                       lib=rec)

@@ -75,6 +75,21 @@ def qkvatt_pairs(g: Graph, params: dict) -> dict:
     return out
 
 
+# Where a zero-copy ("all") uint8 ResNet request lives when HIPZAP_REQSLOT is unset: "dev" =
+# device-resident request slots + the one-launch stem, "host" = pinned host memory + preprocess and
+# convpool. Decided by the served A/B of profiles/reqslot/README.md (+5.4 to +6.9 % served in four
+# interleaved pairs against a 0.9 % spread of the pinned path's own repeats).
+REQSLOT_DEFAULT = "dev"
+
+
+def _slot_view(slot, like: torch.Tensor) -> torch.Tensor:
+    """CPU tensor over a request slot's host address, shaped like ``like``. Meant to be written
+    only: reading a device-resident slot back is a PCIe round trip per access."""
+    _, host, _, nbytes = slot
+    raw = torch.frombuffer((C.c_uint8 * nbytes).from_address(host), dtype=torch.uint8)
+    return raw.view(like.dtype).reshape(like.shape)
+
+
 def _ln_folded(n) -> bool:
     a = n.attrs
     return n.kind == "gemm" and bool(a.get("ln_in") or a.get("res_ln") or a.get("stats_out") is not None)
@@ -96,9 +111,25 @@ class ExecContext:
         self._nslab: dict[int, int] = {}  # stats tensor -> slabs written by its producer (HzLnFold)
         lib = lib if lib is not None else N.lib()
         self._lib = lib
+        # host_io: the request's PCIe transfers are part of the program (and of the graph):
+        # pinned host inputs -> device inputs ... device output -> pinned host output.
+        # zero_copy ("in", "out", "all"): the first/last kernels read the request from / write the
+        # result to the pinned host buffers directly (UVA), replacing the copy node(s) and their
+        # kernel boundaries; HIPZAP_ZERO_COPY picks the default. "dev" = "all" with the inputs in
+        # device-resident request slots (csrc/runtime.cpp hz_reqslot_alloc: device memory the host
+        # writes through the BAR), so the first kernel reads the request from HBM; where the device
+        # is not host-writable the slots are pinned as under "all" (``input_kind`` says which).
+        self.host_io = host_io
+        zc = zero_copy if zero_copy is not None else os.environ.get("HIPZAP_ZERO_COPY", "")
+        self._req_slots = self._request_slots(g, params, zc, fuse) if host_io else None
+        self.input_kind = N.REQSLOT_DEVICE if self._req_slots else N.REQSLOT_PINNED
+        zc = "all" if zc == "dev" else zc
+        u8_request = len(g.inputs) == 1 and g.tensors[g.inputs[0]].dtype == torch.uint8
         # fused ResNet stages (engine/fusion.py, csrc/block.hip): runs of nodes bound as ONE launch;
         # the arena plan keeps each run's tensors live over the whole run
-        self.fused = fusion.plan(g, params, fusion.enabled_kinds(fuse) if fuse is not None else None)
+        kinds = fusion.enabled_kinds(fuse) if fuse is not None else \
+            fusion.default_kinds(self.input_kind == N.REQSLOT_DEVICE and u8_request)
+        self.fused = fusion.plan(g, params, kinds)
         conv_plans = self._conv_plans(g, params, tuned)
         if pair_convs is None:
             pair_convs = os.environ.get("HIPZAP_PAIR_CONVS", "1") != "0"
@@ -148,9 +179,13 @@ class ExecContext:
             if spec.external:
                 self.ext[tid] = torch.zeros(spec.shape, dtype=spec.dtype, device=self.device)
 
+        self._dev_addr: dict[int, int] = {}
+
         def addr(tid):
             if tid is None:
                 return 0
+            if tid in self._dev_addr:
+                return self._dev_addr[tid]
             if tid in self.ext:
                 return self.ext[tid].data_ptr()
             return base + offsets[tid]
@@ -159,22 +194,20 @@ class ExecContext:
         self.tensor_offsets = offsets
         self.prog = lib.hz_prog_create()
         self.configs: list = []
-        # host_io: the request's PCIe transfers are part of the program (and of the graph):
-        # pinned host inputs -> device inputs ... device output -> pinned host output.
-        # zero_copy ("in", "out", "all"): the first/last kernels read the request from / write the
-        # result to the pinned host buffers directly (UVA), replacing the copy node(s) and their
-        # kernel boundaries; HIPZAP_ZERO_COPY picks the default.
-        self.host_io = host_io
-        zc = zero_copy if zero_copy is not None else os.environ.get("HIPZAP_ZERO_COPY", "")
         self.zc_in, self.zc_out = host_io and zc in ("in", "all", "1"), host_io and zc in ("out", "all", "1")
         if host_io:
             pin = (lambda t: t) if self.recording else (lambda t: t.pin_memory())
-            self.host_inputs = [pin(torch.zeros(self.ext[t].shape, dtype=self.ext[t].dtype)) for t in g.inputs]
+            if self._req_slots:  # CPU views of the slots' host addresses: write-only (write_input)
+                self.host_inputs = [_slot_view(s, self.ext[t]) for s, t in zip(self._req_slots, g.inputs)]
+            else:
+                self.host_inputs = [pin(torch.zeros(self.ext[t].shape, dtype=self.ext[t].dtype)) for t in g.inputs]
             self.host_input = self.host_inputs[0]
             self.host_output = pin(torch.zeros(self.output.shape, dtype=self.output.dtype))
-            for t, hbuf in zip(g.inputs, self.host_inputs):
+            for k, (t, hbuf) in enumerate(zip(g.inputs, self.host_inputs)):
                 if self.zc_in:
                     self.ext[t] = hbuf
+                    if self._req_slots:  # kernels read the slot's device address
+                        self._dev_addr[t] = self._req_slots[k][0]
                     continue
                 d = self.ext[t]
                 N.check(lib.hz_prog_add_memcpy(self.prog, d.data_ptr(), hbuf.data_ptr(), d.numel() * d.element_size(),
@@ -492,6 +525,45 @@ class ExecContext:
             raise NotImplementedError(f"node kind {n.kind}")
 
     # ------------------------------------------------------------------
+    def _request_slots(self, g, params, zc: str, fuse) -> list | None:
+        """[(dev, host, kind, bytes)] per graph input when this context's inputs live in
+        device-resident request slots, else None (pinned host inputs, as ever). ``zc == "dev"`` asks
+        for them for any graph; ``"all"`` takes them where HIPZAP_REQSLOT (default
+        :data:`REQSLOT_DEFAULT`) says ``dev`` and the program is the fixed-shape uint8 ResNet whose
+        stem then binds as one launch (resize plans, fp32 and token inputs keep pinned slots). A
+        device that is not host-writable, or a failed allocation, gives None: the fallback."""
+        if zc != "dev":
+            if zc not in ("all", "1") or self.recording or fuse is not None or \
+                    os.environ.get("HIPZAP_REQSLOT", REQSLOT_DEFAULT) != "dev":
+                return None
+            if len(g.inputs) != 1 or g.tensors[g.inputs[0]].dtype != torch.uint8 or \
+                    not any(fusion.match_stem(g, params, i) for i in range(len(g.nodes))):
+                return None
+        slots = []
+        self._slot_free = N.reqslot_free  # (the allocator's counterpart, bound with the slots)
+        for t in g.inputs:
+            spec = g.tensors[t]
+            s = N.reqslot_alloc(spec.nbytes)
+            if s is not None:
+                slots.append((*s, spec.nbytes))
+            if s is None or s[2] != N.REQSLOT_DEVICE:
+                for dev, _, kind, _ in slots:
+                    N.reqslot_free(dev, kind)
+                return None
+        return slots
+
+    def write_input(self, k: int, x: torch.Tensor) -> None:
+        """Fill host input k from ``x`` (any dtype / layout convertible to the input's). A
+        device-resident slot is written through the native streaming copy from a staged contiguous
+        tensor and never read; a pinned one takes a plain ``copy_``."""
+        hb = self.host_inputs[k]
+        if not self._req_slots:
+            hb.copy_(x.reshape(hb.shape))
+            return
+        src = x.detach().to("cpu", hb.dtype).reshape(hb.shape).contiguous()
+        _, host, _, nbytes = self._req_slots[k]
+        N.lib().hz_reqslot_write(host, src.data_ptr(), nbytes, (nbytes + 15) // 16 * 16)
+
     @property
     def input(self) -> torch.Tensor:
         return self.ext[self.graph.inputs[0]]
@@ -533,6 +605,9 @@ class ExecContext:
             if getattr(self, "prog", None):
                 self._lib.hz_prog_destroy(self.prog)
                 self.prog = None
+            for dev, _, kind, _ in getattr(self, "_req_slots", None) or []:
+                self._slot_free(dev, kind)
+            self._req_slots = None
         except Exception:
             pass
 

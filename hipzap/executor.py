@@ -15,8 +15,11 @@ from . import _native as N
 
 class Executor:
     def __init__(self, progs: list, streams: list, host_in: list, in_bytes: list, host_out: list, out_bytes: int,
-                 rows: int = 1, max_wait_us: float = 200.0, min_inflight: int = 1):
+                 rows: int = 1, max_wait_us: float = 200.0, min_inflight: int = 1, in_kinds: list | None = None):
         """``host_in[k][i]``: address of context i's pinned input k; ``host_out[i]``: its output.
+        ``in_kinds[k]``: ``N.REQSLOT_DEVICE`` when input k of every context is a device-resident
+        request slot (``host_in`` = its host address): the payload goes in with the streaming
+        write-only copy (csrc/reqcopy.h).
 
         ``rows > 1``: dynamic batching -- the contexts are captured at batch ``rows`` and every
         request is ONE row (``in_bytes[k] / rows`` in, ``out_bytes / rows`` out); a filling batch
@@ -39,6 +42,8 @@ class Executor:
         if not h:
             raise RuntimeError("hz_exec_create failed")
         self._h = h
+        for k, kind in enumerate(in_kinds or []):
+            N.check(N.lib().hz_exec_set_input_kind(h, k, int(kind)), "exec_set_input_kind")
 
     def submit(self, in_ptrs: list, out_ptr: int) -> float:
         """Blocking request: ``in_ptrs[k]`` = host address of input k's payload (exactly
