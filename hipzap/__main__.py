@@ -4,6 +4,7 @@
     python -m hipzap pack --model resnet50 --ckpt m.pth --out m.hzpack
     python -m hipzap plan --model resnet50 --ckpt m.pth [--contexts 24]  # torch-free cold-start image
     python -m hipzap plan --model resnet50 --ckpt m.pth --resize 256 [--max-image 1024x1024]  # any-size images
+    python -m hipzap plan --model bert-base --ckpt bert.pth --embed [--pooling mean|cls] [--no-normalize]  # vectors
     python -m hipzap tune --model resnet50 --batch 1 --concurrent 1 8
     python -m hipzap upload --models-dir ./models  # scripts/upload_models.py parity
     python -m hipzap info
@@ -69,12 +70,17 @@ def cmd_plan(a):
     from .lite import read_meta
     from .models import registry
     crop = a.crop or getattr(registry.get(a.model), "image", 224)
+    embed = {"pooling": a.pooling or ("cls" if a.model.startswith("vit") else "mean"),
+             "normalize": not a.no_normalize} if a.embed else None
+    if embed is None and (a.pooling or a.no_normalize):
+        raise SystemExit("--pooling / --no-normalize go with --embed")
     out = export_from_checkpoint(a.model, a.ckpt, a.out, batch=a.batch, contexts=a.contexts, probs=a.probs,
                                  dp_shard=a.dp_shard, seq_len=a.seq_len,
-                                 resize=resize_spec(a.resize, crop, a.max_image))
+                                 resize=resize_spec(a.resize, crop, a.max_image), embed=embed)
     m = read_meta(out)
     print(json.dumps({"out": out, "ops": m["n_ops"], "blob_bytes": m["blob_bytes"], "source": m["source"],
-                      **({"resize": m["resize"]} if m.get("resize") else {})}))
+                      **({"resize": m["resize"]} if m.get("resize") else {}),
+                      **({"embed": m["embed"]} if m.get("embed") else {})}))
 
 
 def cmd_tune(a):
@@ -138,6 +144,12 @@ def main(argv=None):
     pl.add_argument("--resize", type=int, default=None,
                     help="vision models: write a RESIZE plan -- requests are uint8 images of any size, the shorter "
                          "side resized to this (antialiased bilinear), centre-cropped and normalised on the GPU")
+    pl.add_argument("--embed", action="store_true",
+                    help="BERT / ViT: write an EMBEDDING plan (<ckpt>.emb.hzplan) -- the output is one pooled vector "
+                         "per sequence / image (POST /embed) instead of class logits")
+    pl.add_argument("--pooling", choices=["mean", "cls"], default=None,
+                    help="with --embed: masked token mean or the CLS token (default: mean for BERT, cls for ViT)")
+    pl.add_argument("--no-normalize", action="store_true", help="with --embed: do not L2-normalise the vectors")
     pl.add_argument("--crop", type=int, default=None, help="with --resize: crop size (default: the model's image size)")
     pl.add_argument("--max-image", default=None,
                     help="with --resize: largest request image, HEIGHTxWIDTH (default 1024x1024)")

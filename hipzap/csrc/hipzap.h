@@ -407,6 +407,20 @@ typedef struct HzQkvAttParams {
 } HzQkvAttParams;
 int hz_qkvatt_launch(const HzQkvAttParams* p, hipStream_t st);
 int hz_vit_tokens_launch(const HzVitTokensParams* p, hipStream_t st);
+// pooled embeddings (transformer.hip pool_embed_kernel): the final hidden states -> one fp32 vector per
+// sequence in one launch. mode 0: the CLS row (row b*L; mask and first ignored); mode 1: the mean of the
+// counted tokens of [first, L), a token counting iff its additive mask value is 0 (the hosts write 0 or
+// -1e9; NULL mask: all count). normalize: divide by max(||v||_2, 1e-12) in fp32. A sequence with no
+// counted token gives a zero row. One workgroup per sequence, fp32 sums in a fixed order, no atomics: a
+// sequence's output bits do not depend on B, on its row or on the other rows.
+typedef struct HzPoolEmbedParams {
+  const unsigned short* x;    // [B*L][ldx] bf16, D columns used (16-B aligned, ldx % 8 == 0)
+  const float* mask;          // additive mask [B][L] or NULL
+  float* out;                 // [B][ldo] fp32; columns D..ldo-1 are written as zero
+  int B, L, D, ldx, ldo;      // D % 8 == 0, D <= 2048
+  int first, mode, normalize;
+} HzPoolEmbedParams;
+int hz_pool_embed_launch(const HzPoolEmbedParams* p, hipStream_t st);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -580,7 +594,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(PREPROCESS, 25, HzPreprocessArgs, hz_preprocess_op, VISION)           \
   X(STEP_BUMP, 26, HzStepBumpArgs, hz_step_bump_op, LSTM)                 \
   X(DIAG, 27, HzDiagArgs, hz_diag_op, DIAG)                               \
-  X(RESIZE_PREPROCESS, 28, HzResizeParams, hz_resize_preprocess_op, VISION)
+  X(RESIZE_PREPROCESS, 28, HzResizeParams, hz_resize_preprocess_op, VISION) \
+  X(POOL_EMBED, 29, HzPoolEmbedParams, hz_pool_embed_op, TRANSFORMER)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

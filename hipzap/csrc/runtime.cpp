@@ -417,6 +417,11 @@ extern "C" __attribute__((weak)) int hz_resize_preprocess_launch(const HzResizeP
 static int hz_resize_preprocess_op(const HzResizeParams* p, hipStream_t st) {
   return hz_resize_preprocess_launch ? hz_resize_preprocess_launch(p, st) : -102;
 }
+// (the pooled-embedding launcher likewise: transformer.hip in the library)
+extern "C" __attribute__((weak)) int hz_pool_embed_launch(const HzPoolEmbedParams* p, hipStream_t st);
+static int hz_pool_embed_op(const HzPoolEmbedParams* p, hipStream_t st) {
+  return hz_pool_embed_launch ? hz_pool_embed_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -53,6 +53,7 @@ struct Spec {
   int probs = 0;
   std::string model;
   bool host_io = false;
+  bool embed = false;  // an embedding plan (meta "embed"): its output is a vector per request, not class scores
 };
 
 bool read_spec(const char* path, Spec& s) {
@@ -69,6 +70,8 @@ bool read_spec(const char* path, Spec& s) {
   if (mi != std::string::npos) s.model = js.substr(mi + 10, js.find('"', mi + 10) - (mi + 10));
   s.probs = js.find("\"probs\": true") != std::string::npos;
   s.host_io = js.find("\"host_io\": true") != std::string::npos;
+  s.embed = js.find("\"embed\": {") != std::string::npos;
+  if (s.embed) return true;  // refused by main before anything else of the plan is looked at
   const size_t ii = js.find("\"inputs\": [");
   const size_t oi = js.find("\"output\": {");
   if (ii == std::string::npos || oi == std::string::npos) return false;
@@ -131,7 +134,13 @@ int main(int argc, char** argv) {
     else if (a == "--once") once = argv[i + 1];
   }
   Spec sp;
-  if (!read_spec(plan_path, sp) || !sp.host_io) {
+  const bool spec_ok = read_spec(plan_path, sp);
+  if (spec_ok && sp.embed) {
+    std::fprintf(stderr, "hipzap-serve-plan: %s is an embedding plan: serve it with `hipzap serve` (POST /embed)\n",
+                 plan_path);
+    return 1;
+  }
+  if (!spec_ok || !sp.host_io) {
     std::fprintf(stderr, "hipzap-serve-plan: %s is not a single-uint8-image host-I/O plan\n", plan_path);
     return 1;
   }

@@ -10,6 +10,8 @@
 //                  in LDS (BERT L=128, ViT L=197); attention_stream_kernel: any L, K/V streamed
 //                  in 64-key tiles with the online softmax (BERT L=512, ViT-384 L=577).
 //   * patch_tokens — ViT: CLS token + position embedding add around the patch-embed GEMM.
+//   * pool_embed — the embedding head: CLS row or masked token mean of the final hidden states,
+//                  optionally L2-normalised, fp32, one workgroup per sequence.
 #include <cstdlib>
 
 #include "common.h"
@@ -804,6 +806,120 @@ __global__ __launch_bounds__(256) void vit_tokens_kernel(const HzVitTokensParams
   *reinterpret_cast<u32x4*>(p.out + rt * p.D + ch * 8) = pack8(a);
 }
 
+// --------------------------------------------------------------------------- pooled embeddings
+// Final hidden states -> one fp32 vector per sequence (HzPoolEmbedParams). One workgroup of NW waves
+// per sequence. Wave w sums tokens first + w, first + w + NW, ... in that order: lane l holds the
+// 16-B chunks l, l + 64, ... of the row (NC of them, sized to D at launch), four tokens' loads in
+// flight at a time; a token whose mask value is not 0 is skipped before its load. The NW partial
+// rows meet in LDS and are summed in wave order, divided by the token count (a true division: one
+// rounding), and the L2 norm is a butterfly over each wave plus NW values in wave order. Every sum has
+// a fixed order and stays inside the workgroup, so the bits of a row depend on that sequence alone.
+// There is no data-dependent address: the kernel reads rows b*L + first .. b*L + L - 1 of x and
+// mask[b*L + first .. b*L + L - 1], and nothing else (the launcher checks the geometry; nothing to clamp).
+template <int NC, int NW>
+__global__ __launch_bounds__(64 * NW) void pool_embed_kernel(const HzPoolEmbedParams p) {
+  constexpr int NJ = NC * 8 / NW;  // output columns per thread: NC * 512 columns over 64 * NW threads
+  static_assert(NJ * NW == NC * 8, "the final phase covers every column");
+  __shared__ __attribute__((aligned(16))) float part[NW][NC * 512];
+  __shared__ float sq[NW];
+  __shared__ int cnt[NW];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int b = blockIdx.x;
+  const int nch = p.D >> 3;
+  if (!HZ_DCHECK(p.D <= NC * 512 && p.ldx >= p.D && p.L >= 1 && (p.mode == 0 || (p.first >= 0 && p.first < p.L)))) return;
+  const bf16_t* xb = p.x + (long)b * p.L * p.ldx;
+  const float* mb = p.mask ? p.mask + (long)b * p.L : nullptr;
+  float acc[NC][8];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[c][e] = 0.f;
+  int n = 0;
+  if (p.mode == 0) {  // CLS: wave 0 holds the row itself (no add: -0 stays -0)
+    if (w == 0) {
+      n = 1;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (c * 64 + lane < nch) unpack8(*reinterpret_cast<const u32x4*>(xb + (c * 64 + lane) * 8), acc[c]);
+    }
+  } else {
+    for (int t0 = p.first + w; t0 < p.L; t0 += 4 * NW) {  // wave-uniform bounds and branches
+      u32x4 v[4][NC];
+      bool on[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int t = t0 + u * NW;
+        on[u] = t < p.L && (!mb || mb[t] == 0.f);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          v[u][c] = u32x4{0u, 0u, 0u, 0u};
+          if (on[u] && c * 64 + lane < nch)
+            v[u][c] = *reinterpret_cast<const u32x4*>(xb + (long)t * p.ldx + (c * 64 + lane) * 8);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (!on[u]) continue;
+        ++n;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          float f[8];
+          unpack8(v[u][c], f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[c][e] += f[e];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {  // chunk c*64 + lane < 64 * NC: inside part[w] for every lane
+    float* d = &part[w][(c * 64 + lane) * 8];
+    *reinterpret_cast<f32x4*>(d) = f32x4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]};
+    *reinterpret_cast<f32x4*>(d + 4) = f32x4{acc[c][4], acc[c][5], acc[c][6], acc[c][7]};
+  }
+  if (lane == 0) cnt[w] = n;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) total += cnt[i];
+  float o[NJ];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    const int j = threadIdx.x + i * 64 * NW;
+    float s = 0.f;
+    if (j < p.D && total > 0) {
+      s = part[0][j];
+      if (p.mode != 0) {
+#pragma unroll
+        for (int k = 1; k < NW; ++k) s += part[k][j];
+      }
+      s = s / (float)total;
+    }
+    o[i] = s;
+    ss += s * s;
+  }
+  if (p.normalize) {
+    ss = warp_sum(ss);
+    if (lane == 0) sq[w] = ss;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) tot += sq[i];
+    const float nrm = fmaxf(sqrtf(tot), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < NJ; ++i) o[i] = o[i] / nrm;
+  }
+  float* ob = p.out + (long)b * p.ldo;
+#pragma unroll
+  for (int i = 0; i < NJ; ++i) {
+    const int j = threadIdx.x + i * 64 * NW;
+    if (j < p.D) ob[j] = o[i];
+  }
+  for (int j = p.D + threadIdx.x; j < p.ldo; j += 64 * NW) ob[j] = 0.f;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- row softmax
@@ -914,6 +1030,23 @@ extern "C" int hz_vit_tokens_launch(const HzVitTokensParams* pp, hipStream_t st)
   if (p.D % 8) return -1;
   const long total = (long)p.B * (p.np + 1) * (p.D / 8);
   hipLaunchKernelGGL(vit_tokens_kernel, dim3((total + 255) / 256), dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_pool_embed_launch(const HzPoolEmbedParams* pp, hipStream_t st) {
+  const HzPoolEmbedParams& p = *pp;
+  if (!p.x || !p.out || p.B < 1 || p.L < 1) return -1;
+  if (p.D < 8 || p.D % 8 || p.D > 2048) return -1;
+  if (p.ldx < p.D || p.ldx % 8 || (reinterpret_cast<uintptr_t>(p.x) & 15) || p.ldo < p.D) return -1;  // 16-B loads
+  if (p.mode != 0 && p.mode != 1) return -1;
+  if (p.mode == 1 && (p.first < 0 || p.first >= p.L)) return -1;
+  // 8 waves per sequence up to D = 1024, 4 beyond (the partial rows: 32 KiB of LDS at most)
+  switch ((p.D / 8 + 63) / 64) {
+    case 1: hipLaunchKernelGGL((pool_embed_kernel<1, 8>), dim3(p.B), dim3(512), 0, st, p); break;
+    case 2: hipLaunchKernelGGL((pool_embed_kernel<2, 8>), dim3(p.B), dim3(512), 0, st, p); break;
+    case 3: hipLaunchKernelGGL((pool_embed_kernel<3, 4>), dim3(p.B), dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((pool_embed_kernel<4, 4>), dim3(p.B), dim3(256), 0, st, p); break;
+  }
   return (int)hipGetLastError();
 }
 

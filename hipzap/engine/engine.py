@@ -291,6 +291,13 @@ class Engine:
         """{"resize", "crop", "max_h", "max_w"} of a resize engine (``arch_kw["resize"]``), else None."""
         return (getattr(self.graph, "meta", None) or {}).get("resize")
 
+    @property
+    def embed(self) -> dict | None:
+        """{"pooling", "normalize", "dim"} of an embedding engine (``arch_kw["head"] == "embed"``: ``infer``
+        returns one fp32 vector per sequence / image), else None."""
+        m = getattr(self.graph, "meta", None) or {}
+        return {k: m[k] for k in ("pooling", "normalize", "dim")} if m.get("head") == "embed" else None
+
     def infer_image(self, img) -> torch.Tensor:
         """One request of a RESIZE engine: ``img`` is a uint8 [H, W, 3] image of any size within the
         engine's maximum (tensor or array), or a list of up to ``batch`` of them. The geometry header

@@ -172,7 +172,10 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
     Returns the metadata dict stored in the file."""
     adapter = registry.get(model)
     g = adapter.build_graph(batch=batch, **arch_kw)
+    head = getattr(g, "meta", None) or {}
     if probs:
+        if head.get("head") == "embed":
+            raise ValueError("probs=True (a softmax over class logits) does not combine with an embedding plan")
         add_softmax_head(g)
     if tuned is None:
         tuned = load_tuning(model, batch, contexts)
@@ -262,6 +265,8 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
     rz = (getattr(g, "meta", None) or {}).get("resize")
     if rz:  # a resize plan: inputs are the packed image bytes and the geometry header (lite.PlanEngine.infer_image)
         meta["resize"] = dict(rz)
+    if head.get("head") == "embed":  # an embedding plan: the output is [batch, dim] fp32 vectors (POST /embed)
+        meta["embed"] = {k: head[k] for k in ("pooling", "normalize", "dim")}
     emb = params.get("emb")
     if emb is not None and hasattr(emb, "word"):  # BERT-style text plan: inputs ids / types / additive mask
         meta.update({"kind": "text", "seq_len": int(g.shape(g.inputs[0])[0]) // batch,
@@ -312,12 +317,14 @@ def export_plan(model: str, params: dict, arch_kw: dict, path: str, batch: int =
 
 def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch: int = 1, contexts: int = 1,
                            input_uint8: bool | None = None, dp_shard: int | None = None,
-                           seq_len: int | None = None, resize=None, **kw) -> str:
+                           seq_len: int | None = None, resize=None, embed: dict | None = None, **kw) -> str:
     """``torch.load`` the checkpoint, pack it on the CPU and write its plan image (deploy time,
     ``hipzap plan``); the plan is keyed to the checkpoint's identity (size, mtime, sampled hash).
     ``seq_len``: the captured sequence length of a text model (default: the adapter's, 128).
     ``resize``: ``(resize, crop, max_h, max_w)`` writes a RESIZE plan (``<ckpt>.rz.hzplan`` by default):
-    requests are uint8 images of any size up to the maximum (models/resnet.py build_graph)."""
+    requests are uint8 images of any size up to the maximum (models/resnet.py build_graph).
+    ``embed``: ``{"pooling": "mean" | "cls", "normalize": bool}`` writes an EMBEDDING plan of a BERT / ViT
+    checkpoint (``<ckpt>.emb.hzplan`` by default): the output is one pooled vector per sequence / image."""
     from .packfile import source_stamp
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
@@ -335,6 +342,14 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
         arch_kw["resize"] = [int(v) for v in resize]
         input_uint8 = False
         path = path or plan_path(ckpt, "rz")
+    if embed is not None:
+        if model.startswith("resnet"):
+            raise ValueError(f"embedding plans cover the BERT and ViT encoders, not {model}")
+        if kw.get("probs"):
+            raise ValueError("probs=True (a softmax over class logits) does not combine with an embedding plan")
+        arch_kw.update(head="embed", pooling=str(embed.get("pooling", "mean")),
+                       normalize=bool(embed.get("normalize", True)))
+        path = path or plan_path(ckpt, "emb")
     if input_uint8 is None:
         input_uint8 = model.startswith("resnet")
     if input_uint8 and model.startswith("resnet"):

@@ -501,6 +501,14 @@ class ExecContext:
             prm = tx.VitTokensParams(addr(n.inputs[0]), self.params[a["cls"]].data_ptr(),
                                      self.params[a["pos"]].data_ptr(), addr(n.outputs[0]), a["B"], a["np"], D)
             N.prog_add(lib, self.prog, N.HZ_K_VIT_TOKENS, prm, n.slot, "add_vit_tokens")
+        elif n.kind == "pool_embed":  # the embedding head: hidden states -> one fp32 vector per sequence
+            a = n.attrs
+            rows, D = g.shape(n.inputs[0])
+            assert rows == a["B"] * a["L"] and g.shape(n.outputs[0]) == (a["B"], D)
+            mask = n.inputs[1] if len(n.inputs) > 1 else None
+            prm = tx.PoolEmbedParams(addr(n.inputs[0]), addr(mask), addr(n.outputs[0]), a["B"], a["L"], D, D, D,
+                                     a["first"], tx.POOL_MODES[a["mode"]], int(a["normalize"]))
+            N.prog_add(lib, self.prog, N.HZ_K_POOL_EMBED, prm, n.slot, "add_pool_embed")
         elif n.kind == "pool_fc":
             pc = self.params[n.attrs["w"]]
             nb, h, w, c = g.shape(n.inputs[0])

@@ -171,6 +171,13 @@ def run_graph_reference(g: Graph, params: dict, inputs: list, bf16_acts: bool = 
             from ..ops.transformer import softmax_ref
             x = vals[n.inputs[0]].float().reshape(g.shape(n.inputs[0])[0], -1)
             store(n.outputs[0], softmax_ref(x, n.attrs.get("D"), float(n.attrs.get("scale", 1.0))))
+        elif k == "pool_embed":
+            from ..ops.transformer import pool_embed_ref
+            a = n.attrs
+            mask = vals[n.inputs[1]] if len(n.inputs) > 1 else None
+            y = pool_embed_ref(vals[n.inputs[0]].float().reshape(a["B"] * a["L"], -1), a["B"], a["L"], mask, a["mode"],
+                               a["first"], a["normalize"])
+            store(n.outputs[0], y.float())
         elif k == "vit_tokens":
             a = n.attrs
             D = g.shape(n.outputs[0])[-1]

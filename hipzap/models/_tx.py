@@ -189,3 +189,36 @@ class TxBuilder:
         out = g.tensor((B * L, heads * 64), torch.bfloat16, "ctx")
         g.add("attention", ins, [out], B=B, L=L, heads=heads)
         return out
+
+    def pool_embed(self, x, B, L, mask=None, mode="mean", first=0, normalize=True):
+        """The embedding head: one fp32 vector per sequence from the hidden states ``x`` (rows
+        ``b*L + t``; B rows when only the CLS rows were kept, then L = 1): the CLS row or the mean
+        of the tokens of ``[first, L)`` whose additive mask value is 0, L2-normalised if asked.
+        The output ``[B, D]`` is external (the graph's result)."""
+        if mode not in POOLINGS:
+            raise ValueError(f"pooling {mode!r}: one of {POOLINGS}")
+        g = self.g
+        rows, D = g.shape(x)
+        assert rows == B * L and (mode == "cls" or 0 <= first < L)
+        out = g.tensor((B, D), torch.float32, "embedding", external=True)
+        g.add("pool_embed", [x] if mask is None else [x, mask], [out], B=B, L=L, mode=mode, first=first,
+              normalize=bool(normalize))
+        return out
+
+
+POOLINGS = ("mean", "cls")
+HEADS = ("cls", "embed")
+
+
+def embed_head(head: str, pooling: str, has_classifier: bool, what: str) -> bool:
+    """Validate ``build_graph``'s head arguments; True for the embedding head."""
+    if head not in HEADS:
+        raise ValueError(f"head {head!r}: one of {HEADS}")
+    if head == "embed":
+        if pooling not in POOLINGS:
+            raise ValueError(f"pooling {pooling!r}: one of {POOLINGS}")
+        return True
+    if not has_classifier:
+        raise ValueError(f"head='cls' needs a classification head, and this {what} checkpoint has no "
+                         f"classifier.weight (an encoder-only checkpoint): build it with head='embed'")
+    return False

@@ -21,7 +21,7 @@ import torch
 
 from ..engine.graph import Graph
 from ..ops.transformer import EmbedTables
-from ._tx import TxBuilder, fold_ln_linear, norm, pack_linear_padded, pack_qkv
+from ._tx import TxBuilder, embed_head, fold_ln_linear, norm, pack_linear_padded, pack_qkv
 
 
 def ln_fold_default() -> bool:
@@ -37,14 +37,25 @@ def make_model(num_labels: int = 2, **cfg):
     return m.eval()
 
 
+def with_prefix(sd: dict, prefix: str, probe: str) -> dict:
+    """An encoder-only HF checkpoint (``BertModel`` / ``ViTModel``: keys without the task model's
+    ``bert.`` / ``vit.`` prefix) under the classification layout's key names; others unchanged."""
+    if prefix + probe in sd or probe not in sd:
+        return sd
+    return {(k if k.startswith("classifier.") else prefix + k): v for k, v in sd.items()}
+
+
 def config_from_sd(sd: dict) -> dict:
+    """``num_labels`` is None for a checkpoint without ``classifier.weight`` (an encoder-only
+    ``BertModel``): it lowers with ``head="embed"`` only."""
+    sd = with_prefix(sd, "bert.", "embeddings.word_embeddings.weight")
     layers = 0
     while f"bert.encoder.layer.{layers}.attention.self.query.weight" in sd:
         layers += 1
     hidden = sd["bert.embeddings.word_embeddings.weight"].shape[1]
     return {"layers": layers, "hidden": hidden, "heads": hidden // 64,
             "ffn": sd["bert.encoder.layer.0.intermediate.dense.weight"].shape[0],
-            "num_labels": sd["classifier.weight"].shape[0],
+            "num_labels": sd["classifier.weight"].shape[0] if "classifier.weight" in sd else None,
             "max_pos": sd["bert.embeddings.position_embeddings.weight"].shape[0]}
 
 
@@ -53,8 +64,10 @@ def pack_bert(sd: dict, device="cpu", eps: float = 1e-12, ln_fold: bool | None =
     """``ln_fold``: fold every encoder LayerNorm into its consumer GEMMs (see build_graph); the
     returned cfg records the choice so the graph is built to match the packed weights.
     ``weights="fp8"``: encoder projections as e4m3 + per-channel scales on the MX fp8 MFMA path
-    (pooler and classifier stay bf16; no LayerNorm fold)."""
-    sd = {k: v.to(device) for k, v in sd.items()}
+    (pooler and classifier stay bf16; no LayerNorm fold). An encoder-only ``BertModel`` checkpoint
+    packs too (no ``bert.`` prefix, no classifier, pooler optional): the parameters it lacks are
+    left out and cfg's ``num_labels`` is None."""
+    sd = {k: v.to(device) for k, v in with_prefix(sd, "bert.", "embeddings.word_embeddings.weight").items()}
     cfg = config_from_sd(sd)
     cfg["ln_fold"] = False if weights == "fp8" else (ln_fold_default() if ln_fold is None else bool(ln_fold))
     cfg["weights"] = weights
@@ -85,8 +98,10 @@ def pack_bert(sd: dict, device="cpu", eps: float = 1e-12, ln_fold: bool | None =
                                                  sd[f"{pre}.intermediate.dense.bias"])
         P[f"l{i}.ffn2"] = pack_linear_padded(sd[f"{pre}.output.dense.weight"], sd[f"{pre}.output.dense.bias"])
         P[f"l{i}.ln2"] = norm(sd, f"{pre}.output.LayerNorm", eps)
-    P["pooler"] = pack_linear_padded(sd["bert.pooler.dense.weight"], sd["bert.pooler.dense.bias"])
-    P["cls"] = pack_linear_padded(sd["classifier.weight"], sd["classifier.bias"])
+    if "bert.pooler.dense.weight" in sd:
+        P["pooler"] = pack_linear_padded(sd["bert.pooler.dense.weight"], sd["bert.pooler.dense.bias"])
+    if "classifier.weight" in sd:
+        P["cls"] = pack_linear_padded(sd["classifier.weight"], sd["classifier.bias"])
     if weights == "fp8":
         from ..ops.fp8 import quantize_params
         P = quantize_params(P, [n for n in P if n.startswith("l") and n.rsplit(".", 1)[-1] in ("qkv", "o", "ffn1", "ffn2")])
@@ -94,15 +109,21 @@ def pack_bert(sd: dict, device="cpu", eps: float = 1e-12, ln_fold: bool | None =
 
 
 def build_graph(batch: int, seq_len: int = 128, layers: int = 12, hidden: int = 768, heads: int = 12,
-                ffn: int = 3072, num_labels: int = 2, ln_fold: bool = False, weights: str = "bf16",
-                max_pos: int | None = None, **_) -> Graph:
+                ffn: int = 3072, num_labels: int | None = 2, ln_fold: bool = False, weights: str = "bf16",
+                max_pos: int | None = None, head: str = "cls", pooling: str = "mean", normalize: bool = True,
+                **_) -> Graph:
     """``ln_fold`` (must match pack_bert's cfg): no standalone encoder LayerNorm. The O-proj and
     FFN2 GEMMs emit per-row (sum, sumsq) slabs of their raw output y; FFN1 and the next layer's
     QKV run on y with gamma/beta folded into their weights and normalise in the epilogue; the
     residual reads of y are normalised in the epilogue too (HzLnFold, csrc/hipzap.h). Only the
     B CLS rows get a real LayerNorm, for the pooler. 5 kernels per layer instead of 7.
     ``max_pos``: rows of the checkpoint's position table (pack_bert's cfg); a longer ``seq_len``
-    would gather past it."""
+    would gather past it.
+    ``head="embed"``: no pooler / classifier; the graph's output is one fp32 vector ``[B, hidden]`` per
+    sequence, pooled from the last layer's LayerNorm output (``pooling`` "mean": the attention-masked
+    token mean, "cls": token 0), L2-normalised with ``normalize`` (csrc/transformer.hip
+    pool_embed_kernel). ``head="cls"`` needs the checkpoint's classifier (``num_labels`` not None)."""
+    embed = embed_head(head, pooling, num_labels is not None, "BERT")
     if seq_len < 1 or (max_pos is not None and seq_len > max_pos):
         raise ValueError(f"seq_len {seq_len} is outside the checkpoint's position table (1..{max_pos} positions)")
     B, L, D = batch, seq_len, hidden
@@ -144,6 +165,12 @@ def build_graph(batch: int, seq_len: int = 128, layers: int = 12, hidden: int = 
         h = tb.gemm(x1, f"l{i}.ffn1", ffn, act="gelu")
         y2 = tb.gemm(h, f"l{i}.ffn2", D, res=x1)
         x = tb.layernorm(y2, f"l{i}.ln2")
+    if embed:
+        if ln_x is not None:
+            raise ValueError("head='embed' pools LayerNorm outputs: not with the folded LayerNorms (ln_fold)")
+        g.outputs.append(tb.pool_embed(x, B, L, mask, mode=pooling, normalize=normalize))
+        g.meta = {"head": "embed", "pooling": pooling, "normalize": bool(normalize), "dim": D}
+        return g
     if ln_x is not None:  # the pooler reads only the CLS rows: normalise just those B rows
         xc = tb.layernorm(x, ln_x[0], rows=B, ldx=L * D, name="cls_ln")
         pooled = tb.gemm(xc, "pooler", D, act="tanh", rows=B)

@@ -23,7 +23,7 @@ import torch
 
 from ..engine.graph import Graph
 from ..ops.conv import pack_conv
-from ._tx import TxBuilder, norm, pack_linear_padded, pack_qkv
+from ._tx import TxBuilder, embed_head, norm, pack_linear_padded, pack_qkv
 
 
 def _patch_lowering(patch: int = 16, image: int = 224) -> str:
@@ -57,7 +57,16 @@ def _layer_keys(sd: dict, i: int) -> dict:
     return {}
 
 
+def _vit_keys(sd: dict) -> dict:
+    """An encoder-only ``ViTModel`` checkpoint (no ``vit.`` prefix) under the classification key names."""
+    from .bert import with_prefix
+    return with_prefix(sd, "vit.", "embeddings.patch_embeddings.projection.weight")
+
+
 def config_from_sd(sd: dict) -> dict:
+    """``num_labels`` is None for a checkpoint without ``classifier.weight`` (an encoder-only
+    ``ViTModel``): it lowers with ``head="embed"`` only."""
+    sd = _vit_keys(sd)
     layers = 0
     while _layer_keys(sd, layers):
         layers += 1
@@ -67,13 +76,15 @@ def config_from_sd(sd: dict) -> dict:
     image = int(round((npos - 1) ** 0.5)) * patch
     fc1 = _layer_keys(sd, 0)["fc1"]
     return {"layers": layers, "hidden": hidden, "heads": hidden // 64, "patch": patch, "image": image,
-            "ffn": sd[f"{fc1}.weight"].shape[0], "num_labels": sd["classifier.weight"].shape[0]}
+            "ffn": sd[f"{fc1}.weight"].shape[0],
+            "num_labels": sd["classifier.weight"].shape[0] if "classifier.weight" in sd else None}
 
 
 def pack_vit(sd: dict, device="cpu", eps: float = 1e-12, weights: str = "bf16",
              patch_lowering: str | None = None) -> tuple[dict, dict]:
-    """``patch_lowering``: the source rank's choice (broadcast metadata); default: decided here."""
-    sd = {k: v.to(device) for k, v in sd.items()}
+    """``patch_lowering``: the source rank's choice (broadcast metadata); default: decided here.
+    An encoder-only ``ViTModel`` checkpoint packs too: no ``head`` parameter, cfg ``num_labels`` None."""
+    sd = {k: v.to(device) for k, v in _vit_keys(sd).items()}
     cfg = config_from_sd(sd)
     pw = sd["vit.embeddings.patch_embeddings.projection.weight"]
     pb = sd["vit.embeddings.patch_embeddings.projection.bias"]
@@ -82,8 +93,9 @@ def pack_vit(sd: dict, device="cpu", eps: float = 1e-12, weights: str = "bf16",
                    else pack_linear_padded(pw.reshape(pw.shape[0], -1), pb)),
          "cls_token": sd["vit.embeddings.cls_token"].reshape(-1).to(torch.bfloat16).contiguous(),
          "pos": sd["vit.embeddings.position_embeddings"].reshape(-1, cfg["hidden"]).to(torch.bfloat16).contiguous(),
-         "final_ln": norm(sd, "vit.layernorm", eps),
-         "head": pack_linear_padded(sd["classifier.weight"], sd["classifier.bias"])}
+         "final_ln": norm(sd, "vit.layernorm", eps)}
+    if "classifier.weight" in sd:
+        P["head"] = pack_linear_padded(sd["classifier.weight"], sd["classifier.bias"])
     for i in range(cfg["layers"]):
         k = _layer_keys(sd, i)
         P[f"l{i}.qkv"] = pack_qkv(sd[f"{k['q']}.weight"], sd[f"{k['q']}.bias"], sd[f"{k['k']}.weight"],
@@ -101,8 +113,15 @@ def pack_vit(sd: dict, device="cpu", eps: float = 1e-12, weights: str = "bf16",
 
 
 def build_graph(batch: int, layers: int = 12, hidden: int = 768, heads: int = 12, ffn: int = 3072,
-                patch: int = 16, image: int = 224, num_labels: int = 1000, weights: str = "bf16",
-                patch_lowering: str | None = None, **_) -> Graph:
+                patch: int = 16, image: int = 224, num_labels: int | None = 1000, weights: str = "bf16",
+                patch_lowering: str | None = None, head: str = "cls", pooling: str = "cls",
+                normalize: bool = True, **_) -> Graph:
+    """``head="embed"``: no classifier; the output is one fp32 vector ``[B, hidden]`` per image, pooled
+    from the final LayerNorm's output -- ``pooling`` "cls" (the CLS token; the LayerNorm runs on the B
+    CLS rows only) or "mean" (the patch tokens' mean, CLS skipped; the LayerNorm runs on every row) --
+    L2-normalised with ``normalize`` (csrc/transformer.hip pool_embed_kernel). ``head="cls"`` needs the
+    checkpoint's classifier (``num_labels`` not None)."""
+    embed = embed_head(head, pooling, num_labels is not None, "ViT")
     B, D = batch, hidden
     n_side = image // patch
     npch = n_side * n_side
@@ -139,6 +158,16 @@ def build_graph(batch: int, layers: int = 12, hidden: int = 768, heads: int = 12
             x2 = tb.gemm(ctx, f"l{i}.o", D, res=x)
             f = tb.gemm(tb.layernorm(x2, f"l{i}.ln2"), f"l{i}.fc1", ffn, act="gelu")
             x = tb.gemm(f, f"l{i}.fc2", D, res=x2)
+    if embed:
+        if pooling == "cls":
+            e = tb.pool_embed(tb.layernorm(x, "final_ln", rows=B, ldx=T * D, name="cls_ln"), B, 1, mode="cls",
+                              normalize=normalize)
+        else:
+            e = tb.pool_embed(tb.layernorm(x, "final_ln", name="final_ln"), B, T, mode="mean", first=1,
+                              normalize=normalize)
+        g.outputs.append(e)
+        g.meta = {"head": "embed", "pooling": pooling, "normalize": bool(normalize), "dim": D}
+        return g
     cls = tb.layernorm(x, "final_ln", rows=B, ldx=T * D, name="cls_ln")
     npad = (num_labels + 3) // 4 * 4
     logits = tb.linear(cls, "head", npad, fp8=f8, out_f32=True, ext=True)

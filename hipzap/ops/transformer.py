@@ -56,6 +56,16 @@ class VitTokensParams(C.Structure):
                 ("B", C.c_int), ("np", C.c_int), ("D", C.c_int)]
 
 
+@N.params_of("HZ_K_POOL_EMBED")
+class PoolEmbedParams(C.Structure):  # HzPoolEmbedParams: CLS row / masked token mean (+ L2 norm) per sequence
+    _fields_ = [("x", C.c_void_p), ("mask", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("L", C.c_int),
+                ("D", C.c_int), ("ldx", C.c_int), ("ldo", C.c_int), ("first", C.c_int), ("mode", C.c_int),
+                ("normalize", C.c_int)]
+
+
+POOL_MODES = {"cls": 0, "mean": 1}  # HzPoolEmbedParams.mode
+
+
 def launch(kind: int, prm, stream=None):
     N.check(N.lib().hz_launch_kernel(kind, C.byref(prm), N.stream_ptr(stream)), f"kernel {kind}")
 
@@ -139,7 +149,43 @@ def attention(qkv: torch.Tensor, B: int, L: int, heads: int, mask: torch.Tensor 
     return out
 
 
+def pool_embed(x: torch.Tensor, B: int, L: int, mask: torch.Tensor | None = None, mode: str = "mean",
+               first: int = 0, normalize: bool = True, D: int | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """One fp32 vector per sequence from the hidden states ``x`` (bf16 ``[B*L, ldx]``, ``D`` columns
+    used): the CLS row (``mode="cls"``) or the mean of the tokens of ``[first, L)`` whose additive
+    ``mask`` value is 0, optionally divided by its L2 norm. ``out``: fp32 ``[B, ldo]``, columns past
+    ``D`` are zeroed. A shape the kernel does not take raises."""
+    assert x.dtype == torch.bfloat16 and x.stride(1) == 1
+    D = D if D is not None else x.shape[1]
+    out = out if out is not None else torch.empty(B, D, dtype=torch.float32, device=x.device)
+    prm = PoolEmbedParams(x.data_ptr(), N.ptr(mask), out.data_ptr(), B, L, D, x.stride(0), out.stride(0),
+                          first, POOL_MODES[mode], int(bool(normalize)))
+    launch(N.HZ_K_POOL_EMBED, prm)
+    return out
+
+
 # ----------------------------------------------------------------------------- oracles
+def pool_embed_ref(x, B: int, L: int, mask=None, mode: str = "mean", first: int = 0,
+                   normalize: bool = True) -> torch.Tensor:
+    """fp64 on the CPU: ``x`` ``[B*L, D]`` (any float dtype) -> ``[B, D]``. ``mean``: the sum of
+    the counted tokens over their number (a token of ``[first, L)`` counts iff its additive mask
+    value is 0; no counted token: zeros); ``cls``: row 0 of each sequence. ``normalize``: divided
+    by ``max(||v||_2, 1e-12)`` (``F.normalize``)."""
+    x = x.detach().to("cpu", torch.float64).reshape(B, L, -1)
+    if POOL_MODES[mode] == 0:
+        v = x[:, 0]
+    else:
+        on = torch.ones(B, L, dtype=torch.float64) if mask is None else \
+            (mask.detach().to("cpu", torch.float64).reshape(B, L) == 0).double()
+        on[:, :first] = 0
+        cnt = on.sum(1, keepdim=True)
+        v = (x * on[:, :, None]).sum(1) / cnt.clamp(min=1.0)
+    if normalize:
+        v = v / v.norm(dim=1, keepdim=True).clamp(min=1e-12)
+    return v
+
+
 def layernorm_ref(x, np_: NormParams, residual=None):
     x = x.float() + (residual.float() if residual is not None else 0)
     return F.layer_norm(x, (x.shape[-1],), np_.gamma.float(), np_.beta.float(), np_.eps)

@@ -5,6 +5,9 @@ Routes (reference: /root/reference/main.py:17-18, 105-112):
                     optional query: prompt, words, seed
   POST /predict     image / tensor classification -> {"model", "top5", "timing_ms", ...}
                     (north-star API; ``model`` selects resnet50 (default), resnet18, ...)
+  POST /embed       one pooled vector per text / image from a BERT or ViT encoder served with
+                    ``extra.embed`` -> {"model", "dim", "pooling", "normalized", "embeddings", ...}, or a
+                    float32 ``.npy`` [n, dim] with ``Accept: application/octet-stream``
   GET  /health      liveness + loaded models;  GET /metrics  Prometheus text;  GET /  info
 torch is imported lazily: a plan-backed vision model (server.PlanVisionBackend) serves uint8
 images end to end without it (decode -> pinned input -> hipGraph -> top-5 in numpy).
@@ -124,7 +127,7 @@ def _error(e):
 def index():
     s = get_server()
     return _json({"service": "hipzap", "version": __version__, "backend": s.backend,
-                  "routes": ["GET /inference", "POST /predict", "GET /health", "GET /metrics"]})
+                  "routes": ["GET /inference", "POST /predict", "POST /embed", "GET /health", "GET /metrics"]})
 
 
 @app.route("/inference", methods=["GET"])
@@ -312,6 +315,75 @@ def predict():
     if request.args.get("logits") and logits is not None:
         out["logits"] = logits.tolist()
     return _json(out)
+
+
+def _text_arrays(body):
+    ids = np.asarray(body["input_ids"], dtype=np.int64)
+    if ids.ndim == 1:
+        ids = ids[None]
+    tt = body.get("token_type_ids")
+    am = body.get("attention_mask")
+    tt = np.asarray(tt, dtype=np.int64).reshape(ids.shape) if tt is not None else None
+    am = np.asarray(am, dtype=np.int64).reshape(ids.shape) if am is not None else None
+    return ids, tt, am
+
+
+def _need_embed(backend, model):
+    if getattr(backend, "embed", None) is None:
+        raise ValueError(f"{model} is served without extra.embed (a classification model): POST /predict, or set "
+                         f'"embed": {{"pooling": "mean", "normalize": true}} in its settings block')
+    return backend.embed
+
+
+@app.route("/embed", methods=["POST"])
+def embed():
+    """One pooled vector per sequence (``input_ids`` [+ ``attention_mask``, ``token_type_ids``]) or
+    per image (the bodies of /predict) from a model whose settings block has ``extra.embed``."""
+    s = get_server()
+    body = {}
+    if request.mimetype != "application/octet-stream" and request.mimetype not in IMAGE_TYPES:
+        body = request.get_json(force=True, silent=True) or {}
+    if "input_ids" in body:
+        model = body.get("model") or "bert-base"
+        ids, tt, am = _text_arrays(body)
+        with phase("load"):
+            backend = s.text(model)
+        e = _need_embed(backend, model)
+        t0 = time.perf_counter()
+        with phase("infer"):
+            if hasattr(backend, "embed_np"):  # plan-backed: torch-free
+                vec = backend.embed_np(ids, tt, am)
+            else:
+                import torch
+                def tens(a):
+                    return None if a is None else torch.from_numpy(a)
+                vec = backend.embed_ids(tens(ids), tens(tt), tens(am)).float().numpy()
+        n = int(ids.shape[0])
+    else:
+        with phase("decode"):
+            model, arr = decode_input(request)
+        with phase("load"):
+            backend = s.vision(model)
+        e = _need_embed(backend, model)
+        t0 = time.perf_counter()
+        if arr.dtype == np.uint8 and hasattr(backend, "embed_u8") and backend.accepts_u8(arr.shape):
+            with phase("infer"):
+                vec = backend.embed_u8(arr)
+        else:
+            with phase("preprocess"):
+                x = to_model_input(arr, s.resize_spec(model))
+            with phase("infer"):
+                vec = backend.embed_x(x).float().numpy()
+        n = int(arr.shape[0])
+    dt = (time.perf_counter() - t0) * 1e3
+    vec = np.ascontiguousarray(vec, np.float32)
+    if "application/octet-stream" in request.headers.get("Accept", ""):
+        buf = io.BytesIO()
+        np.save(buf, vec, allow_pickle=False)
+        return Response(response=buf.getvalue(), status=200, mimetype="application/octet-stream")
+    return _json({"model": model, "backend": backend.backend, "batch": n, "dim": int(vec.shape[1]),
+                  "pooling": e["pooling"], "normalized": bool(e["normalize"]),
+                  "embeddings": [[float(v) for v in row] for row in vec], "timing_ms": round(dt, 3)})
 
 
 @app.route("/health", methods=["GET"])

@@ -59,6 +59,21 @@ def _state_dict(src) -> dict:
     return sd
 
 
+def embed_spec(spec: ModelSpec, default_pooling: str) -> dict | None:
+    """``extra.embed`` of a model's settings block -> {"pooling", "normalize"}, or None (no /embed)."""
+    e = spec.extra.get("embed")
+    if not e:
+        return None
+    e = e if isinstance(e, dict) else {}
+    return {"pooling": str(e.get("pooling", default_pooling)), "normalize": bool(e.get("normalize", True))}
+
+
+def _strip_prefix(sd: dict, prefix: str) -> dict:
+    """A classification checkpoint's encoder under the encoder-only model's key names."""
+    return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)} or \
+        {k: v for k, v in sd.items() if not k.startswith("classifier.")}
+
+
 class VisionBackend:
     def __init__(self, name: str, sd, backend: str, device: str, spec: ModelSpec, capture: bool):
         from ..models import registry
@@ -67,10 +82,29 @@ class VisionBackend:
         self.adapter = registry.get(name)
         # "probs": true in the model's settings block -> the softmax runs on device, responses are probabilities
         self.probs = bool(spec.extra.get("probs", False))
+        # "embed": {"pooling", "normalize"} in the model's settings block -> an embedding backend (POST /embed)
+        self.embed = embed_spec(spec, "cls") if name.startswith("vit") else None
+        if self.embed is not None and self.probs:
+            raise ValueError(f"{name}: extra.probs does not combine with extra.embed")
         if backend == "gpu":
+            akw = dict(self.embed, head="embed") if self.embed is not None else None
             self.engine = _gpu_engine(name, sd, device, batch=spec.batch, num_contexts=spec.contexts,
-                                      capture=capture, probs=self.probs)
+                                      capture=capture, probs=self.probs, arch_kw=akw)
             self.model = None
+            if self.embed is not None:
+                self.embed = self.engine.embed
+        elif self.embed is not None:  # the HF encoder; pooled by the oracle (ops/transformer.py pool_embed_ref)
+            from transformers import ViTConfig, ViTModel
+            from ..models.vit import config_from_sd
+            sd = _state_dict(sd)
+            cfg = config_from_sd(sd)
+            self.model = ViTModel(ViTConfig(num_hidden_layers=cfg["layers"], hidden_size=cfg["hidden"],
+                                            num_attention_heads=cfg["heads"], intermediate_size=cfg["ffn"],
+                                            patch_size=cfg["patch"], image_size=cfg["image"]),
+                                  add_pooling_layer=False).eval()
+            self.model.load_state_dict(_strip_prefix(sd, "vit."), strict=False)
+            self.embed = dict(self.embed, dim=cfg["hidden"])
+            self.engine = None
         else:
             from ..models.resnet import infer_arch
             sd = _state_dict(sd)
@@ -96,8 +130,25 @@ class VisionBackend:
             chunk = torch.cat([chunk, chunk.new_zeros((self.batch - n,) + tuple(chunk.shape[1:]))])
         return self.engine.infer(chunk)[:n]
 
+    def embed_x(self, x):
+        """fp32 NCHW images -> [n, dim] float32 vectors (an ``extra.embed`` backend)."""
+        import torch
+        if self.embed is None:
+            raise ValueError(f"{self.name} is served without extra.embed: POST /predict")
+        if self.engine is not None:
+            return torch.cat([self._run_padded(x[i: i + self.batch]) for i in range(0, x.shape[0], self.batch)])
+        from ..ops.transformer import pool_embed_ref
+        with torch.no_grad():
+            h = self.model(pixel_values=x.float()).last_hidden_state
+        n, T, _ = h.shape
+        e = self.embed
+        return pool_embed_ref(h.reshape(n * T, -1), n, T, None, e["pooling"], int(e["pooling"] == "mean"),
+                              e["normalize"]).float()
+
     def __call__(self, x):
         import torch
+        if self.embed is not None:
+            raise ValueError(f"{self.name} is an embedding plan: POST /embed")
         if self.engine is not None:
             if self.batcher is not None and x.shape[0] < self.batch:
                 return self.batcher(x)
@@ -116,12 +167,31 @@ class TextBackend:
         t0 = time.perf_counter()
         self.adapter = registry.get(name)
         self.seq_len = int(spec.extra.get("seq_len", 128))
+        # "embed": {"pooling", "normalize"} in the model's settings block -> an embedding backend (POST /embed)
+        self.embed = embed_spec(spec, "mean")
         if backend == "gpu":
             # "seq_len" in the model's settings block is the captured length (default: the adapter's)
-            akw = {"seq_len": self.seq_len} if "seq_len" in spec.extra else None
+            akw = {"seq_len": self.seq_len} if "seq_len" in spec.extra else {}
+            if self.embed is not None:
+                akw.update(self.embed, head="embed")
             self.engine = _gpu_engine(name, sd, device, batch=spec.batch, num_contexts=spec.contexts, capture=capture,
-                                      arch_kw=akw)
+                                      arch_kw=akw or None)
             self.model = None
+            if self.embed is not None:
+                self.embed = self.engine.embed
+        elif self.embed is not None:  # the HF encoder; pooled by the oracle (ops/transformer.py pool_embed_ref)
+            from transformers import BertConfig, BertModel
+            from ..models.bert import config_from_sd, with_prefix
+            sd = with_prefix(_state_dict(sd), "bert.", "embeddings.word_embeddings.weight")
+            cfg = config_from_sd(sd)
+            self.model = BertModel(BertConfig(
+                num_hidden_layers=cfg["layers"], hidden_size=cfg["hidden"], num_attention_heads=cfg["heads"],
+                intermediate_size=cfg["ffn"], vocab_size=sd["bert.embeddings.word_embeddings.weight"].shape[0],
+                max_position_embeddings=cfg["max_pos"]), add_pooling_layer=False).eval()
+            self.model.load_state_dict(_strip_prefix(sd, "bert."), strict=False)
+            self.embed = dict(self.embed, dim=cfg["hidden"])
+            self.vocab = int(sd["bert.embeddings.word_embeddings.weight"].shape[0])
+            self.engine = None
         else:
             from ..models.bert import config_from_sd, make_model
             sd = _state_dict(sd)
@@ -135,11 +205,34 @@ class TextBackend:
         self.batch = spec.batch
         self.cold_ms = (time.perf_counter() - t0) * 1e3
 
+    def embed_ids(self, ids, types=None, mask=None):
+        """Token ids [n, L] (+ optional token types / attention mask) -> [n, dim] float32 vectors."""
+        if self.embed is None:
+            raise ValueError(f"{self.name} is served without extra.embed: POST /predict")
+        return self._run(ids, types, mask)
+
     def __call__(self, ids, types=None, mask=None):
+        if self.embed is not None:
+            raise ValueError(f"{self.name} is an embedding plan: POST /embed")
+        return self._run(ids, types, mask)
+
+    def _run(self, ids, types=None, mask=None):
         import torch
         B, L = ids.shape
         types = types if types is not None else torch.zeros_like(ids)
         mask = mask if mask is not None else torch.ones_like(ids)
+        if self.engine is None and self.embed is not None:
+            from ..models.bert import encode_inputs
+            from ..ops.transformer import pool_embed_ref
+            if L > self.seq_len:
+                raise ValueError(f"sequence length {L} exceeds the captured {self.seq_len}")
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.vocab):
+                raise ValueError(f"token ids must lie in [0, {self.vocab})")
+            with torch.no_grad():
+                h = self.model(input_ids=ids, token_type_ids=types, attention_mask=mask).last_hidden_state
+            e = self.embed
+            return pool_embed_ref(h.reshape(B * L, -1), B, L, encode_inputs(ids, types, mask)[2], e["pooling"], 0,
+                                  e["normalize"]).float()
         if self.engine is None:
             with torch.no_grad():
                 return self.model(input_ids=ids, token_type_ids=types, attention_mask=mask).logits
@@ -327,7 +420,8 @@ class ModelServer:
         from ..engine.packfile import same_source
         ckpt = self.store.fetch(spec.key)
         # "resize" in the model's settings block: the resize plan (`hipzap plan --resize`, <ckpt>.rz.hzplan)
-        suffix = ".rz.hzplan" if spec.extra.get("resize") else ".hzplan"
+        # "embed": the embedding plan (`hipzap plan --embed`, <ckpt>.emb.hzplan)
+        suffix = ".emb.hzplan" if spec.extra.get("embed") else ".rz.hzplan" if spec.extra.get("resize") else ".hzplan"
         path = ckpt + suffix
         fetched = False
         if not os.path.exists(path):
@@ -458,6 +552,7 @@ class PlanVisionBackend:
         self.batch = self.in_shape[0]
         self.probs = bool(self.meta.get("probs"))
         self.num_labels = self.meta["output"].get("num_labels") or self.meta["output"]["shape"][-1]
+        self.embed = self.meta.get("embed")  # an embedding plan: {"pooling", "normalize", "dim"}, else None
         # batch-B plan behind the native /predict route: dynamic batching, "batching": {"max_wait_ms"}
         self.max_wait_us = float((spec.extra.get("batching") or {}).get("max_wait_ms", 0.2)) * 1e3
         self._torch, self._torch_lock = None, threading.Lock()
@@ -484,6 +579,17 @@ class PlanVisionBackend:
     def infer_u8(self, imgs):
         """``imgs``: uint8 numpy array [N, H, W, 3] -> numpy [N, classes] (logits or probs). With a
         resize plan also a list of [H, W, 3] arrays of different sizes."""
+        if self.embed is not None:
+            raise ValueError(f"{self.name} is an embedding plan: POST /embed")
+        return self._run_u8(imgs)
+
+    def embed_u8(self, imgs):
+        """As :meth:`infer_u8` on an embedding plan -> numpy float32 vectors [N, dim]."""
+        if self.embed is None:
+            raise ValueError(f"{self.name} is served without extra.embed: POST /predict")
+        return self._run_u8(imgs)
+
+    def _run_u8(self, imgs):
         import numpy as np
         if self.resize is not None:
             return self._infer_images(list(imgs))
@@ -502,14 +608,22 @@ class PlanVisionBackend:
     def __call__(self, x):
         """torch-tensor entry (fp32 NCHW etc.): served by a torch-built engine of the same
         checkpoint (the plan's source), built on first use."""
+        return self._torch_backend()(x)
+
+    def embed_x(self, x):
+        """As :meth:`__call__` for an embedding plan: [n, dim] vectors from the torch-built engine."""
+        return self._torch_backend().embed_x(x)
+
+    def _torch_backend(self):
         with self._torch_lock:
             if self._torch is None:
-                ckpt = self.plan[: -len(".rz.hzplan" if self.plan.endswith(".rz.hzplan") else ".hzplan")]
+                sfx = [f for f in (".rz.hzplan", ".emb.hzplan") if self.plan.endswith(f)]
+                ckpt = self.plan[: -len(sfx[0] if sfx else ".hzplan")]
                 if not os.path.exists(ckpt):
                     raise ValueError(f"{self.name} is served from a plan image: send uint8 HWC images "
                                      f"{list(self.in_shape[1:])} (image_b64 or a uint8 .npy)")
                 self._torch = VisionBackend(self.name, ckpt, "gpu", f"cuda:{self.device}", self.spec, True)
-        return self._torch(x)
+        return self._torch
 
 class PlanTextBackend:
     """Torch-free BERT-style serving from a text plan image (``hipzap plan --model bert-base
@@ -533,12 +647,24 @@ class PlanTextBackend:
         self.batch, self.seq_len = int(m["batch"]), int(m["seq_len"])
         self.vocab, self.type_vocab = int(m["vocab"]), int(m["type_vocab"])
         self.num_labels = m["output"].get("num_labels") or m["output"]["shape"][-1]
+        self.embed = m.get("embed")  # an embedding plan: {"pooling", "normalize", "dim"}, else None
         self.cold_ms = (time.perf_counter() - t0) * 1e3
         threading.Thread(target=self.engine.ensure_contexts, daemon=True, name=f"{name}-contexts").start()
 
     def infer_np(self, ids, types=None, mask=None):
         """``ids`` (and optional ``types`` / ``mask``): int arrays [n, L] with L <= seq_len ->
         numpy float32 logits [n, num_labels]."""
+        if self.embed is not None:
+            raise ValueError(f"{self.name} is an embedding plan: POST /embed")
+        return self._run(ids, types, mask, self.num_labels)
+
+    def embed_np(self, ids, types=None, mask=None):
+        """As :meth:`infer_np` on an embedding plan -> numpy float32 vectors [n, dim]."""
+        if self.embed is None:
+            raise ValueError(f"{self.name} is served without extra.embed: POST /predict")
+        return self._run(ids, types, mask, int(self.embed["dim"]))
+
+    def _run(self, ids, types, mask, width):
         import numpy as np
         ids = np.asarray(ids)
         if ids.ndim == 1:
@@ -553,7 +679,7 @@ class PlanTextBackend:
         if types.size and (types.min() < 0 or types.max() >= self.type_vocab):
             raise ValueError(f"token type ids must lie in [0, {self.type_vocab})")
         B, Lc = self.batch, self.seq_len
-        out = np.empty((n, self.num_labels), np.float32)
+        out = np.empty((n, width), np.float32)
         for i in range(0, n, B):
             m = min(B, n - i)
             ci = np.zeros((B, Lc), np.int32)
@@ -564,7 +690,7 @@ class PlanTextBackend:
             cm[:m, :L] = mask[i: i + m]
             madd = (np.float32(1.0) - cm) * np.float32(-1e9)
             y = np.frombuffer(self.engine.infer_raw([ci, ct, madd]), np.float32).reshape(B, -1)
-            out[i: i + m] = y[:m, : self.num_labels]
+            out[i: i + m] = y[:m, :width]
         return out
 
     def __call__(self, ids, types=None, mask=None):

@@ -3,7 +3,9 @@
 synthetic inputs): BERT-base seq-cls bs=16 L=128, ViT-B/16 (bf16 / fp8) per-GPU batch 8,
 ResNet-50 per-GPU batch 4 (the bs=32 DP=8 config's per-GPU share). One JSON line per config.
 ``--seq-len N`` (BERT) / ``--image N`` (ViT) / ``--batch N`` time other shapes, e.g. BERT L=512 or
-ViT-B/16 at 384 px (577 tokens): the streamed attention kernel's ground."""
+ViT-B/16 at 384 px (577 tokens): the streamed attention kernel's ground. ``--embed`` times the BERT /
+ViT embedding engines (head="embed": masked mean for BERT, CLS for ViT, L2-normalised) instead of the
+classifiers."""
 import json
 import os
 import sys
@@ -36,7 +38,7 @@ def _make_model(name, a, image=None):
     return a.make_model()
 
 
-def run(name, batch, contexts, iters=100, seq_len=None, image=None):
+def run(name, batch, contexts, iters=100, seq_len=None, image=None, embed=False):
     a = registry.get(name)
     torch.manual_seed(0)
     m = _make_model(name, a, image)
@@ -46,7 +48,10 @@ def run(name, batch, contexts, iters=100, seq_len=None, image=None):
     sd = m.state_dict()
     t0 = time.perf_counter()
     text = name.startswith("bert")
-    akw = {"seq_len": seq_len} if text and seq_len else None
+    akw = {"seq_len": seq_len} if text and seq_len else {}
+    if embed and not name.startswith("resnet"):
+        akw.update(head="embed", pooling="mean" if text else "cls", normalize=True)
+    akw = akw or None
     eng = Engine.from_state_dict(name, sd, "cuda:0", batch=batch, num_contexts=contexts, arch_kw=akw)
     if text:
         x = a.example_input(batch, seq_len=seq_len)
@@ -106,6 +111,7 @@ def torch_reference(name, batch, iters=100, seq_len=None, image=None):
 
 def main():
     seq_len, image, batch = _opt("--seq-len"), _opt("--image"), _opt("--batch")
+    embed = "--embed" in sys.argv
     vals = {sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a in ("--seq-len", "--image", "--batch")}
     args = [a for a in sys.argv[1:] if not a.startswith("--") and a not in vals]
     names = args or list(CONFIGS)
@@ -123,8 +129,10 @@ def main():
                 print(json.dumps({"model": name, "impl": "pytorch", "error": repr(e)[:300]}), flush=True)
         for ctx in (1, 4):
             try:
-                r = run(name, c["batch"], ctx, seq_len=seq_len, image=image)
+                r = run(name, c["batch"], ctx, seq_len=seq_len, image=image, embed=embed)
                 r.update(shape)
+                if embed and not name.startswith("resnet"):
+                    r["head"] = "embed"
                 r["unit"] = c["unit"]
                 if not shape and not batch:  # the CPU figures are for the default shapes
                     r["vs_sandbox_cpu"] = round(r["items_per_s"] / c["ref_cpu"], 1)
