@@ -142,7 +142,7 @@ def main(argv=None):
     pl.add_argument("--dp-shard", type=int, default=None,
                     help="also write <ckpt>.dp<S>.hzplan: the per-GPU shard program of batched DP requests")
     pl.add_argument("--resize", type=int, default=None,
-                    help="vision models: write a RESIZE plan -- requests are uint8 images of any size, the shorter "
+                    help="ResNet / ViT: write a RESIZE plan (with --embed: <ckpt>.emb.rz.hzplan) -- requests are uint8 images of any size, the shorter "
                          "side resized to this (antialiased bilinear), centre-cropped and normalised on the GPU")
     pl.add_argument("--embed", action="store_true",
                     help="BERT / ViT: write an EMBEDDING plan (<ckpt>.emb.hzplan) -- the output is one pooled vector "

@@ -35,6 +35,7 @@ KINDS = {
     "HZ_K_LMB_ADMIT": 16, "HZ_K_STEM": 18, "HZ_K_BNECK": 19, "HZ_K_SEAM": 20, "HZ_K_KCONV": 21,
     "HZ_K_QKVATT": 22, "HZ_K_CONV2": 23, "HZ_K_AVGPOOL": 24, "HZ_K_PREPROCESS": 25, "HZ_K_STEP_BUMP": 26,
     "HZ_K_DIAG": 27, "HZ_K_RESIZE_PREPROCESS": 28, "HZ_K_POOL_EMBED": 29,
+    "HZ_K_RESIZE_PATCHIFY": 30,
 }
 globals().update(KINDS)
 KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct

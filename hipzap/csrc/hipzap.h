@@ -101,6 +101,12 @@ typedef struct HzResizeParams {
   float mean[4], inv_std[4];   // (x / 255 - mean) * inv_std
 } HzResizeParams;
 int hz_resize_preprocess_launch(const HzResizeParams* p, hipStream_t st);
+// The same resize, crop and normalisation written as ViT patch rows (vision.hip resize_patchify_kernel):
+// `out` is bf16 [B * n * n][3 * 16 * 16], n = crop / 16; pixel (oy, ox) channel c of image b is column
+// c * 256 + (oy % 16) * 16 + ox % 16 of row (b * n + oy / 16) * n + ox / 16 (the patchify layout, the
+// patch-embed GEMM's operand). The same value per pixel as the NHWC8 kernel, bit for bit. Also refuses
+// a crop that is no multiple of 16 or below 16.
+int hz_resize_patchify_launch(const HzResizeParams* p, hipStream_t st);
 
 // elementwise helpers
 int hz_cast_f32_bf16(const float* x, unsigned short* y, long n, hipStream_t st);
@@ -595,7 +601,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(STEP_BUMP, 26, HzStepBumpArgs, hz_step_bump_op, LSTM)                 \
   X(DIAG, 27, HzDiagArgs, hz_diag_op, DIAG)                               \
   X(RESIZE_PREPROCESS, 28, HzResizeParams, hz_resize_preprocess_op, VISION) \
-  X(POOL_EMBED, 29, HzPoolEmbedParams, hz_pool_embed_op, TRANSFORMER)
+  X(POOL_EMBED, 29, HzPoolEmbedParams, hz_pool_embed_op, TRANSFORMER)     \
+  X(RESIZE_PATCHIFY, 30, HzResizeParams, hz_resize_patchify_op, VISION)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -417,6 +417,10 @@ extern "C" __attribute__((weak)) int hz_resize_preprocess_launch(const HzResizeP
 static int hz_resize_preprocess_op(const HzResizeParams* p, hipStream_t st) {
   return hz_resize_preprocess_launch ? hz_resize_preprocess_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_resize_patchify_launch(const HzResizeParams* p, hipStream_t st);
+static int hz_resize_patchify_op(const HzResizeParams* p, hipStream_t st) {
+  return hz_resize_patchify_launch ? hz_resize_patchify_launch(p, st) : -102;
+}
 // (the pooled-embedding launcher likewise: transformer.hip in the library)
 extern "C" __attribute__((weak)) int hz_pool_embed_launch(const HzPoolEmbedParams* p, hipStream_t st);
 static int hz_pool_embed_op(const HzPoolEmbedParams* p, hipStream_t st) {

@@ -325,8 +325,11 @@ __device__ __forceinline__ float rsz_inv_total(const RszTaps& t) {
 // registers before the staged one is consumed. Per source row a thread forms its horizontally filtered
 // pixel from LDS and adds it into the band's output rows with their vertical weights (fp32 throughout;
 // no intermediate image). Geometry comes from dims[b] and is wave-uniform except the thread's own column.
-__global__ __launch_bounds__(256) void resize_preprocess_kernel(const HzResizeParams p) {
-  __shared__ __attribute__((aligned(16))) u32x4 stage[256 * HZ_RSZ_UNITS];
+// rsz_band is that computation, shared by the two kernels below so that both form the same value for
+// the same pixel: v[r][c] = the normalised fp32 pixel (band row r, the thread's column, channel c).
+// Every thread of the workgroup runs it to the end (its barriers are workgroup-uniform); a thread past
+// the crop's last column computes column crop - 1 again. `stage` is free once it returns.
+__device__ __forceinline__ void rsz_band(const HzResizeParams& p, u32x4* stage, float (&v)[HZ_RSZ_ROWS][3]) {
   constexpr int R = HZ_RSZ_ROWS, U = HZ_RSZ_UNITS;
   const int t = threadIdx.x, b = blockIdx.y, oy0 = blockIdx.x * R;
   const int* d = p.dims + (long)b * 8;
@@ -404,15 +407,57 @@ __global__ __launch_bounds__(256) void resize_preprocess_kernel(const HzResizePa
     }
     __syncthreads();
   }
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[r][c] = (acc[r][c] * (1.0f / 255.0f) - p.mean[c]) * p.inv_std[c];
+}
+
+// -> bf16 NHWC8 [B][crop][crop][8], channels 3..7 zero: one 16-B store per pixel.
+__global__ __launch_bounds__(256) void resize_preprocess_kernel(const HzResizeParams p) {
+  __shared__ __attribute__((aligned(16))) u32x4 stage[256 * HZ_RSZ_UNITS];
+  constexpr int R = HZ_RSZ_ROWS;
+  const int t = threadIdx.x, b = blockIdx.y, oy0 = blockIdx.x * R;
+  float v[R][3];
+  rsz_band(p, stage, v);
   if (t >= p.crop) return;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int oy = oy0 + r;
     if (oy >= p.crop) break;
-    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const float o[8] = {v[r][0], v[r][1], v[r][2], 0, 0, 0, 0, 0};
+    *reinterpret_cast<u32x4*>(p.out + (((long)b * p.crop + oy) * p.crop + t) * 8) = pack8(o);
+  }
+}
+
+// -> bf16 ViT patch rows [B * n * n][3 * 16 * 16], n = crop / 16, column (c, ky, kx): patchify_kernel's
+// layout, written without the NHWC8 image in between. crop % 16 == 0 (launcher), so a band of 8 output
+// rows is the upper or lower half (h) of one row of patches: ky in [8h, 8h + 8). A thread's 8 x 3
+// values go as bf16 into an LDS tile [px][c][r][kx] (the staging buffer, free after the band's final
+// barrier; 12 KiB at crop 256). For a fixed (px, c) the tile's 8 x 16 values are the 256 contiguous
+// bytes at column c * 256 + h * 128 of patch row px, so 16-B chunk q of the tile goes to chunk q & 15
+// of run q >> 4: consecutive lanes store consecutive 16 bytes. Threads past the crop's last column own
+// no pixel but take part in the barrier and the write-out (crop 16: 48 chunks, 240 such threads).
+__global__ __launch_bounds__(256) void resize_patchify_kernel(const HzResizeParams p) {
+  __shared__ __attribute__((aligned(16))) u32x4 stage[256 * HZ_RSZ_UNITS];
+  constexpr int R = HZ_RSZ_ROWS;
+  const int t = threadIdx.x, b = blockIdx.y;
+  float v[R][3];
+  rsz_band(p, stage, v);  // ends on a barrier whenever it wrote `stage`
+  bf16_t* tile = reinterpret_cast<bf16_t*>(stage);
+  if (t < p.crop) {
+    const int px = t >> 4, kx = t & 15;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = (acc[r][c] * (1.0f / 255.0f) - p.mean[c]) * p.inv_std[c];
-    *reinterpret_cast<u32x4*>(p.out + (((long)b * p.crop + oy) * p.crop + t) * 8) = pack8(v);
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int r = 0; r < R; ++r) tile[((px * 3 + c) * R + r) * 16 + kx] = f2bf(v[r][c]);
+  }
+  __syncthreads();
+  const int n = p.crop >> 4, py = blockIdx.x >> 1, h = blockIdx.x & 1;
+  bf16_t* row0 = p.out + ((long)b * n + py) * n * 768 + h * 128;
+  for (int q = t; q < n * 48; q += 256) {
+    const int run = q >> 4, px = run / 3, c = run - px * 3;
+    *reinterpret_cast<u32x4*>(row0 + (long)px * 768 + c * 256 + (q & 15) * 8) = stage[q];
   }
 }
 
@@ -542,6 +587,21 @@ extern "C" int hz_resize_preprocess_launch(const HzResizeParams* pp, hipStream_t
   if (((uintptr_t)p.image & 15) || ((uintptr_t)p.out & 15) || ((uintptr_t)p.dims & 3)) return -1;
   const dim3 grid((p.crop + HZ_RSZ_ROWS - 1) / HZ_RSZ_ROWS, p.B);
   HZ_LAUNCH(resize_preprocess_kernel, grid, dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_resize_patchify_launch(const HzResizeParams* pp, hipStream_t st) {
+  const HzResizeParams& p = *pp;
+  if (p.B < 1 || p.crop < 16 || p.crop > 256 || p.crop % 16 || p.maxH < 1 || p.maxW < 1 || !p.image || !p.dims ||
+      !p.out)
+    return -1;
+  if (((long)p.maxW * 3 + 30) >> 4 > 256 * HZ_RSZ_UNITS) return -1;  // as above: a staged row fits the chunk
+  if (p.cap_bytes % 16 || (long long)p.maxH * p.maxW * 3 > p.cap_bytes) return -1;
+  if (((uintptr_t)p.image & 15) || ((uintptr_t)p.out & 15) || ((uintptr_t)p.dims & 3)) return -1;
+  static_assert(HZ_RSZ_ROWS == 8 && 3 * HZ_RSZ_ROWS * 256 * 2 <= 256 * HZ_RSZ_UNITS * 16,
+                "a band is half a patch row and its bf16 tile fits the staging buffer");
+  const dim3 grid(p.crop / HZ_RSZ_ROWS, p.B);
+  HZ_LAUNCH(resize_patchify_kernel, grid, dim3(256), 0, st, p);
   return (int)hipGetLastError();
 }
 

@@ -322,7 +322,8 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
     ``hipzap plan``); the plan is keyed to the checkpoint's identity (size, mtime, sampled hash).
     ``seq_len``: the captured sequence length of a text model (default: the adapter's, 128).
     ``resize``: ``(resize, crop, max_h, max_w)`` writes a RESIZE plan (``<ckpt>.rz.hzplan`` by default):
-    requests are uint8 images of any size up to the maximum (models/resnet.py build_graph).
+    requests are uint8 images of any size up to the maximum (ResNet and ViT; models/resnet.py and
+    models/vit.py build_graph). With ``embed`` on a ViT the default is ``<ckpt>.emb.rz.hzplan``.
     ``embed``: ``{"pooling": "mean" | "cls", "normalize": bool}`` writes an EMBEDDING plan of a BERT / ViT
     checkpoint (``<ckpt>.emb.hzplan`` by default): the output is one pooled vector per sequence / image."""
     from .packfile import source_stamp
@@ -337,11 +338,11 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
             raise ValueError(f"{model} has no sequence length to set")
         arch_kw["seq_len"] = int(seq_len)
     if resize is not None:
-        if not model.startswith("resnet"):
-            raise ValueError(f"resize plans cover the ResNet family, not {model}")
+        if not model.startswith(("resnet", "vit")):
+            raise ValueError(f"resize plans cover the ResNet and ViT families, not {model}")
         arch_kw["resize"] = [int(v) for v in resize]
         input_uint8 = False
-        path = path or plan_path(ckpt, "rz")
+        path = path or plan_path(ckpt, "emb.rz" if embed is not None else "rz")
     if embed is not None:
         if model.startswith("resnet"):
             raise ValueError(f"embedding plans cover the BERT and ViT encoders, not {model}")

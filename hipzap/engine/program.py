@@ -423,6 +423,15 @@ class ExecContext:
             prm = vision.resize_params(addr(n.inputs[0]), addr(n.inputs[1]), addr(n.outputs[0]), nb, crop,
                                        a["max_h"], a["max_w"], a.get("mean"), a.get("std"))
             N.prog_add(lib, self.prog, N.HZ_K_RESIZE_PREPROCESS, prm, n.slot, "add_resize_preprocess")
+        elif n.kind == "resize_patchify":  # the same request -> bf16 ViT patch rows (replaces patchify)
+            a = n.attrs
+            nb, crop = g.shape(n.inputs[0])[0], a["crop"]
+            assert a["patch"] == 16 and crop % 16 == 0 and g.shape(n.outputs[0]) == (
+                nb * (crop // 16) ** 2, 768) and g.shape(n.inputs[0]) == (
+                nb, vision.resize_cap_bytes(a["max_h"], a["max_w"])) and g.shape(n.inputs[1]) == (nb, 8)
+            prm = vision.resize_params(addr(n.inputs[0]), addr(n.inputs[1]), addr(n.outputs[0]), nb, crop,
+                                       a["max_h"], a["max_w"], a.get("mean"), a.get("std"))
+            N.prog_add(lib, self.prog, N.HZ_K_RESIZE_PATCHIFY, prm, n.slot, "add_resize_patchify")
         elif n.kind == "patchify":  # preprocess mode 2: fp32 NCHW -> bf16 patch rows (Cpad = patch)
             nb, cin, h, w = g.tensors[n.inputs[0]].shape
             mean = std = None

@@ -65,6 +65,14 @@ def run_graph_reference(g: Graph, params: dict, inputs: list, bf16_acts: bool = 
                 rows.append(resize_preprocess_reference(img, a.get("mean"), a.get("std"), a["resize"], a["crop"],
                                                         g.shape(n.outputs[0])[-1]))
             store(n.outputs[0], torch.stack(rows))
+        elif k == "resize_patchify":  # resize_preprocess per row -> NCHW -> the patchify rearrangement
+            from ..ops.vision import resize_patchify_reference
+            a = n.attrs
+            image, dims = vals[n.inputs[0]], vals[n.inputs[1]]
+            imgs = [image[b, : int(dims[b, 0]) * int(dims[b, 1]) * 3].reshape(int(dims[b, 0]), int(dims[b, 1]), 3)
+                    for b in range(image.shape[0])]
+            store(n.outputs[0], resize_patchify_reference(imgs, a.get("mean"), a.get("std"), a["resize"], a["crop"],
+                                                          a["patch"]))
         elif k == "patchify":
             x = vals[n.inputs[0]].float()
             if n.attrs.get("mean") is not None:

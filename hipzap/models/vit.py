@@ -115,8 +115,14 @@ def pack_vit(sd: dict, device="cpu", eps: float = 1e-12, weights: str = "bf16",
 def build_graph(batch: int, layers: int = 12, hidden: int = 768, heads: int = 12, ffn: int = 3072,
                 patch: int = 16, image: int = 224, num_labels: int | None = 1000, weights: str = "bf16",
                 patch_lowering: str | None = None, head: str = "cls", pooling: str = "cls",
-                normalize: bool = True, **_) -> Graph:
-    """``head="embed"``: no classifier; the output is one fp32 vector ``[B, hidden]`` per image, pooled
+                normalize: bool = True, resize=None, **_) -> Graph:
+    """``resize``: None, or ``(resize, crop, max_h, max_w)`` for a RESIZE graph, as ``models/resnet.py``
+    builds one: the inputs are ``image`` [batch, cap_bytes] uint8 (an image of any size up to max_h x
+    max_w packed at its row's start) and ``dims`` [batch, 8] int32, and the first node resizes, crops,
+    normalises (the ImageNet constants, what the serving route applies to every uint8 image) and writes
+    the patch rows in one launch (csrc/vision.hip resize_patchify_kernel) in place of ``patchify``.
+
+    ``head="embed"``: no classifier; the output is one fp32 vector ``[B, hidden]`` per image, pooled
     from the final LayerNorm's output -- ``pooling`` "cls" (the CLS token; the LayerNorm runs on the B
     CLS rows only) or "mean" (the patch tokens' mean, CLS skipped; the LayerNorm runs on every row) --
     L2-normalised with ``normalize`` (csrc/transformer.hip pool_embed_kernel). ``head="cls"`` needs the
@@ -127,17 +133,40 @@ def build_graph(batch: int, layers: int = 12, hidden: int = 768, heads: int = 12
     npch = n_side * n_side
     T = npch + 1
     g = Graph(f"vit_bs{B}")
-    x_in = g.tensor((B, 3, image, image), torch.float32, "input", external=True)
-    g.inputs.append(x_in)
+    lowering = patch_lowering or _patch_lowering(patch, image)
+    rz_meta = {}
+    if resize is not None:
+        from ..imgeom import resize_cap_bytes
+        from ..ops.vision import IMAGENET_MEAN, IMAGENET_STD
+        rs, crop, max_h, max_w = (int(v) for v in resize)
+        if crop != image:
+            raise ValueError(f"resize plan crops {crop}, the model takes {image}")
+        if lowering == "conv":
+            raise ValueError("resize plans need the GEMM patch lowering (16 x 16 patches), not the conv lowering")
+        if crop % 16:
+            raise ValueError(f"resize plan crop {crop} is not a multiple of the 16-pixel patch")
+        if crop > 256:
+            raise ValueError(f"resize plans cover crops up to 256; ViT-384 (crop {crop}) is not covered")
+        x_in = g.tensor((B, resize_cap_bytes(max_h, max_w)), torch.uint8, "image", external=True)
+        dims = g.tensor((B, 8), torch.int32, "dims", external=True)
+        g.inputs += [x_in, dims]
+        rz_meta = {"resize": {"resize": rs, "crop": crop, "max_h": max_h, "max_w": max_w}}
+    else:
+        x_in = g.tensor((B, 3, image, image), torch.float32, "input", external=True)
+        g.inputs.append(x_in)
     tb = TxBuilder(g)
-    if (patch_lowering or _patch_lowering(patch, image)) == "conv":  # any patch size; the A/B lowering
+    if lowering == "conv":  # any patch size; the A/B lowering
         nhwc = g.tensor((B, image, image, 8), name="nhwc")
         g.add("preprocess", [x_in], [nhwc], mean=None, std=None)
         patches = g.tensor((B * npch, D), torch.bfloat16, "patches")
         g.add("conv", [nhwc], [patches], w="patch", act="none", rowmajor=True, name="patch_embed")
     else:
         prow = g.tensor((B * npch, 3 * patch * patch), torch.bfloat16, "patch_rows")
-        g.add("patchify", [x_in], [prow], patch=patch, mean=None, std=None)
+        if resize is not None:
+            g.add("resize_patchify", [x_in, dims], [prow], mean=IMAGENET_MEAN, std=IMAGENET_STD, resize=rs,
+                  crop=crop, max_h=max_h, max_w=max_w, patch=patch)
+        else:
+            g.add("patchify", [x_in], [prow], patch=patch, mean=None, std=None)
         patches = tb.gemm(prow, "patch", D, name="patch_embed")
     tok = g.tensor((B * T, D), torch.bfloat16, "tokens")
     g.add("vit_tokens", [patches], [tok], cls="cls_token", pos="pos", B=B, np=npch)
@@ -166,11 +195,11 @@ def build_graph(batch: int, layers: int = 12, hidden: int = 768, heads: int = 12
             e = tb.pool_embed(tb.layernorm(x, "final_ln", name="final_ln"), B, T, mode="mean", first=1,
                               normalize=normalize)
         g.outputs.append(e)
-        g.meta = {"head": "embed", "pooling": pooling, "normalize": bool(normalize), "dim": D}
+        g.meta = {"head": "embed", "pooling": pooling, "normalize": bool(normalize), "dim": D, **rz_meta}
         return g
     cls = tb.layernorm(x, "final_ln", rows=B, ldx=T * D, name="cls_ln")
     npad = (num_labels + 3) // 4 * 4
     logits = tb.linear(cls, "head", npad, fp8=f8, out_f32=True, ext=True)
     g.outputs.append(logits)
-    g.meta = {"num_labels": num_labels}
+    g.meta = {"num_labels": num_labels, **rz_meta}
     return g

@@ -31,6 +31,7 @@ class PreprocessArgs(C.Structure):
                 ("mode", C.c_int)]
 
 
+@N.params_of("HZ_K_RESIZE_PATCHIFY")  # the same block; ``out`` is then the ViT patch rows
 @N.params_of("HZ_K_RESIZE_PREPROCESS")
 class ResizeParams(C.Structure):
     _fields_ = [("image", C.c_void_p), ("dims", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("crop", C.c_int),
@@ -106,6 +107,34 @@ def resize_preprocess(image: torch.Tensor, dims: torch.Tensor, crop: int, max_h:
     prm = resize_params(image.data_ptr(), dims.data_ptr(), out.data_ptr(), b, crop, max_h, max_w, mean, std)
     N.check(N.lib().hz_launch_kernel(N.HZ_K_RESIZE_PREPROCESS, C.byref(prm), N.stream_ptr()), "resize_preprocess")
     return out
+
+
+def resize_patchify(image: torch.Tensor, dims: torch.Tensor, crop: int, max_h: int, max_w: int, mean=None,
+                    std=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Eager launch of the resize + patchify kernel: the inputs of ``resize_preprocess`` -> bf16 ViT patch
+    rows [B * (crop/16)^2, 768], columns in (c, ky, kx) order (``patchify``'s layout). ``out``: a
+    contiguous bf16 tensor of that many elements to write into (default: a fresh one)."""
+    b = image.shape[0]
+    assert image.dtype == torch.uint8 and image.shape == (b, resize_cap_bytes(max_h, max_w)), tuple(image.shape)
+    assert dims.dtype == torch.int32 and dims.shape == (b, 8) and image.is_contiguous() and dims.is_contiguous()
+    dev = image.device if image.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    rows = b * (crop // 16) ** 2
+    if out is None:
+        out = torch.empty(rows, 768, device=dev, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == rows * 768 and out.is_cuda
+    prm = resize_params(image.data_ptr(), dims.data_ptr(), out.data_ptr(), b, crop, max_h, max_w, mean, std)
+    N.check(N.lib().hz_launch_kernel(N.HZ_K_RESIZE_PATCHIFY, C.byref(prm), N.stream_ptr()), "resize_patchify")
+    return out
+
+
+def resize_patchify_reference(images, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize: int = 256, crop: int = 224,
+                              patch: int = 16) -> torch.Tensor:
+    """fp32 oracle of ``resize_patchify``: uint8 [H, W, 3] images -> float32 [B * (crop/patch)^2,
+    3 * patch * patch]: ``resize_preprocess_reference`` per image, then the patchify rearrangement."""
+    x = torch.stack([resize_preprocess_reference(im, mean, std, resize, crop, cpad=3) for im in images])
+    b, n = x.shape[0], crop // patch
+    x = x.permute(0, 3, 1, 2).reshape(b, 3, n, patch, n, patch).permute(0, 2, 4, 1, 3, 5)
+    return x.reshape(b * n * n, 3 * patch * patch).contiguous()
 
 
 def maxpool_nhwc(x: torch.Tensor, k=3, stride=2, pad=1) -> torch.Tensor:

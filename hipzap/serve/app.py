@@ -370,6 +370,9 @@ def embed():
             with phase("infer"):
                 vec = backend.embed_u8(arr)
         else:
+            prz = getattr(backend, "resize", None)  # a resize plan refused the image: above its maximum
+            if prz is not None and arr.dtype == np.uint8 and arr.ndim == 4:
+                check_image_size(arr, (prz["resize"], prz["crop"], prz["max_h"], prz["max_w"]))
             with phase("preprocess"):
                 x = to_model_input(arr, s.resize_spec(model))
             with phase("infer"):

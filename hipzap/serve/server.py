@@ -420,8 +420,9 @@ class ModelServer:
         from ..engine.packfile import same_source
         ckpt = self.store.fetch(spec.key)
         # "resize" in the model's settings block: the resize plan (`hipzap plan --resize`, <ckpt>.rz.hzplan)
-        # "embed": the embedding plan (`hipzap plan --embed`, <ckpt>.emb.hzplan)
-        suffix = ".emb.hzplan" if spec.extra.get("embed") else ".rz.hzplan" if spec.extra.get("resize") else ".hzplan"
+        # "embed": the embedding plan (`hipzap plan --embed`, <ckpt>.emb.hzplan); both: <ckpt>.emb.rz.hzplan
+        emb, rz = bool(spec.extra.get("embed")), bool(spec.extra.get("resize"))
+        suffix = ".emb.rz.hzplan" if emb and rz else ".emb.hzplan" if emb else ".rz.hzplan" if rz else ".hzplan"
         path = ckpt + suffix
         fetched = False
         if not os.path.exists(path):
@@ -526,6 +527,19 @@ def gpu_visible() -> bool:
         return False
 
 
+PLAN_SUFFIXES = (".emb.rz.hzplan", ".rz.hzplan", ".emb.hzplan", ".hzplan")  # longest match first
+
+
+def plan_checkpoint(plan: str) -> str:
+    """The checkpoint path a plan image's default name was derived from: ``m.pth.emb.rz.hzplan``,
+    ``m.pth.rz.hzplan``, ``m.pth.emb.hzplan`` and ``m.pth.hzplan`` -> ``m.pth`` (the longest matching
+    suffix is stripped; a path without one is returned as it is)."""
+    for sfx in PLAN_SUFFIXES:
+        if plan.endswith(sfx):
+            return plan[: -len(sfx)]
+    return plan
+
+
 class PlanVisionBackend:
     """Torch-free vision serving from a plan image (``hipzap plan``; hipzap/lite.py): a request
     is a uint8 HWC image (the decoded-JPEG format) copied into a pinned input and one hipGraph
@@ -617,8 +631,7 @@ class PlanVisionBackend:
     def _torch_backend(self):
         with self._torch_lock:
             if self._torch is None:
-                sfx = [f for f in (".rz.hzplan", ".emb.hzplan") if self.plan.endswith(f)]
-                ckpt = self.plan[: -len(sfx[0] if sfx else ".hzplan")]
+                ckpt = plan_checkpoint(self.plan)
                 if not os.path.exists(ckpt):
                     raise ValueError(f"{self.name} is served from a plan image: send uint8 HWC images "
                                      f"{list(self.in_shape[1:])} (image_b64 or a uint8 .npy)")
