@@ -349,6 +349,10 @@ def match_xseam(g, params, i: int, seams: dict) -> Fused | None:
     nb, h, w, _ = g.shape(y)
     if h % 2 or w % 2 or h * w > 196:  # the stride-2 K-split consumer stages (h+2)(w+2) <= 256 pixels
         return None
+    # conv1's sum is fp32 for that K-split consumer alone: at an image size where the stride-2 3x3 has
+    # no launchable K-split geometry (match_kconvs leaves it per conv) the boundary binds per conv too
+    if (h + 2) * (w + 2) > 256 or not kconv_launchable(h, w, 512, 2):
+        return None
     return Fused("seam", i, i + 3, [c3, c1], init=i - 1, consumer=i + 3)
 
 

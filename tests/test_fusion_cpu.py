@@ -365,6 +365,36 @@ def test_kconv_and_tail_only_bind_geometries_the_launchers_accept(r50, image):
                        params[f.nodes[0].attrs["w"]].stride == 1 for f in fz.values())
 
 
+@pytest.mark.parametrize("image,batch", [(112, 1), (128, 1), (160, 1), (160, 2), (192, 1), (224, 1), (256, 1),
+                                         (288, 1)])
+@pytest.mark.parametrize("spec", [None, "all"])
+def test_the_plan_is_what_a_context_binds_at_every_image_size(r50, image, batch, spec, monkeypatch):
+    """A cross-stage seam (layer3's last conv3 + layer4's first conv1, three nodes) is planned only with
+    its K-split stride-2 consumer: at 128 and 160 px layer4's 3x3 has no launchable K-split geometry
+    (8 x 8 -> 4 x 4, 10 x 10 -> 5 x 5: one 32-pixel group), and the planner used to plan the seam
+    anyway and leave the context to drop it. Now ``fusion.plan`` and the bound context agree at every
+    size (bound against the plan recorder: no GPU)."""
+    from hipzap.engine.plan import PlanRecorder
+    from hipzap.engine.program import ExecContext
+    from hipzap.models.resnet import build_graph
+    monkeypatch.delenv("HIPZAP_FUSE", raising=False)
+    a, params, kw = r50
+    g = build_graph("resnet50", batch, 1000, image, True)
+    fz = fusion.plan(g, params, fusion.enabled_kinds(spec))
+    for f in fz.values():
+        if f.kind == "seam" and f.end - f.start == 3:
+            assert fz.get(f.consumer) is not None and fz[f.consumer].kind == "kconv", image
+        if f.ds is not None:  # a launch computes a downsample only for the run that skipped its node
+            assert f.ds_from in fz
+    # (12 x 12 -> 6 x 6 and 14 x 14 -> 7 x 7 are two 32-pixel groups: launchable)
+    assert any(f.kind == "seam" and f.end - f.start == 3 for f in fz.values()) == (spec is None and image in (192, 224))
+    ctx = ExecContext(g, params, torch.device("cpu"), lib=PlanRecorder(), fuse=spec)
+    assert sorted((i, f.kind) for i, f in ctx.fused.items()) == sorted((i, f.kind) for i, f in fz.items())
+    if image % 32 == 0:
+        kinds = [f.kind for f in fz.values()]
+        assert kinds[0] in ("stem", "convpool") and kinds.count("bneck") == 3 and kinds.count("bneck2") == 4
+
+
 def test_kconv_launchable_mirrors_the_launcher_refusals():
     """Every geometry the host predicate rejects is refused by hz_kconv_launch before any HIP call
     (so the predicate is never looser than the launcher's own checks)."""
