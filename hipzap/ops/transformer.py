@@ -129,11 +129,12 @@ def softmax(x: torch.Tensor, cols: int | None = None, scale: float = 1.0, mask: 
     return out
 
 
-def softmax_ref(x: torch.Tensor, cols: int | None = None, scale: float = 1.0, mask=None) -> torch.Tensor:
+def softmax_ref(x: torch.Tensor, cols: int | None = None, scale: float = 1.0, mask=None,
+                dtype=torch.float32) -> torch.Tensor:
     D = cols or x.shape[-1]
-    v = x[..., :D].float() * scale
+    v = x[..., :D].to(dtype) * scale
     if mask is not None:
-        v = v + mask.float()
+        v = v + mask.to(dtype)
     return torch.softmax(v, dim=-1)
 
 
