@@ -7,7 +7,9 @@
     python -m hipzap plan --model bert-base --ckpt bert.pth --embed [--pooling mean|cls] [--no-normalize]  # vectors
     python -m hipzap tune --model resnet50 --batch 1 --concurrent 1 8
     python -m hipzap upload --models-dir ./models  # scripts/upload_models.py parity
-    python -m hipzap info
+    python -m hipzap index --vectors v.npy [--labels labels.json] [--metric cosine|ip] --out x.hzidx  # vector index
+    python -m hipzap index --embed-plan bert.pth.emb.hzplan --ids ids.npy [--mask mask.npy] --out x.hzidx
+    python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
 
@@ -100,7 +102,41 @@ def cmd_upload(a):
     print(json.dumps({"bucket": bucket, "copied": copied}))
 
 
+def cmd_index(a):
+    """Write a .hzidx vector index (hipzap/search.py) from ready vectors, or from the vectors an embedding
+    plan gives for rows of token ids (on the GPU, torch-free)."""
+    import numpy as np
+
+    from .search import write_index
+    if (a.vectors is None) == (a.embed_plan is None):
+        raise SystemExit("index: give one of --vectors and --embed-plan")
+    embed, model = None, a.model
+    if a.vectors is not None:
+        if a.ids or a.mask:
+            raise SystemExit("index: --ids / --mask go with --embed-plan")
+        vec = np.load(a.vectors, allow_pickle=False)
+    else:
+        if not a.ids:
+            raise SystemExit("index: --embed-plan needs --ids (an .npy of token-id rows)")
+        from .serve.server import PlanTextBackend
+        from .serve.settings import ModelSpec
+        ids = np.load(a.ids, allow_pickle=False)
+        mask = np.load(a.mask, allow_pickle=False) if a.mask else None
+        be = PlanTextBackend(a.model or "bert-base", a.embed_plan, a.device, ModelSpec(name=a.model or "bert-base"))
+        if be.embed is None:
+            raise SystemExit(f"index: {a.embed_plan} is not an embedding plan (hipzap plan --embed)")
+        vec, embed = be.embed_np(ids, None, mask), dict(be.embed)
+        model = model or be.meta.get("model")
+    labels = json.load(open(a.labels)) if a.labels else None
+    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed)
+    print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
+
+
 def cmd_info(a):
+    if a.path:  # a .hzidx file: its header
+        from .search import read_header
+        print(json.dumps({"path": a.path, **read_header(a.path)}, indent=1))
+        return
     import torch
 
     from . import __version__, _native
@@ -162,12 +198,24 @@ def main(argv=None):
     u.add_argument("--bucket", default=None)
     u.add_argument("--stage", default=None)
     u.add_argument("--settings", default=None)
-    sub.add_parser("info")
+    ix = sub.add_parser("index")
+    ix.add_argument("--vectors", default=None, help="an .npy float array [N, D]")
+    ix.add_argument("--embed-plan", default=None, help="a text embedding plan: the vectors of the --ids rows, on the GPU")
+    ix.add_argument("--ids", default=None, help="with --embed-plan: an .npy of token-id rows [N, L]")
+    ix.add_argument("--mask", default=None, help="with --embed-plan: an .npy attention mask [N, L]")
+    ix.add_argument("--labels", default=None, help="a JSON list of N strings")
+    ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")
+    ix.add_argument("--model", default=None, help="free text kept in the header")
+    ix.add_argument("--device", type=int, default=0)
+    ix.add_argument("--out", required=True)
+    inf = sub.add_parser("info")
+    inf.add_argument("path", nargs="?", default=None, help="a .hzidx file: print its header")
     sub.add_parser("bench", add_help=False)
     args, rest = ap.parse_known_args(argv)
     if args.cmd == "bench":
         return cmd_bench(args, rest)
-    {"serve": cmd_serve, "pack": cmd_pack, "plan": cmd_plan, "tune": cmd_tune, "upload": cmd_upload, "info": cmd_info}[args.cmd](args)
+    {"serve": cmd_serve, "pack": cmd_pack, "plan": cmd_plan, "tune": cmd_tune, "upload": cmd_upload, "info": cmd_info,
+     "index": cmd_index}[args.cmd](args)
 
 
 if __name__ == "__main__":

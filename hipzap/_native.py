@@ -19,7 +19,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.realpath(__file__)), "_lib",
                          "libhipzap_debug.so" if DEBUG else "libhipzap.so")
 if os.environ.get("HIPZAP_LIB"):  # same-box A/B of two builds (scripts/ab_lib.sh)
     _LIB_PATH = os.path.realpath(os.environ["HIPZAP_LIB"])
-DEBUG_UNITS = ("conv", "gemm", "vision", "transformer", "lstm", "lmbatch", "pack", "block")
+DEBUG_UNITS = ("conv", "gemm", "vision", "transformer", "lstm", "lmbatch", "pack", "block", "search")
 _lock = threading.Lock()
 _lib = None
 
@@ -35,7 +35,7 @@ KINDS = {
     "HZ_K_LMB_ADMIT": 16, "HZ_K_STEM": 18, "HZ_K_BNECK": 19, "HZ_K_SEAM": 20, "HZ_K_KCONV": 21,
     "HZ_K_QKVATT": 22, "HZ_K_CONV2": 23, "HZ_K_AVGPOOL": 24, "HZ_K_PREPROCESS": 25, "HZ_K_STEP_BUMP": 26,
     "HZ_K_DIAG": 27, "HZ_K_RESIZE_PREPROCESS": 28, "HZ_K_POOL_EMBED": 29,
-    "HZ_K_RESIZE_PATCHIFY": 30,
+    "HZ_K_RESIZE_PATCHIFY": 30, "HZ_K_SEARCH_SCAN": 31, "HZ_K_SEARCH_MERGE": 32,
 }
 globals().update(KINDS)
 KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct

@@ -428,6 +428,56 @@ typedef struct HzPoolEmbedParams {
 } HzPoolEmbedParams;
 int hz_pool_embed_launch(const HzPoolEmbedParams* p, hipStream_t st);
 
+// ---- vector search (csrc/search.hip, csrc/index.cpp): exact top-k by inner product ----
+// scan: one workgroup per tile of HZ_SEARCH_TILE corpus rows scores every row of its tile against all Q
+// queries (fp32 FMAs over the fp32 query and the bf16 row widened to fp32) and writes the tile's best
+// min(k, rows in tile) candidates per query, best first, as 64-bit keys; unused slots hold key 0.
+// merge: one workgroup per query reduces its ntile x k keys to the final k, best first.
+// Order (total): higher score first, then the lower row id. key = (orderable(score) << 32) | ~id with
+// -0.0 canonicalised to +0.0; key 0 is below every real key and decodes to id -1, score -inf.
+// The bits of score(q, r) depend on the D values of the query and of the row only.
+#define HZ_SEARCH_TILE 256
+#define HZ_SEARCH_MAX_Q 16
+#define HZ_SEARCH_MAX_K 128
+typedef struct HzSearchParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows (ldc % 8 == 0), ldc >= D
+  const float* queries;          // fp32 [Q][D], 16-B aligned
+  unsigned long long* cand;      // scratch [ntile][Q][k] keys, at least hz_search_scratch_bytes(N, Q, k)
+  float* out_score;              // fp32 [Q][k]
+  int* out_id;                   // int32 [Q][k]
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launchers: ceil(N / HZ_SEARCH_TILE)
+  unsigned long long cand_bytes; // bytes of `cand`
+} HzSearchParams;
+int hz_search_tile_rows(void);   // HZ_SEARCH_TILE
+// bytes of candidate scratch a search of (N, Q, k) needs; 0 for a refused shape
+unsigned long long hz_search_scratch_bytes(long long N, int Q, int k);
+// 0, or a negative code for a refused parameter block (nothing is launched then)
+int hz_search_scan_launch(const HzSearchParams* p, hipStream_t st);
+int hz_search_merge_launch(const HzSearchParams* p, hipStream_t st);
+int hz_search_code_warm(void);
+
+// an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
+// (stream, pinned query slot, device query buffer, candidate scratch, device and pinned result buffers).
+// A context's program (H2D copy, scan, merge, two D2H copies) is captured per (Q, k) on first use.
+// .hzidx: HzIndexHeader, the JSON header (json_len bytes), zero padding, the rows at data_off (4096-aligned)
+#define HZ_INDEX_MAGIC "HZIDX\0\0\1"
+enum { HZ_INDEX_COSINE = 0, HZ_INDEX_IP = 1 };
+typedef struct HzIndexHeader {
+  char magic[8];
+  uint32_t version, json_len;
+  uint64_t data_off, count;
+  uint32_t dim, metric;
+} HzIndexHeader;
+const char* hz_index_last_error(void);
+void* hz_index_open(const char* path, int device, int nctx);  // nctx <= 0: 2
+// out[8] = {count, dim, metric, contexts, tile rows, captured programs, device bytes, 0}
+int hz_index_describe(void* idx, uint64_t* out);
+// queries fp32 [Q][dim] -> out_score [Q][k], out_id [Q][k]; blocks until the results are in host memory.
+// One search at a time per context (a second caller of the same context waits).
+int hz_index_search(void* idx, int ctx, const float* queries, int Q, int k, float* out_score, int* out_id);
+void hz_index_close(void* idx);
+
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
   const void* x;       // [rows][ldx] fp32 (x_bf16 = 0) or bf16
@@ -566,7 +616,8 @@ typedef struct HzDiagArgs {  // hz_diag_launch (csrc/diag.hip)
 } HzDiagArgs;
 // translation units holding device code (hz_plan_open warms the ones a plan's kernels live in)
 enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORMER = 8, HZ_UNIT_FP8 = 16,
-       HZ_UNIT_PACK = 32, HZ_UNIT_BLOCK = 64, HZ_UNIT_LSTM = 128, HZ_UNIT_LMBATCH = 256, HZ_UNIT_DIAG = 512 };
+       HZ_UNIT_PACK = 32, HZ_UNIT_BLOCK = 64, HZ_UNIT_LSTM = 128, HZ_UNIT_LMBATCH = 256, HZ_UNIT_DIAG = 512,
+       HZ_UNIT_SEARCH = 1024 };
 // X(NAME, value, parameter struct, launcher, code unit): the ONE list of kinds. A launcher is
 // `int f(const Params*, hipStream_t)`; the *_op launchers are the adapters in runtime.cpp that unpack
 // an argument record. hz_launch_kernel, hz_kernel_param_size, hz_kernel_name, hz_kernel_code_unit and
@@ -602,7 +653,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(DIAG, 27, HzDiagArgs, hz_diag_op, DIAG)                               \
   X(RESIZE_PREPROCESS, 28, HzResizeParams, hz_resize_preprocess_op, VISION) \
   X(POOL_EMBED, 29, HzPoolEmbedParams, hz_pool_embed_op, TRANSFORMER)     \
-  X(RESIZE_PATCHIFY, 30, HzResizeParams, hz_resize_patchify_op, VISION)
+  X(RESIZE_PATCHIFY, 30, HzResizeParams, hz_resize_patchify_op, VISION)   \
+  X(SEARCH_SCAN, 31, HzSearchParams, hz_search_scan_op, SEARCH)           \
+  X(SEARCH_MERGE, 32, HzSearchParams, hz_search_merge_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

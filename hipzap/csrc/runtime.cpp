@@ -426,6 +426,15 @@ extern "C" __attribute__((weak)) int hz_pool_embed_launch(const HzPoolEmbedParam
 static int hz_pool_embed_op(const HzPoolEmbedParams* p, hipStream_t st) {
   return hz_pool_embed_launch ? hz_pool_embed_launch(p, st) : -102;
 }
+// (the search launchers: search.hip in the library)
+extern "C" __attribute__((weak)) int hz_search_scan_launch(const HzSearchParams* p, hipStream_t st);
+static int hz_search_scan_op(const HzSearchParams* p, hipStream_t st) {
+  return hz_search_scan_launch ? hz_search_scan_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_merge_launch(const HzSearchParams* p, hipStream_t st);
+static int hz_search_merge_op(const HzSearchParams* p, hipStream_t st) {
+  return hz_search_merge_launch ? hz_search_merge_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

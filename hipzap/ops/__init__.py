@@ -1,0 +1,1 @@
+from . import search  # noqa: F401  (registers the search kinds' parameter struct beside the others)

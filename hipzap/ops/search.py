@@ -1,0 +1,57 @@
+"""Vector search kernels (csrc/search.hip): exact top-k by inner product over a bf16 corpus.
+
+``HzSearchParams`` is the parameter block of both kinds: ``HZ_K_SEARCH_SCAN`` (one workgroup per tile
+of ``tile_rows()`` corpus rows, all queries of the launch resident in LDS, the tile's best ``k`` keys per
+query into ``cand``) and ``HZ_K_SEARCH_MERGE`` (one workgroup per query, ``ntile x k`` keys -> the final
+``k``). torch-free: indexes (:mod:`hipzap.search`) are served without it."""
+from __future__ import annotations
+
+import ctypes as C
+
+from .. import _native as N
+
+MAX_Q, MAX_K = 16, 128  # HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K (csrc/hipzap.h)
+
+
+@N.params_of("HZ_K_SEARCH_MERGE")
+@N.params_of("HZ_K_SEARCH_SCAN")
+class SearchParams(C.Structure):
+    _fields_ = [("corpus", C.c_void_p), ("queries", C.c_void_p), ("cand", C.c_void_p), ("out_score", C.c_void_p),
+                ("out_id", C.c_void_p), ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("k", C.c_int),
+                ("ldc", C.c_int), ("ntile", C.c_int), ("cand_bytes", C.c_uint64)]
+
+
+def _sigs(lib):
+    P, U64 = C.c_void_p, C.c_uint64
+    N._sig(lib, "hz_search_tile_rows", C.c_int)
+    N._sig(lib, "hz_search_scratch_bytes", U64, C.c_longlong, C.c_int, C.c_int)
+    N._sig(lib, "hz_search_scan_launch", C.c_int, C.POINTER(SearchParams), P)
+    N._sig(lib, "hz_search_merge_launch", C.c_int, C.POINTER(SearchParams), P)
+    N._sig(lib, "hz_search_code_warm", C.c_int)
+    N._sig(lib, "hz_index_last_error", C.c_char_p)
+    N._sig(lib, "hz_index_open", P, C.c_char_p, C.c_int, C.c_int)
+    N._sig(lib, "hz_index_describe", C.c_int, P, C.POINTER(U64))
+    N._sig(lib, "hz_index_search", C.c_int, P, C.c_int, P, C.c_int, C.c_int, P, P)
+    N._sig(lib, "hz_index_close", None, P)
+
+
+N._EXTRA_SIGS.append(_sigs)
+if N._lib is not None:  # the library was loaded before this module
+    _sigs(N._lib)
+
+
+def tile_rows() -> int:
+    """Corpus rows per scan workgroup (a tile)."""
+    return int(N.lib().hz_search_tile_rows())
+
+
+def scratch_bytes(n: int, q: int, k: int) -> int:
+    """Bytes of candidate scratch a search of (N, Q, k) needs; 0 for a refused shape."""
+    return int(N.lib().hz_search_scratch_bytes(int(n), int(q), int(k)))
+
+
+def launch(prm: SearchParams, stream: int = 0) -> tuple:
+    """Scan then merge on ``stream``: (scan code, merge code); the merge is not launched after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_scan_launch(C.byref(prm), stream)
+    return rc, (lib.hz_search_merge_launch(C.byref(prm), stream) if rc == 0 else None)

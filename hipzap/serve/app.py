@@ -8,6 +8,9 @@ Routes (reference: /root/reference/main.py:17-18, 105-112):
   POST /embed       one pooled vector per text / image from a BERT or ViT encoder served with
                     ``extra.embed`` -> {"model", "dim", "pooling", "normalized", "embeddings", ...}, or a
                     float32 ``.npy`` [n, dim] with ``Accept: application/octet-stream``
+  POST /search      nearest rows of the model's vector index (``extra.index``, a ``.hzidx`` file) for the
+                    bodies of /embed or ready ``vectors`` -> {"model", "metric", "k", "count", "results", ...},
+                    or a structured ``.npy`` [Q, k] (id, score) with ``Accept: application/octet-stream``
   GET  /health      liveness + loaded models;  GET /metrics  Prometheus text;  GET /  info
 torch is imported lazily: a plan-backed vision model (server.PlanVisionBackend) serves uint8
 images end to end without it (decode -> pinned input -> hipGraph -> top-5 in numpy).
@@ -127,7 +130,7 @@ def _error(e):
 def index():
     s = get_server()
     return _json({"service": "hipzap", "version": __version__, "backend": s.backend,
-                  "routes": ["GET /inference", "POST /predict", "POST /embed", "GET /health", "GET /metrics"]})
+                  "routes": ["GET /inference", "POST /predict", "POST /embed", "POST /search", "GET /health", "GET /metrics"]})
 
 
 @app.route("/inference", methods=["GET"])
@@ -335,11 +338,9 @@ def _need_embed(backend, model):
     return backend.embed
 
 
-@app.route("/embed", methods=["POST"])
-def embed():
-    """One pooled vector per sequence (``input_ids`` [+ ``attention_mask``, ``token_type_ids``]) or
-    per image (the bodies of /predict) from a model whose settings block has ``extra.embed``."""
-    s = get_server()
+def _embed_vectors(s, limit: bool = False):
+    """The request's inputs embedded by the model's backend -> (model, backend, embed spec, vectors, n, t0).
+    ``limit``: refuse more inputs than the backend's batch (POST /search: one replay per request)."""
     body = {}
     if request.mimetype != "application/octet-stream" and request.mimetype not in IMAGE_TYPES:
         body = request.get_json(force=True, silent=True) or {}
@@ -349,6 +350,7 @@ def embed():
         with phase("load"):
             backend = s.text(model)
         e = _need_embed(backend, model)
+        _check_inputs(limit, int(ids.shape[0]), backend)
         t0 = time.perf_counter()
         with phase("infer"):
             if hasattr(backend, "embed_np"):  # plan-backed: torch-free
@@ -365,6 +367,7 @@ def embed():
         with phase("load"):
             backend = s.vision(model)
         e = _need_embed(backend, model)
+        _check_inputs(limit, int(arr.shape[0]), backend)
         t0 = time.perf_counter()
         if arr.dtype == np.uint8 and hasattr(backend, "embed_u8") and backend.accepts_u8(arr.shape):
             with phase("infer"):
@@ -378,6 +381,19 @@ def embed():
             with phase("infer"):
                 vec = backend.embed_x(x).float().numpy()
         n = int(arr.shape[0])
+    return model, backend, e, vec, n, t0
+
+
+def _check_inputs(limit: bool, n: int, backend) -> None:
+    if limit and n > int(getattr(backend, "batch", 1)):
+        raise ValueError(f"{n} inputs exceed the batch of {backend.batch} this model is served with")
+
+
+@app.route("/embed", methods=["POST"])
+def embed():
+    """One pooled vector per sequence (``input_ids`` [+ ``attention_mask``, ``token_type_ids``]) or
+    per image (the bodies of /predict) from a model whose settings block has ``extra.embed``."""
+    model, backend, e, vec, n, t0 = _embed_vectors(get_server())
     dt = (time.perf_counter() - t0) * 1e3
     vec = np.ascontiguousarray(vec, np.float32)
     if "application/octet-stream" in request.headers.get("Accept", ""):
@@ -387,6 +403,66 @@ def embed():
     return _json({"model": model, "backend": backend.backend, "batch": n, "dim": int(vec.shape[1]),
                   "pooling": e["pooling"], "normalized": bool(e["normalize"]),
                   "embeddings": [[float(v) for v in row] for row in vec], "timing_ms": round(dt, 3)})
+
+
+def _embedding_backend(s, model):
+    """The backend of an embedding model named in a ``vectors`` request (text or vision)."""
+    name = s.spec(model).name
+    with phase("load"):
+        backend = s.vision(model) if name.startswith(("vit", "resnet")) else s.text(model)
+    return backend
+
+
+@app.route("/search", methods=["POST"])
+def search():
+    """The ``k`` nearest rows of the model's vector index (``extra.index``) per query. The queries are the
+    vectors /embed gives for the same body, or ``{"model", "vectors": [[...]]}``; a cosine index gets them
+    L2-normalised in fp32. ``"k"`` (JSON field or query argument): 1..128, default 10."""
+    from ..search import check_k, check_queries, normalize_rows
+    s = get_server()
+    body = {}
+    if request.mimetype != "application/octet-stream" and request.mimetype not in IMAGE_TYPES:
+        body = request.get_json(force=True, silent=True) or {}
+    k = body.get("k", request.args.get("k", 10))
+    if isinstance(k, str) and k.lstrip("-").isdigit():
+        k = int(k)
+    k = check_k(k)
+    if "vectors" in body:
+        model = body.get("model") or request.args.get("model") or "bert-base"
+        backend = _embedding_backend(s, model)
+        e = _need_embed(backend, model)
+        index = s.index(model, backend)
+        t0 = time.perf_counter()
+        try:
+            q = np.asarray(body["vectors"], dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("vectors must be a list of equally long lists of numbers") from None
+        q = check_queries(q, index.dim)
+    else:
+        model, backend, e, vec, _, t0 = _embed_vectors(s, limit=True)
+        index = s.index(model, backend)
+        q = check_queries(vec, index.dim)
+    if index.metric == "cosine":
+        q = normalize_rows(q)
+    with phase("search"):
+        scores, ids = index.search(q, k)
+    dt = (time.perf_counter() - t0) * 1e3
+    if "application/octet-stream" in request.headers.get("Accept", ""):
+        out = np.empty(ids.shape, dtype=[("id", "<i4"), ("score", "<f4")])
+        out["id"], out["score"] = ids, scores
+        buf = io.BytesIO()
+        np.save(buf, out, allow_pickle=False)
+        return Response(response=buf.getvalue(), status=200, mimetype="application/octet-stream")
+    labels = index.labels
+
+    def hit(i, sc):
+        h = {"id": int(i), "score": float(sc) if np.isfinite(sc) else None}
+        if labels is not None and i >= 0:
+            h["label"] = labels[i]
+        return h
+    return _json({"model": model, "backend": backend.backend, "metric": index.metric, "k": k, "count": int(index.count),
+                  "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(ids, scores)],
+                  "timing_ms": round(dt, 3)})
 
 
 @app.route("/health", methods=["GET"])

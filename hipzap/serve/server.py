@@ -339,6 +339,7 @@ class ModelServer:
         self.comm = None  # set by a DP cluster worker (serve/cluster.py): plan weights arrive by RCCL broadcast
         self.stats = {"requests": 0, "errors": 0, "cold_loads": 0}
         self.lm_listeners: list = []  # called with the GET /inference backend once it is loaded
+        self._indexes: dict = {}  # model name -> its open vector index (extra.index; POST /search)
 
     def spec(self, name: str) -> ModelSpec:
         return self.settings.models.get(name) or ModelSpec(name=name)
@@ -490,6 +491,31 @@ class ModelServer:
                     except Exception:  # noqa: BLE001 - the WSGI route keeps serving
                         log.exception("GET /inference listener failed")
             return self._models[key]
+
+    def index(self, name: str, backend):
+        """The vector index of an embedding model (``extra.index``: a path, or an artifact key fetched like
+        a checkpoint), opened once next to its backend: on the GPU for the GPU backend, else on the host."""
+        key = self.spec(name).extra.get("index")
+        if not key:
+            raise ValueError(f'{name} is served without extra.index: set "index": "<path or artifact key>" in its '
+                             f"settings block (hipzap index writes one)")
+        with self._lock:
+            if name not in self._indexes:
+                from ..search import open_index, read_header
+                path = key if os.path.isabs(key) and os.path.exists(key) else self.store.fetch(key)
+                dim, want = read_header(path)["dim"], int(backend.embed["dim"])
+                if dim != want:
+                    raise RuntimeError(f"{name}: index {path} has dim {dim}, the backend's embed.dim is {want}")
+                self._indexes[name] = open_index(path, self.backend, self.settings.devices[0])
+            return self._indexes[name]
+
+    def close(self) -> None:
+        """Close the vector indexes and drop the backends."""
+        with self._lock:
+            for ix in self._indexes.values():
+                ix.close()
+            self._indexes.clear()
+            self._models.clear()
 
     def loaded(self) -> dict:
         return {k: {"backend": getattr(v, "backend", "?"), "cold_ms": round(getattr(v, "cold_ms", 0), 1)}
