@@ -128,14 +128,15 @@ def cmd_index(a):
         vec, embed = be.embed_np(ids, None, mask), dict(be.embed)
         model = model or be.meta.get("model")
     labels = json.load(open(a.labels)) if a.labels else None
-    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed)
+    tags = np.load(a.tags, allow_pickle=False) if a.tags else None
+    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
 def cmd_info(a):
     if a.path:  # a .hzidx file: its header
-        from .search import read_header
-        print(json.dumps({"path": a.path, **read_header(a.path)}, indent=1))
+        from .search import file_info, read_header
+        print(json.dumps({"path": a.path, **read_header(a.path), **file_info(a.path)}, indent=1))
         return
     import torch
 
@@ -204,6 +205,7 @@ def main(argv=None):
     ix.add_argument("--ids", default=None, help="with --embed-plan: an .npy of token-id rows [N, L]")
     ix.add_argument("--mask", default=None, help="with --embed-plan: an .npy attention mask [N, L]")
     ix.add_argument("--labels", default=None, help="a JSON list of N strings")
+    ix.add_argument("--tags", default=None, help="an .npy of N uint32 tag words (search filters test them): a version-2 file")
     ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")
     ix.add_argument("--model", default=None, help="free text kept in the header")
     ix.add_argument("--device", type=int, default=0)

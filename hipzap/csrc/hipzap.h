@@ -455,12 +455,27 @@ unsigned long long hz_search_scratch_bytes(long long N, int Q, int k);
 // 0, or a negative code for a refused parameter block (nothing is launched then)
 int hz_search_scan_launch(const HzSearchParams* p, hipStream_t st);
 int hz_search_merge_launch(const HzSearchParams* p, hipStream_t st);
+// filtered scan (HZ_K_SEARCH_FSCAN): the scan over the rows that pass
+//   pass(q, r) = live(r) && (filt == NULL || (tags[r] & filt[q][0]) == filt[q][1])
+// A failing (q, r) scores the sentinel 0 (below every real key), whatever the row holds; a row that fails for
+// every query of the launch is not loaded. A tile's list holds its passing rows' best k keys, then key 0.
+// The score bits of a passing (q, r) are those of HZ_K_SEARCH_SCAN; HZ_K_SEARCH_MERGE reduces the lists.
+typedef struct HzSearchFilterParams {
+  HzSearchParams s;              // the scan's block, unchanged
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5
+  const unsigned* tags;          // one u32 per row [N], or NULL (then filt must be NULL)
+  const unsigned* filt;          // device [Q][2] = {mask, value} per query, or NULL: no tag predicate
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+} HzSearchFilterParams;
+int hz_search_fscan_launch(const HzSearchFilterParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
 // (stream, pinned query slot, device query buffer, candidate scratch, device and pinned result buffers).
 // A context's program (H2D copy, scan, merge, two D2H copies) is captured per (Q, k) on first use.
-// .hzidx: HzIndexHeader, the JSON header (json_len bytes), zero padding, the rows at data_off (4096-aligned)
+// .hzidx: HzIndexHeader, the JSON header (json_len bytes), zero padding, the rows at data_off (4096-aligned);
+// version 2 adds the JSON keys "capacity", "tags_off" and "live_off": two 4096-aligned blocks after the rows
+// holding count u32 tags and the live bitmap (4 * ceil(count / 32) bytes). Version 1: all live, zero tags.
 #define HZ_INDEX_MAGIC "HZIDX\0\0\1"
 enum { HZ_INDEX_COSINE = 0, HZ_INDEX_IP = 1 };
 typedef struct HzIndexHeader {
@@ -471,12 +486,28 @@ typedef struct HzIndexHeader {
 } HzIndexHeader;
 const char* hz_index_last_error(void);
 void* hz_index_open(const char* path, int device, int nctx);  // nctx <= 0: 2
-// out[8] = {count, dim, metric, contexts, tile rows, captured programs, device bytes, 0}
+// out[8] = {count, dim, metric, contexts, tile rows, captured programs, device bytes, capacity}
 int hz_index_describe(void* idx, uint64_t* out);
 // queries fp32 [Q][dim] -> out_score [Q][k], out_id [Q][k]; blocks until the results are in host memory.
 // One search at a time per context (a second caller of the same context waits).
 int hz_index_search(void* idx, int ctx, const float* queries, int Q, int k, float* out_score, int* out_id);
 void hz_index_close(void* idx);
+// a live index. open2: rows, tags and the live bitmap are allocated for max(count, reserve_rows)
+// rows rounded up to whole tiles. Ids are row positions, never reused. A mutation excludes every search: it
+// holds all context mutexes and synchronises its copies before it returns.
+void* hz_index_open2(const char* path, int device, int nctx, long long reserve_rows);
+// out[8] = {capacity, live rows, tags present, filtered programs in use, the filtered programs' N, 0, 0, 0};
+// hz_index_describe's out[0] is the current count and out[7] the capacity
+int hz_index_describe2(void* idx, uint64_t* out);
+// filt: host [Q][2] u32 {mask, value} or NULL. A never-mutated index without filt runs scan + merge (N = count)
+int hz_index_search_filtered(void* idx, int ctx, const float* queries, const unsigned* filt, int Q, int k,
+                             float* out_score, int* out_id);
+// append n bf16 rows (finite values: the caller checks) at ids [count, count + n); grows by doubling
+int hz_index_add(void* idx, const unsigned short* rows_bf16, long long n, const unsigned* tags_or_null, long long* first_id_out);
+int hz_index_delete(void* idx, const int* ids, long long n, long long* newly_deleted_out);  // -20: an id outside [0, count)
+int hz_index_set_tags(void* idx, const int* ids, const unsigned* tags, long long n);
+// the first n rows / tag words / ceil(n / 32) live words to host memory (any pointer may be NULL)
+int hz_index_read_state(void* idx, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -655,7 +686,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(POOL_EMBED, 29, HzPoolEmbedParams, hz_pool_embed_op, TRANSFORMER)     \
   X(RESIZE_PATCHIFY, 30, HzResizeParams, hz_resize_patchify_op, VISION)   \
   X(SEARCH_SCAN, 31, HzSearchParams, hz_search_scan_op, SEARCH)           \
-  X(SEARCH_MERGE, 32, HzSearchParams, hz_search_merge_op, SEARCH)
+  X(SEARCH_MERGE, 32, HzSearchParams, hz_search_merge_op, SEARCH)         \
+  X(SEARCH_FSCAN, 33, HzSearchFilterParams, hz_search_fscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

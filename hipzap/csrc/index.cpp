@@ -4,16 +4,28 @@
 // scores and ids, then waits on the context's stream. Q and k size the merge grid and the candidate
 // layout, which a captured graph holds by value, so a program is built, run once eagerly and captured
 // on the first search of each (Q, k), and replayed from then on (at most 16 x 128 small programs).
+//
+// A live index: the rows are allocated for a capacity of whole tiles, beside them a live
+// bitmap and one tag word per row. An index that was never mutated, searched without a filter, runs the
+// program above. Every other search runs the FILTERED program of its (Q, k): H2D copy of the slot (the
+// {mask, value} pairs in front of the queries), filtered scan, merge, two D2H copies. Its N is the count
+// rounded up to a whole tile (the rows past the count are dead in the bitmap), so deletes, tag writes and
+// adds inside the last tile change device data only and keep every captured program; an add that crosses
+// a tile boundary, or a growth (new allocations), destroys the programs, which are re-captured on next use.
+// A mutation holds every context's mutex and synchronises its copies before it releases them.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -27,25 +39,53 @@ std::nullptr_t fail(const std::string& m) {
   return nullptr;
 }
 
+constexpr uint64_t kTile = HZ_SEARCH_TILE;
+constexpr size_t kFiltBytes = (size_t)HZ_SEARCH_MAX_Q * 2 * 4;  // [MAX_Q][2] u32 in front of the queries
+
 struct Ctx {
   std::mutex mu;
   hipStream_t st = nullptr;
-  float* q_host = nullptr;            // pinned [MAX_Q][dim]
+  char* slot_host = nullptr;          // pinned: the filters [MAX_Q][2] u32, then the queries
+  char* slot_dev = nullptr;
+  float* q_host = nullptr;            // slot_host + kFiltBytes: [MAX_Q][dim]
   float* q_dev = nullptr;
   unsigned long long* cand = nullptr;
   uint64_t cand_bytes = 0;
   char* out_dev = nullptr;            // [MAX_Q][MAX_K] fp32 scores, then [MAX_Q][MAX_K] int32 ids
   char* out_host = nullptr;           // pinned, the same layout
-  std::map<std::pair<int, int>, HzProgram> progs;
+  std::map<std::tuple<int, int, int>, HzProgram> progs;  // (Q, k, filtered)
 };
 
 constexpr size_t kOutHalf = (size_t)HZ_SEARCH_MAX_Q * HZ_SEARCH_MAX_K * 4;
 
+uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
+
+// the unsigned integer value of `"key": <digits>` in the JSON header. The writer puts these keys last, after
+// the labels, so the LAST occurrence is the key itself even when a label spells the same word
+bool json_u64(const std::string& js, const char* key, uint64_t* out) {
+  const std::string k = std::string("\"") + key + "\"";
+  size_t at = js.rfind(k);
+  if (at == std::string::npos) return false;
+  at = js.find(':', at + k.size());
+  if (at == std::string::npos) return false;
+  ++at;
+  while (at < js.size() && js[at] == ' ') ++at;
+  if (at >= js.size() || js[at] < '0' || js[at] > '9') return false;
+  *out = std::strtoull(js.c_str() + at, nullptr, 10);
+  return true;
+}
+
 struct Index {
   int device = 0;
-  HzIndexHeader h{};
+  HzIndexHeader h{};                  // of the file; `count` below is the open index's
+  uint64_t count = 0, cap = 0;        // rows in use (ids 0 .. count-1), rows allocated (whole tiles)
+  uint64_t live_count = 0;
+  bool mutated = false;               // the unfiltered program (N = the file's count, all live) no longer holds
+  bool has_tags = false;
   unsigned short* rows = nullptr;
-  uint64_t row_bytes = 0;
+  unsigned* live = nullptr;           // device, cap / 32 words
+  unsigned* tags = nullptr;           // device, cap words
+  std::vector<uint32_t> live_host, tags_host;  // mirrors, sized like the device buffers
   std::vector<std::unique_ptr<Ctx>> ctx;
 
   ~Index() {
@@ -53,36 +93,75 @@ struct Index {
     for (auto& c : ctx) {
       if (c->st) (void)hipStreamSynchronize(c->st);
       for (auto& kv : c->progs) hz_prog_destroy(kv.second);
-      if (c->q_host) (void)hipHostFree(c->q_host);
+      if (c->slot_host) (void)hipHostFree(c->slot_host);
       if (c->out_host) (void)hipHostFree(c->out_host);
-      if (c->q_dev) (void)hipFree(c->q_dev);
+      if (c->slot_dev) (void)hipFree(c->slot_dev);
       if (c->cand) (void)hipFree(c->cand);
       if (c->out_dev) (void)hipFree(c->out_dev);
       if (c->st) (void)hipStreamDestroy(c->st);
     }
     if (rows) (void)hipFree(rows);
+    if (live) (void)hipFree(live);
+    if (tags) (void)hipFree(tags);
   }
 
-  // the context's program for (Q, k), built on first use (the caller holds c.mu)
-  HzProgram program(Ctx& c, int Q, int k, bool* fresh) {
-    auto it = c.progs.find({Q, k});
+  uint64_t row_bytes() const { return cap * h.dim * 2; }
+  uint64_t scan_rows() const { return round_up(count, kTile); }  // the filtered programs' N
+
+  void drop_programs() {  // the caller holds every context's mutex
+    for (auto& c : ctx) {
+      for (auto& kv : c->progs) hz_prog_destroy(kv.second);
+      c->progs.clear();
+    }
+  }
+
+  // the first mutation: the unfiltered programs (N = the file's count, all live) are never replayed again
+  void set_mutated() {  // the caller holds every context's mutex
+    if (mutated) return;
+    mutated = true;
+    for (auto& c : ctx)
+      for (auto it = c->progs.begin(); it != c->progs.end();) {
+        if (std::get<2>(it->first) == 0) {
+          hz_prog_destroy(it->second);
+          it = c->progs.erase(it);
+        } else {
+          ++it;
+        }
+      }
+  }
+
+  // the context's program for (Q, k, filtered), built on first use (the caller holds c.mu)
+  HzProgram program(Ctx& c, int Q, int k, bool filtered, bool* fresh) {
+    const auto key = std::make_tuple(Q, k, (int)filtered);
+    auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
-    HzSearchParams p{};
+    HzSearchFilterParams f{};
+    HzSearchParams& p = f.s;
     p.corpus = rows;
     p.queries = c.q_dev;
     p.cand = c.cand;
     p.out_score = reinterpret_cast<float*>(c.out_dev);
     p.out_id = reinterpret_cast<int*>(c.out_dev + kOutHalf);
-    p.N = (int)h.count;
+    p.N = (int)(filtered ? scan_rows() : count);
     p.D = p.ldc = (int)h.dim;
     p.Q = Q;
     p.k = k;
     p.cand_bytes = c.cand_bytes;
+    f.live = live;
+    f.tags = tags;
+    f.filt = reinterpret_cast<const unsigned*>(c.slot_dev);
+    f.live_bytes = cap / 8;
     HzProgram g = hz_prog_create();
-    const size_t qk = (size_t)Q * k * 4;
-    int rc = hz_prog_add_memcpy(g, c.q_dev, c.q_host, (size_t)Q * h.dim * 4, 0);
-    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_SCAN, &p, sizeof(p), 0);
+    const size_t qk = (size_t)Q * k * 4, qb = (size_t)Q * h.dim * 4;
+    int rc;
+    if (filtered) {
+      rc = hz_prog_add_memcpy(g, c.slot_dev, c.slot_host, kFiltBytes + qb, 0);
+      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_FSCAN, &f, sizeof(f), 0);
+    } else {
+      rc = hz_prog_add_memcpy(g, c.q_dev, c.q_host, qb, 0);
+      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_SCAN, &p, sizeof(p), 0);
+    }
     if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGE, &p, sizeof(p), 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.out_host, c.out_dev, qk, 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.out_dev + kOutHalf, qk, 0);
@@ -90,10 +169,63 @@ struct Index {
       hz_prog_destroy(g);
       return nullptr;
     }
-    c.progs[{Q, k}] = g;
+    c.progs[key] = g;
     return g;
   }
+
+  // device buffers for `new_cap` rows (whole tiles); the first `count` rows, their tags and the bitmap move
+  // over (device-to-device on `st`, synchronised), the rest is dead: zero bitmap, zero tags, rows untouched.
+  // The caller holds every context's mutex (or the index is not yet shared) and drops the programs.
+  int reallocate(uint64_t new_cap, hipStream_t st) {
+    unsigned short* nrows = nullptr;
+    unsigned *nlive = nullptr, *ntags = nullptr;
+    const uint64_t cand_bytes = hz_search_scratch_bytes((long long)new_cap, HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
+    if (!cand_bytes) return -21;  // 2^31 rows and above
+    std::vector<unsigned long long*> ncand(ctx.size(), nullptr);
+    bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * h.dim * 2) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&nlive), new_cap / 8) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&ntags), new_cap * 4) == hipSuccess;
+    for (size_t i = 0; ok && i < ctx.size(); ++i)
+      ok = hipMalloc(reinterpret_cast<void**>(&ncand[i]), cand_bytes) == hipSuccess;
+    ok = ok && hipMemsetAsync(nlive, 0, new_cap / 8, st) == hipSuccess;
+    ok = ok && hipMemsetAsync(ntags, 0, new_cap * 4, st) == hipSuccess;
+    if (ok && rows) {
+      ok = hipMemcpyAsync(nrows, rows, count * h.dim * 2, hipMemcpyDeviceToDevice, st) == hipSuccess;
+      ok = ok && hipMemcpyAsync(ntags, tags, count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+      ok = ok && hipMemcpyAsync(nlive, live, round_up(count, 32) / 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    }
+    ok = ok && hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) {
+      (void)hipFree(nrows), (void)hipFree(nlive), (void)hipFree(ntags);
+      for (auto* p : ncand) (void)hipFree(p);
+      return -22;
+    }
+    (void)hipFree(rows), (void)hipFree(live), (void)hipFree(tags);
+    rows = nrows, live = nlive, tags = ntags, cap = new_cap;
+    for (size_t i = 0; i < ctx.size(); ++i) {
+      (void)hipFree(ctx[i]->cand);
+      ctx[i]->cand = ncand[i];
+      ctx[i]->cand_bytes = cand_bytes;
+    }
+    live_host.resize(cap / 32, 0u);
+    tags_host.resize(cap, 0u);
+    return 0;
+  }
 };
+
+// every context's mutex, in index order: no search runs, and none starts, while a mutation holds them
+struct AllLocked {
+  std::vector<std::unique_lock<std::mutex>> lk;
+  explicit AllLocked(Index& x) {
+    for (auto& c : x.ctx) lk.emplace_back(c->mu);
+  }
+};
+
+// host words [w0, w1) of a mirror -> the device buffer, on `st`
+int push_words(unsigned* dev, const std::vector<uint32_t>& host, uint64_t w0, uint64_t w1, hipStream_t st) {
+  if (w1 <= w0) return 0;
+  return (int)hipMemcpyAsync(dev + w0, host.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, st);
+}
 
 }  // namespace
 
@@ -101,67 +233,119 @@ extern "C" {
 
 const char* hz_index_last_error(void) { return g_err.c_str(); }
 
-void* hz_index_open(const char* path, int device, int nctx) {
+void* hz_index_open2(const char* path, int device, int nctx, long long reserve_rows) {
   g_err.clear();
   if (nctx <= 0) nctx = 2;
   if (nctx > 16) return fail("index: at most 16 contexts");
+  if (reserve_rows < 0 || reserve_rows >= (1ll << 31)) return fail("index: reserve must be in 0..2^31-1 rows");
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) return fail(std::string("index: cannot open ") + path);
   HzIndexHeader h{};
   struct stat sb {};
-  const bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
+  bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
+  std::string js;
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version == 2 && h.json_len < (1u << 30)) {
+    js.resize(h.json_len);
+    got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
+  }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version != 1) return fail("index: unknown format version " + std::to_string(h.version));
+  if (h.version != 1 && h.version != 2) return fail("index: unknown format version " + std::to_string(h.version));
   if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
   if (h.count < 1 || h.count >= (1ull << 31)) return fail("index: count must be in 1..2^31-1");
   if (h.metric > HZ_INDEX_IP) return fail("index: unknown metric");
-  const uint64_t bytes = h.count * h.dim * 2;
-  if (h.data_off % 4096 || h.data_off < sizeof(h) + h.json_len || h.data_off + bytes > (uint64_t)sb.st_size)
+  const uint64_t bytes = h.count * h.dim * 2, fsize = (uint64_t)sb.st_size;
+  if (h.data_off % 4096 || h.data_off < sizeof(h) + h.json_len || h.data_off + bytes > fsize)
     return fail("index: row block outside the file");
+  uint64_t tags_off = 0, live_off = 0;
+  const uint64_t tag_bytes = h.count * 4, live_bytes = round_up(h.count, 32) / 8;
+  if (h.version == 2) {
+    if (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off))
+      return fail("index: a version-2 file without tags_off / live_off");
+    if (tags_off % 4096 || live_off % 4096 || tags_off < h.data_off + bytes || live_off < h.data_off + bytes ||
+        tags_off > fsize || tag_bytes > fsize - tags_off || live_off > fsize || live_bytes > fsize - live_off)
+      return fail("index: tags or live block outside the file");
+  }
   if (hipSetDevice(device) != hipSuccess) return fail("index: hipSetDevice failed");
   auto idx = std::make_unique<Index>();
   idx->device = device;
   idx->h = h;
-  idx->row_bytes = bytes;
+  idx->count = h.count;
   if (hz_search_code_warm()) return fail("index: device code load failed");
-  if (hipMalloc(reinterpret_cast<void**>(&idx->rows), bytes) != hipSuccess) return fail("index: device allocation failed");
-  const uint64_t cand_bytes = hz_search_scratch_bytes((long long)h.count, HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
   for (int i = 0; i < nctx; ++i) {
     auto c = std::make_unique<Ctx>();
-    const size_t qb = (size_t)HZ_SEARCH_MAX_Q * h.dim * 4;
+    const size_t sb_ = kFiltBytes + (size_t)HZ_SEARCH_MAX_Q * h.dim * 4;
     bool ok = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->q_host), qb, hipHostMallocDefault) == hipSuccess;
+    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->slot_host), sb_, hipHostMallocDefault) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->out_host), 2 * kOutHalf, hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->q_dev), qb) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->cand), cand_bytes) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&c->slot_dev), sb_) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->out_dev), 2 * kOutHalf) == hipSuccess;
-    c->cand_bytes = cand_bytes;
+    if (ok) {
+      std::memset(c->slot_host, 0, sb_);
+      c->q_host = reinterpret_cast<float*>(c->slot_host + kFiltBytes);
+      c->q_dev = reinterpret_cast<float*>(c->slot_dev + kFiltBytes);
+    }
     idx->ctx.push_back(std::move(c));
     if (!ok) return fail("index: context allocation failed");
   }
-  const uint64_t off = h.data_off;
-  void* dst = idx->rows;
-  if (hz_upload_file(path, 1, &off, &bytes, &dst, idx->ctx[0]->st)) return fail(std::string("index: ") + hz_plan_last_error());
-  if (hipStreamSynchronize(idx->ctx[0]->st) != hipSuccess) return fail("index: upload failed");
+  hipStream_t st = idx->ctx[0]->st;
+  const uint64_t cap = round_up(std::max<uint64_t>(h.count, (uint64_t)reserve_rows), kTile);
+  if (idx->reallocate(cap, st)) return fail("index: device allocation failed");
+  const uint64_t words = live_bytes / 4;
+  if (h.version == 2) {
+    const uint64_t off[3] = {h.data_off, tags_off, live_off}, len[3] = {bytes, tag_bytes, live_bytes};
+    void* dst[3] = {idx->rows, idx->tags, idx->live};
+    if (hz_upload_file(path, 3, off, len, dst, st)) return fail(std::string("index: ") + hz_plan_last_error());
+    bool ok = hipStreamSynchronize(st) == hipSuccess;
+    // the mirrors come back from the device copy (one read of the file); bits past the count are cleared
+    ok = ok && hipMemcpy(idx->tags_host.data(), idx->tags, tag_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(idx->live_host.data(), idx->live, live_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return fail("index: upload failed");
+    if (h.count % 32) idx->live_host[words - 1] &= (1u << (h.count % 32)) - 1u;
+    if (push_words(idx->live, idx->live_host, words - 1, words, st) || hipStreamSynchronize(st) != hipSuccess)
+      return fail("index: upload failed");
+    for (uint64_t w = 0; w < words; ++w) idx->live_count += (uint64_t)__builtin_popcount(idx->live_host[w]);
+    idx->has_tags = true;
+    idx->mutated = idx->live_count < h.count;
+  } else {
+    const uint64_t off = h.data_off;
+    void* dst = idx->rows;
+    if (hz_upload_file(path, 1, &off, &bytes, &dst, st)) return fail(std::string("index: ") + hz_plan_last_error());
+    for (uint64_t r = 0; r < h.count; ++r) idx->live_host[r >> 5] |= 1u << (r & 31);
+    idx->live_count = h.count;
+    if (push_words(idx->live, idx->live_host, 0, words, st) || hipStreamSynchronize(st) != hipSuccess)
+      return fail("index: upload failed");
+  }
   return idx.release();
 }
+
+void* hz_index_open(const char* path, int device, int nctx) { return hz_index_open2(path, device, nctx, 0); }
 
 int hz_index_describe(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
-  uint64_t progs = 0, dev = x->row_bytes;
+  AllLocked all(*x);
+  uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4;
   for (auto& c : x->ctx) {
-    std::lock_guard<std::mutex> lk(c->mu);
     progs += c->progs.size();
-    dev += c->cand_bytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf;
+    dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf;
   }
-  const uint64_t v[8] = {x->h.count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, 0};
+  const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
 
-int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float* out_score, int* out_id) {
+int hz_index_describe2(void* h, uint64_t* out) {
+  if (!h || !out) return -1;
+  Index* x = static_cast<Index*>(h);
+  AllLocked all(*x);
+  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), 0, 0, 0};
+  std::memcpy(out, v, sizeof(v));
+  return 0;
+}
+
+int hz_index_search_filtered(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, float* out_score,
+                             int* out_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !queries || !out_score || !out_id) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
@@ -170,10 +354,15 @@ int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float*
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
+  const bool filtered = x->mutated || filt != nullptr;
   bool fresh = false;
-  HzProgram g = x->program(c, Q, k, &fresh);
+  HzProgram g = x->program(c, Q, k, filtered, &fresh);
   if (!g) return -11;
   std::memcpy(c.q_host, queries, (size_t)Q * x->h.dim * 4);
+  if (filtered) {  // no filter: mask 0, value 0 passes every tag
+    if (filt) std::memcpy(c.slot_host, filt, (size_t)Q * 8);
+    else std::memset(c.slot_host, 0, (size_t)Q * 8);
+  }
   // first use: one eager run (it also answers this search), then the capture for the next ones
   int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
   if (!rc) rc = (int)hipStreamSynchronize(c.st);
@@ -185,6 +374,111 @@ int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float*
     if (!rc) rc = (int)hipStreamSynchronize(c.st);
   }
   return rc;
+}
+
+int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float* out_score, int* out_id) {
+  return hz_index_search_filtered(h, ctx, queries, nullptr, Q, k, out_score, out_id);
+}
+
+int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const unsigned* tags, long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !rows_bf16 || n < 1) return -1;
+  AllLocked all(*x);
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  const uint64_t first = x->count, last = first + (uint64_t)n;
+  if (last > (1ull << 31) - kTile) return -21;  // the capacity is whole tiles and below 2^31
+  hipStream_t st = x->ctx[0]->st;
+  const uint64_t scan_before = x->scan_rows();
+  if (last > x->cap) {  // grow by doubling: new allocations, device-to-device copies, a swap
+    x->drop_programs();
+    const uint64_t want = std::min<uint64_t>(round_up(std::max(last, 2 * x->cap), kTile), (1ull << 31) - kTile);
+    if (const int rc = x->reallocate(want, st)) return rc;
+  }
+  // rows and tags first: above `count` they are dead, so a failure here leaves nothing a search can see
+  for (uint64_t r = first; r < last; ++r) x->tags_host[r] = tags ? tags[r - first] : 0u;
+  int rc = (int)hipMemcpyAsync(x->rows + first * x->h.dim, rows_bf16, (uint64_t)n * x->h.dim * 2, hipMemcpyHostToDevice, st);
+  if (!rc) rc = push_words(x->tags, x->tags_host, first, last, st);
+  if (!rc) rc = (int)hipStreamSynchronize(st);
+  if (rc) return rc;
+  // then the live bits; if their copy fails the mirror is rolled back and the old words are pushed again
+  const uint64_t w0 = first >> 5, w1 = (last + 31) >> 5;
+  const std::vector<uint32_t> before(x->live_host.begin() + w0, x->live_host.begin() + w1);
+  for (uint64_t r = first; r < last; ++r) x->live_host[r >> 5] |= 1u << (r & 31);
+  rc = push_words(x->live, x->live_host, w0, w1, st);
+  if (!rc) rc = (int)hipStreamSynchronize(st);
+  if (rc) {
+    std::copy(before.begin(), before.end(), x->live_host.begin() + w0);
+    (void)push_words(x->live, x->live_host, w0, w1, st);
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  for (uint64_t r = first; r < last && tags && !x->has_tags; ++r) x->has_tags = tags[r - first] != 0;
+  x->count = last;
+  x->live_count += (uint64_t)n;
+  x->set_mutated();
+  if (x->scan_rows() != scan_before) x->drop_programs();  // the filtered programs hold N and ntile by value
+  if (first_id) *first_id = (long long)first;
+  return 0;
+}
+
+int hz_index_delete(void* h, const int* ids, long long n, long long* newly_deleted) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || (!ids && n > 0) || n < 0) return -1;
+  AllLocked all(*x);
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  for (long long i = 0; i < n; ++i)
+    if (ids[i] < 0 || (uint64_t)ids[i] >= x->count) return -20;
+  uint64_t lo = ~0ull, hi = 0, gone = 0;
+  for (long long i = 0; i < n; ++i) {
+    const uint64_t w = (uint64_t)ids[i] >> 5;
+    const uint32_t bit = 1u << (ids[i] & 31);
+    if (!(x->live_host[w] & bit)) continue;
+    x->live_host[w] &= ~bit;
+    lo = std::min(lo, w), hi = std::max(hi, w + 1), ++gone;
+  }
+  if (gone) {
+    hipStream_t st = x->ctx[0]->st;
+    int rc = push_words(x->live, x->live_host, lo, hi, st);
+    if (!rc) rc = (int)hipStreamSynchronize(st);
+    if (rc) return rc;
+    x->live_count -= gone;
+    x->set_mutated();
+  }
+  if (newly_deleted) *newly_deleted = (long long)gone;
+  return 0;
+}
+
+int hz_index_set_tags(void* h, const int* ids, const unsigned* tags, long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || ((!ids || !tags) && n > 0) || n < 0) return -1;
+  AllLocked all(*x);
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  for (long long i = 0; i < n; ++i)
+    if (ids[i] < 0 || (uint64_t)ids[i] >= x->count) return -20;
+  uint64_t lo = ~0ull, hi = 0;
+  for (long long i = 0; i < n; ++i) {
+    x->tags_host[ids[i]] = tags[i];
+    if (tags[i]) x->has_tags = true;
+    lo = std::min<uint64_t>(lo, ids[i]), hi = std::max<uint64_t>(hi, (uint64_t)ids[i] + 1);
+  }
+  if (n == 0) return 0;
+  hipStream_t st = x->ctx[0]->st;
+  int rc = push_words(x->tags, x->tags_host, lo, hi, st);
+  if (!rc) rc = (int)hipStreamSynchronize(st);
+  return rc;
+}
+
+// the first `n` (<= count) rows, tag words and ceil(n / 32) live words back to the host (for save); any may be NULL
+int hz_index_read_state(void* h, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || n < 0) return -1;
+  AllLocked all(*x);
+  if ((uint64_t)n > x->count) return -20;
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  if (tags_out) std::memcpy(tags_out, x->tags_host.data(), (size_t)n * 4);
+  if (live_out) std::memcpy(live_out, x->live_host.data(), (size_t)(((uint64_t)n + 31) / 32) * 4);
+  if (rows_out && n) return (int)hipMemcpy(rows_out, x->rows, (uint64_t)n * x->h.dim * 2, hipMemcpyDeviceToHost);
+  return 0;
 }
 
 void hz_index_close(void* h) { delete static_cast<Index*>(h); }

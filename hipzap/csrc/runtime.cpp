@@ -435,6 +435,10 @@ extern "C" __attribute__((weak)) int hz_search_merge_launch(const HzSearchParams
 static int hz_search_merge_op(const HzSearchParams* p, hipStream_t st) {
   return hz_search_merge_launch ? hz_search_merge_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_fscan_launch(const HzSearchFilterParams* p, hipStream_t st);
+static int hz_search_fscan_op(const HzSearchFilterParams* p, hipStream_t st) {
+  return hz_search_fscan_launch ? hz_search_fscan_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

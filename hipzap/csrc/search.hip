@@ -1,8 +1,9 @@
 // hipzap vector search for gfx950 (CDNA4): exact top-k by inner product over a bf16 corpus.
 //   * search_scan  — one workgroup per tile of HZ_SEARCH_TILE rows: every row is read once and scored
 //                    against all Q queries of the launch (resident in LDS); the tile's best k per query
+//   * search_fscan — the scan over the rows that pass a live bit and a per-query tag predicate
 //   * search_merge — one workgroup per query: ntile x k candidates -> the final k, best first
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l for the reasoning.
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m for the reasoning.
 #include <stdio.h>
 
 #include "common.h"
@@ -111,6 +112,137 @@ __global__ __launch_bounds__(T) void search_scan_kernel(const HzSearchParams p) 
         out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
     }
     if (t >= kk && t < p.k && slot_ok) out[t] = 0ull;  // a partial tile's unused slots (k <= 128 < T)
+  }
+}
+
+// ------------------------------------------------------------------------------------- filtered scan
+// The scan with pass(q, r) = live(r) && (filt == null || (tags[r] & mask[q]) == value[q]). Beside the
+// queries, the kernel's start stages the tile's 8 live words, its T tag words and the Q {mask, value} pairs
+// (one coalesced read each); thread t then folds them into pm[t], row t's pass bits over the queries. The
+// row loop reads pm of its (wave-uniform) rows through readfirstlane: a row with no pass bit is not
+// loaded, and a group of ROWS such rows only writes its sentinels -- scalar branches, no divergence. What a
+// dead row holds (the uninitialised rows between count and capacity included) never reaches a register.
+// A failing (q, r) is the sentinel 0 in `sc`, below orderable() of every real float. Ranking: a passing
+// row's rank counts only keys above it, all real, so it is below the tile's pass count `np`; sentinel rows
+// write nothing and slots np .. k-1 are zero-filled.
+// Addresses beyond the scan's: live words [row0/32, row0/32 + 8) under word*32 < N (the launcher checks
+// live_bytes), tags[row0 + t] under t < rows, filt[i] under i < 2Q.
+//
+// score_group: one group of ROWS rows (r0 .. r0 + ROWS - 1 of the tile, already in `v`) against every query: the fmaf
+// chains and the butterfly of search_scan_kernel, statement for statement (the score bits are the same by
+// construction; the unfiltered kernel keeps its own copy so that its code object does not change). `pm[r]`
+// holds row r's pass bits (bit q = query q); a failing (q, r) writes the sentinel 0 instead of its score.
+template <int NC>
+__device__ __forceinline__ void score_group(const HzSearchParams& p, const float* qs, unsigned* sc,
+                                            const u32x4 (&v)[ROWS][NC], const unsigned (&pm)[ROWS], int lane, int nch,
+                                            int r0, int rows) {
+  for (int q = 0; q < p.Q; ++q) {
+    float acc[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      if (c * 64 + lane < nch) {
+        const float* qp = qs + q * p.D + (c * 64 + lane) * 8;
+        const f32x4 qa = *reinterpret_cast<const f32x4*>(qp), qb = *reinterpret_cast<const f32x4*>(qp + 4);
+        const float qv[8] = {qa[0], qa[1], qa[2], qa[3], qb[0], qb[1], qb[2], qb[3]};
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+          float f[8];
+          unpack8(v[r][c], f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[r] = fmaf(qv[e], f[e], acc[r]);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const float s = warp_sum(acc[r]);
+      if (lane == r && r0 + r < rows) sc[q * T + r0 + r] = ((pm[r] >> q) & 1u) ? orderable(s) : 0u;
+    }
+  }
+}
+
+template <int NC>
+__global__ __launch_bounds__(T) void search_fscan_kernel(const HzSearchFilterParams fp) {
+  const HzSearchParams& p = fp.s;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* qs = lds;                                              // [Q][D]
+  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);  // [Q][T]
+  unsigned* pmask = sc + p.Q * T;                               // [T]: tags, then pass bits
+  unsigned* lv = pmask + T;                                     // [T / 32] live words of the tile
+  unsigned* fl = lv + T / 32;                                   // [Q][2]
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int nch = p.D >> 3;
+  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 512 && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  for (int i = t; i < p.Q * (p.D >> 2); i += T)
+    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(p.queries)[i];
+  unsigned tag = 0u;
+  if (fp.tags && t < rows && HZ_DCHECK(row0 + t < (long)p.N)) tag = fp.tags[row0 + t];
+  if (t < T / 32) {
+    const long word = (row0 >> 5) + t;
+    lv[t] = (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)fp.live_bytes)) ? fp.live[word] : 0u;
+  }
+  if (fp.filt && t < 2 * p.Q && HZ_DCHECK(t < 2 * HZ_SEARCH_MAX_Q)) fl[t] = fp.filt[t];
+  __syncthreads();
+  {
+    unsigned bits = 0u;
+    if (t < rows && ((lv[t >> 5] >> (t & 31)) & 1u)) {
+      bits = (1u << p.Q) - 1u;  // Q <= 16
+      if (fp.filt) {
+        bits = 0u;
+        for (int q = 0; q < p.Q; ++q) bits |= (unsigned)((tag & fl[2 * q]) == fl[2 * q + 1]) << q;
+      }
+    }
+    pmask[t] = bits;
+  }
+  __syncthreads();
+
+  for (int g = 0; g < 64; g += ROWS) {  // wave-uniform bounds
+    const int r0 = w * 64 + g;
+    if (r0 >= rows) break;
+    unsigned pm[ROWS], any = 0u;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {  // r0 + r < T: rows past the tile's end have pass bits 0
+      pm[r] = __builtin_amdgcn_readfirstlane(pmask[r0 + r]);
+      any |= pm[r];
+    }
+    if (any == 0u) {  // scalar: nothing of this group is loaded or scored
+      if (lane < ROWS && r0 + lane < rows)
+        for (int q = 0; q < p.Q; ++q) sc[q * T + r0 + lane] = 0u;
+      continue;
+    }
+    u32x4 v[ROWS][NC];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        v[r][c] = u32x4{0u, 0u, 0u, 0u};
+        if (pm[r] != 0u && c * 64 + lane < nch && HZ_DCHECK(row0 + r0 + r < (long)p.N))
+          v[r][c] = *reinterpret_cast<const u32x4*>(p.corpus + (row0 + r0 + r) * p.ldc + (c * 64 + lane) * 8);
+      }
+    score_group<NC>(p, qs, sc, v, pm, lane, nch, r0, rows);
+  }
+  __syncthreads();
+
+  for (int q = 0; q < p.Q; ++q) {
+    unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
+    const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
+    const unsigned mine = t < rows ? sc[q * T + t] : 0u;
+    int rank = 0, np = 0;
+    for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
+      const unsigned o = sc[q * T + j];
+      rank += (o > mine) || (o == mine && j < t);
+      np += o != 0u;
+    }
+    if (mine != 0u && rank < p.k && slot_ok)
+      out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
+    if (t >= np && t < p.k && slot_ok) out[t] = 0ull;  // the slots past the passing rows (k <= 128 < T)
   }
 }
 
@@ -249,10 +381,14 @@ int raise_lds_limit() {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
   if (done[d]) return 0;
-  const void* fns[4] = {reinterpret_cast<const void*>(&search_scan_kernel<1>),
+  const void* fns[8] = {reinterpret_cast<const void*>(&search_scan_kernel<1>),
                         reinterpret_cast<const void*>(&search_scan_kernel<2>),
                         reinterpret_cast<const void*>(&search_scan_kernel<3>),
-                        reinterpret_cast<const void*>(&search_scan_kernel<4>)};
+                        reinterpret_cast<const void*>(&search_scan_kernel<4>),
+                        reinterpret_cast<const void*>(&search_fscan_kernel<1>),
+                        reinterpret_cast<const void*>(&search_fscan_kernel<2>),
+                        reinterpret_cast<const void*>(&search_fscan_kernel<3>),
+                        reinterpret_cast<const void*>(&search_fscan_kernel<4>)};
   for (const void* f : fns) HZ_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   done[d] = true;
   return 0;
@@ -277,6 +413,26 @@ extern "C" int hz_search_scan_launch(const HzSearchParams* pp, hipStream_t st) {
     case 2: hipLaunchKernelGGL((search_scan_kernel<2>), dim3(p.ntile), dim3(T), lds, st, p); break;
     case 3: hipLaunchKernelGGL((search_scan_kernel<3>), dim3(p.ntile), dim3(T), lds, st, p); break;
     default: hipLaunchKernelGGL((search_scan_kernel<4>), dim3(p.ntile), dim3(T), lds, st, p); break;
+  }
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_search_fscan_launch(const HzSearchFilterParams* pp, hipStream_t st) {
+  HzSearchFilterParams f = *pp;
+  HzSearchParams& p = f.s;
+  if (const int rc = search_check(p)) return rc;
+  if (!f.live || (reinterpret_cast<uintptr_t>(f.live) & 3)) return -12;
+  if (f.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -13;
+  if (f.filt && !f.tags) return -14;
+  if ((reinterpret_cast<uintptr_t>(f.tags) & 3) || (reinterpret_cast<uintptr_t>(f.filt) & 3)) return -15;
+  // the scan's LDS plus the pass bits [T], the tile's live words and the Q filters: <= 144 KiB + 1184 B
+  const size_t lds = ((size_t)p.Q * p.D + (size_t)p.Q * T + T + T / 32 + 2 * (size_t)p.Q) * 4;
+  if (const int rc = raise_lds_limit()) return rc;
+  switch ((p.D / 8 + 63) / 64) {
+    case 1: hipLaunchKernelGGL((search_fscan_kernel<1>), dim3(p.ntile), dim3(T), lds, st, f); break;
+    case 2: hipLaunchKernelGGL((search_fscan_kernel<2>), dim3(p.ntile), dim3(T), lds, st, f); break;
+    case 3: hipLaunchKernelGGL((search_fscan_kernel<3>), dim3(p.ntile), dim3(T), lds, st, f); break;
+    default: hipLaunchKernelGGL((search_fscan_kernel<4>), dim3(p.ntile), dim3(T), lds, st, f); break;
   }
   return (int)hipGetLastError();
 }

@@ -3,7 +3,8 @@
 ``HzSearchParams`` is the parameter block of both kinds: ``HZ_K_SEARCH_SCAN`` (one workgroup per tile
 of ``tile_rows()`` corpus rows, all queries of the launch resident in LDS, the tile's best ``k`` keys per
 query into ``cand``) and ``HZ_K_SEARCH_MERGE`` (one workgroup per query, ``ntile x k`` keys -> the final
-``k``). torch-free: indexes (:mod:`hipzap.search`) are served without it."""
+``k``). ``HZ_K_SEARCH_FSCAN`` (``FilterScanParams``: the same block plus a live bitmap, per-row tags and
+per-query ``{mask, value}`` filters) is the scan over the rows that pass. torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,18 +22,39 @@ class SearchParams(C.Structure):
                 ("ldc", C.c_int), ("ntile", C.c_int), ("cand_bytes", C.c_uint64)]
 
 
+_FILTER_FIELDS = [("live", C.c_void_p), ("tags", C.c_void_p), ("filt", C.c_void_p), ("live_bytes", C.c_uint64)]
+
+
+@N.params_of("HZ_K_SEARCH_FSCAN")
+class FilterScanParams(C.Structure):
+    """HzSearchFilterParams: the fields of ``SearchParams``, then the filter's."""
+    _fields_ = SearchParams._fields_ + _FILTER_FIELDS
+
+    def scan_params(self) -> SearchParams:
+        """The leading ``SearchParams`` of this block (what the merge takes)."""
+        return SearchParams.from_buffer_copy(self)
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
     N._sig(lib, "hz_search_tile_rows", C.c_int)
     N._sig(lib, "hz_search_scratch_bytes", U64, C.c_longlong, C.c_int, C.c_int)
     N._sig(lib, "hz_search_scan_launch", C.c_int, C.POINTER(SearchParams), P)
     N._sig(lib, "hz_search_merge_launch", C.c_int, C.POINTER(SearchParams), P)
+    N._sig(lib, "hz_search_fscan_launch", C.c_int, C.POINTER(FilterScanParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
     N._sig(lib, "hz_index_last_error", C.c_char_p)
     N._sig(lib, "hz_index_open", P, C.c_char_p, C.c_int, C.c_int)
     N._sig(lib, "hz_index_describe", C.c_int, P, C.POINTER(U64))
     N._sig(lib, "hz_index_search", C.c_int, P, C.c_int, P, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_close", None, P)
+    N._sig(lib, "hz_index_open2", P, C.c_char_p, C.c_int, C.c_int, C.c_longlong)
+    N._sig(lib, "hz_index_describe2", C.c_int, P, C.POINTER(U64))
+    N._sig(lib, "hz_index_search_filtered", C.c_int, P, C.c_int, P, P, C.c_int, C.c_int, P, P)
+    N._sig(lib, "hz_index_add", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_delete", C.c_int, P, P, C.c_longlong, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_set_tags", C.c_int, P, P, P, C.c_longlong)
+    N._sig(lib, "hz_index_read_state", C.c_int, P, P, P, P, C.c_longlong)
 
 
 N._EXTRA_SIGS.append(_sigs)
@@ -55,3 +77,13 @@ def launch(prm: SearchParams, stream: int = 0) -> tuple:
     lib = N.lib()
     rc = lib.hz_search_scan_launch(C.byref(prm), stream)
     return rc, (lib.hz_search_merge_launch(C.byref(prm), stream) if rc == 0 else None)
+
+
+def launch_filtered(prm: FilterScanParams, stream: int = 0) -> tuple:
+    """Filtered scan then merge on ``stream``: (scan code, merge code); no merge after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_fscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    sp = prm.scan_params()
+    return rc, lib.hz_search_merge_launch(C.byref(sp), stream)

@@ -6,7 +6,14 @@ torch-free, like :mod:`hipzap.lite`: numpy and ctypes only.
 File format ``.hzidx`` (version 1): ``HzIndexHeader`` (csrc/hipzap.h: magic, version, the JSON header's
 length, the row block's offset, count, dim, metric), the JSON header ``{"dim", "count", "dtype": "bf16",
 "metric": "cosine" | "ip", "model", "embed": {"pooling", "normalize", "dim"} | null, "labels"?}``, zero
-padding, then the bf16 rows ``[count][dim]`` at a 4096-aligned offset.
+padding, then the bf16 rows ``[count][dim]`` at a 4096-aligned offset. Version 2 (written when an index has
+tags or deleted rows) adds the JSON keys ``capacity``, ``tags_off`` and ``live_off``: two 4096-aligned blocks
+after the rows, ``count`` uint32 tags and the live bitmap (bit ``r & 31`` of word ``r >> 5``). A version-1
+file opens as all live with zero tags.
+
+A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
+positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
+the query's ``(mask, value)`` filter, ``(tag & mask) == value``.
 
 Order rule (kernels and oracle alike): higher score first; among equal scores the lower row id first;
 ``-0.0`` counts as ``+0.0``; with fewer than ``k`` rows the slots past ``count`` hold id -1, score -inf.
@@ -18,6 +25,7 @@ import json
 import os
 import queue
 import struct
+import threading
 
 import numpy as np
 
@@ -25,6 +33,7 @@ from .ops.search import MAX_K, MAX_Q
 
 MAGIC = b"HZIDX\0\0\1"
 VERSION = 1
+VERSION2 = 2  # version 1 plus the JSON keys capacity / tags_off / live_off and their two blocks
 METRICS = ("cosine", "ip")
 ALIGN = 4096
 HEAD = struct.Struct("<8sIIQQII")  # HzIndexHeader: magic, version, json_len, data_off, count, dim, metric
@@ -40,9 +49,9 @@ def bf16_to_f32(b: np.ndarray) -> np.ndarray:
     return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
-def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None) -> dict:
-    """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
-    divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded."""
+def prepare_rows(vectors, metric: str) -> np.ndarray:
+    """fp32 [N, D] -> the bf16 bit patterns (uint16 [N, D]) an index of ``metric`` stores: the checks, the
+    cosine normalisation and the rounding of :func:`write_index` and of ``add`` (one function: the same bits)."""
     v = np.asarray(vectors)
     if v.ndim != 2 or v.dtype.kind != "f":
         raise ValueError(f"vectors must be a float array [N, D], got {v.dtype} {list(v.shape)}")
@@ -57,30 +66,92 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     bad = np.flatnonzero(~np.isfinite(v).all(axis=1))
     if bad.size:
         raise ValueError(f"row {int(bad[0])} has a non-finite value ({bad.size} such rows)")
-    if labels is not None:
-        labels = [str(s) for s in labels]
-        if len(labels) != n:
-            raise ValueError(f"{len(labels)} labels for {n} rows")
     if metric == "cosine":
         norm = np.sqrt((v * v).sum(axis=1, dtype=np.float32), dtype=np.float32)
         v = v / np.maximum(norm, np.float32(1e-12))[:, None]
     rows = to_bf16(v)
     if not np.isfinite(bf16_to_f32(rows)).all():
         raise ValueError("a value overflows bf16")
+    return rows
+
+
+def check_tags(tags, n: int) -> np.ndarray:
+    """``tags`` as uint32 [n]; integers in 0..2^32-1 only."""
+    t = np.asarray(tags)
+    if t.ndim != 1 or t.shape[0] != n or t.dtype.kind not in "iu":
+        raise ValueError(f"tags must be {n} integers, got {t.dtype} {list(t.shape)}")
+    if t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+        raise ValueError("tags must be in 0..2^32-1")
+    return np.ascontiguousarray(t.astype(np.uint32))
+
+
+def pack_live(live) -> np.ndarray:
+    """bool [N] -> the live bitmap, uint32 [ceil(N / 32)]: bit r & 31 of word r >> 5."""
+    live = np.asarray(live, bool)
+    pad = np.zeros(-(-live.size // 32) * 32, np.uint8)
+    pad[:live.size] = live
+    return np.packbits(pad, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def unpack_live(words, n: int) -> np.ndarray:
+    return np.unpackbits(np.ascontiguousarray(words, "<u4").view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
+def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None) -> dict:
+    """The file of ``hdr`` and ``rows``: version 1 without ``tags`` / ``live``, else version 2 (zero tags / all
+    live where one is missing). Atomic: a temporary file, then a rename. Returns the JSON header written."""
+    n = rows.shape[0]
+
+    def align(x):
+        return -(-x // ALIGN) * ALIGN
+    if tags is None and live is None:
+        version, js = VERSION, json.dumps(hdr).encode()
+        data_off = align(HEAD.size + len(js))
+    else:
+        version = VERSION2
+        tags = np.zeros(n, np.uint32) if tags is None else tags
+        words = pack_live(np.ones(n, bool) if live is None else live)
+        hdr = dict(hdr, capacity=int(max(capacity or 0, n)), tags_off=0, live_off=0)
+        while True:  # the offsets follow the JSON's own length: a few rounds until they agree
+            js = json.dumps(hdr).encode()
+            data_off = align(HEAD.size + len(js))
+            tags_off = align(data_off + rows.nbytes)
+            live_off = align(tags_off + 4 * n)
+            if (hdr["tags_off"], hdr["live_off"]) == (tags_off, live_off):
+                break
+            hdr["tags_off"], hdr["live_off"] = tags_off, live_off
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(HEAD.pack(MAGIC, version, len(js), data_off, n, rows.shape[1], METRICS.index(hdr["metric"])))
+        f.write(js)
+        f.write(bytes(data_off - HEAD.size - len(js)))
+        f.write(rows.tobytes())
+        if version == VERSION2:
+            f.write(bytes(tags_off - data_off - rows.nbytes))
+            f.write(tags.astype("<u4").tobytes())
+            f.write(bytes(live_off - tags_off - 4 * n))
+            f.write(words.astype("<u4").tobytes())
+    os.replace(tmp, path)
+    return hdr
+
+
+def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None) -> dict:
+    """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
+    divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
+    ``tags`` the file is version 1; with them (uint32 [N]) version 2."""
+    rows = prepare_rows(vectors, metric)
+    n, d = rows.shape
+    if labels is not None:
+        labels = [str(s) for s in labels]
+        if len(labels) != n:
+            raise ValueError(f"{len(labels)} labels for {n} rows")
+    if tags is not None:
+        tags = check_tags(tags, n)
     hdr = {"dim": d, "count": n, "dtype": "bf16", "metric": metric, "model": str(model or ""),
            "embed": dict(embed) if embed else None}
     if labels is not None:
         hdr["labels"] = labels
-    js = json.dumps(hdr).encode()
-    data_off = -(-(HEAD.size + len(js)) // ALIGN) * ALIGN
-    tmp = path + ".tmp"
-    with open(tmp, "wb") as f:
-        f.write(HEAD.pack(MAGIC, VERSION, len(js), data_off, n, d, METRICS.index(metric)))
-        f.write(js)
-        f.write(bytes(data_off - HEAD.size - len(js)))
-        f.write(rows.tobytes())
-    os.replace(tmp, path)
-    return hdr
+    return _write_file(path, hdr, rows, tags)
 
 
 def read_header(path: str) -> dict:
@@ -90,15 +161,48 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version != VERSION:
+        if version not in (VERSION, VERSION2):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
+        size = os.fstat(f.fileno()).st_size
     if metric >= len(METRICS) or (hdr.get("dim"), hdr.get("count"), hdr.get("metric")) != (dim, count, METRICS[metric]) \
             or hdr.get("dtype") != "bf16":
         raise ValueError(f"{path}: the JSON header disagrees with the file head")
     if hdr.get("labels") is not None and len(hdr["labels"]) != count:
         raise ValueError(f"{path}: {len(hdr['labels'])} labels for {count} rows")
+    if version == VERSION2:
+        end = data_off + count * dim * 2
+        for key, nbytes in (("tags_off", 4 * count), ("live_off", 4 * (-(-count // 32)))):
+            off = hdr.get(key)
+            if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
+                raise ValueError(f"{path}: the {key[:4]} block lies outside the file")
+        if not isinstance(hdr.get("capacity"), int) or hdr["capacity"] < count:
+            raise ValueError(f"{path}: capacity below count")
     return dict(hdr, data_off=int(data_off))
+
+
+def read_tags(path: str) -> np.ndarray:
+    """The tag words, uint32 [count] (zeros for a version-1 file)."""
+    hdr = read_header(path)
+    if "tags_off" not in hdr:
+        return np.zeros(hdr["count"], np.uint32)
+    return np.fromfile(path, "<u4", hdr["count"], offset=hdr["tags_off"]).astype(np.uint32)
+
+
+def read_live(path: str) -> np.ndarray:
+    """Liveness per row, bool [count] (all live for a version-1 file)."""
+    hdr = read_header(path)
+    if "live_off" not in hdr:
+        return np.ones(hdr["count"], bool)
+    return unpack_live(np.fromfile(path, "<u4", -(-hdr["count"] // 32), offset=hdr["live_off"]), hdr["count"])
+
+
+def file_info(path: str) -> dict:
+    """What ``hipzap info`` adds to the header: the format version, capacity, live rows, tags presence."""
+    hdr = read_header(path)
+    v2 = "tags_off" in hdr
+    return {"version": VERSION2 if v2 else VERSION, "capacity": hdr.get("capacity", hdr["count"]),
+            "live": int(read_live(path).sum()), "tags": v2}
 
 
 def read_rows(path: str) -> np.ndarray:
@@ -107,20 +211,29 @@ def read_rows(path: str) -> np.ndarray:
     return np.fromfile(path, np.uint16, hdr["count"] * hdr["dim"], offset=hdr["data_off"]).reshape(hdr["count"], hdr["dim"])
 
 
-def search_ref(corpus, q, k: int):
+def search_ref(corpus, q, k: int, allow=None):
     """The oracle: ``corpus`` (the bf16 rows widened to fp32, [N, D]) against ``q`` (fp32 [Q, D]) in fp64
     -> (scores float64 [Q, k], ids int32 [Q, k]) under the order rule. Each score is one row's own sum, so
-    equal rows give equal scores wherever they stand."""
+    equal rows give equal scores wherever they stand. ``allow`` (bool [N] or [Q, N]): only these rows may be
+    returned, under their own ids; the slots past the allowed rows hold id -1, score -inf."""
     c = np.asarray(corpus, np.float64)
     q = np.asarray(q, np.float64)
     if q.ndim == 1:
         q = q[None]
     n = c.shape[0]
+    if allow is not None:
+        allow = np.asarray(allow, bool)
+        if allow.shape not in ((n,), (q.shape[0], n)):
+            raise ValueError(f"allow must be bool [{n}] or [{q.shape[0]}, {n}], got {list(allow.shape)}")
     scores = np.full((q.shape[0], k), -np.inf)
     ids = np.full((q.shape[0], k), -1, np.int32)
     for i, row in enumerate(q):
         s = (c * row[None, :]).sum(axis=1) + 0.0  # -0.0 + 0.0 = +0.0
-        order = np.argsort(-s, kind="stable")[:k]  # stable: equal scores keep ascending ids
+        if allow is None:
+            order = np.argsort(-s, kind="stable")[:k]  # stable: equal scores keep ascending ids
+        else:
+            rows = np.flatnonzero(allow if allow.ndim == 1 else allow[i])
+            order = rows[np.argsort(-s[rows], kind="stable")[:k]]
         scores[i, :order.size] = s[order]
         ids[i, :order.size] = order
     return scores, ids
@@ -151,12 +264,39 @@ def normalize_rows(q: np.ndarray) -> np.ndarray:
     return q / np.maximum(norm, np.float32(1e-12))[:, None]
 
 
+def check_filter(filter, nq: int):
+    """``filter`` -> uint32 [nq, 2] of {mask, value} per query, or None: ``(mask, value)`` for every query,
+    or a sequence of ``nq`` such pairs; integers in 0..2^32-1."""
+    if filter is None:
+        return None
+
+    def is_int(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+    f = list(filter) if not isinstance(filter, np.ndarray) else filter.tolist()
+    if len(f) == 2 and is_int(f[0]) and is_int(f[1]):
+        f = [f] * nq
+    if len(f) != nq:
+        raise ValueError(f"filter must be (mask, value) or {nq} such pairs, got {len(f)}")
+    out = np.empty((nq, 2), np.uint32)
+    for i, pair in enumerate(f):
+        pair = list(pair) if isinstance(pair, (list, tuple, np.ndarray)) else [pair]
+        if len(pair) != 2 or not all(is_int(x) and 0 <= x <= 0xFFFFFFFF for x in pair):
+            raise ValueError(f"filter {i}: mask and value must be integers in 0..2^32-1, got {pair!r}")
+        out[i] = pair
+    return out
+
+
 class _Base:
+    """What both backends share: the header, the argument checks of the mutators and ``save``. A backend
+    provides ``_append(bits, tags, publish)`` (which calls ``publish(first id)`` before searches may run again), ``_kill(ids) -> int``, ``_retag(ids, tags)`` and ``_state() -> (bits,
+    tags, live)``."""
+
     def __init__(self, path: str):
         self.path = path
         self.header = read_header(path)
         self.dim, self.count, self.metric = self.header["dim"], self.header["count"], self.header["metric"]
         self.labels = self.header.get("labels")
+        self._mut = threading.Lock()  # one mutator at a time
 
     def __enter__(self):
         return self
@@ -164,23 +304,128 @@ class _Base:
     def __exit__(self, *exc):
         self.close()
 
+    def _check_ids(self, ids) -> np.ndarray:
+        a = np.atleast_1d(np.asarray(ids))
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError(f"ids must be a list of integers, got {a.dtype} {list(a.shape)}")
+        bad = a[(a < 0) | (a >= self.count)] if a.size else a
+        if bad.size:
+            raise ValueError(f"id {int(bad[0])} is outside [0, {self.count})")
+        return np.ascontiguousarray(a.astype(np.int32))
+
+    def add(self, vectors, tags=None, labels=None) -> np.ndarray:
+        """Append rows (fp32 [n, dim], through :func:`prepare_rows`: the bits ``write_index`` would store) ->
+        their ids, int32 [n]. ``tags``: uint32 [n], default 0. ``labels``: required iff the index has labels."""
+        bits = prepare_rows(vectors, self.metric)
+        n = bits.shape[0]
+        if bits.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [N, {self.dim}], got {list(bits.shape)}")
+        if (labels is not None) != (self.labels is not None):
+            raise ValueError("labels are required: the index has labels" if labels is None
+                             else "the index has no labels")
+        if labels is not None:
+            labels = [str(x) for x in labels]
+            if len(labels) != n:
+                raise ValueError(f"{len(labels)} labels for {n} rows")
+        tags = np.zeros(n, np.uint32) if tags is None else check_tags(tags, n)
+        with self._mut:
+            if self.count + n >= 2 ** 31:
+                raise ValueError("count must stay below 2^31")
+
+            def publish(first):  # runs while searches are still excluded: no search sees an id without its label
+                if labels is not None:
+                    self.labels = list(self.labels) + labels
+                self.count = first + n
+                self.header["count"] = self.count
+            first = self._append(bits, tags, publish)
+        return np.arange(first, first + n, dtype=np.int32)
+
+    def delete(self, ids) -> int:
+        """Hide rows for good -> how many were live until now. An id outside [0, count) is a ValueError."""
+        with self._mut:
+            return int(self._kill(self._check_ids(ids)))
+
+    def set_tags(self, ids, tags) -> None:
+        with self._mut:
+            ids = self._check_ids(ids)
+            self._retag(ids, check_tags(tags, ids.size))
+
+    def save(self, path: str | None = None, compact: bool = False) -> dict:
+        """Write the index as it stands (atomic: a temporary file, then a rename) -> the JSON header.
+        ``compact=False`` keeps ids and tombstones; ``compact=True`` drops the dead rows and renumbers the
+        rest in order. Version 1 when every row is live and every tag is 0, else version 2."""
+        with self._mut:
+            bits, tags, live = self._state()
+            labels = self.labels
+            if compact:
+                if not live.any():
+                    raise ValueError("no live row to save")
+                bits, tags = bits[live], tags[live]
+                labels = [x for x, keep in zip(labels, live) if keep] if labels is not None else None
+                live = np.ones(bits.shape[0], bool)
+            hdr = {"dim": self.dim, "count": int(bits.shape[0]), "dtype": "bf16", "metric": self.metric,
+                   "model": self.header.get("model", ""), "embed": self.header.get("embed")}
+            if labels is not None:
+                hdr["labels"] = list(labels)
+            plain = bool(live.all()) and not tags.any()
+            return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), None if plain else tags,
+                               None if plain else live, self.capacity())
+
 
 class RefIndex(_Base):
-    """The index on the host: :func:`search_ref` over the file's rows (the CPU backend's implementation)."""
+    """The index on the host: :func:`search_ref` over the rows (the CPU backend's implementation and the
+    oracle of the GPU one)."""
     backend = "cpu"
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, reserve: int = 0):
         super().__init__(path)
-        self._rows = bf16_to_f32(read_rows(path))
+        self._bits = read_rows(path)
+        self._rows = bf16_to_f32(self._bits)
+        self._tags, self._live = read_tags(path), read_live(path)
+        self._cap = max(self.count, int(reserve), int(self.header.get("capacity", 0)))
 
-    def search(self, q, k: int = 10):
+    def allow(self, filt) -> np.ndarray:
+        """bool [N] (no filter) or [Q, N]: the rows each query may return."""
+        if filt is None:
+            return self._live
+        return self._live[None, :] & ((self._tags[None, :] & filt[:, :1]) == filt[:, 1:])
+
+    def search(self, q, k: int = 10, *, filter=None):
         q, k = check_queries(q, self.dim), check_k(k)
-        s, i = search_ref(self._rows, q, k)
+        filt = check_filter(filter, q.shape[0])
+        with self._mut:  # the mutators replace the arrays one by one
+            s, i = search_ref(self._rows, q, k, None if filt is None and self._live.all() else self.allow(filt))
         return s.astype(np.float32), i
+
+    def _append(self, bits, tags, publish):
+        first = self.count
+        self._bits = np.concatenate([self._bits, bits])
+        self._rows = np.concatenate([self._rows, bf16_to_f32(bits)])
+        self._tags = np.concatenate([self._tags, tags])
+        self._live = np.concatenate([self._live, np.ones(bits.shape[0], bool)])
+        while self._cap < self._bits.shape[0]:
+            self._cap *= 2
+        publish(first)
+        return first
+
+    def _kill(self, ids):
+        was = int(self._live.sum())
+        self._live[ids] = False
+        return was - int(self._live.sum())
+
+    def _retag(self, ids, tags):
+        self._tags[ids] = tags
+
+    def _state(self):
+        return self._bits, self._tags, self._live
+
+    def capacity(self) -> int:
+        return self._cap
 
     def describe(self) -> dict:
         return {"path": self.path, "backend": "cpu", **{k: v for k, v in self.header.items() if k != "labels"},
-                "labels": self.labels is not None}
+                "labels": self.labels is not None, "capacity": self._cap, "live": int(self._live.sum()),
+                "tags": bool(self._tags.any()) or "tags_off" in self.header}
 
     def close(self) -> None:
         self._rows = None
@@ -189,14 +434,17 @@ class RefIndex(_Base):
 class Index(_Base):
     """An open ``.hzidx`` on the GPU: the rows in device memory and ``contexts`` search contexts (each
     its own stream and buffers). :meth:`search` is thread-safe: a call takes a free context, or waits for
-    one. Query batches above 16 rows are searched 16 at a time."""
+    one. Query batches above 16 rows are searched 16 at a time. ``reserve``: rows to allocate for (adds
+    beyond the capacity grow it by doubling). A mutator takes every context before it calls native code,
+    so a search sees the index entirely before or entirely after a mutation."""
     backend = "gpu"
 
-    def __init__(self, path: str, device: int = 0, contexts: int = 2):
+    def __init__(self, path: str, device: int = 0, contexts: int = 2, reserve: int = 0):
         super().__init__(path)
         from . import _native as N
         self._lib = N.lib()
-        self._h = self._lib.hz_index_open(os.fsencode(path), int(device), int(contexts))
+        reserve = max(int(reserve), int(self.header.get("capacity", 0)))
+        self._h = self._lib.hz_index_open2(os.fsencode(path), int(device), int(contexts), reserve)
         if not self._h:
             raise RuntimeError((self._lib.hz_index_last_error() or b"hz_index_open failed").decode())
         self.device, self.contexts = int(device), int(contexts)
@@ -204,9 +452,11 @@ class Index(_Base):
         for c in range(self.contexts):
             self._free.put(c)
 
-    def search(self, q, k: int = 10, ctx: int | None = None):
-        """fp32 queries [Q, dim] -> (scores float32 [Q, k], ids int32 [Q, k]), best first."""
+    def search(self, q, k: int = 10, ctx: int | None = None, *, filter=None):
+        """fp32 queries [Q, dim] -> (scores float32 [Q, k], ids int32 [Q, k]), best first. ``filter``:
+        ``(mask, value)`` for all queries or Q such pairs; a row passes iff ``(tag & mask) == value``."""
         q, k = check_queries(q, self.dim), check_k(k)
+        filt = check_filter(filter, q.shape[0])
         if self._h is None:
             raise RuntimeError("the index is closed")
         scores = np.empty((q.shape[0], k), np.float32)
@@ -216,7 +466,9 @@ class Index(_Base):
             for a in range(0, q.shape[0], MAX_Q):
                 part = q[a:a + MAX_Q]
                 s, i = scores[a:a + MAX_Q], ids[a:a + MAX_Q]  # contiguous row ranges of the outputs
-                rc = self._lib.hz_index_search(self._h, c, part.ctypes.data, part.shape[0], k, s.ctypes.data, i.ctypes.data)
+                f = None if filt is None else np.ascontiguousarray(filt[a:a + MAX_Q])
+                rc = self._lib.hz_index_search_filtered(self._h, c, part.ctypes.data, None if f is None else f.ctypes.data,
+                                                        part.shape[0], k, s.ctypes.data, i.ctypes.data)
                 if rc:
                     raise RuntimeError(f"hz_index_search failed with code {rc}")
         finally:
@@ -224,12 +476,61 @@ class Index(_Base):
                 self._free.put(c)
         return scores, ids
 
+    def _exclusive(self, call, what):
+        """Run a native mutation holding every context token (the caller holds the mutation lock, so no
+        second mutator waits on a partial set)."""
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        held = [self._free.get() for _ in range(self.contexts)]
+        try:
+            rc = call()
+        finally:
+            for c in held:
+                self._free.put(c)
+        if rc:
+            raise RuntimeError(f"{what} failed with code {rc}")
+
+    def _append(self, bits, tags, publish):
+        first = C.c_longlong(-1)
+        bits = np.ascontiguousarray(bits)
+
+        def call():
+            rc = self._lib.hz_index_add(self._h, bits.ctypes.data, bits.shape[0], tags.ctypes.data, C.byref(first))
+            if rc == 0:
+                publish(int(first.value))
+            return rc
+        self._exclusive(call, "hz_index_add")
+        return int(first.value)
+
+    def _kill(self, ids):
+        gone = C.c_longlong(0)
+        self._exclusive(lambda: self._lib.hz_index_delete(self._h, ids.ctypes.data, ids.size, C.byref(gone)),
+                        "hz_index_delete")
+        return int(gone.value)
+
+    def _retag(self, ids, tags):
+        self._exclusive(lambda: self._lib.hz_index_set_tags(self._h, ids.ctypes.data, tags.ctypes.data, ids.size),
+                        "hz_index_set_tags")
+
+    def _state(self):
+        n = self.count
+        bits, tags = np.empty((n, self.dim), np.uint16), np.empty(n, np.uint32)
+        words = np.empty(-(-n // 32), np.uint32)
+        self._exclusive(lambda: self._lib.hz_index_read_state(self._h, bits.ctypes.data, tags.ctypes.data,
+                                                              words.ctypes.data, n), "hz_index_read_state")
+        return bits, tags, unpack_live(words, n)
+
+    def capacity(self) -> int:
+        return self.describe()["capacity"]
+
     def describe(self) -> dict:
-        out = (C.c_uint64 * 8)()
+        out, more = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
         self._lib.hz_index_describe(self._h, out)
+        self._lib.hz_index_describe2(self._h, more)
         return {"path": self.path, "backend": "gpu", "device": self.device,
                 **{k: v for k, v in self.header.items() if k != "labels"}, "labels": self.labels is not None,
-                "contexts": int(out[3]), "tile_rows": int(out[4]), "programs": int(out[5]), "device_bytes": int(out[6])}
+                "contexts": int(out[3]), "tile_rows": int(out[4]), "programs": int(out[5]), "device_bytes": int(out[6]),
+                "capacity": int(more[0]), "live": int(more[1]), "tags": bool(more[2]), "filtered": bool(more[3])}
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -243,5 +544,5 @@ class Index(_Base):
             pass
 
 
-def open_index(path: str, backend: str = "gpu", device: int = 0):
-    return Index(path, device) if backend == "gpu" else RefIndex(path)
+def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 0):
+    return Index(path, device, reserve=reserve) if backend == "gpu" else RefIndex(path, reserve)

@@ -8,6 +8,7 @@ Routes (reference: /root/reference/main.py:17-18, 105-112):
   POST /embed       one pooled vector per text / image from a BERT or ViT encoder served with
                     ``extra.embed`` -> {"model", "dim", "pooling", "normalized", "embeddings", ...}, or a
                     float32 ``.npy`` [n, dim] with ``Accept: application/octet-stream``
+  POST /index/add, /index/delete, /index/save   mutate the model's index (``extra.index_writable: true``)
   POST /search      nearest rows of the model's vector index (``extra.index``, a ``.hzidx`` file) for the
                     bodies of /embed or ready ``vectors`` -> {"model", "metric", "k", "count", "results", ...},
                     or a structured ``.npy`` [Q, k] (id, score) with ``Accept: application/octet-stream``
@@ -130,7 +131,8 @@ def _error(e):
 def index():
     s = get_server()
     return _json({"service": "hipzap", "version": __version__, "backend": s.backend,
-                  "routes": ["GET /inference", "POST /predict", "POST /embed", "POST /search", "GET /health", "GET /metrics"]})
+                  "routes": ["GET /inference", "POST /predict", "POST /embed", "POST /search", "POST /index/add", "POST /index/delete",
+                             "POST /index/save", "GET /health", "GET /metrics"]})
 
 
 @app.route("/inference", methods=["GET"])
@@ -413,11 +415,105 @@ def _embedding_backend(s, model):
     return backend
 
 
+def _u32_field(value, name: str) -> int:
+    if not isinstance(value, int) or isinstance(value, bool) or not 0 <= value <= 0xFFFFFFFF:
+        raise ValueError(f"{name} must be an integer in 0..4294967295, got {value!r}")
+    return value
+
+
+def _search_filter(body):
+    """``"filter": {"mask": m, "value": v}`` or the shorthand ``"tag": t`` (mask 0xffffffff) -> (mask, value)."""
+    if "filter" in body:
+        f = body["filter"]
+        if not isinstance(f, dict) or set(f) != {"mask", "value"}:
+            raise ValueError('filter must be {"mask": m, "value": v}')
+        if "tag" in body:
+            raise ValueError("give one of filter and tag")
+        return _u32_field(f["mask"], "filter.mask"), _u32_field(f["value"], "filter.value")
+    if "tag" in body:
+        return 0xFFFFFFFF, _u32_field(body["tag"], "tag")
+    return None
+
+
+def _writable_index(s, body):
+    """The model's index for a mutation route: 400 without ``extra.index``, 403 without
+    ``extra.index_writable: true``."""
+    model = body.get("model") or request.args.get("model") or "bert-base"
+    extra = s.spec(model).extra
+    if not extra.get("index"):
+        raise ValueError(f'{model} is served without extra.index: set "index": "<path or artifact key>" in its '
+                         f"settings block (hipzap index writes one)")
+    if extra.get("index_writable") is not True:
+        return model, None
+    return model, s.index(model, _embedding_backend(s, model))
+
+
+def _forbidden(model):
+    return _json({"error": "Forbidden", "message": f'{model}: the index is read-only; set "index_writable": true in its settings block'}, 403)
+
+
+@app.route("/index/add", methods=["POST"])
+def index_add():
+    """Append rows to the model's index: the vectors /embed gives for the body, or ``{"model", "vectors"}``;
+    optional ``"tags"`` (integers 0..2^32-1) and ``"labels"`` (required iff the index has labels)."""
+    s = get_server()
+    body = {}
+    if request.mimetype != "application/octet-stream" and request.mimetype not in IMAGE_TYPES:
+        body = request.get_json(force=True, silent=True) or {}
+    model, index = _writable_index(s, body)
+    if index is None:
+        return _forbidden(model)
+    if "vectors" in body:
+        try:
+            vec = np.asarray(body["vectors"], dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError("vectors must be a list of equally long lists of numbers") from None
+        vec = vec[None] if vec.ndim == 1 else vec
+    else:
+        vec = np.ascontiguousarray(_embed_vectors(s)[3], np.float32)
+    tags = body.get("tags")
+    if tags is not None:
+        if not isinstance(tags, list):
+            raise ValueError("tags must be a list of integers in 0..4294967295")
+        tags = np.asarray([_u32_field(t, "tags") for t in tags], np.uint32)
+    labels = body.get("labels")
+    if labels is not None and (not isinstance(labels, list) or not all(isinstance(x, str) for x in labels)):
+        raise ValueError("labels must be a list of strings")
+    ids = index.add(vec, tags=tags, labels=labels)
+    return _json({"model": model, "ids": [int(i) for i in ids], "count": int(index.count)})
+
+
+@app.route("/index/delete", methods=["POST"])
+def index_delete():
+    s = get_server()
+    body = request.get_json(force=True, silent=True) or {}
+    model, index = _writable_index(s, body)
+    if index is None:
+        return _forbidden(model)
+    ids = body.get("ids")
+    if not isinstance(ids, list) or not all(isinstance(i, int) and not isinstance(i, bool) for i in ids):
+        raise ValueError("ids must be a list of integers")
+    return _json({"model": model, "deleted": index.delete(ids)})
+
+
+@app.route("/index/save", methods=["POST"])
+def index_save():
+    """Write the index, ids and tombstones kept, to the path it was opened from."""
+    s = get_server()
+    body = request.get_json(force=True, silent=True) or {}
+    model, index = _writable_index(s, body)
+    if index is None:
+        return _forbidden(model)
+    hdr = index.save()
+    return _json({"model": model, "path": index.path, "count": int(hdr["count"])})
+
+
 @app.route("/search", methods=["POST"])
 def search():
     """The ``k`` nearest rows of the model's vector index (``extra.index``) per query. The queries are the
     vectors /embed gives for the same body, or ``{"model", "vectors": [[...]]}``; a cosine index gets them
-    L2-normalised in fp32. ``"k"`` (JSON field or query argument): 1..128, default 10."""
+    L2-normalised in fp32. ``"k"`` (JSON field or query argument): 1..128, default 10. ``"filter": {"mask",
+    "value"}`` or ``"tag": t`` restricts the answer to the rows whose tag passes ``(tag & mask) == value``."""
     from ..search import check_k, check_queries, normalize_rows
     s = get_server()
     body = {}
@@ -444,8 +540,9 @@ def search():
         q = check_queries(vec, index.dim)
     if index.metric == "cosine":
         q = normalize_rows(q)
+    filt = _search_filter(body)
     with phase("search"):
-        scores, ids = index.search(q, k)
+        scores, ids = index.search(q, k) if filt is None else index.search(q, k, filter=filt)
     dt = (time.perf_counter() - t0) * 1e3
     if "application/octet-stream" in request.headers.get("Accept", ""):
         out = np.empty(ids.shape, dtype=[("id", "<i4"), ("score", "<f4")])

@@ -506,7 +506,8 @@ class ModelServer:
                 dim, want = read_header(path)["dim"], int(backend.embed["dim"])
                 if dim != want:
                     raise RuntimeError(f"{name}: index {path} has dim {dim}, the backend's embed.dim is {want}")
-                self._indexes[name] = open_index(path, self.backend, self.settings.devices[0])
+                self._indexes[name] = open_index(path, self.backend, self.settings.devices[0],
+                                                 reserve=int(self.spec(name).extra.get("index_reserve", 0)))
             return self._indexes[name]
 
     def close(self) -> None:
