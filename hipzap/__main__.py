@@ -9,6 +9,7 @@
     python -m hipzap upload --models-dir ./models  # scripts/upload_models.py parity
     python -m hipzap index --vectors v.npy [--labels labels.json] [--metric cosine|ip] --out x.hzidx  # vector index
     python -m hipzap index --embed-plan bert.pth.emb.hzplan --ids ids.npy [--mask mask.npy] --out x.hzidx
+    python -m hipzap index --from-index a.hzidx --dtype fp8 --out b.hzidx  # requantise a bf16 index (ids kept)
     python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
@@ -107,9 +108,15 @@ def cmd_index(a):
     plan gives for rows of token ids (on the GPU, torch-free)."""
     import numpy as np
 
-    from .search import write_index
+    from .search import convert_index, write_index
+    if a.from_index is not None:
+        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask:
+            raise SystemExit("index: --from-index takes only --dtype and --out")
+        hdr = convert_index(a.from_index, a.out, a.dtype)
+        print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": "labels" in hdr}))
+        return
     if (a.vectors is None) == (a.embed_plan is None):
-        raise SystemExit("index: give one of --vectors and --embed-plan")
+        raise SystemExit("index: give one of --vectors, --embed-plan and --from-index")
     embed, model = None, a.model
     if a.vectors is not None:
         if a.ids or a.mask:
@@ -129,7 +136,7 @@ def cmd_index(a):
         model = model or be.meta.get("model")
     labels = json.load(open(a.labels)) if a.labels else None
     tags = np.load(a.tags, allow_pickle=False) if a.tags else None
-    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags)
+    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
@@ -207,6 +214,9 @@ def main(argv=None):
     ix.add_argument("--labels", default=None, help="a JSON list of N strings")
     ix.add_argument("--tags", default=None, help="an .npy of N uint32 tag words (search filters test them): a version-2 file")
     ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")
+    ix.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D % 16 == 0)")
+    ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept)")
     ix.add_argument("--model", default=None, help="free text kept in the header")
     ix.add_argument("--device", type=int, default=0)
     ix.add_argument("--out", required=True)

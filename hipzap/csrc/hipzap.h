@@ -468,6 +468,16 @@ typedef struct HzSearchFilterParams {
   unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
 } HzSearchFilterParams;
 int hz_search_fscan_launch(const HzSearchFilterParams* p, hipStream_t st);
+// quantised scan (HZ_K_SEARCH_QSCAN): the filtered scan over rows of OCP e4m3fn bytes, one fp32 scale per row.
+// `f.s.corpus` points at uint8 [N][ldc] (ldc in bytes, ldc % 16 == 0, D % 16 == 0, 16 <= D <= 2048).
+//   score(q, r) = fl32(scales[r] * sum_i q_i * decode(code_ri)), the sum as in HZ_K_SEARCH_SCAN
+// Its bits depend on the query's D values, the row's D codes and the row's scale only. The codes and the scale
+// of a row that fails for every query are never loaded. HZ_K_SEARCH_MERGE reduces the lists.
+typedef struct HzSearchQuantParams {
+  HzSearchFilterParams f;        // the filtered scan's block, unchanged (live is required)
+  const float* scales;           // fp32 [N], 4-B aligned
+} HzSearchQuantParams;
+int hz_search_qscan_launch(const HzSearchQuantParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
@@ -496,7 +506,7 @@ void hz_index_close(void* idx);
 // rows rounded up to whole tiles. Ids are row positions, never reused. A mutation excludes every search: it
 // holds all context mutexes and synchronises its copies before it returns.
 void* hz_index_open2(const char* path, int device, int nctx, long long reserve_rows);
-// out[8] = {capacity, live rows, tags present, filtered programs in use, the filtered programs' N, 0, 0, 0};
+// out[8] = {capacity, live rows, tags present, filtered programs in use, the filtered programs' N, dtype, 0, 0};
 // hz_index_describe's out[0] is the current count and out[7] the capacity
 int hz_index_describe2(void* idx, uint64_t* out);
 // filt: host [Q][2] u32 {mask, value} or NULL. A never-mutated index without filt runs scan + merge (N = count)
@@ -508,6 +518,15 @@ int hz_index_delete(void* idx, const int* ids, long long n, long long* newly_del
 int hz_index_set_tags(void* idx, const int* ids, const unsigned* tags, long long n);
 // the first n rows / tag words / ceil(n / 32) live words to host memory (any pointer may be NULL)
 int hz_index_read_state(void* idx, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n);
+// an fp8 index (a version-3 .hzidx): rows are [count][dim] e4m3fn bytes, and "scales_off" of the
+// JSON header names a 4096-aligned block of count fp32 scales after them (tags and bitmap, when present, follow).
+// hz_index_open2 opens it; every search replays H2D, HZ_K_SEARCH_QSCAN, merge, two D2H. hz_index_describe2's
+// out[5] is the dtype (0 bf16, 1 fp8_e4m3). The _q calls are hz_index_add / hz_index_read_state for such an
+// index; each form refuses (-26, hz_index_last_error names both dtypes) an index of the other dtype.
+int hz_index_add_q(void* idx, const unsigned char* codes, const float* scales, long long n, const unsigned* tags_or_null,
+                   long long* first_id_out);
+int hz_index_read_state_q(void* idx, unsigned char* codes_out, float* scales_out, unsigned* tags_out, unsigned* live_out,
+                          long long n);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -687,7 +706,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(RESIZE_PATCHIFY, 30, HzResizeParams, hz_resize_patchify_op, VISION)   \
   X(SEARCH_SCAN, 31, HzSearchParams, hz_search_scan_op, SEARCH)           \
   X(SEARCH_MERGE, 32, HzSearchParams, hz_search_merge_op, SEARCH)         \
-  X(SEARCH_FSCAN, 33, HzSearchFilterParams, hz_search_fscan_op, SEARCH)
+  X(SEARCH_FSCAN, 33, HzSearchFilterParams, hz_search_fscan_op, SEARCH)   \
+  X(SEARCH_QSCAN, 34, HzSearchQuantParams, hz_search_qscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -13,6 +13,10 @@
 // adds inside the last tile change device data only and keep every captured program; an add that crosses
 // a tile boundary, or a growth (new allocations), destroys the programs, which are re-captured on next use.
 // A mutation holds every context's mutex and synchronises its copies before it releases them.
+//
+// An fp8 index (a version-3 file): the rows are e4m3fn bytes and beside them lies one fp32 scale
+// per row. It ALWAYS replays the quantised-scan program of its (Q, k) -- H2D, qscan, merge, two D2H -- with the
+// filtered programs' N and mask 0 / value 0 when there is no filter; the invalidation rules are the same.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -62,10 +66,13 @@ uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
 // the unsigned integer value of `"key": <digits>` in the JSON header. The writer puts these keys last, after
 // the labels, so the LAST occurrence is the key itself even when a label spells the same word
-bool json_u64(const std::string& js, const char* key, uint64_t* out) {
+// (`strict`: the colon must follow the key at once -- a version-3 file may lack the key, and a label that
+// spells it is followed by a comma or a bracket)
+bool json_u64(const std::string& js, const char* key, uint64_t* out, bool strict = false) {
   const std::string k = std::string("\"") + key + "\"";
   size_t at = js.rfind(k);
   if (at == std::string::npos) return false;
+  if (strict && (at + k.size() >= js.size() || js[at + k.size()] != ':')) return false;
   at = js.find(':', at + k.size());
   if (at == std::string::npos) return false;
   ++at;
@@ -82,7 +89,9 @@ struct Index {
   uint64_t live_count = 0;
   bool mutated = false;               // the unfiltered program (N = the file's count, all live) no longer holds
   bool has_tags = false;
-  unsigned short* rows = nullptr;
+  bool fp8 = false;                   // a version-3 file: e4m3fn byte rows and `scales`
+  unsigned short* rows = nullptr;     // bf16 [cap][dim], or uint8 [cap][dim] of an fp8 index
+  float* scales = nullptr;            // device, cap floats (fp8 only)
   unsigned* live = nullptr;           // device, cap / 32 words
   unsigned* tags = nullptr;           // device, cap words
   std::vector<uint32_t> live_host, tags_host;  // mirrors, sized like the device buffers
@@ -103,9 +112,11 @@ struct Index {
     if (rows) (void)hipFree(rows);
     if (live) (void)hipFree(live);
     if (tags) (void)hipFree(tags);
+    if (scales) (void)hipFree(scales);
   }
 
-  uint64_t row_bytes() const { return cap * h.dim * 2; }
+  uint64_t esize() const { return fp8 ? 1 : 2; }  // bytes per stored element
+  uint64_t row_bytes() const { return cap * h.dim * esize(); }
   uint64_t scan_rows() const { return round_up(count, kTile); }  // the filtered programs' N
 
   void drop_programs() {  // the caller holds every context's mutex
@@ -136,7 +147,8 @@ struct Index {
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
-    HzSearchFilterParams f{};
+    HzSearchQuantParams qp{};
+    HzSearchFilterParams& f = qp.f;
     HzSearchParams& p = f.s;
     p.corpus = rows;
     p.queries = c.q_dev;
@@ -152,12 +164,14 @@ struct Index {
     f.tags = tags;
     f.filt = reinterpret_cast<const unsigned*>(c.slot_dev);
     f.live_bytes = cap / 8;
+    qp.scales = scales;
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4, qb = (size_t)Q * h.dim * 4;
     int rc;
     if (filtered) {
       rc = hz_prog_add_memcpy(g, c.slot_dev, c.slot_host, kFiltBytes + qb, 0);
-      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_FSCAN, &f, sizeof(f), 0);
+      if (!rc) rc = fp8 ? hz_prog_add_kernel(g, HZ_K_SEARCH_QSCAN, &qp, sizeof(qp), 0)
+                        : hz_prog_add_kernel(g, HZ_K_SEARCH_FSCAN, &f, sizeof(f), 0);
     } else {
       rc = hz_prog_add_memcpy(g, c.q_dev, c.q_host, qb, 0);
       if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_SCAN, &p, sizeof(p), 0);
@@ -179,10 +193,12 @@ struct Index {
   int reallocate(uint64_t new_cap, hipStream_t st) {
     unsigned short* nrows = nullptr;
     unsigned *nlive = nullptr, *ntags = nullptr;
+    float* nscales = nullptr;
     const uint64_t cand_bytes = hz_search_scratch_bytes((long long)new_cap, HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
     if (!cand_bytes) return -21;  // 2^31 rows and above
     std::vector<unsigned long long*> ncand(ctx.size(), nullptr);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * h.dim * 2) == hipSuccess;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * h.dim * esize()) == hipSuccess;
+    if (fp8) ok = ok && hipMalloc(reinterpret_cast<void**>(&nscales), new_cap * 4) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&nlive), new_cap / 8) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&ntags), new_cap * 4) == hipSuccess;
     for (size_t i = 0; ok && i < ctx.size(); ++i)
@@ -190,18 +206,19 @@ struct Index {
     ok = ok && hipMemsetAsync(nlive, 0, new_cap / 8, st) == hipSuccess;
     ok = ok && hipMemsetAsync(ntags, 0, new_cap * 4, st) == hipSuccess;
     if (ok && rows) {
-      ok = hipMemcpyAsync(nrows, rows, count * h.dim * 2, hipMemcpyDeviceToDevice, st) == hipSuccess;
+      ok = hipMemcpyAsync(nrows, rows, count * h.dim * esize(), hipMemcpyDeviceToDevice, st) == hipSuccess;
+      if (fp8) ok = ok && hipMemcpyAsync(nscales, scales, count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
       ok = ok && hipMemcpyAsync(ntags, tags, count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
       ok = ok && hipMemcpyAsync(nlive, live, round_up(count, 32) / 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
     }
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
     if (!ok) {
-      (void)hipFree(nrows), (void)hipFree(nlive), (void)hipFree(ntags);
+      (void)hipFree(nrows), (void)hipFree(nlive), (void)hipFree(ntags), (void)hipFree(nscales);
       for (auto* p : ncand) (void)hipFree(p);
       return -22;
     }
-    (void)hipFree(rows), (void)hipFree(live), (void)hipFree(tags);
-    rows = nrows, live = nlive, tags = ntags, cap = new_cap;
+    (void)hipFree(rows), (void)hipFree(live), (void)hipFree(tags), (void)hipFree(scales);
+    rows = nrows, live = nlive, tags = ntags, scales = nscales, cap = new_cap;
     for (size_t i = 0; i < ctx.size(); ++i) {
       (void)hipFree(ctx[i]->cand);
       ctx[i]->cand = ncand[i];
@@ -244,25 +261,39 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version == 2 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && (h.version == 2 || h.version == 3) && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version != 1 && h.version != 2) return fail("index: unknown format version " + std::to_string(h.version));
+  if (h.version < 1 || h.version > 3) return fail("index: unknown format version " + std::to_string(h.version));
+  const bool fp8 = h.version == 3;
+  if (fp8 && (h.dim < 16 || h.dim % 16 || h.dim > 2048))
+    return fail("index: dim of an fp8 index must be a multiple of 16 in 16..2048");
   if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
   if (h.count < 1 || h.count >= (1ull << 31)) return fail("index: count must be in 1..2^31-1");
   if (h.metric > HZ_INDEX_IP) return fail("index: unknown metric");
-  const uint64_t bytes = h.count * h.dim * 2, fsize = (uint64_t)sb.st_size;
+  const uint64_t bytes = h.count * h.dim * (fp8 ? 1 : 2), fsize = (uint64_t)sb.st_size;
   if (h.data_off % 4096 || h.data_off < sizeof(h) + h.json_len || h.data_off + bytes > fsize)
     return fail("index: row block outside the file");
   uint64_t tags_off = 0, live_off = 0;
   const uint64_t tag_bytes = h.count * 4, live_bytes = round_up(h.count, 32) / 8;
-  if (h.version == 2) {
-    if (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off))
+  uint64_t scales_off = 0, after_rows = h.data_off + bytes;
+  bool blocks = h.version == 2;  // tags and a bitmap in the file
+  if (fp8) {
+    if (!json_u64(js, "scales_off", &scales_off, true)) return fail("index: a version-3 file without scales_off");
+    if (scales_off % 4096 || scales_off < after_rows || scales_off > fsize || h.count * 4 > fsize - scales_off)
+      return fail("index: scales block outside the file");
+    after_rows = scales_off + h.count * 4;
+    const bool t = json_u64(js, "tags_off", &tags_off, true), l = json_u64(js, "live_off", &live_off, true);
+    if (t != l) return fail("index: a version-3 file with only one of tags_off / live_off");
+    blocks = t;
+  }
+  if (blocks) {
+    if (!fp8 && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
       return fail("index: a version-2 file without tags_off / live_off");
-    if (tags_off % 4096 || live_off % 4096 || tags_off < h.data_off + bytes || live_off < h.data_off + bytes ||
+    if (tags_off % 4096 || live_off % 4096 || tags_off < after_rows || live_off < after_rows ||
         tags_off > fsize || tag_bytes > fsize - tags_off || live_off > fsize || live_bytes > fsize - live_off)
       return fail("index: tags or live block outside the file");
   }
@@ -271,6 +302,7 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
   idx->device = device;
   idx->h = h;
   idx->count = h.count;
+  idx->fp8 = fp8;
   if (hz_search_code_warm()) return fail("index: device code load failed");
   for (int i = 0; i < nctx; ++i) {
     auto c = std::make_unique<Ctx>();
@@ -292,10 +324,10 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
   const uint64_t cap = round_up(std::max<uint64_t>(h.count, (uint64_t)reserve_rows), kTile);
   if (idx->reallocate(cap, st)) return fail("index: device allocation failed");
   const uint64_t words = live_bytes / 4;
-  if (h.version == 2) {
-    const uint64_t off[3] = {h.data_off, tags_off, live_off}, len[3] = {bytes, tag_bytes, live_bytes};
-    void* dst[3] = {idx->rows, idx->tags, idx->live};
-    if (hz_upload_file(path, 3, off, len, dst, st)) return fail(std::string("index: ") + hz_plan_last_error());
+  if (blocks) {
+    const uint64_t off[4] = {h.data_off, tags_off, live_off, scales_off}, len[4] = {bytes, tag_bytes, live_bytes, h.count * 4};
+    void* dst[4] = {idx->rows, idx->tags, idx->live, idx->scales};
+    if (hz_upload_file(path, fp8 ? 4 : 3, off, len, dst, st)) return fail(std::string("index: ") + hz_plan_last_error());
     bool ok = hipStreamSynchronize(st) == hipSuccess;
     // the mirrors come back from the device copy (one read of the file); bits past the count are cleared
     ok = ok && hipMemcpy(idx->tags_host.data(), idx->tags, tag_bytes, hipMemcpyDeviceToHost) == hipSuccess;
@@ -308,9 +340,9 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
     idx->has_tags = true;
     idx->mutated = idx->live_count < h.count;
   } else {
-    const uint64_t off = h.data_off;
-    void* dst = idx->rows;
-    if (hz_upload_file(path, 1, &off, &bytes, &dst, st)) return fail(std::string("index: ") + hz_plan_last_error());
+    const uint64_t off[2] = {h.data_off, scales_off}, len[2] = {bytes, h.count * 4};
+    void* dst[2] = {idx->rows, idx->scales};
+    if (hz_upload_file(path, fp8 ? 2 : 1, off, len, dst, st)) return fail(std::string("index: ") + hz_plan_last_error());
     for (uint64_t r = 0; r < h.count; ++r) idx->live_host[r >> 5] |= 1u << (r & 31);
     idx->live_count = h.count;
     if (push_words(idx->live, idx->live_host, 0, words, st) || hipStreamSynchronize(st) != hipSuccess)
@@ -325,7 +357,7 @@ int hz_index_describe(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
-  uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4;
+  uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4 + (x->fp8 ? x->cap * 4 : 0);
   for (auto& c : x->ctx) {
     progs += c->progs.size();
     dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf;
@@ -339,7 +371,7 @@ int hz_index_describe2(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
-  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), 0, 0, 0};
+  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->fp8 ? 1u : 0u, 0, 0};
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
@@ -354,7 +386,7 @@ int hz_index_search_filtered(void* h, int ctx, const float* queries, const unsig
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
-  const bool filtered = x->mutated || filt != nullptr;
+  const bool filtered = x->fp8 || x->mutated || filt != nullptr;
   bool fresh = false;
   HzProgram g = x->program(c, Q, k, filtered, &fresh);
   if (!g) return -11;
@@ -380,9 +412,12 @@ int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float*
   return hz_index_search_filtered(h, ctx, queries, nullptr, Q, k, out_score, out_id);
 }
 
-int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const unsigned* tags, long long* first_id) {
-  Index* x = static_cast<Index*>(h);
-  if (!x || !rows_bf16 || n < 1) return -1;
+}  // extern "C"
+
+namespace {
+
+// hz_index_add / hz_index_add_q: `data` holds n rows in the index's own format, `scales` n floats (fp8) or NULL
+int add_rows(Index* x, const void* data, const float* scales, long long n, const unsigned* tags, long long* first_id) {
   AllLocked all(*x);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   const uint64_t first = x->count, last = first + (uint64_t)n;
@@ -396,7 +431,9 @@ int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const un
   }
   // rows and tags first: above `count` they are dead, so a failure here leaves nothing a search can see
   for (uint64_t r = first; r < last; ++r) x->tags_host[r] = tags ? tags[r - first] : 0u;
-  int rc = (int)hipMemcpyAsync(x->rows + first * x->h.dim, rows_bf16, (uint64_t)n * x->h.dim * 2, hipMemcpyHostToDevice, st);
+  const uint64_t rb = x->h.dim * x->esize();
+  int rc = (int)hipMemcpyAsync(reinterpret_cast<char*>(x->rows) + first * rb, data, (uint64_t)n * rb, hipMemcpyHostToDevice, st);
+  if (!rc && scales) rc = (int)hipMemcpyAsync(x->scales + first, scales, (uint64_t)n * 4, hipMemcpyHostToDevice, st);
   if (!rc) rc = push_words(x->tags, x->tags_host, first, last, st);
   if (!rc) rc = (int)hipStreamSynchronize(st);
   if (rc) return rc;
@@ -419,6 +456,30 @@ int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const un
   if (x->scan_rows() != scan_before) x->drop_programs();  // the filtered programs hold N and ntile by value
   if (first_id) *first_id = (long long)first;
   return 0;
+}
+
+int wrong_dtype(const Index* x, const char* call, const char* takes) {
+  g_err = std::string("index: ") + call + " takes " + takes + " rows, the index holds " + (x->fp8 ? "fp8_e4m3" : "bf16");
+  return -26;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const unsigned* tags, long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !rows_bf16 || n < 1) return -1;
+  if (x->fp8) return wrong_dtype(x, "hz_index_add", "bf16");
+  return add_rows(x, rows_bf16, nullptr, n, tags, first_id);
+}
+
+int hz_index_add_q(void* h, const unsigned char* codes, const float* scales, long long n, const unsigned* tags,
+                   long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !codes || !scales || n < 1) return -1;
+  if (!x->fp8) return wrong_dtype(x, "hz_index_add_q", "fp8_e4m3");
+  return add_rows(x, codes, scales, n, tags, first_id);
 }
 
 int hz_index_delete(void* h, const int* ids, long long n, long long* newly_deleted) {
@@ -468,17 +529,41 @@ int hz_index_set_tags(void* h, const int* ids, const unsigned* tags, long long n
   return rc;
 }
 
-// the first `n` (<= count) rows, tag words and ceil(n / 32) live words back to the host (for save); any may be NULL
-int hz_index_read_state(void* h, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n) {
-  Index* x = static_cast<Index*>(h);
-  if (!x || n < 0) return -1;
+}  // extern "C"
+
+namespace {
+
+// the first `n` (<= count) rows, scales (fp8), tag words and ceil(n / 32) live words back to the host (for save)
+int read_state(Index* x, void* rows_out, float* scales_out, unsigned* tags_out, unsigned* live_out, long long n) {
   AllLocked all(*x);
   if ((uint64_t)n > x->count) return -20;
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   if (tags_out) std::memcpy(tags_out, x->tags_host.data(), (size_t)n * 4);
   if (live_out) std::memcpy(live_out, x->live_host.data(), (size_t)(((uint64_t)n + 31) / 32) * 4);
-  if (rows_out && n) return (int)hipMemcpy(rows_out, x->rows, (uint64_t)n * x->h.dim * 2, hipMemcpyDeviceToHost);
-  return 0;
+  int rc = 0;
+  if (scales_out && n) rc = (int)hipMemcpy(scales_out, x->scales, (uint64_t)n * 4, hipMemcpyDeviceToHost);
+  if (!rc && rows_out && n) rc = (int)hipMemcpy(rows_out, x->rows, (uint64_t)n * x->h.dim * x->esize(), hipMemcpyDeviceToHost);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+// any output pointer may be NULL
+int hz_index_read_state(void* h, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || n < 0) return -1;
+  if (x->fp8) return wrong_dtype(x, "hz_index_read_state", "bf16");
+  return read_state(x, rows_out, nullptr, tags_out, live_out, n);
+}
+
+int hz_index_read_state_q(void* h, unsigned char* codes_out, float* scales_out, unsigned* tags_out, unsigned* live_out,
+                          long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || n < 0) return -1;
+  if (!x->fp8) return wrong_dtype(x, "hz_index_read_state_q", "fp8_e4m3");
+  return read_state(x, codes_out, scales_out, tags_out, live_out, n);
 }
 
 void hz_index_close(void* h) { delete static_cast<Index*>(h); }

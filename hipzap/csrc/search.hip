@@ -2,8 +2,9 @@
 //   * search_scan  — one workgroup per tile of HZ_SEARCH_TILE rows: every row is read once and scored
 //                    against all Q queries of the launch (resident in LDS); the tile's best k per query
 //   * search_fscan — the scan over the rows that pass a live bit and a per-query tag predicate
+//   * search_qscan — the filtered scan over OCP e4m3fn byte rows with one fp32 scale per row
 //   * search_merge — one workgroup per query: ntile x k candidates -> the final k, best first
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m for the reasoning.
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n for the reasoning.
 #include <stdio.h>
 
 #include "common.h"
@@ -246,6 +247,155 @@ __global__ __launch_bounds__(T) void search_fscan_kernel(const HzSearchFilterPar
   }
 }
 
+// ------------------------------------------------------------------------------------ quantised scan
+// search_fscan_kernel's structure over rows of OCP e4m3fn bytes with one fp32 scale per row
+// (HzSearchQuantParams; always with a live bitmap, tags and filter optional). Staging is the filtered scan's;
+// after the pass bits are known, thread t reads scales[row0 + t] into LDS iff row t passes for some query
+// (one coalesced read of at most 1 KB), so neither the bytes nor the scale of a dead row is ever loaded:
+// they may be NaN codes and NaN or inf scales. Lane l holds the 16-B chunks l, l + 64 of a row: 16 elements
+// each, NC = 1 up to D = 1024 and 2 up to 2048. A group's bytes are decoded to fp32 ONCE, before the loop
+// over the queries (v_cvt_pk_f32_fp8: exact for the 254 finite codes, subnormals and -0 included).
+// score(q, r): every lane runs one fmaf chain over its elements in ascending column order from +0 (a lane
+// past the row's end keeps +0), the 64 sums meet in the xor butterfly, and the sum is multiplied ONCE, in
+// fp32, by scales[r]; then orderable().
+// CONTRACT: the bits of score(q, r) depend on the query's D values, the row's D codes and the row's scale,
+// and on nothing else: not on N, Q, k, the row's position or tile, the other queries, the filter, or what
+// dead rows hold. Ranking, candidate layout and zero fill are search_fscan_kernel's.
+// Addresses beyond the filtered scan's: the byte rows at (row0 + r) * ldc + chunk * 16 under chunk < D / 16
+// and row < N, scales[row0 + t] under t < rows.
+__device__ __forceinline__ void decode16(const u32x4 v, float* f) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false);  // bytes 0, 1 of the word
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);   // bytes 2, 3
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+}
+
+template <int NC>
+__global__ __launch_bounds__(T) void search_qscan_kernel(const HzSearchQuantParams qp) {
+  const HzSearchFilterParams& fp = qp.f;
+  const HzSearchParams& p = fp.s;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* qs = lds;                                              // [Q][D]
+  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);  // [Q][T]
+  unsigned* pmask = sc + p.Q * T;                               // [T]: pass bits
+  unsigned* lv = pmask + T;                                     // [T / 32] live words of the tile
+  unsigned* fl = lv + T / 32;                                   // [Q][2]
+  float* scl = reinterpret_cast<float*>(fl + 2 * p.Q);          // [T]: the scales of the passing rows
+  const unsigned char* rows8 = reinterpret_cast<const unsigned char*>(p.corpus);
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int nch = p.D >> 4;
+  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 1024 && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  for (int i = t; i < p.Q * (p.D >> 2); i += T)
+    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(p.queries)[i];
+  unsigned tag = 0u;
+  if (fp.tags && t < rows && HZ_DCHECK(row0 + t < (long)p.N)) tag = fp.tags[row0 + t];
+  if (t < T / 32) {
+    const long word = (row0 >> 5) + t;
+    lv[t] = (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)fp.live_bytes)) ? fp.live[word] : 0u;
+  }
+  if (fp.filt && t < 2 * p.Q && HZ_DCHECK(t < 2 * HZ_SEARCH_MAX_Q)) fl[t] = fp.filt[t];
+  __syncthreads();
+  {
+    unsigned bits = 0u;
+    if (t < rows && ((lv[t >> 5] >> (t & 31)) & 1u)) {
+      bits = (1u << p.Q) - 1u;  // Q <= 16
+      if (fp.filt) {
+        bits = 0u;
+        for (int q = 0; q < p.Q; ++q) bits |= (unsigned)((tag & fl[2 * q]) == fl[2 * q + 1]) << q;
+      }
+    }
+    pmask[t] = bits;
+    float s = 0.f;
+    if (bits != 0u && HZ_DCHECK(t < rows && row0 + t < (long)p.N)) s = qp.scales[row0 + t];
+    scl[t] = s;
+  }
+  __syncthreads();
+
+  for (int g = 0; g < 64; g += ROWS) {  // wave-uniform bounds
+    const int r0 = w * 64 + g;
+    if (r0 >= rows) break;
+    unsigned pm[ROWS], any = 0u;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {  // r0 + r < T: rows past the tile's end have pass bits 0
+      pm[r] = __builtin_amdgcn_readfirstlane(pmask[r0 + r]);
+      any |= pm[r];
+    }
+    if (any == 0u) {  // scalar: nothing of this group is loaded or scored
+      if (lane < ROWS && r0 + lane < rows)
+        for (int q = 0; q < p.Q; ++q) sc[q * T + r0 + lane] = 0u;
+      continue;
+    }
+    u32x4 v[ROWS][NC];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        v[r][c] = u32x4{0u, 0u, 0u, 0u};
+        if (pm[r] != 0u && c * 64 + lane < nch && HZ_DCHECK(row0 + r0 + r < (long)p.N))
+          v[r][c] = *reinterpret_cast<const u32x4*>(rows8 + (row0 + r0 + r) * p.ldc + (c * 64 + lane) * 16);
+      }
+    float f[ROWS][NC][16], rs[ROWS];  // decoded once for all queries
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      rs[r] = scl[r0 + r];  // every lane reads the same word: an LDS broadcast
+#pragma unroll
+      for (int c = 0; c < NC; ++c) decode16(v[r][c], f[r][c]);
+    }
+    for (int q = 0; q < p.Q; ++q) {
+      float acc[ROWS];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        if (c * 64 + lane < nch) {
+          const f32x4* qv4 = reinterpret_cast<const f32x4*>(qs + q * p.D + (c * 64 + lane) * 16);
+          float qv[16];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const f32x4 x = qv4[i];
+            qv[4 * i] = x[0], qv[4 * i + 1] = x[1], qv[4 * i + 2] = x[2], qv[4 * i + 3] = x[3];
+          }
+#pragma unroll
+          for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[r] = fmaf(qv[e], f[r][c][e], acc[r]);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const float s = warp_sum(acc[r]) * rs[r];
+        if (lane == r && r0 + r < rows) sc[q * T + r0 + r] = ((pm[r] >> q) & 1u) ? orderable(s) : 0u;
+      }
+    }
+  }
+  __syncthreads();
+
+  for (int q = 0; q < p.Q; ++q) {
+    unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
+    const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
+    const unsigned mine = t < rows ? sc[q * T + t] : 0u;
+    int rank = 0, np = 0;
+    for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
+      const unsigned o = sc[q * T + j];
+      rank += (o > mine) || (o == mine && j < t);
+      np += o != 0u;
+    }
+    if (mine != 0u && rank < p.k && slot_ok)
+      out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
+    if (t >= np && t < p.k && slot_ok) out[t] = 0ull;  // the slots past the passing rows (k <= 128 < T)
+  }
+}
+
 // ------------------------------------------------------------------------------------------ merge
 // Query q's ntile * k keys, MERGE_THREADS * MERGE_E per round. `best` holds the k best so far, best first
 // (zeros at the start). A key survives a round iff it is above best[k - 1]; the survivors are compacted
@@ -381,14 +531,16 @@ int raise_lds_limit() {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
   if (done[d]) return 0;
-  const void* fns[8] = {reinterpret_cast<const void*>(&search_scan_kernel<1>),
+  const void* fns[10] = {reinterpret_cast<const void*>(&search_scan_kernel<1>),
                         reinterpret_cast<const void*>(&search_scan_kernel<2>),
                         reinterpret_cast<const void*>(&search_scan_kernel<3>),
                         reinterpret_cast<const void*>(&search_scan_kernel<4>),
                         reinterpret_cast<const void*>(&search_fscan_kernel<1>),
                         reinterpret_cast<const void*>(&search_fscan_kernel<2>),
                         reinterpret_cast<const void*>(&search_fscan_kernel<3>),
-                        reinterpret_cast<const void*>(&search_fscan_kernel<4>)};
+                        reinterpret_cast<const void*>(&search_fscan_kernel<4>),
+                        reinterpret_cast<const void*>(&search_qscan_kernel<1>),
+                        reinterpret_cast<const void*>(&search_qscan_kernel<2>)};
   for (const void* f : fns) HZ_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   done[d] = true;
   return 0;
@@ -434,6 +586,32 @@ extern "C" int hz_search_fscan_launch(const HzSearchFilterParams* pp, hipStream_
     case 3: hipLaunchKernelGGL((search_fscan_kernel<3>), dim3(p.ntile), dim3(T), lds, st, f); break;
     default: hipLaunchKernelGGL((search_fscan_kernel<4>), dim3(p.ntile), dim3(T), lds, st, f); break;
   }
+  return (int)hipGetLastError();
+}
+
+// The filtered launcher's refusals with the byte rows' dimension rules: -16 D % 16, -17 D < 16, -18 D > 2048,
+// -19 ldc < D, -23 ldc % 16 (ldc in bytes), -24 scales null, -25 scales not 4-byte aligned.
+extern "C" int hz_search_qscan_launch(const HzSearchQuantParams* pp, hipStream_t st) {
+  HzSearchQuantParams qp = *pp;
+  HzSearchFilterParams& f = qp.f;
+  HzSearchParams& p = f.s;
+  if (p.D < 16) return -17;
+  if (p.D % 16) return -16;
+  if (p.D > 2048) return -18;
+  if (p.ldc < p.D) return -19;
+  if (p.ldc % 16) return -23;
+  if (const int rc = search_check(p)) return rc;
+  if (!f.live || (reinterpret_cast<uintptr_t>(f.live) & 3)) return -12;
+  if (f.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -13;
+  if (f.filt && !f.tags) return -14;
+  if ((reinterpret_cast<uintptr_t>(f.tags) & 3) || (reinterpret_cast<uintptr_t>(f.filt) & 3)) return -15;
+  if (!qp.scales) return -24;
+  if (reinterpret_cast<uintptr_t>(qp.scales) & 3) return -25;
+  // the filtered scan's LDS plus the tile's scales [T]: <= 144 KiB + 1184 B + 1 KiB
+  const size_t lds = ((size_t)p.Q * p.D + (size_t)p.Q * T + T + T / 32 + 2 * (size_t)p.Q + T) * 4;
+  if (const int rc = raise_lds_limit()) return rc;
+  if (p.D <= 1024) hipLaunchKernelGGL((search_qscan_kernel<1>), dim3(p.ntile), dim3(T), lds, st, qp);
+  else hipLaunchKernelGGL((search_qscan_kernel<2>), dim3(p.ntile), dim3(T), lds, st, qp);
   return (int)hipGetLastError();
 }
 

@@ -4,7 +4,9 @@
 of ``tile_rows()`` corpus rows, all queries of the launch resident in LDS, the tile's best ``k`` keys per
 query into ``cand``) and ``HZ_K_SEARCH_MERGE`` (one workgroup per query, ``ntile x k`` keys -> the final
 ``k``). ``HZ_K_SEARCH_FSCAN`` (``FilterScanParams``: the same block plus a live bitmap, per-row tags and
-per-query ``{mask, value}`` filters) is the scan over the rows that pass. torch-free: indexes (:mod:`hipzap.search`) are served without it."""
+per-query ``{mask, value}`` filters) is the scan over the rows that pass. ``HZ_K_SEARCH_QSCAN``
+(``QuantScanParams``: that block plus one fp32 scale per row) is the filtered scan over rows of OCP e4m3fn bytes.
+torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -35,6 +37,16 @@ class FilterScanParams(C.Structure):
         return SearchParams.from_buffer_copy(self)
 
 
+@N.params_of("HZ_K_SEARCH_QSCAN")
+class QuantScanParams(C.Structure):
+    """HzSearchQuantParams: the fields of ``FilterScanParams`` (``corpus``: uint8 rows, ``ldc`` in bytes), then
+    ``scales`` (fp32 [N])."""
+    _fields_ = FilterScanParams._fields_ + [("scales", C.c_void_p)]
+
+    def scan_params(self) -> SearchParams:
+        return SearchParams.from_buffer_copy(self)
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -42,6 +54,7 @@ def _sigs(lib):
     N._sig(lib, "hz_search_scan_launch", C.c_int, C.POINTER(SearchParams), P)
     N._sig(lib, "hz_search_merge_launch", C.c_int, C.POINTER(SearchParams), P)
     N._sig(lib, "hz_search_fscan_launch", C.c_int, C.POINTER(FilterScanParams), P)
+    N._sig(lib, "hz_search_qscan_launch", C.c_int, C.POINTER(QuantScanParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
     N._sig(lib, "hz_index_last_error", C.c_char_p)
     N._sig(lib, "hz_index_open", P, C.c_char_p, C.c_int, C.c_int)
@@ -55,6 +68,8 @@ def _sigs(lib):
     N._sig(lib, "hz_index_delete", C.c_int, P, P, C.c_longlong, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_set_tags", C.c_int, P, P, P, C.c_longlong)
     N._sig(lib, "hz_index_read_state", C.c_int, P, P, P, P, C.c_longlong)
+    N._sig(lib, "hz_index_add_q", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_read_state_q", C.c_int, P, P, P, P, P, C.c_longlong)
 
 
 N._EXTRA_SIGS.append(_sigs)
@@ -83,6 +98,16 @@ def launch_filtered(prm: FilterScanParams, stream: int = 0) -> tuple:
     """Filtered scan then merge on ``stream``: (scan code, merge code); no merge after a refused scan."""
     lib = N.lib()
     rc = lib.hz_search_fscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    sp = prm.scan_params()
+    return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def launch_quant(prm: QuantScanParams, stream: int = 0) -> tuple:
+    """Quantised scan then merge on ``stream``: (scan code, merge code); no merge after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_qscan_launch(C.byref(prm), stream)
     if rc:
         return rc, None
     sp = prm.scan_params()

@@ -9,7 +9,11 @@ length, the row block's offset, count, dim, metric), the JSON header ``{"dim", "
 padding, then the bf16 rows ``[count][dim]`` at a 4096-aligned offset. Version 2 (written when an index has
 tags or deleted rows) adds the JSON keys ``capacity``, ``tags_off`` and ``live_off``: two 4096-aligned blocks
 after the rows, ``count`` uint32 tags and the live bitmap (bit ``r & 31`` of word ``r >> 5``). A version-1
-file opens as all live with zero tags.
+file opens as all live with zero tags. Version 3 is an fp8 index (``dtype`` ``"fp8_e4m3"``): the rows are
+``[count][dim]`` OCP e4m3fn bytes (``dim % 16 == 0``) and the JSON key ``scales_off`` names a 4096-aligned
+block of ``count`` little-endian fp32 scales after them; row r stands for ``scales[r] * decode(codes[r])``
+(:func:`prepare_rows_fp8`). ``capacity``, ``tags_off`` and ``live_off`` are present exactly when version 2
+would have them, their blocks after the scales.
 
 A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
 positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
@@ -34,6 +38,9 @@ from .ops.search import MAX_K, MAX_Q
 MAGIC = b"HZIDX\0\0\1"
 VERSION = 1
 VERSION2 = 2  # version 1 plus the JSON keys capacity / tags_off / live_off and their two blocks
+VERSION3 = 3  # fp8 rows: uint8 codes, the JSON key scales_off and its block; tags / live as in version 2, or absent
+DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3"}  # write_index(dtype=...) -> the header's "dtype"
+FP8 = "fp8_e4m3"
 METRICS = ("cosine", "ip")
 ALIGN = 4096
 HEAD = struct.Struct("<8sIIQQII")  # HzIndexHeader: magic, version, json_len, data_off, count, dim, metric
@@ -49,9 +56,38 @@ def bf16_to_f32(b: np.ndarray) -> np.ndarray:
     return (np.ascontiguousarray(b, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
-def prepare_rows(vectors, metric: str) -> np.ndarray:
-    """fp32 [N, D] -> the bf16 bit patterns (uint16 [N, D]) an index of ``metric`` stores: the checks, the
-    cosine normalisation and the rounding of :func:`write_index` and of ``add`` (one function: the same bits)."""
+def _e4m3_table() -> np.ndarray:
+    """The value of every e4m3fn code, float32 [256]; 0x7F and 0xFF are NaN."""
+    c = np.arange(256)
+    e, m = (c >> 3) & 15, (c & 7).astype(np.float64)
+    mag = np.where(e == 0, m * 2.0 ** -9, (1 + m / 8) * 2.0 ** (e.astype(np.float64) - 7))
+    mag[[0x7F, 0xFF]] = np.nan
+    return np.where(c & 0x80, -mag, mag).astype(np.float32)
+
+
+E4M3 = _e4m3_table()
+E4M3_MAX = 448.0
+_E4M3_POS = E4M3[:127].astype(np.float64)           # the 127 non-negative finite values, ascending
+_E4M3_MID = (_E4M3_POS[:-1] + _E4M3_POS[1:]) / 2     # exact: neighbours differ in their last bit
+
+
+def e4m3_to_f32(codes) -> np.ndarray:
+    """e4m3fn codes (uint8) -> their values, exactly (every finite code is an fp32 value)."""
+    return E4M3[np.asarray(codes, np.uint8)]
+
+
+def to_e4m3(x) -> np.ndarray:
+    """Finite values in [-448, 448] -> OCP e4m3fn codes (uint8), round to nearest even, the subnormals
+    (step 2^-9) included; the sign of a value that rounds to zero is kept. Never 0x7F / 0xFF."""
+    x = np.asarray(x, np.float64)
+    a = np.minimum(np.abs(x), E4M3_MAX)
+    code = np.searchsorted(_E4M3_MID, a, side="left")  # the midpoints below a: a tie lands on the lower code
+    tie = (code < 126) & (_E4M3_MID[np.minimum(code, 125)] == a) & (code & 1 == 1)
+    return (code + tie).astype(np.uint8) | (np.signbit(x).astype(np.uint8) << 7)
+
+
+def _checked_rows(vectors, metric: str, step: int, what: str = "dim") -> np.ndarray:
+    """The checks and the cosine normalisation that every stored format shares -> fp32 [N, D]."""
     v = np.asarray(vectors)
     if v.ndim != 2 or v.dtype.kind != "f":
         raise ValueError(f"vectors must be a float array [N, D], got {v.dtype} {list(v.shape)}")
@@ -59,8 +95,8 @@ def prepare_rows(vectors, metric: str) -> np.ndarray:
     n, d = v.shape
     if metric not in METRICS:
         raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
-    if d < 8 or d % 8 or d > 2048:
-        raise ValueError(f"dim must be a multiple of 8 in 8..2048, got {d}")
+    if d < step or d % step or d > 2048:
+        raise ValueError(f"{what} must be a multiple of {step} in {step}..2048, got {d}")
     if n < 1 or n >= 2 ** 31:
         raise ValueError(f"count must be in 1..2^31-1, got {n}")
     bad = np.flatnonzero(~np.isfinite(v).all(axis=1))
@@ -69,10 +105,37 @@ def prepare_rows(vectors, metric: str) -> np.ndarray:
     if metric == "cosine":
         norm = np.sqrt((v * v).sum(axis=1, dtype=np.float32), dtype=np.float32)
         v = v / np.maximum(norm, np.float32(1e-12))[:, None]
-    rows = to_bf16(v)
+    return v
+
+
+def prepare_rows(vectors, metric: str) -> np.ndarray:
+    """fp32 [N, D] -> the bf16 bit patterns (uint16 [N, D]) an index of ``metric`` stores: the checks, the
+    cosine normalisation and the rounding of :func:`write_index` and of ``add`` (one function: the same bits)."""
+    rows = to_bf16(_checked_rows(vectors, metric, 8))
     if not np.isfinite(bf16_to_f32(rows)).all():
         raise ValueError("a value overflows bf16")
     return rows
+
+
+def quantize_rows(v: np.ndarray):
+    """fp32 [N, D] as it stands -> (codes uint8 [N, D], scales float32 [N]); see :func:`prepare_rows_fp8`."""
+    v = np.ascontiguousarray(v, np.float32)
+    amax = np.abs(v).max(axis=1)
+    scale = (amax / np.float32(E4M3_MAX)).astype(np.float32)
+    scale = np.maximum(scale, np.finfo(np.float32).tiny)
+    scale[amax == 0] = np.float32(1.0)
+    x = np.clip((v / scale[:, None]).astype(np.float32), np.float32(-E4M3_MAX), np.float32(E4M3_MAX))
+    return to_e4m3(x), scale
+
+
+def prepare_rows_fp8(vectors, metric: str):
+    """fp32 [N, D] -> (codes uint8 [N, D], scales float32 [N]), what an fp8 index of ``metric`` stores: the
+    checks and the normalisation of :func:`prepare_rows` (D % 16 == 0 here), then per row, in fp32,
+    ``scale = max|v| / 448`` (at least the smallest normal; 1 for an all-zero row) and
+    ``code = e4m3fn_rne(clamp(v / scale, -448, 448))``. Each row depends on itself only, so ``add(B)`` onto
+    an index of A stores the bytes ``write_index(A u B)`` would.
+    ``|v - scale * decode(code)| <= scale * max(|v / scale| * 2^-4, 2^-10) * (1 + 2^-10)``."""
+    return quantize_rows(_checked_rows(vectors, metric, 16, "dim of an fp8 index"))
 
 
 def check_tags(tags, n: int) -> np.ndarray:
@@ -97,37 +160,53 @@ def unpack_live(words, n: int) -> np.ndarray:
     return np.unpackbits(np.ascontiguousarray(words, "<u4").view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
-def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None) -> dict:
+def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None, scales=None) -> dict:
     """The file of ``hdr`` and ``rows``: version 1 without ``tags`` / ``live``, else version 2 (zero tags / all
-    live where one is missing). Atomic: a temporary file, then a rename. Returns the JSON header written."""
+    live where one is missing); with ``scales`` (fp8 rows) version 3, whose tags and bitmap are present under
+    the same rule. Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
 
     def align(x):
         return -(-x // ALIGN) * ALIGN
-    if tags is None and live is None:
+    blocks = tags is not None or live is not None
+    if not blocks and scales is None:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
-        version = VERSION2
-        tags = np.zeros(n, np.uint32) if tags is None else tags
-        words = pack_live(np.ones(n, bool) if live is None else live)
-        hdr = dict(hdr, capacity=int(max(capacity or 0, n)), tags_off=0, live_off=0)
+        version = VERSION2 if scales is None else VERSION3
+        if scales is not None:
+            hdr = dict(hdr, scales_off=0)
+        if blocks:
+            tags = np.zeros(n, np.uint32) if tags is None else tags
+            words = pack_live(np.ones(n, bool) if live is None else live)
+            hdr = dict(hdr, capacity=int(max(capacity or 0, n)), tags_off=0, live_off=0)
         while True:  # the offsets follow the JSON's own length: a few rounds until they agree
             js = json.dumps(hdr).encode()
             data_off = align(HEAD.size + len(js))
-            tags_off = align(data_off + rows.nbytes)
-            live_off = align(tags_off + 4 * n)
-            if (hdr["tags_off"], hdr["live_off"]) == (tags_off, live_off):
+            end = data_off + rows.nbytes
+            offs = {}
+            if scales is not None:
+                offs["scales_off"] = align(end)
+                end = offs["scales_off"] + 4 * n
+            if blocks:
+                offs["tags_off"] = tags_off = align(end)
+                offs["live_off"] = live_off = align(tags_off + 4 * n)
+            if all(hdr[k] == v for k, v in offs.items()):
                 break
-            hdr["tags_off"], hdr["live_off"] = tags_off, live_off
+            hdr.update(offs)
     tmp = path + ".tmp"
     with open(tmp, "wb") as f:
         f.write(HEAD.pack(MAGIC, version, len(js), data_off, n, rows.shape[1], METRICS.index(hdr["metric"])))
         f.write(js)
         f.write(bytes(data_off - HEAD.size - len(js)))
         f.write(rows.tobytes())
-        if version == VERSION2:
-            f.write(bytes(tags_off - data_off - rows.nbytes))
+        at = data_off + rows.nbytes
+        if scales is not None:
+            f.write(bytes(hdr["scales_off"] - at))
+            f.write(np.asarray(scales).astype("<f4").tobytes())
+            at = hdr["scales_off"] + 4 * n
+        if blocks:
+            f.write(bytes(tags_off - at))
             f.write(tags.astype("<u4").tobytes())
             f.write(bytes(live_off - tags_off - 4 * n))
             f.write(words.astype("<u4").tobytes())
@@ -135,11 +214,15 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
     return hdr
 
 
-def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None) -> dict:
+def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
+                dtype: str = "bf16") -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
-    ``tags`` the file is version 1; with them (uint32 [N]) version 2."""
-    rows = prepare_rows(vectors, metric)
+    ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
+    scale per row (:func:`prepare_rows_fp8`), a version-3 file."""
+    if dtype not in DTYPES:
+        raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
     n, d = rows.shape
     if labels is not None:
         labels = [str(s) for s in labels]
@@ -147,11 +230,11 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
             raise ValueError(f"{len(labels)} labels for {n} rows")
     if tags is not None:
         tags = check_tags(tags, n)
-    hdr = {"dim": d, "count": n, "dtype": "bf16", "metric": metric, "model": str(model or ""),
+    hdr = {"dim": d, "count": n, "dtype": DTYPES[dtype], "metric": metric, "model": str(model or ""),
            "embed": dict(embed) if embed else None}
     if labels is not None:
         hdr["labels"] = labels
-    return _write_file(path, hdr, rows, tags)
+    return _write_file(path, hdr, rows, tags, scales=scales)
 
 
 def read_header(path: str) -> dict:
@@ -161,17 +244,33 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version not in (VERSION, VERSION2):
+        if version not in (VERSION, VERSION2, VERSION3):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
     if metric >= len(METRICS) or (hdr.get("dim"), hdr.get("count"), hdr.get("metric")) != (dim, count, METRICS[metric]) \
-            or hdr.get("dtype") != "bf16":
+            or hdr.get("dtype") not in DTYPES.values():
         raise ValueError(f"{path}: the JSON header disagrees with the file head")
+    fp8 = version == VERSION3
+    if (hdr["dtype"] == FP8) != fp8:
+        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (version 3 means fp8_e4m3 rows)")
+    if fp8 and (dim < 16 or dim % 16 or dim > 2048):
+        raise ValueError(f"{path}: dim of an fp8 index must be a multiple of 16 in 16..2048, got {dim}")
     if hdr.get("labels") is not None and len(hdr["labels"]) != count:
         raise ValueError(f"{path}: {len(hdr['labels'])} labels for {count} rows")
-    if version == VERSION2:
-        end = data_off + count * dim * 2
+    end = data_off + count * dim * (1 if fp8 else 2)
+    if fp8:
+        off = hdr.get("scales_off")
+        if not isinstance(off, int) or off % ALIGN:
+            raise ValueError(f"{path}: scales_off {off!r} is not a multiple of {ALIGN}")
+        if off < end:
+            raise ValueError(f"{path}: the scales block at {off} overlaps the rows, which end at {end}")
+        if off + 4 * count > size:
+            raise ValueError(f"{path}: the scales block lies outside the file")
+        end = off + 4 * count
+        if ("tags_off" in hdr) != ("live_off" in hdr):
+            raise ValueError(f"{path}: a version-3 file with only one of tags_off / live_off")
+    if version == VERSION2 or (fp8 and "tags_off" in hdr):
         for key, nbytes in (("tags_off", 4 * count), ("live_off", 4 * (-(-count // 32)))):
             off = hdr.get(key)
             if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
@@ -201,21 +300,34 @@ def file_info(path: str) -> dict:
     """What ``hipzap info`` adds to the header: the format version, capacity, live rows, tags presence."""
     hdr = read_header(path)
     v2 = "tags_off" in hdr
-    return {"version": VERSION2 if v2 else VERSION, "capacity": hdr.get("capacity", hdr["count"]),
+    info = {"version": VERSION2 if v2 else VERSION, "capacity": hdr.get("capacity", hdr["count"]),
             "live": int(read_live(path).sum()), "tags": v2}
+    if hdr["dtype"] == FP8:
+        info.update(version=VERSION3, dtype=FP8)
+    return info
 
 
 def read_rows(path: str) -> np.ndarray:
-    """The row block as bf16 bit patterns, uint16 [count, dim]."""
+    """The row block: bf16 bit patterns, uint16 [count, dim]; e4m3fn codes, uint8, for an fp8 index."""
     hdr = read_header(path)
-    return np.fromfile(path, np.uint16, hdr["count"] * hdr["dim"], offset=hdr["data_off"]).reshape(hdr["count"], hdr["dim"])
+    dt = np.uint8 if hdr["dtype"] == FP8 else np.uint16
+    return np.fromfile(path, dt, hdr["count"] * hdr["dim"], offset=hdr["data_off"]).reshape(hdr["count"], hdr["dim"])
 
 
-def search_ref(corpus, q, k: int, allow=None):
+def read_scales(path: str) -> np.ndarray:
+    """The row scales of an fp8 index, float32 [count]."""
+    hdr = read_header(path)
+    if hdr["dtype"] != FP8:
+        raise ValueError(f"{path}: a {hdr['dtype']} index has no scales")
+    return np.fromfile(path, "<f4", hdr["count"], offset=hdr["scales_off"]).astype(np.float32)
+
+
+def search_ref(corpus, q, k: int, allow=None, scales=None):
     """The oracle: ``corpus`` (the bf16 rows widened to fp32, [N, D]) against ``q`` (fp32 [Q, D]) in fp64
     -> (scores float64 [Q, k], ids int32 [Q, k]) under the order rule. Each score is one row's own sum, so
     equal rows give equal scores wherever they stand. ``allow`` (bool [N] or [Q, N]): only these rows may be
-    returned, under their own ids; the slots past the allowed rows hold id -1, score -inf."""
+    returned, under their own ids; the slots past the allowed rows hold id -1, score -inf. ``scales`` ([N],
+    an fp8 index): row r's score is ``scales[r]`` times its sum over the decoded codes."""
     c = np.asarray(corpus, np.float64)
     q = np.asarray(q, np.float64)
     if q.ndim == 1:
@@ -228,7 +340,10 @@ def search_ref(corpus, q, k: int, allow=None):
     scores = np.full((q.shape[0], k), -np.inf)
     ids = np.full((q.shape[0], k), -1, np.int32)
     for i, row in enumerate(q):
-        s = (c * row[None, :]).sum(axis=1) + 0.0  # -0.0 + 0.0 = +0.0
+        s = (c * row[None, :]).sum(axis=1)
+        if scales is not None:
+            s = s * np.asarray(scales, np.float64)
+        s = s + 0.0  # -0.0 + 0.0 = +0.0
         if allow is None:
             order = np.argsort(-s, kind="stable")[:k]  # stable: equal scores keep ascending ids
         else:
@@ -286,16 +401,24 @@ def check_filter(filter, nq: int):
     return out
 
 
+class _QRows:
+    """What ``add`` hands a backend's ``_append`` on an fp8 index: the codes and their row scales."""
+
+    def __init__(self, codes, scales):
+        self.codes, self.scales, self.shape = np.ascontiguousarray(codes), np.ascontiguousarray(scales, np.float32), codes.shape
+
+
 class _Base:
     """What both backends share: the header, the argument checks of the mutators and ``save``. A backend
     provides ``_append(bits, tags, publish)`` (which calls ``publish(first id)`` before searches may run again), ``_kill(ids) -> int``, ``_retag(ids, tags)`` and ``_state() -> (bits,
-    tags, live)``."""
+    tags, live)``. On an fp8 index ``bits`` is a ``_QRows`` and ``_state`` returns ``(codes, tags, live, scales)``."""
 
     def __init__(self, path: str):
         self.path = path
         self.header = read_header(path)
         self.dim, self.count, self.metric = self.header["dim"], self.header["count"], self.header["metric"]
         self.labels = self.header.get("labels")
+        self.dtype = self.header["dtype"]
         self._mut = threading.Lock()  # one mutator at a time
 
     def __enter__(self):
@@ -314,9 +437,13 @@ class _Base:
         return np.ascontiguousarray(a.astype(np.int32))
 
     def add(self, vectors, tags=None, labels=None) -> np.ndarray:
-        """Append rows (fp32 [n, dim], through :func:`prepare_rows`: the bits ``write_index`` would store) ->
-        their ids, int32 [n]. ``tags``: uint32 [n], default 0. ``labels``: required iff the index has labels."""
-        bits = prepare_rows(vectors, self.metric)
+        """Append rows (fp32 [n, dim], through :func:`prepare_rows` or, on an fp8 index, :func:`prepare_rows_fp8`:
+        the bits ``write_index`` would store) -> their ids, int32 [n]. ``tags``: uint32 [n], default 0.
+        ``labels``: required iff the index has labels."""
+        if self.dtype == FP8:
+            bits = _QRows(*prepare_rows_fp8(vectors, self.metric))
+        else:
+            bits = prepare_rows(vectors, self.metric)
         n = bits.shape[0]
         if bits.shape[1] != self.dim:
             raise ValueError(f"vectors must be [N, {self.dim}], got {list(bits.shape)}")
@@ -353,23 +480,26 @@ class _Base:
     def save(self, path: str | None = None, compact: bool = False) -> dict:
         """Write the index as it stands (atomic: a temporary file, then a rename) -> the JSON header.
         ``compact=False`` keeps ids and tombstones; ``compact=True`` drops the dead rows and renumbers the
-        rest in order. Version 1 when every row is live and every tag is 0, else version 2."""
+        rest in order. Version 1 when every row is live and every tag is 0, else version 2; an fp8 index is
+        version 3 with or without tags and bitmap under the same rule."""
         with self._mut:
-            bits, tags, live = self._state()
+            bits, tags, live, *rest = self._state()
+            scales = rest[0] if rest else None
             labels = self.labels
             if compact:
                 if not live.any():
                     raise ValueError("no live row to save")
                 bits, tags = bits[live], tags[live]
+                scales = scales[live] if scales is not None else None
                 labels = [x for x, keep in zip(labels, live) if keep] if labels is not None else None
                 live = np.ones(bits.shape[0], bool)
-            hdr = {"dim": self.dim, "count": int(bits.shape[0]), "dtype": "bf16", "metric": self.metric,
+            hdr = {"dim": self.dim, "count": int(bits.shape[0]), "dtype": self.dtype, "metric": self.metric,
                    "model": self.header.get("model", ""), "embed": self.header.get("embed")}
             if labels is not None:
                 hdr["labels"] = list(labels)
             plain = bool(live.all()) and not tags.any()
             return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), None if plain else tags,
-                               None if plain else live, self.capacity())
+                               None if plain else live, self.capacity(), scales=scales)
 
 
 class RefIndex(_Base):
@@ -380,7 +510,9 @@ class RefIndex(_Base):
     def __init__(self, path: str, reserve: int = 0):
         super().__init__(path)
         self._bits = read_rows(path)
-        self._rows = bf16_to_f32(self._bits)
+        fp8 = self.dtype == FP8
+        self._rows = e4m3_to_f32(self._bits) if fp8 else bf16_to_f32(self._bits)
+        self.scales = read_scales(path) if fp8 else None
         self._tags, self._live = read_tags(path), read_live(path)
         self._cap = max(self.count, int(reserve), int(self.header.get("capacity", 0)))
 
@@ -394,13 +526,19 @@ class RefIndex(_Base):
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
         with self._mut:  # the mutators replace the arrays one by one
-            s, i = search_ref(self._rows, q, k, None if filt is None and self._live.all() else self.allow(filt))
+            s, i = search_ref(self._rows, q, k, None if filt is None and self._live.all() else self.allow(filt),
+                              scales=self.scales)
         return s.astype(np.float32), i
 
     def _append(self, bits, tags, publish):
         first = self.count
+        if self.scales is not None:
+            self.scales = np.concatenate([self.scales, bits.scales])
+            bits, new = bits.codes, e4m3_to_f32(bits.codes)
+        else:
+            new = bf16_to_f32(bits)
         self._bits = np.concatenate([self._bits, bits])
-        self._rows = np.concatenate([self._rows, bf16_to_f32(bits)])
+        self._rows = np.concatenate([self._rows, new])
         self._tags = np.concatenate([self._tags, tags])
         self._live = np.concatenate([self._live, np.ones(bits.shape[0], bool)])
         while self._cap < self._bits.shape[0]:
@@ -417,6 +555,8 @@ class RefIndex(_Base):
         self._tags[ids] = tags
 
     def _state(self):
+        if self.scales is not None:
+            return self._bits, self._tags, self._live, self.scales
         return self._bits, self._tags, self._live
 
     def capacity(self) -> int:
@@ -492,10 +632,16 @@ class Index(_Base):
 
     def _append(self, bits, tags, publish):
         first = C.c_longlong(-1)
-        bits = np.ascontiguousarray(bits)
+        fp8 = self.dtype == FP8
+        if not fp8:
+            bits = np.ascontiguousarray(bits)
 
         def call():
-            rc = self._lib.hz_index_add(self._h, bits.ctypes.data, bits.shape[0], tags.ctypes.data, C.byref(first))
+            if fp8:
+                rc = self._lib.hz_index_add_q(self._h, bits.codes.ctypes.data, bits.scales.ctypes.data, bits.shape[0],
+                                              tags.ctypes.data, C.byref(first))
+            else:
+                rc = self._lib.hz_index_add(self._h, bits.ctypes.data, bits.shape[0], tags.ctypes.data, C.byref(first))
             if rc == 0:
                 publish(int(first.value))
             return rc
@@ -514,8 +660,14 @@ class Index(_Base):
 
     def _state(self):
         n = self.count
-        bits, tags = np.empty((n, self.dim), np.uint16), np.empty(n, np.uint32)
-        words = np.empty(-(-n // 32), np.uint32)
+        tags, words = np.empty(n, np.uint32), np.empty(-(-n // 32), np.uint32)
+        if self.dtype == FP8:
+            codes, scales = np.empty((n, self.dim), np.uint8), np.empty(n, np.float32)
+            self._exclusive(lambda: self._lib.hz_index_read_state_q(self._h, codes.ctypes.data, scales.ctypes.data,
+                                                                    tags.ctypes.data, words.ctypes.data, n),
+                            "hz_index_read_state_q")
+            return codes, tags, unpack_live(words, n), scales
+        bits = np.empty((n, self.dim), np.uint16)
         self._exclusive(lambda: self._lib.hz_index_read_state(self._h, bits.ctypes.data, tags.ctypes.data,
                                                               words.ctypes.data, n), "hz_index_read_state")
         return bits, tags, unpack_live(words, n)
@@ -546,3 +698,26 @@ class Index(_Base):
 
 def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 0):
     return Index(path, device, reserve=reserve) if backend == "gpu" else RefIndex(path, reserve)
+
+
+def convert_index(src: str, dst: str, dtype: str = "fp8") -> dict:
+    """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
+    widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
+    labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid."""
+    if dtype not in DTYPES:
+        raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    hdr = read_header(src)
+    if hdr["dtype"] != "bf16":
+        raise ValueError(f"{src}: only a bf16 index can be converted, this one holds {hdr['dtype']}")
+    bits, scales = read_rows(src), None
+    if dtype == "fp8":
+        if hdr["dim"] % 16:
+            raise ValueError(f"dim of an fp8 index must be a multiple of 16 in 16..2048, got {hdr['dim']}")
+        bits, scales = quantize_rows(bf16_to_f32(bits))
+    out = {k: hdr[k] for k in ("dim", "count") if k in hdr}
+    out.update(dtype=DTYPES[dtype], metric=hdr["metric"], model=hdr.get("model", ""), embed=hdr.get("embed"))
+    if hdr.get("labels") is not None:
+        out["labels"] = hdr["labels"]
+    v2 = "tags_off" in hdr
+    return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
+                       hdr.get("capacity"), scales=scales)

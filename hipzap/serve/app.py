@@ -557,7 +557,8 @@ def search():
         if labels is not None and i >= 0:
             h["label"] = labels[i]
         return h
-    return _json({"model": model, "backend": backend.backend, "metric": index.metric, "k": k, "count": int(index.count),
+    return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "k": k,
+                  "count": int(index.count),
                   "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(ids, scores)],
                   "timing_ms": round(dt, 3)})
 
