@@ -1,11 +1,14 @@
-// hipzap vector search for gfx950 (CDNA4): exact top-k by inner product over a bf16 corpus.
+// hipzap vector search for gfx950 (CDNA4): exact top-k by inner product over a bf16 or e4m3 corpus.
 //   * search_scan  — one workgroup per tile of HZ_SEARCH_TILE rows: every row is read once and scored
-//                    against all Q queries of the launch (resident in LDS); the tile's best k per query
-//   * search_fscan — the scan over the rows that pass a live bit and a per-query tag predicate
-//   * search_qscan — the filtered scan over OCP e4m3fn byte rows with one fp32 scale per row
+//                    against all Q queries of the launch (resident in LDS); the tile's best k per query.
+//                    One template; its instantiations are the kinds SCAN (bf16 rows), FSCAN (bf16 rows that
+//                    pass a live bit and a per-query tag predicate) and QSCAN (FSCAN over OCP e4m3fn byte
+//                    rows with one fp32 scale per row)
 //   * search_merge — one workgroup per query: ntile x k candidates -> the final k, best first
 // See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n for the reasoning.
 #include <stdio.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "hipzap.h"
@@ -31,112 +34,153 @@ __device__ __forceinline__ float unorderable(unsigned o) {
 }
 
 // ------------------------------------------------------------------------------------------- scan
-// Wave w of the workgroup owns rows w*64 .. w*64+63 of the tile, ROWS at a time. Lane l holds the 16-B
-// chunks l, l + 64, ... of a row (NC of them, sized to D at launch). score(q, r): every lane runs ONE
-// fmaf chain over its elements in ascending column order starting from +0 (a lane past the row's end keeps
-// +0), then the 64 lane sums meet in a xor butterfly (32, 16, ..., 1). Both orders are fixed by D alone,
-// so the bits of a score depend on the query's and the row's D values and on nothing else: not on the
-// row's position, its tile, N, Q, k or the other queries. Each (row, query) score lands in LDS as an
-// order-preserving u32; thread t then ranks row t of the tile among the tile's rows (higher score first,
-// then the lower row) and the rows ranked below k write their key to slot `rank` of the tile's list.
-// Addresses: corpus rows [tile*T, min(N, tile*T + T)), the Q x D queries, and cand[(tile*Q + q)*k + s]
-// with s < k -- `rank` is the one data-dependent index and is used only under `rank < k`.
-template <int NC>
-__global__ __launch_bounds__(T) void search_scan_kernel(const HzSearchParams p) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* qs = lds;                                              // [Q][D]
-  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);  // [Q][T]
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tile = blockIdx.x;
-  const int nch = p.D >> 3;
-  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 512 && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
-  const long row0 = (long)tile * T;
-  const int rows = (int)min((long)T, (long)p.N - row0);
-  for (int i = threadIdx.x; i < p.Q * (p.D >> 2); i += T)
-    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(p.queries)[i];
-  __syncthreads();
-
-  for (int g = 0; g < 64; g += ROWS) {  // wave-uniform bounds
-    const int r0 = w * 64 + g;
-    if (r0 >= rows) break;
-    u32x4 v[ROWS][NC];
+// search_scan_kernel<Fmt, NC, FILT>: row format, 16-B chunks per lane (sized to D at launch), filtered or not.
+// Wave w of the workgroup owns rows w*64 .. w*64+63 of the tile, ROWS at a time. Lane l holds the 16-B chunks
+// l, l + 64, ... of a row, Fmt::E elements each.
+// CONTRACT: score(q, r) is ONE fmaf chain per lane over the lane's elements in ascending column order starting
+// from +0 (a lane past the row's end keeps +0), then the xor butterfly over the 64 lane sums (32, 16, ..., 1),
+// then, for a scaled format, ONE fp32 multiply by the row's scale; then orderable(). All of it is fixed by D
+// alone, so the bits of a score depend on the query's D values, the row's D elements and the row's scale, and
+// on nothing else: not on N, Q, k, the row's position or tile, the other queries, the filter, or what dead
+// rows hold. The three kinds share these statements, so a passing (q, r) scores the same bits in all of them.
+// No NaN reaches the kernels (the writers refuse non-finite rows and queries): orderable() of a real score is never 0.
+// Each (row, query) score lands in LDS as an order-preserving u32; thread t then ranks row t of the tile among
+// the tile's rows (higher score first, then the lower row) and the rows ranked below k write their key to
+// slot `rank` of the tile's list; the slots past the tile's passing rows are zero-filled.
+// Per variant:
+//   * unfiltered (SCAN): every row of the tile is loaded and scored; no pass bits exist, in LDS or registers.
+//   * filtered (FSCAN, QSCAN): pass(q, r) = live(r) && (filt == null || (tags[r] & mask[q]) == value[q]). The
+//     kernel's start stages the tile's 8 live words, its T tag words and the Q {mask, value} pairs (one
+//     coalesced read each) and thread t folds them into row t's pass bits. The row loop reads the pass bits of
+//     its (wave-uniform) rows through readfirstlane: a row with no pass bit is not loaded, and a group of ROWS
+//     such rows only writes its Q x ROWS sentinels, one per lane -- scalar branches, no divergence. A failing
+//     (q, r) is the sentinel 0 in the score array, below orderable() of every real float, whatever the row holds (the uninitialised
+//     rows between count and capacity included). A passing row's rank counts only keys above it, all real,
+//     so it is below the tile's pass count; sentinel rows write nothing.
+//   * Bf16Rows: 8 elements per chunk, NC 1 .. 4; a chunk is unpacked inside the query loop.
+//   * E4m3Rows (QSCAN; filtered only, live bitmap required): 16 elements per chunk, NC 1 .. 2; a group's bytes
+//     are decoded to fp32 ONCE, before the query loop. Thread t stages scales[row0 + t] iff row t passes for
+//     some query, so neither the bytes nor the scale of a dead row is ever loaded (NaN codes, NaN or inf
+//     scales).
+// Addresses: corpus rows [tile*T, min(N, tile*T + T)) at row * ldc elements + chunk * 16 B under
+// chunk < D / E, the Q x D queries, and cand[(tile*Q + q)*k + s] with s < k -- `rank` is the one data-dependent
+// index and is used only under `rank < k`. Filtered: live words [row0/32, row0/32 + 8) under word*32 < N (the
+// launcher checks live_bytes), tags[row0 + t] under t < rows, filt[i] under i < 2Q. Scaled: scales[row0 + t]
+// under t < rows.
+//
+// A row format (what each member means: DESIGN.md 4l, "One template, three kinds"): Elem is the stored element
+// (`ldc` counts these), E the elements per 16-B chunk, MAX_NC the chunks per lane at D = 2048.
+struct Bf16Rows {
+  using Elem = unsigned short;
+  static constexpr int E = 8, MAX_NC = 4;
+  static constexpr bool WIDEN_ONCE = false, SCALED = false;
+  template <bool FILT>
+  using Args = std::conditional_t<FILT, HzSearchFilterParams, HzSearchParams>;
+  static __device__ __forceinline__ void widen(const u32x4 v, float* f) { unpack8(v, f); }
+};
+struct E4m3Rows {
+  using Elem = unsigned char;
+  static constexpr int E = 16, MAX_NC = 2;
+  static constexpr bool WIDEN_ONCE = true, SCALED = true;
+  template <bool FILT>
+  using Args = std::enable_if_t<FILT, HzSearchQuantParams>;
+  // v_cvt_pk_f32_fp8: exact for the 254 finite codes, subnormals and -0 included
+  static __device__ __forceinline__ void widen(const u32x4 v, float* f) {
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        v[r][c] = u32x4{0u, 0u, 0u, 0u};
-        if (r0 + r < rows && c * 64 + lane < nch && HZ_DCHECK(row0 + r0 + r < (long)p.N))
-          v[r][c] = *reinterpret_cast<const u32x4*>(p.corpus + (row0 + r0 + r) * p.ldc + (c * 64 + lane) * 8);
-      }
-    for (int q = 0; q < p.Q; ++q) {
-      float acc[ROWS];
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        if (c * 64 + lane < nch) {
-          const float* qp = qs + q * p.D + (c * 64 + lane) * 8;
-          const f32x4 qa = *reinterpret_cast<const f32x4*>(qp), qb = *reinterpret_cast<const f32x4*>(qp + 4);
-          const float qv[8] = {qa[0], qa[1], qa[2], qa[3], qb[0], qb[1], qb[2], qb[3]};
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) {
-            float f[8];
-            unpack8(v[r][c], f);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[r] = fmaf(qv[e], f[e], acc[r]);
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const float s = warp_sum(acc[r]);
-        if (lane == r && r0 + r < rows) sc[q * T + r0 + r] = orderable(s);
-      }
+    for (int i = 0; i < 4; ++i) {
+      const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false);  // bytes 0, 1 of the word
+      const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);   // bytes 2, 3
+      f[4 * i] = lo[0];
+      f[4 * i + 1] = lo[1];
+      f[4 * i + 2] = hi[0];
+      f[4 * i + 3] = hi[1];
     }
   }
-  __syncthreads();
+};
 
+// the nested parameter blocks: each kind's block starts with the blocks of the kinds it extends
+__host__ __device__ inline const HzSearchParams& scan_part(const HzSearchParams& a) { return a; }
+__host__ __device__ inline const HzSearchParams& scan_part(const HzSearchFilterParams& a) { return a.s; }
+__host__ __device__ inline const HzSearchParams& scan_part(const HzSearchQuantParams& a) { return a.f.s; }
+__host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchFilterParams& a) { return a; }
+__host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchQuantParams& a) { return a.f; }
+
+// Dynamic LDS of a scan, in the kernel's order: queries [Q][D], scores [Q][T]; filtered: pass bits [T], the
+// tile's live words [T / 32], filters [Q][2]; scaled: the passing rows' scales [T]. At most 144 KiB (Q = 16,
+// D = 2048) + 1184 B + 1 KiB.
+constexpr size_t lds_bytes(int Q, int D, bool filtered, bool scaled) {
+  return ((size_t)Q * D + (size_t)Q * T + (filtered ? T + T / 32 + 2 * (size_t)Q : 0) + (scaled ? T : 0)) * 4;
+}
+
+__device__ __forceinline__ void stage_queries(const HzSearchParams& p, float* qs) {
+  for (int i = threadIdx.x; i < p.Q * (p.D >> 2); i += T)
+    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(p.queries)[i];
+}
+
+// Filtered: row t's pass bits over the queries into pmask[t] (rows past the tile's end: 0) and, for a scaled
+// format, the scale of a passing row into scl[t]. One barrier inside; the caller's barrier publishes the result.
+template <class Fmt, class A>
+__device__ __forceinline__ void stage_pass_bits(const A& a, unsigned* pmask, float* scl, long row0, int rows) {
+  const HzSearchFilterParams& fp = filter_part(a);
+  const HzSearchParams& p = fp.s;
+  unsigned* lv = pmask + T;      // [T / 32] live words of the tile
+  unsigned* fl = lv + T / 32;    // [Q][2]
   const int t = threadIdx.x;
-  const int kk = min(p.k, rows);
-  for (int q = 0; q < p.Q; ++q) {
-    unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
-    const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
-    if (t < rows) {
-      const unsigned mine = sc[q * T + t];
-      int rank = 0;
-      for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
-        const unsigned o = sc[q * T + j];
-        rank += (o > mine) || (o == mine && j < t);
-      }
-      if (rank < kk && slot_ok)
-        out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
+  unsigned tag = 0u;
+  if (fp.tags && t < rows && HZ_DCHECK(row0 + t < (long)p.N)) tag = fp.tags[row0 + t];
+  if (t < T / 32) {
+    const long word = (row0 >> 5) + t;
+    lv[t] = (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)fp.live_bytes)) ? fp.live[word] : 0u;
+  }
+  if (fp.filt && t < 2 * p.Q && HZ_DCHECK(t < 2 * HZ_SEARCH_MAX_Q)) fl[t] = fp.filt[t];
+  __syncthreads();
+  unsigned bits = 0u;
+  if (t < rows && ((lv[t >> 5] >> (t & 31)) & 1u)) {
+    bits = (1u << p.Q) - 1u;  // Q <= 16
+    if (fp.filt) {
+      bits = 0u;
+      for (int q = 0; q < p.Q; ++q) bits |= (unsigned)((tag & fl[2 * q]) == fl[2 * q + 1]) << q;
     }
-    if (t >= kk && t < p.k && slot_ok) out[t] = 0ull;  // a partial tile's unused slots (k <= 128 < T)
+  }
+  pmask[t] = bits;
+  if constexpr (Fmt::SCALED) {
+    float s = 0.f;
+    if (bits != 0u && HZ_DCHECK(t < rows && row0 + t < (long)p.N)) s = a.scales[row0 + t];
+    scl[t] = s;
   }
 }
 
-// ------------------------------------------------------------------------------------- filtered scan
-// The scan with pass(q, r) = live(r) && (filt == null || (tags[r] & mask[q]) == value[q]). Beside the
-// queries, the kernel's start stages the tile's 8 live words, its T tag words and the Q {mask, value} pairs
-// (one coalesced read each); thread t then folds them into pm[t], row t's pass bits over the queries. The
-// row loop reads pm of its (wave-uniform) rows through readfirstlane: a row with no pass bit is not
-// loaded, and a group of ROWS such rows only writes its sentinels -- scalar branches, no divergence. What a
-// dead row holds (the uninitialised rows between count and capacity included) never reaches a register.
-// A failing (q, r) is the sentinel 0 in `sc`, below orderable() of every real float. Ranking: a passing
-// row's rank counts only keys above it, all real, so it is below the tile's pass count `np`; sentinel rows
-// write nothing and slots np .. k-1 are zero-filled.
-// Addresses beyond the scan's: live words [row0/32, row0/32 + 8) under word*32 < N (the launcher checks
-// live_bytes), tags[row0 + t] under t < rows, filt[i] under i < 2Q.
-//
-// score_group: one group of ROWS rows (r0 .. r0 + ROWS - 1 of the tile, already in `v`) against every query: the fmaf
-// chains and the butterfly of search_scan_kernel, statement for statement (the score bits are the same by
-// construction; the unfiltered kernel keeps its own copy so that its code object does not change). `pm[r]`
-// holds row r's pass bits (bit q = query q); a failing (q, r) writes the sentinel 0 instead of its score.
-template <int NC>
-__device__ __forceinline__ void score_group(const HzSearchParams& p, const float* qs, unsigned* sc,
-                                            const u32x4 (&v)[ROWS][NC], const unsigned (&pm)[ROWS], int lane, int nch,
+// Which rows of a group are loaded and which (q, r) are scored. Unfiltered: the rows before the tile's end,
+// for every query. Filtered: row r's pass bits (bit q = query q), wave-uniform.
+template <bool FILT>
+struct GroupPass {
+  int r0, rows;  // the group's first row, the tile's rows
+  __device__ __forceinline__ bool row(int r) const { return r0 + r < rows; }
+  __device__ __forceinline__ bool pair(int, int) const { return true; }
+};
+template <>
+struct GroupPass<true> {
+  unsigned pm[ROWS];
+  __device__ __forceinline__ bool row(int r) const { return pm[r] != 0u; }
+  __device__ __forceinline__ bool pair(int q, int r) const { return (pm[r] >> q) & 1u; }
+};
+
+// The group in `v` (rows r0 .. r0 + ROWS - 1 of the tile) against every query: the contract's fmaf chain,
+// butterfly and scale multiply, then the order-preserving score, or the sentinel 0 for a failing (q, r).
+template <class Fmt, int NC, bool FILT>
+__device__ __forceinline__ void score_group(const HzSearchParams& p, const float* qs, unsigned* sc, const float* scl,
+                                            const u32x4 (&v)[ROWS][NC], const GroupPass<FILT>& pass, int lane, int nch,
                                             int r0, int rows) {
+  constexpr int E = Fmt::E;
+  float f[Fmt::WIDEN_ONCE ? ROWS : 1][Fmt::WIDEN_ONCE ? NC : 1][E], rs[ROWS];  // WIDEN_ONCE: the group as fp32
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) {
+    if constexpr (Fmt::SCALED) rs[r] = scl[r0 + r];  // every lane reads the same word: an LDS broadcast
+    if constexpr (Fmt::WIDEN_ONCE) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) Fmt::widen(v[r][c], f[r][c]);
+    }
+  }
   for (int q = 0; q < p.Q; ++q) {
     float acc[ROWS];
 #pragma unroll
@@ -144,256 +188,113 @@ __device__ __forceinline__ void score_group(const HzSearchParams& p, const float
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       if (c * 64 + lane < nch) {
-        const float* qp = qs + q * p.D + (c * 64 + lane) * 8;
-        const f32x4 qa = *reinterpret_cast<const f32x4*>(qp), qb = *reinterpret_cast<const f32x4*>(qp + 4);
-        const float qv[8] = {qa[0], qa[1], qa[2], qa[3], qb[0], qb[1], qb[2], qb[3]};
+        const f32x4* qv4 = reinterpret_cast<const f32x4*>(qs + q * p.D + (c * 64 + lane) * E);
+        float qv[E];
+#pragma unroll
+        for (int i = 0; i < E / 4; ++i) {
+          const f32x4 x = qv4[i];
+          qv[4 * i] = x[0], qv[4 * i + 1] = x[1], qv[4 * i + 2] = x[2], qv[4 * i + 3] = x[3];
+        }
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
-          float f[8];
-          unpack8(v[r][c], f);
+          float g[E];
+          const float* fr = g;
+          if constexpr (Fmt::WIDEN_ONCE) fr = f[r][c];
+          else Fmt::widen(v[r][c], g);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) acc[r] = fmaf(qv[e], f[e], acc[r]);
+          for (int e = 0; e < E; ++e) acc[r] = fmaf(qv[e], fr[e], acc[r]);
         }
       }
     }
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
-      const float s = warp_sum(acc[r]);
-      if (lane == r && r0 + r < rows) sc[q * T + r0 + r] = ((pm[r] >> q) & 1u) ? orderable(s) : 0u;
+      float s = warp_sum(acc[r]);
+      if constexpr (Fmt::SCALED) s *= rs[r];
+      if (lane == r && r0 + r < rows) sc[q * T + r0 + r] = pass.pair(q, r) ? orderable(s) : 0u;
     }
   }
 }
 
-template <int NC>
-__global__ __launch_bounds__(T) void search_fscan_kernel(const HzSearchFilterParams fp) {
-  const HzSearchParams& p = fp.s;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* qs = lds;                                              // [Q][D]
-  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);  // [Q][T]
-  unsigned* pmask = sc + p.Q * T;                               // [T]: tags, then pass bits
-  unsigned* lv = pmask + T;                                     // [T / 32] live words of the tile
-  unsigned* fl = lv + T / 32;                                   // [Q][2]
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+// Thread t ranks row t among the tile's scores of each query and writes the tile's candidate list: the passing
+// rows' best k keys, then key 0. Unfiltered: every row passes and the pass count is `rows`.
+template <bool FILT>
+__device__ __forceinline__ void rank_tile(const HzSearchParams& p, const unsigned* sc, int tile, long row0, int rows) {
   const int t = threadIdx.x;
-  const int tile = blockIdx.x;
-  const int nch = p.D >> 3;
-  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 512 && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
-  const long row0 = (long)tile * T;
-  const int rows = (int)min((long)T, (long)p.N - row0);
-  for (int i = t; i < p.Q * (p.D >> 2); i += T)
-    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(p.queries)[i];
-  unsigned tag = 0u;
-  if (fp.tags && t < rows && HZ_DCHECK(row0 + t < (long)p.N)) tag = fp.tags[row0 + t];
-  if (t < T / 32) {
-    const long word = (row0 >> 5) + t;
-    lv[t] = (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)fp.live_bytes)) ? fp.live[word] : 0u;
-  }
-  if (fp.filt && t < 2 * p.Q && HZ_DCHECK(t < 2 * HZ_SEARCH_MAX_Q)) fl[t] = fp.filt[t];
-  __syncthreads();
-  {
-    unsigned bits = 0u;
-    if (t < rows && ((lv[t >> 5] >> (t & 31)) & 1u)) {
-      bits = (1u << p.Q) - 1u;  // Q <= 16
-      if (fp.filt) {
-        bits = 0u;
-        for (int q = 0; q < p.Q; ++q) bits |= (unsigned)((tag & fl[2 * q]) == fl[2 * q + 1]) << q;
-      }
-    }
-    pmask[t] = bits;
-  }
-  __syncthreads();
-
-  for (int g = 0; g < 64; g += ROWS) {  // wave-uniform bounds
-    const int r0 = w * 64 + g;
-    if (r0 >= rows) break;
-    unsigned pm[ROWS], any = 0u;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {  // r0 + r < T: rows past the tile's end have pass bits 0
-      pm[r] = __builtin_amdgcn_readfirstlane(pmask[r0 + r]);
-      any |= pm[r];
-    }
-    if (any == 0u) {  // scalar: nothing of this group is loaded or scored
-      if (lane < ROWS && r0 + lane < rows)
-        for (int q = 0; q < p.Q; ++q) sc[q * T + r0 + lane] = 0u;
-      continue;
-    }
-    u32x4 v[ROWS][NC];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        v[r][c] = u32x4{0u, 0u, 0u, 0u};
-        if (pm[r] != 0u && c * 64 + lane < nch && HZ_DCHECK(row0 + r0 + r < (long)p.N))
-          v[r][c] = *reinterpret_cast<const u32x4*>(p.corpus + (row0 + r0 + r) * p.ldc + (c * 64 + lane) * 8);
-      }
-    score_group<NC>(p, qs, sc, v, pm, lane, nch, r0, rows);
-  }
-  __syncthreads();
-
   for (int q = 0; q < p.Q; ++q) {
     unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
     const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
-    const unsigned mine = t < rows ? sc[q * T + t] : 0u;
-    int rank = 0, np = 0;
-    for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
-      const unsigned o = sc[q * T + j];
-      rank += (o > mine) || (o == mine && j < t);
-      np += o != 0u;
+    // np: the tile's passing rows that can take a slot. Unfiltered: every row passes, so a thread past the
+    // tile's end skips the loop and a real row needs no sentinel test.
+    unsigned mine = 0u;
+    int rank = 0, np = FILT ? 0 : min(p.k, rows);
+    if (FILT || t < rows) {
+      if (t < rows) mine = sc[q * T + t];
+      for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
+        const unsigned o = sc[q * T + j];
+        rank += (o > mine) || (o == mine && j < t);
+        if constexpr (FILT) np += o != 0u;
+      }
     }
-    if (mine != 0u && rank < p.k && slot_ok)
+    if ((FILT ? mine != 0u : t < rows) && rank < (FILT ? p.k : np) && slot_ok)
       out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
     if (t >= np && t < p.k && slot_ok) out[t] = 0ull;  // the slots past the passing rows (k <= 128 < T)
   }
 }
 
-// ------------------------------------------------------------------------------------ quantised scan
-// search_fscan_kernel's structure over rows of OCP e4m3fn bytes with one fp32 scale per row
-// (HzSearchQuantParams; always with a live bitmap, tags and filter optional). Staging is the filtered scan's;
-// after the pass bits are known, thread t reads scales[row0 + t] into LDS iff row t passes for some query
-// (one coalesced read of at most 1 KB), so neither the bytes nor the scale of a dead row is ever loaded:
-// they may be NaN codes and NaN or inf scales. Lane l holds the 16-B chunks l, l + 64 of a row: 16 elements
-// each, NC = 1 up to D = 1024 and 2 up to 2048. A group's bytes are decoded to fp32 ONCE, before the loop
-// over the queries (v_cvt_pk_f32_fp8: exact for the 254 finite codes, subnormals and -0 included).
-// score(q, r): every lane runs one fmaf chain over its elements in ascending column order from +0 (a lane
-// past the row's end keeps +0), the 64 sums meet in the xor butterfly, and the sum is multiplied ONCE, in
-// fp32, by scales[r]; then orderable().
-// CONTRACT: the bits of score(q, r) depend on the query's D values, the row's D codes and the row's scale,
-// and on nothing else: not on N, Q, k, the row's position or tile, the other queries, the filter, or what
-// dead rows hold. Ranking, candidate layout and zero fill are search_fscan_kernel's.
-// Addresses beyond the filtered scan's: the byte rows at (row0 + r) * ldc + chunk * 16 under chunk < D / 16
-// and row < N, scales[row0 + t] under t < rows.
-__device__ __forceinline__ void decode16(const u32x4 v, float* f) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], false);  // bytes 0, 1 of the word
-    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[i], true);   // bytes 2, 3
-    f[4 * i] = lo[0];
-    f[4 * i + 1] = lo[1];
-    f[4 * i + 2] = hi[0];
-    f[4 * i + 3] = hi[1];
-  }
-}
-
-template <int NC>
-__global__ __launch_bounds__(T) void search_qscan_kernel(const HzSearchQuantParams qp) {
-  const HzSearchFilterParams& fp = qp.f;
-  const HzSearchParams& p = fp.s;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* qs = lds;                                              // [Q][D]
-  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);  // [Q][T]
-  unsigned* pmask = sc + p.Q * T;                               // [T]: pass bits
-  unsigned* lv = pmask + T;                                     // [T / 32] live words of the tile
-  unsigned* fl = lv + T / 32;                                   // [Q][2]
-  float* scl = reinterpret_cast<float*>(fl + 2 * p.Q);          // [T]: the scales of the passing rows
-  const unsigned char* rows8 = reinterpret_cast<const unsigned char*>(p.corpus);
+template <class Fmt, int NC, bool FILT>
+__global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::template Args<FILT> a) {
+  const HzSearchParams& p = scan_part(a);
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // lds_bytes()
+  float* qs = lds;                                                      // [Q][D]
+  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);          // [Q][T]
+  unsigned* pmask = nullptr;  // filtered: [T] pass bits, then the tile's live words and the filters
+  float* scl = nullptr;       // scaled: [T] scales of the passing rows
+  if constexpr (FILT) pmask = sc + p.Q * T;
+  if constexpr (Fmt::SCALED) scl = reinterpret_cast<float*>(pmask + T + T / 32 + 2 * p.Q);
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int t = threadIdx.x;
   const int tile = blockIdx.x;
-  const int nch = p.D >> 4;
-  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 1024 && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
+  const int nch = p.D >> __builtin_ctz(Fmt::E);
+  const typename Fmt::Elem* corpus = reinterpret_cast<const typename Fmt::Elem*>(p.corpus);
+  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 64 * Fmt::E && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
   const long row0 = (long)tile * T;
   const int rows = (int)min((long)T, (long)p.N - row0);
-  for (int i = t; i < p.Q * (p.D >> 2); i += T)
-    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(p.queries)[i];
-  unsigned tag = 0u;
-  if (fp.tags && t < rows && HZ_DCHECK(row0 + t < (long)p.N)) tag = fp.tags[row0 + t];
-  if (t < T / 32) {
-    const long word = (row0 >> 5) + t;
-    lv[t] = (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)fp.live_bytes)) ? fp.live[word] : 0u;
-  }
-  if (fp.filt && t < 2 * p.Q && HZ_DCHECK(t < 2 * HZ_SEARCH_MAX_Q)) fl[t] = fp.filt[t];
-  __syncthreads();
-  {
-    unsigned bits = 0u;
-    if (t < rows && ((lv[t >> 5] >> (t & 31)) & 1u)) {
-      bits = (1u << p.Q) - 1u;  // Q <= 16
-      if (fp.filt) {
-        bits = 0u;
-        for (int q = 0; q < p.Q; ++q) bits |= (unsigned)((tag & fl[2 * q]) == fl[2 * q + 1]) << q;
-      }
-    }
-    pmask[t] = bits;
-    float s = 0.f;
-    if (bits != 0u && HZ_DCHECK(t < rows && row0 + t < (long)p.N)) s = qp.scales[row0 + t];
-    scl[t] = s;
-  }
+  stage_queries(p, qs);
+  if constexpr (FILT) stage_pass_bits<Fmt>(a, pmask, scl, row0, rows);
   __syncthreads();
 
   for (int g = 0; g < 64; g += ROWS) {  // wave-uniform bounds
     const int r0 = w * 64 + g;
     if (r0 >= rows) break;
-    unsigned pm[ROWS], any = 0u;
+    GroupPass<FILT> pass;
+    if constexpr (FILT) {
+      unsigned any = 0u;
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) {  // r0 + r < T: rows past the tile's end have pass bits 0
-      pm[r] = __builtin_amdgcn_readfirstlane(pmask[r0 + r]);
-      any |= pm[r];
+      for (int r = 0; r < ROWS; ++r) {  // r0 + r < T: rows past the tile's end have pass bits 0
+        pass.pm[r] = __builtin_amdgcn_readfirstlane(pmask[r0 + r]);
+        any |= pass.pm[r];
+      }
+      if (__builtin_expect(any == 0u, 0)) {  // scalar: nothing of this group is loaded or scored
+        static_assert(ROWS * HZ_SEARCH_MAX_Q <= 64, "one lane per (q, r) sentinel");
+        if (lane < ROWS * p.Q && r0 + lane % ROWS < rows) sc[lane / ROWS * T + r0 + lane % ROWS] = 0u;
+        continue;
+      }
+    } else {
+      pass.r0 = r0, pass.rows = rows;
     }
-    if (any == 0u) {  // scalar: nothing of this group is loaded or scored
-      if (lane < ROWS && r0 + lane < rows)
-        for (int q = 0; q < p.Q; ++q) sc[q * T + r0 + lane] = 0u;
-      continue;
-    }
-    u32x4 v[ROWS][NC];
+    u32x4 v[ROWS][NC];  // this lane's chunks of the group's rows, zeros where nothing is loaded
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         v[r][c] = u32x4{0u, 0u, 0u, 0u};
-        if (pm[r] != 0u && c * 64 + lane < nch && HZ_DCHECK(row0 + r0 + r < (long)p.N))
-          v[r][c] = *reinterpret_cast<const u32x4*>(rows8 + (row0 + r0 + r) * p.ldc + (c * 64 + lane) * 16);
+        if (pass.row(r) && c * 64 + lane < nch && HZ_DCHECK(row0 + r0 + r < (long)p.N))
+          v[r][c] = *reinterpret_cast<const u32x4*>(corpus + (row0 + r0 + r) * p.ldc + (c * 64 + lane) * Fmt::E);
       }
-    float f[ROWS][NC][16], rs[ROWS];  // decoded once for all queries
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      rs[r] = scl[r0 + r];  // every lane reads the same word: an LDS broadcast
-#pragma unroll
-      for (int c = 0; c < NC; ++c) decode16(v[r][c], f[r][c]);
-    }
-    for (int q = 0; q < p.Q; ++q) {
-      float acc[ROWS];
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        if (c * 64 + lane < nch) {
-          const f32x4* qv4 = reinterpret_cast<const f32x4*>(qs + q * p.D + (c * 64 + lane) * 16);
-          float qv[16];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const f32x4 x = qv4[i];
-            qv[4 * i] = x[0], qv[4 * i + 1] = x[1], qv[4 * i + 2] = x[2], qv[4 * i + 3] = x[3];
-          }
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[r] = fmaf(qv[e], f[r][c][e], acc[r]);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const float s = warp_sum(acc[r]) * rs[r];
-        if (lane == r && r0 + r < rows) sc[q * T + r0 + r] = ((pm[r] >> q) & 1u) ? orderable(s) : 0u;
-      }
-    }
+    score_group<Fmt, NC>(p, qs, sc, scl, v, pass, lane, nch, r0, rows);
   }
   __syncthreads();
-
-  for (int q = 0; q < p.Q; ++q) {
-    unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
-    const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
-    const unsigned mine = t < rows ? sc[q * T + t] : 0u;
-    int rank = 0, np = 0;
-    for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
-      const unsigned o = sc[q * T + j];
-      rank += (o > mine) || (o == mine && j < t);
-      np += o != 0u;
-    }
-    if (mine != 0u && rank < p.k && slot_ok)
-      out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
-    if (t >= np && t < p.k && slot_ok) out[t] = 0ull;  // the slots past the passing rows (k <= 128 < T)
-  }
+  rank_tile<FILT>(p, sc, tile, row0, rows);
 }
 
 // ------------------------------------------------------------------------------------------ merge
@@ -524,26 +425,52 @@ int search_check(HzSearchParams& p) {
   return 0;
 }
 
+// the filtered kinds' refusals, after search_check's
+int filter_check(const HzSearchFilterParams& f) {
+  if (!f.live || (reinterpret_cast<uintptr_t>(f.live) & 3)) return -12;
+  if (f.live_bytes < 4ull * (((unsigned long long)f.s.N + 31) / 32)) return -13;
+  if (f.filt && !f.tags) return -14;
+  if ((reinterpret_cast<uintptr_t>(f.tags) & 3) || (reinterpret_cast<uintptr_t>(f.filt) & 3)) return -15;
+  return 0;
+}
+
 // dynamic LDS above 64 KiB is allowed per kernel and device: once, outside any capture (an index does it
-// at open through hz_search_code_warm; a direct launch here)
+// at open through hz_search_code_warm; a direct launch here). Every instantiation scan_dispatch can reach.
+template <class Fmt, bool FILT, int NC = 1>
+int raise_lds_limit_of() {
+  HZ_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_scan_kernel<Fmt, NC, FILT>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if constexpr (NC < Fmt::MAX_NC) return raise_lds_limit_of<Fmt, FILT, NC + 1>();
+  return 0;
+}
 int raise_lds_limit() {
   static bool done[64];
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
   if (done[d]) return 0;
-  const void* fns[10] = {reinterpret_cast<const void*>(&search_scan_kernel<1>),
-                        reinterpret_cast<const void*>(&search_scan_kernel<2>),
-                        reinterpret_cast<const void*>(&search_scan_kernel<3>),
-                        reinterpret_cast<const void*>(&search_scan_kernel<4>),
-                        reinterpret_cast<const void*>(&search_fscan_kernel<1>),
-                        reinterpret_cast<const void*>(&search_fscan_kernel<2>),
-                        reinterpret_cast<const void*>(&search_fscan_kernel<3>),
-                        reinterpret_cast<const void*>(&search_fscan_kernel<4>),
-                        reinterpret_cast<const void*>(&search_qscan_kernel<1>),
-                        reinterpret_cast<const void*>(&search_qscan_kernel<2>)};
-  for (const void* f : fns) HZ_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  if (const int rc = raise_lds_limit_of<Bf16Rows, false>()) return rc;
+  if (const int rc = raise_lds_limit_of<Bf16Rows, true>()) return rc;
+  if (const int rc = raise_lds_limit_of<E4m3Rows, true>()) return rc;
   done[d] = true;
   return 0;
+}
+
+// the instantiation with the fewest chunks per lane that covers D
+template <class Fmt, bool FILT, int NC = 1>
+void scan_dispatch(const typename Fmt::template Args<FILT>& a, const HzSearchParams& p, hipStream_t st) {
+  if constexpr (NC < Fmt::MAX_NC) {
+    if (p.D > NC * 64 * Fmt::E) return scan_dispatch<Fmt, FILT, NC + 1>(a, p, st);
+  }
+  hipLaunchKernelGGL((search_scan_kernel<Fmt, NC, FILT>), dim3(p.ntile), dim3(T),
+                     lds_bytes(p.Q, p.D, FILT, Fmt::SCALED), st, a);
+}
+
+// a checked parameter block (ntile filled) -> the launch
+template <class Fmt, bool FILT>
+int scan_launch(const typename Fmt::template Args<FILT>& a, hipStream_t st) {
+  if (const int rc = raise_lds_limit()) return rc;
+  scan_dispatch<Fmt, FILT>(a, scan_part(a), st);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -558,61 +485,31 @@ extern "C" unsigned long long hz_search_scratch_bytes(long long N, int Q, int k)
 extern "C" int hz_search_scan_launch(const HzSearchParams* pp, hipStream_t st) {
   HzSearchParams p = *pp;
   if (const int rc = search_check(p)) return rc;
-  const size_t lds = ((size_t)p.Q * p.D + (size_t)p.Q * T) * 4;  // <= 16 * (2048 + 256) * 4 = 144 KiB
-  if (const int rc = raise_lds_limit()) return rc;
-  switch ((p.D / 8 + 63) / 64) {
-    case 1: hipLaunchKernelGGL((search_scan_kernel<1>), dim3(p.ntile), dim3(T), lds, st, p); break;
-    case 2: hipLaunchKernelGGL((search_scan_kernel<2>), dim3(p.ntile), dim3(T), lds, st, p); break;
-    case 3: hipLaunchKernelGGL((search_scan_kernel<3>), dim3(p.ntile), dim3(T), lds, st, p); break;
-    default: hipLaunchKernelGGL((search_scan_kernel<4>), dim3(p.ntile), dim3(T), lds, st, p); break;
-  }
-  return (int)hipGetLastError();
+  return scan_launch<Bf16Rows, false>(p, st);
 }
 
 extern "C" int hz_search_fscan_launch(const HzSearchFilterParams* pp, hipStream_t st) {
   HzSearchFilterParams f = *pp;
-  HzSearchParams& p = f.s;
-  if (const int rc = search_check(p)) return rc;
-  if (!f.live || (reinterpret_cast<uintptr_t>(f.live) & 3)) return -12;
-  if (f.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -13;
-  if (f.filt && !f.tags) return -14;
-  if ((reinterpret_cast<uintptr_t>(f.tags) & 3) || (reinterpret_cast<uintptr_t>(f.filt) & 3)) return -15;
-  // the scan's LDS plus the pass bits [T], the tile's live words and the Q filters: <= 144 KiB + 1184 B
-  const size_t lds = ((size_t)p.Q * p.D + (size_t)p.Q * T + T + T / 32 + 2 * (size_t)p.Q) * 4;
-  if (const int rc = raise_lds_limit()) return rc;
-  switch ((p.D / 8 + 63) / 64) {
-    case 1: hipLaunchKernelGGL((search_fscan_kernel<1>), dim3(p.ntile), dim3(T), lds, st, f); break;
-    case 2: hipLaunchKernelGGL((search_fscan_kernel<2>), dim3(p.ntile), dim3(T), lds, st, f); break;
-    case 3: hipLaunchKernelGGL((search_fscan_kernel<3>), dim3(p.ntile), dim3(T), lds, st, f); break;
-    default: hipLaunchKernelGGL((search_fscan_kernel<4>), dim3(p.ntile), dim3(T), lds, st, f); break;
-  }
-  return (int)hipGetLastError();
+  if (const int rc = search_check(f.s)) return rc;
+  if (const int rc = filter_check(f)) return rc;
+  return scan_launch<Bf16Rows, true>(f, st);
 }
 
 // The filtered launcher's refusals with the byte rows' dimension rules: -16 D % 16, -17 D < 16, -18 D > 2048,
 // -19 ldc < D, -23 ldc % 16 (ldc in bytes), -24 scales null, -25 scales not 4-byte aligned.
 extern "C" int hz_search_qscan_launch(const HzSearchQuantParams* pp, hipStream_t st) {
   HzSearchQuantParams qp = *pp;
-  HzSearchFilterParams& f = qp.f;
-  HzSearchParams& p = f.s;
+  HzSearchParams& p = qp.f.s;
   if (p.D < 16) return -17;
   if (p.D % 16) return -16;
   if (p.D > 2048) return -18;
   if (p.ldc < p.D) return -19;
   if (p.ldc % 16) return -23;
   if (const int rc = search_check(p)) return rc;
-  if (!f.live || (reinterpret_cast<uintptr_t>(f.live) & 3)) return -12;
-  if (f.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -13;
-  if (f.filt && !f.tags) return -14;
-  if ((reinterpret_cast<uintptr_t>(f.tags) & 3) || (reinterpret_cast<uintptr_t>(f.filt) & 3)) return -15;
+  if (const int rc = filter_check(qp.f)) return rc;
   if (!qp.scales) return -24;
   if (reinterpret_cast<uintptr_t>(qp.scales) & 3) return -25;
-  // the filtered scan's LDS plus the tile's scales [T]: <= 144 KiB + 1184 B + 1 KiB
-  const size_t lds = ((size_t)p.Q * p.D + (size_t)p.Q * T + T + T / 32 + 2 * (size_t)p.Q + T) * 4;
-  if (const int rc = raise_lds_limit()) return rc;
-  if (p.D <= 1024) hipLaunchKernelGGL((search_qscan_kernel<1>), dim3(p.ntile), dim3(T), lds, st, qp);
-  else hipLaunchKernelGGL((search_qscan_kernel<2>), dim3(p.ntile), dim3(T), lds, st, qp);
-  return (int)hipGetLastError();
+  return scan_launch<E4m3Rows, true>(qp, st);
 }
 
 extern "C" int hz_search_merge_launch(const HzSearchParams* pp, hipStream_t st) {

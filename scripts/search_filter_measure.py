@@ -4,8 +4,7 @@
 D = 768, k = 10, Q = 1, N in {1e5, 1e6}. Every comparison is interleaved round by round on one box.
 
 1. Kernels, launch to launch (device events around ``--launches`` back-to-back pairs): the unfiltered scan +
-   merge (kinds 31 + 32; ``search_scan_kernel``'s instructions are those of the commit before the filtered scan
-   was added, so this is also that commit's kernel) against fscan + merge (kinds 33 + 32) with
+   merge (kinds 31 + 32) against fscan + merge (kinds 33 + 32), both of the library that is loaded, with
    all rows live and no filter; half the rows dead at random; half the rows dead as whole tiles (a random half
    of the tiles, and every other tile: consecutive workgroups go to the 8 XCDs in turn, so that pattern leaves
    the live tiles on half of them); all rows live and a tag filter that passes 1 % of them.
@@ -160,9 +159,8 @@ def main():
              f"Device: {res['device']}, torch {res['torch']}. D = {D}, k = {K}, Q = {Q}, tile = {res['tile_rows']} rows.", "",
              "## Kernels, launch to launch", "",
              f"Device events around {launches} back-to-back (scan, merge) pairs; medians over {rounds} rounds, the variants "
-             "interleaved within each round; in brackets the spread (max - min) over the rounds. `scan` is kinds 31 + 32; "
-             "`search_scan_kernel`'s instructions are unchanged from the commit before this one, so `scan` is also the "
-             "parent's kernel on this box.", "",
+             "interleaved within each round; in brackets the spread (max - min) over the rounds. `scan` is kinds 31 + 32 and "
+             "the other columns kind 33 + 32, all of the library that was loaded for this run.", "",
              "| N | scan + merge (us) | all live, no filter | half dead, random rows | half dead, random whole tiles | "
              "half dead, every other tile | tag filter, 1 % pass |", "|---|---|---|---|---|---|---|"]
     for c in res["kernels"]:

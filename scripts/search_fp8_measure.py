@@ -6,8 +6,7 @@ D = 768, k = 10. Every comparison is interleaved round by round on one box.
 1. Speed, launch to launch (device events around ``--launches`` back-to-back pairs): fscan + merge (kinds 33 + 32)
    over a bf16 corpus against qscan + merge (kinds 34 + 32) over the fp8 corpus of the same vectors, all rows live,
    no filter, N in {1e5, 1e6} and Q in {1, 16}; at the largest N also with a tag filter that passes 1 % of the rows.
-   The bf16 kernels are those of the commit before the fp8 index (their source is untouched), so they run here in
-   the same process. Achieved bytes/s count the row block (and the scales) once.
+   Both are kernels of the library that is loaded and run in the same process. Achieved bytes/s count the row block (and the scales) once.
 2. Quality: recall@10 and the mean absolute score error of the fp8 index and of the bf16 index against the fp64
    truth over the unquantised, normalised fp32 vectors: 1e5 x 768 cosine rows, 1,000 queries drawn like the rows;
    an isotropic Gaussian corpus, and 1,000 Gaussian clusters (centres N(0, I), rows = centre + 0.1 * N(0, I)).
