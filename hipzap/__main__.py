@@ -10,6 +10,7 @@
     python -m hipzap index --vectors v.npy [--labels labels.json] [--metric cosine|ip] --out x.hzidx  # vector index
     python -m hipzap index --embed-plan bert.pth.emb.hzplan --ids ids.npy [--mask mask.npy] --out x.hzidx
     python -m hipzap index --from-index a.hzidx --dtype fp8 --out b.hzidx  # requantise a bf16 index (ids kept)
+    python -m hipzap index --vectors v.npy --dtype fp8 --rescore --out c.hzidx  # fp8 scan + bf16 rescoring (version 4)
     python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
@@ -109,10 +110,13 @@ def cmd_index(a):
     import numpy as np
 
     from .search import convert_index, write_index
+    if a.rescore and a.dtype != "fp8":
+        raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
+                         f"there is nothing to re-score against")
     if a.from_index is not None:
         if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask:
-            raise SystemExit("index: --from-index takes only --dtype and --out")
-        hdr = convert_index(a.from_index, a.out, a.dtype)
+            raise SystemExit("index: --from-index takes only --dtype, --rescore and --out")
+        hdr = convert_index(a.from_index, a.out, a.dtype, rescore=a.rescore)
         print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": "labels" in hdr}))
         return
     if (a.vectors is None) == (a.embed_plan is None):
@@ -136,7 +140,8 @@ def cmd_index(a):
         model = model or be.meta.get("model")
     labels = json.load(open(a.labels)) if a.labels else None
     tags = np.load(a.tags, allow_pickle=False) if a.tags else None
-    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype)
+    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
+                      rescore=a.rescore)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
@@ -216,6 +221,9 @@ def main(argv=None):
     ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")
     ix.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D % 16 == 0)")
+    ix.add_argument("--rescore", action="store_true",
+                    help="with --dtype fp8: also store the bf16 rows (a version-4 file) for two-stage search, "
+                         "fp8 scan then exact bf16 re-scoring of the candidates")
     ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept)")
     ix.add_argument("--model", default=None, help="free text kept in the header")
     ix.add_argument("--device", type=int, default=0)

@@ -36,7 +36,7 @@ KINDS = {
     "HZ_K_QKVATT": 22, "HZ_K_CONV2": 23, "HZ_K_AVGPOOL": 24, "HZ_K_PREPROCESS": 25, "HZ_K_STEP_BUMP": 26,
     "HZ_K_DIAG": 27, "HZ_K_RESIZE_PREPROCESS": 28, "HZ_K_POOL_EMBED": 29,
     "HZ_K_RESIZE_PATCHIFY": 30, "HZ_K_SEARCH_SCAN": 31, "HZ_K_SEARCH_MERGE": 32,
-    "HZ_K_SEARCH_FSCAN": 33, "HZ_K_SEARCH_QSCAN": 34,
+    "HZ_K_SEARCH_FSCAN": 33, "HZ_K_SEARCH_QSCAN": 34, "HZ_K_SEARCH_RESCORE": 35,
 }
 globals().update(KINDS)
 KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct

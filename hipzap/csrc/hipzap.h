@@ -478,6 +478,22 @@ typedef struct HzSearchQuantParams {
   const float* scales;           // fp32 [N], 4-B aligned
 } HzSearchQuantParams;
 int hz_search_qscan_launch(const HzSearchQuantParams* p, hipStream_t st);
+// rescore (HZ_K_SEARCH_RESCORE): the second stage of a two-stage search. One workgroup per query
+// scores the query against the R bf16 rows that `in_id` names (a merge's out_id of stage one; a slot is real
+// iff (unsigned)id < (unsigned)N, every other value is an empty slot and nothing is loaded for it) and writes
+// the best k of them under the order rule; the slots from the number of real candidates to k hold -inf / -1.
+// The score bits of a real (q, r) are those of HZ_K_SEARCH_SCAN for the same query and the same bf16 row.
+// Refusals: the scan's -2 (D, ldc), -3 (N), -4 (Q); -30 R outside 1..HZ_SEARCH_MAX_K, -31 k outside 1..R,
+// -32 a null pointer, -33 rows or queries not 16-B aligned or in_id / out_* not 4-B aligned.
+typedef struct HzSearchRescoreParams {
+  const unsigned short* rows;    // bf16 [N][ldc], 16-B aligned rows; device memory or mapped pinned host memory
+  const float* queries;          // fp32 [Q][D], 16-B aligned
+  const int* in_id;              // int32 [Q][R], -1 in unused slots
+  float* out_score;              // fp32 [Q][k]
+  int* out_id;                   // int32 [Q][k]
+  int N, D, Q, R, k, ldc;
+} HzSearchRescoreParams;
+int hz_search_rescore_launch(const HzSearchRescoreParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
@@ -527,6 +543,23 @@ int hz_index_add_q(void* idx, const unsigned char* codes, const float* scales, l
                    long long* first_id_out);
 int hz_index_read_state_q(void* idx, unsigned char* codes_out, float* scales_out, unsigned* tags_out, unsigned* live_out,
                           long long n);
+// a two-stage index (a version-4 .hzidx): version 3 plus the JSON keys "rescore": "bf16" and
+// "rescore_off", a 4096-aligned block of [count][dim] bf16 rows after every version-3 block -- the rows a bf16
+// index of the same vectors holds. open3 opens any version; for version 4 the bf16 rows go to device memory
+// (rescore_host = 0; open / open2 do this) or to pinned host memory that the rescore kernel reads through its
+// mapped address, which leaves the index at an fp8 index's device bytes. describe2's out[6] is 1 for an index
+// with rescore rows and out[7] their placement (0 device, 1 host).
+void* hz_index_open3(const char* path, int device, int nctx, long long reserve_rows, int rescore_host);
+// refine = 0: hz_index_search_filtered. refine = R, k <= R <= HZ_SEARCH_MAX_K: the fp8 scan and merge at k = R,
+// then HZ_K_SEARCH_RESCORE of those R ids against the bf16 rows -> the best k. -27: the index has no rescore
+// rows; -28: R outside k..HZ_SEARCH_MAX_K (hz_index_last_error says which).
+int hz_index_search2(void* idx, int ctx, const float* queries, const unsigned* filt, int Q, int k, int refine,
+                     float* out_score, int* out_id);
+// append rows to a two-stage index: codes, scales and bf16 rows together, so a row is fully present or absent.
+// -29 (with a message naming the right call): hz_index_add_q on a two-stage index, or this call on any other.
+int hz_index_add_qr(void* idx, const unsigned char* codes, const float* scales, const unsigned short* rows_bf16,
+                    long long n, const unsigned* tags_or_null, long long* first_id_out);
+int hz_index_read_rescore(void* idx, unsigned short* rows_out, long long n);  // the first n bf16 rescore rows
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -707,7 +740,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_SCAN, 31, HzSearchParams, hz_search_scan_op, SEARCH)           \
   X(SEARCH_MERGE, 32, HzSearchParams, hz_search_merge_op, SEARCH)         \
   X(SEARCH_FSCAN, 33, HzSearchFilterParams, hz_search_fscan_op, SEARCH)   \
-  X(SEARCH_QSCAN, 34, HzSearchQuantParams, hz_search_qscan_op, SEARCH)
+  X(SEARCH_QSCAN, 34, HzSearchQuantParams, hz_search_qscan_op, SEARCH)   \
+  X(SEARCH_RESCORE, 35, HzSearchRescoreParams, hz_search_rescore_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

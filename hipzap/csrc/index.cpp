@@ -17,6 +17,11 @@
 // An fp8 index (a version-3 file): the rows are e4m3fn bytes and beside them lies one fp32 scale
 // per row. It ALWAYS replays the quantised-scan program of its (Q, k) -- H2D, qscan, merge, two D2H -- with the
 // filtered programs' N and mask 0 / value 0 when there is no filter; the invalidation rules are the same.
+//
+// A two-stage index (a version-4 file): an fp8 index that also holds its rows as a bf16 index
+// would, in device memory or in pinned host memory that the kernel reads through its mapped address. A search
+// with refine = R replays H2D, qscan at k = R, merge at k = R into the context's intermediate buffer, rescore
+// of those R ids into out_dev, two D2H; refine = 0 replays the fp8 program above. R is part of a program's key.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -57,7 +62,8 @@ struct Ctx {
   uint64_t cand_bytes = 0;
   char* out_dev = nullptr;            // [MAX_Q][MAX_K] fp32 scores, then [MAX_Q][MAX_K] int32 ids
   char* out_host = nullptr;           // pinned, the same layout
-  std::map<std::tuple<int, int, int>, HzProgram> progs;  // (Q, k, filtered)
+  char* mid_dev = nullptr;            // two-stage only: stage one's scores and ids, the layout of out_dev
+  std::map<std::tuple<int, int, int, int>, HzProgram> progs;  // (Q, k, filtered, R; R = 0: one stage)
 };
 
 constexpr size_t kOutHalf = (size_t)HZ_SEARCH_MAX_Q * HZ_SEARCH_MAX_K * 4;
@@ -92,7 +98,11 @@ struct Index {
   bool fp8 = false;                   // a version-3 file: e4m3fn byte rows and `scales`
   unsigned short* rows = nullptr;     // bf16 [cap][dim], or uint8 [cap][dim] of an fp8 index
   float* scales = nullptr;            // device, cap floats (fp8 only)
-  unsigned* live = nullptr;           // device, cap / 32 words
+  bool rescore = false;               // a version-4 file: `rrows` beside the fp8 rows
+  bool rescore_host = false;          // rrows is pinned host memory (hipHostMalloc), else device memory
+  unsigned short* rrows = nullptr;    // bf16 [cap][dim], the allocation
+  unsigned short* rrows_dev = nullptr;  // the address the rescore kernel reads (the mapped address of a host block)
+  unsigned* live = nullptr;          // device, cap / 32 words
   unsigned* tags = nullptr;           // device, cap words
   std::vector<uint32_t> live_host, tags_host;  // mirrors, sized like the device buffers
   std::vector<std::unique_ptr<Ctx>> ctx;
@@ -107,8 +117,10 @@ struct Index {
       if (c->slot_dev) (void)hipFree(c->slot_dev);
       if (c->cand) (void)hipFree(c->cand);
       if (c->out_dev) (void)hipFree(c->out_dev);
+      if (c->mid_dev) (void)hipFree(c->mid_dev);
       if (c->st) (void)hipStreamDestroy(c->st);
     }
+    free_rescore(rrows);
     if (rows) (void)hipFree(rows);
     if (live) (void)hipFree(live);
     if (tags) (void)hipFree(tags);
@@ -118,6 +130,21 @@ struct Index {
   uint64_t esize() const { return fp8 ? 1 : 2; }  // bytes per stored element
   uint64_t row_bytes() const { return cap * h.dim * esize(); }
   uint64_t scan_rows() const { return round_up(count, kTile); }  // the filtered programs' N
+  uint64_t rescore_bytes() const { return rescore ? cap * h.dim * 2 : 0; }
+
+  // a block for the rescore rows in the index's placement: *p the allocation, *dev what a kernel reads
+  bool alloc_rescore(uint64_t bytes, unsigned short** p, unsigned short** dev) const {
+    if (!rescore_host) {
+      if (hipMalloc(reinterpret_cast<void**>(p), bytes) != hipSuccess) return false;
+      *dev = *p;
+      return true;
+    }
+    if (hipHostMalloc(reinterpret_cast<void**>(p), bytes, hipHostMallocMapped) != hipSuccess) return false;
+    return hipHostGetDevicePointer(reinterpret_cast<void**>(dev), *p, 0) == hipSuccess;
+  }
+  void free_rescore(unsigned short* p) const {
+    if (p) (void)(rescore_host ? hipHostFree(p) : hipFree(p));
+  }
 
   void drop_programs() {  // the caller holds every context's mutex
     for (auto& c : ctx) {
@@ -141,9 +168,10 @@ struct Index {
       }
   }
 
-  // the context's program for (Q, k, filtered), built on first use (the caller holds c.mu)
-  HzProgram program(Ctx& c, int Q, int k, bool filtered, bool* fresh) {
-    const auto key = std::make_tuple(Q, k, (int)filtered);
+  // the context's program for (Q, k, filtered, R), built on first use (the caller holds c.mu). R > 0 (a
+  // two-stage index only): stage one runs at k = R into mid_dev and the rescore writes the k results.
+  HzProgram program(Ctx& c, int Q, int k, bool filtered, int R, bool* fresh) {
+    const auto key = std::make_tuple(Q, k, (int)filtered, R);
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
@@ -153,12 +181,20 @@ struct Index {
     p.corpus = rows;
     p.queries = c.q_dev;
     p.cand = c.cand;
-    p.out_score = reinterpret_cast<float*>(c.out_dev);
-    p.out_id = reinterpret_cast<int*>(c.out_dev + kOutHalf);
+    char* stage1 = R ? c.mid_dev : c.out_dev;
+    p.out_score = reinterpret_cast<float*>(stage1);
+    p.out_id = reinterpret_cast<int*>(stage1 + kOutHalf);
     p.N = (int)(filtered ? scan_rows() : count);
     p.D = p.ldc = (int)h.dim;
     p.Q = Q;
-    p.k = k;
+    p.k = R ? R : k;
+    HzSearchRescoreParams rp{};
+    rp.rows = rrows_dev;
+    rp.queries = c.q_dev;
+    rp.in_id = p.out_id;
+    rp.out_score = reinterpret_cast<float*>(c.out_dev);
+    rp.out_id = reinterpret_cast<int*>(c.out_dev + kOutHalf);
+    rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
     p.cand_bytes = c.cand_bytes;
     f.live = live;
     f.tags = tags;
@@ -177,6 +213,7 @@ struct Index {
       if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_SCAN, &p, sizeof(p), 0);
     }
     if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGE, &p, sizeof(p), 0);
+    if (!rc && R) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCORE, &rp, sizeof(rp), 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.out_host, c.out_dev, qk, 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.out_dev + kOutHalf, qk, 0);
     if (rc) {
@@ -194,11 +231,13 @@ struct Index {
     unsigned short* nrows = nullptr;
     unsigned *nlive = nullptr, *ntags = nullptr;
     float* nscales = nullptr;
+    unsigned short *nrr = nullptr, *nrr_dev = nullptr;
     const uint64_t cand_bytes = hz_search_scratch_bytes((long long)new_cap, HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
     if (!cand_bytes) return -21;  // 2^31 rows and above
     std::vector<unsigned long long*> ncand(ctx.size(), nullptr);
     bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * h.dim * esize()) == hipSuccess;
     if (fp8) ok = ok && hipMalloc(reinterpret_cast<void**>(&nscales), new_cap * 4) == hipSuccess;
+    if (rescore) ok = ok && alloc_rescore(new_cap * h.dim * 2, &nrr, &nrr_dev);
     ok = ok && hipMalloc(reinterpret_cast<void**>(&nlive), new_cap / 8) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&ntags), new_cap * 4) == hipSuccess;
     for (size_t i = 0; ok && i < ctx.size(); ++i)
@@ -208,17 +247,24 @@ struct Index {
     if (ok && rows) {
       ok = hipMemcpyAsync(nrows, rows, count * h.dim * esize(), hipMemcpyDeviceToDevice, st) == hipSuccess;
       if (fp8) ok = ok && hipMemcpyAsync(nscales, scales, count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+      if (rescore && !rescore_host)
+        ok = ok && hipMemcpyAsync(nrr, rrows, count * h.dim * 2, hipMemcpyDeviceToDevice, st) == hipSuccess;
       ok = ok && hipMemcpyAsync(ntags, tags, count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
       ok = ok && hipMemcpyAsync(nlive, live, round_up(count, 32) / 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
     }
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
     if (!ok) {
       (void)hipFree(nrows), (void)hipFree(nlive), (void)hipFree(ntags), (void)hipFree(nscales);
+      free_rescore(nrr);
       for (auto* p : ncand) (void)hipFree(p);
       return -22;
     }
+    // a host block is copied by the CPU: no search runs (the caller holds the contexts) and the stream is idle
+    if (rescore && rescore_host && rrows) std::memcpy(nrr, rrows, count * h.dim * 2);
     (void)hipFree(rows), (void)hipFree(live), (void)hipFree(tags), (void)hipFree(scales);
+    free_rescore(rrows);
     rows = nrows, live = nlive, tags = ntags, scales = nscales, cap = new_cap;
+    rrows = nrr, rrows_dev = nrr_dev;
     for (size_t i = 0; i < ctx.size(); ++i) {
       (void)hipFree(ctx[i]->cand);
       ctx[i]->cand = ncand[i];
@@ -250,7 +296,7 @@ extern "C" {
 
 const char* hz_index_last_error(void) { return g_err.c_str(); }
 
-void* hz_index_open2(const char* path, int device, int nctx, long long reserve_rows) {
+void* hz_index_open3(const char* path, int device, int nctx, long long reserve_rows, int rescore_host) {
   g_err.clear();
   if (nctx <= 0) nctx = 2;
   if (nctx > 16) return fail("index: at most 16 contexts");
@@ -261,14 +307,14 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && (h.version == 2 || h.version == 3) && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 4 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 3) return fail("index: unknown format version " + std::to_string(h.version));
-  const bool fp8 = h.version == 3;
+  if (h.version < 1 || h.version > 4) return fail("index: unknown format version " + std::to_string(h.version));
+  const bool fp8 = h.version >= 3, rescore = h.version == 4;
   if (fp8 && (h.dim < 16 || h.dim % 16 || h.dim > 2048))
     return fail("index: dim of an fp8 index must be a multiple of 16 in 16..2048");
   if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
@@ -290,19 +336,32 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
     if (t != l) return fail("index: a version-3 file with only one of tags_off / live_off");
     blocks = t;
   }
+  uint64_t rescore_off = 0;
+  const uint64_t rescore_len = h.count * h.dim * 2;
+  if (fp8) {
+    const bool off = json_u64(js, "rescore_off", &rescore_off, true);
+    const bool key = js.rfind("\"rescore\": \"bf16\"") != std::string::npos;
+    if (rescore && !(off && key)) return fail("index: a version-4 file without rescore / rescore_off");
+    if (!rescore && (off || key)) return fail("index: a version-3 file with rescore keys (they belong to version 4)");
+  }
   if (blocks) {
     if (!fp8 && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
       return fail("index: a version-2 file without tags_off / live_off");
     if (tags_off % 4096 || live_off % 4096 || tags_off < after_rows || live_off < after_rows ||
         tags_off > fsize || tag_bytes > fsize - tags_off || live_off > fsize || live_bytes > fsize - live_off)
       return fail("index: tags or live block outside the file");
+    after_rows = std::max(after_rows, std::max(tags_off + tag_bytes, live_off + live_bytes));
   }
+  if (rescore && (rescore_off % 4096 || rescore_off < after_rows || rescore_off > fsize || rescore_len > fsize - rescore_off))
+    return fail("index: rescore block unaligned, overlapping another block or outside the file");
   if (hipSetDevice(device) != hipSuccess) return fail("index: hipSetDevice failed");
   auto idx = std::make_unique<Index>();
   idx->device = device;
   idx->h = h;
   idx->count = h.count;
   idx->fp8 = fp8;
+  idx->rescore = rescore;
+  idx->rescore_host = rescore && rescore_host != 0;
   if (hz_search_code_warm()) return fail("index: device code load failed");
   for (int i = 0; i < nctx; ++i) {
     auto c = std::make_unique<Ctx>();
@@ -312,6 +371,7 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
     ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->out_host), 2 * kOutHalf, hipHostMallocDefault) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->slot_dev), sb_) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->out_dev), 2 * kOutHalf) == hipSuccess;
+    if (rescore) ok = ok && hipMalloc(reinterpret_cast<void**>(&c->mid_dev), 2 * kOutHalf) == hipSuccess;
     if (ok) {
       std::memset(c->slot_host, 0, sb_);
       c->q_host = reinterpret_cast<float*>(c->slot_host + kFiltBytes);
@@ -348,7 +408,26 @@ void* hz_index_open2(const char* path, int device, int nctx, long long reserve_r
     if (push_words(idx->live, idx->live_host, 0, words, st) || hipStreamSynchronize(st) != hipSuccess)
       return fail("index: upload failed");
   }
+  if (rescore && idx->rescore_host) {  // the file's block straight into the pinned rows
+    const int rfd = open(path, O_RDONLY | O_CLOEXEC);
+    uint64_t done = 0;
+    while (rfd >= 0 && done < rescore_len) {
+      const ssize_t n = pread(rfd, reinterpret_cast<char*>(idx->rrows) + done, rescore_len - done, (off_t)(rescore_off + done));
+      if (n <= 0) break;
+      done += (uint64_t)n;
+    }
+    if (rfd >= 0) close(rfd);
+    if (done != rescore_len) return fail("index: cannot read the rescore block");
+  } else if (rescore) {
+    void* dst[1] = {idx->rrows};
+    if (hz_upload_file(path, 1, &rescore_off, &rescore_len, dst, st) || hipStreamSynchronize(st) != hipSuccess)
+      return fail(std::string("index: rescore upload failed: ") + hz_plan_last_error());
+  }
   return idx.release();
+}
+
+void* hz_index_open2(const char* path, int device, int nctx, long long reserve_rows) {
+  return hz_index_open3(path, device, nctx, reserve_rows, 0);
 }
 
 void* hz_index_open(const char* path, int device, int nctx) { return hz_index_open2(path, device, nctx, 0); }
@@ -358,9 +437,10 @@ int hz_index_describe(void* h, uint64_t* out) {
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
   uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4 + (x->fp8 ? x->cap * 4 : 0);
+  if (!x->rescore_host) dev += x->rescore_bytes();
   for (auto& c : x->ctx) {
     progs += c->progs.size();
-    dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf;
+    dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf + (c->mid_dev ? 2 * kOutHalf : 0);
   }
   const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
   std::memcpy(out, v, sizeof(v));
@@ -371,24 +451,34 @@ int hz_index_describe2(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
-  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->fp8 ? 1u : 0u, 0, 0};
+  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->fp8 ? 1u : 0u,
+                       x->rescore ? 1u : 0u, x->rescore_host ? 1u : 0u};
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
 
-int hz_index_search_filtered(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, float* out_score,
-                             int* out_id) {
+int hz_index_search2(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, int refine,
+                     float* out_score, int* out_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !queries || !out_score || !out_id) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
   if (Q < 1 || Q > HZ_SEARCH_MAX_Q) return -4;
   if (k < 1 || k > HZ_SEARCH_MAX_K) return -5;
+  if (refine && !x->rescore) {
+    g_err = std::string("index: refine needs rescore rows (a version-4 file), the index holds ") +
+            (x->fp8 ? "fp8_e4m3" : "bf16") + " rows only";
+    return -27;
+  }
+  if (refine && (refine < k || refine > HZ_SEARCH_MAX_K)) {
+    g_err = "index: refine must be 0 or in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(refine);
+    return -28;
+  }
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   const bool filtered = x->fp8 || x->mutated || filt != nullptr;
   bool fresh = false;
-  HzProgram g = x->program(c, Q, k, filtered, &fresh);
+  HzProgram g = x->program(c, Q, k, filtered, refine, &fresh);
   if (!g) return -11;
   std::memcpy(c.q_host, queries, (size_t)Q * x->h.dim * 4);
   if (filtered) {  // no filter: mask 0, value 0 passes every tag
@@ -408,6 +498,11 @@ int hz_index_search_filtered(void* h, int ctx, const float* queries, const unsig
   return rc;
 }
 
+int hz_index_search_filtered(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, float* out_score,
+                             int* out_id) {
+  return hz_index_search2(h, ctx, queries, filt, Q, k, 0, out_score, out_id);
+}
+
 int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float* out_score, int* out_id) {
   return hz_index_search_filtered(h, ctx, queries, nullptr, Q, k, out_score, out_id);
 }
@@ -416,8 +511,10 @@ int hz_index_search(void* h, int ctx, const float* queries, int Q, int k, float*
 
 namespace {
 
-// hz_index_add / hz_index_add_q: `data` holds n rows in the index's own format, `scales` n floats (fp8) or NULL
-int add_rows(Index* x, const void* data, const float* scales, long long n, const unsigned* tags, long long* first_id) {
+// hz_index_add / hz_index_add_q / hz_index_add_qr: `data` holds n rows in the index's own format, `scales` n
+// floats (fp8) or NULL, `rr` the n bf16 rescore rows (a two-stage index) or NULL
+int add_rows(Index* x, const void* data, const float* scales, const unsigned short* rr, long long n, const unsigned* tags,
+             long long* first_id) {
   AllLocked all(*x);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   const uint64_t first = x->count, last = first + (uint64_t)n;
@@ -434,6 +531,10 @@ int add_rows(Index* x, const void* data, const float* scales, long long n, const
   const uint64_t rb = x->h.dim * x->esize();
   int rc = (int)hipMemcpyAsync(reinterpret_cast<char*>(x->rows) + first * rb, data, (uint64_t)n * rb, hipMemcpyHostToDevice, st);
   if (!rc && scales) rc = (int)hipMemcpyAsync(x->scales + first, scales, (uint64_t)n * 4, hipMemcpyHostToDevice, st);
+  if (!rc && rr) {  // like the other halves: dead above `count` until the live bits are set
+    if (x->rescore_host) std::memcpy(x->rrows + first * x->h.dim, rr, (uint64_t)n * x->h.dim * 2);
+    else rc = (int)hipMemcpyAsync(x->rrows + first * x->h.dim, rr, (uint64_t)n * x->h.dim * 2, hipMemcpyHostToDevice, st);
+  }
   if (!rc) rc = push_words(x->tags, x->tags_host, first, last, st);
   if (!rc) rc = (int)hipStreamSynchronize(st);
   if (rc) return rc;
@@ -471,7 +572,7 @@ int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const un
   Index* x = static_cast<Index*>(h);
   if (!x || !rows_bf16 || n < 1) return -1;
   if (x->fp8) return wrong_dtype(x, "hz_index_add", "bf16");
-  return add_rows(x, rows_bf16, nullptr, n, tags, first_id);
+  return add_rows(x, rows_bf16, nullptr, nullptr, n, tags, first_id);
 }
 
 int hz_index_add_q(void* h, const unsigned char* codes, const float* scales, long long n, const unsigned* tags,
@@ -479,7 +580,23 @@ int hz_index_add_q(void* h, const unsigned char* codes, const float* scales, lon
   Index* x = static_cast<Index*>(h);
   if (!x || !codes || !scales || n < 1) return -1;
   if (!x->fp8) return wrong_dtype(x, "hz_index_add_q", "fp8_e4m3");
-  return add_rows(x, codes, scales, n, tags, first_id);
+  if (x->rescore) {
+    g_err = "index: hz_index_add_q adds fp8 rows only; an index with rescore rows takes hz_index_add_qr (codes, scales and bf16 rows)";
+    return -29;
+  }
+  return add_rows(x, codes, scales, nullptr, n, tags, first_id);
+}
+
+int hz_index_add_qr(void* h, const unsigned char* codes, const float* scales, const unsigned short* rows_bf16, long long n,
+                    const unsigned* tags, long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !codes || !scales || !rows_bf16 || n < 1) return -1;
+  if (!x->fp8) return wrong_dtype(x, "hz_index_add_qr", "fp8_e4m3");
+  if (!x->rescore) {
+    g_err = "index: hz_index_add_qr needs an index with rescore rows (a version-4 file); use hz_index_add_q";
+    return -29;
+  }
+  return add_rows(x, codes, scales, rows_bf16, n, tags, first_id);
 }
 
 int hz_index_delete(void* h, const int* ids, long long n, long long* newly_deleted) {
@@ -564,6 +681,23 @@ int hz_index_read_state_q(void* h, unsigned char* codes_out, float* scales_out, 
   if (!x || n < 0) return -1;
   if (!x->fp8) return wrong_dtype(x, "hz_index_read_state_q", "fp8_e4m3");
   return read_state(x, codes_out, scales_out, tags_out, live_out, n);
+}
+
+// the first n (<= count) rescore rows back to the host (for save)
+int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !rows_out || n < 0) return -1;
+  AllLocked all(*x);
+  if (!x->rescore) {
+    g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-4 file)";
+    return -29;
+  }
+  if ((uint64_t)n > x->count) return -20;
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  const uint64_t bytes = (uint64_t)n * x->h.dim * 2;
+  if (x->rescore_host) std::memcpy(rows_out, x->rrows, bytes);
+  else if (n) return (int)hipMemcpy(rows_out, x->rrows, bytes, hipMemcpyDeviceToHost);
+  return 0;
 }
 
 void hz_index_close(void* h) { delete static_cast<Index*>(h); }

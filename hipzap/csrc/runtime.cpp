@@ -443,6 +443,10 @@ extern "C" __attribute__((weak)) int hz_search_qscan_launch(const HzSearchQuantP
 static int hz_search_qscan_op(const HzSearchQuantParams* p, hipStream_t st) {
   return hz_search_qscan_launch ? hz_search_qscan_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_rescore_launch(const HzSearchRescoreParams* p, hipStream_t st);
+static int hz_search_rescore_op(const HzSearchRescoreParams* p, hipStream_t st) {
+  return hz_search_rescore_launch ? hz_search_rescore_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

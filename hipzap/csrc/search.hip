@@ -407,6 +407,105 @@ __global__ __launch_bounds__(MERGE_THREADS) void search_merge_kernel(const HzSea
   }
 }
 
+// ---------------------------------------------------------------------------------------- rescore
+// search_rescore_kernel<NC>: the second stage of a two-stage search. Workgroup q scores query q
+// against the R rows that in_id[q][0 .. R) names and writes the best k of them. A slot is real iff
+// (unsigned)id < (unsigned)N; every other value (the merge's -1 of an unused slot) is an empty slot: nothing is
+// loaded for it and its score is the sentinel 0. Wave w takes the slots w*ROWS .. w*ROWS + ROWS - 1, then the
+// next RESCORE_THREADS / 64 * ROWS on, their 16-byte loads in flight together; the group's scores come from
+// score_group<Bf16Rows, NC> with one query, so a real (q, r) has the bits of HZ_K_SEARCH_SCAN for that query and
+// row. Thread t < R then ranks slot t among the R: higher score first, then the lower id, then the lower slot
+// (stage one's ids are distinct; the slot only keeps ranks distinct when a caller repeats an id). The slots
+// ranked below k write out[rank]; the slots from the number of real candidates to k get -inf / -1.
+// 512 threads: R = 128 is 32 groups of ROWS, four per wave, and up to 8 x ROWS rows are in flight per query --
+// the launch is latency-bound (at most 16 workgroups, rows that may lie in pinned host memory), not
+// occupancy-bound; 1024 threads would halve the register budget that NC = 4 needs for its 16 chunks in flight.
+// Addresses: queries[q*D + i] under i < D, in_id[q*R + t] under t < R, rows[id*ldc + chunk*8 ..] under
+// (unsigned)id < (unsigned)N and chunk < D / 8 -- the one data-dependent address --, out_*[q*k + s] under s < k.
+constexpr int RESCORE_THREADS = 512;
+static_assert(HZ_SEARCH_MAX_K % ROWS == 0 && HZ_SEARCH_MAX_K <= T, "a group never reads past ids[] / sc[]");
+
+template <int NC>
+__global__ __launch_bounds__(RESCORE_THREADS) void search_rescore_kernel(const HzSearchRescoreParams a) {
+  __shared__ __attribute__((aligned(16))) float qs[2048];  // the query
+  __shared__ unsigned sc[HZ_SEARCH_MAX_K];                  // orderable scores, 0 for an empty slot
+  __shared__ int ids[HZ_SEARCH_MAX_K];                      // in_id[q], -1 past R
+  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int nch = a.D >> 3;
+  if (!HZ_DCHECK(q < a.Q && a.D >= 8 && a.D % 8 == 0 && a.D <= NC * 64 * 8 && a.D <= 2048 && a.ldc >= a.D && a.N >= 1 &&
+                 a.R >= 1 && a.R <= HZ_SEARCH_MAX_K && a.k >= 1 && a.k <= a.R))
+    return;
+  for (int i = t; i < a.D >> 2; i += RESCORE_THREADS)
+    if (HZ_DCHECK((long)q * a.D + 4 * i + 4 <= (long)a.Q * a.D))
+      reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(a.queries + (long)q * a.D)[i];
+  if (t < HZ_SEARCH_MAX_K) {
+    int id = -1;
+    if (t < a.R && HZ_DCHECK((long)q * a.R + t < (long)a.Q * a.R)) id = a.in_id[(long)q * a.R + t];
+    ids[t] = id;
+  }
+  __syncthreads();
+
+  HzSearchParams one{};  // what score_group reads of the scan's block: one query of D values
+  one.Q = 1, one.D = a.D;
+  for (int r0 = w * ROWS; r0 < a.R; r0 += RESCORE_THREADS / 64 * ROWS) {  // wave-uniform bounds
+    GroupPass<true> pass;
+    int id[ROWS];
+    unsigned any = 0u;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {  // r0 + r < HZ_SEARCH_MAX_K: the slots past R hold -1
+      id[r] = __builtin_amdgcn_readfirstlane(ids[r0 + r]);
+      pass.pm[r] = (unsigned)id[r] < (unsigned)a.N ? 1u : 0u;
+      any |= pass.pm[r];
+    }
+    if (any == 0u) {  // scalar: nothing of this group is loaded or scored
+      if (lane < ROWS && r0 + lane < a.R) sc[r0 + lane] = 0u;
+      continue;
+    }
+    u32x4 v[ROWS][NC];  // this lane's chunks of the group's rows, zeros where nothing is loaded
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        v[r][c] = u32x4{0u, 0u, 0u, 0u};
+        if (pass.row(r) && c * 64 + lane < nch &&
+            HZ_DCHECK(id[r] >= 0 && id[r] < a.N && (long)id[r] * a.ldc + (c * 64 + lane) * 8 + 8 <= ((long)a.N - 1) * a.ldc + a.D))
+          v[r][c] = *reinterpret_cast<const u32x4*>(a.rows + (long)id[r] * a.ldc + (c * 64 + lane) * 8);
+      }
+    score_group<Bf16Rows, NC>(one, qs, sc, nullptr, v, pass, lane, nch, r0, a.R);
+  }
+  __syncthreads();
+
+  if (t < a.R) {
+    const unsigned mine = sc[t];
+    const int me = ids[t];
+    int rank = 0, nreal = 0;
+    for (int j = 0; j < a.R; ++j) {  // every lane reads the same words: LDS broadcasts
+      const unsigned o = sc[j];
+      const int oid = ids[j];
+      rank += (o > mine) || (o == mine && (oid < me || (oid == me && j < t)));
+      nreal += o != 0u;
+    }
+    const long at = (long)q * a.k;
+    if (mine != 0u && rank < a.k && HZ_DCHECK(at + rank < (long)a.Q * a.k)) {  // real keys only above a real key
+      a.out_score[at + rank] = unorderable(mine);
+      a.out_id[at + rank] = me;
+    }
+    if (t >= nreal && t < a.k && HZ_DCHECK(at + t < (long)a.Q * a.k)) {
+      a.out_score[at + t] = -__builtin_inff();
+      a.out_id[at + t] = -1;
+    }
+  }
+}
+
+template <int NC = 1>
+void rescore_dispatch(const HzSearchRescoreParams& a, hipStream_t st) {
+  if constexpr (NC < Bf16Rows::MAX_NC) {
+    if (a.D > NC * 64 * Bf16Rows::E) return rescore_dispatch<NC + 1>(a, st);
+  }
+  hipLaunchKernelGGL(search_rescore_kernel<NC>, dim3(a.Q), dim3(RESCORE_THREADS), 0, st, a);
+}
+
 // one refusal list for both launchers: the kernels then have no address that the data can move out of
 // its buffer. Fills ntile.
 int search_check(HzSearchParams& p) {
@@ -516,6 +615,24 @@ extern "C" int hz_search_merge_launch(const HzSearchParams* pp, hipStream_t st) 
   HzSearchParams p = *pp;
   if (const int rc = search_check(p)) return rc;
   hipLaunchKernelGGL(search_merge_kernel, dim3(p.Q), dim3(MERGE_THREADS), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+// The scan's D / ldc (-2), N (-3) and Q (-4) rules; then -30 R outside 1..HZ_SEARCH_MAX_K, -31 k outside 1..R,
+// -32 a null pointer, -33 rows or queries not 16-B aligned or in_id / out_* not 4-B aligned.
+extern "C" int hz_search_rescore_launch(const HzSearchRescoreParams* pp, hipStream_t st) {
+  const HzSearchRescoreParams a = *pp;
+  if (a.D < 8 || a.D % 8 || a.D > 2048 || a.ldc < a.D || a.ldc % 8) return -2;
+  if (a.N < 1) return -3;
+  if (a.Q < 1 || a.Q > HZ_SEARCH_MAX_Q) return -4;
+  if (a.R < 1 || a.R > HZ_SEARCH_MAX_K) return -30;
+  if (a.k < 1 || a.k > a.R) return -31;
+  if (!a.rows || !a.queries || !a.in_id || !a.out_score || !a.out_id) return -32;
+  if ((reinterpret_cast<uintptr_t>(a.rows) & 15) || (reinterpret_cast<uintptr_t>(a.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.in_id) & 3) || (reinterpret_cast<uintptr_t>(a.out_score) & 3) ||
+      (reinterpret_cast<uintptr_t>(a.out_id) & 3))
+    return -33;
+  rescore_dispatch(a, st);
   return (int)hipGetLastError();
 }
 

@@ -6,6 +6,8 @@ query into ``cand``) and ``HZ_K_SEARCH_MERGE`` (one workgroup per query, ``ntile
 ``k``). ``HZ_K_SEARCH_FSCAN`` (``FilterScanParams``: the same block plus a live bitmap, per-row tags and
 per-query ``{mask, value}`` filters) is the scan over the rows that pass. ``HZ_K_SEARCH_QSCAN``
 (``QuantScanParams``: that block plus one fp32 scale per row) is the filtered scan over rows of OCP e4m3fn bytes.
+``HZ_K_SEARCH_RESCORE`` (``RescoreParams``) is the second stage of a two-stage search: one workgroup per query
+re-scores the ``R`` bf16 rows that a merge's ``out_id`` names and writes the best ``k`` of them.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -47,6 +49,15 @@ class QuantScanParams(C.Structure):
         return SearchParams.from_buffer_copy(self)
 
 
+@N.params_of("HZ_K_SEARCH_RESCORE")
+class RescoreParams(C.Structure):
+    """HzSearchRescoreParams: ``rows`` bf16 [N][ldc] (device or mapped pinned host memory), ``queries`` fp32
+    [Q][D], ``in_id`` int32 [Q][R] (-1: an empty slot), the outputs [Q][k]."""
+    _fields_ = [("rows", C.c_void_p), ("queries", C.c_void_p), ("in_id", C.c_void_p), ("out_score", C.c_void_p),
+                ("out_id", C.c_void_p), ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("R", C.c_int),
+                ("k", C.c_int), ("ldc", C.c_int)]
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -55,6 +66,7 @@ def _sigs(lib):
     N._sig(lib, "hz_search_merge_launch", C.c_int, C.POINTER(SearchParams), P)
     N._sig(lib, "hz_search_fscan_launch", C.c_int, C.POINTER(FilterScanParams), P)
     N._sig(lib, "hz_search_qscan_launch", C.c_int, C.POINTER(QuantScanParams), P)
+    N._sig(lib, "hz_search_rescore_launch", C.c_int, C.POINTER(RescoreParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
     N._sig(lib, "hz_index_last_error", C.c_char_p)
     N._sig(lib, "hz_index_open", P, C.c_char_p, C.c_int, C.c_int)
@@ -70,6 +82,10 @@ def _sigs(lib):
     N._sig(lib, "hz_index_read_state", C.c_int, P, P, P, P, C.c_longlong)
     N._sig(lib, "hz_index_add_q", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_read_state_q", C.c_int, P, P, P, P, P, C.c_longlong)
+    N._sig(lib, "hz_index_open3", P, C.c_char_p, C.c_int, C.c_int, C.c_longlong, C.c_int)
+    N._sig(lib, "hz_index_search2", C.c_int, P, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P)
+    N._sig(lib, "hz_index_add_qr", C.c_int, P, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_read_rescore", C.c_int, P, P, C.c_longlong)
 
 
 N._EXTRA_SIGS.append(_sigs)
@@ -112,3 +128,8 @@ def launch_quant(prm: QuantScanParams, stream: int = 0) -> tuple:
         return rc, None
     sp = prm.scan_params()
     return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def launch_rescore(prm: RescoreParams, stream: int = 0) -> int:
+    """The rescore launch on ``stream`` -> its code (0, or negative for a refused block: nothing ran)."""
+    return int(N.lib().hz_search_rescore_launch(C.byref(prm), stream))

@@ -13,7 +13,11 @@ file opens as all live with zero tags. Version 3 is an fp8 index (``dtype`` ``"f
 ``[count][dim]`` OCP e4m3fn bytes (``dim % 16 == 0``) and the JSON key ``scales_off`` names a 4096-aligned
 block of ``count`` little-endian fp32 scales after them; row r stands for ``scales[r] * decode(codes[r])``
 (:func:`prepare_rows_fp8`). ``capacity``, ``tags_off`` and ``live_off`` are present exactly when version 2
-would have them, their blocks after the scales.
+would have them, their blocks after the scales. Version 4 is version 3 plus the JSON keys ``"rescore": "bf16"``
+and ``rescore_off``: a 4096-aligned block of ``[count][dim]`` bf16 rows after every version-3 block, the rows a
+bf16 index of the same vectors holds (``write_index(dtype="fp8", rescore=True)``). A search of such an index is
+two-stage (``search(refine=R)``): the fp8 rows give the best R candidates, which are re-scored against the bf16
+rows; the best k of them are returned.
 
 A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
 positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
@@ -39,6 +43,7 @@ MAGIC = b"HZIDX\0\0\1"
 VERSION = 1
 VERSION2 = 2  # version 1 plus the JSON keys capacity / tags_off / live_off and their two blocks
 VERSION3 = 3  # fp8 rows: uint8 codes, the JSON key scales_off and its block; tags / live as in version 2, or absent
+VERSION4 = 4  # version 3 plus the JSON keys rescore / rescore_off and the block of bf16 rows they name
 DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3"}  # write_index(dtype=...) -> the header's "dtype"
 FP8 = "fp8_e4m3"
 METRICS = ("cosine", "ip")
@@ -160,11 +165,15 @@ def unpack_live(words, n: int) -> np.ndarray:
     return np.unpackbits(np.ascontiguousarray(words, "<u4").view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
-def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None, scales=None) -> dict:
+def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None, scales=None,
+                rescore=None) -> dict:
     """The file of ``hdr`` and ``rows``: version 1 without ``tags`` / ``live``, else version 2 (zero tags / all
     live where one is missing); with ``scales`` (fp8 rows) version 3, whose tags and bitmap are present under
-    the same rule. Atomic: a temporary file, then a rename. Returns the JSON header written."""
+    the same rule; with ``rescore`` as well (bf16 bit patterns [N, D]) version 4, their block last.
+    Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
+    if rescore is not None and (scales is None or rescore.shape != rows.shape or rescore.dtype != np.uint16):
+        raise ValueError("rescore rows go with fp8 rows of the same shape")
 
     def align(x):
         return -(-x // ALIGN) * ALIGN
@@ -173,13 +182,15 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
-        version = VERSION2 if scales is None else VERSION3
+        version = VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
         if scales is not None:
             hdr = dict(hdr, scales_off=0)
         if blocks:
             tags = np.zeros(n, np.uint32) if tags is None else tags
             words = pack_live(np.ones(n, bool) if live is None else live)
             hdr = dict(hdr, capacity=int(max(capacity or 0, n)), tags_off=0, live_off=0)
+        if rescore is not None:
+            hdr = dict(hdr, rescore="bf16", rescore_off=0)
         while True:  # the offsets follow the JSON's own length: a few rounds until they agree
             js = json.dumps(hdr).encode()
             data_off = align(HEAD.size + len(js))
@@ -191,6 +202,9 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             if blocks:
                 offs["tags_off"] = tags_off = align(end)
                 offs["live_off"] = live_off = align(tags_off + 4 * n)
+                end = live_off + words.nbytes
+            if rescore is not None:
+                offs["rescore_off"] = align(end)
             if all(hdr[k] == v for k, v in offs.items()):
                 break
             hdr.update(offs)
@@ -210,19 +224,27 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             f.write(tags.astype("<u4").tobytes())
             f.write(bytes(live_off - tags_off - 4 * n))
             f.write(words.astype("<u4").tobytes())
+            at = live_off + words.nbytes
+        if rescore is not None:
+            f.write(bytes(hdr["rescore_off"] - at))
+            f.write(np.ascontiguousarray(rescore).astype("<u2").tobytes())
     os.replace(tmp, path)
     return hdr
 
 
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
-                dtype: str = "bf16") -> dict:
+                dtype: str = "bf16", rescore: bool = False) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
-    scale per row (:func:`prepare_rows_fp8`), a version-3 file."""
+    scale per row (:func:`prepare_rows_fp8`), a version-3 file; with ``rescore=True`` a version-4 file, which
+    also holds the rows of the bf16 index of the same vectors (:func:`prepare_rows`) for the second stage."""
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    if rescore and dtype != "fp8":
+        raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
     rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
+    rrows = prepare_rows(vectors, metric) if rescore else None
     n, d = rows.shape
     if labels is not None:
         labels = [str(s) for s in labels]
@@ -234,7 +256,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
            "embed": dict(embed) if embed else None}
     if labels is not None:
         hdr["labels"] = labels
-    return _write_file(path, hdr, rows, tags, scales=scales)
+    return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows)
 
 
 def read_header(path: str) -> dict:
@@ -244,16 +266,21 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version not in (VERSION, VERSION2, VERSION3):
+        if version not in (VERSION, VERSION2, VERSION3, VERSION4):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
     if metric >= len(METRICS) or (hdr.get("dim"), hdr.get("count"), hdr.get("metric")) != (dim, count, METRICS[metric]) \
             or hdr.get("dtype") not in DTYPES.values():
         raise ValueError(f"{path}: the JSON header disagrees with the file head")
-    fp8 = version == VERSION3
+    fp8 = version in (VERSION3, VERSION4)
     if (hdr["dtype"] == FP8) != fp8:
-        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (version 3 means fp8_e4m3 rows)")
+        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (version 3 means fp8_e4m3 rows, and so does "
+                         f"version 4)")
+    if version == VERSION4 and (hdr.get("rescore") != "bf16" or "rescore_off" not in hdr):
+        raise ValueError(f"{path}: a version-4 file without rescore / rescore_off")
+    if version != VERSION4 and ("rescore" in hdr or "rescore_off" in hdr):
+        raise ValueError(f"{path}: rescore keys in a version-{version} file (they belong to version 4)")
     if fp8 and (dim < 16 or dim % 16 or dim > 2048):
         raise ValueError(f"{path}: dim of an fp8 index must be a multiple of 16 in 16..2048, got {dim}")
     if hdr.get("labels") is not None and len(hdr["labels"]) != count:
@@ -270,13 +297,23 @@ def read_header(path: str) -> dict:
         end = off + 4 * count
         if ("tags_off" in hdr) != ("live_off" in hdr):
             raise ValueError(f"{path}: a version-3 file with only one of tags_off / live_off")
+    last = end  # the end of the last block before a rescore block
     if version == VERSION2 or (fp8 and "tags_off" in hdr):
         for key, nbytes in (("tags_off", 4 * count), ("live_off", 4 * (-(-count // 32)))):
             off = hdr.get(key)
             if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
                 raise ValueError(f"{path}: the {key[:4]} block lies outside the file")
+            last = max(last, off + nbytes)
         if not isinstance(hdr.get("capacity"), int) or hdr["capacity"] < count:
             raise ValueError(f"{path}: capacity below count")
+    if version == VERSION4:
+        off = hdr["rescore_off"]
+        if not isinstance(off, int) or isinstance(off, bool) or off % ALIGN:
+            raise ValueError(f"{path}: rescore_off {off!r} is not a multiple of {ALIGN}")
+        if off < last:
+            raise ValueError(f"{path}: the rescore block at {off} overlaps another block, which ends at {last}")
+        if off + 2 * count * dim > size:
+            raise ValueError(f"{path}: the rescore block lies outside the file")
     return dict(hdr, data_off=int(data_off))
 
 
@@ -304,6 +341,8 @@ def file_info(path: str) -> dict:
             "live": int(read_live(path).sum()), "tags": v2}
     if hdr["dtype"] == FP8:
         info.update(version=VERSION3, dtype=FP8)
+    if "rescore_off" in hdr:
+        info.update(version=VERSION4, rescore=hdr["rescore"])
     return info
 
 
@@ -320,6 +359,28 @@ def read_scales(path: str) -> np.ndarray:
     if hdr["dtype"] != FP8:
         raise ValueError(f"{path}: a {hdr['dtype']} index has no scales")
     return np.fromfile(path, "<f4", hdr["count"], offset=hdr["scales_off"]).astype(np.float32)
+
+
+def read_rescore_rows(path: str) -> np.ndarray:
+    """The rescore block of a version-4 index: bf16 bit patterns, uint16 [count, dim]."""
+    hdr = read_header(path)
+    if "rescore_off" not in hdr:
+        raise ValueError(f"{path}: a {hdr['dtype']} index without rescore rows (version 4 holds them)")
+    return np.fromfile(path, "<u2", hdr["count"] * hdr["dim"], offset=hdr["rescore_off"]) \
+        .astype(np.uint16).reshape(hdr["count"], hdr["dim"])
+
+
+def rescore_ref(rrows, q, ids, k: int):
+    """The oracle's second stage: query ``q`` ([D]) against the candidates ``ids`` (stage one's, -1 in unused
+    slots) of ``rrows`` (the bf16 rescore rows widened to fp32, [N, D]) in fp64 -> (scores float64 [k], ids int32
+    [k]) under the order rule."""
+    ids = np.asarray(ids)
+    ids = ids[ids >= 0]
+    s = (np.asarray(rrows[ids], np.float64) * np.asarray(q, np.float64)[None, :]).sum(axis=1) + 0.0
+    order = np.lexsort((ids, -s))[:k]  # higher score first, then the lower id
+    scores, out = np.full(k, -np.inf), np.full(k, -1, np.int32)
+    scores[:order.size], out[:order.size] = s[order], ids[order]
+    return scores, out
 
 
 def search_ref(corpus, q, k: int, allow=None, scales=None):
@@ -402,16 +463,19 @@ def check_filter(filter, nq: int):
 
 
 class _QRows:
-    """What ``add`` hands a backend's ``_append`` on an fp8 index: the codes and their row scales."""
+    """What ``add`` hands a backend's ``_append`` on an fp8 index: the codes and their row scales; on an index
+    with rescore rows also ``rescore``, the bf16 bit patterns of the same input."""
 
-    def __init__(self, codes, scales):
+    def __init__(self, codes, scales, rescore=None):
         self.codes, self.scales, self.shape = np.ascontiguousarray(codes), np.ascontiguousarray(scales, np.float32), codes.shape
+        self.rescore = None if rescore is None else np.ascontiguousarray(rescore, np.uint16)
 
 
 class _Base:
     """What both backends share: the header, the argument checks of the mutators and ``save``. A backend
     provides ``_append(bits, tags, publish)`` (which calls ``publish(first id)`` before searches may run again), ``_kill(ids) -> int``, ``_retag(ids, tags)`` and ``_state() -> (bits,
-    tags, live)``. On an fp8 index ``bits`` is a ``_QRows`` and ``_state`` returns ``(codes, tags, live, scales)``."""
+    tags, live)``. On an fp8 index ``bits`` is a ``_QRows`` and ``_state`` returns ``(codes, tags, live, scales)``,
+    on one with rescore rows ``(codes, tags, live, scales, rescore rows)``."""
 
     def __init__(self, path: str):
         self.path = path
@@ -419,6 +483,9 @@ class _Base:
         self.dim, self.count, self.metric = self.header["dim"], self.header["count"], self.header["metric"]
         self.labels = self.header.get("labels")
         self.dtype = self.header["dtype"]
+        self.rescore = "rescore_off" in self.header  # a version-4 file: bf16 rows for a second stage
+        self.version = (VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
+                        else VERSION2 if "tags_off" in self.header else VERSION)
         self._mut = threading.Lock()  # one mutator at a time
 
     def __enter__(self):
@@ -436,12 +503,27 @@ class _Base:
             raise ValueError(f"id {int(bad[0])} is outside [0, {self.count})")
         return np.ascontiguousarray(a.astype(np.int32))
 
+    def _refine(self, refine, k: int) -> int:
+        """``search(refine=...)`` -> the R of the two-stage search, 0 for a one-stage search. On an index with
+        rescore rows ``None`` means ``MAX_K`` (a cluster of ~100 near neighbours loses its order under fp8,
+        DESIGN.md 4n, and 128 is the most the merge supports), ``0`` turns rescoring off and an integer in
+        ``[k, MAX_K]`` is taken as given; on any other index only ``None`` and ``0`` are accepted."""
+        if refine is None:
+            return MAX_K if self.rescore else 0
+        if isinstance(refine, (int, np.integer)) and not isinstance(refine, bool):
+            if refine == 0 or (self.rescore and k <= refine <= MAX_K):
+                return int(refine)
+        wants = f"None, 0 or an integer in [k, {MAX_K}]" if self.rescore else "None or 0 (the index has no rescore rows)"
+        raise ValueError(f"refine must be {wants}, got {refine!r} with k = {k} on a {self.dtype} index of version "
+                         f"{self.version}")
+
     def add(self, vectors, tags=None, labels=None) -> np.ndarray:
         """Append rows (fp32 [n, dim], through :func:`prepare_rows` or, on an fp8 index, :func:`prepare_rows_fp8`:
         the bits ``write_index`` would store) -> their ids, int32 [n]. ``tags``: uint32 [n], default 0.
         ``labels``: required iff the index has labels."""
         if self.dtype == FP8:
-            bits = _QRows(*prepare_rows_fp8(vectors, self.metric))
+            bits = _QRows(*prepare_rows_fp8(vectors, self.metric),
+                          rescore=prepare_rows(vectors, self.metric) if self.rescore else None)
         else:
             bits = prepare_rows(vectors, self.metric)
         n = bits.shape[0]
@@ -481,16 +563,18 @@ class _Base:
         """Write the index as it stands (atomic: a temporary file, then a rename) -> the JSON header.
         ``compact=False`` keeps ids and tombstones; ``compact=True`` drops the dead rows and renumbers the
         rest in order. Version 1 when every row is live and every tag is 0, else version 2; an fp8 index is
-        version 3 with or without tags and bitmap under the same rule."""
+        version 3 with or without tags and bitmap under the same rule, and version 4 when it has rescore rows."""
         with self._mut:
             bits, tags, live, *rest = self._state()
             scales = rest[0] if rest else None
+            rrows = rest[1] if len(rest) > 1 else None
             labels = self.labels
             if compact:
                 if not live.any():
                     raise ValueError("no live row to save")
                 bits, tags = bits[live], tags[live]
                 scales = scales[live] if scales is not None else None
+                rrows = rrows[live] if rrows is not None else None
                 labels = [x for x, keep in zip(labels, live) if keep] if labels is not None else None
                 live = np.ones(bits.shape[0], bool)
             hdr = {"dim": self.dim, "count": int(bits.shape[0]), "dtype": self.dtype, "metric": self.metric,
@@ -499,7 +583,7 @@ class _Base:
                 hdr["labels"] = list(labels)
             plain = bool(live.all()) and not tags.any()
             return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), None if plain else tags,
-                               None if plain else live, self.capacity(), scales=scales)
+                               None if plain else live, self.capacity(), scales=scales, rescore=rrows)
 
 
 class RefIndex(_Base):
@@ -513,6 +597,8 @@ class RefIndex(_Base):
         fp8 = self.dtype == FP8
         self._rows = e4m3_to_f32(self._bits) if fp8 else bf16_to_f32(self._bits)
         self.scales = read_scales(path) if fp8 else None
+        self._rbits = read_rescore_rows(path) if self.rescore else None
+        self._rrows = bf16_to_f32(self._rbits) if self.rescore else None
         self._tags, self._live = read_tags(path), read_live(path)
         self._cap = max(self.count, int(reserve), int(self.header.get("capacity", 0)))
 
@@ -522,18 +608,27 @@ class RefIndex(_Base):
             return self._live
         return self._live[None, :] & ((self._tags[None, :] & filt[:, :1]) == filt[:, 1:])
 
-    def search(self, q, k: int = 10, *, filter=None):
+    def search(self, q, k: int = 10, *, filter=None, refine=None):
+        """``refine`` (:meth:`_Base._refine`): R > 0 is the two-stage search -- ``search_ref(scales=...)`` at
+        k = R, then those ids re-scored in fp64 over the widened bf16 rows (:func:`rescore_ref`)."""
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
+        R = self._refine(refine, k)
         with self._mut:  # the mutators replace the arrays one by one
-            s, i = search_ref(self._rows, q, k, None if filt is None and self._live.all() else self.allow(filt),
+            s, i = search_ref(self._rows, q, R or k, None if filt is None and self._live.all() else self.allow(filt),
                               scales=self.scales)
+            if R:
+                two = [rescore_ref(self._rrows, q[a], i[a], k) for a in range(q.shape[0])]
+                s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
         return s.astype(np.float32), i
 
     def _append(self, bits, tags, publish):
         first = self.count
         if self.scales is not None:
             self.scales = np.concatenate([self.scales, bits.scales])
+            if self.rescore:
+                self._rbits = np.concatenate([self._rbits, bits.rescore])
+                self._rrows = np.concatenate([self._rrows, bf16_to_f32(bits.rescore)])
             bits, new = bits.codes, e4m3_to_f32(bits.codes)
         else:
             new = bf16_to_f32(bits)
@@ -555,6 +650,8 @@ class RefIndex(_Base):
         self._tags[ids] = tags
 
     def _state(self):
+        if self.rescore:
+            return self._bits, self._tags, self._live, self.scales, self._rbits
         if self.scales is not None:
             return self._bits, self._tags, self._live, self.scales
         return self._bits, self._tags, self._live
@@ -576,15 +673,21 @@ class Index(_Base):
     its own stream and buffers). :meth:`search` is thread-safe: a call takes a free context, or waits for
     one. Query batches above 16 rows are searched 16 at a time. ``reserve``: rows to allocate for (adds
     beyond the capacity grow it by doubling). A mutator takes every context before it calls native code,
-    so a search sees the index entirely before or entirely after a mutation."""
+    so a search sees the index entirely before or entirely after a mutation. ``rescore_rows`` (a version-4
+    file): the bf16 rows of the second stage in ``"device"`` memory or in pinned ``"host"`` memory, which
+    leaves the index at an fp8 index's device bytes."""
     backend = "gpu"
 
-    def __init__(self, path: str, device: int = 0, contexts: int = 2, reserve: int = 0):
+    def __init__(self, path: str, device: int = 0, contexts: int = 2, reserve: int = 0, rescore_rows: str = "device"):
         super().__init__(path)
+        if rescore_rows not in ("device", "host"):
+            raise ValueError(f"rescore_rows must be 'device' or 'host', got {rescore_rows!r}")
         from . import _native as N
         self._lib = N.lib()
         reserve = max(int(reserve), int(self.header.get("capacity", 0)))
-        self._h = self._lib.hz_index_open2(os.fsencode(path), int(device), int(contexts), reserve)
+        self.rescore_rows = rescore_rows if self.rescore else None
+        self._h = self._lib.hz_index_open3(os.fsencode(path), int(device), int(contexts), reserve,
+                                           int(rescore_rows == "host"))
         if not self._h:
             raise RuntimeError((self._lib.hz_index_last_error() or b"hz_index_open failed").decode())
         self.device, self.contexts = int(device), int(contexts)
@@ -592,11 +695,14 @@ class Index(_Base):
         for c in range(self.contexts):
             self._free.put(c)
 
-    def search(self, q, k: int = 10, ctx: int | None = None, *, filter=None):
+    def search(self, q, k: int = 10, ctx: int | None = None, *, filter=None, refine=None):
         """fp32 queries [Q, dim] -> (scores float32 [Q, k], ids int32 [Q, k]), best first. ``filter``:
-        ``(mask, value)`` for all queries or Q such pairs; a row passes iff ``(tag & mask) == value``."""
+        ``(mask, value)`` for all queries or Q such pairs; a row passes iff ``(tag & mask) == value``.
+        ``refine`` (an index with rescore rows): the candidates R that the fp8 scan hands the exact bf16
+        second stage, ``None`` for 128, ``0`` for the fp8 answer alone (:meth:`_Base._refine`)."""
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
+        R = self._refine(refine, k)
         if self._h is None:
             raise RuntimeError("the index is closed")
         scores = np.empty((q.shape[0], k), np.float32)
@@ -607,8 +713,8 @@ class Index(_Base):
                 part = q[a:a + MAX_Q]
                 s, i = scores[a:a + MAX_Q], ids[a:a + MAX_Q]  # contiguous row ranges of the outputs
                 f = None if filt is None else np.ascontiguousarray(filt[a:a + MAX_Q])
-                rc = self._lib.hz_index_search_filtered(self._h, c, part.ctypes.data, None if f is None else f.ctypes.data,
-                                                        part.shape[0], k, s.ctypes.data, i.ctypes.data)
+                rc = self._lib.hz_index_search2(self._h, c, part.ctypes.data, None if f is None else f.ctypes.data,
+                                                part.shape[0], k, R, s.ctypes.data, i.ctypes.data)
                 if rc:
                     raise RuntimeError(f"hz_index_search failed with code {rc}")
         finally:
@@ -637,7 +743,10 @@ class Index(_Base):
             bits = np.ascontiguousarray(bits)
 
         def call():
-            if fp8:
+            if fp8 and self.rescore:
+                rc = self._lib.hz_index_add_qr(self._h, bits.codes.ctypes.data, bits.scales.ctypes.data,
+                                               bits.rescore.ctypes.data, bits.shape[0], tags.ctypes.data, C.byref(first))
+            elif fp8:
                 rc = self._lib.hz_index_add_q(self._h, bits.codes.ctypes.data, bits.scales.ctypes.data, bits.shape[0],
                                               tags.ctypes.data, C.byref(first))
             else:
@@ -666,6 +775,11 @@ class Index(_Base):
             self._exclusive(lambda: self._lib.hz_index_read_state_q(self._h, codes.ctypes.data, scales.ctypes.data,
                                                                     tags.ctypes.data, words.ctypes.data, n),
                             "hz_index_read_state_q")
+            if self.rescore:
+                rrows = np.empty((n, self.dim), np.uint16)
+                self._exclusive(lambda: self._lib.hz_index_read_rescore(self._h, rrows.ctypes.data, n),
+                                "hz_index_read_rescore")
+                return codes, tags, unpack_live(words, n), scales, rrows
             return codes, tags, unpack_live(words, n), scales
         bits = np.empty((n, self.dim), np.uint16)
         self._exclusive(lambda: self._lib.hz_index_read_state(self._h, bits.ctypes.data, tags.ctypes.data,
@@ -682,7 +796,8 @@ class Index(_Base):
         return {"path": self.path, "backend": "gpu", "device": self.device,
                 **{k: v for k, v in self.header.items() if k != "labels"}, "labels": self.labels is not None,
                 "contexts": int(out[3]), "tile_rows": int(out[4]), "programs": int(out[5]), "device_bytes": int(out[6]),
-                "capacity": int(more[0]), "live": int(more[1]), "tags": bool(more[2]), "filtered": bool(more[3])}
+                "capacity": int(more[0]), "live": int(more[1]), "tags": bool(more[2]), "filtered": bool(more[3]),
+                **({"rescore_rows": "host" if more[7] else "device"} if more[6] else {})}
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -696,20 +811,28 @@ class Index(_Base):
             pass
 
 
-def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 0):
-    return Index(path, device, reserve=reserve) if backend == "gpu" else RefIndex(path, reserve)
+def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 0, rescore_rows: str = "device"):
+    """``rescore_rows`` places a version-4 index's bf16 rows on the GPU backend; the CPU backend holds every row
+    in host memory."""
+    if backend == "gpu":
+        return Index(path, device, reserve=reserve, rescore_rows=rescore_rows)
+    return RefIndex(path, reserve)
 
 
-def convert_index(src: str, dst: str, dtype: str = "fp8") -> dict:
+def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False) -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
-    labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid."""
+    labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
+    ``rescore=True`` (fp8 only) keeps the stored bf16 rows as the rescore block: a version-4 file."""
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    if rescore and dtype != "fp8":
+        raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
     hdr = read_header(src)
     if hdr["dtype"] != "bf16":
         raise ValueError(f"{src}: only a bf16 index can be converted, this one holds {hdr['dtype']}")
     bits, scales = read_rows(src), None
+    rrows = bits if rescore else None
     if dtype == "fp8":
         if hdr["dim"] % 16:
             raise ValueError(f"dim of an fp8 index must be a multiple of 16 in 16..2048, got {hdr['dim']}")
@@ -720,4 +843,4 @@ def convert_index(src: str, dst: str, dtype: str = "fp8") -> dict:
         out["labels"] = hdr["labels"]
     v2 = "tags_off" in hdr
     return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
-                       hdr.get("capacity"), scales=scales)
+                       hdr.get("capacity"), scales=scales, rescore=rrows)

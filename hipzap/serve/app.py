@@ -513,7 +513,10 @@ def search():
     """The ``k`` nearest rows of the model's vector index (``extra.index``) per query. The queries are the
     vectors /embed gives for the same body, or ``{"model", "vectors": [[...]]}``; a cosine index gets them
     L2-normalised in fp32. ``"k"`` (JSON field or query argument): 1..128, default 10. ``"filter": {"mask",
-    "value"}`` or ``"tag": t`` restricts the answer to the rows whose tag passes ``(tag & mask) == value``."""
+    "value"}`` or ``"tag": t`` restricts the answer to the rows whose tag passes ``(tag & mask) == value``.
+    ``"refine"`` (an index with rescore rows): the candidates the fp8 scan hands the exact bf16 second stage,
+    an integer in k..128, ``0`` for none; absent or null: 128 on such an index. The answer's ``"refine"`` is the
+    R used, 0 if none."""
     from ..search import check_k, check_queries, normalize_rows
     s = get_server()
     body = {}
@@ -541,8 +544,9 @@ def search():
     if index.metric == "cosine":
         q = normalize_rows(q)
     filt = _search_filter(body)
+    refine = index._refine(body.get("refine"), k)  # ValueError -> 400
     with phase("search"):
-        scores, ids = index.search(q, k) if filt is None else index.search(q, k, filter=filt)
+        scores, ids = index.search(q, k, filter=filt, refine=refine)
     dt = (time.perf_counter() - t0) * 1e3
     if "application/octet-stream" in request.headers.get("Accept", ""):
         out = np.empty(ids.shape, dtype=[("id", "<i4"), ("score", "<f4")])
@@ -557,7 +561,7 @@ def search():
         if labels is not None and i >= 0:
             h["label"] = labels[i]
         return h
-    return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "k": k,
+    return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "refine": refine, "k": k,
                   "count": int(index.count),
                   "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(ids, scores)],
                   "timing_ms": round(dt, 3)})

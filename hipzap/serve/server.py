@@ -507,7 +507,8 @@ class ModelServer:
                 if dim != want:
                     raise RuntimeError(f"{name}: index {path} has dim {dim}, the backend's embed.dim is {want}")
                 self._indexes[name] = open_index(path, self.backend, self.settings.devices[0],
-                                                 reserve=int(self.spec(name).extra.get("index_reserve", 0)))
+                                                 reserve=int(self.spec(name).extra.get("index_reserve", 0)),
+                                                 rescore_rows=self.spec(name).extra.get("index_rescore_rows", "device"))
             return self._indexes[name]
 
     def close(self) -> None:
