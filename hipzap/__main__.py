@@ -114,7 +114,7 @@ def cmd_index(a):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
     if a.from_index is not None:
-        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask:
+        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask or a.ivf is not None:
             raise SystemExit("index: --from-index takes only --dtype, --rescore and --out")
         hdr = convert_index(a.from_index, a.out, a.dtype, rescore=a.rescore)
         print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": "labels" in hdr}))
@@ -140,8 +140,10 @@ def cmd_index(a):
         model = model or be.meta.get("model")
     labels = json.load(open(a.labels)) if a.labels else None
     tags = np.load(a.tags, allow_pickle=False) if a.tags else None
+    if a.ivf is None and (a.nprobe is not None or a.ivf_seed is not None):
+        raise SystemExit("index: --nprobe and --ivf-seed go with --ivf NLIST")
     hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
-                      rescore=a.rescore)
+                      rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
@@ -224,6 +226,11 @@ def main(argv=None):
     ix.add_argument("--rescore", action="store_true",
                     help="with --dtype fp8: also store the bf16 rows (a version-4 file) for two-stage search, "
                          "fp8 scan then exact bf16 re-scoring of the candidates")
+    ix.add_argument("--ivf", type=int, default=None, metavar="NLIST",
+                    help="an IVF index (a version-5 file): the rows grouped into NLIST k-means lists; a search scans the "
+                         "--nprobe lists nearest to the query")
+    ix.add_argument("--nprobe", type=int, default=None, help="with --ivf: the lists a search scans by default (min(NLIST, 16))")
+    ix.add_argument("--ivf-seed", type=int, default=None, help="with --ivf: the k-means seed (0)")
     ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept)")
     ix.add_argument("--model", default=None, help="free text kept in the header")
     ix.add_argument("--device", type=int, default=0)

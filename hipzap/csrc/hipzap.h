@@ -494,6 +494,28 @@ typedef struct HzSearchRescoreParams {
   int N, D, Q, R, k, ldc;
 } HzSearchRescoreParams;
 int hz_search_rescore_launch(const HzSearchRescoreParams* p, hipStream_t st);
+// list scan (HZ_K_SEARCH_LSCAN): the filtered scan over an indirect, per-query set of tiles of an
+// IVF index. `f.s.N` stored rows are a whole number of tiles (padding rows are dead in `live`); `list_tiles` holds
+// every tile id once, list l's tiles at [list_off[l], list_off[l + 1]); `rowid[r]` is the external id of stored row
+// r. The grid is (P, Q): workgroup (j, q) scans the j-th tile of the lists probes[q][0 .. nprobe) in probe order
+// against query q alone and writes its best k keys to cand[(j*Q + q)*k ..], the key's id field being
+// ~rowid[row]; a workgroup past the probe set's tiles writes k zero keys. probes == NULL: every list -- P is
+// N / HZ_SEARCH_TILE and workgroup j takes tile j. HZ_K_SEARCH_MERGE with N = P * HZ_SEARCH_TILE reduces the lists.
+// The score bits of a passing (q, r) are those of HZ_K_SEARCH_SCAN for the same query and the same bf16 row.
+// A probe id outside [0, nlist), offsets that are not 0 <= off[l] <= off[l + 1] <= N / HZ_SEARCH_TILE or a tile
+// id outside [0, N / HZ_SEARCH_TILE) make the workgroup write zero keys; nothing is read through them.
+// Refusals: the filtered scan's (its -7 is cand_bytes < P*Q*k*8 here); -40 nlist < 1; -41 nprobe outside
+// 1..min(nlist, HZ_SEARCH_MAX_K) with probes; -42 P < 1, P * HZ_SEARCH_TILE >= 2^31, or P != N / HZ_SEARCH_TILE
+// without probes; -43 N % HZ_SEARCH_TILE; -44 a null table; -45 a table or probes not 4-B aligned.
+typedef struct HzSearchListParams {
+  HzSearchFilterParams f;        // the filtered scan's block; f.s.cand holds [P][Q][k] keys
+  const int* probes;             // device int32 [Q][nprobe] list ids (a merge's out_id), or NULL: every list
+  const int* list_off;           // int32 [nlist + 1]: offsets into list_tiles
+  const int* list_tiles;         // int32 [N / HZ_SEARCH_TILE]: the tile ids, list by list
+  const int* rowid;              // int32 [N]: the external id of each stored row
+  int nlist, nprobe, P, pad_;
+} HzSearchListParams;
+int hz_search_lscan_launch(const HzSearchListParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
@@ -560,6 +582,22 @@ int hz_index_search2(void* idx, int ctx, const float* queries, const unsigned* f
 int hz_index_add_qr(void* idx, const unsigned char* codes, const float* scales, const unsigned short* rows_bf16,
                     long long n, const unsigned* tags_or_null, long long* first_id_out);
 int hz_index_read_rescore(void* idx, unsigned short* rows_out, long long n);  // the first n bf16 rescore rows
+// an IVF index (a version-5 .hzidx): version 2 whose rows, tags and live bitmap are stored list by
+// list, every list on a tile boundary (capacity = tiles * HZ_SEARCH_TILE stored rows, padding rows dead), plus
+// the JSON block "ivf": nlist, nprobe, seed, iters and the offsets of four 4096-aligned blocks -- centroids_off
+// (bf16 [nlist][dim]), list_off_off (int32 [nlist + 1]), list_tiles_off (int32 [tiles]) and rowid_off (int32
+// [capacity], -1 on padding). open3 opens it (and refuses inconsistent tables); ids are the external ids.
+// search3: nprobe = 0 scans every list (no coarse stage); 1 <= nprobe < nlist replays H2D, scan + merge over the
+// centroids at k = nprobe, HZ_K_SEARCH_LSCAN over those lists with P = the tiles of the nprobe largest lists,
+// merge, two D2H. -34: nprobe on an index without lists, nprobe outside 0..min(nlist, HZ_SEARCH_MAX_K), refine
+// on an IVF index, or hz_index_add on one (hz_index_last_error says which). On any other index search3 with
+// nprobe = 0 is search2.
+int hz_index_search3(void* idx, int ctx, const float* queries, const unsigned* filt, int Q, int k, int refine,
+                     int nprobe, float* out_score, int* out_id);
+// the coarse stage alone: the nprobe best lists of each query, best first -> out_list int32 [Q][nprobe]
+int hz_index_probes(void* idx, int ctx, const float* queries, int Q, int nprobe, int* out_list);
+// out[8] = {1 for an IVF index, nlist, default nprobe, tiles, external count, 0, 0, 0}
+int hz_index_describe3(void* idx, uint64_t* out);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -741,7 +779,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_MERGE, 32, HzSearchParams, hz_search_merge_op, SEARCH)         \
   X(SEARCH_FSCAN, 33, HzSearchFilterParams, hz_search_fscan_op, SEARCH)   \
   X(SEARCH_QSCAN, 34, HzSearchQuantParams, hz_search_qscan_op, SEARCH)   \
-  X(SEARCH_RESCORE, 35, HzSearchRescoreParams, hz_search_rescore_op, SEARCH)
+  X(SEARCH_RESCORE, 35, HzSearchRescoreParams, hz_search_rescore_op, SEARCH) \
+  X(SEARCH_LSCAN, 36, HzSearchListParams, hz_search_lscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -22,6 +22,13 @@
 // would, in device memory or in pinned host memory that the kernel reads through its mapped address. A search
 // with refine = R replays H2D, qscan at k = R, merge at k = R into the context's intermediate buffer, rescore
 // of those R ids into out_dev, two D2H; refine = 0 replays the fp8 program above. R is part of a program's key.
+//
+// An IVF index (a version-5 file): a bf16 index whose rows, tags and bitmap are stored list by list
+// in whole tiles; `count` here is the stored row count (the file's capacity), `n_ext` the number of vectors, and
+// every public id is an external id that `pos_of` maps to its stored row. A search with nprobe lists replays
+// H2D, scan + merge over the centroids at k = nprobe into the context's probe buffer, the list scan over those
+// lists with P = the tiles of the nprobe largest lists, merge over the P candidate lists, two D2H; nprobe = 0
+// (every list) has no coarse stage. nprobe is part of a program's key. Rows are never added.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -30,6 +37,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -63,7 +71,11 @@ struct Ctx {
   char* out_dev = nullptr;            // [MAX_Q][MAX_K] fp32 scores, then [MAX_Q][MAX_K] int32 ids
   char* out_host = nullptr;           // pinned, the same layout
   char* mid_dev = nullptr;            // two-stage only: stage one's scores and ids, the layout of out_dev
-  std::map<std::tuple<int, int, int, int>, HzProgram> progs;  // (Q, k, filtered, R; R = 0: one stage)
+  char* probe_dev = nullptr;          // IVF only: the coarse stage's scores and list ids, the layout of out_dev
+  unsigned long long* ccand = nullptr;  // IVF only: the coarse stage's candidate scratch
+  uint64_t ccand_bytes = 0;
+  // (Q, k, filtered, R; R = 0: one stage); IVF: (Q, k, 1, nprobe; 0: every list) and (Q, nprobe, 2, 0): probes alone
+  std::map<std::tuple<int, int, int, int>, HzProgram> progs;
 };
 
 constexpr size_t kOutHalf = (size_t)HZ_SEARCH_MAX_Q * HZ_SEARCH_MAX_K * 4;
@@ -105,6 +117,13 @@ struct Index {
   unsigned* live = nullptr;          // device, cap / 32 words
   unsigned* tags = nullptr;           // device, cap words
   std::vector<uint32_t> live_host, tags_host;  // mirrors, sized like the device buffers
+  bool ivf = false;                   // a version-5 file
+  uint64_t n_ext = 0;                 // IVF: the number of vectors (external ids 0 .. n_ext-1)
+  int nlist = 0, nprobe_default = 0;
+  unsigned short* centroids = nullptr;  // device bf16 [nlist][dim]
+  int* ivf_tables = nullptr;          // device: list_off [nlist + 1], list_tiles [tiles], rowid [count], one block
+  std::vector<int32_t> pos_of;        // external id -> stored row
+  std::vector<int> tiles_desc;        // the lists' tile counts, largest first
   std::vector<std::unique_ptr<Ctx>> ctx;
 
   ~Index() {
@@ -118,6 +137,8 @@ struct Index {
       if (c->cand) (void)hipFree(c->cand);
       if (c->out_dev) (void)hipFree(c->out_dev);
       if (c->mid_dev) (void)hipFree(c->mid_dev);
+      if (c->probe_dev) (void)hipFree(c->probe_dev);
+      if (c->ccand) (void)hipFree(c->ccand);
       if (c->st) (void)hipStreamDestroy(c->st);
     }
     free_rescore(rrows);
@@ -125,6 +146,14 @@ struct Index {
     if (live) (void)hipFree(live);
     if (tags) (void)hipFree(tags);
     if (scales) (void)hipFree(scales);
+    if (centroids) (void)hipFree(centroids);
+    if (ivf_tables) (void)hipFree(ivf_tables);
+  }
+
+  // the stored row of a public id, -1 for an id outside the index
+  int64_t pos(int id) const {
+    if (id < 0 || (uint64_t)id >= (ivf ? n_ext : count)) return -1;
+    return ivf ? pos_of[id] : id;
   }
 
   uint64_t esize() const { return fp8 ? 1 : 2; }  // bytes per stored element
@@ -224,6 +253,69 @@ struct Index {
     return g;
   }
 
+  // The IVF programs (the caller holds c.mu). probes_only: H2D of the queries, scan + merge over the centroids
+  // at k = nprobe, D2H of the list ids. Else the search of (Q, k) over nprobe lists, 0 for every list.
+  HzProgram ivf_program(Ctx& c, int Q, int k, int nprobe, bool probes_only, bool* fresh) {
+    const auto key = probes_only ? std::make_tuple(Q, nprobe, 2, 0) : std::make_tuple(Q, k, 1, nprobe);
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    HzSearchParams cp{};  // the coarse stage: the centroids are a small bf16 corpus
+    cp.corpus = centroids;
+    cp.queries = c.q_dev;
+    cp.cand = c.ccand;
+    cp.out_score = reinterpret_cast<float*>(c.probe_dev);
+    cp.out_id = reinterpret_cast<int*>(c.probe_dev + kOutHalf);
+    cp.N = nlist, cp.D = cp.ldc = (int)h.dim, cp.Q = Q, cp.k = nprobe;
+    cp.cand_bytes = c.ccand_bytes;
+    HzSearchListParams lp{};
+    HzSearchParams& p = lp.f.s;
+    p.corpus = rows;
+    p.queries = c.q_dev;
+    p.cand = c.cand;
+    p.out_score = reinterpret_cast<float*>(c.out_dev);
+    p.out_id = reinterpret_cast<int*>(c.out_dev + kOutHalf);
+    p.N = (int)count, p.D = p.ldc = (int)h.dim, p.Q = Q, p.k = k;
+    p.cand_bytes = c.cand_bytes;
+    lp.f.live = live;
+    lp.f.tags = tags;
+    lp.f.filt = reinterpret_cast<const unsigned*>(c.slot_dev);
+    lp.f.live_bytes = cap / 8;
+    const int ntile = (int)(count / kTile);
+    lp.probes = nprobe ? cp.out_id : nullptr;
+    lp.list_off = ivf_tables;
+    lp.list_tiles = ivf_tables + nlist + 1;
+    lp.rowid = lp.list_tiles + ntile;
+    lp.nlist = nlist, lp.nprobe = nprobe;
+    lp.P = ntile;
+    if (nprobe) {  // the most tiles nprobe lists can hold
+      lp.P = 0;
+      for (int i = 0; i < nprobe && i < (int)tiles_desc.size(); ++i) lp.P += tiles_desc[i];
+    }
+    HzSearchParams mp = p;  // the merge over the P candidate lists
+    mp.N = lp.P * (int)kTile;
+    HzProgram g = hz_prog_create();
+    const size_t qk = (size_t)Q * k * 4, qb = (size_t)Q * h.dim * 4;
+    int rc = probes_only ? hz_prog_add_memcpy(g, c.q_dev, c.q_host, qb, 0)
+                         : hz_prog_add_memcpy(g, c.slot_dev, c.slot_host, kFiltBytes + qb, 0);
+    if (!rc && nprobe) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_SCAN, &cp, sizeof(cp), 0);
+    if (!rc && nprobe) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGE, &cp, sizeof(cp), 0);
+    if (probes_only) {
+      if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.probe_dev + kOutHalf, (size_t)Q * nprobe * 4, 0);
+    } else {
+      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_LSCAN, &lp, sizeof(lp), 0);
+      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGE, &mp, sizeof(mp), 0);
+      if (!rc) rc = hz_prog_add_memcpy(g, c.out_host, c.out_dev, qk, 0);
+      if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.out_dev + kOutHalf, qk, 0);
+    }
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
   // device buffers for `new_cap` rows (whole tiles); the first `count` rows, their tags and the bitmap move
   // over (device-to-device on `st`, synchronised), the rest is dead: zero bitmap, zero tags, rows untouched.
   // The caller holds every context's mutex (or the index is not yet shared) and drops the programs.
@@ -307,26 +399,43 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 4 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 5 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 4) return fail("index: unknown format version " + std::to_string(h.version));
-  const bool fp8 = h.version >= 3, rescore = h.version == 4;
+  if (h.version < 1 || h.version > 5) return fail("index: unknown format version " + std::to_string(h.version));
+  const bool fp8 = h.version == 3 || h.version == 4, rescore = h.version == 4, ivf = h.version == 5;
   if (fp8 && (h.dim < 16 || h.dim % 16 || h.dim > 2048))
     return fail("index: dim of an fp8 index must be a multiple of 16 in 16..2048");
   if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
   if (h.count < 1 || h.count >= (1ull << 31)) return fail("index: count must be in 1..2^31-1");
   if (h.metric > HZ_INDEX_IP) return fail("index: unknown metric");
+  // an IVF file's blocks hold `capacity` stored rows (whole tiles); from here on h.count is that number
+  const uint64_t n_ext = h.count;
+  uint64_t ivf_u[6] = {0, 0, 0, 0, 0, 0};  // nlist, nprobe, then the four offsets
+  if (ivf) {
+    static const char* keys[6] = {"nlist", "nprobe", "centroids_off", "list_off_off", "list_tiles_off", "rowid_off"};
+    uint64_t stored = 0;
+    if (js.rfind("\"ivf\"") == std::string::npos || !json_u64(js, "capacity", &stored, true))
+      return fail("index: a version-5 file without an ivf block or capacity");
+    for (int i = 0; i < 6; ++i)
+      if (!json_u64(js, keys[i], &ivf_u[i], true)) return fail(std::string("index: the ivf block lacks ") + keys[i]);
+    if (stored < n_ext || stored % kTile || stored >= (1ull << 31))
+      return fail("index: capacity of an IVF index must be whole tiles holding count rows");
+    if (ivf_u[0] < 1 || ivf_u[0] > std::min<uint64_t>(n_ext, 65536) || ivf_u[1] < 1 ||
+        ivf_u[1] > std::min<uint64_t>(ivf_u[0], HZ_SEARCH_MAX_K))
+      return fail("index: ivf nlist / nprobe out of range");
+    h.count = stored;
+  }
   const uint64_t bytes = h.count * h.dim * (fp8 ? 1 : 2), fsize = (uint64_t)sb.st_size;
   if (h.data_off % 4096 || h.data_off < sizeof(h) + h.json_len || h.data_off + bytes > fsize)
     return fail("index: row block outside the file");
   uint64_t tags_off = 0, live_off = 0;
   const uint64_t tag_bytes = h.count * 4, live_bytes = round_up(h.count, 32) / 8;
   uint64_t scales_off = 0, after_rows = h.data_off + bytes;
-  bool blocks = h.version == 2;  // tags and a bitmap in the file
+  bool blocks = h.version == 2 || ivf;  // tags and a bitmap in the file
   if (fp8) {
     if (!json_u64(js, "scales_off", &scales_off, true)) return fail("index: a version-3 file without scales_off");
     if (scales_off % 4096 || scales_off < after_rows || scales_off > fsize || h.count * 4 > fsize - scales_off)
@@ -354,6 +463,64 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   }
   if (rescore && (rescore_off % 4096 || rescore_off < after_rows || rescore_off > fsize || rescore_len > fsize - rescore_off))
     return fail("index: rescore block unaligned, overlapping another block or outside the file");
+  // the IVF tables: read, and checked before anything reaches the device -- the list scan trusts them
+  const uint64_t ntile = h.count / kTile;
+  std::vector<unsigned short> cent_host;
+  std::vector<int32_t> tables_host;  // list_off [nlist + 1], list_tiles [ntile], rowid [h.count]
+  std::vector<int32_t> pos_of;
+  std::vector<int> tiles_desc;
+  if (ivf) {
+    const uint64_t nlist = ivf_u[0];
+    const uint64_t len[4] = {nlist * h.dim * 2, (nlist + 1) * 4, ntile * 4, h.count * 4};
+    cent_host.resize(nlist * h.dim);
+    tables_host.resize(nlist + 1 + ntile + h.count);
+    char* dst[4] = {reinterpret_cast<char*>(cent_host.data()), reinterpret_cast<char*>(tables_host.data()),
+                    reinterpret_cast<char*>(tables_host.data() + nlist + 1),
+                    reinterpret_cast<char*>(tables_host.data() + nlist + 1 + ntile)};
+    const int tfd = open(path, O_RDONLY | O_CLOEXEC);
+    bool ok = tfd >= 0;
+    for (int i = 0; ok && i < 4; ++i) {
+      const uint64_t off = ivf_u[2 + i];
+      if (off % 4096 || off < after_rows || off > fsize || len[i] > fsize - off) {
+        close(tfd);
+        return fail("index: an ivf block is unaligned, overlaps another block or lies outside the file");
+      }
+      after_rows = off + len[i];
+      uint64_t done = 0;
+      while (done < len[i]) {
+        const ssize_t n = pread(tfd, dst[i] + done, len[i] - done, (off_t)(off + done));
+        if (n <= 0) break;
+        done += (uint64_t)n;
+      }
+      ok = done == len[i];
+    }
+    if (tfd >= 0) close(tfd);
+    if (!ok) return fail("index: cannot read the ivf blocks");
+    const int32_t* loff = tables_host.data();
+    const int32_t* ltiles = loff + nlist + 1;
+    const int32_t* rowid = ltiles + ntile;
+    if (loff[0] != 0 || (uint64_t)loff[nlist] != ntile) return fail("index: ivf list_off does not rise from 0 to the tile count");
+    for (uint64_t l = 0; l < nlist; ++l) {
+      if (loff[l + 1] < loff[l]) return fail("index: ivf list_off does not rise from 0 to the tile count");
+      tiles_desc.push_back(loff[l + 1] - loff[l]);
+    }
+    std::sort(tiles_desc.begin(), tiles_desc.end(), std::greater<int>());
+    std::vector<char> seen(ntile, 0);
+    for (uint64_t i = 0; i < ntile; ++i) {
+      if (ltiles[i] < 0 || (uint64_t)ltiles[i] >= ntile || seen[ltiles[i]])
+        return fail("index: ivf list_tiles is not a permutation of the tile ids");
+      seen[ltiles[i]] = 1;
+    }
+    pos_of.assign(n_ext, -1);
+    uint64_t real = 0;
+    for (uint64_t r = 0; r < h.count; ++r) {
+      if (rowid[r] == -1) continue;
+      if (rowid[r] < 0 || (uint64_t)rowid[r] >= n_ext || pos_of[rowid[r]] != -1)
+        return fail("index: ivf rowid is not a permutation of the ids over the stored rows");
+      pos_of[rowid[r]] = (int32_t)r, ++real;
+    }
+    if (real != n_ext) return fail("index: ivf rowid is not a permutation of the ids over the stored rows");
+  }
   if (hipSetDevice(device) != hipSuccess) return fail("index: hipSetDevice failed");
   auto idx = std::make_unique<Index>();
   idx->device = device;
@@ -362,6 +529,11 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   idx->fp8 = fp8;
   idx->rescore = rescore;
   idx->rescore_host = rescore && rescore_host != 0;
+  idx->ivf = ivf;
+  idx->n_ext = n_ext;
+  idx->nlist = (int)ivf_u[0], idx->nprobe_default = (int)ivf_u[1];
+  idx->pos_of = std::move(pos_of);
+  idx->tiles_desc = std::move(tiles_desc);
   if (hz_search_code_warm()) return fail("index: device code load failed");
   for (int i = 0; i < nctx; ++i) {
     auto c = std::make_unique<Ctx>();
@@ -372,6 +544,11 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->slot_dev), sb_) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->out_dev), 2 * kOutHalf) == hipSuccess;
     if (rescore) ok = ok && hipMalloc(reinterpret_cast<void**>(&c->mid_dev), 2 * kOutHalf) == hipSuccess;
+    if (ivf) {
+      c->ccand_bytes = hz_search_scratch_bytes((long long)ivf_u[0], HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c->probe_dev), 2 * kOutHalf) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c->ccand), c->ccand_bytes) == hipSuccess;
+    }
     if (ok) {
       std::memset(c->slot_host, 0, sb_);
       c->q_host = reinterpret_cast<float*>(c->slot_host + kFiltBytes);
@@ -407,6 +584,23 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     idx->live_count = h.count;
     if (push_words(idx->live, idx->live_host, 0, words, st) || hipStreamSynchronize(st) != hipSuccess)
       return fail("index: upload failed");
+  }
+  if (ivf) {
+    bool ok = hipMalloc(reinterpret_cast<void**>(&idx->centroids), cent_host.size() * 2) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&idx->ivf_tables), tables_host.size() * 4) == hipSuccess;
+    ok = ok && hipMemcpy(idx->centroids, cent_host.data(), cent_host.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(idx->ivf_tables, tables_host.data(), tables_host.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) return fail("index: ivf upload failed");
+    // a padding row is dead whatever the file's bitmap says: the list scan never loads it
+    const int32_t* rowid = tables_host.data() + idx->nlist + 1 + ntile;
+    uint64_t cleared = 0;
+    for (uint64_t r = 0; r < h.count; ++r)
+      if (rowid[r] < 0 && (idx->live_host[r >> 5] >> (r & 31) & 1u)) idx->live_host[r >> 5] &= ~(1u << (r & 31)), ++cleared;
+    if (cleared) {
+      idx->live_count -= cleared;
+      if (push_words(idx->live, idx->live_host, 0, words, st) || hipStreamSynchronize(st) != hipSuccess)
+        return fail("index: upload failed");
+    }
   }
   if (rescore && idx->rescore_host) {  // the file's block straight into the pinned rows
     const int rfd = open(path, O_RDONLY | O_CLOEXEC);
@@ -457,7 +651,17 @@ int hz_index_describe2(void* h, uint64_t* out) {
   return 0;
 }
 
-int hz_index_search2(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, int refine,
+int hz_index_describe3(void* h, uint64_t* out) {
+  if (!h || !out) return -1;
+  Index* x = static_cast<Index*>(h);
+  AllLocked all(*x);
+  const uint64_t v[8] = {x->ivf ? 1u : 0u, (uint64_t)x->nlist, (uint64_t)x->nprobe_default, x->ivf ? x->count / kTile : 0,
+                         x->ivf ? x->n_ext : x->count, 0, 0, 0};
+  std::memcpy(out, v, sizeof(v));
+  return 0;
+}
+
+int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, int refine, int nprobe,
                      float* out_score, int* out_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !queries || !out_score || !out_id) return -1;
@@ -473,12 +677,23 @@ int hz_index_search2(void* h, int ctx, const float* queries, const unsigned* fil
     g_err = "index: refine must be 0 or in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(refine);
     return -28;
   }
+  if (nprobe && !x->ivf) {
+    g_err = "index: nprobe needs an IVF index (a version-5 file)";
+    return -34;
+  }
+  if (x->ivf && (refine || nprobe < 0 || (nprobe > HZ_SEARCH_MAX_K && nprobe < x->nlist))) {
+    g_err = refine ? "index: an IVF index has no rescore rows"
+                   : "index: nprobe must be 0 (every list) or in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " +
+                         std::to_string(nprobe);
+    return -34;
+  }
+  if (x->ivf && nprobe >= x->nlist) nprobe = 0;  // every list: no coarse stage
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
-  const bool filtered = x->fp8 || x->mutated || filt != nullptr;
+  const bool filtered = x->fp8 || x->mutated || filt != nullptr || x->ivf;
   bool fresh = false;
-  HzProgram g = x->program(c, Q, k, filtered, refine, &fresh);
+  HzProgram g = x->ivf ? x->ivf_program(c, Q, k, nprobe, false, &fresh) : x->program(c, Q, k, filtered, refine, &fresh);
   if (!g) return -11;
   std::memcpy(c.q_host, queries, (size_t)Q * x->h.dim * 4);
   if (filtered) {  // no filter: mask 0, value 0 passes every tag
@@ -491,6 +706,39 @@ int hz_index_search2(void* h, int ctx, const float* queries, const unsigned* fil
   if (rc) return rc;
   std::memcpy(out_score, c.out_host, (size_t)Q * k * 4);
   std::memcpy(out_id, c.out_host + kOutHalf, (size_t)Q * k * 4);
+  if (fresh) {
+    rc = hz_prog_capture(g, c.st);
+    if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  }
+  return rc;
+}
+
+int hz_index_search2(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, int refine,
+                     float* out_score, int* out_id) {
+  return hz_index_search3(h, ctx, queries, filt, Q, k, refine, 0, out_score, out_id);
+}
+
+int hz_index_probes(void* h, int ctx, const float* queries, int Q, int nprobe, int* out_list) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_list) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (Q < 1 || Q > HZ_SEARCH_MAX_Q) return -4;
+  if (!x->ivf || nprobe < 1 || nprobe > x->nlist || nprobe > HZ_SEARCH_MAX_K) {
+    g_err = x->ivf ? "index: nprobe must be in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " + std::to_string(nprobe)
+                   : std::string("index: probes needs an IVF index (a version-5 file)");
+    return -34;
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->ivf_program(c, Q, 0, nprobe, true, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.q_host, queries, (size_t)Q * x->h.dim * 4);
+  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
+  if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  if (rc) return rc;
+  std::memcpy(out_list, c.out_host + kOutHalf, (size_t)Q * nprobe * 4);
   if (fresh) {
     rc = hz_prog_capture(g, c.st);
     if (!rc) rc = (int)hipStreamSynchronize(c.st);
@@ -571,6 +819,10 @@ extern "C" {
 int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const unsigned* tags, long long* first_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !rows_bf16 || n < 1) return -1;
+  if (x->ivf) {
+    g_err = "index: IVF indexes do not take hz_index_add yet";
+    return -34;
+  }
   if (x->fp8) return wrong_dtype(x, "hz_index_add", "bf16");
   return add_rows(x, rows_bf16, nullptr, nullptr, n, tags, first_id);
 }
@@ -605,11 +857,12 @@ int hz_index_delete(void* h, const int* ids, long long n, long long* newly_delet
   AllLocked all(*x);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   for (long long i = 0; i < n; ++i)
-    if (ids[i] < 0 || (uint64_t)ids[i] >= x->count) return -20;
+    if (x->pos(ids[i]) < 0) return -20;
   uint64_t lo = ~0ull, hi = 0, gone = 0;
   for (long long i = 0; i < n; ++i) {
-    const uint64_t w = (uint64_t)ids[i] >> 5;
-    const uint32_t bit = 1u << (ids[i] & 31);
+    const uint64_t r = (uint64_t)x->pos(ids[i]);
+    const uint64_t w = r >> 5;
+    const uint32_t bit = 1u << (r & 31);
     if (!(x->live_host[w] & bit)) continue;
     x->live_host[w] &= ~bit;
     lo = std::min(lo, w), hi = std::max(hi, w + 1), ++gone;
@@ -632,12 +885,13 @@ int hz_index_set_tags(void* h, const int* ids, const unsigned* tags, long long n
   AllLocked all(*x);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   for (long long i = 0; i < n; ++i)
-    if (ids[i] < 0 || (uint64_t)ids[i] >= x->count) return -20;
+    if (x->pos(ids[i]) < 0) return -20;
   uint64_t lo = ~0ull, hi = 0;
   for (long long i = 0; i < n; ++i) {
-    x->tags_host[ids[i]] = tags[i];
+    const uint64_t r = (uint64_t)x->pos(ids[i]);
+    x->tags_host[r] = tags[i];
     if (tags[i]) x->has_tags = true;
-    lo = std::min<uint64_t>(lo, ids[i]), hi = std::max<uint64_t>(hi, (uint64_t)ids[i] + 1);
+    lo = std::min<uint64_t>(lo, r), hi = std::max<uint64_t>(hi, r + 1);
   }
   if (n == 0) return 0;
   hipStream_t st = x->ctx[0]->st;

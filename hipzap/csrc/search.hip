@@ -4,8 +4,10 @@
 //                    One template; its instantiations are the kinds SCAN (bf16 rows), FSCAN (bf16 rows that
 //                    pass a live bit and a per-query tag predicate) and QSCAN (FSCAN over OCP e4m3fn byte
 //                    rows with one fp32 scale per row)
+//   * search_lscan — the filtered bf16 scan over an IVF index's lists (kind LSCAN): workgroup (j, q) scores the
+//                    j-th tile of the lists query q probes against that query alone, with the template's pieces
 //   * search_merge — one workgroup per query: ntile x k candidates -> the final k, best first
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n for the reasoning.
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -215,54 +217,47 @@ __device__ __forceinline__ void score_group(const HzSearchParams& p, const float
   }
 }
 
-// Thread t ranks row t among the tile's scores of each query and writes the tile's candidate list: the passing
-// rows' best k keys, then key 0. Unfiltered: every row passes and the pass count is `rows`.
+// Thread t ranks row t among the tile's scores `sc` ([T]) of one query and writes that query's candidate list
+// `out`: the passing rows' best k keys, then key 0. `id` is the id field of row t's key: the row's position, or
+// (HZ_K_SEARCH_LSCAN) the external id that rowid[] gives it. Unfiltered: every row passes, the pass count is `rows`.
+template <bool FILT>
+__device__ __forceinline__ void rank_query(const unsigned* sc, unsigned long long* out, bool slot_ok, int k, int rows,
+                                           unsigned id) {
+  const int t = threadIdx.x;
+  // np: the tile's passing rows that can take a slot. Unfiltered: every row passes, so a thread past the
+  // tile's end skips the loop and a real row needs no sentinel test.
+  unsigned mine = 0u;
+  int rank = 0, np = FILT ? 0 : min(k, rows);
+  if (FILT || t < rows) {
+    if (t < rows) mine = sc[t];
+    for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
+      const unsigned o = sc[j];
+      rank += (o > mine) || (o == mine && j < t);
+      if constexpr (FILT) np += o != 0u;
+    }
+  }
+  if ((FILT ? mine != 0u : t < rows) && rank < (FILT ? k : np) && slot_ok)
+    out[rank] = ((unsigned long long)mine << 32) | (unsigned)~id;
+  if (t >= np && t < k && slot_ok) out[t] = 0ull;  // the slots past the passing rows (k <= 128 < T)
+}
+
+// The tile's candidate lists of every query of the launch, the id of a key being the row's position.
 template <bool FILT>
 __device__ __forceinline__ void rank_tile(const HzSearchParams& p, const unsigned* sc, int tile, long row0, int rows) {
-  const int t = threadIdx.x;
   for (int q = 0; q < p.Q; ++q) {
     unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
     const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
-    // np: the tile's passing rows that can take a slot. Unfiltered: every row passes, so a thread past the
-    // tile's end skips the loop and a real row needs no sentinel test.
-    unsigned mine = 0u;
-    int rank = 0, np = FILT ? 0 : min(p.k, rows);
-    if (FILT || t < rows) {
-      if (t < rows) mine = sc[q * T + t];
-      for (int j = 0; j < rows; ++j) {  // every lane reads the same word: an LDS broadcast
-        const unsigned o = sc[q * T + j];
-        rank += (o > mine) || (o == mine && j < t);
-        if constexpr (FILT) np += o != 0u;
-      }
-    }
-    if ((FILT ? mine != 0u : t < rows) && rank < (FILT ? p.k : np) && slot_ok)
-      out[rank] = ((unsigned long long)mine << 32) | (unsigned)~(unsigned)(row0 + t);
-    if (t >= np && t < p.k && slot_ok) out[t] = 0ull;  // the slots past the passing rows (k <= 128 < T)
+    rank_query<FILT>(sc + q * T, out, slot_ok, p.k, rows, (unsigned)(row0 + threadIdx.x));
   }
 }
 
+// The row loop of a scan workgroup: wave w scores rows w*64 .. w*64+63 of the tile at `row0` (`rows` of them)
+// against the p.Q queries in `qs`, ROWS at a time, into sc[q * T + row]. Filtered: a row with no pass bit is not
+// loaded and a group of such rows only writes its sentinels (the group skip).
 template <class Fmt, int NC, bool FILT>
-__global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::template Args<FILT> a) {
-  const HzSearchParams& p = scan_part(a);
-  extern __shared__ __attribute__((aligned(16))) float lds[];  // lds_bytes()
-  float* qs = lds;                                                      // [Q][D]
-  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);          // [Q][T]
-  unsigned* pmask = nullptr;  // filtered: [T] pass bits, then the tile's live words and the filters
-  float* scl = nullptr;       // scaled: [T] scales of the passing rows
-  if constexpr (FILT) pmask = sc + p.Q * T;
-  if constexpr (Fmt::SCALED) scl = reinterpret_cast<float*>(pmask + T + T / 32 + 2 * p.Q);
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tile = blockIdx.x;
-  const int nch = p.D >> __builtin_ctz(Fmt::E);
+__device__ __forceinline__ void scan_rows(const HzSearchParams& p, const float* qs, unsigned* sc, const unsigned* pmask,
+                                          const float* scl, long row0, int rows, int lane, int w, int nch) {
   const typename Fmt::Elem* corpus = reinterpret_cast<const typename Fmt::Elem*>(p.corpus);
-  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 64 * Fmt::E && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
-  const long row0 = (long)tile * T;
-  const int rows = (int)min((long)T, (long)p.N - row0);
-  stage_queries(p, qs);
-  if constexpr (FILT) stage_pass_bits<Fmt>(a, pmask, scl, row0, rows);
-  __syncthreads();
-
   for (int g = 0; g < 64; g += ROWS) {  // wave-uniform bounds
     const int r0 = w * 64 + g;
     if (r0 >= rows) break;
@@ -293,8 +288,107 @@ __global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::temp
       }
     score_group<Fmt, NC>(p, qs, sc, scl, v, pass, lane, nch, r0, rows);
   }
+}
+
+template <class Fmt, int NC, bool FILT>
+__global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::template Args<FILT> a) {
+  const HzSearchParams& p = scan_part(a);
+  extern __shared__ __attribute__((aligned(16))) float lds[];  // lds_bytes()
+  float* qs = lds;                                                      // [Q][D]
+  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.Q * p.D);          // [Q][T]
+  unsigned* pmask = nullptr;  // filtered: [T] pass bits, then the tile's live words and the filters
+  float* scl = nullptr;       // scaled: [T] scales of the passing rows
+  if constexpr (FILT) pmask = sc + p.Q * T;
+  if constexpr (Fmt::SCALED) scl = reinterpret_cast<float*>(pmask + T + T / 32 + 2 * p.Q);
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tile = blockIdx.x;
+  const int nch = p.D >> __builtin_ctz(Fmt::E);
+  if (!HZ_DCHECK(tile < p.ntile && p.D <= NC * 64 * Fmt::E && p.ldc >= p.D && (long)tile * T < (long)p.N)) return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  stage_queries(p, qs);
+  if constexpr (FILT) stage_pass_bits<Fmt>(a, pmask, scl, row0, rows);
+  __syncthreads();
+
+  scan_rows<Fmt, NC, FILT>(p, qs, sc, pmask, scl, row0, rows, lane, w, nch);
   __syncthreads();
   rank_tile<FILT>(p, sc, tile, row0, rows);
+}
+
+// -------------------------------------------------------------------------------------- list scan
+// search_lscan_kernel<NC> (HZ_K_SEARCH_LSCAN): the filtered bf16 scan over an indirect, per-query
+// set of tiles. Grid (P, Q); workgroup (j, q) finds the j-th tile of query q's probe set and scores it against
+// query q ALONE with the template's pieces at Q = 1 (stage_queries, stage_pass_bits, scan_rows with its group
+// skip, score_group), so a passing (q, r) has kind 31's bits and a dead or padding row is never loaded.
+// Addressing: thread i < nprobe reads probes[q*nprobe + i] = l, and under (unsigned)l < nlist the pair
+// a = list_off[l], b = list_off[l + 1]; under 0 <= a <= b <= ntile its count b - a and start a go to LDS, else
+// the count -1. Every thread then walks the nprobe counts in probe order (LDS broadcasts): the running sum
+// finds the probe whose range holds j and the index x = a + (j - sum before) < b <= ntile into list_tiles, whose
+// length is ntile. tile = list_tiles[x] is used under (unsigned)tile < ntile. A count of -1, a j at or past the
+// total and a tile out of range all end in k zero keys for this workgroup's slot and nothing else read.
+// probes == NULL: tile = j under j < ntile. rowid[row0 + t] is read once per tile (coalesced) under
+// row0 + t < N; N = ntile * T (the launcher refuses anything else), so every tile is whole.
+// Dynamic LDS: lds_bytes(1, D, true, false) = (D + 2 T + T / 32 + 2) * 4 <= 10,280 B; static: 2 x 128 ints.
+template <int NC>
+__global__ __launch_bounds__(T) void search_lscan_kernel(const HzSearchListParams a) {
+  const HzSearchParams& p = a.f.s;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  __shared__ int pcnt[HZ_SEARCH_MAX_K], poff[HZ_SEARCH_MAX_K];  // the probed lists' tile counts and starts
+  float* qs = lds;                                        // [D]
+  unsigned* sc = reinterpret_cast<unsigned*>(lds + p.D);  // [T]
+  unsigned* pmask = sc + T;                               // [T] pass bits, the tile's live words, {mask, value}
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int j = blockIdx.x, q = blockIdx.y;
+  const int nch = p.D >> 3;
+  if (!HZ_DCHECK(j < a.P && q < p.Q && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K && p.D <= NC * 64 * 8 && p.ldc >= p.D &&
+                 p.N == p.ntile * T && a.nlist >= 1))
+    return;
+  unsigned long long* out = p.cand + ((long)j * p.Q + q) * p.k;
+  const bool slot_ok = HZ_DCHECK(((long)j * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
+  int tile = -1;
+  if (a.probes) {
+    if (!HZ_DCHECK(a.nprobe >= 1 && a.nprobe <= HZ_SEARCH_MAX_K)) return;
+    if (t < a.nprobe) {
+      const int l = a.probes[(long)q * a.nprobe + t];
+      int cnt = -1, off = 0;
+      if ((unsigned)l < (unsigned)a.nlist) {
+        const int lo = a.list_off[l], hi = a.list_off[l + 1];
+        if (lo >= 0 && lo <= hi && hi <= p.ntile) cnt = hi - lo, off = lo;
+      }
+      pcnt[t] = cnt, poff[t] = off;
+    }
+    __syncthreads();
+    int sum = 0, at = -1;
+    bool bad = false;
+    for (int i = 0; i < a.nprobe; ++i) {  // every lane reads the same words: LDS broadcasts
+      const int c = pcnt[i];
+      bad |= c < 0;
+      if (at < 0 && c > 0 && j < sum + c) at = poff[i] + (j - sum);
+      sum += c > 0 ? c : 0;
+    }
+    if (!bad && at >= 0 && HZ_DCHECK(at < p.ntile)) tile = a.list_tiles[at];
+  } else {
+    tile = j;
+  }
+  if ((unsigned)tile >= (unsigned)p.ntile) {  // an idle workgroup (block-uniform): its slot holds no candidate
+    if (t < p.k && slot_ok) out[t] = 0ull;
+    return;
+  }
+  const long row0 = (long)tile * T;
+  unsigned id = 0u;
+  if (HZ_DCHECK(row0 + t < (long)p.N)) id = (unsigned)a.rowid[row0 + t];
+  HzSearchFilterParams one = a.f;  // what the template's pieces read: this query, and its {mask, value}
+  one.s.Q = 1;
+  one.s.queries = p.queries + (long)q * p.D;
+  if (one.filt) one.filt += 2 * q;
+  stage_queries(one.s, qs);
+  stage_pass_bits<Bf16Rows>(one, pmask, nullptr, row0, T);
+  __syncthreads();
+  scan_rows<Bf16Rows, NC, true>(one.s, qs, sc, pmask, nullptr, row0, T, lane, w, nch);
+  __syncthreads();
+  rank_query<true>(sc, out, slot_ok, p.k, T, id);
 }
 
 // ------------------------------------------------------------------------------------------ merge
@@ -507,8 +601,8 @@ void rescore_dispatch(const HzSearchRescoreParams& a, hipStream_t st) {
 }
 
 // one refusal list for both launchers: the kernels then have no address that the data can move out of
-// its buffer. Fills ntile.
-int search_check(HzSearchParams& p) {
+// its buffer. Fills ntile. `need`: the bytes `cand` must hold, 0 for the scan's hz_search_scratch_bytes(N, Q, k).
+int search_check(HzSearchParams& p, unsigned long long need = 0) {
   if (!p.corpus || !p.queries || !p.cand || !p.out_score || !p.out_id) return -1;
   if (p.D < 8 || p.D % 8 || p.D > 2048 || p.ldc < p.D || p.ldc % 8) return -2;
   if (p.N < 1) return -3;  // N is an int: N >= 2^31 cannot be expressed (hz_search_scratch_bytes refuses it)
@@ -518,7 +612,7 @@ int search_check(HzSearchParams& p) {
       (reinterpret_cast<uintptr_t>(p.cand) & 7) || (reinterpret_cast<uintptr_t>(p.out_score) & 3) ||
       (reinterpret_cast<uintptr_t>(p.out_id) & 3))
     return -6;
-  const unsigned long long need = hz_search_scratch_bytes(p.N, p.Q, p.k);
+  if (!need) need = hz_search_scratch_bytes(p.N, p.Q, p.k);
   if (!need || p.cand_bytes < need) return -7;
   p.ntile = (int)(((long)p.N + T - 1) / T);
   return 0;
@@ -609,6 +703,36 @@ extern "C" int hz_search_qscan_launch(const HzSearchQuantParams* pp, hipStream_t
   if (!qp.scales) return -24;
   if (reinterpret_cast<uintptr_t>(qp.scales) & 3) return -25;
   return scan_launch<E4m3Rows, true>(qp, st);
+}
+
+template <int NC = 1>
+void lscan_dispatch(const HzSearchListParams& a, hipStream_t st) {
+  const HzSearchParams& p = a.f.s;
+  if constexpr (NC < Bf16Rows::MAX_NC) {
+    if (p.D > NC * 64 * Bf16Rows::E) return lscan_dispatch<NC + 1>(a, st);
+  }
+  hipLaunchKernelGGL(search_lscan_kernel<NC>, dim3(a.P, p.Q), dim3(T), lds_bytes(1, p.D, true, false), st, a);
+}
+
+// The filtered launcher's refusals (-7: cand_bytes below P*Q*k*8), then the list tables' (hipzap.h).
+extern "C" int hz_search_lscan_launch(const HzSearchListParams* pp, hipStream_t st) {
+  HzSearchListParams a = *pp;
+  HzSearchParams& p = a.f.s;
+  if (a.P < 1 || (long long)a.P * T >= (1ll << 31)) return -42;
+  const unsigned long long need =
+      (p.Q >= 1 && p.Q <= HZ_SEARCH_MAX_Q && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K) ? (unsigned long long)a.P * p.Q * p.k * 8ull : 0;
+  if (const int rc = search_check(p, need ? need : 1)) return rc;  // Q or k out of range: refused before -7
+  if (const int rc = filter_check(a.f)) return rc;
+  if (a.nlist < 1) return -40;
+  if (a.probes && (a.nprobe < 1 || a.nprobe > a.nlist || a.nprobe > HZ_SEARCH_MAX_K)) return -41;
+  if (p.N % T) return -43;
+  if (!a.probes && a.P != p.ntile) return -42;
+  if (!a.list_off || !a.list_tiles || !a.rowid) return -44;
+  if ((reinterpret_cast<uintptr_t>(a.probes) & 3) || (reinterpret_cast<uintptr_t>(a.list_off) & 3) ||
+      (reinterpret_cast<uintptr_t>(a.list_tiles) & 3) || (reinterpret_cast<uintptr_t>(a.rowid) & 3))
+    return -45;
+  lscan_dispatch(a, st);
+  return (int)hipGetLastError();
 }
 
 extern "C" int hz_search_merge_launch(const HzSearchParams* pp, hipStream_t st) {

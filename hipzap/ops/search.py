@@ -8,6 +8,8 @@ per-query ``{mask, value}`` filters) is the scan over the rows that pass. ``HZ_K
 (``QuantScanParams``: that block plus one fp32 scale per row) is the filtered scan over rows of OCP e4m3fn bytes.
 ``HZ_K_SEARCH_RESCORE`` (``RescoreParams``) is the second stage of a two-stage search: one workgroup per query
 re-scores the ``R`` bf16 rows that a merge's ``out_id`` names and writes the best ``k`` of them.
+``HZ_K_SEARCH_LSCAN`` (``ListScanParams``) is the filtered scan over an IVF index's lists: workgroup (j, q) scans
+the j-th tile of the lists that ``probes[q]`` names.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -58,6 +60,22 @@ class RescoreParams(C.Structure):
                 ("k", C.c_int), ("ldc", C.c_int)]
 
 
+@N.params_of("HZ_K_SEARCH_LSCAN")
+class ListScanParams(C.Structure):
+    """HzSearchListParams: the fields of ``FilterScanParams`` (``N`` stored rows, whole tiles; ``cand`` holds
+    [P][Q][k] keys), then ``probes`` (device int32 [Q][nprobe], or 0: every list), ``list_off`` (int32 [nlist + 1]),
+    ``list_tiles`` (int32 [N / tile_rows()]), ``rowid`` (int32 [N]) and ``nlist``, ``nprobe``, ``P``."""
+    _fields_ = FilterScanParams._fields_ + [("probes", C.c_void_p), ("list_off", C.c_void_p), ("list_tiles", C.c_void_p),
+                                            ("rowid", C.c_void_p), ("nlist", C.c_int), ("nprobe", C.c_int),
+                                            ("P", C.c_int), ("pad_", C.c_int)]
+
+    def merge_params(self) -> SearchParams:
+        """The merge's block for this scan's candidates: ``ntile`` = P, so N = P * 256."""
+        sp = SearchParams.from_buffer_copy(self)
+        sp.N = self.P * 256
+        return sp
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -67,6 +85,7 @@ def _sigs(lib):
     N._sig(lib, "hz_search_fscan_launch", C.c_int, C.POINTER(FilterScanParams), P)
     N._sig(lib, "hz_search_qscan_launch", C.c_int, C.POINTER(QuantScanParams), P)
     N._sig(lib, "hz_search_rescore_launch", C.c_int, C.POINTER(RescoreParams), P)
+    N._sig(lib, "hz_search_lscan_launch", C.c_int, C.POINTER(ListScanParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
     N._sig(lib, "hz_index_last_error", C.c_char_p)
     N._sig(lib, "hz_index_open", P, C.c_char_p, C.c_int, C.c_int)
@@ -86,6 +105,9 @@ def _sigs(lib):
     N._sig(lib, "hz_index_search2", C.c_int, P, C.c_int, P, P, C.c_int, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_add_qr", C.c_int, P, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_read_rescore", C.c_int, P, P, C.c_longlong)
+    N._sig(lib, "hz_index_search3", C.c_int, P, C.c_int, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P)
+    N._sig(lib, "hz_index_probes", C.c_int, P, C.c_int, P, C.c_int, C.c_int, P)
+    N._sig(lib, "hz_index_describe3", C.c_int, P, C.POINTER(U64))
 
 
 N._EXTRA_SIGS.append(_sigs)
@@ -133,3 +155,14 @@ def launch_quant(prm: QuantScanParams, stream: int = 0) -> tuple:
 def launch_rescore(prm: RescoreParams, stream: int = 0) -> int:
     """The rescore launch on ``stream`` -> its code (0, or negative for a refused block: nothing ran)."""
     return int(N.lib().hz_search_rescore_launch(C.byref(prm), stream))
+
+
+def launch_list(prm: ListScanParams, stream: int = 0) -> tuple:
+    """List scan then merge (over the P candidate lists) on ``stream``: (scan code, merge code); no merge after a
+    refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_lscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    sp = prm.merge_params()
+    return rc, lib.hz_search_merge_launch(C.byref(sp), stream)

@@ -17,7 +17,15 @@ would have them, their blocks after the scales. Version 4 is version 3 plus the 
 and ``rescore_off``: a 4096-aligned block of ``[count][dim]`` bf16 rows after every version-3 block, the rows a
 bf16 index of the same vectors holds (``write_index(dtype="fp8", rescore=True)``). A search of such an index is
 two-stage (``search(refine=R)``): the fp8 rows give the best R candidates, which are re-scored against the bf16
-rows; the best k of them are returned.
+rows; the best k of them are returned. Version 5 is an IVF index (``write_index(ivf=nlist)``): version 2 whose
+rows, tags and live bitmap are stored list by list around ``nlist`` k-means centroids, every list on a tile
+boundary (``capacity`` = tiles * 256 stored rows; the padding rows are dead), plus the JSON block ``"ivf"``:
+``nlist``, the default ``nprobe``, ``seed``, ``iters`` and the offsets of four 4096-aligned blocks -- ``centroids_off``
+(bf16 ``[nlist][dim]``), ``list_off_off`` (int32 ``[nlist + 1]``, offsets into the next table), ``list_tiles_off``
+(int32 ``[tiles]``, each list's tile ids) and ``rowid_off`` (int32 ``[capacity]``: the external id of each stored
+row, -1 on padding). ``count`` stays the number of vectors; ids, labels and every public call speak external ids
+(the row's position in the input of ``write_index``). A search scans the ``nprobe`` lists whose centroids are
+nearest to the query (``search(nprobe=...)``; ``"all"`` scans every list and is exact).
 
 A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
 positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
@@ -44,6 +52,11 @@ VERSION = 1
 VERSION2 = 2  # version 1 plus the JSON keys capacity / tags_off / live_off and their two blocks
 VERSION3 = 3  # fp8 rows: uint8 codes, the JSON key scales_off and its block; tags / live as in version 2, or absent
 VERSION4 = 4  # version 3 plus the JSON keys rescore / rescore_off and the block of bf16 rows they name
+VERSION5 = 5  # version 2 stored list by list plus the JSON block ivf and the four blocks it names
+TILE = 256    # HZ_SEARCH_TILE (csrc/hipzap.h): an IVF list starts on a tile boundary
+IVF_MAX_LISTS = 65536
+IVF_SAMPLE = 256  # k-means trains on at most this many rows per centroid
+IVF_KEYS = ("centroids_off", "list_off_off", "list_tiles_off", "rowid_off")
 DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3"}  # write_index(dtype=...) -> the header's "dtype"
 FP8 = "fp8_e4m3"
 METRICS = ("cosine", "ip")
@@ -166,10 +179,12 @@ def unpack_live(words, n: int) -> np.ndarray:
 
 
 def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None, scales=None,
-                rescore=None) -> dict:
+                rescore=None, ivf=None) -> dict:
     """The file of ``hdr`` and ``rows``: version 1 without ``tags`` / ``live``, else version 2 (zero tags / all
     live where one is missing); with ``scales`` (fp8 rows) version 3, whose tags and bitmap are present under
-    the same rule; with ``rescore`` as well (bf16 bit patterns [N, D]) version 4, their block last.
+    the same rule; with ``rescore`` as well (bf16 bit patterns [N, D]) version 4, their block last. With ``ivf``
+    (:func:`ivf_layout`'s tables; ``rows``, ``tags`` and ``live`` in stored order, ``hdr["count"]`` the number of
+    vectors) version 5, the four tables last.
     Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
     if rescore is not None and (scales is None or rescore.shape != rows.shape or rescore.dtype != np.uint16):
@@ -177,12 +192,15 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
 
     def align(x):
         return -(-x // ALIGN) * ALIGN
+    if ivf is not None and (scales is not None or tags is None or live is None or n % TILE):
+        raise ValueError("an IVF index holds bf16 rows, tags and a live bitmap for whole tiles")
     blocks = tags is not None or live is not None
+    tables = ()  # the four blocks of an IVF index
     if not blocks and scales is None:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
-        version = VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
+        version = VERSION5 if ivf is not None else VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
         if scales is not None:
             hdr = dict(hdr, scales_off=0)
         if blocks:
@@ -191,6 +209,11 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             hdr = dict(hdr, capacity=int(max(capacity or 0, n)), tags_off=0, live_off=0)
         if rescore is not None:
             hdr = dict(hdr, rescore="bf16", rescore_off=0)
+        if ivf is not None:
+            tables = (np.ascontiguousarray(ivf["centroids"]).astype("<u2"), np.asarray(ivf["list_off"]).astype("<i4"),
+                      np.asarray(ivf["list_tiles"]).astype("<i4"), np.asarray(ivf["rowid"]).astype("<i4"))
+            hdr = dict(hdr, ivf=dict({k: int(ivf[k]) for k in ("nlist", "nprobe", "seed", "iters")},
+                                     **{k: 0 for k in IVF_KEYS}))
         while True:  # the offsets follow the JSON's own length: a few rounds until they agree
             js = json.dumps(hdr).encode()
             data_off = align(HEAD.size + len(js))
@@ -205,12 +228,19 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
                 end = live_off + words.nbytes
             if rescore is not None:
                 offs["rescore_off"] = align(end)
-            if all(hdr[k] == v for k, v in offs.items()):
+            ioffs = {}
+            for key, block in zip(IVF_KEYS, tables):
+                ioffs[key] = align(end)
+                end = ioffs[key] + block.nbytes
+            if all(hdr[k] == v for k, v in offs.items()) and all(hdr["ivf"][k] == v for k, v in ioffs.items()):
                 break
             hdr.update(offs)
+            if ioffs:
+                hdr["ivf"].update(ioffs)
     tmp = path + ".tmp"
     with open(tmp, "wb") as f:
-        f.write(HEAD.pack(MAGIC, version, len(js), data_off, n, rows.shape[1], METRICS.index(hdr["metric"])))
+        f.write(HEAD.pack(MAGIC, version, len(js), data_off, n if ivf is None else hdr["count"], rows.shape[1],
+                          METRICS.index(hdr["metric"])))
         f.write(js)
         f.write(bytes(data_off - HEAD.size - len(js)))
         f.write(rows.tobytes())
@@ -228,19 +258,80 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         if rescore is not None:
             f.write(bytes(hdr["rescore_off"] - at))
             f.write(np.ascontiguousarray(rescore).astype("<u2").tobytes())
+        for key, block in zip(IVF_KEYS, tables):
+            f.write(bytes(hdr["ivf"][key] - at))
+            f.write(block.tobytes())
+            at = hdr["ivf"][key] + block.nbytes
     os.replace(tmp, path)
     return hdr
 
 
+def _nearest_centroid(rows32: np.ndarray, cent32: np.ndarray) -> np.ndarray:
+    """The centroid of largest inner product per row (the lowest index among equals), int32 [N]; fp32, in blocks."""
+    out = np.empty(rows32.shape[0], np.int32)
+    step = max(1, (1 << 24) // max(cent32.shape[0], 1))
+    for a in range(0, rows32.shape[0], step):
+        out[a:a + step] = np.argmax(rows32[a:a + step] @ cent32.T, axis=1)
+    return out
+
+
+def ivf_kmeans(rows32: np.ndarray, nlist: int, metric: str, seed: int = 0, iters: int = 10):
+    """k-means over the stored rows (bf16 values as fp32 [N, D]) -> (centroid bf16 bits uint16 [nlist, D], the list
+    of every row int32 [N]). Trains on at most ``IVF_SAMPLE`` rows per centroid, drawn with ``seed``; the first
+    centroids are ``nlist`` distinct sample rows. Assignment is by the largest inner product with the bf16-rounded
+    centroids; ``cosine``: spherical k-means (a centroid is its members' mean divided by its norm), ``ip``: plain
+    means. A centroid that loses every member keeps its value. Lists may be empty."""
+    rng = np.random.default_rng(seed)
+    n = rows32.shape[0]
+    m = min(n, IVF_SAMPLE * nlist)
+    sample = rows32[np.sort(rng.choice(n, m, replace=False))] if m < n else rows32
+    cent = sample[np.sort(rng.choice(m, nlist, replace=False))].astype(np.float32)
+    for _ in range(int(iters)):
+        a = _nearest_centroid(sample, bf16_to_f32(to_bf16(cent)))
+        order = np.argsort(a, kind="stable")
+        lists, starts, sizes = np.unique(a[order], return_index=True, return_counts=True)
+        sums = np.add.reduceat(sample[order].astype(np.float64), starts, axis=0)
+        mean = (sums / sizes[:, None]).astype(np.float32)
+        if metric == "cosine":
+            mean = mean / np.maximum(np.sqrt((mean * mean).sum(axis=1, dtype=np.float32)), np.float32(1e-12))[:, None]
+        cent[lists] = mean
+    bits = to_bf16(cent)
+    return bits, _nearest_centroid(rows32, bf16_to_f32(bits))
+
+
+def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
+    """The stored order of an IVF index whose row ``i`` belongs to list ``assign[i]``: list after list, each list's
+    rows in ascending id and starting on a tile boundary -> ``list_off`` int32 [nlist + 1], ``list_tiles`` int32
+    [tiles] (list l's tiles are ``list_tiles[list_off[l]:list_off[l + 1]]``) and ``rowid`` int32 [tiles * TILE]
+    (the id of each stored row, -1 on padding)."""
+    sizes = np.bincount(assign, minlength=nlist)
+    ntiles = -(-sizes // TILE)
+    list_off = np.concatenate([[0], np.cumsum(ntiles)]).astype(np.int32)
+    rowid = np.full(int(list_off[-1]) * TILE, -1, np.int32)
+    order = np.argsort(assign, kind="stable")  # ascending ids inside a list
+    first = np.concatenate([[0], np.cumsum(sizes)])[:-1]
+    lists = assign[order]
+    rowid[list_off[lists].astype(np.int64) * TILE + (np.arange(order.size) - first[lists])] = order
+    return {"list_off": list_off, "list_tiles": np.arange(int(list_off[-1]), dtype=np.int32), "rowid": rowid}
+
+
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
-                dtype: str = "bf16", rescore: bool = False) -> dict:
+                dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
+                ivf_iters: int = 10) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
     scale per row (:func:`prepare_rows_fp8`), a version-3 file; with ``rescore=True`` a version-4 file, which
-    also holds the rows of the bf16 index of the same vectors (:func:`prepare_rows`) for the second stage."""
+    also holds the rows of the bf16 index of the same vectors (:func:`prepare_rows`) for the second stage.
+    ``ivf=nlist``: an IVF index, a version-5 file -- the rows a plain bf16 index stores (the same bits), grouped
+    into ``nlist`` lists by :func:`ivf_kmeans` (``ivf_seed``, ``ivf_iters``) and stored in :func:`ivf_layout`'s order;
+    ``nprobe``: the lists a search scans by default, ``min(nlist, 16)`` when None. Ids stay the positions in
+    ``vectors``."""
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    if ivf is not None and (dtype != "bf16" or rescore):
+        raise ValueError(f"ivf={ivf!r} goes with dtype='bf16' without rescore rows, got dtype={dtype!r}, rescore={rescore!r}: "
+                         f"fp8 and two-stage IVF indexes are not built")
     if rescore and dtype != "fp8":
         raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
     rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
@@ -256,7 +347,31 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
            "embed": dict(embed) if embed else None}
     if labels is not None:
         hdr["labels"] = labels
+    if ivf is not None:
+        if not _is_int(ivf) or not 1 <= ivf <= min(n, IVF_MAX_LISTS):
+            raise ValueError(f"ivf must be an integer in 1..min(count, {IVF_MAX_LISTS}) = 1..{min(n, IVF_MAX_LISTS)}, got {ivf!r}")
+        nlist = int(ivf)
+        if nprobe is None:
+            nprobe = min(nlist, 16)
+        if not _is_int(nprobe) or not 1 <= nprobe <= min(nlist, MAX_K):
+            raise ValueError(f"nprobe must be an integer in 1..min(ivf, {MAX_K}) = 1..{min(nlist, MAX_K)}, got {nprobe!r}")
+        if not _is_int(ivf_seed) or ivf_seed < 0 or not _is_int(ivf_iters) or ivf_iters < 0:
+            raise ValueError(f"ivf_seed and ivf_iters must be integers >= 0, got {ivf_seed!r}, {ivf_iters!r}")
+        cbits, assign = ivf_kmeans(bf16_to_f32(rows), nlist, metric, int(ivf_seed), int(ivf_iters))
+        lay = ivf_layout(assign, nlist)
+        real = lay["rowid"] >= 0
+        srows = np.zeros((real.size, d), np.uint16)
+        srows[real] = rows[lay["rowid"][real]]
+        stags = np.zeros(real.size, np.uint32)
+        if tags is not None:
+            stags[real] = tags[lay["rowid"][real]]
+        lay.update(centroids=cbits, nlist=nlist, nprobe=int(nprobe), seed=int(ivf_seed), iters=int(ivf_iters))
+        return _write_file(path, hdr, srows, stags, real, ivf=lay)
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows)
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
 
 
 def read_header(path: str) -> dict:
@@ -266,7 +381,7 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version not in (VERSION, VERSION2, VERSION3, VERSION4):
+        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
@@ -285,7 +400,19 @@ def read_header(path: str) -> dict:
         raise ValueError(f"{path}: dim of an fp8 index must be a multiple of 16 in 16..2048, got {dim}")
     if hdr.get("labels") is not None and len(hdr["labels"]) != count:
         raise ValueError(f"{path}: {len(hdr['labels'])} labels for {count} rows")
-    end = data_off + count * dim * (1 if fp8 else 2)
+    ivf = hdr.get("ivf")
+    if (version == VERSION5) != (ivf is not None):
+        raise ValueError(f"{path}: an ivf block belongs to a version-5 file and to no other (version {version})")
+    stored = count  # rows in the file's blocks
+    if version == VERSION5:
+        stored = hdr.get("capacity")
+        if not _is_int(stored) or stored < count or stored % TILE or stored >= 2 ** 31:
+            raise ValueError(f"{path}: capacity {stored!r} of an IVF index is not a whole number of tiles holding {count} rows")
+        if not isinstance(ivf, dict) or not all(_is_int(ivf.get(k)) for k in ("nlist", "nprobe", "seed", "iters") + IVF_KEYS):
+            raise ValueError(f"{path}: the ivf block lacks one of nlist, nprobe, seed, iters, {', '.join(IVF_KEYS)}")
+        if not 1 <= ivf["nlist"] <= min(count, IVF_MAX_LISTS) or not 1 <= ivf["nprobe"] <= min(ivf["nlist"], MAX_K):
+            raise ValueError(f"{path}: ivf nlist {ivf['nlist']} / nprobe {ivf['nprobe']} out of range for {count} rows")
+    end = data_off + stored * dim * (1 if fp8 else 2)
     if fp8:
         off = hdr.get("scales_off")
         if not isinstance(off, int) or off % ALIGN:
@@ -298,8 +425,8 @@ def read_header(path: str) -> dict:
         if ("tags_off" in hdr) != ("live_off" in hdr):
             raise ValueError(f"{path}: a version-3 file with only one of tags_off / live_off")
     last = end  # the end of the last block before a rescore block
-    if version == VERSION2 or (fp8 and "tags_off" in hdr):
-        for key, nbytes in (("tags_off", 4 * count), ("live_off", 4 * (-(-count // 32)))):
+    if version in (VERSION2, VERSION5) or (fp8 and "tags_off" in hdr):
+        for key, nbytes in (("tags_off", 4 * stored), ("live_off", 4 * (-(-stored // 32)))):
             off = hdr.get(key)
             if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
                 raise ValueError(f"{path}: the {key[:4]} block lies outside the file")
@@ -314,7 +441,21 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path}: the rescore block at {off} overlaps another block, which ends at {last}")
         if off + 2 * count * dim > size:
             raise ValueError(f"{path}: the rescore block lies outside the file")
+    if version == VERSION5:
+        sizes = (2 * ivf["nlist"] * dim, 4 * (ivf["nlist"] + 1), 4 * (stored // TILE), 4 * stored)
+        for key, nbytes in zip(IVF_KEYS, sizes):
+            off = ivf[key]
+            if off % ALIGN or off < last or off + nbytes > size:
+                raise ValueError(f"{path}: the ivf block {key[:-4]} at {off} is unaligned, overlaps another block or lies "
+                                 f"outside the file")
+            last = off + nbytes
     return dict(hdr, data_off=int(data_off))
+
+
+def stored_rows(hdr: dict) -> int:
+    """Rows in the file's row, tag and live blocks: ``count``, or an IVF index's ``capacity`` (whole tiles, stored
+    list by list -- its blocks are in stored order, :func:`read_ivf`'s ``rowid`` gives each stored row's id)."""
+    return hdr["capacity"] if "ivf" in hdr else hdr["count"]
 
 
 def read_tags(path: str) -> np.ndarray:
@@ -322,7 +463,7 @@ def read_tags(path: str) -> np.ndarray:
     hdr = read_header(path)
     if "tags_off" not in hdr:
         return np.zeros(hdr["count"], np.uint32)
-    return np.fromfile(path, "<u4", hdr["count"], offset=hdr["tags_off"]).astype(np.uint32)
+    return np.fromfile(path, "<u4", stored_rows(hdr), offset=hdr["tags_off"]).astype(np.uint32)
 
 
 def read_live(path: str) -> np.ndarray:
@@ -330,7 +471,8 @@ def read_live(path: str) -> np.ndarray:
     hdr = read_header(path)
     if "live_off" not in hdr:
         return np.ones(hdr["count"], bool)
-    return unpack_live(np.fromfile(path, "<u4", -(-hdr["count"] // 32), offset=hdr["live_off"]), hdr["count"])
+    n = stored_rows(hdr)
+    return unpack_live(np.fromfile(path, "<u4", -(-n // 32), offset=hdr["live_off"]), n)
 
 
 def file_info(path: str) -> dict:
@@ -339,6 +481,8 @@ def file_info(path: str) -> dict:
     v2 = "tags_off" in hdr
     info = {"version": VERSION2 if v2 else VERSION, "capacity": hdr.get("capacity", hdr["count"]),
             "live": int(read_live(path).sum()), "tags": v2}
+    if "ivf" in hdr:
+        info.update(version=VERSION5, ivf=ivf_facts(hdr, read_ivf(path)))
     if hdr["dtype"] == FP8:
         info.update(version=VERSION3, dtype=FP8)
     if "rescore_off" in hdr:
@@ -350,7 +494,58 @@ def read_rows(path: str) -> np.ndarray:
     """The row block: bf16 bit patterns, uint16 [count, dim]; e4m3fn codes, uint8, for an fp8 index."""
     hdr = read_header(path)
     dt = np.uint8 if hdr["dtype"] == FP8 else np.uint16
-    return np.fromfile(path, dt, hdr["count"] * hdr["dim"], offset=hdr["data_off"]).reshape(hdr["count"], hdr["dim"])
+    n = stored_rows(hdr)
+    return np.fromfile(path, dt, n * hdr["dim"], offset=hdr["data_off"]).reshape(n, hdr["dim"])
+
+
+def read_ivf(path: str) -> dict:
+    """The tables of an IVF index, validated: ``centroids`` (bf16 bits uint16 [nlist, dim]), ``list_off`` int32
+    [nlist + 1], ``list_tiles`` int32 [tiles], ``rowid`` int32 [capacity], and what follows from them: ``pos``
+    int32 [count] (the stored row of each id) and ``list_of`` int32 [count] (its list). A ValueError names the
+    first inconsistency: offsets that do not rise from 0 to the tile count, a tile id out of range or in two
+    lists, ids that are not each present once, a live padding row or a list whose ids do not ascend."""
+    hdr = read_header(path)
+    if "ivf" not in hdr:
+        raise ValueError(f"{path}: not an IVF index (version 5 holds the lists)")
+    ivf, n, cap, dim = hdr["ivf"], hdr["count"], hdr["capacity"], hdr["dim"]
+    nlist, ntile = ivf["nlist"], cap // TILE
+    cent = np.fromfile(path, "<u2", nlist * dim, offset=ivf["centroids_off"]).astype(np.uint16).reshape(nlist, dim)
+    off = np.fromfile(path, "<i4", nlist + 1, offset=ivf["list_off_off"]).astype(np.int32)
+    tiles = np.fromfile(path, "<i4", ntile, offset=ivf["list_tiles_off"]).astype(np.int32)
+    rowid = np.fromfile(path, "<i4", cap, offset=ivf["rowid_off"]).astype(np.int32)
+    if not np.isfinite(bf16_to_f32(cent)).all():
+        raise ValueError(f"{path}: an ivf centroid is not finite")
+    if off[0] != 0 or off[-1] != ntile or (np.diff(off) < 0).any():
+        raise ValueError(f"{path}: ivf list_off does not rise from 0 to the {ntile} tiles")
+    if tiles.size and (tiles.min() < 0 or tiles.max() >= ntile):
+        raise ValueError(f"{path}: an ivf list_tiles entry is outside [0, {ntile})")
+    if np.unique(tiles).size != ntile:
+        raise ValueError(f"{path}: ivf list_tiles names a tile twice (every tile belongs to exactly one list)")
+    real = rowid >= 0
+    if (rowid < -1).any() or (rowid >= n).any() or int(real.sum()) != n or np.unique(rowid[real]).size != n:
+        raise ValueError(f"{path}: ivf rowid is not a permutation of the {n} ids over the stored rows (-1 on padding)")
+    if read_live(path)[~real].any():
+        raise ValueError(f"{path}: a padding row of the IVF index is live")
+    tile_list = np.empty(ntile, np.int32)
+    tile_list[tiles] = np.repeat(np.arange(nlist, dtype=np.int32), np.diff(off))
+    seq = rowid.reshape(ntile, TILE)[tiles].reshape(-1)   # the stored rows in list order
+    lst = np.repeat(tile_list[tiles], TILE)
+    keep = seq >= 0
+    ids, lst = seq[keep], lst[keep]
+    if ((np.diff(ids) <= 0) & (np.diff(lst) == 0)).any():
+        raise ValueError(f"{path}: the ids of an ivf list do not ascend in stored order")
+    pos = np.empty(n, np.int32)
+    pos[rowid[real]] = np.flatnonzero(real)
+    return {"centroids": cent, "list_off": off, "list_tiles": tiles, "rowid": rowid, "pos": pos,
+            "list_of": tile_list[pos // TILE], **{k: ivf[k] for k in ("nlist", "nprobe", "seed", "iters")}}
+
+
+def ivf_facts(hdr: dict, t: dict) -> dict:
+    """What ``describe()`` and ``hipzap info`` say about the lists."""
+    sizes = np.bincount(t["list_of"], minlength=t["nlist"])
+    return {"nlist": int(t["nlist"]), "nprobe": int(t["nprobe"]), "seed": int(t["seed"]), "iters": int(t["iters"]),
+            "empty_lists": int((sizes == 0).sum()), "largest_list": int(sizes.max()), "tiles": int(hdr["capacity"] // TILE),
+            "padding_rows": int(hdr["capacity"] - hdr["count"])}
 
 
 def read_scales(path: str) -> np.ndarray:
@@ -484,8 +679,10 @@ class _Base:
         self.labels = self.header.get("labels")
         self.dtype = self.header["dtype"]
         self.rescore = "rescore_off" in self.header  # a version-4 file: bf16 rows for a second stage
-        self.version = (VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
+        self.ivf = read_ivf(path) if "ivf" in self.header else None  # the validated tables of a version-5 file
+        self.version = (VERSION5 if self.ivf else VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
                         else VERSION2 if "tags_off" in self.header else VERSION)
+        self.nprobe = self.ivf["nprobe"] if self.ivf else None  # what search(nprobe=None) scans; settable
         self._mut = threading.Lock()  # one mutator at a time
 
     def __enter__(self):
@@ -517,10 +714,39 @@ class _Base:
         raise ValueError(f"refine must be {wants}, got {refine!r} with k = {k} on a {self.dtype} index of version "
                          f"{self.version}")
 
+    def _nprobe(self, nprobe, refine=None) -> int:
+        """``search(nprobe=...)`` -> the lists to scan, 0 for every list (and for an index without lists). On an
+        IVF index ``None`` means ``self.nprobe`` (the header's default unless set), ``"all"`` or a value from
+        ``nlist`` up scans every list, which is exact; anything else must be an integer in 1..min(nlist, MAX_K)."""
+        if self.ivf is None:
+            if nprobe is not None:
+                raise ValueError(f"nprobe={nprobe!r} needs an IVF index (write_index(ivf=...)), this one is version {self.version}")
+            return 0
+        if refine not in (None, 0):
+            raise ValueError(f"refine={refine!r}: an IVF index has no rescore rows (two-stage IVF is not built)")
+        nlist = self.ivf["nlist"]
+        if nprobe is None:
+            nprobe = self.nprobe
+        if isinstance(nprobe, str) and nprobe == "all":
+            return 0
+        if not _is_int(nprobe) or nprobe < 1 or (nprobe > MAX_K and nprobe < nlist):
+            raise ValueError(f"nprobe must be an integer in 1..{min(nlist, MAX_K)}, 'all' or at least nlist = {nlist}, "
+                             f"got {nprobe!r}")
+        return 0 if nprobe >= nlist else int(nprobe)
+
+    def _check_probes(self, q, nprobe):
+        if self.ivf is None:
+            raise ValueError(f"probes needs an IVF index (write_index(ivf=...)), this one is version {self.version}")
+        if not _is_int(nprobe) or not 1 <= nprobe <= min(self.ivf["nlist"], MAX_K):
+            raise ValueError(f"nprobe must be an integer in 1..{min(self.ivf['nlist'], MAX_K)}, got {nprobe!r}")
+        return check_queries(q, self.dim), int(nprobe)
+
     def add(self, vectors, tags=None, labels=None) -> np.ndarray:
         """Append rows (fp32 [n, dim], through :func:`prepare_rows` or, on an fp8 index, :func:`prepare_rows_fp8`:
         the bits ``write_index`` would store) -> their ids, int32 [n]. ``tags``: uint32 [n], default 0.
         ``labels``: required iff the index has labels."""
+        if self.ivf is not None:
+            raise ValueError("IVF indexes do not take add yet: write a new index with write_index(ivf=...)")
         if self.dtype == FP8:
             bits = _QRows(*prepare_rows_fp8(vectors, self.metric),
                           rescore=prepare_rows(vectors, self.metric) if self.rescore else None)
@@ -564,8 +790,16 @@ class _Base:
         ``compact=False`` keeps ids and tombstones; ``compact=True`` drops the dead rows and renumbers the
         rest in order. Version 1 when every row is live and every tag is 0, else version 2; an fp8 index is
         version 3 with or without tags and bitmap under the same rule, and version 4 when it has rescore rows."""
+        if self.ivf is not None and compact:
+            raise ValueError("IVF indexes do not take save(compact=True) yet: ids would change with the lists' layout")
         with self._mut:
             bits, tags, live, *rest = self._state()
+            if self.ivf is not None:  # stored order, as it was read: version 5 again
+                hdr = {"dim": self.dim, "count": self.count, "dtype": self.dtype, "metric": self.metric,
+                       "model": self.header.get("model", ""), "embed": self.header.get("embed")}
+                if self.labels is not None:
+                    hdr["labels"] = list(self.labels)
+                return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), tags, live, ivf=self.ivf)
             scales = rest[0] if rest else None
             rrows = rest[1] if len(rest) > 1 else None
             labels = self.labels
@@ -601,6 +835,11 @@ class RefIndex(_Base):
         self._rrows = bf16_to_f32(self._rbits) if self.rescore else None
         self._tags, self._live = read_tags(path), read_live(path)
         self._cap = max(self.count, int(reserve), int(self.header.get("capacity", 0)))
+        if self.ivf is not None:  # held by id, like every other index; _state() puts the stored order back
+            pos = self.ivf["pos"]
+            self._bits, self._rows, self._tags, self._live = self._bits[pos], self._rows[pos], self._tags[pos], self._live[pos]
+            self._cent = bf16_to_f32(self.ivf["centroids"])
+            self._cap = int(self.header["capacity"])
 
     def allow(self, filt) -> np.ndarray:
         """bool [N] (no filter) or [Q, N]: the rows each query may return."""
@@ -608,15 +847,26 @@ class RefIndex(_Base):
             return self._live
         return self._live[None, :] & ((self._tags[None, :] & filt[:, :1]) == filt[:, 1:])
 
-    def search(self, q, k: int = 10, *, filter=None, refine=None):
+    def probes(self, q, nprobe: int) -> np.ndarray:
+        """The ``nprobe`` lists nearest to each query, best first, int32 [Q, nprobe]: :func:`search_ref` over the
+        centroids."""
+        q, nprobe = self._check_probes(q, nprobe)
+        return search_ref(self._cent, q, nprobe)[1]
+
+    def search(self, q, k: int = 10, *, filter=None, refine=None, nprobe=None):
         """``refine`` (:meth:`_Base._refine`): R > 0 is the two-stage search -- ``search_ref(scales=...)`` at
-        k = R, then those ids re-scored in fp64 over the widened bf16 rows (:func:`rescore_ref`)."""
+        k = R, then those ids re-scored in fp64 over the widened bf16 rows (:func:`rescore_ref`). ``nprobe``
+        (:meth:`_Base._nprobe`, an IVF index): only rows of the lists :meth:`probes` names may be returned."""
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
-        R = self._refine(refine, k)
+        lists = self._nprobe(nprobe, refine)
+        R = 0 if self.ivf is not None else self._refine(refine, k)
         with self._mut:  # the mutators replace the arrays one by one
-            s, i = search_ref(self._rows, q, R or k, None if filt is None and self._live.all() else self.allow(filt),
-                              scales=self.scales)
+            allow = None if filt is None and self._live.all() else self.allow(filt)
+            if lists:
+                near = (self.ivf["list_of"][None, :, None] == self.probes(q, lists)[:, None, :]).any(axis=2)  # [Q, N]
+                allow = near if allow is None else near & allow
+            s, i = search_ref(self._rows, q, R or k, allow, scales=self.scales)
             if R:
                 two = [rescore_ref(self._rrows, q[a], i[a], k) for a in range(q.shape[0])]
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
@@ -650,6 +900,11 @@ class RefIndex(_Base):
         self._tags[ids] = tags
 
     def _state(self):
+        if self.ivf is not None:
+            pos, cap = self.ivf["pos"], int(self.header["capacity"])
+            bits, tags, live = np.zeros((cap, self.dim), np.uint16), np.zeros(cap, np.uint32), np.zeros(cap, bool)
+            bits[pos], tags[pos], live[pos] = self._bits, self._tags, self._live
+            return bits, tags, live
         if self.rescore:
             return self._bits, self._tags, self._live, self.scales, self._rbits
         if self.scales is not None:
@@ -662,7 +917,8 @@ class RefIndex(_Base):
     def describe(self) -> dict:
         return {"path": self.path, "backend": "cpu", **{k: v for k, v in self.header.items() if k != "labels"},
                 "labels": self.labels is not None, "capacity": self._cap, "live": int(self._live.sum()),
-                "tags": bool(self._tags.any()) or "tags_off" in self.header}
+                "tags": bool(self._tags.any()) or "tags_off" in self.header,
+                **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
         self._rows = None
@@ -695,14 +951,36 @@ class Index(_Base):
         for c in range(self.contexts):
             self._free.put(c)
 
-    def search(self, q, k: int = 10, ctx: int | None = None, *, filter=None, refine=None):
+    def probes(self, q, nprobe: int, ctx: int | None = None) -> np.ndarray:
+        """The ``nprobe`` lists nearest to each query, best first, int32 [Q, nprobe]: the coarse stage of a search
+        alone (scan + merge over the centroids)."""
+        q, nprobe = self._check_probes(q, nprobe)
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        out = np.empty((q.shape[0], nprobe), np.int32)
+        c = self._free.get() if ctx is None else ctx
+        try:
+            for a in range(0, q.shape[0], MAX_Q):
+                part, o = q[a:a + MAX_Q], out[a:a + MAX_Q]
+                rc = self._lib.hz_index_probes(self._h, c, part.ctypes.data, part.shape[0], nprobe, o.ctypes.data)
+                if rc:
+                    raise RuntimeError(f"hz_index_probes failed with code {rc}")
+        finally:
+            if ctx is None:
+                self._free.put(c)
+        return out
+
+    def search(self, q, k: int = 10, ctx: int | None = None, *, filter=None, refine=None, nprobe=None):
         """fp32 queries [Q, dim] -> (scores float32 [Q, k], ids int32 [Q, k]), best first. ``filter``:
         ``(mask, value)`` for all queries or Q such pairs; a row passes iff ``(tag & mask) == value``.
         ``refine`` (an index with rescore rows): the candidates R that the fp8 scan hands the exact bf16
-        second stage, ``None`` for 128, ``0`` for the fp8 answer alone (:meth:`_Base._refine`)."""
+        second stage, ``None`` for 128, ``0`` for the fp8 answer alone (:meth:`_Base._refine`). ``nprobe`` (an
+        IVF index): the lists each query scans, ``None`` for ``self.nprobe``, ``"all"`` for every list
+        (:meth:`_Base._nprobe`)."""
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
-        R = self._refine(refine, k)
+        lists = self._nprobe(nprobe, refine)
+        R = 0 if self.ivf is not None else self._refine(refine, k)
         if self._h is None:
             raise RuntimeError("the index is closed")
         scores = np.empty((q.shape[0], k), np.float32)
@@ -713,8 +991,8 @@ class Index(_Base):
                 part = q[a:a + MAX_Q]
                 s, i = scores[a:a + MAX_Q], ids[a:a + MAX_Q]  # contiguous row ranges of the outputs
                 f = None if filt is None else np.ascontiguousarray(filt[a:a + MAX_Q])
-                rc = self._lib.hz_index_search2(self._h, c, part.ctypes.data, None if f is None else f.ctypes.data,
-                                                part.shape[0], k, R, s.ctypes.data, i.ctypes.data)
+                rc = self._lib.hz_index_search3(self._h, c, part.ctypes.data, None if f is None else f.ctypes.data,
+                                                part.shape[0], k, R, lists, s.ctypes.data, i.ctypes.data)
                 if rc:
                     raise RuntimeError(f"hz_index_search failed with code {rc}")
         finally:
@@ -768,7 +1046,7 @@ class Index(_Base):
                         "hz_index_set_tags")
 
     def _state(self):
-        n = self.count
+        n = self.count if self.ivf is None else int(self.header["capacity"])  # an IVF index: the stored rows
         tags, words = np.empty(n, np.uint32), np.empty(-(-n // 32), np.uint32)
         if self.dtype == FP8:
             codes, scales = np.empty((n, self.dim), np.uint8), np.empty(n, np.float32)
@@ -797,7 +1075,8 @@ class Index(_Base):
                 **{k: v for k, v in self.header.items() if k != "labels"}, "labels": self.labels is not None,
                 "contexts": int(out[3]), "tile_rows": int(out[4]), "programs": int(out[5]), "device_bytes": int(out[6]),
                 "capacity": int(more[0]), "live": int(more[1]), "tags": bool(more[2]), "filtered": bool(more[3]),
-                **({"rescore_rows": "host" if more[7] else "device"} if more[6] else {})}
+                **({"rescore_rows": "host" if more[7] else "device"} if more[6] else {}),
+                **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -516,8 +516,10 @@ def search():
     "value"}`` or ``"tag": t`` restricts the answer to the rows whose tag passes ``(tag & mask) == value``.
     ``"refine"`` (an index with rescore rows): the candidates the fp8 scan hands the exact bf16 second stage,
     an integer in k..128, ``0`` for none; absent or null: 128 on such an index. The answer's ``"refine"`` is the
-    R used, 0 if none."""
-    from ..search import check_k, check_queries, normalize_rows
+    R used, 0 if none. ``"nprobe"`` (an IVF index): the lists each query scans, an integer in 1..min(nlist, 128)
+    or ``"all"``; absent: ``extra.index_nprobe``, else the file's default. The answer of an IVF index carries
+    ``"ivf": true`` and the ``"nprobe"`` used (``"all"`` when every list was scanned)."""
+    from ..search import MAX_K, check_k, check_queries, normalize_rows
     s = get_server()
     body = {}
     if request.mimetype != "application/octet-stream" and request.mimetype not in IMAGE_TYPES:
@@ -544,9 +546,14 @@ def search():
     if index.metric == "cosine":
         q = normalize_rows(q)
     filt = _search_filter(body)
-    refine = index._refine(body.get("refine"), k)  # ValueError -> 400
+    nprobe = body.get("nprobe")
+    if index.ivf is not None and nprobe is not None and nprobe != "all" and (
+            isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= min(index.ivf["nlist"], MAX_K)):
+        raise ValueError(f"nprobe must be an integer in 1..{min(index.ivf['nlist'], MAX_K)} or \"all\", got {nprobe!r}")
+    lists = index._nprobe(nprobe, body.get("refine"))  # ValueError -> 400 (nprobe without lists, refine with them)
+    refine = 0 if index.ivf is not None else index._refine(body.get("refine"), k)  # ValueError -> 400
     with phase("search"):
-        scores, ids = index.search(q, k, filter=filt, refine=refine)
+        scores, ids = index.search(q, k, filter=filt, refine=None if index.ivf is not None else refine, nprobe=nprobe)
     dt = (time.perf_counter() - t0) * 1e3
     if "application/octet-stream" in request.headers.get("Accept", ""):
         out = np.empty(ids.shape, dtype=[("id", "<i4"), ("score", "<f4")])
@@ -562,7 +569,7 @@ def search():
             h["label"] = labels[i]
         return h
     return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "refine": refine, "k": k,
-                  "count": int(index.count),
+                  "count": int(index.count), **({"ivf": True, "nprobe": lists or "all"} if index.ivf is not None else {}),
                   "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(ids, scores)],
                   "timing_ms": round(dt, 3)})
 

@@ -506,9 +506,17 @@ class ModelServer:
                 dim, want = read_header(path)["dim"], int(backend.embed["dim"])
                 if dim != want:
                     raise RuntimeError(f"{name}: index {path} has dim {dim}, the backend's embed.dim is {want}")
-                self._indexes[name] = open_index(path, self.backend, self.settings.devices[0],
-                                                 reserve=int(self.spec(name).extra.get("index_reserve", 0)),
-                                                 rescore_rows=self.spec(name).extra.get("index_rescore_rows", "device"))
+                ix = open_index(path, self.backend, self.settings.devices[0],
+                                reserve=int(self.spec(name).extra.get("index_reserve", 0)),
+                                rescore_rows=self.spec(name).extra.get("index_rescore_rows", "device"))
+                if self.spec(name).extra.get("index_nprobe") is not None:  # overrides the IVF header's default
+                    try:
+                        ix._nprobe(self.spec(name).extra["index_nprobe"])
+                    except ValueError as e:
+                        ix.close()
+                        raise RuntimeError(f"{name}: extra.index_nprobe: {e}") from None
+                    ix.nprobe = self.spec(name).extra["index_nprobe"]
+                self._indexes[name] = ix
             return self._indexes[name]
 
     def close(self) -> None:
