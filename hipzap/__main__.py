@@ -114,9 +114,15 @@ def cmd_index(a):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
     if a.from_index is not None:
-        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask or a.ivf is not None:
-            raise SystemExit("index: --from-index takes only --dtype, --rescore and --out")
-        hdr = convert_index(a.from_index, a.out, a.dtype, rescore=a.rescore)
+        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask:
+            raise SystemExit("index: --from-index takes only --dtype, --rescore, --ivf with --nprobe / --ivf-seed, and --out")
+        if a.ivf is None and (a.nprobe is not None or a.ivf_seed is not None):
+            raise SystemExit("index: --nprobe and --ivf-seed go with --ivf NLIST")
+        try:
+            hdr = convert_index(a.from_index, a.out, a.dtype, rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe,
+                                ivf_seed=a.ivf_seed or 0)
+        except ValueError as e:
+            raise SystemExit(f"index: {e}") from None
         print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": "labels" in hdr}))
         return
     if (a.vectors is None) == (a.embed_plan is None):
@@ -142,8 +148,18 @@ def cmd_index(a):
     tags = np.load(a.tags, allow_pickle=False) if a.tags else None
     if a.ivf is None and (a.nprobe is not None or a.ivf_seed is not None):
         raise SystemExit("index: --nprobe and --ivf-seed go with --ivf NLIST")
-    hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
-                      rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
+    if a.ivf is not None and a.dtype == "fp8":  # the lists are trained on the bf16 rows, which are then quantised
+        tmp = a.out + ".bf16-ivf.tmp"
+        try:
+            write_index(tmp, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, ivf=a.ivf,
+                        nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
+            hdr = convert_index(tmp, a.out, "fp8", rescore=a.rescore)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+    else:
+        hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
+                          rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
@@ -227,11 +243,12 @@ def main(argv=None):
                     help="with --dtype fp8: also store the bf16 rows (a version-4 file) for two-stage search, "
                          "fp8 scan then exact bf16 re-scoring of the candidates")
     ix.add_argument("--ivf", type=int, default=None, metavar="NLIST",
-                    help="an IVF index (a version-5 file): the rows grouped into NLIST k-means lists; a search scans the "
-                         "--nprobe lists nearest to the query")
+                    help="an IVF index (a version-5 file; with --dtype fp8 version 6, with --rescore 7): the rows grouped "
+                         "into NLIST k-means lists; a search scans the --nprobe lists nearest to the query")
     ix.add_argument("--nprobe", type=int, default=None, help="with --ivf: the lists a search scans by default (min(NLIST, 16))")
     ix.add_argument("--ivf-seed", type=int, default=None, help="with --ivf: the k-means seed (0)")
-    ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept)")
+    ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept); an IVF file keeps its lists "
+                         "(versions 6 and 7), --ivf NLIST builds lists over a plain file's stored rows")
     ix.add_argument("--model", default=None, help="free text kept in the header")
     ix.add_argument("--device", type=int, default=0)
     ix.add_argument("--out", required=True)

@@ -516,6 +516,17 @@ typedef struct HzSearchListParams {
   int nlist, nprobe, P, pad_;
 } HzSearchListParams;
 int hz_search_lscan_launch(const HzSearchListParams* p, hipStream_t st);
+// quantised list scan (HZ_K_SEARCH_QLSCAN): the list scan over rows of OCP e4m3fn bytes with one fp32
+// scale per stored row. `l.f.s.corpus` points at uint8 [N][ldc] (ldc in bytes, ldc % 16 == 0, D % 16 == 0,
+// 16 <= D <= 2048). The score bits of a passing (q, r) are those of HZ_K_SEARCH_QSCAN for the same query, codes
+// and scale; the codes and the scale of a dead or padding row are never loaded. Refusals: the byte rows' of the
+// quantised launcher (-16 D % 16, -17 D < 16, -18 D > 2048, -19 ldc < D, -23 ldc % 16), every one of the list
+// launcher, then -24 scales null and -25 scales not 4-B aligned.
+typedef struct HzSearchQuantListParams {
+  HzSearchListParams l;          // the list scan's block, unchanged
+  const float* scales;           // fp32 [N] in stored order, 4-B aligned
+} HzSearchQuantListParams;
+int hz_search_qlscan_launch(const HzSearchQuantListParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
@@ -596,7 +607,14 @@ int hz_index_search3(void* idx, int ctx, const float* queries, const unsigned* f
                      int nprobe, float* out_score, int* out_id);
 // the coarse stage alone: the nprobe best lists of each query, best first -> out_list int32 [Q][nprobe]
 int hz_index_probes(void* idx, int ctx, const float* queries, int Q, int nprobe, int* out_list);
-// out[8] = {1 for an IVF index, nlist, default nprobe, tiles, external count, 0, 0, 0}
+// An fp8 IVF index (a version-6 or version-7 .hzidx): version 5's layout over version 3's rows --
+// e4m3 codes [capacity][dim] and "scales_off" fp32 [capacity], both in stored order (padding: code 0, scale 1, dead).
+// Its programs replace HZ_K_SEARCH_LSCAN by HZ_K_SEARCH_QLSCAN. Version 7 adds "rescore": "bf16" / "rescore_off":
+// bf16 [count][dim] in EXTERNAL-ID order, the last block (device or pinned host memory per open3's rescore_host).
+// search3 with refine = R on it: list scan and merge at k = R, then HZ_K_SEARCH_RESCORE over rows[id] with
+// N = count. -34 stays the answer to refine on an IVF index without rescore rows. hz_index_read_state_q returns the
+// stored rows, hz_index_read_rescore up to count rows by id. Rows are never added (-34).
+// out[8] = {1 for an IVF index, nlist, default nprobe, tiles, external count, the file's version, 0, 0}
 int hz_index_describe3(void* idx, uint64_t* out);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
@@ -780,7 +798,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_FSCAN, 33, HzSearchFilterParams, hz_search_fscan_op, SEARCH)   \
   X(SEARCH_QSCAN, 34, HzSearchQuantParams, hz_search_qscan_op, SEARCH)   \
   X(SEARCH_RESCORE, 35, HzSearchRescoreParams, hz_search_rescore_op, SEARCH) \
-  X(SEARCH_LSCAN, 36, HzSearchListParams, hz_search_lscan_op, SEARCH)
+  X(SEARCH_LSCAN, 36, HzSearchListParams, hz_search_lscan_op, SEARCH)     \
+  X(SEARCH_QLSCAN, 37, HzSearchQuantListParams, hz_search_qlscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -29,6 +29,12 @@
 // H2D, scan + merge over the centroids at k = nprobe into the context's probe buffer, the list scan over those
 // lists with P = the tiles of the nprobe largest lists, merge over the P candidate lists, two D2H; nprobe = 0
 // (every list) has no coarse stage. nprobe is part of a program's key. Rows are never added.
+//
+// An fp8 IVF index (a version-6 or version-7 file): version 5's layout over e4m3 rows with one scale
+// per stored row; the list scan of its programs is HZ_K_SEARCH_QLSCAN, the coarse stage (bf16 centroids) is the
+// same. Version 7 also holds the vectors' bf16 rows BY EXTERNAL ID (`n_ext` rows, device or pinned host memory):
+// with refine = R the list scan and its merge run at k = R into the context's intermediate buffer and
+// HZ_K_SEARCH_RESCORE re-scores those external ids against rrows[id] with N = n_ext. R is part of the key too.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -74,8 +80,9 @@ struct Ctx {
   char* probe_dev = nullptr;          // IVF only: the coarse stage's scores and list ids, the layout of out_dev
   unsigned long long* ccand = nullptr;  // IVF only: the coarse stage's candidate scratch
   uint64_t ccand_bytes = 0;
-  // (Q, k, filtered, R; R = 0: one stage); IVF: (Q, k, 1, nprobe; 0: every list) and (Q, nprobe, 2, 0): probes alone
-  std::map<std::tuple<int, int, int, int>, HzProgram> progs;
+  // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
+  // probes alone
+  std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
 constexpr size_t kOutHalf = (size_t)HZ_SEARCH_MAX_Q * HZ_SEARCH_MAX_K * 4;
@@ -107,17 +114,17 @@ struct Index {
   uint64_t live_count = 0;
   bool mutated = false;               // the unfiltered program (N = the file's count, all live) no longer holds
   bool has_tags = false;
-  bool fp8 = false;                   // a version-3 file: e4m3fn byte rows and `scales`
+  bool fp8 = false;                   // a version-3, 4, 6 or 7 file: e4m3fn byte rows and `scales`
   unsigned short* rows = nullptr;     // bf16 [cap][dim], or uint8 [cap][dim] of an fp8 index
   float* scales = nullptr;            // device, cap floats (fp8 only)
-  bool rescore = false;               // a version-4 file: `rrows` beside the fp8 rows
+  bool rescore = false;               // a version-4 or 7 file: `rrows` beside the fp8 rows
   bool rescore_host = false;          // rrows is pinned host memory (hipHostMalloc), else device memory
-  unsigned short* rrows = nullptr;    // bf16 [cap][dim], the allocation
+  unsigned short* rrows = nullptr;    // bf16 [cap][dim] ([n_ext][dim], by external id, of an IVF index), the allocation
   unsigned short* rrows_dev = nullptr;  // the address the rescore kernel reads (the mapped address of a host block)
   unsigned* live = nullptr;          // device, cap / 32 words
   unsigned* tags = nullptr;           // device, cap words
   std::vector<uint32_t> live_host, tags_host;  // mirrors, sized like the device buffers
-  bool ivf = false;                   // a version-5 file
+  bool ivf = false;                   // a version-5, 6 or 7 file
   uint64_t n_ext = 0;                 // IVF: the number of vectors (external ids 0 .. n_ext-1)
   int nlist = 0, nprobe_default = 0;
   unsigned short* centroids = nullptr;  // device bf16 [nlist][dim]
@@ -159,7 +166,8 @@ struct Index {
   uint64_t esize() const { return fp8 ? 1 : 2; }  // bytes per stored element
   uint64_t row_bytes() const { return cap * h.dim * esize(); }
   uint64_t scan_rows() const { return round_up(count, kTile); }  // the filtered programs' N
-  uint64_t rescore_bytes() const { return rescore ? cap * h.dim * 2 : 0; }
+  uint64_t rescore_rows(uint64_t for_cap) const { return ivf ? n_ext : for_cap; }  // an IVF index holds them by id
+  uint64_t rescore_bytes() const { return rescore ? rescore_rows(cap) * h.dim * 2 : 0; }
 
   // a block for the rescore rows in the index's placement: *p the allocation, *dev what a kernel reads
   bool alloc_rescore(uint64_t bytes, unsigned short** p, unsigned short** dev) const {
@@ -200,7 +208,7 @@ struct Index {
   // the context's program for (Q, k, filtered, R), built on first use (the caller holds c.mu). R > 0 (a
   // two-stage index only): stage one runs at k = R into mid_dev and the rescore writes the k results.
   HzProgram program(Ctx& c, int Q, int k, bool filtered, int R, bool* fresh) {
-    const auto key = std::make_tuple(Q, k, (int)filtered, R);
+    const auto key = std::make_tuple(Q, k, (int)filtered, R, 0);
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
@@ -254,9 +262,11 @@ struct Index {
   }
 
   // The IVF programs (the caller holds c.mu). probes_only: H2D of the queries, scan + merge over the centroids
-  // at k = nprobe, D2H of the list ids. Else the search of (Q, k) over nprobe lists, 0 for every list.
-  HzProgram ivf_program(Ctx& c, int Q, int k, int nprobe, bool probes_only, bool* fresh) {
-    const auto key = probes_only ? std::make_tuple(Q, nprobe, 2, 0) : std::make_tuple(Q, k, 1, nprobe);
+  // at k = nprobe, D2H of the list ids. Else the search of (Q, k) over nprobe lists, 0 for every list; R > 0 (an
+  // index with rescore rows): the list scan and its merge run at k = R into mid_dev and the rescore writes the k
+  // results from the rows held by external id.
+  HzProgram ivf_program(Ctx& c, int Q, int k, int nprobe, int R, bool probes_only, bool* fresh) {
+    const auto key = probes_only ? std::make_tuple(Q, nprobe, 2, 0, 0) : std::make_tuple(Q, k, 1, R, nprobe);
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
@@ -273,9 +283,17 @@ struct Index {
     p.corpus = rows;
     p.queries = c.q_dev;
     p.cand = c.cand;
-    p.out_score = reinterpret_cast<float*>(c.out_dev);
-    p.out_id = reinterpret_cast<int*>(c.out_dev + kOutHalf);
-    p.N = (int)count, p.D = p.ldc = (int)h.dim, p.Q = Q, p.k = k;
+    char* stage1 = R ? c.mid_dev : c.out_dev;
+    p.out_score = reinterpret_cast<float*>(stage1);
+    p.out_id = reinterpret_cast<int*>(stage1 + kOutHalf);
+    p.N = (int)count, p.D = p.ldc = (int)h.dim, p.Q = Q, p.k = R ? R : k;
+    HzSearchRescoreParams rp{};  // stage one's ids are external ids: the rescore rows are held by id
+    rp.rows = rrows_dev;
+    rp.queries = c.q_dev;
+    rp.in_id = p.out_id;
+    rp.out_score = reinterpret_cast<float*>(c.out_dev);
+    rp.out_id = reinterpret_cast<int*>(c.out_dev + kOutHalf);
+    rp.N = (int)n_ext, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
     p.cand_bytes = c.cand_bytes;
     lp.f.live = live;
     lp.f.tags = tags;
@@ -294,6 +312,9 @@ struct Index {
     }
     HzSearchParams mp = p;  // the merge over the P candidate lists
     mp.N = lp.P * (int)kTile;
+    HzSearchQuantListParams qlp{};
+    qlp.l = lp;
+    qlp.scales = scales;
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4, qb = (size_t)Q * h.dim * 4;
     int rc = probes_only ? hz_prog_add_memcpy(g, c.q_dev, c.q_host, qb, 0)
@@ -303,8 +324,10 @@ struct Index {
     if (probes_only) {
       if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.probe_dev + kOutHalf, (size_t)Q * nprobe * 4, 0);
     } else {
-      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_LSCAN, &lp, sizeof(lp), 0);
+      if (!rc) rc = fp8 ? hz_prog_add_kernel(g, HZ_K_SEARCH_QLSCAN, &qlp, sizeof(qlp), 0)
+                        : hz_prog_add_kernel(g, HZ_K_SEARCH_LSCAN, &lp, sizeof(lp), 0);
       if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGE, &mp, sizeof(mp), 0);
+      if (!rc && R) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCORE, &rp, sizeof(rp), 0);
       if (!rc) rc = hz_prog_add_memcpy(g, c.out_host, c.out_dev, qk, 0);
       if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.out_dev + kOutHalf, qk, 0);
     }
@@ -329,7 +352,7 @@ struct Index {
     std::vector<unsigned long long*> ncand(ctx.size(), nullptr);
     bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * h.dim * esize()) == hipSuccess;
     if (fp8) ok = ok && hipMalloc(reinterpret_cast<void**>(&nscales), new_cap * 4) == hipSuccess;
-    if (rescore) ok = ok && alloc_rescore(new_cap * h.dim * 2, &nrr, &nrr_dev);
+    if (rescore) ok = ok && alloc_rescore(rescore_rows(new_cap) * h.dim * 2, &nrr, &nrr_dev);
     ok = ok && hipMalloc(reinterpret_cast<void**>(&nlive), new_cap / 8) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&ntags), new_cap * 4) == hipSuccess;
     for (size_t i = 0; ok && i < ctx.size(); ++i)
@@ -399,14 +422,20 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 5 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 7 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 5) return fail("index: unknown format version " + std::to_string(h.version));
-  const bool fp8 = h.version == 3 || h.version == 4, rescore = h.version == 4, ivf = h.version == 5;
+  if (h.version < 1 || h.version > 7) return fail("index: unknown format version " + std::to_string(h.version));
+  const bool ivf = h.version >= 5;
+  const bool fp8 = h.version == 3 || h.version == 4 || h.version >= 6, rescore = h.version == 4 || h.version == 7;
+  const std::string vname = "version-" + std::to_string(h.version);
+  if (fp8 != (js.rfind("\"dtype\": \"fp8_e4m3\"") != std::string::npos))
+    return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
+  if (!ivf && js.rfind("\"ivf\": {") != std::string::npos)
+    return fail("index: an ivf block in a " + vname + " file (it belongs to versions 5, 6 and 7)");
   if (fp8 && (h.dim < 16 || h.dim % 16 || h.dim > 2048))
     return fail("index: dim of an fp8 index must be a multiple of 16 in 16..2048");
   if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
@@ -419,7 +448,7 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     static const char* keys[6] = {"nlist", "nprobe", "centroids_off", "list_off_off", "list_tiles_off", "rowid_off"};
     uint64_t stored = 0;
     if (js.rfind("\"ivf\"") == std::string::npos || !json_u64(js, "capacity", &stored, true))
-      return fail("index: a version-5 file without an ivf block or capacity");
+      return fail("index: a " + vname + " file without an ivf block or capacity");
     for (int i = 0; i < 6; ++i)
       if (!json_u64(js, keys[i], &ivf_u[i], true)) return fail(std::string("index: the ivf block lacks ") + keys[i]);
     if (stored < n_ext || stored % kTile || stored >= (1ull << 31))
@@ -437,21 +466,22 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   uint64_t scales_off = 0, after_rows = h.data_off + bytes;
   bool blocks = h.version == 2 || ivf;  // tags and a bitmap in the file
   if (fp8) {
-    if (!json_u64(js, "scales_off", &scales_off, true)) return fail("index: a version-3 file without scales_off");
+    if (!json_u64(js, "scales_off", &scales_off, true)) return fail("index: a " + vname + " file without scales_off");
     if (scales_off % 4096 || scales_off < after_rows || scales_off > fsize || h.count * 4 > fsize - scales_off)
       return fail("index: scales block outside the file");
     after_rows = scales_off + h.count * 4;
     const bool t = json_u64(js, "tags_off", &tags_off, true), l = json_u64(js, "live_off", &live_off, true);
-    if (t != l) return fail("index: a version-3 file with only one of tags_off / live_off");
+    if (t != l) return fail("index: a " + vname + " file with only one of tags_off / live_off");
+    if (ivf && !t) return fail("index: a " + vname + " file without tags_off / live_off");
     blocks = t;
   }
   uint64_t rescore_off = 0;
-  const uint64_t rescore_len = h.count * h.dim * 2;
+  const uint64_t rescore_len = n_ext * h.dim * 2;  // [count][dim]: an IVF file holds them by external id
   if (fp8) {
     const bool off = json_u64(js, "rescore_off", &rescore_off, true);
     const bool key = js.rfind("\"rescore\": \"bf16\"") != std::string::npos;
-    if (rescore && !(off && key)) return fail("index: a version-4 file without rescore / rescore_off");
-    if (!rescore && (off || key)) return fail("index: a version-3 file with rescore keys (they belong to version 4)");
+    if (rescore && !(off && key)) return fail("index: a " + vname + " file without rescore / rescore_off");
+    if (!rescore && (off || key)) return fail("index: a " + vname + " file with rescore keys (they belong to versions 4 and 7)");
   }
   if (blocks) {
     if (!fp8 && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
@@ -461,8 +491,6 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
       return fail("index: tags or live block outside the file");
     after_rows = std::max(after_rows, std::max(tags_off + tag_bytes, live_off + live_bytes));
   }
-  if (rescore && (rescore_off % 4096 || rescore_off < after_rows || rescore_off > fsize || rescore_len > fsize - rescore_off))
-    return fail("index: rescore block unaligned, overlapping another block or outside the file");
   // the IVF tables: read, and checked before anything reaches the device -- the list scan trusts them
   const uint64_t ntile = h.count / kTile;
   std::vector<unsigned short> cent_host;
@@ -521,6 +549,9 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     }
     if (real != n_ext) return fail("index: ivf rowid is not a permutation of the ids over the stored rows");
   }
+  // the rescore block lies after every other block (the ivf tables included)
+  if (rescore && (rescore_off % 4096 || rescore_off < after_rows || rescore_off > fsize || rescore_len > fsize - rescore_off))
+    return fail("index: rescore block unaligned, overlapping another block or outside the file");
   if (hipSetDevice(device) != hipSuccess) return fail("index: hipSetDevice failed");
   auto idx = std::make_unique<Index>();
   idx->device = device;
@@ -656,7 +687,7 @@ int hz_index_describe3(void* h, uint64_t* out) {
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
   const uint64_t v[8] = {x->ivf ? 1u : 0u, (uint64_t)x->nlist, (uint64_t)x->nprobe_default, x->ivf ? x->count / kTile : 0,
-                         x->ivf ? x->n_ext : x->count, 0, 0, 0};
+                         x->ivf ? x->n_ext : x->count, x->h.version, 0, 0};
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
@@ -668,8 +699,12 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
   if (Q < 1 || Q > HZ_SEARCH_MAX_Q) return -4;
   if (k < 1 || k > HZ_SEARCH_MAX_K) return -5;
+  if (x->ivf && refine && !x->rescore) {
+    g_err = "index: an IVF index has no rescore rows unless it is a version-7 file";
+    return -34;
+  }
   if (refine && !x->rescore) {
-    g_err = std::string("index: refine needs rescore rows (a version-4 file), the index holds ") +
+    g_err = std::string("index: refine needs rescore rows (a version-4 or version-7 file), the index holds ") +
             (x->fp8 ? "fp8_e4m3" : "bf16") + " rows only";
     return -27;
   }
@@ -678,13 +713,12 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
     return -28;
   }
   if (nprobe && !x->ivf) {
-    g_err = "index: nprobe needs an IVF index (a version-5 file)";
+    g_err = "index: nprobe needs an IVF index (a version-5, 6 or 7 file)";
     return -34;
   }
-  if (x->ivf && (refine || nprobe < 0 || (nprobe > HZ_SEARCH_MAX_K && nprobe < x->nlist))) {
-    g_err = refine ? "index: an IVF index has no rescore rows"
-                   : "index: nprobe must be 0 (every list) or in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " +
-                         std::to_string(nprobe);
+  if (x->ivf && (nprobe < 0 || (nprobe > HZ_SEARCH_MAX_K && nprobe < x->nlist))) {
+    g_err = "index: nprobe must be 0 (every list) or in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " +
+            std::to_string(nprobe);
     return -34;
   }
   if (x->ivf && nprobe >= x->nlist) nprobe = 0;  // every list: no coarse stage
@@ -693,7 +727,7 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   const bool filtered = x->fp8 || x->mutated || filt != nullptr || x->ivf;
   bool fresh = false;
-  HzProgram g = x->ivf ? x->ivf_program(c, Q, k, nprobe, false, &fresh) : x->program(c, Q, k, filtered, refine, &fresh);
+  HzProgram g = x->ivf ? x->ivf_program(c, Q, k, nprobe, refine, false, &fresh) : x->program(c, Q, k, filtered, refine, &fresh);
   if (!g) return -11;
   std::memcpy(c.q_host, queries, (size_t)Q * x->h.dim * 4);
   if (filtered) {  // no filter: mask 0, value 0 passes every tag
@@ -725,14 +759,14 @@ int hz_index_probes(void* h, int ctx, const float* queries, int Q, int nprobe, i
   if (Q < 1 || Q > HZ_SEARCH_MAX_Q) return -4;
   if (!x->ivf || nprobe < 1 || nprobe > x->nlist || nprobe > HZ_SEARCH_MAX_K) {
     g_err = x->ivf ? "index: nprobe must be in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " + std::to_string(nprobe)
-                   : std::string("index: probes needs an IVF index (a version-5 file)");
+                   : std::string("index: probes needs an IVF index (a version-5, 6 or 7 file)");
     return -34;
   }
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   bool fresh = false;
-  HzProgram g = x->ivf_program(c, Q, 0, nprobe, true, &fresh);
+  HzProgram g = x->ivf_program(c, Q, 0, nprobe, 0, true, &fresh);
   if (!g) return -11;
   std::memcpy(c.q_host, queries, (size_t)Q * x->h.dim * 4);
   int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
@@ -807,6 +841,11 @@ int add_rows(Index* x, const void* data, const float* scales, const unsigned sho
   return 0;
 }
 
+int no_ivf_add() {
+  g_err = "index: IVF indexes do not take hz_index_add yet";
+  return -34;
+}
+
 int wrong_dtype(const Index* x, const char* call, const char* takes) {
   g_err = std::string("index: ") + call + " takes " + takes + " rows, the index holds " + (x->fp8 ? "fp8_e4m3" : "bf16");
   return -26;
@@ -819,10 +858,7 @@ extern "C" {
 int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const unsigned* tags, long long* first_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !rows_bf16 || n < 1) return -1;
-  if (x->ivf) {
-    g_err = "index: IVF indexes do not take hz_index_add yet";
-    return -34;
-  }
+  if (x->ivf) return no_ivf_add();
   if (x->fp8) return wrong_dtype(x, "hz_index_add", "bf16");
   return add_rows(x, rows_bf16, nullptr, nullptr, n, tags, first_id);
 }
@@ -831,6 +867,7 @@ int hz_index_add_q(void* h, const unsigned char* codes, const float* scales, lon
                    long long* first_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !codes || !scales || n < 1) return -1;
+  if (x->ivf) return no_ivf_add();
   if (!x->fp8) return wrong_dtype(x, "hz_index_add_q", "fp8_e4m3");
   if (x->rescore) {
     g_err = "index: hz_index_add_q adds fp8 rows only; an index with rescore rows takes hz_index_add_qr (codes, scales and bf16 rows)";
@@ -843,6 +880,7 @@ int hz_index_add_qr(void* h, const unsigned char* codes, const float* scales, co
                     const unsigned* tags, long long* first_id) {
   Index* x = static_cast<Index*>(h);
   if (!x || !codes || !scales || !rows_bf16 || n < 1) return -1;
+  if (x->ivf) return no_ivf_add();
   if (!x->fp8) return wrong_dtype(x, "hz_index_add_qr", "fp8_e4m3");
   if (!x->rescore) {
     g_err = "index: hz_index_add_qr needs an index with rescore rows (a version-4 file); use hz_index_add_q";
@@ -943,10 +981,10 @@ int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
   if (!x || !rows_out || n < 0) return -1;
   AllLocked all(*x);
   if (!x->rescore) {
-    g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-4 file)";
+    g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-4 or version-7 file)";
     return -29;
   }
-  if ((uint64_t)n > x->count) return -20;
+  if ((uint64_t)n > x->rescore_rows(x->count)) return -20;
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   const uint64_t bytes = (uint64_t)n * x->h.dim * 2;
   if (x->rescore_host) std::memcpy(rows_out, x->rrows, bytes);

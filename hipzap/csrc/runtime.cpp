@@ -451,6 +451,10 @@ extern "C" __attribute__((weak)) int hz_search_lscan_launch(const HzSearchListPa
 static int hz_search_lscan_op(const HzSearchListParams* p, hipStream_t st) {
   return hz_search_lscan_launch ? hz_search_lscan_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_qlscan_launch(const HzSearchQuantListParams* p, hipStream_t st);
+static int hz_search_qlscan_op(const HzSearchQuantListParams* p, hipStream_t st) {
+  return hz_search_qlscan_launch ? hz_search_qlscan_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -4,10 +4,11 @@
 //                    One template; its instantiations are the kinds SCAN (bf16 rows), FSCAN (bf16 rows that
 //                    pass a live bit and a per-query tag predicate) and QSCAN (FSCAN over OCP e4m3fn byte
 //                    rows with one fp32 scale per row)
-//   * search_lscan — the filtered bf16 scan over an IVF index's lists (kind LSCAN): workgroup (j, q) scores the
-//                    j-th tile of the lists query q probes against that query alone, with the template's pieces
+//   * search_lscan — the filtered scan over an IVF index's lists (kinds LSCAN: bf16 rows, QLSCAN: e4m3 rows with
+//                    row scales): workgroup (j, q) scores the j-th tile of the lists query q probes against that
+//                    query alone, with the template's pieces
 //   * search_merge — one workgroup per query: ntile x k candidates -> the final k, best first
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p for the reasoning.
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -317,10 +318,12 @@ __global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::temp
 }
 
 // -------------------------------------------------------------------------------------- list scan
-// search_lscan_kernel<NC> (HZ_K_SEARCH_LSCAN): the filtered bf16 scan over an indirect, per-query
-// set of tiles. Grid (P, Q); workgroup (j, q) finds the j-th tile of query q's probe set and scores it against
-// query q ALONE with the template's pieces at Q = 1 (stage_queries, stage_pass_bits, scan_rows with its group
-// skip, score_group), so a passing (q, r) has kind 31's bits and a dead or padding row is never loaded.
+// search_lscan_kernel<Fmt, NC> (HZ_K_SEARCH_LSCAN: Bf16Rows; HZ_K_SEARCH_QLSCAN: E4m3Rows, 4q): the
+// filtered scan over an indirect, per-query set of tiles. Grid (P, Q); workgroup (j, q) finds the j-th tile of
+// query q's probe set and scores it against query q ALONE with the template's pieces at Q = 1 (stage_queries,
+// stage_pass_bits, scan_rows with its group skip, score_group), so a passing (q, r) has the bits of the filtered
+// scan of its row format (kind 31's for bf16 rows, kind 34's for e4m3 rows) and a dead or padding row is never
+// loaded: neither its elements nor, for e4m3 rows, its scale.
 // Addressing: thread i < nprobe reads probes[q*nprobe + i] = l, and under (unsigned)l < nlist the pair
 // a = list_off[l], b = list_off[l + 1]; under 0 <= a <= b <= ntile its count b - a and start a go to LDS, else
 // the count -1. Every thread then walks the nprobe counts in probe order (LDS broadcasts): the running sum
@@ -328,21 +331,35 @@ __global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::temp
 // length is ntile. tile = list_tiles[x] is used under (unsigned)tile < ntile. A count of -1, a j at or past the
 // total and a tile out of range all end in k zero keys for this workgroup's slot and nothing else read.
 // probes == NULL: tile = j under j < ntile. rowid[row0 + t] is read once per tile (coalesced) under
-// row0 + t < N; N = ntile * T (the launcher refuses anything else), so every tile is whole.
-// Dynamic LDS: lds_bytes(1, D, true, false) = (D + 2 T + T / 32 + 2) * 4 <= 10,280 B; static: 2 x 128 ints.
-template <int NC>
-__global__ __launch_bounds__(T) void search_lscan_kernel(const HzSearchListParams a) {
+// row0 + t < N; N = ntile * T (the launcher refuses anything else), so every tile is whole. E4m3Rows:
+// scales[row0 + t] under the same bound, and only for a passing row (stage_pass_bits).
+// Dynamic LDS: lds_bytes(1, D, true, SCALED) = (D + 2 T + T / 32 + 2 (+ T)) * 4 <= 11,304 B; static: 2 x 128 ints.
+template <class Fmt>
+using ListArgs = std::conditional_t<Fmt::SCALED, HzSearchQuantListParams, HzSearchListParams>;
+__host__ __device__ inline const HzSearchListParams& list_part(const HzSearchListParams& a) { return a; }
+__host__ __device__ inline const HzSearchListParams& list_part(const HzSearchQuantListParams& a) { return a.l; }
+// the block the template's pieces read for one query: the filtered scan's, with the row scales where the format has them
+__device__ __forceinline__ HzSearchFilterParams one_query(const HzSearchFilterParams& f, const HzSearchListParams&) { return f; }
+__device__ __forceinline__ HzSearchQuantParams one_query(const HzSearchFilterParams& f, const HzSearchQuantListParams& a) {
+  return HzSearchQuantParams{f, a.scales};
+}
+
+template <class Fmt, int NC>
+__global__ __launch_bounds__(T) void search_lscan_kernel(const ListArgs<Fmt> args) {
+  const HzSearchListParams& a = list_part(args);
   const HzSearchParams& p = a.f.s;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int pcnt[HZ_SEARCH_MAX_K], poff[HZ_SEARCH_MAX_K];  // the probed lists' tile counts and starts
   float* qs = lds;                                        // [D]
   unsigned* sc = reinterpret_cast<unsigned*>(lds + p.D);  // [T]
   unsigned* pmask = sc + T;                               // [T] pass bits, the tile's live words, {mask, value}
+  float* scl = nullptr;                                   // scaled: [T] scales of the passing rows
+  if constexpr (Fmt::SCALED) scl = reinterpret_cast<float*>(pmask + T + T / 32 + 2);
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int j = blockIdx.x, q = blockIdx.y;
-  const int nch = p.D >> 3;
-  if (!HZ_DCHECK(j < a.P && q < p.Q && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K && p.D <= NC * 64 * 8 && p.ldc >= p.D &&
+  const int nch = p.D >> __builtin_ctz(Fmt::E);
+  if (!HZ_DCHECK(j < a.P && q < p.Q && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K && p.D <= NC * 64 * Fmt::E && p.ldc >= p.D &&
                  p.N == p.ntile * T && a.nlist >= 1))
     return;
   unsigned long long* out = p.cand + ((long)j * p.Q + q) * p.k;
@@ -379,14 +396,15 @@ __global__ __launch_bounds__(T) void search_lscan_kernel(const HzSearchListParam
   const long row0 = (long)tile * T;
   unsigned id = 0u;
   if (HZ_DCHECK(row0 + t < (long)p.N)) id = (unsigned)a.rowid[row0 + t];
-  HzSearchFilterParams one = a.f;  // what the template's pieces read: this query, and its {mask, value}
-  one.s.Q = 1;
-  one.s.queries = p.queries + (long)q * p.D;
-  if (one.filt) one.filt += 2 * q;
-  stage_queries(one.s, qs);
-  stage_pass_bits<Bf16Rows>(one, pmask, nullptr, row0, T);
+  HzSearchFilterParams f1 = a.f;  // what the template's pieces read: this query, and its {mask, value}
+  f1.s.Q = 1;
+  f1.s.queries = p.queries + (long)q * p.D;
+  if (f1.filt) f1.filt += 2 * q;
+  const auto one = one_query(f1, args);
+  stage_queries(f1.s, qs);
+  stage_pass_bits<Fmt>(one, pmask, scl, row0, T);
   __syncthreads();
-  scan_rows<Bf16Rows, NC, true>(one.s, qs, sc, pmask, nullptr, row0, T, lane, w, nch);
+  scan_rows<Fmt, NC, true>(f1.s, qs, sc, pmask, scl, row0, T, lane, w, nch);
   __syncthreads();
   rank_query<true>(sc, out, slot_ok, p.k, T, id);
 }
@@ -705,18 +723,20 @@ extern "C" int hz_search_qscan_launch(const HzSearchQuantParams* pp, hipStream_t
   return scan_launch<E4m3Rows, true>(qp, st);
 }
 
-template <int NC = 1>
-void lscan_dispatch(const HzSearchListParams& a, hipStream_t st) {
+namespace {
+
+template <class Fmt, int NC = 1>
+void lscan_dispatch(const ListArgs<Fmt>& args, hipStream_t st) {
+  const HzSearchListParams& a = list_part(args);
   const HzSearchParams& p = a.f.s;
-  if constexpr (NC < Bf16Rows::MAX_NC) {
-    if (p.D > NC * 64 * Bf16Rows::E) return lscan_dispatch<NC + 1>(a, st);
+  if constexpr (NC < Fmt::MAX_NC) {
+    if (p.D > NC * 64 * Fmt::E) return lscan_dispatch<Fmt, NC + 1>(args, st);
   }
-  hipLaunchKernelGGL(search_lscan_kernel<NC>, dim3(a.P, p.Q), dim3(T), lds_bytes(1, p.D, true, false), st, a);
+  hipLaunchKernelGGL((search_lscan_kernel<Fmt, NC>), dim3(a.P, p.Q), dim3(T), lds_bytes(1, p.D, true, Fmt::SCALED), st, args);
 }
 
-// The filtered launcher's refusals (-7: cand_bytes below P*Q*k*8), then the list tables' (hipzap.h).
-extern "C" int hz_search_lscan_launch(const HzSearchListParams* pp, hipStream_t st) {
-  HzSearchListParams a = *pp;
+// The filtered launcher's refusals (-7: cand_bytes below P*Q*k*8), then the list tables' (hipzap.h). Fills ntile.
+int list_check(HzSearchListParams& a) {
   HzSearchParams& p = a.f.s;
   if (a.P < 1 || (long long)a.P * T >= (1ll << 31)) return -42;
   const unsigned long long need =
@@ -731,7 +751,32 @@ extern "C" int hz_search_lscan_launch(const HzSearchListParams* pp, hipStream_t 
   if ((reinterpret_cast<uintptr_t>(a.probes) & 3) || (reinterpret_cast<uintptr_t>(a.list_off) & 3) ||
       (reinterpret_cast<uintptr_t>(a.list_tiles) & 3) || (reinterpret_cast<uintptr_t>(a.rowid) & 3))
     return -45;
-  lscan_dispatch(a, st);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int hz_search_lscan_launch(const HzSearchListParams* pp, hipStream_t st) {
+  HzSearchListParams a = *pp;
+  if (const int rc = list_check(a)) return rc;
+  lscan_dispatch<Bf16Rows>(a, st);
+  return (int)hipGetLastError();
+}
+
+// The byte rows' dimension rules of the quantised launcher (-16 .. -19, -23), the list launcher's refusals, then
+// -24 scales null, -25 scales not 4-byte aligned.
+extern "C" int hz_search_qlscan_launch(const HzSearchQuantListParams* pp, hipStream_t st) {
+  HzSearchQuantListParams qa = *pp;
+  const HzSearchParams& p = qa.l.f.s;
+  if (p.D < 16) return -17;
+  if (p.D % 16) return -16;
+  if (p.D > 2048) return -18;
+  if (p.ldc < p.D) return -19;
+  if (p.ldc % 16) return -23;
+  if (const int rc = list_check(qa.l)) return rc;
+  if (!qa.scales) return -24;
+  if (reinterpret_cast<uintptr_t>(qa.scales) & 3) return -25;
+  lscan_dispatch<E4m3Rows>(qa, st);
   return (int)hipGetLastError();
 }
 

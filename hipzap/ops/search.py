@@ -9,7 +9,8 @@ per-query ``{mask, value}`` filters) is the scan over the rows that pass. ``HZ_K
 ``HZ_K_SEARCH_RESCORE`` (``RescoreParams``) is the second stage of a two-stage search: one workgroup per query
 re-scores the ``R`` bf16 rows that a merge's ``out_id`` names and writes the best ``k`` of them.
 ``HZ_K_SEARCH_LSCAN`` (``ListScanParams``) is the filtered scan over an IVF index's lists: workgroup (j, q) scans
-the j-th tile of the lists that ``probes[q]`` names.
+the j-th tile of the lists that ``probes[q]`` names; ``HZ_K_SEARCH_QLSCAN`` (``QuantListScanParams``: that block plus
+one fp32 scale per stored row) is the list scan over rows of e4m3fn bytes.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -76,6 +77,18 @@ class ListScanParams(C.Structure):
         return sp
 
 
+@N.params_of("HZ_K_SEARCH_QLSCAN")
+class QuantListScanParams(C.Structure):
+    """HzSearchQuantListParams: the fields of ``ListScanParams`` (``corpus``: uint8 rows, ``ldc`` in bytes), then
+    ``scales`` (fp32 [N] in stored order)."""
+    _fields_ = ListScanParams._fields_ + [("scales", C.c_void_p)]
+
+    def merge_params(self) -> SearchParams:
+        sp = SearchParams.from_buffer_copy(self)
+        sp.N = self.P * 256
+        return sp
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -86,6 +99,7 @@ def _sigs(lib):
     N._sig(lib, "hz_search_qscan_launch", C.c_int, C.POINTER(QuantScanParams), P)
     N._sig(lib, "hz_search_rescore_launch", C.c_int, C.POINTER(RescoreParams), P)
     N._sig(lib, "hz_search_lscan_launch", C.c_int, C.POINTER(ListScanParams), P)
+    N._sig(lib, "hz_search_qlscan_launch", C.c_int, C.POINTER(QuantListScanParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
     N._sig(lib, "hz_index_last_error", C.c_char_p)
     N._sig(lib, "hz_index_open", P, C.c_char_p, C.c_int, C.c_int)
@@ -162,6 +176,17 @@ def launch_list(prm: ListScanParams, stream: int = 0) -> tuple:
     refused scan."""
     lib = N.lib()
     rc = lib.hz_search_lscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    sp = prm.merge_params()
+    return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def launch_quant_list(prm: QuantListScanParams, stream: int = 0) -> tuple:
+    """Quantised list scan then merge (over the P candidate lists) on ``stream``: (scan code, merge code); no merge
+    after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_qlscan_launch(C.byref(prm), stream)
     if rc:
         return rc, None
     sp = prm.merge_params()

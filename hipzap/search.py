@@ -25,7 +25,13 @@ boundary (``capacity`` = tiles * 256 stored rows; the padding rows are dead), pl
 (int32 ``[tiles]``, each list's tile ids) and ``rowid_off`` (int32 ``[capacity]``: the external id of each stored
 row, -1 on padding). ``count`` stays the number of vectors; ids, labels and every public call speak external ids
 (the row's position in the input of ``write_index``). A search scans the ``nprobe`` lists whose centroids are
-nearest to the query (``search(nprobe=...)``; ``"all"`` scans every list and is exact).
+nearest to the query (``search(nprobe=...)``; ``"all"`` scans every list and is exact). Version 6 is version 5's
+layout with version 3's rows (``dtype`` ``"fp8_e4m3"``): codes uint8 ``[capacity][dim]`` in stored order,
+``scales_off`` naming fp32 ``[capacity]`` in stored order (padding rows: code 0, scale 1, dead), the tags, bitmap and
+``ivf`` block as in version 5. Version 7 is version 6 plus ``"rescore": "bf16"`` and ``rescore_off``: bf16
+``[count][dim]`` in EXTERNAL-ID order (the rows a plain bf16 index of the same vectors holds), the last block of the
+file -- stage one's candidates carry external ids, so the second stage reads ``rows[id]``. Both come from
+:func:`convert_index`, which trains the lists on the bf16 rows and then quantises.
 
 A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
 positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
@@ -53,7 +59,11 @@ VERSION2 = 2  # version 1 plus the JSON keys capacity / tags_off / live_off and 
 VERSION3 = 3  # fp8 rows: uint8 codes, the JSON key scales_off and its block; tags / live as in version 2, or absent
 VERSION4 = 4  # version 3 plus the JSON keys rescore / rescore_off and the block of bf16 rows they name
 VERSION5 = 5  # version 2 stored list by list plus the JSON block ivf and the four blocks it names
-TILE = 256    # HZ_SEARCH_TILE (csrc/hipzap.h): an IVF list starts on a tile boundary
+VERSION6 = 6  # version 5's layout with version 3's rows: e4m3 codes and fp32 scales for `capacity` stored rows
+VERSION7 = 7  # version 6 plus rescore / rescore_off: bf16 rows [count][dim] in external-id order, the last block
+FP8_VERSIONS, IVF_VERSIONS, RESCORE_VERSIONS = (VERSION3, VERSION4, VERSION6, VERSION7), (VERSION5, VERSION6, VERSION7), \
+    (VERSION4, VERSION7)
+TILE = 256   # HZ_SEARCH_TILE (csrc/hipzap.h): an IVF list starts on a tile boundary
 IVF_MAX_LISTS = 65536
 IVF_SAMPLE = 256  # k-means trains on at most this many rows per centroid
 IVF_KEYS = ("centroids_off", "list_off_off", "list_tiles_off", "rowid_off")
@@ -184,23 +194,28 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
     live where one is missing); with ``scales`` (fp8 rows) version 3, whose tags and bitmap are present under
     the same rule; with ``rescore`` as well (bf16 bit patterns [N, D]) version 4, their block last. With ``ivf``
     (:func:`ivf_layout`'s tables; ``rows``, ``tags`` and ``live`` in stored order, ``hdr["count"]`` the number of
-    vectors) version 5, the four tables last.
+    vectors) version 5, the four tables last; with ``ivf`` and ``scales`` (codes and scales in stored order) version
+    6, and with ``rescore`` as well (``[hdr["count"], D]``, in id order) version 7, their block after the tables.
     Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
-    if rescore is not None and (scales is None or rescore.shape != rows.shape or rescore.dtype != np.uint16):
+    rshape = rows.shape if ivf is None else (hdr["count"], rows.shape[1])
+    if rescore is not None and (scales is None or rescore.shape != rshape or rescore.dtype != np.uint16):
         raise ValueError("rescore rows go with fp8 rows of the same shape")
 
     def align(x):
         return -(-x // ALIGN) * ALIGN
-    if ivf is not None and (scales is not None or tags is None or live is None or n % TILE):
-        raise ValueError("an IVF index holds bf16 rows, tags and a live bitmap for whole tiles")
+    if ivf is not None and (tags is None or live is None or n % TILE):
+        raise ValueError("an IVF index holds rows, tags and a live bitmap for whole tiles")
     blocks = tags is not None or live is not None
     tables = ()  # the four blocks of an IVF index
     if not blocks and scales is None:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
-        version = VERSION5 if ivf is not None else VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
+        if ivf is not None:
+            version = VERSION5 if scales is None else VERSION6 if rescore is None else VERSION7
+        else:
+            version = VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
         if scales is not None:
             hdr = dict(hdr, scales_off=0)
         if blocks:
@@ -226,12 +241,14 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
                 offs["tags_off"] = tags_off = align(end)
                 offs["live_off"] = live_off = align(tags_off + 4 * n)
                 end = live_off + words.nbytes
-            if rescore is not None:
+            if rescore is not None and ivf is None:
                 offs["rescore_off"] = align(end)
             ioffs = {}
             for key, block in zip(IVF_KEYS, tables):
                 ioffs[key] = align(end)
                 end = ioffs[key] + block.nbytes
+            if rescore is not None and ivf is not None:  # version 7: the rescore rows are the last block
+                offs["rescore_off"] = align(end)
             if all(hdr[k] == v for k, v in offs.items()) and all(hdr["ivf"][k] == v for k, v in ioffs.items()):
                 break
             hdr.update(offs)
@@ -255,13 +272,13 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             f.write(bytes(live_off - tags_off - 4 * n))
             f.write(words.astype("<u4").tobytes())
             at = live_off + words.nbytes
-        if rescore is not None:
-            f.write(bytes(hdr["rescore_off"] - at))
-            f.write(np.ascontiguousarray(rescore).astype("<u2").tobytes())
         for key, block in zip(IVF_KEYS, tables):
             f.write(bytes(hdr["ivf"][key] - at))
             f.write(block.tobytes())
             at = hdr["ivf"][key] + block.nbytes
+        if rescore is not None:
+            f.write(bytes(hdr["rescore_off"] - at))
+            f.write(np.ascontiguousarray(rescore).astype("<u2").tobytes())
     os.replace(tmp, path)
     return hdr
 
@@ -331,7 +348,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     if ivf is not None and (dtype != "bf16" or rescore):
         raise ValueError(f"ivf={ivf!r} goes with dtype='bf16' without rescore rows, got dtype={dtype!r}, rescore={rescore!r}: "
-                         f"fp8 and two-stage IVF indexes are not built")
+                         f"an fp8 or two-stage IVF index is convert_index(bf16 IVF file, dst, 'fp8', rescore=...)")
     if rescore and dtype != "fp8":
         raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
     rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
@@ -348,15 +365,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     if labels is not None:
         hdr["labels"] = labels
     if ivf is not None:
-        if not _is_int(ivf) or not 1 <= ivf <= min(n, IVF_MAX_LISTS):
-            raise ValueError(f"ivf must be an integer in 1..min(count, {IVF_MAX_LISTS}) = 1..{min(n, IVF_MAX_LISTS)}, got {ivf!r}")
-        nlist = int(ivf)
-        if nprobe is None:
-            nprobe = min(nlist, 16)
-        if not _is_int(nprobe) or not 1 <= nprobe <= min(nlist, MAX_K):
-            raise ValueError(f"nprobe must be an integer in 1..min(ivf, {MAX_K}) = 1..{min(nlist, MAX_K)}, got {nprobe!r}")
-        if not _is_int(ivf_seed) or ivf_seed < 0 or not _is_int(ivf_iters) or ivf_iters < 0:
-            raise ValueError(f"ivf_seed and ivf_iters must be integers >= 0, got {ivf_seed!r}, {ivf_iters!r}")
+        nlist, nprobe = _check_ivf_args(n, ivf, nprobe, ivf_seed, ivf_iters)
         cbits, assign = ivf_kmeans(bf16_to_f32(rows), nlist, metric, int(ivf_seed), int(ivf_iters))
         lay = ivf_layout(assign, nlist)
         real = lay["rowid"] >= 0
@@ -370,6 +379,20 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows)
 
 
+def _check_ivf_args(n: int, ivf, nprobe, ivf_seed, ivf_iters):
+    """The ranges of ``write_index(ivf=, nprobe=, ivf_seed=, ivf_iters=)`` over ``n`` rows -> (nlist, nprobe)."""
+    if not _is_int(ivf) or not 1 <= ivf <= min(n, IVF_MAX_LISTS):
+        raise ValueError(f"ivf must be an integer in 1..min(count, {IVF_MAX_LISTS}) = 1..{min(n, IVF_MAX_LISTS)}, got {ivf!r}")
+    nlist = int(ivf)
+    if nprobe is None:
+        nprobe = min(nlist, 16)
+    if not _is_int(nprobe) or not 1 <= nprobe <= min(nlist, MAX_K):
+        raise ValueError(f"nprobe must be an integer in 1..min(ivf, {MAX_K}) = 1..{min(nlist, MAX_K)}, got {nprobe!r}")
+    if not _is_int(ivf_seed) or ivf_seed < 0 or not _is_int(ivf_iters) or ivf_iters < 0:
+        raise ValueError(f"ivf_seed and ivf_iters must be integers >= 0, got {ivf_seed!r}, {ivf_iters!r}")
+    return nlist, int(nprobe)
+
+
 def _is_int(x) -> bool:
     return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
 
@@ -381,30 +404,31 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5):
+        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
     if metric >= len(METRICS) or (hdr.get("dim"), hdr.get("count"), hdr.get("metric")) != (dim, count, METRICS[metric]) \
             or hdr.get("dtype") not in DTYPES.values():
         raise ValueError(f"{path}: the JSON header disagrees with the file head")
-    fp8 = version in (VERSION3, VERSION4)
+    fp8 = version in FP8_VERSIONS
     if (hdr["dtype"] == FP8) != fp8:
-        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (version 3 means fp8_e4m3 rows, and so does "
-                         f"version 4)")
-    if version == VERSION4 and (hdr.get("rescore") != "bf16" or "rescore_off" not in hdr):
-        raise ValueError(f"{path}: a version-4 file without rescore / rescore_off")
-    if version != VERSION4 and ("rescore" in hdr or "rescore_off" in hdr):
-        raise ValueError(f"{path}: rescore keys in a version-{version} file (they belong to version 4)")
+        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (version 3 means fp8_e4m3 rows, and so do "
+                         f"versions 4, 6 and 7)")
+    if version in RESCORE_VERSIONS and (hdr.get("rescore") != "bf16" or "rescore_off" not in hdr):
+        raise ValueError(f"{path}: a version-{version} file without rescore / rescore_off")
+    if version not in RESCORE_VERSIONS and ("rescore" in hdr or "rescore_off" in hdr):
+        raise ValueError(f"{path}: rescore keys in a version-{version} file (they belong to versions 4 and 7)")
     if fp8 and (dim < 16 or dim % 16 or dim > 2048):
         raise ValueError(f"{path}: dim of an fp8 index must be a multiple of 16 in 16..2048, got {dim}")
     if hdr.get("labels") is not None and len(hdr["labels"]) != count:
         raise ValueError(f"{path}: {len(hdr['labels'])} labels for {count} rows")
     ivf = hdr.get("ivf")
-    if (version == VERSION5) != (ivf is not None):
-        raise ValueError(f"{path}: an ivf block belongs to a version-5 file and to no other (version {version})")
+    is_ivf = version in IVF_VERSIONS
+    if is_ivf != (ivf is not None):
+        raise ValueError(f"{path}: an ivf block belongs to the files of versions 5, 6 and 7 and to no other (version {version})")
     stored = count  # rows in the file's blocks
-    if version == VERSION5:
+    if is_ivf:
         stored = hdr.get("capacity")
         if not _is_int(stored) or stored < count or stored % TILE or stored >= 2 ** 31:
             raise ValueError(f"{path}: capacity {stored!r} of an IVF index is not a whole number of tiles holding {count} rows")
@@ -419,13 +443,13 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path}: scales_off {off!r} is not a multiple of {ALIGN}")
         if off < end:
             raise ValueError(f"{path}: the scales block at {off} overlaps the rows, which end at {end}")
-        if off + 4 * count > size:
+        if off + 4 * stored > size:
             raise ValueError(f"{path}: the scales block lies outside the file")
-        end = off + 4 * count
+        end = off + 4 * stored
         if ("tags_off" in hdr) != ("live_off" in hdr):
-            raise ValueError(f"{path}: a version-3 file with only one of tags_off / live_off")
+            raise ValueError(f"{path}: a version-{version} file with only one of tags_off / live_off")
     last = end  # the end of the last block before a rescore block
-    if version in (VERSION2, VERSION5) or (fp8 and "tags_off" in hdr):
+    if version == VERSION2 or is_ivf or (fp8 and "tags_off" in hdr):
         for key, nbytes in (("tags_off", 4 * stored), ("live_off", 4 * (-(-stored // 32)))):
             off = hdr.get(key)
             if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
@@ -433,15 +457,7 @@ def read_header(path: str) -> dict:
             last = max(last, off + nbytes)
         if not isinstance(hdr.get("capacity"), int) or hdr["capacity"] < count:
             raise ValueError(f"{path}: capacity below count")
-    if version == VERSION4:
-        off = hdr["rescore_off"]
-        if not isinstance(off, int) or isinstance(off, bool) or off % ALIGN:
-            raise ValueError(f"{path}: rescore_off {off!r} is not a multiple of {ALIGN}")
-        if off < last:
-            raise ValueError(f"{path}: the rescore block at {off} overlaps another block, which ends at {last}")
-        if off + 2 * count * dim > size:
-            raise ValueError(f"{path}: the rescore block lies outside the file")
-    if version == VERSION5:
+    if is_ivf:
         sizes = (2 * ivf["nlist"] * dim, 4 * (ivf["nlist"] + 1), 4 * (stored // TILE), 4 * stored)
         for key, nbytes in zip(IVF_KEYS, sizes):
             off = ivf[key]
@@ -449,6 +465,14 @@ def read_header(path: str) -> dict:
                 raise ValueError(f"{path}: the ivf block {key[:-4]} at {off} is unaligned, overlaps another block or lies "
                                  f"outside the file")
             last = off + nbytes
+    if version in RESCORE_VERSIONS:  # after every other block; [count][dim] whatever the stored order
+        off = hdr["rescore_off"]
+        if not isinstance(off, int) or isinstance(off, bool) or off % ALIGN:
+            raise ValueError(f"{path}: rescore_off {off!r} is not a multiple of {ALIGN}")
+        if off < last:
+            raise ValueError(f"{path}: the rescore block at {off} overlaps another block, which ends at {last}")
+        if off + 2 * count * dim > size:
+            raise ValueError(f"{path}: the rescore block lies outside the file")
     return dict(hdr, data_off=int(data_off))
 
 
@@ -487,6 +511,8 @@ def file_info(path: str) -> dict:
         info.update(version=VERSION3, dtype=FP8)
     if "rescore_off" in hdr:
         info.update(version=VERSION4, rescore=hdr["rescore"])
+    if "ivf" in hdr and hdr["dtype"] == FP8:
+        info.update(version=VERSION7 if "rescore_off" in hdr else VERSION6)
     return info
 
 
@@ -549,15 +575,16 @@ def ivf_facts(hdr: dict, t: dict) -> dict:
 
 
 def read_scales(path: str) -> np.ndarray:
-    """The row scales of an fp8 index, float32 [count]."""
+    """The row scales of an fp8 index, float32 [count] ([capacity], in stored order, for an IVF index)."""
     hdr = read_header(path)
     if hdr["dtype"] != FP8:
         raise ValueError(f"{path}: a {hdr['dtype']} index has no scales")
-    return np.fromfile(path, "<f4", hdr["count"], offset=hdr["scales_off"]).astype(np.float32)
+    return np.fromfile(path, "<f4", stored_rows(hdr), offset=hdr["scales_off"]).astype(np.float32)
 
 
 def read_rescore_rows(path: str) -> np.ndarray:
-    """The rescore block of a version-4 index: bf16 bit patterns, uint16 [count, dim]."""
+    """The rescore block of a version-4 or version-7 index: bf16 bit patterns, uint16 [count, dim], row ``i`` the
+    vector of id ``i`` (also in an IVF index, whose other blocks are in stored order)."""
     hdr = read_header(path)
     if "rescore_off" not in hdr:
         raise ValueError(f"{path}: a {hdr['dtype']} index without rescore rows (version 4 holds them)")
@@ -680,8 +707,11 @@ class _Base:
         self.dtype = self.header["dtype"]
         self.rescore = "rescore_off" in self.header  # a version-4 file: bf16 rows for a second stage
         self.ivf = read_ivf(path) if "ivf" in self.header else None  # the validated tables of a version-5 file
-        self.version = (VERSION5 if self.ivf else VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
-                        else VERSION2 if "tags_off" in self.header else VERSION)
+        if self.ivf:
+            self.version = VERSION5 if self.dtype != FP8 else VERSION7 if self.rescore else VERSION6
+        else:
+            self.version = (VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
+                            else VERSION2 if "tags_off" in self.header else VERSION)
         self.nprobe = self.ivf["nprobe"] if self.ivf else None  # what search(nprobe=None) scans; settable
         self._mut = threading.Lock()  # one mutator at a time
 
@@ -722,8 +752,9 @@ class _Base:
             if nprobe is not None:
                 raise ValueError(f"nprobe={nprobe!r} needs an IVF index (write_index(ivf=...)), this one is version {self.version}")
             return 0
-        if refine not in (None, 0):
-            raise ValueError(f"refine={refine!r}: an IVF index has no rescore rows (two-stage IVF is not built)")
+        if refine not in (None, 0) and not self.rescore:
+            raise ValueError(f"refine={refine!r}: an IVF index has no rescore rows unless it is a version-7 file "
+                             f"(convert_index(..., 'fp8', rescore=True)), this one is version {self.version}")
         nlist = self.ivf["nlist"]
         if nprobe is None:
             nprobe = self.nprobe
@@ -794,14 +825,15 @@ class _Base:
             raise ValueError("IVF indexes do not take save(compact=True) yet: ids would change with the lists' layout")
         with self._mut:
             bits, tags, live, *rest = self._state()
-            if self.ivf is not None:  # stored order, as it was read: version 5 again
+            scales = rest[0] if rest else None
+            rrows = rest[1] if len(rest) > 1 else None
+            if self.ivf is not None:  # stored order, as it was read: the same version again, the same tables
                 hdr = {"dim": self.dim, "count": self.count, "dtype": self.dtype, "metric": self.metric,
                        "model": self.header.get("model", ""), "embed": self.header.get("embed")}
                 if self.labels is not None:
                     hdr["labels"] = list(self.labels)
-                return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), tags, live, ivf=self.ivf)
-            scales = rest[0] if rest else None
-            rrows = rest[1] if len(rest) > 1 else None
+                return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), tags, live, scales=scales,
+                                   rescore=rrows, ivf=self.ivf)
             labels = self.labels
             if compact:
                 if not live.any():
@@ -838,6 +870,7 @@ class RefIndex(_Base):
         if self.ivf is not None:  # held by id, like every other index; _state() puts the stored order back
             pos = self.ivf["pos"]
             self._bits, self._rows, self._tags, self._live = self._bits[pos], self._rows[pos], self._tags[pos], self._live[pos]
+            self.scales = self.scales[pos] if fp8 else None  # the rescore rows are in id order already
             self._cent = bf16_to_f32(self.ivf["centroids"])
             self._cap = int(self.header["capacity"])
 
@@ -860,7 +893,7 @@ class RefIndex(_Base):
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
         lists = self._nprobe(nprobe, refine)
-        R = 0 if self.ivf is not None else self._refine(refine, k)
+        R = self._refine(refine, k)
         with self._mut:  # the mutators replace the arrays one by one
             allow = None if filt is None and self._live.all() else self.allow(filt)
             if lists:
@@ -902,9 +935,13 @@ class RefIndex(_Base):
     def _state(self):
         if self.ivf is not None:
             pos, cap = self.ivf["pos"], int(self.header["capacity"])
-            bits, tags, live = np.zeros((cap, self.dim), np.uint16), np.zeros(cap, np.uint32), np.zeros(cap, bool)
+            bits, tags, live = np.zeros((cap, self.dim), self._bits.dtype), np.zeros(cap, np.uint32), np.zeros(cap, bool)
             bits[pos], tags[pos], live[pos] = self._bits, self._tags, self._live
-            return bits, tags, live
+            if self.scales is None:
+                return bits, tags, live
+            scales = np.ones(cap, np.float32)  # padding rows: code 0, scale 1, dead
+            scales[pos] = self.scales
+            return (bits, tags, live, scales, self._rbits) if self.rescore else (bits, tags, live, scales)
         if self.rescore:
             return self._bits, self._tags, self._live, self.scales, self._rbits
         if self.scales is not None:
@@ -980,7 +1017,7 @@ class Index(_Base):
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
         lists = self._nprobe(nprobe, refine)
-        R = 0 if self.ivf is not None else self._refine(refine, k)
+        R = self._refine(refine, k)
         if self._h is None:
             raise RuntimeError("the index is closed")
         scores = np.empty((q.shape[0], k), np.float32)
@@ -1054,8 +1091,9 @@ class Index(_Base):
                                                                     tags.ctypes.data, words.ctypes.data, n),
                             "hz_index_read_state_q")
             if self.rescore:
-                rrows = np.empty((n, self.dim), np.uint16)
-                self._exclusive(lambda: self._lib.hz_index_read_rescore(self._h, rrows.ctypes.data, n),
+                nr = self.count  # an IVF index: its rescore rows are held by id, not in stored order
+                rrows = np.empty((nr, self.dim), np.uint16)
+                self._exclusive(lambda: self._lib.hz_index_read_rescore(self._h, rrows.ctypes.data, nr),
                                 "hz_index_read_rescore")
                 return codes, tags, unpack_live(words, n), scales, rrows
             return codes, tags, unpack_live(words, n), scales
@@ -1098,11 +1136,18 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
     return RefIndex(path, reserve)
 
 
-def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False) -> dict:
+def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
+                  ivf_seed: int = 0, ivf_iters: int = 10) -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
-    ``rescore=True`` (fp8 only) keeps the stored bf16 rows as the rescore block: a version-4 file."""
+    ``rescore=True`` (fp8 only) keeps the stored bf16 rows as the rescore block: a version-4 file.
+    An IVF ``src`` (version 5) keeps its lists, tables, centroids (bf16), ``nprobe``, ``seed`` and ``iters``:
+    ``dtype="fp8"`` writes version 6, with ``rescore=True`` version 7, whose rescore block is the stored bf16 rows
+    gathered into id order. ``ivf=nlist`` (a plain ``src``, version 1 or 2) builds the lists over the stored rows
+    with :func:`ivf_kmeans` / :func:`ivf_layout` (``nprobe``, ``ivf_seed``, ``ivf_iters`` as in
+    :func:`write_index`): version 5 for ``dtype="bf16"``, 6 or 7 for fp8. A deleted row keeps its id, is assigned to
+    a list and stays dead."""
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     if rescore and dtype != "fp8":
@@ -1110,16 +1155,47 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False)
     hdr = read_header(src)
     if hdr["dtype"] != "bf16":
         raise ValueError(f"{src}: only a bf16 index can be converted, this one holds {hdr['dtype']}")
+    if ivf is None and (nprobe is not None or ivf_seed != 0 or ivf_iters != 10):
+        raise ValueError(f"nprobe={nprobe!r}, ivf_seed={ivf_seed!r} and ivf_iters={ivf_iters!r} go with ivf=nlist")
+    if ivf is not None and "ivf" in hdr:
+        raise ValueError(f"ivf={ivf!r}: {src} is an IVF index already (nlist {hdr['ivf']['nlist']}); its lists are kept")
+    if dtype == "fp8" and hdr["dim"] % 16:
+        raise ValueError(f"dim of an fp8 index must be a multiple of 16 in 16..2048, got {hdr['dim']}")
     bits, scales = read_rows(src), None
-    rrows = bits if rescore else None
-    if dtype == "fp8":
-        if hdr["dim"] % 16:
-            raise ValueError(f"dim of an fp8 index must be a multiple of 16 in 16..2048, got {hdr['dim']}")
-        bits, scales = quantize_rows(bf16_to_f32(bits))
     out = {k: hdr[k] for k in ("dim", "count") if k in hdr}
     out.update(dtype=DTYPES[dtype], metric=hdr["metric"], model=hdr.get("model", ""), embed=hdr.get("embed"))
     if hdr.get("labels") is not None:
         out["labels"] = hdr["labels"]
     v2 = "tags_off" in hdr
+    if ivf is not None or "ivf" in hdr:
+        if "ivf" in hdr:  # the stored order, the tables and the centroids as they are
+            lay = {k: v for k, v in read_ivf(src).items() if k not in ("pos", "list_of")}
+            tags, live = read_tags(src), read_live(src)
+            real = lay["rowid"] >= 0
+        else:
+            n = hdr["count"]
+            nlist, nprobe = _check_ivf_args(n, ivf, nprobe, ivf_seed, ivf_iters)
+            cbits, assign = ivf_kmeans(bf16_to_f32(bits), nlist, hdr["metric"], int(ivf_seed), int(ivf_iters))
+            lay = ivf_layout(assign, nlist)
+            real = lay["rowid"] >= 0
+            ids = lay["rowid"][real]
+            rows, bits = bits, np.zeros((real.size, hdr["dim"]), np.uint16)
+            bits[real] = rows[ids]
+            tags, live = np.zeros(real.size, np.uint32), np.zeros(real.size, bool)
+            tags[real] = read_tags(src)[ids] if v2 else 0
+            live[real] = read_live(src)[ids] if v2 else True
+            lay.update(centroids=cbits, nlist=nlist, nprobe=nprobe, seed=int(ivf_seed), iters=int(ivf_iters))
+        rrows = None
+        if rescore:  # the stored rows gathered into id order: what a plain bf16 index of the vectors holds
+            rrows = np.empty((hdr["count"], hdr["dim"]), np.uint16)
+            rrows[lay["rowid"][real]] = bits[real]
+        if dtype == "fp8":  # padding rows: code 0, scale 1 (and dead)
+            codes, scales = np.zeros(bits.shape, np.uint8), np.ones(bits.shape[0], np.float32)
+            codes[real], scales[real] = quantize_rows(bf16_to_f32(bits[real]))
+            bits = codes
+        return _write_file(dst, out, bits, tags, live, scales=scales, rescore=rrows, ivf=lay)
+    rrows = bits if rescore else None
+    if dtype == "fp8":
+        bits, scales = quantize_rows(bf16_to_f32(bits))
     return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
                        hdr.get("capacity"), scales=scales, rescore=rrows)

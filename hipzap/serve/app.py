@@ -518,7 +518,8 @@ def search():
     an integer in k..128, ``0`` for none; absent or null: 128 on such an index. The answer's ``"refine"`` is the
     R used, 0 if none. ``"nprobe"`` (an IVF index): the lists each query scans, an integer in 1..min(nlist, 128)
     or ``"all"``; absent: ``extra.index_nprobe``, else the file's default. The answer of an IVF index carries
-    ``"ivf": true`` and the ``"nprobe"`` used (``"all"`` when every list was scanned)."""
+    ``"ivf": true`` and the ``"nprobe"`` used (``"all"`` when every list was scanned). ``"nprobe"`` and ``"refine"``
+    go together on an fp8 IVF index with rescore rows (a version-7 file): the probed lists give the R candidates."""
     from ..search import MAX_K, check_k, check_queries, normalize_rows
     s = get_server()
     body = {}
@@ -551,9 +552,9 @@ def search():
             isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= min(index.ivf["nlist"], MAX_K)):
         raise ValueError(f"nprobe must be an integer in 1..{min(index.ivf['nlist'], MAX_K)} or \"all\", got {nprobe!r}")
     lists = index._nprobe(nprobe, body.get("refine"))  # ValueError -> 400 (nprobe without lists, refine with them)
-    refine = 0 if index.ivf is not None else index._refine(body.get("refine"), k)  # ValueError -> 400
+    refine = index._refine(body.get("refine"), k)  # ValueError -> 400
     with phase("search"):
-        scores, ids = index.search(q, k, filter=filt, refine=None if index.ivf is not None else refine, nprobe=nprobe)
+        scores, ids = index.search(q, k, filter=filt, refine=refine, nprobe=nprobe)
     dt = (time.perf_counter() - t0) * 1e3
     if "application/octet-stream" in request.headers.get("Accept", ""):
         out = np.empty(ids.shape, dtype=[("id", "<i4"), ("score", "<f4")])
