@@ -207,7 +207,10 @@ __device__ __forceinline__ u32x4 philox4(unsigned c0, unsigned c1, unsigned c2, 
 }
 
 __device__ __forceinline__ float gumbel_of(unsigned r) {
-  const float u = ((r >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
+  // 23 random bits: k + 0.5 then has 24 significant bits, so u is exact in fp32 and lies in
+  // [2^-24, 1 - 2^-24]. (24 bits rounded k + 0.5f to an integer for k >= 2^23: u == 1.0f at
+  // k = 2^24 - 1, a key of +inf that won the sampler whatever its logit.)
+  const float u = ((r >> 9) + 0.5f) * (1.0f / 8388608.0f);
   return -__logf(-__logf(u));
 }
 

@@ -11,6 +11,7 @@ import torch
 from hipzap.engine.lm import LMEngine, pack_awd_lstm
 from hipzap.engine.lmbatch import LMBatchEngine, pack_lmb
 from hipzap.models.awd_lstm import get_language_model, reference_lm
+from lm_oracle import gumbel_np
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -36,28 +37,6 @@ def _eager_logits(m, ids):
         for t in ids:
             res, *_ = m(torch.tensor([[t]]))
     return res[-1]
-
-
-def gumbel_np(seed: int, t: int, V: int) -> np.ndarray:
-    """Host copy of common.h gumbel(seed, t, j) for j = 0..V-1 (Philox4x32-10, one block per 4 ids)."""
-    M = np.uint64(0xFFFFFFFF)
-    j = np.arange(V, dtype=np.uint64)
-    c0 = j >> np.uint64(2)
-    c1 = np.full(V, t & 0xFFFFFFFF, np.uint64)
-    c2 = np.full(V, 0x5EED, np.uint64)
-    c3 = np.zeros(V, np.uint64)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        h0, l0 = p0 >> np.uint64(32), p0 & M
-        h1, l1 = p1 >> np.uint64(32), p1 & M
-        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M
-    r = np.choose((j & np.uint64(3)).astype(np.int64), [c0, c1, c2, c3])
-    u = ((r >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0
-    return -np.log(-np.log(u))
 
 
 @pytest.mark.parametrize("unroll", [1, 8])
