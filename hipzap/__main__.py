@@ -9,6 +9,8 @@
     python -m hipzap upload --models-dir ./models  # scripts/upload_models.py parity
     python -m hipzap index --vectors v.npy [--labels labels.json] [--metric cosine|ip] --out x.hzidx  # vector index
     python -m hipzap index --embed-plan bert.pth.emb.hzplan --ids ids.npy [--mask mask.npy] --out x.hzidx
+    python -m hipzap plan --model resnet50 --ckpt m.pth --embed [--resize 256] [--no-normalize]  # image vectors
+    python -m hipzap index --embed-plan m.pth.emb.hzplan --images imgs.npy --out x.hzidx  # uint8 [N, H, W, 3]
     python -m hipzap index --from-index a.hzidx --dtype fp8 --out b.hzidx  # requantise a bf16 index (ids kept)
     python -m hipzap index --vectors v.npy --dtype fp8 --rescore --out c.hzidx  # fp8 scan + bf16 rescoring (version 4)
     python -m hipzap info [x.hzidx]
@@ -78,6 +80,9 @@ def cmd_plan(a):
              "normalize": not a.no_normalize} if a.embed else None
     if embed is None and (a.pooling or a.no_normalize):
         raise SystemExit("--pooling / --no-normalize go with --embed")
+    if embed is not None and a.model.startswith("resnet") and embed["pooling"] != "mean":
+        raise SystemExit(f"plan: --pooling {embed['pooling']} does not apply to {a.model}: a ResNet embedding is its "
+                         f"global average pool (--pooling mean, the default)")
     out = export_from_checkpoint(a.model, a.ckpt, a.out, batch=a.batch, contexts=a.contexts, probs=a.probs,
                                  dp_shard=a.dp_shard, seq_len=a.seq_len,
                                  resize=resize_spec(a.resize, crop, a.max_image), embed=embed)
@@ -114,7 +119,7 @@ def cmd_index(a):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
     if a.from_index is not None:
-        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask:
+        if a.vectors is not None or a.embed_plan is not None or a.labels or a.tags or a.ids or a.mask or a.images:
             raise SystemExit("index: --from-index takes only --dtype, --rescore, --ivf with --nprobe / --ivf-seed, and --out")
         if a.ivf is None and (a.nprobe is not None or a.ivf_seed is not None):
             raise SystemExit("index: --nprobe and --ivf-seed go with --ivf NLIST")
@@ -128,10 +133,15 @@ def cmd_index(a):
     if (a.vectors is None) == (a.embed_plan is None):
         raise SystemExit("index: give one of --vectors, --embed-plan and --from-index")
     embed, model = None, a.model
+    if a.images and (a.ids or a.mask):
+        raise SystemExit("index: --images (a vision embedding plan) does not combine with --ids / --mask (a text one)")
     if a.vectors is not None:
-        if a.ids or a.mask:
-            raise SystemExit("index: --ids / --mask go with --embed-plan")
+        if a.ids or a.mask or a.images:
+            raise SystemExit("index: --ids / --mask / --images go with --embed-plan")
         vec = np.load(a.vectors, allow_pickle=False)
+    elif a.images:
+        vec, embed, pm = _embed_images(a)
+        model = model or pm
     else:
         if not a.ids:
             raise SystemExit("index: --embed-plan needs --ids (an .npy of token-id rows)")
@@ -161,6 +171,29 @@ def cmd_index(a):
         hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
                           rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
+
+
+def _embed_images(a):
+    """``hipzap index --embed-plan P --images imgs.npy``: the vectors a vision embedding plan (ResNet or ViT)
+    gives for uint8 [N, H, W, 3] images, on the GPU, torch-free -> (vectors, embed spec, the plan's model)."""
+    import numpy as np
+
+    from .lite import read_meta
+    from .serve.server import PlanVisionBackend
+    from .serve.settings import ModelSpec
+    meta = read_meta(a.embed_plan)
+    if meta.get("kind") == "text":
+        raise SystemExit(f"index: {a.embed_plan} is a text plan: its rows come from --ids, not --images")
+    if not meta.get("embed"):
+        raise SystemExit(f"index: {a.embed_plan} is not an embedding plan (hipzap plan --embed)")
+    imgs = np.load(a.images, allow_pickle=False)
+    name = a.model or meta.get("model") or "resnet50"
+    be = PlanVisionBackend(name, a.embed_plan, a.device, ModelSpec(name=name))
+    if imgs.dtype != np.uint8 or not be.accepts_u8(imgs.shape):
+        want = f"at most {be.resize['max_h']} x {be.resize['max_w']}" if be.resize else f"{list(be.in_shape[1:])}"
+        raise SystemExit(f"index: --images is a uint8 array [N, H, W, 3] with images {want} for this plan, got "
+                         f"{imgs.dtype} {list(imgs.shape)}")
+    return be.embed_u8(imgs), dict(be.embed), meta.get("model")
 
 
 def cmd_info(a):
@@ -212,10 +245,11 @@ def main(argv=None):
                     help="ResNet / ViT: write a RESIZE plan (with --embed: <ckpt>.emb.rz.hzplan) -- requests are uint8 images of any size, the shorter "
                          "side resized to this (antialiased bilinear), centre-cropped and normalised on the GPU")
     pl.add_argument("--embed", action="store_true",
-                    help="BERT / ViT: write an EMBEDDING plan (<ckpt>.emb.hzplan) -- the output is one pooled vector "
+                    help="BERT / ViT / ResNet: write an EMBEDDING plan (<ckpt>.emb.hzplan) -- the output is one pooled vector "
                          "per sequence / image (POST /embed) instead of class logits")
     pl.add_argument("--pooling", choices=["mean", "cls"], default=None,
-                    help="with --embed: masked token mean or the CLS token (default: mean for BERT, cls for ViT)")
+                    help="with --embed: masked token mean or the CLS token (default: mean for BERT, cls for ViT; "
+                         "a ResNet pools by the mean only)")
     pl.add_argument("--no-normalize", action="store_true", help="with --embed: do not L2-normalise the vectors")
     pl.add_argument("--crop", type=int, default=None, help="with --resize: crop size (default: the model's image size)")
     pl.add_argument("--max-image", default=None,
@@ -231,9 +265,13 @@ def main(argv=None):
     u.add_argument("--settings", default=None)
     ix = sub.add_parser("index")
     ix.add_argument("--vectors", default=None, help="an .npy float array [N, D]")
-    ix.add_argument("--embed-plan", default=None, help="a text embedding plan: the vectors of the --ids rows, on the GPU")
+    ix.add_argument("--embed-plan", default=None,
+                    help="an embedding plan: the vectors of the --ids rows (text) or of the --images (vision), on the GPU")
     ix.add_argument("--ids", default=None, help="with --embed-plan: an .npy of token-id rows [N, L]")
     ix.add_argument("--mask", default=None, help="with --embed-plan: an .npy attention mask [N, L]")
+    ix.add_argument("--images", default=None,
+                    help="with a vision --embed-plan (ResNet / ViT): an .npy of uint8 images [N, H, W, 3] at the plan's "
+                         "input size, or within its maximum for a resize plan")
     ix.add_argument("--labels", default=None, help="a JSON list of N strings")
     ix.add_argument("--tags", default=None, help="an .npy of N uint32 tag words (search filters test them): a version-2 file")
     ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")

@@ -81,6 +81,20 @@ typedef struct HzPoolFcParams {
 } HzPoolFcParams;
 int hz_pool_fc_launch(const HzPoolFcParams* p, hipStream_t st);
 
+// global average pool [+ L2 normalisation] without the classifier (ResNet embedding head, DESIGN.md 4r;
+// vision.hip pool_norm_kernel): out[b][c] = mean_hw x[b][c][hw] in fp32, the sum in ascending pixel order
+// times 1.f / HW (pool_fc_kernel's channel mean, bit for bit); normalize: divided by max(||row||_2, 1e-12).
+// One workgroup per image, no atomics: a row's bits depend on that image alone. Columns C..ldo-1 of out
+// are left as they were. Refused (-1, nothing launched): x or out null or not 16-B aligned, B < 1, HW < 1,
+// C < 32, C % 32, C > 2048, ldo < C.
+typedef struct HzPoolNormParams {
+  const unsigned short* x;  // channel-blocked bf16 [B][C/32][HW][32]; pooled: fp32 [B][C] channel means
+  float* out;               // fp32 [B][ldo]
+  int B, C, HW, ldo;
+  int pooled, normalize;    // pooled: as HzPoolFcParams.pooled (then, without normalize, a bitwise copy)
+} HzPoolNormParams;
+int hz_pool_norm_launch(const HzPoolNormParams* p, hipStream_t st);
+
 // image pre-processing: src NCHW fp32 (mode 0) or NHWC uint8 (mode 1) -> NHWC bf16 with Cpad channels;
 // mode 2: src NCHW fp32 -> bf16 patch rows [N * H/P * W/P][Cin * P * P] in (c, ky, kx) order, with
 // P = Cpad (16; the ViT patch embedding as a row-major GEMM)
@@ -799,7 +813,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_QSCAN, 34, HzSearchQuantParams, hz_search_qscan_op, SEARCH)   \
   X(SEARCH_RESCORE, 35, HzSearchRescoreParams, hz_search_rescore_op, SEARCH) \
   X(SEARCH_LSCAN, 36, HzSearchListParams, hz_search_lscan_op, SEARCH)     \
-  X(SEARCH_QLSCAN, 37, HzSearchQuantListParams, hz_search_qlscan_op, SEARCH)
+  X(SEARCH_QLSCAN, 37, HzSearchQuantListParams, hz_search_qlscan_op, SEARCH) \
+  X(POOL_NORM, 38, HzPoolNormParams, hz_pool_norm_op, VISION)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

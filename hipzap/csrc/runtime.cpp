@@ -426,6 +426,11 @@ extern "C" __attribute__((weak)) int hz_pool_embed_launch(const HzPoolEmbedParam
 static int hz_pool_embed_op(const HzPoolEmbedParams* p, hipStream_t st) {
   return hz_pool_embed_launch ? hz_pool_embed_launch(p, st) : -102;
 }
+// (the pooled-feature launcher: vision.hip in the library)
+extern "C" __attribute__((weak)) int hz_pool_norm_launch(const HzPoolNormParams* p, hipStream_t st);
+static int hz_pool_norm_op(const HzPoolNormParams* p, hipStream_t st) {
+  return hz_pool_norm_launch ? hz_pool_norm_launch(p, st) : -102;
+}
 // (the search launchers: search.hip in the library)
 extern "C" __attribute__((weak)) int hz_search_scan_launch(const HzSearchParams* p, hipStream_t st);
 static int hz_search_scan_op(const HzSearchParams* p, hipStream_t st) {

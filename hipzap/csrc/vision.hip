@@ -204,6 +204,78 @@ __global__ __launch_bounds__(256) void pool_fc_kernel(const HzPoolFcParams p) {
     p.out[(long)b * p.ldo + n] = part[t] + part[16 + t] + part[32 + t] + part[48 + t] + (p.bias ? p.bias[n] : 0.f);
 }
 
+// Global average pool [+ L2 normalisation] without the classifier: the ResNet embedding head
+// (HzPoolNormParams). One workgroup per image; thread t owns channels 8t .. 8t + 7 (256 threads cover
+// C = 2048), a thread whose channels lie past C loads and stores nothing and joins the norm's reductions
+// with zeros. pooled == 0: per pixel one 16-B load of the channel-blocked input, HZ_POOLNORM_PB pixel
+// loads in flight per lane; the pixels of a channel are summed in ascending order in fp32 and multiplied
+// by 1.f / HW -- pool_fc_kernel's statements, so a channel mean has that kernel's bits. pooled == 1: x is
+// the fp32 [B][C] channel means a tail seam wrote (block.hip): two 16-B loads, no arithmetic before the
+// norm. normalize: squares summed per thread in channel order, a butterfly over the wave, the four wave
+// values through LDS in wave order, then a true division by max(sqrt(sum), 1e-12): pool_embed_kernel's
+// rule. Nothing crosses a workgroup and there is no atomic: an image's bits depend on that image alone.
+// No address depends on data; columns C .. ldo - 1 of `out` are never written.
+// Depth: the grid is B workgroups of one wave per SIMD, so occupancy hides nothing and VGPRs are free;
+// the wall time is (round trips) x (L2-hit 180-225 cycles, HBM-miss ~900). 32 loads (128 VGPRs) make
+// HW = 49 and 64 two round trips (16: four); 64 would be one, at 256 load VGPRs next to the rest.
+#ifndef HZ_POOLNORM_PB
+#define HZ_POOLNORM_PB 32
+#endif
+__global__ __launch_bounds__(256) void pool_norm_kernel(const HzPoolNormParams p) {
+  __shared__ float sq[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int b = blockIdx.x;
+  if (!HZ_DCHECK(p.C >= 32 && p.C % 32 == 0 && p.C <= 2048 && p.HW >= 1 && p.ldo >= p.C)) return;
+  const bool own = t * 8 < p.C;
+  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (own && p.pooled) {
+    const float* xp = reinterpret_cast<const float*>(p.x) + (long)b * p.C + t * 8;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(xp), c = *reinterpret_cast<const f32x4*>(xp + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[e] = a[e], s[4 + e] = c[e];
+  } else if (own) {
+    const float inv = 1.f / p.HW;
+    const int cb = t >> 2, sub = t & 3;
+    const bf16_t* src = p.x + (((long)b * (p.C >> 5) + cb) * p.HW) * 32 + sub * 8;
+    for (int hw0 = 0; hw0 < p.HW; hw0 += HZ_POOLNORM_PB) {  // PB independent loads in flight per lane
+      u32x4 v[HZ_POOLNORM_PB];
+#pragma unroll
+      for (int j = 0; j < HZ_POOLNORM_PB; ++j)
+        v[j] = *reinterpret_cast<const u32x4*>(src + min(hw0 + j, p.HW - 1) * 32);
+#pragma unroll
+      for (int j = 0; j < HZ_POOLNORM_PB; ++j) {
+        float f[8];
+        unpack8(v[j], f);
+        const float wj = hw0 + j < p.HW ? 1.f : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] += wj * f[e];
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = s[e] * inv;
+  }
+  if (p.normalize) {  // (workgroup-uniform: every thread reaches the barrier)
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss += s[e] * s[e];
+    ss = warp_sum(ss);
+    if (lane == 0) sq[wave] = ss;
+    __syncthreads();
+    const float nrm = fmaxf(sqrtf(sq[0] + sq[1] + sq[2] + sq[3]), 1e-12f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = s[e] / nrm;
+  }
+  if (!own) return;
+  float* o = p.out + (long)b * p.ldo + t * 8;
+  if ((p.ldo & 3) == 0) {  // rows of `out` stay 16-B aligned
+    *reinterpret_cast<f32x4*>(o) = f32x4{s[0], s[1], s[2], s[3]};
+    *reinterpret_cast<f32x4*>(o + 4) = f32x4{s[4], s[5], s[6], s[7]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = s[e];
+  }
+}
+
 // mode 0: src fp32 NCHW (already normalised unless mean/inv_std given)
 // mode 1: src uint8 NHWC (raw image bytes, normalised with mean/inv_std in 0..1 scale)
 __global__ __launch_bounds__(256) void preprocess_kernel(const void* __restrict__ src, bf16_t* __restrict__ dst,
@@ -550,6 +622,16 @@ extern "C" int hz_pool_fc_launch(const HzPoolFcParams* pp, hipStream_t st) {
     case 7: HZ_LAUNCH(pool_fc_kernel<7>, grid, dim3(256), lds, st, p); break;  // 7x7 (ResNet @224)
     default: HZ_LAUNCH(pool_fc_kernel<0>, grid, dim3(256), lds, st, p); break;
   }
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_pool_norm_launch(const HzPoolNormParams* pp, hipStream_t st) {
+  const HzPoolNormParams& p = *pp;
+  if (!p.x || !p.out || ((uintptr_t)p.x & 15) || ((uintptr_t)p.out & 15)) return -1;  // 16-B loads and stores
+  if (p.B < 1 || p.HW < 1) return -1;
+  if (p.C < 32 || p.C % 32 || p.C > 2048) return -1;  // 256 threads x 8 channels
+  if (p.ldo < p.C) return -1;
+  HZ_LAUNCH(pool_norm_kernel, dim3(p.B), dim3(256), 0, st, p);
   return (int)hipGetLastError();
 }
 

@@ -24,7 +24,8 @@ bind as ONE fused kernel instead:
 * ``kconv``: a seam's 3x3 neighbours as K-split 3x3 launches into fp32 accumulators
   (``kconv_kernel``; :func:`match_kconvs`).
 * ``tail``: the last block's conv3 + the global average pool (the seam kernel's tail mode): the
-  classifier's ``pool_fc`` then reads fp32 channel means (``HzPoolFcParams.pooled``).
+  classifier's ``pool_fc`` then reads fp32 channel means (``HzPoolFcParams.pooled``), and so does the
+  embedding head's ``pool_norm`` (``HzPoolNormParams.pooled``).
 * ``dsseam``: layer3's downsample as more K of layer3's first seam (its node skipped), so the
   stage's downsample + conv1 pair launch becomes conv1 alone (:func:`match_dsseam`).
 * ``xseam``: the layer3 -> layer4 boundary -- layer3's last conv3 + layer4's first conv1 as one
@@ -289,14 +290,14 @@ def match_seam(g, params, i: int) -> Fused | None:
 
 def match_tail(g, params, i: int) -> Fused | None:
     """nodes[i] = conv3 of the network's last bottleneck (1x1 512 -> 2048 + residual, <= 64 pixels),
-    nodes[i+1] = the pooled classifier (``pool_fc``) reading its output alone: conv3 binds as the
-    seam kernel's tail mode, which writes the channel means instead of the block output, and the
-    pool_fc launch reads them (``reader``)."""
+    nodes[i+1] = the pooled classifier (``pool_fc``) or the pooled embedding head (``pool_norm``) reading
+    its output alone: conv3 binds as the seam kernel's tail mode, which writes the channel means instead
+    of the block output, and the reader's launch takes them (``reader``; its ``pooled`` flag)."""
     nodes = g.nodes
     if i + 2 > len(nodes):
         return None
     c3, pf = nodes[i:i + 2]
-    if not _conv(c3) or pf.kind != "pool_fc" or pf.inputs != [c3.outputs[0]] or c3.slot != pf.slot:
+    if not _conv(c3) or pf.kind not in ("pool_fc", "pool_norm") or pf.inputs != [c3.outputs[0]] or c3.slot != pf.slot:
         return None
     if c3.attrs.get("out_f32") or c3.attrs.get("rowmajor") or c3.attrs.get("act", "relu") != "relu":
         return None

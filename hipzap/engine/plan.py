@@ -323,9 +323,10 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
     ``seq_len``: the captured sequence length of a text model (default: the adapter's, 128).
     ``resize``: ``(resize, crop, max_h, max_w)`` writes a RESIZE plan (``<ckpt>.rz.hzplan`` by default):
     requests are uint8 images of any size up to the maximum (ResNet and ViT; models/resnet.py and
-    models/vit.py build_graph). With ``embed`` on a ViT the default is ``<ckpt>.emb.rz.hzplan``.
-    ``embed``: ``{"pooling": "mean" | "cls", "normalize": bool}`` writes an EMBEDDING plan of a BERT / ViT
-    checkpoint (``<ckpt>.emb.hzplan`` by default): the output is one pooled vector per sequence / image."""
+    models/vit.py build_graph). With ``embed`` the default is ``<ckpt>.emb.rz.hzplan``.
+    ``embed``: ``{"pooling": "mean" | "cls", "normalize": bool}`` writes an EMBEDDING plan of a BERT, ViT or
+    ResNet checkpoint (``<ckpt>.emb.hzplan`` by default): the output is one pooled vector per sequence /
+    image. A ResNet pools by the mean only (its global average pool, csrc/vision.hip pool_norm_kernel)."""
     from .packfile import source_stamp
     sd = torch.load(ckpt, map_location="cpu", weights_only=True)
     if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
@@ -344,10 +345,11 @@ def export_from_checkpoint(model: str, ckpt: str, path: str | None = None, batch
         input_uint8 = False
         path = path or plan_path(ckpt, "emb.rz" if embed is not None else "rz")
     if embed is not None:
-        if model.startswith("resnet"):
-            raise ValueError(f"embedding plans cover the BERT and ViT encoders, not {model}")
         if kw.get("probs"):
             raise ValueError("probs=True (a softmax over class logits) does not combine with an embedding plan")
+        if model.startswith("resnet") and str(embed.get("pooling", "mean")) != "mean":
+            raise ValueError(f"pooling {embed['pooling']!r}: a ResNet embedding is its global average pool "
+                             f"(pooling 'mean'); 'cls' belongs to the BERT and ViT encoders")
         arch_kw.update(head="embed", pooling=str(embed.get("pooling", "mean")),
                        normalize=bool(embed.get("normalize", True)))
         path = path or plan_path(ckpt, "emb")

@@ -526,6 +526,12 @@ class ExecContext:
                                       nb, c, h * w, pc.cout, g.shape(n.outputs[0])[-1],
                                       int(id(n) in self.pooled_readers))
             N.prog_add(lib, self.prog, N.HZ_K_POOL_FC, prm, n.slot, "add_pool_fc")
+        elif n.kind == "pool_norm":  # the ResNet embedding head: pooled (and normalised) features, no classifier
+            nb, h, w, c = g.shape(n.inputs[0])
+            assert conv_ops.is_blocked(c) and g.shape(n.outputs[0]) == (nb, c)
+            prm = vision.PoolNormParams(addr(n.inputs[0]), addr(n.outputs[0]), nb, c, h * w, c,
+                                        int(id(n) in self.pooled_readers), int(bool(n.attrs["normalize"])))
+            N.prog_add(lib, self.prog, N.HZ_K_POOL_NORM, prm, n.slot, "add_pool_norm")
         elif n.kind == "softmax":
             ishape = g.shape(n.inputs[0])
             rows, ld = ishape[0], int(torch.tensor(ishape[1:]).prod())

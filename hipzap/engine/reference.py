@@ -175,6 +175,10 @@ def run_graph_reference(g: Graph, params: dict, inputs: list, bf16_acts: bool = 
             from ..ops.vision import pool_fc_ref
             x = vals[n.inputs[0]].float().reshape(g.shape(n.inputs[0]))
             store(n.outputs[0], pool_fc_ref(x, params[n.attrs["w"]]))
+        elif k == "pool_norm":
+            from ..ops.vision import pool_norm_ref
+            x = vals[n.inputs[0]].float().reshape(g.shape(n.inputs[0]))
+            store(n.outputs[0], pool_norm_ref(x, n.attrs["normalize"]).float())
         elif k == "softmax":
             from ..ops.transformer import softmax_ref
             x = vals[n.inputs[0]].float().reshape(g.shape(n.inputs[0])[0], -1)

@@ -58,9 +58,9 @@ class VisionAdapter:
             m = self.make_model(num_classes)
         return pack_resnet(m.state_dict(), "meta"), {"num_classes": num_classes or self.num_classes}
 
-    def build_graph(self, batch=1, num_classes=None, input_uint8=False, **kw):
+    def build_graph(self, batch=1, num_classes=None, input_uint8=False, image=None, **kw):
         from .resnet import build_graph
-        return build_graph(self.arch, batch, num_classes or self.num_classes, self.image, input_uint8, **kw)
+        return build_graph(self.arch, batch, num_classes or self.num_classes, image or self.image, input_uint8, **kw)
 
     def example_input(self, batch=1, generator=None):
         return torch.randn(batch, 3, self.image, self.image, generator=generator)

@@ -117,10 +117,14 @@ class ResNet(nn.Module):
             layers.append(block(self.inplanes, planes))
         return nn.Sequential(*layers)
 
-    def forward(self, x):
+    def features(self, x):
+        """The pooled features [N, 512 * expansion] the classifier reads (the embedding head's vector)."""
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        return self.fc(torch.flatten(self.avgpool(x), 1))
+        return torch.flatten(self.avgpool(x), 1)
+
+    def forward(self, x):
+        return self.fc(self.features(x))
 
 
 def resnet18(num_classes=1000) -> ResNet:
@@ -240,7 +244,7 @@ def _conv_stride_pad(name: str, wshape, bottleneck: bool) -> tuple[int, int]:
 
 def build_graph(arch: str, batch: int, num_classes: int = 1000, image: int = 224,
                 input_uint8: bool = False, side_stream: bool = False, fuse_head: bool = True,
-                resize=None) -> Graph:
+                resize=None, head: str = "cls", pooling: str = "mean", normalize: bool = True) -> Graph:
     """Lower ResNet to a static kernel graph for a fixed batch size.
 
     ``side_stream`` puts the downsample conv on a forked stream. Off by default: measured on
@@ -253,7 +257,19 @@ def build_graph(arch: str, batch: int, num_classes: int = 1000, image: int = 224
     ``ops/vision.py pack_images``), and the first node resizes the shorter side to ``resize``
     (antialiased bilinear), centre-crops ``crop`` x ``crop`` and normalises, in one launch
     (csrc/vision.hip resize_preprocess_kernel). Everything after it is the fixed-shape graph.
+
+    ``head="embed"``: no classifier; the graph ends in one ``pool_norm`` node whose output is one fp32
+    vector ``[B, C]`` per image (C = 512 for the basic-block nets, 2048 for the bottleneck ones): the
+    global average pool of the last block's output, L2-normalised with ``normalize`` (csrc/vision.hip
+    pool_norm_kernel). A ResNet pools by the mean only. ``head="cls"`` graphs are unchanged.
     """
+    if head not in ("cls", "embed"):
+        raise ValueError(f"head {head!r}: one of ('cls', 'embed')")
+    if head == "embed":
+        if pooling != "mean":
+            raise ValueError(f"pooling {pooling!r}: a ResNet embedding is its global average pool, pooling='mean'")
+        if not fuse_head:
+            raise ValueError("head='embed' is the fused pool_norm launch: not with fuse_head=False")
     block, layers = ARCHS[arch]
     g = Graph(f"{arch}_bs{batch}")
     if resize is not None:
@@ -322,6 +338,12 @@ def build_graph(arch: str, batch: int, num_classes: int = 1000, image: int = 224
                 x = conv(y, f"{pre}.conv2", cout, 3, 1, 1, res=idt)
             cin = cout
     nb, h, w, c = g.shape(x)
+    if head == "embed":  # one kernel: global average pool + L2 norm (csrc/vision.hip pool_norm_kernel)
+        vec = g.tensor((nb, c), torch.float32, "embed", external=True)
+        g.add("pool_norm", [x], [vec], normalize=bool(normalize), name="pool_norm")
+        g.outputs.append(vec)
+        g.meta = dict(getattr(g, "meta", None) or {}, head="embed", pooling="mean", normalize=bool(normalize), dim=c)
+        return g
     if fuse_head:  # one kernel: global average pool + FC (csrc/vision.hip pool_fc_kernel)
         logits = g.tensor((nb, 1, 1, num_classes), torch.float32, "fc", external=True)
         g.add("pool_fc", [x], [logits], w="fc", name="pool_fc")

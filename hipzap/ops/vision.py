@@ -18,6 +18,12 @@ class PoolFcParams(C.Structure):
                 ("pooled", C.c_int), ("pad_", C.c_int)]
 
 
+@N.params_of("HZ_K_POOL_NORM")
+class PoolNormParams(C.Structure):  # HzPoolNormParams (csrc/hipzap.h)
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("C", C.c_int), ("HW", C.c_int),
+                ("ldo", C.c_int), ("pooled", C.c_int), ("normalize", C.c_int)]
+
+
 @N.params_of("HZ_K_AVGPOOL")
 class AvgpoolArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("N", C.c_int), ("HW", C.c_int), ("C", C.c_int),
@@ -175,6 +181,44 @@ def pool_fc_ref(x: torch.Tensor, pc) -> torch.Tensor:
     """fp32 oracle: x logical [B,H,W,C]."""
     pooled = x.float().mean(dim=(1, 2))
     return pooled @ pc.dense().float().t() + pc.bias.float()
+
+
+def pool_norm(x: torch.Tensor, normalize: bool = True, blocked_input: bool = False,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """Global average pool [+ L2 normalisation] (csrc/vision.hip pool_norm_kernel): x logical [B,H,W,C]
+    bf16 (``blocked_input``: ``ops.conv.to_blocked``'s [B, C/32, H, W, 32] already) -> fp32 [B, C]; an fp32
+    [B, C] ``x`` is taken as the channel means a tail seam wrote (``pooled``). ``out``: an fp32 [B, >= C]
+    tensor to write into (columns past C are left alone; the returned view is its first C columns)."""
+    from .conv import to_blocked
+    pooled = x.dtype == torch.float32
+    if pooled:
+        b, c = x.shape
+        hw, src = 1, x.contiguous()
+    elif blocked_input:
+        b, cb, h, w, c32 = x.shape
+        assert c32 == 32 and x.is_contiguous(), tuple(x.shape)
+        c, hw, src = cb * 32, h * w, x
+    else:
+        b, h, w, c = x.shape
+        assert c % 32 == 0, c
+        hw, src = h * w, to_blocked(x)
+    if out is None:
+        out = torch.empty(b, c, device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.shape[0] == b and out.stride(1) == 1
+    prm = PoolNormParams(src.data_ptr(), out.data_ptr(), b, c, hw, out.stride(0), int(pooled), int(bool(normalize)))
+    N.check(N.lib().hz_launch_kernel(N.HZ_K_POOL_NORM, C.byref(prm), N.stream_ptr()), "pool_norm")
+    return out[:, :c]
+
+
+def pool_norm_ref(x: torch.Tensor, normalize: bool = True) -> torch.Tensor:
+    """fp64 oracle: x logical [B,H,W,C] (or [B, C] channel means) -> [B, C] float64; ``normalize`` divides
+    by max(||row||, 1e-12)."""
+    v = x.double()
+    if v.dim() == 4:
+        v = v.mean(dim=(1, 2))
+    if normalize:
+        v = v / v.norm(dim=1, keepdim=True).clamp(min=1e-12)
+    return v
 
 
 def preprocess(src: torch.Tensor, cpad: int = 8, mean=None, std=None) -> torch.Tensor:

@@ -83,7 +83,12 @@ class VisionBackend:
         # "probs": true in the model's settings block -> the softmax runs on device, responses are probabilities
         self.probs = bool(spec.extra.get("probs", False))
         # "embed": {"pooling", "normalize"} in the model's settings block -> an embedding backend (POST /embed)
-        self.embed = embed_spec(spec, "cls") if name.startswith("vit") else None
+        # (a ViT pools its CLS token by default; a ResNet's vector is its global average pool: "mean" only)
+        self.embed = embed_spec(spec, "cls") if name.startswith("vit") else \
+            embed_spec(spec, "mean") if name.startswith("resnet") else None
+        if self.embed is not None and name.startswith("resnet") and self.embed["pooling"] != "mean":
+            raise ValueError(f"{name}: extra.embed pooling {self.embed['pooling']!r}: a ResNet embedding is its global "
+                             f"average pool (pooling 'mean')")
         if self.embed is not None and self.probs:
             raise ValueError(f"{name}: extra.probs does not combine with extra.embed")
         if backend == "gpu":
@@ -93,6 +98,16 @@ class VisionBackend:
             self.model = None
             if self.embed is not None:
                 self.embed = self.engine.embed
+        elif self.embed is not None and name.startswith("resnet"):
+            # the torch module; its pooled features go through the oracle (ops/vision.py pool_norm_ref)
+            from ..models.resnet import infer_arch
+            sd = _state_dict(sd)
+            _, ncls = infer_arch(sd)
+            self.model = self.adapter.make_model(ncls)
+            self.model.load_state_dict(sd)
+            self.model.eval()
+            self.embed = dict(self.embed, dim=int(self.model.fc.in_features))
+            self.engine = None
         elif self.embed is not None:  # the HF encoder; pooled by the oracle (ops/transformer.py pool_embed_ref)
             from transformers import ViTConfig, ViTModel
             from ..models.vit import config_from_sd
@@ -137,6 +152,11 @@ class VisionBackend:
             raise ValueError(f"{self.name} is served without extra.embed: POST /predict")
         if self.engine is not None:
             return torch.cat([self._run_padded(x[i: i + self.batch]) for i in range(0, x.shape[0], self.batch)])
+        if self.name.startswith("resnet"):
+            from ..ops.vision import pool_norm_ref
+            with torch.no_grad():
+                f = self.model.features(x.float())
+            return pool_norm_ref(f, self.embed["normalize"]).float()
         from ..ops.transformer import pool_embed_ref
         with torch.no_grad():
             h = self.model(pixel_values=x.float()).last_hidden_state
