@@ -212,6 +212,23 @@ def cmd_info(a):
     print(json.dumps(info, indent=1))
 
 
+def cmd_knn(a):
+    """The kNN graph of a plain bf16 index -> an .npz with ``ids`` int32 [count, k] and ``scores`` float32 [count, k]
+    (-1 / -inf in a deleted row's lists)."""
+    import numpy as np
+
+    from .search import open_index
+    try:
+        with open_index(a.index, a.backend, a.device) as ix:
+            ids, scores = ix.knn_graph(a.k, block=a.block) if a.block else ix.knn_graph(a.k)
+    except ValueError as e:
+        sys.exit(f"hipzap knn: {e}")
+    with open(a.out, "wb") as f:
+        np.savez(f, ids=ids, scores=scores)
+    print(json.dumps({"index": a.index, "out": a.out, "count": int(ids.shape[0]), "k": a.k, "backend": a.backend,
+                      "rows_with_neighbors": int((ids[:, 0] >= 0).sum())}))
+
+
 def cmd_bench(a, rest):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.exit(subprocess.call([sys.executable, os.path.join(root, "bench.py"), *rest]))
@@ -290,6 +307,13 @@ def main(argv=None):
     ix.add_argument("--model", default=None, help="free text kept in the header")
     ix.add_argument("--device", type=int, default=0)
     ix.add_argument("--out", required=True)
+    kn = sub.add_parser("knn", help="the kNN graph of a plain bf16 .hzidx (dim %% 32 == 0): every live row's k nearest live rows")
+    kn.add_argument("index", help="a .hzidx file")
+    kn.add_argument("--k", type=int, default=10)
+    kn.add_argument("--out", required=True, help="an .npz: ids int32 [count, k], scores float32 [count, k]")
+    kn.add_argument("--backend", choices=["gpu", "cpu"], default="gpu")
+    kn.add_argument("--block", type=int, default=None, help="rows per pass (default 1024)")
+    kn.add_argument("--device", type=int, default=0)
     inf = sub.add_parser("info")
     inf.add_argument("path", nargs="?", default=None, help="a .hzidx file: print its header")
     sub.add_parser("bench", add_help=False)
@@ -297,7 +321,7 @@ def main(argv=None):
     if args.cmd == "bench":
         return cmd_bench(args, rest)
     {"serve": cmd_serve, "pack": cmd_pack, "plan": cmd_plan, "tune": cmd_tune, "upload": cmd_upload, "info": cmd_info,
-     "index": cmd_index}[args.cmd](args)
+     "index": cmd_index, "knn": cmd_knn}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -541,6 +541,46 @@ typedef struct HzSearchQuantListParams {
   const float* scales;           // fp32 [N] in stored order, 4-B aligned
 } HzSearchQuantListParams;
 int hz_search_qlscan_launch(const HzSearchQuantListParams* p, hipStream_t st);
+// self scan (HZ_K_SEARCH_MSCAN): the queries are ROWS OF THE CORPUS, named by `qid`. The grid is
+// (tile of HZ_SEARCH_TILE rows, block of HZ_SEARCH_SELF_QB queries); a workgroup reads its queries' rows by id and
+// scores them against the tile's rows with v_mfma_f32_16x16x32_bf16, then writes per query the tile's best
+// min(k, passing rows) keys, best first, then key 0, to cand[(tile*Q + q)*k ..]. Keys and their total order are
+// the scan's. pass(q, r) = live(r) && !(skip_self && r == qid[q]); other rows with the query's bits stay and tie by
+// id. A group of 16 rows with no live row is not loaded; a dead row of a mixed group is loaded and scores the
+// sentinel. A qid outside [0, N) gives k zero keys for its query and nothing is read through it; the query's own
+// live bit is not looked at (hz_index_neighbors refuses a deleted id). HZ_K_SEARCH_MERGEN reduces the lists.
+// CONTRACT: every product of two bf16 values is exact in fp32; score(a, b) is the fp32 accumulator of the MFMAs
+// over columns 0..31, 32..63, ... in that order, starting from +0, row a being the A operand and row b the B
+// operand. Its bits depend on the D values of the two rows only: not on N, Q, k, the position of either row, the
+// tile, or the other queries of the block. They are NOT the bits of HZ_K_SEARCH_SCAN for the widened query: that
+// kind is one fmaf chain per lane and a butterfly, this one the matrix unit's sum, a different order of the same
+// products. score(a, b) == score(b, a) is not promised.
+// Refusals (nothing is launched): -50 corpus, qid, live or cand null; -51 D % 32; -52 D < 32; -53 D > 2048;
+// -54 ldc < D or ldc % 8; -55 N < 1; -56 Q outside 1..HZ_SEARCH_SELF_MAX_Q (the grid's y limit of 65535 blocks);
+// -57 k outside 1..HZ_SEARCH_MAX_K; -58 corpus not 16-B, cand not 8-B or qid / live not 4-B aligned;
+// -59 live_bytes < 4 * ceil(N / 32); -60 cand_bytes < ntile * Q * k * 8.
+#define HZ_SEARCH_SELF_QB 64
+#define HZ_SEARCH_SELF_MAX_Q (65535 * HZ_SEARCH_SELF_QB)
+typedef struct HzSearchSelfParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows (ldc % 8 == 0), ldc >= D
+  const int* qid;                // device int32 [Q]: the rows that are the queries
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5 (required)
+  unsigned long long* cand;      // scratch [ntile][Q][k] keys
+  float* out_score;              // fp32 [Q][k]  (HZ_K_SEARCH_MERGEN only)
+  int* out_id;                   // int32 [Q][k] (HZ_K_SEARCH_MERGEN only)
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  unsigned long long cand_bytes; // bytes of `cand`, at least hz_search_self_scratch_bytes(N, Q, k)
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launchers: ceil(N / HZ_SEARCH_TILE)
+  int skip_self, pad_;
+} HzSearchSelfParams;
+// ntile * Q * k * 8; 0 for a refused N, Q or k
+unsigned long long hz_search_self_scratch_bytes(long long N, long long Q, int k);
+int hz_search_mscan_launch(const HzSearchSelfParams* p, hipStream_t st);
+// merge for any number of queries (HZ_K_SEARCH_MERGEN): search_merge_kernel, one workgroup per query over
+// cand [ntile][Q][k] -> out_score / out_id [Q][k]. Reads cand, out_*, N, Q, k and cand_bytes of the block only.
+// Refusals: -50 cand, out_score or out_id null; -55; -56; -57; -58 cand not 8-B or out_* not 4-B aligned; -60.
+int hz_search_mergen_launch(const HzSearchSelfParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
@@ -630,6 +670,18 @@ int hz_index_probes(void* idx, int ctx, const float* queries, int Q, int nprobe,
 // stored rows, hz_index_read_rescore up to count rows by id. Rows are never added (-34).
 // out[8] = {1 for an IVF index, nlist, default nprobe, tiles, external count, the file's version, 0, 0}
 int hz_index_describe3(void* idx, uint64_t* out);
+// neighbours of stored rows (a plain bf16 index, versions 1 and 2, dim % 32 == 0): the k nearest live
+// rows of each of the n rows `ids` names, the row itself excluded iff skip_self -> out_score fp32 [n][k], out_id
+// int32 [n][k], -inf / -1 past the live rows. Replays H2D of the ids, HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two
+// D2H; captured per (n, k, skip_self). One call takes at most HZ_INDEX_SELF_MAX_Q ids (the caller splits above it):
+// the candidate scratch of a context, allocated on first use and grown on demand, is ceil(capacity /
+// HZ_SEARCH_TILE) * n * k * 8 bytes, so at most tiles * HZ_INDEX_SELF_MAX_Q * HZ_SEARCH_MAX_K * 8.
+// -4: n outside 1..the maximum; -5: k; -20: an id outside [0, count); -35: an fp8 or an IVF index; -36: dim % 32;
+// -37: a deleted id (hz_index_last_error names the value in each case).
+#define HZ_INDEX_SELF_MAX_Q 1024
+int hz_index_neighbors(void* idx, int ctx, const int* ids, int n, int k, int skip_self, float* out_score, int* out_id);
+// the ids one hz_index_neighbors call takes; set in 1..HZ_INDEX_SELF_MAX_Q lowers or restores it first (0: only read)
+int hz_index_neighbors_max(void* idx, int set);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -814,7 +866,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_RESCORE, 35, HzSearchRescoreParams, hz_search_rescore_op, SEARCH) \
   X(SEARCH_LSCAN, 36, HzSearchListParams, hz_search_lscan_op, SEARCH)     \
   X(SEARCH_QLSCAN, 37, HzSearchQuantListParams, hz_search_qlscan_op, SEARCH) \
-  X(POOL_NORM, 38, HzPoolNormParams, hz_pool_norm_op, VISION)
+  X(POOL_NORM, 38, HzPoolNormParams, hz_pool_norm_op, VISION)               \
+  X(SEARCH_MSCAN, 39, HzSearchSelfParams, hz_search_mscan_op, SEARCH)     \
+  X(SEARCH_MERGEN, 40, HzSearchSelfParams, hz_search_mergen_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

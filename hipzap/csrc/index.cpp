@@ -35,6 +35,11 @@
 // same. Version 7 also holds the vectors' bf16 rows BY EXTERNAL ID (`n_ext` rows, device or pinned host memory):
 // with refine = R the list scan and its merge run at k = R into the context's intermediate buffer and
 // HZ_K_SEARCH_RESCORE re-scores those external ids against rrows[id] with N = n_ext. R is part of the key too.
+//
+// Neighbours of stored rows (a plain bf16 index): hz_index_neighbors replays H2D of the ids,
+// HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two D2H, with the filtered programs' N (the rows past the count are dead
+// in the bitmap) and so under their invalidation rules. A context's buffers for it (ids, results, candidate
+// scratch) are allocated on the first such call; the scratch grows to the largest (n, k) asked for.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -80,12 +85,21 @@ struct Ctx {
   char* probe_dev = nullptr;          // IVF only: the coarse stage's scores and list ids, the layout of out_dev
   unsigned long long* ccand = nullptr;  // IVF only: the coarse stage's candidate scratch
   uint64_t ccand_bytes = 0;
+  // neighbours only, allocated on first use: the ids (pinned, device), the results [SELF_MAX_Q][MAX_K] scores then
+  // ids (device, pinned) and the candidate scratch [tiles][n][k], grown on demand
+  int* nid_host = nullptr;
+  int* nid_dev = nullptr;
+  char* nout_dev = nullptr;
+  char* nout_host = nullptr;
+  unsigned long long* ncand = nullptr;
+  uint64_t ncand_bytes = 0;
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
-  // probes alone
+  // probes alone; neighbours: (n, k, 3, skip_self, 0)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
 constexpr size_t kOutHalf = (size_t)HZ_SEARCH_MAX_Q * HZ_SEARCH_MAX_K * 4;
+constexpr size_t kSelfOutHalf = (size_t)HZ_INDEX_SELF_MAX_Q * HZ_SEARCH_MAX_K * 4;
 
 uint64_t round_up(uint64_t v, uint64_t m) { return (v + m - 1) / m * m; }
 
@@ -125,6 +139,7 @@ struct Index {
   unsigned* tags = nullptr;           // device, cap words
   std::vector<uint32_t> live_host, tags_host;  // mirrors, sized like the device buffers
   bool ivf = false;                   // a version-5, 6 or 7 file
+  int self_max = HZ_INDEX_SELF_MAX_Q;  // the ids one hz_index_neighbors call takes (hz_index_neighbors_max)
   uint64_t n_ext = 0;                 // IVF: the number of vectors (external ids 0 .. n_ext-1)
   int nlist = 0, nprobe_default = 0;
   unsigned short* centroids = nullptr;  // device bf16 [nlist][dim]
@@ -146,6 +161,11 @@ struct Index {
       if (c->mid_dev) (void)hipFree(c->mid_dev);
       if (c->probe_dev) (void)hipFree(c->probe_dev);
       if (c->ccand) (void)hipFree(c->ccand);
+      if (c->nid_host) (void)hipHostFree(c->nid_host);
+      if (c->nout_host) (void)hipHostFree(c->nout_host);
+      if (c->nid_dev) (void)hipFree(c->nid_dev);
+      if (c->nout_dev) (void)hipFree(c->nout_dev);
+      if (c->ncand) (void)hipFree(c->ncand);
       if (c->st) (void)hipStreamDestroy(c->st);
     }
     free_rescore(rrows);
@@ -253,6 +273,71 @@ struct Index {
     if (!rc && R) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCORE, &rp, sizeof(rp), 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.out_host, c.out_dev, qk, 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.out_host + kOutHalf, c.out_dev + kOutHalf, qk, 0);
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
+  // The neighbours program of (n, k, skip_self) (the caller holds c.mu): H2D of the ids, self scan, merge, two D2H.
+  // Its buffers come first; candidate scratch too small for (n, k) is replaced, and with it the context's
+  // neighbours programs, which hold its address by value.
+  HzProgram self_program(Ctx& c, int n, int k, int skip_self, bool* fresh) {
+    if (!c.nid_host) {
+      bool ok = hipHostMalloc(reinterpret_cast<void**>(&c.nid_host), (size_t)HZ_INDEX_SELF_MAX_Q * 4, hipHostMallocDefault) == hipSuccess;
+      ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c.nout_host), 2 * kSelfOutHalf, hipHostMallocDefault) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.nid_dev), (size_t)HZ_INDEX_SELF_MAX_Q * 4) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.nout_dev), 2 * kSelfOutHalf) == hipSuccess;
+      if (!ok) {
+        if (c.nid_host) (void)hipHostFree(c.nid_host);
+        if (c.nout_host) (void)hipHostFree(c.nout_host);
+        if (c.nid_dev) (void)hipFree(c.nid_dev);
+        if (c.nout_dev) (void)hipFree(c.nout_dev);
+        c.nid_host = c.nid_dev = nullptr, c.nout_host = c.nout_dev = nullptr;
+        return nullptr;
+      }
+    }
+    const uint64_t need = hz_search_self_scratch_bytes((long long)scan_rows(), n, k);
+    if (!need) return nullptr;
+    if (need > c.ncand_bytes) {
+      for (auto it = c.progs.begin(); it != c.progs.end();) {
+        if (std::get<2>(it->first) == 3) {
+          hz_prog_destroy(it->second);
+          it = c.progs.erase(it);
+        } else {
+          ++it;
+        }
+      }
+      if (c.ncand) (void)hipFree(c.ncand);
+      c.ncand = nullptr, c.ncand_bytes = 0;
+      if (hipMalloc(reinterpret_cast<void**>(&c.ncand), need) != hipSuccess) return nullptr;
+      c.ncand_bytes = need;
+    }
+    const auto key = std::make_tuple(n, k, 3, skip_self, 0);
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    HzSearchSelfParams p{};
+    p.corpus = rows;
+    p.qid = c.nid_dev;
+    p.live = live;
+    p.cand = c.ncand;
+    p.out_score = reinterpret_cast<float*>(c.nout_dev);
+    p.out_id = reinterpret_cast<int*>(c.nout_dev + kSelfOutHalf);
+    p.live_bytes = cap / 8;
+    p.cand_bytes = c.ncand_bytes;
+    p.N = (int)scan_rows();
+    p.D = p.ldc = (int)h.dim;
+    p.Q = n, p.k = k, p.skip_self = skip_self;
+    HzProgram g = hz_prog_create();
+    const size_t nk = (size_t)n * k * 4;
+    int rc = hz_prog_add_memcpy(g, c.nid_dev, c.nid_host, (size_t)n * 4, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MSCAN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.nout_host, c.nout_dev, nk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.nout_host + kSelfOutHalf, c.nout_dev + kSelfOutHalf, nk, 0);
     if (rc) {
       hz_prog_destroy(g);
       return nullptr;
@@ -666,6 +751,7 @@ int hz_index_describe(void* h, uint64_t* out) {
   for (auto& c : x->ctx) {
     progs += c->progs.size();
     dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf + (c->mid_dev ? 2 * kOutHalf : 0);
+    dev += c->ncand_bytes + (c->nid_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 + 2 * kSelfOutHalf : 0);  // neighbours, once used
   }
   const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
   std::memcpy(out, v, sizeof(v));
@@ -773,6 +859,66 @@ int hz_index_probes(void* h, int ctx, const float* queries, int Q, int nprobe, i
   if (!rc) rc = (int)hipStreamSynchronize(c.st);
   if (rc) return rc;
   std::memcpy(out_list, c.out_host + kOutHalf, (size_t)Q * nprobe * 4);
+  if (fresh) {
+    rc = hz_prog_capture(g, c.st);
+    if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  }
+  return rc;
+}
+
+int hz_index_neighbors_max(void* h, int set) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || set < 0 || set > HZ_INDEX_SELF_MAX_Q) return -1;
+  AllLocked all(*x);
+  if (set) x->self_max = set;
+  return x->self_max;
+}
+
+int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_self, float* out_score, int* out_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !ids || !out_score || !out_id) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (x->fp8 || x->ivf) {
+    g_err = std::string("index: neighbors is built for plain bf16 indexes (versions 1 and 2), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : "an fp8_e4m3 index") + " of version " +
+            std::to_string(x->h.version);
+    return -35;
+  }
+  if (x->h.dim % 32) {
+    g_err = "index: neighbors needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -36;
+  }
+  if (k < 1 || k > HZ_SEARCH_MAX_K) {
+    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
+    return -5;
+  }
+  skip_self = skip_self ? 1 : 0;
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // count, the bitmap mirror and self_max change only under every context's mutex
+  if (n < 1 || n > x->self_max) {
+    g_err = "index: neighbors takes 1.." + std::to_string(x->self_max) + " ids a call, got " + std::to_string(n);
+    return -4;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || (uint64_t)ids[i] >= x->count) {
+      g_err = "index: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(x->count) + ")";
+      return -20;
+    }
+    if (!(x->live_host[(uint64_t)ids[i] >> 5] >> (ids[i] & 31) & 1u)) {
+      g_err = "index: id " + std::to_string(ids[i]) + " is deleted";
+      return -37;
+    }
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->self_program(c, n, k, skip_self, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.nid_host, ids, (size_t)n * 4);
+  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
+  if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  if (rc) return rc;
+  std::memcpy(out_score, c.nout_host, (size_t)n * k * 4);
+  std::memcpy(out_id, c.nout_host + kSelfOutHalf, (size_t)n * k * 4);
   if (fresh) {
     rc = hz_prog_capture(g, c.st);
     if (!rc) rc = (int)hipStreamSynchronize(c.st);

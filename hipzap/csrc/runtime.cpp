@@ -460,6 +460,14 @@ extern "C" __attribute__((weak)) int hz_search_qlscan_launch(const HzSearchQuant
 static int hz_search_qlscan_op(const HzSearchQuantListParams* p, hipStream_t st) {
   return hz_search_qlscan_launch ? hz_search_qlscan_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_mscan_launch(const HzSearchSelfParams* p, hipStream_t st);
+static int hz_search_mscan_op(const HzSearchSelfParams* p, hipStream_t st) {
+  return hz_search_mscan_launch ? hz_search_mscan_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_mergen_launch(const HzSearchSelfParams* p, hipStream_t st);
+static int hz_search_mergen_op(const HzSearchSelfParams* p, hipStream_t st) {
+  return hz_search_mergen_launch ? hz_search_mergen_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -8,7 +8,10 @@
 //                    row scales): workgroup (j, q) scores the j-th tile of the lists query q probes against that
 //                    query alone, with the template's pieces
 //   * search_merge — one workgroup per query: ntile x k candidates -> the final k, best first
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q for the reasoning.
+//   * search_mscan — the self scan (kind MSCAN): the queries are rows of the corpus named by id; workgroup (tile, block
+//                    of 64 queries) scores them with the bf16 MFMA and cuts before it ranks. Kind MERGEN is
+//                    search_merge behind a launcher that takes any number of queries
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -618,6 +621,197 @@ void rescore_dispatch(const HzSearchRescoreParams& a, hipStream_t st) {
   hipLaunchKernelGGL(search_rescore_kernel<NC>, dim3(a.Q), dim3(RESCORE_THREADS), 0, st, a);
 }
 
+// -------------------------------------------------------------------------------------- self scan
+// search_mscan_kernel (HZ_K_SEARCH_MSCAN): workgroup (tile, qb) scores the tile's T rows against the
+// QB rows that qid[qb*QB ..] names. Both operands are bf16 rows of the corpus, so a lane's MFMA fragment -- 8
+// consecutive columns of one row -- is one 16-byte load for either operand and nothing is staged or converted:
+// the A operand is the query rows (read by id; every workgroup of the block re-reads the same QB rows, which stay
+// in L2), the B operand the tile's rows. Wave w owns rows w*64 .. w*64+63 of the tile as four groups of 16 and
+// holds the 64 x 64 scores of its rows against the block's queries in 16 accumulators of 4 floats.
+// CONTRACT (hipzap.h): acc = mfma_f32_16x16x32_bf16(query fragment, row fragment, acc) over the columns 32s ..
+// 32s+31, s ascending, from +0. The k-steps are loaded two at a time, one pair ahead of the MFMAs.
+// Which rows: the tile's live words are staged with the bits from N on cleared. A group whose 16 live bits are 0
+// is not loaded and its MFMAs are skipped (a scalar branch); a dead row of a mixed group is loaded and scores the
+// sentinel 0, like (q, r) with skip_self and r == qid[q] and every pair of a query whose id is outside [0, N).
+// A NaN pattern in a dead row reaches only that row's own column of the product.
+// Selection: the scores land in LDS as order-preserving u32, sc[q][row] (row stride T + 4 words: the four lane
+// groups of a store hit different banks). Wave w then takes the queries w, w + 4, ... one at a time; lane l holds
+// rows l, l + 64, l + 128, l + 192 as keys. For k <= 64 the wave first finds, by a radix search over the top
+// MSCAN_CUT_BITS bits of the lanes' maxima (one ballot per bit), the largest prefix that at least k maxima reach:
+// k keys lie at or above it, so every key below it is out. The survivors are compacted into the wave's pool
+// (positions from ballots, no atomics) and ranked among themselves; ranks below k write cand[rank]. Keys of real
+// rows are distinct, so the list is a function of the tile's key set. k > 64: every passing key is a survivor.
+// Addresses: qid[q] under q < Q; corpus[id*ldc + ..] under (unsigned)id < N; the tile's rows under row < N; live
+// words [row0/32, row0/32 + 8) under word*32 < N (the launcher checks live_bytes); cand[(tile*Q + q)*k + s] under
+// q < Q and s < k -- `rank` is used only under rank < k.
+constexpr int QB = HZ_SEARCH_SELF_QB;
+constexpr int MSCAN_TS = T + 4;        // words per query in the score array
+constexpr int MSCAN_CUT_BITS = 20;     // sign, exponent and 11 mantissa bits of the score
+static_assert(QB == 64 && T == 256 && QB % 16 == 0, "the fragment and selection maps below");
+// dynamic LDS: scores [QB][MSCAN_TS] u32, the waves' pools [4][T] u64, the block's ids [QB], live words [T / 32]
+constexpr size_t MSCAN_LDS = (size_t)QB * MSCAN_TS * 4 + 4 * (size_t)T * 8 + QB * 4 + T / 32 * 4;
+
+__global__ __launch_bounds__(T) void search_mscan_kernel(const HzSearchSelfParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  unsigned* sc = reinterpret_cast<unsigned*>(lds);                                     // [QB][MSCAN_TS]
+  unsigned long long* pool = reinterpret_cast<unsigned long long*>(sc + QB * MSCAN_TS);  // [4][T]
+  int* qids = reinterpret_cast<int*>(pool + 4 * T);                                    // [QB], -1: no query
+  unsigned* lv = reinterpret_cast<unsigned*>(qids + QB);                               // [T / 32]
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int tile = blockIdx.x, q0 = blockIdx.y * QB;
+  if (!HZ_DCHECK(tile < p.ntile && (long)tile * T < (long)p.N && q0 < p.Q && p.D >= 32 && p.D % 32 == 0 && p.D <= 2048 &&
+                 p.ldc >= p.D && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K))
+    return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  const int nq = min(QB, p.Q - q0);
+  if (t < QB) {
+    int id = -1;
+    if (t < nq && HZ_DCHECK(q0 + t < p.Q)) id = p.qid[q0 + t];
+    qids[t] = (unsigned)id < (unsigned)p.N ? id : -1;
+  }
+  if (t < T / 32) {
+    const long word = (row0 >> 5) + t;
+    unsigned v = 0u;
+    if (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)p.live_bytes)) v = p.live[word];
+    const int left = rows - t * 32;  // the tile's rows from this word on
+    if (left < 32) v &= left <= 0 ? 0u : (1u << left) - 1u;
+    lv[t] = v;
+  }
+  __syncthreads();
+
+  const int lr = lane & 15, lh = lane >> 4;
+  unsigned gm[4], any = 0u;  // the live bits of this wave's four groups (wave-uniform)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int g = w * 4 + j;
+    gm[j] = (__builtin_amdgcn_readfirstlane(lv[g >> 1]) >> ((g & 1) * 16)) & 0xffffu;
+    any |= gm[j];
+  }
+  f32x4 acc[4][4];  // [query group][row group]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (any != 0u) {
+    const bf16_t* arow[4];
+    const bf16_t* brow[4];
+    bool aok[4], bok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int id = qids[i * 16 + lr];
+      aok[i] = id >= 0 && HZ_DCHECK(id < p.N);
+      arow[i] = p.corpus + (long)(aok[i] ? id : 0) * p.ldc + lh * 8;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = w * 64 + j * 16 + lr;
+      bok[j] = gm[j] != 0u && r < rows && HZ_DCHECK(row0 + r < (long)p.N);
+      brow[j] = p.corpus + (row0 + (bok[j] ? r : 0)) * p.ldc + lh * 8;
+    }
+    const int nk = p.D >> 5;
+    bf16x8 a[2][2][4], b[2][2][4];  // [buffer][k-step of the pair][group]
+    auto load = [&](int buf, int kk) {  // the k-steps kk and kk + 1 (columns under D: kk*32 + lh*8 + 8 <= D)
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a[buf][s][i] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+          b[buf][s][i] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+          if (kk + s < nk) {
+            if (aok[i]) a[buf][s][i] = *reinterpret_cast<const bf16x8*>(arow[i] + (kk + s) * 32);
+            if (bok[i]) b[buf][s][i] = *reinterpret_cast<const bf16x8*>(brow[i] + (kk + s) * 32);
+          }
+        }
+    };
+    auto mma = [&](int buf, int kk) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        if (kk + s < nk) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gm[j] != 0u) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[buf][s][i], b[buf][s][j], acc[i][j], 0, 0, 0);
+            }
+        }
+    };
+    load(0, 0);
+    for (int kk = 0; kk < nk; kk += 4) {  // two pairs per trip, so the buffer index is a constant
+      if (kk + 2 < nk) load(1, kk + 2);
+      mma(0, kk);
+      if (kk + 4 < nk) load(0, kk + 4);
+      if (kk + 2 < nk) mma(1, kk + 2);
+    }
+  }
+  // lane holds score(query i*16 + lh*4 + e, row w*64 + j*16 + lr) in acc[i][j][e]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int q = i * 16 + lh * 4 + e;
+      const int id = qids[q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = w * 64 + j * 16 + lr;
+        const bool pass = ((gm[j] >> lr) & 1u) && id >= 0 && !(p.skip_self && (long)id == row0 + r);
+        sc[q * MSCAN_TS + r] = pass ? orderable(acc[i][j][e]) : 0u;
+      }
+    }
+  __syncthreads();
+
+  unsigned long long* mine_pool = pool + w * T;
+  for (int i = 0; i * 4 < nq; ++i) {  // block-uniform trips: the barriers below are reached by every wave
+    const int q = i * 4 + w;
+    const bool valid = q < nq;  // wave-uniform
+    int n = 0, npass = 0;
+    if (valid) {
+      unsigned long long key[4];
+      unsigned mx = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned s = sc[q * MSCAN_TS + j * 64 + lane];
+        key[j] = s ? ((unsigned long long)s << 32) | (unsigned)~(unsigned)(row0 + j * 64 + lane) : 0ull;
+        npass += __popcll(__ballot(s != 0u));
+        mx = s > mx ? s : mx;
+      }
+      unsigned thr = 0u;
+      if (p.k <= 64) {  // the largest prefix that at least k of the lanes' maxima reach; 0: fewer than k lanes pass
+        for (int bit = 31; bit >= 32 - MSCAN_CUT_BITS; --bit) {
+          const unsigned c = thr | (1u << bit);
+          if (__popcll(__ballot(mx >= c)) >= p.k) thr = c;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool keep = key[j] != 0ull && (unsigned)(key[j] >> 32) >= thr;
+        const unsigned long long m = __ballot(keep);
+        const int at = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (keep && HZ_DCHECK(at < T)) mine_pool[at] = key[j];
+        n += __popcll(m);
+      }
+    }
+    __syncthreads();
+    if (valid) {
+      const long slot = (long)tile * p.Q + q0 + q;
+      unsigned long long* out = p.cand + slot * p.k;
+      const bool slot_ok = HZ_DCHECK(q0 + q < p.Q && (slot + 1) * p.k * 8 <= (long)p.cand_bytes);
+      for (int e = lane; e < n; e += 64) {
+        const unsigned long long mine = mine_pool[e];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += mine_pool[j] > mine;  // every lane reads the same word: a broadcast
+        if (rank < p.k && slot_ok) out[rank] = mine;
+      }
+      const int filled = min(p.k, npass);  // n >= filled: the cut keeps at least k keys, or every passing one
+      for (int s = lane; s < p.k; s += 64)
+        if (s >= filled && slot_ok) out[s] = 0ull;
+    }
+    __syncthreads();
+  }
+}
+
 // one refusal list for both launchers: the kernels then have no address that the data can move out of
 // its buffer. Fills ntile. `need`: the bytes `cand` must hold, 0 for the scan's hz_search_scratch_bytes(N, Q, k).
 int search_check(HzSearchParams& p, unsigned long long need = 0) {
@@ -805,10 +999,75 @@ extern "C" int hz_search_rescore_launch(const HzSearchRescoreParams* pp, hipStre
   return (int)hipGetLastError();
 }
 
+namespace {
+
+// the self scan's dynamic LDS is above 64 KiB: allowed once per device, outside any capture (hz_search_code_warm
+// at an index's open; a direct launch here)
+int raise_mscan_lds_limit() {
+  static bool done[64];
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
+  if (done[d]) return 0;
+  HZ_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_mscan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)MSCAN_LDS));
+  done[d] = true;
+  return 0;
+}
+
+// what the self scan and its merge both refuse: -55 N, -56 Q, -57 k, -60 cand_bytes. Fills ntile.
+int self_check(HzSearchSelfParams& p) {
+  if (p.N < 1) return -55;
+  if (p.Q < 1 || p.Q > HZ_SEARCH_SELF_MAX_Q) return -56;
+  if (p.k < 1 || p.k > HZ_SEARCH_MAX_K) return -57;
+  if (p.cand_bytes < hz_search_self_scratch_bytes(p.N, p.Q, p.k)) return -60;
+  p.ntile = (int)(((long)p.N + T - 1) / T);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" unsigned long long hz_search_self_scratch_bytes(long long N, long long Q, int k) {
+  if (N < 1 || N >= (1ll << 31) || Q < 1 || Q > HZ_SEARCH_SELF_MAX_Q || k < 1 || k > HZ_SEARCH_MAX_K) return 0;
+  return (unsigned long long)((N + T - 1) / T) * (unsigned long long)Q * k * 8ull;  // < 2^23 * 2^22 * 2^7 * 2^3
+}
+
+extern "C" int hz_search_mscan_launch(const HzSearchSelfParams* pp, hipStream_t st) {
+  HzSearchSelfParams p = *pp;
+  if (!p.corpus || !p.qid || !p.live || !p.cand) return -50;
+  if (p.D % 32) return -51;
+  if (p.D < 32) return -52;
+  if (p.D > 2048) return -53;
+  if (p.ldc < p.D || p.ldc % 8) return -54;
+  if ((reinterpret_cast<uintptr_t>(p.corpus) & 15) || (reinterpret_cast<uintptr_t>(p.cand) & 7) ||
+      (reinterpret_cast<uintptr_t>(p.qid) & 3) || (reinterpret_cast<uintptr_t>(p.live) & 3))
+    return -58;
+  if (p.N >= 1 && p.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -59;
+  if (const int rc = self_check(p)) return rc;
+  if (const int rc = raise_mscan_lds_limit()) return rc;
+  hipLaunchKernelGGL(search_mscan_kernel, dim3(p.ntile, (p.Q + QB - 1) / QB), dim3(T), MSCAN_LDS, st, p);
+  return (int)hipGetLastError();
+}
+
+// search_merge_kernel as it stands (its body has no limit on Q: one workgroup per query) behind the self scan's block
+extern "C" int hz_search_mergen_launch(const HzSearchSelfParams* pp, hipStream_t st) {
+  HzSearchSelfParams s = *pp;
+  if (!s.cand || !s.out_score || !s.out_id) return -50;
+  if ((reinterpret_cast<uintptr_t>(s.cand) & 7) || (reinterpret_cast<uintptr_t>(s.out_score) & 3) ||
+      (reinterpret_cast<uintptr_t>(s.out_id) & 3))
+    return -58;
+  if (const int rc = self_check(s)) return rc;
+  HzSearchParams p{};
+  p.cand = s.cand, p.out_score = s.out_score, p.out_id = s.out_id;
+  p.N = s.N, p.D = s.D, p.Q = s.Q, p.k = s.k, p.ldc = s.ldc, p.ntile = s.ntile, p.cand_bytes = s.cand_bytes;
+  hipLaunchKernelGGL(search_merge_kernel, dim3(p.Q), dim3(MERGE_THREADS), 0, st, p);
+  return (int)hipGetLastError();
+}
+
 // Load this translation unit's device code without a launch (see hz_conv_code_warm in conv.hip).
 __global__ void hz_search_code_warm_kernel() {}
 extern "C" int hz_search_code_warm(void) {
   hipFuncAttributes a;
   if (const int rc = (int)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&hz_search_code_warm_kernel))) return rc;
-  return raise_lds_limit();
+  if (const int rc = raise_lds_limit()) return rc;
+  return raise_mscan_lds_limit();
 }

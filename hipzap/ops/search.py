@@ -11,6 +11,9 @@ re-scores the ``R`` bf16 rows that a merge's ``out_id`` names and writes the bes
 ``HZ_K_SEARCH_LSCAN`` (``ListScanParams``) is the filtered scan over an IVF index's lists: workgroup (j, q) scans
 the j-th tile of the lists that ``probes[q]`` names; ``HZ_K_SEARCH_QLSCAN`` (``QuantListScanParams``: that block plus
 one fp32 scale per stored row) is the list scan over rows of e4m3fn bytes.
+``HZ_K_SEARCH_MSCAN`` (``SelfScanParams``) scores rows of the corpus, named by ``qid``, against every tile with the
+bf16 MFMA, ``SELF_QB`` queries a workgroup; ``HZ_K_SEARCH_MERGEN`` is the merge for any number of queries over the
+same block.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -19,6 +22,9 @@ import ctypes as C
 from .. import _native as N
 
 MAX_Q, MAX_K = 16, 128  # HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K (csrc/hipzap.h)
+SELF_QB = 64                     # HZ_SEARCH_SELF_QB: queries per workgroup of the self scan
+SELF_MAX_Q = 65535 * SELF_QB     # HZ_SEARCH_SELF_MAX_Q: the self scan's and its merge's limit on Q
+INDEX_SELF_MAX_Q = 1024          # HZ_INDEX_SELF_MAX_Q: ids per hz_index_neighbors call
 
 
 @N.params_of("HZ_K_SEARCH_MERGE")
@@ -89,8 +95,24 @@ class QuantListScanParams(C.Structure):
         return sp
 
 
+@N.params_of("HZ_K_SEARCH_MERGEN")
+@N.params_of("HZ_K_SEARCH_MSCAN")
+class SelfScanParams(C.Structure):
+    """HzSearchSelfParams: ``corpus`` bf16 [N][ldc], ``qid`` device int32 [Q] (the rows that are the queries), the
+    required ``live`` bitmap, ``cand`` [ntile][Q][k] keys, the merge's outputs [Q][k], then the byte counts and shape."""
+    _fields_ = [("corpus", C.c_void_p), ("qid", C.c_void_p), ("live", C.c_void_p), ("cand", C.c_void_p),
+                ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("live_bytes", C.c_uint64), ("cand_bytes", C.c_uint64),
+                ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("ntile", C.c_int),
+                ("skip_self", C.c_int), ("pad_", C.c_int)]
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
+    N._sig(lib, "hz_search_self_scratch_bytes", U64, C.c_longlong, C.c_longlong, C.c_int)
+    N._sig(lib, "hz_search_mscan_launch", C.c_int, C.POINTER(SelfScanParams), P)
+    N._sig(lib, "hz_search_mergen_launch", C.c_int, C.POINTER(SelfScanParams), P)
+    N._sig(lib, "hz_index_neighbors", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P)
+    N._sig(lib, "hz_index_neighbors_max", C.c_int, P, C.c_int)
     N._sig(lib, "hz_search_tile_rows", C.c_int)
     N._sig(lib, "hz_search_scratch_bytes", U64, C.c_longlong, C.c_int, C.c_int)
     N._sig(lib, "hz_search_scan_launch", C.c_int, C.POINTER(SearchParams), P)
@@ -191,3 +213,15 @@ def launch_quant_list(prm: QuantListScanParams, stream: int = 0) -> tuple:
         return rc, None
     sp = prm.merge_params()
     return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def self_scratch_bytes(n: int, q: int, k: int) -> int:
+    """Bytes of candidate scratch a self scan of (N, Q, k) needs; 0 for a refused shape."""
+    return int(N.lib().hz_search_self_scratch_bytes(int(n), int(q), int(k)))
+
+
+def launch_self(prm: SelfScanParams, stream: int = 0) -> tuple:
+    """Self scan then its merge on ``stream``: (scan code, merge code); no merge after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_mscan_launch(C.byref(prm), stream)
+    return rc, (lib.hz_search_mergen_launch(C.byref(prm), stream) if rc == 0 else None)

@@ -66,6 +66,7 @@ FP8_VERSIONS, IVF_VERSIONS, RESCORE_VERSIONS = (VERSION3, VERSION4, VERSION6, VE
 TILE = 256   # HZ_SEARCH_TILE (csrc/hipzap.h): an IVF list starts on a tile boundary
 IVF_MAX_LISTS = 65536
 IVF_SAMPLE = 256  # k-means trains on at most this many rows per centroid
+NEIGHBORS_BLOCK = 1024  # rows per pass of knn_graph: HZ_INDEX_SELF_MAX_Q (csrc/hipzap.h), one native call
 IVF_KEYS = ("centroids_off", "list_off_off", "list_tiles_off", "rowid_off")
 DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3"}  # write_index(dtype=...) -> the header's "dtype"
 FP8 = "fp8_e4m3"
@@ -772,6 +773,30 @@ class _Base:
             raise ValueError(f"nprobe must be an integer in 1..{min(self.ivf['nlist'], MAX_K)}, got {nprobe!r}")
         return check_queries(q, self.dim), int(nprobe)
 
+    def _check_neighbors(self, ids, k):
+        """The refusals of :meth:`neighbors` that both backends share -> (ids int32 [n], k)."""
+        if self.dtype == FP8 or self.ivf is not None:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else f"an {FP8} index"
+            raise ValueError(f"neighbors is built for plain bf16 indexes (versions 1 and 2): this one is {what} of version "
+                             f"{self.version}")
+        if self.dim % 32:
+            raise ValueError(f"neighbors needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
+        return self._check_ids(ids), check_k(k)
+
+    def knn_graph(self, k: int = 10, *, block: int = NEIGHBORS_BLOCK):
+        """The kNN graph of the index: :meth:`neighbors` of every live row (itself excluded), ``block`` rows a pass
+        -> (ids int32 [count, k], scores float32 [count, k]). A deleted row's lists hold -1 / -inf."""
+        if not _is_int(block) or block < 1:
+            raise ValueError(f"block must be a positive integer, got {block!r}")
+        self._check_neighbors([], k)
+        live = np.flatnonzero(self._live_now())
+        ids = np.full((self.count, k), -1, np.int32)
+        scores = np.full((self.count, k), -np.inf, np.float32)
+        for a in range(0, live.size, block):
+            part = live[a:a + block]
+            scores[part], ids[part] = self.neighbors(part, k)
+        return ids, scores
+
     def add(self, vectors, tags=None, labels=None) -> np.ndarray:
         """Append rows (fp32 [n, dim], through :func:`prepare_rows` or, on an fp8 index, :func:`prepare_rows_fp8`:
         the bits ``write_index`` would store) -> their ids, int32 [n]. ``tags``: uint32 [n], default 0.
@@ -905,6 +930,29 @@ class RefIndex(_Base):
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
         return s.astype(np.float32), i
 
+    def neighbors(self, ids, k: int = 10, *, include_self: bool = False):
+        """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]):
+        :func:`search_ref` in fp64 over the stored rows with ``allow`` = live and, unless ``include_self``, not the
+        row itself. Other rows with the same bits stay and tie by id."""
+        ids, k = self._check_neighbors(ids, k)
+        with self._mut:
+            dead = ids[~self._live[ids]]
+            if dead.size:
+                raise ValueError(f"id {int(dead[0])} is deleted")
+            s = np.full((ids.size, k), -np.inf)
+            out = np.full((ids.size, k), -1, np.int32)
+            for a in range(0, ids.size, 256):  # the [n, N] allow matrix, 256 queries at a time
+                part = ids[a:a + 256]
+                allow = np.repeat(self._live[None, :], part.size, axis=0)
+                if not include_self:
+                    allow[np.arange(part.size), part] = False
+                s[a:a + 256], out[a:a + 256] = search_ref(self._rows, self._rows[part], k, allow)
+        return s.astype(np.float32), out
+
+    def _live_now(self) -> np.ndarray:
+        with self._mut:
+            return self._live.copy()
+
     def _append(self, bits, tags, publish):
         first = self.count
         if self.scales is not None:
@@ -1036,6 +1084,42 @@ class Index(_Base):
             if ctx is None:
                 self._free.put(c)
         return scores, ids
+
+    def neighbors(self, ids, k: int = 10, *, include_self: bool = False, ctx: int | None = None):
+        """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]),
+        best first; the row itself is left out unless ``include_self`` (other rows with the same bits stay and tie
+        by id). The rows never leave device memory: one pass is the bf16 MFMA self scan and its merge
+        (DESIGN.md 4s), and ``n`` above the per-pass maximum is split here. A plain bf16 index with
+        ``dim % 32 == 0``; an id outside [0, count) or a deleted id is a ValueError."""
+        ids, k = self._check_neighbors(ids, k)
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        scores = np.empty((ids.size, k), np.float32)
+        out = np.empty((ids.size, k), np.int32)
+        c = self._free.get() if ctx is None else ctx
+        try:
+            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
+            for a in range(0, ids.size, step):
+                part = np.ascontiguousarray(ids[a:a + step])
+                s, i = scores[a:a + step], out[a:a + step]  # contiguous row ranges of the outputs
+                rc = self._lib.hz_index_neighbors(self._h, c, part.ctypes.data, part.size, k, int(not include_self),
+                                                  s.ctypes.data, i.ctypes.data)
+                if rc in (-4, -5, -20, -35, -36, -37):
+                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
+                if rc:
+                    raise RuntimeError(f"hz_index_neighbors failed with code {rc}")
+        finally:
+            if ctx is None:
+                self._free.put(c)
+        return scores, out
+
+    def _live_now(self) -> np.ndarray:
+        with self._mut:
+            n = self.count
+            words = np.empty(-(-n // 32), np.uint32)
+            self._exclusive(lambda: self._lib.hz_index_read_state(self._h, None, None, words.ctypes.data, n),
+                            "hz_index_read_state")
+        return unpack_live(words, n)
 
     def _exclusive(self, call, what):
         """Run a native mutation holding every context token (the caller holds the mutation lock, so no

@@ -9,6 +9,7 @@ Routes (reference: /root/reference/main.py:17-18, 105-112):
                     ``extra.embed`` -> {"model", "dim", "pooling", "normalized", "embeddings", ...}, or a
                     float32 ``.npy`` [n, dim] with ``Accept: application/octet-stream``
   POST /index/add, /index/delete, /index/save   mutate the model's index (``extra.index_writable: true``)
+  POST /index/neighbors   nearest live rows of stored rows of the model's index: {"model", "ids", "k"?, "include_self"?}
   POST /search      nearest rows of the model's vector index (``extra.index``, a ``.hzidx`` file) for the
                     bodies of /embed or ready ``vectors`` -> {"model", "metric", "k", "count", "results", ...},
                     or a structured ``.npy`` [Q, k] (id, score) with ``Accept: application/octet-stream``
@@ -131,7 +132,7 @@ def _error(e):
 def index():
     s = get_server()
     return _json({"service": "hipzap", "version": __version__, "backend": s.backend,
-                  "routes": ["GET /inference", "POST /predict", "POST /embed", "POST /search", "POST /index/add", "POST /index/delete",
+                  "routes": ["GET /inference", "POST /predict", "POST /embed", "POST /search", "POST /index/neighbors", "POST /index/add", "POST /index/delete",
                              "POST /index/save", "GET /health", "GET /metrics"]})
 
 
@@ -572,6 +573,56 @@ def search():
     return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "refine": refine, "k": k,
                   "count": int(index.count), **({"ivf": True, "nprobe": lists or "all"} if index.ivf is not None else {}),
                   "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(ids, scores)],
+                  "timing_ms": round(dt, 3)})
+
+
+@app.route("/index/neighbors", methods=["POST"])
+def index_neighbors():
+    """The ``k`` nearest live rows of stored rows of the model's index (``extra.index``; it only reads, so no
+    ``extra.index_writable``): ``{"model", "ids": [...], "k"?: 10, "include_self"?: false}``. A row is left out of its
+    own list unless ``include_self``. The answer has /search's two shapes: JSON hits (with labels where the index
+    has them) or, with ``Accept: application/octet-stream``, a structured ``.npy`` [n, k] (id, score). 400 with the
+    index's message for an id outside [0, count), a deleted id, k outside 1..128, and an fp8 or IVF index or a
+    ``dim % 32 != 0`` one, for which neighbours are not built."""
+    from ..search import check_k
+    s = get_server()
+    body = request.get_json(force=True, silent=True) or {}
+    model = body.get("model") or request.args.get("model") or "bert-base"
+    k = body.get("k", request.args.get("k", 10))
+    if isinstance(k, str) and k.lstrip("-").isdigit():
+        k = int(k)
+    k = check_k(k)
+    ids = body.get("ids")
+    if not isinstance(ids, list) or not ids or not all(isinstance(i, int) and not isinstance(i, bool) for i in ids):
+        raise ValueError("ids must be a non-empty list of integers")
+    include_self = body.get("include_self", False)
+    if not isinstance(include_self, bool):
+        raise ValueError(f"include_self must be true or false, got {include_self!r}")
+    if not s.spec(model).extra.get("index"):
+        raise ValueError(f'{model} is served without extra.index: set "index": "<path or artifact key>" in its '
+                         f"settings block (hipzap index writes one)")
+    backend = _embedding_backend(s, model)
+    index = s.index(model, backend)
+    t0 = time.perf_counter()
+    with phase("search"):
+        scores, near = index.neighbors(ids, k, include_self=include_self)  # ValueError -> 400
+    dt = (time.perf_counter() - t0) * 1e3
+    if "application/octet-stream" in request.headers.get("Accept", ""):
+        out = np.empty(near.shape, dtype=[("id", "<i4"), ("score", "<f4")])
+        out["id"], out["score"] = near, scores
+        buf = io.BytesIO()
+        np.save(buf, out, allow_pickle=False)
+        return Response(response=buf.getvalue(), status=200, mimetype="application/octet-stream")
+    labels = index.labels
+
+    def hit(i, sc):
+        h = {"id": int(i), "score": float(sc) if np.isfinite(sc) else None}
+        if labels is not None and i >= 0:
+            h["label"] = labels[i]
+        return h
+    return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "k": k,
+                  "include_self": include_self, "count": int(index.count), "ids": ids,
+                  "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(near, scores)],
                   "timing_ms": round(dt, 3)})
 
 
