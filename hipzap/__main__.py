@@ -123,9 +123,11 @@ def cmd_index(a):
             raise SystemExit("index: --from-index takes only --dtype, --rescore, --ivf with --nprobe / --ivf-seed, and --out")
         if a.ivf is None and (a.nprobe is not None or a.ivf_seed is not None):
             raise SystemExit("index: --nprobe and --ivf-seed go with --ivf NLIST")
+        if a.ivf is None and a.ivf_backend != "cpu":
+            raise SystemExit("index: --ivf-backend goes with --ivf NLIST")
         try:
             hdr = convert_index(a.from_index, a.out, a.dtype, rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe,
-                                ivf_seed=a.ivf_seed or 0)
+                                ivf_seed=a.ivf_seed or 0, ivf_backend=a.ivf_backend, device=a.device)
         except ValueError as e:
             raise SystemExit(f"index: {e}") from None
         print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": "labels" in hdr}))
@@ -158,18 +160,21 @@ def cmd_index(a):
     tags = np.load(a.tags, allow_pickle=False) if a.tags else None
     if a.ivf is None and (a.nprobe is not None or a.ivf_seed is not None):
         raise SystemExit("index: --nprobe and --ivf-seed go with --ivf NLIST")
+    if a.ivf is None and a.ivf_backend != "cpu":
+        raise SystemExit("index: --ivf-backend goes with --ivf NLIST")
     if a.ivf is not None and a.dtype == "fp8":  # the lists are trained on the bf16 rows, which are then quantised
         tmp = a.out + ".bf16-ivf.tmp"
         try:
             write_index(tmp, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, ivf=a.ivf,
-                        nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
+                        nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0, ivf_backend=a.ivf_backend, device=a.device)
             hdr = convert_index(tmp, a.out, "fp8", rescore=a.rescore)
         finally:
             if os.path.exists(tmp):
                 os.remove(tmp)
     else:
         hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
-                          rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0)
+                          rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0,
+                          ivf_backend=a.ivf_backend, device=a.device)
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
@@ -227,6 +232,25 @@ def cmd_knn(a):
         np.savez(f, ids=ids, scores=scores)
     print(json.dumps({"index": a.index, "out": a.out, "count": int(ids.shape[0]), "k": a.k, "backend": a.backend,
                       "rows_with_neighbors": int((ids[:, 0] >= 0).sum())}))
+
+
+def cmd_cluster(a):
+    """k-means over the live rows of a plain bf16 index -> an .npz with ``centroids`` uint16 [k, dim] (bf16 bits),
+    ``assign`` int32 [count] and ``score`` float32 [count] (-1 / -inf for a deleted row)."""
+    import numpy as np
+
+    from .search import open_index
+    try:
+        with open_index(a.index, a.backend, a.device) as ix:
+            cent, assign, score = ix.cluster(a.k, iters=a.iters, seed=a.seed)
+    except ValueError as e:
+        sys.exit(f"hipzap cluster: {e}")
+    with open(a.out, "wb") as f:
+        np.savez(f, centroids=cent, assign=assign, score=score)
+    sizes = np.bincount(assign[assign >= 0], minlength=a.k)
+    print(json.dumps({"index": a.index, "out": a.out, "count": int(assign.size), "k": a.k, "iters": a.iters, "seed": a.seed,
+                      "backend": a.backend, "clustered_rows": int((assign >= 0).sum()), "empty_clusters": int((sizes == 0).sum()),
+                      "largest_cluster": int(sizes.max())}))
 
 
 def cmd_bench(a, rest):
@@ -302,6 +326,8 @@ def main(argv=None):
                          "into NLIST k-means lists; a search scans the --nprobe lists nearest to the query")
     ix.add_argument("--nprobe", type=int, default=None, help="with --ivf: the lists a search scans by default (min(NLIST, 16))")
     ix.add_argument("--ivf-seed", type=int, default=None, help="with --ivf: the k-means seed (0)")
+    ix.add_argument("--ivf-backend", choices=["cpu", "gpu"], default="cpu",
+                    help="with --ivf: where k-means runs; gpu: Index.cluster on --device (dim %% 32 == 0)")
     ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept); an IVF file keeps its lists "
                          "(versions 6 and 7), --ivf NLIST builds lists over a plain file's stored rows")
     ix.add_argument("--model", default=None, help="free text kept in the header")
@@ -314,6 +340,14 @@ def main(argv=None):
     kn.add_argument("--backend", choices=["gpu", "cpu"], default="gpu")
     kn.add_argument("--block", type=int, default=None, help="rows per pass (default 1024)")
     kn.add_argument("--device", type=int, default=0)
+    cl = sub.add_parser("cluster", help="k-means over the live rows of a plain bf16 .hzidx (dim %% 32 == 0)")
+    cl.add_argument("index", help="a .hzidx file")
+    cl.add_argument("--k", type=int, required=True, help="the number of clusters")
+    cl.add_argument("--iters", type=int, default=10)
+    cl.add_argument("--seed", type=int, default=0)
+    cl.add_argument("--backend", choices=["gpu", "cpu"], default="gpu")
+    cl.add_argument("--device", type=int, default=0)
+    cl.add_argument("--out", required=True, help="an .npz: centroids uint16 [k, dim], assign int32 [count], score float32 [count]")
     inf = sub.add_parser("info")
     inf.add_argument("path", nargs="?", default=None, help="a .hzidx file: print its header")
     sub.add_parser("bench", add_help=False)
@@ -321,7 +355,7 @@ def main(argv=None):
     if args.cmd == "bench":
         return cmd_bench(args, rest)
     {"serve": cmd_serve, "pack": cmd_pack, "plan": cmd_plan, "tune": cmd_tune, "upload": cmd_upload, "info": cmd_info,
-     "index": cmd_index, "knn": cmd_knn}[args.cmd](args)
+     "index": cmd_index, "knn": cmd_knn, "cluster": cmd_cluster}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -581,6 +581,65 @@ int hz_search_mscan_launch(const HzSearchSelfParams* p, hipStream_t st);
 // cand [ntile][Q][k] -> out_score / out_id [Q][k]. Reads cand, out_*, N, Q, k and cand_bytes of the block only.
 // Refusals: -50 cand, out_score or out_id null; -55; -56; -57; -58 cand not 8-B or out_* not 4-B aligned; -60.
 int hz_search_mergen_launch(const HzSearchSelfParams* p, hipStream_t st);
+// nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
+// of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
+// of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
+// map and load schedule of HZ_K_SEARCH_MSCAN). Each row keeps one running best key (orderable(score) << 32) | ~c,
+// the scan's total order: the highest score wins and, among centroids of equal score bits, the lowest index. After
+// the last block the row's key is reduced over its four lanes and written: out_list[r] = c, out_score[r] = the score.
+// No atomics, no scratch. `live` is ANY bitmap (the index passes live AND a sample mask): a row whose bit is 0
+// writes out_list = -1, out_score = -inf; a group of 16 rows with no set bit is neither loaded nor multiplied; a
+// dead row of a mixed group is loaded and its column of the product is dropped, so what it holds (NaN patterns
+// included) reaches no other row. Rows from N on are not read and not written.
+// CONTRACT: score(c, r) is the fp32 accumulator of the MFMAs over columns 0..31, 32..63, ... in that order,
+// starting from +0, centroid c being the A operand and row r the B operand: HZ_K_SEARCH_MSCAN's statement. Its bits
+// depend on the D values of the centroid and of the row only: not on N, C, the centroid's index or block, the row's
+// tile or position, or the other bits of `live`. They are therefore HZ_K_SEARCH_MSCAN's bits for the same two
+// D-vectors. Replays are bitwise equal. (out_score is +0.0 where the accumulator is -0.0, as in every search kind.)
+// Refusals (nothing is launched): -61 corpus, cent, live, out_list or out_score null; -62 D % 32; -63 D < 32;
+// -64 D > 2048; -65 ldc or ldk < D or not a multiple of 8; -66 N < 1; -67 C outside 1..HZ_SEARCH_ASSIGN_MAX_C;
+// -68 corpus or cent not 16-B, live, out_list or out_score not 4-B aligned; -69 live_bytes < 4 * ceil(N / 32).
+#define HZ_SEARCH_ASSIGN_CB 64
+#define HZ_SEARCH_ASSIGN_MAX_C 65536  // IVF_MAX_LISTS of hipzap/search.py
+typedef struct HzSearchAssignParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows
+  const unsigned short* cent;    // bf16 [C][ldk], 16-B aligned rows
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5 (required)
+  int* out_list;                 // int32 [N]
+  float* out_score;              // fp32 [N]
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  int N, D, C, ldc, ldk;
+  int ntile;                     // filled by the launcher: ceil(N / HZ_SEARCH_TILE)
+} HzSearchAssignParams;
+int hz_search_assign_launch(const HzSearchAssignParams* p, hipStream_t st);
+// the k-means update step (HZ_K_SEARCH_CMEAN): workgroup c replaces centroid c by the mean of the rows
+// order[seg_off[c] .. seg_off[c + 1]). A member id outside [0, N) is skipped before any address is formed and does
+// not count; a segment with no counted member, or whose bounds are not 0 <= seg_off[c] <= seg_off[c + 1] <= M, writes
+// nothing (the centroid keeps its value). With `cosine` the mean is then divided by max(||mean||, 1e-12).
+// cent32[c] (when not null) is the fp32 result, cent[c] its round-to-nearest-even bf16 bits.
+// SUMMATION ORDER, a function of (member position, D) alone, no atomics: with nch = D / 8 and G = 256 / nch (integer
+// division, 1..64), thread t < G * nch owns the 8 columns 8 * (t % nch) .. + 7 and the members at positions g, g + G,
+// g + 2G, ... of the segment (g = t / nch), which it adds in that order to one fp32 sum per column starting from +0
+// (a bf16 value widens exactly; a skipped member adds nothing). Column d's sum is then partial[0][d] + partial[1][d] +
+// ... + partial[G - 1][d] in that order, divided by (float)count. ||mean||^2: thread t adds mean[d]^2 over d = t,
+// t + 256, ... ascending from +0; the 64 lanes of a wave are summed by the xor butterfly 32, 16, .., 1 and the four
+// waves' sums added in wave order. The bits of centroid c therefore depend on its own segment's rows and order only:
+// not on C, on c or on the other segments.
+// Refusals: -70 corpus, order, seg_off or cent null; -71 D % 32; -72 D < 32; -73 D > 2048; -74 ldc or ldk < D or
+// not a multiple of 8; -75 N < 1; -76 C outside 1..HZ_SEARCH_ASSIGN_MAX_C; -77 M < 0; -78 corpus or cent not 16-B,
+// order, seg_off or cent32 not 4-B aligned; -79 cosine not 0 or 1. seg_off and order live in device memory and are
+// not checkable by the launcher: the kernel bounds every value it reads from them as stated above, and
+// hz_index_cmean validates both on the host before the upload.
+typedef struct HzSearchCmeanParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows
+  const int* order;              // device int32 [M]: the row ids of all members, cluster after cluster
+  const int* seg_off;            // device int32 [C + 1]
+  unsigned short* cent;          // bf16 [C][ldk], in and out
+  float* cent32;                 // fp32 [C][D], out; may be null
+  int N, D, C, M, ldc, ldk;
+  int cosine, pad_;
+} HzSearchCmeanParams;
+int hz_search_cmean_launch(const HzSearchCmeanParams* p, hipStream_t st);
 int hz_search_code_warm(void);
 
 // an open .hzidx index (csrc/index.cpp): the bf16 row block in device memory plus `nctx` search contexts
@@ -682,6 +741,23 @@ int hz_index_describe3(void* idx, uint64_t* out);
 int hz_index_neighbors(void* idx, int ctx, const int* ids, int n, int k, int skip_self, float* out_score, int* out_id);
 // the ids one hz_index_neighbors call takes; set in 1..HZ_INDEX_SELF_MAX_Q lowers or restores it first (0: only read)
 int hz_index_neighbors_max(void* idx, int set);
+// clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
+// context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
+// and grown on demand (a call that needs no more than an earlier one allocates nothing).
+// hz_index_assign: the nearest of the C centroids `cent_bits` (bf16 [C][dim]) for every row -> out_list int32
+// [count], out_score fp32 [count]. `mask_words` (null: every row) holds one bit per row, ceil(count / 32) words; a
+// row takes part iff it is live and its mask bit is set, every other row gets -1 / -inf. Uploads the centroids and
+// live AND mask, launches HZ_K_SEARCH_ASSIGN over the filtered programs' N, copies both arrays back.
+// hz_index_cmean: centroid c becomes the mean of the rows order[seg_off[c] .. seg_off[c + 1]) (divided by its norm on
+// a cosine index), an empty segment keeps its value: HZ_K_SEARCH_CMEAN over `cent_bits_inout`; `cent32_out` (may be
+// null) receives the fp32 values [C][dim], untouched where the segment is empty.
+// -38: an fp8 or an IVF index; -39: dim % 32; -40: C outside 1..HZ_SEARCH_ASSIGN_MAX_C; -41: M outside [0, 2^31);
+// -42: seg_off not 0 = seg_off[0] <= ... <= seg_off[C] = M; -43: a member id outside [0, count)
+// (hz_index_last_error names the value in each case).
+int hz_index_assign(void* idx, int ctx, const unsigned short* cent_bits, int C, const unsigned* mask_words, int* out_list,
+                    float* out_score);
+int hz_index_cmean(void* idx, int ctx, const int* order, long long M, const int* seg_off, int C,
+                   unsigned short* cent_bits_inout, float* cent32_out);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -868,7 +944,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_QLSCAN, 37, HzSearchQuantListParams, hz_search_qlscan_op, SEARCH) \
   X(POOL_NORM, 38, HzPoolNormParams, hz_pool_norm_op, VISION)               \
   X(SEARCH_MSCAN, 39, HzSearchSelfParams, hz_search_mscan_op, SEARCH)     \
-  X(SEARCH_MERGEN, 40, HzSearchSelfParams, hz_search_mergen_op, SEARCH)
+  X(SEARCH_MERGEN, 40, HzSearchSelfParams, hz_search_mergen_op, SEARCH)   \
+  X(SEARCH_ASSIGN, 41, HzSearchAssignParams, hz_search_assign_op, SEARCH) \
+  X(SEARCH_CMEAN, 42, HzSearchCmeanParams, hz_search_cmean_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

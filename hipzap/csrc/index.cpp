@@ -93,6 +93,12 @@ struct Ctx {
   char* nout_host = nullptr;
   unsigned long long* ncand = nullptr;
   uint64_t ncand_bytes = 0;
+  // clustering only (hz_index_assign / hz_index_cmean), device memory allocated on first use and grown on demand:
+  // centroids bf16 [C][dim]; live AND mask, cap / 8 bytes; lists int32 then scores fp32, [scan rows] each; the
+  // members int32 [M]; seg_off int32 [C + 1]; the fp32 centroids [C][dim]
+  enum { kClCent, kClMask, kClOut, kClOrder, kClSeg, kClCent32, kClBufs };
+  void* cl[kClBufs] = {};
+  uint64_t cl_bytes[kClBufs] = {};
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
   // probes alone; neighbours: (n, k, 3, skip_self, 0)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
@@ -166,6 +172,8 @@ struct Index {
       if (c->nid_dev) (void)hipFree(c->nid_dev);
       if (c->nout_dev) (void)hipFree(c->nout_dev);
       if (c->ncand) (void)hipFree(c->ncand);
+      for (void* b : c->cl)
+        if (b) (void)hipFree(b);
       if (c->st) (void)hipStreamDestroy(c->st);
     }
     free_rescore(rrows);
@@ -752,6 +760,7 @@ int hz_index_describe(void* h, uint64_t* out) {
     progs += c->progs.size();
     dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf + (c->mid_dev ? 2 * kOutHalf : 0);
     dev += c->ncand_bytes + (c->nid_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 + 2 * kSelfOutHalf : 0);  // neighbours, once used
+    for (const uint64_t b : c->cl_bytes) dev += b;  // clustering, once used
   }
   const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
   std::memcpy(out, v, sizeof(v));
@@ -924,6 +933,125 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
     if (!rc) rc = (int)hipStreamSynchronize(c.st);
   }
   return rc;
+}
+
+namespace {
+
+// a clustering buffer of a context of at least `need` bytes: kept when large enough, else replaced (the caller
+// holds c.mu and nothing is in flight on c.st)
+void* cl_buffer(Ctx& c, int which, uint64_t need) {
+  if (need <= c.cl_bytes[which] && c.cl[which]) return c.cl[which];
+  if (c.cl[which]) (void)hipFree(c.cl[which]);
+  c.cl[which] = nullptr, c.cl_bytes[which] = 0;
+  if (hipMalloc(&c.cl[which], need) != hipSuccess) return nullptr;
+  c.cl_bytes[which] = need;
+  return c.cl[which];
+}
+
+// what both clustering calls refuse: -9 the context, -38 an fp8 or an IVF index, -39 dim % 32, -40 C
+int cluster_check(const Index* x, int ctx, int C, const char* call) {
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (x->fp8 || x->ivf) {
+    g_err = std::string("index: ") + call + " is built for plain bf16 indexes (versions 1 and 2), this one is " +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : "an fp8_e4m3 index") + " of version " +
+            std::to_string(x->h.version);
+    return -38;
+  }
+  if (x->h.dim % 32) {
+    g_err = std::string("index: ") + call + " needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -39;
+  }
+  if (C < 1 || C > HZ_SEARCH_ASSIGN_MAX_C) {
+    g_err = "index: the number of centroids must be in 1.." + std::to_string(HZ_SEARCH_ASSIGN_MAX_C) + ", got " + std::to_string(C);
+    return -40;
+  }
+  return 0;
+}
+
+}  // namespace
+
+int hz_index_assign(void* h, int ctx, const unsigned short* cent_bits, int C, const unsigned* mask_words, int* out_list,
+                    float* out_score) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !cent_bits || !out_list || !out_score) return -1;
+  if (const int rc = cluster_check(x, ctx, C, "assign")) return rc;
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // count and the bitmap mirror change only under every context's mutex
+  if (x->count < 1) return 0;
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  const uint64_t n = x->scan_rows(), dim = x->h.dim, words = x->cap / 32, used = (x->count + 31) / 32;
+  void* cent = cl_buffer(c, Ctx::kClCent, (uint64_t)C * dim * 2);
+  void* mask = cl_buffer(c, Ctx::kClMask, words * 4);
+  void* out = cl_buffer(c, Ctx::kClOut, n * 8);
+  if (!cent || !mask || !out) return -11;
+  std::vector<uint32_t> bits(words, 0u);  // live AND mask; the rows from count on stay dead
+  for (uint64_t i = 0; i < used; ++i) bits[i] = x->live_host[i] & (mask_words ? mask_words[i] : ~0u);
+  HzSearchAssignParams p{};
+  p.corpus = x->rows;
+  p.cent = static_cast<const unsigned short*>(cent);
+  p.live = static_cast<const unsigned*>(mask);
+  p.out_list = static_cast<int*>(out);
+  p.out_score = reinterpret_cast<float*>(static_cast<char*>(out) + n * 4);
+  p.live_bytes = words * 4;
+  p.N = (int)n, p.D = p.ldc = p.ldk = (int)dim, p.C = C;
+  int rc = (int)hipMemcpyAsync(cent, cent_bits, (uint64_t)C * dim * 2, hipMemcpyHostToDevice, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(mask, bits.data(), words * 4, hipMemcpyHostToDevice, c.st);
+  if (!rc) rc = hz_launch_kernel(HZ_K_SEARCH_ASSIGN, &p, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(out_list, p.out_list, x->count * 4, hipMemcpyDeviceToHost, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(out_score, p.out_score, x->count * 4, hipMemcpyDeviceToHost, c.st);
+  const int rs = (int)hipStreamSynchronize(c.st);  // `bits` and the caller's arrays are in use until here
+  return rc ? rc : rs;
+}
+
+int hz_index_cmean(void* h, int ctx, const int* order, long long M, const int* seg_off, int C, unsigned short* cent_bits_inout,
+                   float* cent32_out) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !seg_off || !cent_bits_inout || (!order && M > 0)) return -1;
+  if (const int rc = cluster_check(x, ctx, C, "cmean")) return rc;
+  if (M < 0 || M >= (1ll << 31)) {
+    g_err = "index: the number of members must be in [0, 2^31), got " + std::to_string(M);
+    return -41;
+  }
+  for (int i = 0; i <= C; ++i) {
+    const long long lo = i ? seg_off[i - 1] : 0, want_hi = M;
+    if (seg_off[i] < lo || seg_off[i] > want_hi || (i == 0 && seg_off[0] != 0) || (i == C && seg_off[C] != M)) {
+      g_err = "index: seg_off must run 0 = seg_off[0] <= ... <= seg_off[C] = " + std::to_string(M) + ", got seg_off[" +
+              std::to_string(i) + "] = " + std::to_string(seg_off[i]);
+      return -42;
+    }
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);
+  for (long long i = 0; i < M; ++i)
+    if (order[i] < 0 || (uint64_t)order[i] >= x->count) {
+      g_err = "index: member id " + std::to_string(order[i]) + " is outside [0, " + std::to_string(x->count) + ")";
+      return -43;
+    }
+  if (M == 0) return 0;  // every segment is empty: every centroid keeps its value
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  const uint64_t dim = x->h.dim;
+  void* cent = cl_buffer(c, Ctx::kClCent, (uint64_t)C * dim * 2);
+  void* ord = cl_buffer(c, Ctx::kClOrder, (uint64_t)M * 4);
+  void* seg = cl_buffer(c, Ctx::kClSeg, ((uint64_t)C + 1) * 4);
+  void* c32 = cent32_out ? cl_buffer(c, Ctx::kClCent32, (uint64_t)C * dim * 4) : nullptr;
+  if (!cent || !ord || !seg || (cent32_out && !c32)) return -11;
+  HzSearchCmeanParams p{};
+  p.corpus = x->rows;
+  p.order = static_cast<const int*>(ord);
+  p.seg_off = static_cast<const int*>(seg);
+  p.cent = static_cast<unsigned short*>(cent);
+  p.cent32 = static_cast<float*>(c32);
+  p.N = (int)x->count, p.D = p.ldc = p.ldk = (int)dim, p.C = C, p.M = (int)M;
+  p.cosine = x->h.metric == 0 ? 1 : 0;
+  int rc = (int)hipMemcpyAsync(cent, cent_bits_inout, (uint64_t)C * dim * 2, hipMemcpyHostToDevice, c.st);
+  if (!rc && c32) rc = (int)hipMemcpyAsync(c32, cent32_out, (uint64_t)C * dim * 4, hipMemcpyHostToDevice, c.st);  // an empty segment keeps the caller's values
+  if (!rc) rc = (int)hipMemcpyAsync(ord, order, (uint64_t)M * 4, hipMemcpyHostToDevice, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(seg, seg_off, ((uint64_t)C + 1) * 4, hipMemcpyHostToDevice, c.st);
+  if (!rc) rc = hz_launch_kernel(HZ_K_SEARCH_CMEAN, &p, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(cent_bits_inout, cent, (uint64_t)C * dim * 2, hipMemcpyDeviceToHost, c.st);
+  if (!rc && c32) rc = (int)hipMemcpyAsync(cent32_out, c32, (uint64_t)C * dim * 4, hipMemcpyDeviceToHost, c.st);
+  const int rs = (int)hipStreamSynchronize(c.st);
+  return rc ? rc : rs;
 }
 
 int hz_index_search_filtered(void* h, int ctx, const float* queries, const unsigned* filt, int Q, int k, float* out_score,

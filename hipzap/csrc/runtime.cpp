@@ -468,6 +468,14 @@ extern "C" __attribute__((weak)) int hz_search_mergen_launch(const HzSearchSelfP
 static int hz_search_mergen_op(const HzSearchSelfParams* p, hipStream_t st) {
   return hz_search_mergen_launch ? hz_search_mergen_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_assign_launch(const HzSearchAssignParams* p, hipStream_t st);
+static int hz_search_assign_op(const HzSearchAssignParams* p, hipStream_t st) {
+  return hz_search_assign_launch ? hz_search_assign_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_cmean_launch(const HzSearchCmeanParams* p, hipStream_t st);
+static int hz_search_cmean_op(const HzSearchCmeanParams* p, hipStream_t st) {
+  return hz_search_cmean_launch ? hz_search_cmean_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -11,7 +11,9 @@
 //   * search_mscan — the self scan (kind MSCAN): the queries are rows of the corpus named by id; workgroup (tile, block
 //                    of 64 queries) scores them with the bf16 MFMA and cuts before it ranks. Kind MERGEN is
 //                    search_merge behind a launcher that takes any number of queries
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s for the reasoning.
+//   * search_assign — the nearest centroid of every row (kind ASSIGN): the self scan with the roles turned, a running
+//                    top-1 key per row; search_cmean (kind CMEAN): a cluster's mean in a fixed summation order
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -812,6 +814,233 @@ __global__ __launch_bounds__(T) void search_mscan_kernel(const HzSearchSelfParam
   }
 }
 
+// ------------------------------------------------------------------------- nearest centroid, means
+// search_assign_kernel (HZ_K_SEARCH_ASSIGN): the self scan with the roles turned. Workgroup `tile`
+// scores its T rows against all C centroids, CB at a time: the A operand is the centroid block (every workgroup
+// re-reads the same C rows, which stay in L2; nothing is staged), the B operand the tile's rows. Wave w owns rows
+// w*64 .. w*64+63 as four groups of 16; the fragment map, the k-step pairs and their two-pairs-ahead schedule are
+// search_mscan_kernel's, so acc = mfma_f32_16x16x32_bf16(centroid fragment, row fragment, acc) over the columns
+// 32s .. 32s+31, s ascending, from +0, are that kernel's bits for the same two D-vectors (CONTRACT, hipzap.h).
+// A group of 16 centroids from C on is not multiplied (a scalar branch); a centroid from C on inside a mixed group
+// loads zeros and is left out of the selection.
+// Selection: after a block lane (lr, lh) holds score(c0 + i*16 + lh*4 + e, row j*16 + lr) in acc[i][j][e]; it folds
+// the 16 keys (orderable(score) << 32) | ~c of each row group into the group's running key, 4 keys a lane. After
+// the last block the four lanes lh = 0..3 of a row are reduced with two xor shuffles and lane lh == 0 writes.
+// Which rows: as in the self scan (live words staged with the bits from N on cleared; a group with no bit set is
+// neither loaded nor multiplied; a dead row of a mixed group is loaded, its column dropped). Every row < N of the
+// tile is written: a row without its bit gets -1 / -inf.
+// Addresses: cent[c*ldk + ..] under c < C; the tile's rows under row < N; live words [row0/32, row0/32 + 8) under
+// word*32 < N (the launcher checks live_bytes); out_list / out_score [row0 + r] under row0 + r < N.
+constexpr int CB = HZ_SEARCH_ASSIGN_CB;
+static_assert(CB == 64 && T == 256, "the fragment map below");
+
+__global__ __launch_bounds__(T) void search_assign_kernel(const HzSearchAssignParams p) {
+  __shared__ unsigned lv[T / 32];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int tile = blockIdx.x;
+  if (!HZ_DCHECK(tile < p.ntile && (long)tile * T < (long)p.N && p.D >= 32 && p.D % 32 == 0 && p.D <= 2048 && p.ldc >= p.D &&
+                 p.ldk >= p.D && p.C >= 1 && p.C <= HZ_SEARCH_ASSIGN_MAX_C))
+    return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  if (t < T / 32) {
+    const long word = (row0 >> 5) + t;
+    unsigned v = 0u;
+    if (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)p.live_bytes)) v = p.live[word];
+    const int left = rows - t * 32;  // the tile's rows from this word on
+    if (left < 32) v &= left <= 0 ? 0u : (1u << left) - 1u;
+    lv[t] = v;
+  }
+  __syncthreads();
+
+  const int lr = lane & 15, lh = lane >> 4;
+  unsigned gm[4], any = 0u;  // the bits of this wave's four row groups (wave-uniform)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int g = w * 4 + j;
+    gm[j] = (__builtin_amdgcn_readfirstlane(lv[g >> 1]) >> ((g & 1) * 16)) & 0xffffu;
+    any |= gm[j];
+  }
+  unsigned long long best[4] = {0ull, 0ull, 0ull, 0ull};  // per row group: this lane's best key so far
+  if (any != 0u) {
+    const bf16_t* brow[4];
+    bool bok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = w * 64 + j * 16 + lr;
+      bok[j] = gm[j] != 0u && r < rows && HZ_DCHECK(row0 + r < (long)p.N);
+      brow[j] = p.corpus + (row0 + (bok[j] ? r : 0)) * p.ldc + lh * 8;
+    }
+    const int nk = p.D >> 5;
+    for (int c0 = 0; c0 < p.C; c0 += CB) {  // block-uniform
+      const bf16_t* arow[4];
+      bool aok[4], gok[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = c0 + i * 16 + lr;
+        gok[i] = c0 + i * 16 < p.C;  // wave-uniform: the group holds a centroid
+        aok[i] = c < p.C && HZ_DCHECK(c >= 0 && c < p.C);
+        arow[i] = p.cent + (long)(aok[i] ? c : 0) * p.ldk + lh * 8;
+      }
+      f32x4 acc[4][4];  // [centroid group][row group]
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      bf16x8 a[2][2][4], b[2][2][4];  // [buffer][k-step of the pair][group]
+      auto load = [&](int buf, int kk) {  // the k-steps kk and kk + 1 (columns under D: kk*32 + lh*8 + 8 <= D)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            a[buf][s][i] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+            b[buf][s][i] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+            if (kk + s < nk) {
+              if (aok[i]) a[buf][s][i] = *reinterpret_cast<const bf16x8*>(arow[i] + (kk + s) * 32);
+              if (bok[i]) b[buf][s][i] = *reinterpret_cast<const bf16x8*>(brow[i] + (kk + s) * 32);
+            }
+          }
+      };
+      auto mma = [&](int buf, int kk) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          if (kk + s < nk) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (gm[j] != 0u) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                  if (gok[i])
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[buf][s][i], b[buf][s][j], acc[i][j], 0, 0, 0);
+              }
+          }
+      };
+      load(0, 0);
+      for (int kk = 0; kk < nk; kk += 4) {  // two pairs per trip, so the buffer index is a constant
+        if (kk + 2 < nk) load(1, kk + 2);
+        mma(0, kk);
+        if (kk + 4 < nk) load(0, kk + 4);
+        if (kk + 2 < nk) mma(1, kk + 2);
+      }
+      // lane holds score(c0 + i*16 + lh*4 + e, row w*64 + j*16 + lr) in acc[i][j][e]
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = c0 + i * 16 + lh * 4 + e;
+          if (c < p.C) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const unsigned long long key = ((unsigned long long)orderable(acc[i][j][e]) << 32) | (unsigned)~(unsigned)c;
+              best[j] = key > best[j] ? key : best[j];
+            }
+          }
+        }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    unsigned long long k = best[j];
+    const unsigned long long k1 = __shfl_xor(k, 16);
+    k = k1 > k ? k1 : k;
+    const unsigned long long k2 = __shfl_xor(k, 32);
+    k = k2 > k ? k2 : k;
+    const int r = w * 64 + j * 16 + lr;
+    if (lh == 0 && r < rows && HZ_DCHECK(row0 + r < (long)p.N)) {
+      const bool pass = ((gm[j] >> lr) & 1u) != 0u && k != 0ull;
+      p.out_list[row0 + r] = pass ? (int)~(unsigned)k : -1;
+      p.out_score[row0 + r] = pass ? unorderable((unsigned)(k >> 32)) : -__builtin_inff();
+    }
+  }
+}
+
+// search_cmean_kernel (HZ_K_SEARCH_CMEAN): workgroup c, the mean of the rows order[seg_off[c] ..
+// seg_off[c + 1]). SUMMATION ORDER (hipzap.h): nch = D / 8 chunks of 8 columns, G = 256 / nch member lanes; thread
+// (g, chunk) adds the members at positions g, g + G, ... in that order (four loads in flight, added in position
+// order), the G partials of a column are added in g order, then one division by the count.
+// Addresses: seg_off[c], seg_off[c + 1] under c < C; order[i] under lo <= i < hi with 0 <= lo <= hi <= M;
+// corpus[id*ldc + ..] under (unsigned)id < N; cent / cent32 [c][d] under c < C and d < D.
+constexpr int CMEAN_THREADS = 256;
+constexpr int CMEAN_UNROLL = 4;
+
+__global__ __launch_bounds__(CMEAN_THREADS) void search_cmean_kernel(const HzSearchCmeanParams p) {
+  __shared__ float part[CMEAN_THREADS * 8];  // [G][D]: G * D = (256 / nch) * nch * 8 <= 2048
+  __shared__ float wsum[4];
+  const int t = threadIdx.x, c = blockIdx.x;
+  if (!HZ_DCHECK(c < p.C && p.D >= 32 && p.D % 32 == 0 && p.D <= 2048 && p.ldc >= p.D && p.ldk >= p.D)) return;
+  const int lo = p.seg_off[c], hi = p.seg_off[c + 1];
+  if (lo < 0 || hi < lo || hi > p.M) return;  // block-uniform: not a segment of `order`
+  const int m = hi - lo;
+  int count = 0;  // the members inside [0, N)
+  for (int base = 0; base < m; base += CMEAN_THREADS) {
+    const int i = base + t;
+    count += __syncthreads_count(i < m && (unsigned)p.order[lo + i] < (unsigned)p.N);
+  }
+  if (count == 0) return;  // block-uniform
+  const int nch = p.D >> 3, G = CMEAN_THREADS / nch;
+  const int g = t / nch, chunk = t - g * nch;
+  if (g < G) {
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = g; i < m; i += G * CMEAN_UNROLL) {
+      u32x4 v[CMEAN_UNROLL];
+      bool ok[CMEAN_UNROLL];
+#pragma unroll
+      for (int u = 0; u < CMEAN_UNROLL; ++u) {
+        const int at = i + u * G;
+        int id = -1;
+        if (at < m && HZ_DCHECK(lo + at < p.M)) id = p.order[lo + at];
+        ok[u] = (unsigned)id < (unsigned)p.N;
+        v[u] = u32x4{0u, 0u, 0u, 0u};
+        if (ok[u]) v[u] = *reinterpret_cast<const u32x4*>(p.corpus + (long)id * p.ldc + chunk * 8);
+      }
+#pragma unroll
+      for (int u = 0; u < CMEAN_UNROLL; ++u)
+        if (ok[u]) {
+          float f[8];
+          unpack8(v[u], f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s[e] += f[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[g * p.D + chunk * 8 + e] = s[e];
+  }
+  __syncthreads();
+  float mean[8];  // columns t, t + 256, ...
+  float ss = 0.f;
+  const float n = (float)count;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int d = t + u * CMEAN_THREADS;
+    mean[u] = 0.f;
+    if (d < p.D) {
+      float v = part[d];
+      for (int gg = 1; gg < G; ++gg) v += part[gg * p.D + d];
+      mean[u] = v / n;
+      ss += mean[u] * mean[u];
+    }
+  }
+  float inv = 1.f;
+  if (p.cosine) {  // block-uniform
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+    if ((t & 63) == 0) wsum[t >> 6] = ss;
+    __syncthreads();
+    const float tot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    inv = fmaxf(sqrtf(tot), 1e-12f);
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int d = t + u * CMEAN_THREADS;
+    if (d < p.D && HZ_DCHECK(c < p.C)) {
+      const float v = p.cosine ? mean[u] / inv : mean[u];
+      if (p.cent32) p.cent32[(long)c * p.D + d] = v;
+      p.cent[(long)c * p.ldk + d] = f2bf(v);
+    }
+  }
+}
+
 // one refusal list for both launchers: the kernels then have no address that the data can move out of
 // its buffer. Fills ntile. `need`: the bytes `cand` must hold, 0 for the scan's hz_search_scratch_bytes(N, Q, k).
 int search_check(HzSearchParams& p, unsigned long long need = 0) {
@@ -1060,6 +1289,44 @@ extern "C" int hz_search_mergen_launch(const HzSearchSelfParams* pp, hipStream_t
   p.cand = s.cand, p.out_score = s.out_score, p.out_id = s.out_id;
   p.N = s.N, p.D = s.D, p.Q = s.Q, p.k = s.k, p.ldc = s.ldc, p.ntile = s.ntile, p.cand_bytes = s.cand_bytes;
   hipLaunchKernelGGL(search_merge_kernel, dim3(p.Q), dim3(MERGE_THREADS), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_search_assign_launch(const HzSearchAssignParams* pp, hipStream_t st) {
+  HzSearchAssignParams p = *pp;
+  if (!p.corpus || !p.cent || !p.live || !p.out_list || !p.out_score) return -61;
+  if (p.D % 32) return -62;
+  if (p.D < 32) return -63;
+  if (p.D > 2048) return -64;
+  if (p.ldc < p.D || p.ldc % 8 || p.ldk < p.D || p.ldk % 8) return -65;
+  if (p.N < 1) return -66;
+  if (p.C < 1 || p.C > HZ_SEARCH_ASSIGN_MAX_C) return -67;
+  if ((reinterpret_cast<uintptr_t>(p.corpus) & 15) || (reinterpret_cast<uintptr_t>(p.cent) & 15) ||
+      (reinterpret_cast<uintptr_t>(p.live) & 3) || (reinterpret_cast<uintptr_t>(p.out_list) & 3) ||
+      (reinterpret_cast<uintptr_t>(p.out_score) & 3))
+    return -68;
+  if (p.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -69;
+  p.ntile = (int)(((long)p.N + T - 1) / T);
+  hipLaunchKernelGGL(search_assign_kernel, dim3(p.ntile), dim3(T), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_search_cmean_launch(const HzSearchCmeanParams* pp, hipStream_t st) {
+  const HzSearchCmeanParams p = *pp;
+  if (!p.corpus || !p.order || !p.seg_off || !p.cent) return -70;
+  if (p.D % 32) return -71;
+  if (p.D < 32) return -72;
+  if (p.D > 2048) return -73;
+  if (p.ldc < p.D || p.ldc % 8 || p.ldk < p.D || p.ldk % 8) return -74;
+  if (p.N < 1) return -75;
+  if (p.C < 1 || p.C > HZ_SEARCH_ASSIGN_MAX_C) return -76;
+  if (p.M < 0) return -77;
+  if ((reinterpret_cast<uintptr_t>(p.corpus) & 15) || (reinterpret_cast<uintptr_t>(p.cent) & 15) ||
+      (reinterpret_cast<uintptr_t>(p.order) & 3) || (reinterpret_cast<uintptr_t>(p.seg_off) & 3) ||
+      (reinterpret_cast<uintptr_t>(p.cent32) & 3))
+    return -78;
+  if (p.cosine != 0 && p.cosine != 1) return -79;
+  hipLaunchKernelGGL(search_cmean_kernel, dim3(p.C), dim3(CMEAN_THREADS), 0, st, p);
   return (int)hipGetLastError();
 }
 

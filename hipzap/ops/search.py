@@ -14,6 +14,8 @@ one fp32 scale per stored row) is the list scan over rows of e4m3fn bytes.
 ``HZ_K_SEARCH_MSCAN`` (``SelfScanParams``) scores rows of the corpus, named by ``qid``, against every tile with the
 bf16 MFMA, ``SELF_QB`` queries a workgroup; ``HZ_K_SEARCH_MERGEN`` is the merge for any number of queries over the
 same block.
+``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
+same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -25,6 +27,8 @@ MAX_Q, MAX_K = 16, 128  # HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K (csrc/hipzap.h)
 SELF_QB = 64                     # HZ_SEARCH_SELF_QB: queries per workgroup of the self scan
 SELF_MAX_Q = 65535 * SELF_QB     # HZ_SEARCH_SELF_MAX_Q: the self scan's and its merge's limit on Q
 INDEX_SELF_MAX_Q = 1024          # HZ_INDEX_SELF_MAX_Q: ids per hz_index_neighbors call
+ASSIGN_CB = 64                   # HZ_SEARCH_ASSIGN_CB: centroids per block of the assign kernel
+ASSIGN_MAX_C = 65536             # HZ_SEARCH_ASSIGN_MAX_C: the most centroids (hipzap.search.IVF_MAX_LISTS)
 
 
 @N.params_of("HZ_K_SEARCH_MERGE")
@@ -106,8 +110,30 @@ class SelfScanParams(C.Structure):
                 ("skip_self", C.c_int), ("pad_", C.c_int)]
 
 
+@N.params_of("HZ_K_SEARCH_ASSIGN")
+class AssignParams(C.Structure):
+    """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
+    bitmap: a row without its bit gets -1 / -inf), ``out_list`` int32 [N], ``out_score`` fp32 [N]."""
+    _fields_ = [("corpus", C.c_void_p), ("cent", C.c_void_p), ("live", C.c_void_p), ("out_list", C.c_void_p),
+                ("out_score", C.c_void_p), ("live_bytes", C.c_uint64), ("N", C.c_int), ("D", C.c_int), ("C", C.c_int),
+                ("ldc", C.c_int), ("ldk", C.c_int), ("ntile", C.c_int)]
+
+
+@N.params_of("HZ_K_SEARCH_CMEAN")
+class CmeanParams(C.Structure):
+    """HzSearchCmeanParams: ``order`` device int32 [M] (the members' row ids, cluster after cluster), ``seg_off`` device
+    int32 [C + 1], ``cent`` bf16 [C][ldk] in and out, ``cent32`` fp32 [C][D] out or null."""
+    _fields_ = [("corpus", C.c_void_p), ("order", C.c_void_p), ("seg_off", C.c_void_p), ("cent", C.c_void_p),
+                ("cent32", C.c_void_p), ("N", C.c_int), ("D", C.c_int), ("C", C.c_int), ("M", C.c_int), ("ldc", C.c_int),
+                ("ldk", C.c_int), ("cosine", C.c_int), ("pad_", C.c_int)]
+
+
 def _sigs(lib):
     P, U64 = C.c_void_p, C.c_uint64
+    N._sig(lib, "hz_search_assign_launch", C.c_int, C.POINTER(AssignParams), P)
+    N._sig(lib, "hz_search_cmean_launch", C.c_int, C.POINTER(CmeanParams), P)
+    N._sig(lib, "hz_index_assign", C.c_int, P, C.c_int, P, C.c_int, P, P, P)
+    N._sig(lib, "hz_index_cmean", C.c_int, P, C.c_int, P, C.c_longlong, P, C.c_int, P, P)
     N._sig(lib, "hz_search_self_scratch_bytes", U64, C.c_longlong, C.c_longlong, C.c_int)
     N._sig(lib, "hz_search_mscan_launch", C.c_int, C.POINTER(SelfScanParams), P)
     N._sig(lib, "hz_search_mergen_launch", C.c_int, C.POINTER(SelfScanParams), P)

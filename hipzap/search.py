@@ -42,6 +42,7 @@ Order rule (kernels and oracle alike): higher score first; among equal scores th
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import os
@@ -293,17 +294,35 @@ def _nearest_centroid(rows32: np.ndarray, cent32: np.ndarray) -> np.ndarray:
     return out
 
 
-def ivf_kmeans(rows32: np.ndarray, nlist: int, metric: str, seed: int = 0, iters: int = 10):
+def check_init(init, nlist: int, dim: int) -> np.ndarray:
+    """``init`` of :func:`ivf_kmeans` / ``cluster``: starting centroids, a finite floating-point [nlist, dim] array
+    -> fp32."""
+    a = np.asarray(init)
+    if a.dtype.kind != "f":
+        raise ValueError(f"init must be a floating-point array, got dtype {a.dtype}")
+    if a.shape != (nlist, dim):
+        raise ValueError(f"init must have the shape [nlist, dim] = [{nlist}, {dim}], got {list(a.shape)}")
+    bad = np.argwhere(~np.isfinite(a))
+    if bad.size:
+        r, c = (int(v) for v in bad[0])
+        raise ValueError(f"init must be finite, got {a[r, c]!r} at [{r}, {c}]")
+    return np.ascontiguousarray(a, np.float32)
+
+
+def ivf_kmeans(rows32: np.ndarray, nlist: int, metric: str, seed: int = 0, iters: int = 10, init=None):
     """k-means over the stored rows (bf16 values as fp32 [N, D]) -> (centroid bf16 bits uint16 [nlist, D], the list
     of every row int32 [N]). Trains on at most ``IVF_SAMPLE`` rows per centroid, drawn with ``seed``; the first
     centroids are ``nlist`` distinct sample rows. Assignment is by the largest inner product with the bf16-rounded
     centroids; ``cosine``: spherical k-means (a centroid is its members' mean divided by its norm), ``ip``: plain
-    means. A centroid that loses every member keeps its value. Lists may be empty."""
+    means. A centroid that loses every member keeps its value. Lists may be empty. ``init`` (fp32 [nlist, D]): the
+    starting centroids in place of the random draw of rows (the sample is drawn as without it)."""
     rng = np.random.default_rng(seed)
     n = rows32.shape[0]
     m = min(n, IVF_SAMPLE * nlist)
     sample = rows32[np.sort(rng.choice(n, m, replace=False))] if m < n else rows32
     cent = sample[np.sort(rng.choice(m, nlist, replace=False))].astype(np.float32)
+    if init is not None:
+        cent = check_init(init, nlist, rows32.shape[1]).copy()
     for _ in range(int(iters)):
         a = _nearest_centroid(sample, bf16_to_f32(to_bf16(cent)))
         order = np.argsort(a, kind="stable")
@@ -335,7 +354,7 @@ def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
 
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
-                ivf_iters: int = 10) -> dict:
+                ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -344,7 +363,9 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     ``ivf=nlist``: an IVF index, a version-5 file -- the rows a plain bf16 index stores (the same bits), grouped
     into ``nlist`` lists by :func:`ivf_kmeans` (``ivf_seed``, ``ivf_iters``) and stored in :func:`ivf_layout`'s order;
     ``nprobe``: the lists a search scans by default, ``min(nlist, 16)`` when None. Ids stay the positions in
-    ``vectors``."""
+    ``vectors``. ``ivf_backend="gpu"``: the lists come from :meth:`Index.cluster` on ``device`` (:func:`cluster_rows`)
+    in place of :func:`ivf_kmeans`; the file has the same layout either way."""
+    _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     if ivf is not None and (dtype != "bf16" or rescore):
@@ -367,7 +388,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
         hdr["labels"] = labels
     if ivf is not None:
         nlist, nprobe = _check_ivf_args(n, ivf, nprobe, ivf_seed, ivf_iters)
-        cbits, assign = ivf_kmeans(bf16_to_f32(rows), nlist, metric, int(ivf_seed), int(ivf_iters))
+        cbits, assign = _ivf_lists(rows, nlist, metric, int(ivf_seed), int(ivf_iters), ivf_backend, device, path)
         lay = ivf_layout(assign, nlist)
         real = lay["rowid"] >= 0
         srows = np.zeros((real.size, d), np.uint16)
@@ -378,6 +399,44 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
         lay.update(centroids=cbits, nlist=nlist, nprobe=int(nprobe), seed=int(ivf_seed), iters=int(ivf_iters))
         return _write_file(path, hdr, srows, stags, real, ivf=lay)
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows)
+
+
+IVF_BACKENDS = ("cpu", "gpu")
+
+
+def _check_ivf_backend(ivf_backend, ivf):
+    if ivf_backend not in IVF_BACKENDS:
+        raise ValueError(f"ivf_backend must be one of {IVF_BACKENDS}, got {ivf_backend!r}")
+    if ivf is None and ivf_backend != "cpu":
+        raise ValueError(f"ivf_backend={ivf_backend!r} goes with ivf=nlist")
+
+
+def cluster_rows(bits: np.ndarray, nlist: int, metric: str, seed: int = 0, iters: int = 10, device: int = 0,
+                 near: str | None = None):
+    """:func:`ivf_kmeans` on the GPU: the bf16 rows ``bits`` (uint16 [N, D], D % 32 == 0) are written as a temporary
+    plain index (next to ``near``, or in the temporary directory), opened, and clustered with :meth:`Index.cluster`
+    -> (centroid bits uint16 [nlist, D], the list of every row int32 [N])."""
+    import tempfile
+    if bits.shape[1] % 32:
+        raise ValueError(f"ivf_backend='gpu' needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {bits.shape[1]}")
+    where = os.path.dirname(os.path.abspath(near)) if near else None
+    fd, tmp = tempfile.mkstemp(suffix=".hzidx", prefix=".cluster-", dir=where)
+    os.close(fd)
+    try:
+        _write_file(tmp, {"dim": int(bits.shape[1]), "count": int(bits.shape[0]), "dtype": "bf16", "metric": metric,
+                          "model": "", "embed": None}, bits)
+        with Index(tmp, device, contexts=1) as ix:
+            cbits, assign, _ = ix.cluster(nlist, iters=iters, seed=seed)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return cbits, assign
+
+
+def _ivf_lists(bits, nlist, metric, seed, iters, backend, device, near):
+    if backend == "gpu":
+        return cluster_rows(bits, nlist, metric, seed, iters, device, near)
+    return ivf_kmeans(bf16_to_f32(bits), nlist, metric, seed, iters)
 
 
 def _check_ivf_args(n: int, ivf, nprobe, ivf_seed, ivf_iters):
@@ -783,6 +842,63 @@ class _Base:
             raise ValueError(f"neighbors needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
         return self._check_ids(ids), check_k(k)
 
+    def _check_cluster_index(self):
+        """:meth:`cluster` is built for plain bf16 indexes with ``dim % 32 == 0``."""
+        if self.dtype == FP8 or self.ivf is not None:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else f"an {FP8} index"
+            raise ValueError(f"cluster is built for plain bf16 indexes (versions 1 and 2): this one is {what} of version "
+                             f"{self.version}")
+        if self.dim % 32:
+            raise ValueError(f"cluster needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
+
+    def _check_cluster(self, nlist, iters, seed, init, nlive: int):
+        """The argument refusals of :meth:`cluster` that both backends share -> init as fp32 or None."""
+        if not _is_int(nlist) or not 1 <= nlist <= min(nlive, IVF_MAX_LISTS):
+            raise ValueError(f"nlist must be an integer in 1..min(live rows, {IVF_MAX_LISTS}) = 1..{min(nlive, IVF_MAX_LISTS)}, "
+                             f"got {nlist!r}")
+        if not _is_int(iters) or iters < 0:
+            raise ValueError(f"iters must be an integer >= 0, got {iters!r}")
+        if not _is_int(seed) or seed < 0:
+            raise ValueError(f"seed must be an integer >= 0, got {seed!r}")
+        return None if init is None else check_init(init, int(nlist), self.dim)
+
+    def cluster(self, nlist: int, *, iters: int = 10, seed: int = 0, init=None, ctx: int | None = None):
+        """k-means over the live rows -> (centroid bf16 bits uint16 [nlist, dim], the cluster of every row int32 [count],
+        its score float32 [count]); a deleted row gets -1 / -inf. :func:`ivf_kmeans`'s algorithm: the same sample draw
+        and the same first centroids (``nlist`` distinct sample rows, or ``init``), both taken over the live rows;
+        assignment by the largest inner product with the bf16 centroids, the lowest index among equals; a centroid
+        is its members' mean (``cosine``: divided by its norm) and keeps its value when it has none. The training
+        assignments cover the sample only, the last one every live row. On :class:`Index` both steps run on the
+        GPU; :class:`RefIndex` scores and averages in fp64. ``ctx`` is the GPU backend's context."""
+        self._check_cluster_index()
+        live = self._live_now()
+        ids = np.flatnonzero(live)
+        init = self._check_cluster(nlist, iters, seed, init, ids.size)
+        nlist = int(nlist)
+        rng = np.random.default_rng(seed)
+        n = ids.size
+        m = min(n, IVF_SAMPLE * nlist)
+        sample = ids[np.sort(rng.choice(n, m, replace=False))] if m < n else ids
+        first = sample[np.sort(rng.choice(m, nlist, replace=False))]
+        bits = self._cluster_rows(first) if init is None else to_bf16(init)
+        take = np.zeros(self.count, bool)
+        take[sample] = True
+        trace = None
+        with self._cluster_hold(ctx) as ctx:  # one context for the whole job: its buffers are allocated once
+            for _ in range(int(iters)):
+                a = self._cluster_assign(bits, take, ctx)[0]
+                order = np.argsort(a[sample], kind="stable")  # ascending ids inside a cluster, as in ivf_kmeans
+                seg_off = np.concatenate([[0], np.cumsum(np.bincount(a[sample], minlength=nlist))]).astype(np.int32)
+                bits, c32 = self._cluster_update(np.ascontiguousarray(sample[order], np.int32), seg_off, bits, ctx)
+                trace = (a, c32)
+            assign, score = self._cluster_assign(bits, live, ctx)
+        self._cluster_trace = trace  # the last training assignment and the fp32 centroids it gave (tests)
+        return bits, assign, score
+
+    @contextlib.contextmanager
+    def _cluster_hold(self, ctx):
+        yield ctx
+
     def knn_graph(self, k: int = 10, *, block: int = NEIGHBORS_BLOCK):
         """The kNN graph of the index: :meth:`neighbors` of every live row (itself excluded), ``block`` rows a pass
         -> (ids int32 [count, k], scores float32 [count, k]). A deleted row's lists hold -1 / -inf."""
@@ -953,6 +1069,38 @@ class RefIndex(_Base):
         with self._mut:
             return self._live.copy()
 
+    def _cluster_rows(self, ids):
+        return self._bits[ids].copy()
+
+    def _cluster_assign(self, bits, take, ctx=None):
+        """fp64 scores over the bf16 centroids ``bits``; rows outside ``take`` get -1 / -inf."""
+        cent = bf16_to_f32(bits).astype(np.float64)
+        take = np.asarray(take, bool) & self._live
+        out, score = np.full(self.count, -1, np.int32), np.full(self.count, -np.inf, np.float32)
+        rows = np.flatnonzero(take)
+        step = max(1, (1 << 22) // max(cent.shape[0], 1))
+        for a in range(0, rows.size, step):
+            part = rows[a:a + step]
+            s = self._rows[part].astype(np.float64) @ cent.T
+            best = np.argmax(s, axis=1)  # the lowest index among equals
+            out[part], score[part] = best, s[np.arange(part.size), best]
+        return out, score
+
+    def _cluster_update(self, order, seg_off, bits, ctx=None):
+        """fp64 means of the segments (``cosine``: divided by max(norm, 1e-12)); an empty segment keeps its bits."""
+        bits = bits.copy()
+        c32 = bf16_to_f32(bits)
+        sizes = np.diff(seg_off)
+        lists = np.flatnonzero(sizes)
+        if lists.size:
+            sums = np.add.reduceat(self._rows[order].astype(np.float64), seg_off[lists], axis=0)
+            mean = sums / sizes[lists][:, None]
+            if self.metric == "cosine":
+                mean = mean / np.maximum(np.sqrt((mean * mean).sum(axis=1)), 1e-12)[:, None]
+            c32[lists] = mean.astype(np.float32)
+            bits[lists] = to_bf16(c32[lists])
+        return bits, c32
+
     def _append(self, bits, tags, publish):
         first = self.count
         if self.scales is not None:
@@ -1121,6 +1269,56 @@ class Index(_Base):
                             "hz_index_read_state")
         return unpack_live(words, n)
 
+    def _cluster_rows(self, ids):
+        return self._state()[0][ids].copy()
+
+    @contextlib.contextmanager
+    def _cluster_hold(self, ctx):
+        """A free context (or ``ctx``) for the length of a clustering job."""
+        if ctx is not None or self._h is None:
+            yield ctx
+            return
+        c = self._free.get()
+        try:
+            yield c
+        finally:
+            self._free.put(c)
+
+    def _cluster_call(self, ctx, call, what):
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        c = self._free.get() if ctx is None else ctx
+        try:
+            rc = call(c)
+        finally:
+            if ctx is None:
+                self._free.put(c)
+        if rc in (-38, -39, -40, -41, -42, -43):
+            raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
+        if rc:
+            raise RuntimeError(f"{what} failed with code {rc}")
+
+    def _cluster_assign(self, bits, take, ctx=None):
+        """HZ_K_SEARCH_ASSIGN over the index's rows against the bf16 centroids ``bits``; the native side ANDs ``take``
+        (bool [count]) with the live bitmap."""
+        bits = np.ascontiguousarray(bits, np.uint16)
+        words = pack_live(take)
+        out, score = np.empty(self.count, np.int32), np.empty(self.count, np.float32)
+        self._cluster_call(ctx, lambda c: self._lib.hz_index_assign(self._h, c, bits.ctypes.data, bits.shape[0],
+                                                                    words.ctypes.data, out.ctypes.data, score.ctypes.data),
+                           "hz_index_assign")
+        return out, score
+
+    def _cluster_update(self, order, seg_off, bits, ctx=None):
+        """HZ_K_SEARCH_CMEAN: the segments' means over ``bits`` -> (new bits, their fp32 values)."""
+        bits = np.ascontiguousarray(bits, np.uint16).copy()
+        c32 = bf16_to_f32(bits)
+        order, seg_off = np.ascontiguousarray(order, np.int32), np.ascontiguousarray(seg_off, np.int32)
+        self._cluster_call(ctx, lambda c: self._lib.hz_index_cmean(self._h, c, order.ctypes.data, order.size,
+                                                                   seg_off.ctypes.data, bits.shape[0], bits.ctypes.data,
+                                                                   c32.ctypes.data), "hz_index_cmean")
+        return bits, c32
+
     def _exclusive(self, call, what):
         """Run a native mutation holding every context token (the caller holds the mutation lock, so no
         second mutator waits on a partial set)."""
@@ -1221,7 +1419,7 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 
 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
-                  ivf_seed: int = 0, ivf_iters: int = 10) -> dict:
+                  ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0) -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -1231,7 +1429,8 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     gathered into id order. ``ivf=nlist`` (a plain ``src``, version 1 or 2) builds the lists over the stored rows
     with :func:`ivf_kmeans` / :func:`ivf_layout` (``nprobe``, ``ivf_seed``, ``ivf_iters`` as in
     :func:`write_index`): version 5 for ``dtype="bf16"``, 6 or 7 for fp8. A deleted row keeps its id, is assigned to
-    a list and stays dead."""
+    a list and stays dead. ``ivf_backend="gpu"``: the lists come from :func:`cluster_rows` on ``device``."""
+    _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     if rescore and dtype != "fp8":
@@ -1259,7 +1458,7 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
         else:
             n = hdr["count"]
             nlist, nprobe = _check_ivf_args(n, ivf, nprobe, ivf_seed, ivf_iters)
-            cbits, assign = ivf_kmeans(bf16_to_f32(bits), nlist, hdr["metric"], int(ivf_seed), int(ivf_iters))
+            cbits, assign = _ivf_lists(bits, nlist, hdr["metric"], int(ivf_seed), int(ivf_iters), ivf_backend, device, dst)
             lay = ivf_layout(assign, nlist)
             real = lay["rowid"] >= 0
             ids = lay["rowid"][real]
