@@ -13,6 +13,7 @@
     python -m hipzap index --embed-plan m.pth.emb.hzplan --images imgs.npy --out x.hzidx  # uint8 [N, H, W, 3]
     python -m hipzap index --from-index a.hzidx --dtype fp8 --out b.hzidx  # requantise a bf16 index (ids kept)
     python -m hipzap index --vectors v.npy --dtype fp8 --rescore --out c.hzidx  # fp8 scan + bf16 rescoring (version 4)
+    python -m hipzap index --vectors v.npy --dtype bin --rescore --out d.hzidx  # sign-bit scan + bf16 rescoring (version 9)
     python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
@@ -115,7 +116,9 @@ def cmd_index(a):
     import numpy as np
 
     from .search import convert_index, write_index
-    if a.rescore and a.dtype != "fp8":
+    if a.ivf is not None and a.dtype == "bin":
+        raise SystemExit("index: --ivf with --dtype bin: IVF lists over binary rows are not built")
+    if a.rescore and a.dtype not in ("fp8", "bin"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
     if a.from_index is not None:
@@ -316,8 +319,10 @@ def main(argv=None):
     ix.add_argument("--labels", default=None, help="a JSON list of N strings")
     ix.add_argument("--tags", default=None, help="an .npy of N uint32 tag words (search filters test them): a version-2 file")
     ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")
-    ix.add_argument("--dtype", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D % 16 == 0)")
+    ix.add_argument("--dtype", choices=["bf16", "fp8", "bin"], default="bf16",
+                    help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D %% 16 == 0); "
+                         "bin: one sign bit per column (a version-8 file, a sixteenth of the bytes; D %% 128 == 0), "
+                         "with --rescore version 9")
     ix.add_argument("--rescore", action="store_true",
                     help="with --dtype fp8: also store the bf16 rows (a version-4 file) for two-stage search, "
                          "fp8 scan then exact bf16 re-scoring of the candidates")

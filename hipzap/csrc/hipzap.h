@@ -492,6 +492,25 @@ typedef struct HzSearchQuantParams {
   const float* scales;           // fp32 [N], 4-B aligned
 } HzSearchQuantParams;
 int hz_search_qscan_launch(const HzSearchQuantParams* p, hipStream_t st);
+// binary scan (HZ_K_SEARCH_BSCAN): the filtered scan over sign-bit rows. `f.s.corpus` points at
+// uint32 [N][ldc] (ldc in WORDS, ldc % 4 == 0, ldc >= W = D / 32; D % 128 == 0, 128 <= D <= 2048): bit i & 31 of
+// word i >> 5 of a row is 1 iff the sign bit of column i is clear (the live bitmap's bit convention; -0.0 gives 0).
+// The kernel binarises the fp32 queries by the same rule and scores
+//   score(q, r) = (float)(D - 2 * popcount(qbits ^ rbits)),
+// an integer in [-D, D], exact in fp32; keys and the total order are HZ_K_SEARCH_SCAN's, so equal scores (the
+// normal case: only D + 1 values exist) rank by the lower id. The bits of a score depend on the query's D sign bits
+// and the row's W words, and on nothing else: not on N, Q, k, ldc, the row's tile or position, the other queries,
+// the filter, or what dead rows hold. The words of a row that fails for every query are never loaded.
+// HZ_K_SEARCH_MERGE reduces the lists. Filtered only: `live` is required.
+// Refusals (nothing is launched): -80 a null corpus, queries, cand, out_score or out_id; -81 D % 128; -82 D < 128;
+// -83 D > 2048; -84 ldc < D / 32 or ldc % 4; -85 N < 1 (N >= 2^31 cannot be expressed: hz_search_scratch_bytes
+// refuses it); -86 Q outside 1..HZ_SEARCH_MAX_Q; -87 k outside 1..HZ_SEARCH_MAX_K; -88 corpus or queries not 16-B,
+// cand not 8-B or out_* / tags / filt / live not 4-B aligned; -89 a null live bitmap; -90 live_bytes below
+// 4 * ceil(N / 32); -91 filt without tags; -92 cand_bytes below ntile * Q * k * 8.
+typedef struct HzSearchBinParams {
+  HzSearchFilterParams f;        // the filtered scan's block, unchanged (live is required; ldc counts words)
+} HzSearchBinParams;
+int hz_search_bscan_launch(const HzSearchBinParams* p, hipStream_t st);
 // rescore (HZ_K_SEARCH_RESCORE): the second stage of a two-stage search. One workgroup per query
 // scores the query against the R bf16 rows that `in_id` names (a merge's out_id of stage one; a slot is real
 // iff (unsigned)id < (unsigned)N, every other value is an empty slot and nothing is loaded for it) and writes
@@ -729,6 +748,20 @@ int hz_index_probes(void* idx, int ctx, const float* queries, int Q, int nprobe,
 // stored rows, hz_index_read_rescore up to count rows by id. Rows are never added (-34).
 // out[8] = {1 for an IVF index, nlist, default nprobe, tiles, external count, the file's version, 0, 0}
 int hz_index_describe3(void* idx, uint64_t* out);
+// A binary index (a version-8 or version-9 .hzidx): version 3's rule set over sign-bit rows --
+// "dtype": "bin_sign", the row block uint32 [count][dim / 32] (dim % 128 == 0, 128 <= dim <= 2048), no scales block,
+// "capacity" / "tags_off" / "live_off" present exactly when version 3 would have them. Version 9 adds "rescore":
+// "bf16" / "rescore_off" as version 4 does. open3 opens both (either rescore placement); every search replays H2D,
+// HZ_K_SEARCH_BSCAN, merge, two D2H, and with refine = R the scan and merge at k = R, then HZ_K_SEARCH_RESCORE:
+// version 4's programs with the binary scan in place of the fp8 scan, under the same key and invalidation rules.
+// describe2's out[5] is 2. The _b calls are hz_index_add / hz_index_read_state for such an index (-26 on any other
+// dtype, and from the other forms on this one); hz_index_add_br takes the words and the bf16 rows together, live
+// bits set last (-29, naming the right call: add_b on a version-9 index, add_br on a version-8 one). nprobe, probes
+// (-34), neighbors (-35), assign and cmean (-38) refuse it by name: "a bin_sign index of version 8".
+int hz_index_add_b(void* idx, const unsigned* words, long long n, const unsigned* tags_or_null, long long* first_id_out);
+int hz_index_add_br(void* idx, const unsigned* words, const unsigned short* rows_bf16, long long n,
+                    const unsigned* tags_or_null, long long* first_id_out);
+int hz_index_read_state_b(void* idx, unsigned* words_out, unsigned* tags_out, unsigned* live_out, long long n);
 // neighbours of stored rows (a plain bf16 index, versions 1 and 2, dim % 32 == 0): the k nearest live
 // rows of each of the n rows `ids` names, the row itself excluded iff skip_self -> out_score fp32 [n][k], out_id
 // int32 [n][k], -inf / -1 past the live rows. Replays H2D of the ids, HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two
@@ -946,7 +979,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_MSCAN, 39, HzSearchSelfParams, hz_search_mscan_op, SEARCH)     \
   X(SEARCH_MERGEN, 40, HzSearchSelfParams, hz_search_mergen_op, SEARCH)   \
   X(SEARCH_ASSIGN, 41, HzSearchAssignParams, hz_search_assign_op, SEARCH) \
-  X(SEARCH_CMEAN, 42, HzSearchCmeanParams, hz_search_cmean_op, SEARCH)
+  X(SEARCH_CMEAN, 42, HzSearchCmeanParams, hz_search_cmean_op, SEARCH)   \
+  X(SEARCH_BSCAN, 43, HzSearchBinParams, hz_search_bscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

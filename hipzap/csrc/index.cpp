@@ -36,6 +36,11 @@
 // with refine = R the list scan and its merge run at k = R into the context's intermediate buffer and
 // HZ_K_SEARCH_RESCORE re-scores those external ids against rrows[id] with N = n_ext. R is part of the key too.
 //
+// A binary index (a version-8 or version-9 file): the rows are sign bits, dim / 32 words each, with no
+// scales. It replays version 3's programs with HZ_K_SEARCH_BSCAN in place of the quantised scan (the scan's block
+// carries the pitch in words, the merge's keeps ldc = dim), and version 9 (bf16 rescore rows, either placement)
+// replays version 4's two-stage programs; keys and invalidation rules are the same.
+//
 // Neighbours of stored rows (a plain bf16 index): hz_index_neighbors replays H2D of the ids,
 // HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two D2H, with the filtered programs' N (the rows past the count are dead
 // in the bitmap) and so under their invalidation rules. A context's buffers for it (ids, results, candidate
@@ -135,9 +140,10 @@ struct Index {
   bool mutated = false;               // the unfiltered program (N = the file's count, all live) no longer holds
   bool has_tags = false;
   bool fp8 = false;                   // a version-3, 4, 6 or 7 file: e4m3fn byte rows and `scales`
+  bool bin = false;                   // a version-8 or 9 file: sign-bit rows, dim / 32 words each (never with fp8 or ivf)
   unsigned short* rows = nullptr;     // bf16 [cap][dim], or uint8 [cap][dim] of an fp8 index
   float* scales = nullptr;            // device, cap floats (fp8 only)
-  bool rescore = false;               // a version-4 or 7 file: `rrows` beside the fp8 rows
+  bool rescore = false;               // a version-4, 7 or 9 file: `rrows` beside the fp8 or sign-bit rows
   bool rescore_host = false;          // rrows is pinned host memory (hipHostMalloc), else device memory
   unsigned short* rrows = nullptr;    // bf16 [cap][dim] ([n_ext][dim], by external id, of an IVF index), the allocation
   unsigned short* rrows_dev = nullptr;  // the address the rescore kernel reads (the mapped address of a host block)
@@ -191,8 +197,9 @@ struct Index {
     return ivf ? pos_of[id] : id;
   }
 
-  uint64_t esize() const { return fp8 ? 1 : 2; }  // bytes per stored element
-  uint64_t row_bytes() const { return cap * h.dim * esize(); }
+  uint64_t rowb() const { return bin ? h.dim / 8 : fp8 ? h.dim : h.dim * 2ull; }  // bytes per stored row
+  const char* dtype_name() const { return bin ? "bin_sign" : fp8 ? "fp8_e4m3" : "bf16"; }
+  uint64_t row_bytes() const { return cap * rowb(); }
   uint64_t scan_rows() const { return round_up(count, kTile); }  // the filtered programs' N
   uint64_t rescore_rows(uint64_t for_cap) const { return ivf ? n_ext : for_cap; }  // an IVF index holds them by id
   uint64_t rescore_bytes() const { return rescore ? rescore_rows(cap) * h.dim * 2 : 0; }
@@ -266,12 +273,16 @@ struct Index {
     f.filt = reinterpret_cast<const unsigned*>(c.slot_dev);
     f.live_bytes = cap / 8;
     qp.scales = scales;
+    HzSearchBinParams bp{};  // sign-bit rows: the filtered block with the pitch in words (the merge keeps ldc = D)
+    bp.f = f;
+    bp.f.s.ldc = (int)h.dim / 32;
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4, qb = (size_t)Q * h.dim * 4;
     int rc;
     if (filtered) {
       rc = hz_prog_add_memcpy(g, c.slot_dev, c.slot_host, kFiltBytes + qb, 0);
-      if (!rc) rc = fp8 ? hz_prog_add_kernel(g, HZ_K_SEARCH_QSCAN, &qp, sizeof(qp), 0)
+      if (!rc) rc = bin ? hz_prog_add_kernel(g, HZ_K_SEARCH_BSCAN, &bp, sizeof(bp), 0)
+                  : fp8 ? hz_prog_add_kernel(g, HZ_K_SEARCH_QSCAN, &qp, sizeof(qp), 0)
                         : hz_prog_add_kernel(g, HZ_K_SEARCH_FSCAN, &f, sizeof(f), 0);
     } else {
       rc = hz_prog_add_memcpy(g, c.q_dev, c.q_host, qb, 0);
@@ -443,7 +454,7 @@ struct Index {
     const uint64_t cand_bytes = hz_search_scratch_bytes((long long)new_cap, HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
     if (!cand_bytes) return -21;  // 2^31 rows and above
     std::vector<unsigned long long*> ncand(ctx.size(), nullptr);
-    bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * h.dim * esize()) == hipSuccess;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&nrows), new_cap * rowb()) == hipSuccess;
     if (fp8) ok = ok && hipMalloc(reinterpret_cast<void**>(&nscales), new_cap * 4) == hipSuccess;
     if (rescore) ok = ok && alloc_rescore(rescore_rows(new_cap) * h.dim * 2, &nrr, &nrr_dev);
     ok = ok && hipMalloc(reinterpret_cast<void**>(&nlive), new_cap / 8) == hipSuccess;
@@ -453,7 +464,7 @@ struct Index {
     ok = ok && hipMemsetAsync(nlive, 0, new_cap / 8, st) == hipSuccess;
     ok = ok && hipMemsetAsync(ntags, 0, new_cap * 4, st) == hipSuccess;
     if (ok && rows) {
-      ok = hipMemcpyAsync(nrows, rows, count * h.dim * esize(), hipMemcpyDeviceToDevice, st) == hipSuccess;
+      ok = hipMemcpyAsync(nrows, rows, count * rowb(), hipMemcpyDeviceToDevice, st) == hipSuccess;
       if (fp8) ok = ok && hipMemcpyAsync(nscales, scales, count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
       if (rescore && !rescore_host)
         ok = ok && hipMemcpyAsync(nrr, rrows, count * h.dim * 2, hipMemcpyDeviceToDevice, st) == hipSuccess;
@@ -515,22 +526,28 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 7 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 9 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 7) return fail("index: unknown format version " + std::to_string(h.version));
-  const bool ivf = h.version >= 5;
-  const bool fp8 = h.version == 3 || h.version == 4 || h.version >= 6, rescore = h.version == 4 || h.version == 7;
+  if (h.version < 1 || h.version > 9) return fail("index: unknown format version " + std::to_string(h.version));
+  const bool ivf = h.version >= 5 && h.version <= 7;
+  const bool fp8 = h.version == 3 || h.version == 4 || h.version == 6 || h.version == 7;
+  const bool bin = h.version == 8 || h.version == 9;
+  const bool rescore = h.version == 4 || h.version == 7 || h.version == 9;
   const std::string vname = "version-" + std::to_string(h.version);
   if (fp8 != (js.rfind("\"dtype\": \"fp8_e4m3\"") != std::string::npos))
+    return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
+  if (bin != (js.rfind("\"dtype\": \"bin_sign\"") != std::string::npos))
     return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
   if (!ivf && js.rfind("\"ivf\": {") != std::string::npos)
     return fail("index: an ivf block in a " + vname + " file (it belongs to versions 5, 6 and 7)");
   if (fp8 && (h.dim < 16 || h.dim % 16 || h.dim > 2048))
     return fail("index: dim of an fp8 index must be a multiple of 16 in 16..2048");
+  if (bin && (h.dim < 128 || h.dim % 128 || h.dim > 2048))
+    return fail("index: dim of a binary index must be a multiple of 128 in 128..2048");
   if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
   if (h.count < 1 || h.count >= (1ull << 31)) return fail("index: count must be in 1..2^31-1");
   if (h.metric > HZ_INDEX_IP) return fail("index: unknown metric");
@@ -551,7 +568,7 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
       return fail("index: ivf nlist / nprobe out of range");
     h.count = stored;
   }
-  const uint64_t bytes = h.count * h.dim * (fp8 ? 1 : 2), fsize = (uint64_t)sb.st_size;
+  const uint64_t bytes = bin ? h.count * (h.dim / 8) : h.count * h.dim * (fp8 ? 1 : 2), fsize = (uint64_t)sb.st_size;
   if (h.data_off % 4096 || h.data_off < sizeof(h) + h.json_len || h.data_off + bytes > fsize)
     return fail("index: row block outside the file");
   uint64_t tags_off = 0, live_off = 0;
@@ -563,6 +580,8 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     if (scales_off % 4096 || scales_off < after_rows || scales_off > fsize || h.count * 4 > fsize - scales_off)
       return fail("index: scales block outside the file");
     after_rows = scales_off + h.count * 4;
+  }
+  if (fp8 || bin) {
     const bool t = json_u64(js, "tags_off", &tags_off, true), l = json_u64(js, "live_off", &live_off, true);
     if (t != l) return fail("index: a " + vname + " file with only one of tags_off / live_off");
     if (ivf && !t) return fail("index: a " + vname + " file without tags_off / live_off");
@@ -570,14 +589,14 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   }
   uint64_t rescore_off = 0;
   const uint64_t rescore_len = n_ext * h.dim * 2;  // [count][dim]: an IVF file holds them by external id
-  if (fp8) {
+  if (fp8 || bin) {
     const bool off = json_u64(js, "rescore_off", &rescore_off, true);
     const bool key = js.rfind("\"rescore\": \"bf16\"") != std::string::npos;
     if (rescore && !(off && key)) return fail("index: a " + vname + " file without rescore / rescore_off");
-    if (!rescore && (off || key)) return fail("index: a " + vname + " file with rescore keys (they belong to versions 4 and 7)");
+    if (!rescore && (off || key)) return fail("index: a " + vname + " file with rescore keys (they belong to versions " + (bin ? "4, 7 and 9" : "4 and 7") + ")");
   }
   if (blocks) {
-    if (!fp8 && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
+    if (!fp8 && !bin && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
       return fail("index: a version-2 file without tags_off / live_off");
     if (tags_off % 4096 || live_off % 4096 || tags_off < after_rows || live_off < after_rows ||
         tags_off > fsize || tag_bytes > fsize - tags_off || live_off > fsize || live_bytes > fsize - live_off)
@@ -651,6 +670,7 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   idx->h = h;
   idx->count = h.count;
   idx->fp8 = fp8;
+  idx->bin = bin;
   idx->rescore = rescore;
   idx->rescore_host = rescore && rescore_host != 0;
   idx->ivf = ivf;
@@ -771,7 +791,7 @@ int hz_index_describe2(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
-  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->fp8 ? 1u : 0u,
+  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->bin ? 2u : x->fp8 ? 1u : 0u,
                        x->rescore ? 1u : 0u, x->rescore_host ? 1u : 0u};
   std::memcpy(out, v, sizeof(v));
   return 0;
@@ -799,8 +819,8 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
     return -34;
   }
   if (refine && !x->rescore) {
-    g_err = std::string("index: refine needs rescore rows (a version-4 or version-7 file), the index holds ") +
-            (x->fp8 ? "fp8_e4m3" : "bf16") + " rows only";
+    g_err = std::string("index: refine needs rescore rows (") + (x->bin ? "a version-9 file" : "a version-4 or version-7 file") +
+            "), the index holds " + x->dtype_name() + " rows only";
     return -27;
   }
   if (refine && (refine < k || refine > HZ_SEARCH_MAX_K)) {
@@ -809,6 +829,7 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
   }
   if (nprobe && !x->ivf) {
     g_err = "index: nprobe needs an IVF index (a version-5, 6 or 7 file)";
+    if (x->bin) g_err += ", this one is a bin_sign index of version " + std::to_string(x->h.version);
     return -34;
   }
   if (x->ivf && (nprobe < 0 || (nprobe > HZ_SEARCH_MAX_K && nprobe < x->nlist))) {
@@ -820,7 +841,7 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
-  const bool filtered = x->fp8 || x->mutated || filt != nullptr || x->ivf;
+  const bool filtered = x->fp8 || x->bin || x->mutated || filt != nullptr || x->ivf;
   bool fresh = false;
   HzProgram g = x->ivf ? x->ivf_program(c, Q, k, nprobe, refine, false, &fresh) : x->program(c, Q, k, filtered, refine, &fresh);
   if (!g) return -11;
@@ -854,7 +875,8 @@ int hz_index_probes(void* h, int ctx, const float* queries, int Q, int nprobe, i
   if (Q < 1 || Q > HZ_SEARCH_MAX_Q) return -4;
   if (!x->ivf || nprobe < 1 || nprobe > x->nlist || nprobe > HZ_SEARCH_MAX_K) {
     g_err = x->ivf ? "index: nprobe must be in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " + std::to_string(nprobe)
-                   : std::string("index: probes needs an IVF index (a version-5, 6 or 7 file)");
+                   : std::string("index: probes needs an IVF index (a version-5, 6 or 7 file)") +
+                         (x->bin ? ", this one is a bin_sign index of version " + std::to_string(x->h.version) : std::string());
     return -34;
   }
   Ctx& c = *x->ctx[ctx];
@@ -887,9 +909,9 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
   Index* x = static_cast<Index*>(h);
   if (!x || !ids || !out_score || !out_id) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (x->fp8 || x->ivf) {
+  if (x->fp8 || x->ivf || x->bin) {
     g_err = std::string("index: neighbors is built for plain bf16 indexes (versions 1 and 2), this one is ") +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : "an fp8_e4m3 index") + " of version " +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin ? "a bin_sign index" : "an fp8_e4m3 index") + " of version " +
             std::to_string(x->h.version);
     return -35;
   }
@@ -951,9 +973,9 @@ void* cl_buffer(Ctx& c, int which, uint64_t need) {
 // what both clustering calls refuse: -9 the context, -38 an fp8 or an IVF index, -39 dim % 32, -40 C
 int cluster_check(const Index* x, int ctx, int C, const char* call) {
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (x->fp8 || x->ivf) {
+  if (x->fp8 || x->ivf || x->bin) {
     g_err = std::string("index: ") + call + " is built for plain bf16 indexes (versions 1 and 2), this one is " +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : "an fp8_e4m3 index") + " of version " +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin ? "a bin_sign index" : "an fp8_e4m3 index") + " of version " +
             std::to_string(x->h.version);
     return -38;
   }
@@ -1084,7 +1106,7 @@ int add_rows(Index* x, const void* data, const float* scales, const unsigned sho
   }
   // rows and tags first: above `count` they are dead, so a failure here leaves nothing a search can see
   for (uint64_t r = first; r < last; ++r) x->tags_host[r] = tags ? tags[r - first] : 0u;
-  const uint64_t rb = x->h.dim * x->esize();
+  const uint64_t rb = x->rowb();
   int rc = (int)hipMemcpyAsync(reinterpret_cast<char*>(x->rows) + first * rb, data, (uint64_t)n * rb, hipMemcpyHostToDevice, st);
   if (!rc && scales) rc = (int)hipMemcpyAsync(x->scales + first, scales, (uint64_t)n * 4, hipMemcpyHostToDevice, st);
   if (!rc && rr) {  // like the other halves: dead above `count` until the live bits are set
@@ -1121,7 +1143,7 @@ int no_ivf_add() {
 }
 
 int wrong_dtype(const Index* x, const char* call, const char* takes) {
-  g_err = std::string("index: ") + call + " takes " + takes + " rows, the index holds " + (x->fp8 ? "fp8_e4m3" : "bf16");
+  g_err = std::string("index: ") + call + " takes " + takes + " rows, the index holds " + x->dtype_name();
   return -26;
 }
 
@@ -1133,7 +1155,7 @@ int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const un
   Index* x = static_cast<Index*>(h);
   if (!x || !rows_bf16 || n < 1) return -1;
   if (x->ivf) return no_ivf_add();
-  if (x->fp8) return wrong_dtype(x, "hz_index_add", "bf16");
+  if (x->fp8 || x->bin) return wrong_dtype(x, "hz_index_add", "bf16");
   return add_rows(x, rows_bf16, nullptr, nullptr, n, tags, first_id);
 }
 
@@ -1161,6 +1183,33 @@ int hz_index_add_qr(void* h, const unsigned char* codes, const float* scales, co
     return -29;
   }
   return add_rows(x, codes, scales, rows_bf16, n, tags, first_id);
+}
+
+// sign-bit rows (a version-8 file): n rows of dim / 32 words
+int hz_index_add_b(void* h, const unsigned* words, long long n, const unsigned* tags, long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !words || n < 1) return -1;
+  if (x->ivf) return no_ivf_add();
+  if (!x->bin) return wrong_dtype(x, "hz_index_add_b", "bin_sign");
+  if (x->rescore) {
+    g_err = "index: hz_index_add_b adds sign-bit rows only; an index with rescore rows takes hz_index_add_br (words and bf16 rows)";
+    return -29;
+  }
+  return add_rows(x, words, nullptr, nullptr, n, tags, first_id);
+}
+
+// a two-stage binary index (a version-9 file): words and bf16 rows together, the live bits set last
+int hz_index_add_br(void* h, const unsigned* words, const unsigned short* rows_bf16, long long n, const unsigned* tags,
+                    long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !words || !rows_bf16 || n < 1) return -1;
+  if (x->ivf) return no_ivf_add();
+  if (!x->bin) return wrong_dtype(x, "hz_index_add_br", "bin_sign");
+  if (!x->rescore) {
+    g_err = "index: hz_index_add_br needs an index with rescore rows (a version-9 file); use hz_index_add_b";
+    return -29;
+  }
+  return add_rows(x, words, nullptr, rows_bf16, n, tags, first_id);
 }
 
 int hz_index_delete(void* h, const int* ids, long long n, long long* newly_deleted) {
@@ -1225,7 +1274,7 @@ int read_state(Index* x, void* rows_out, float* scales_out, unsigned* tags_out, 
   if (live_out) std::memcpy(live_out, x->live_host.data(), (size_t)(((uint64_t)n + 31) / 32) * 4);
   int rc = 0;
   if (scales_out && n) rc = (int)hipMemcpy(scales_out, x->scales, (uint64_t)n * 4, hipMemcpyDeviceToHost);
-  if (!rc && rows_out && n) rc = (int)hipMemcpy(rows_out, x->rows, (uint64_t)n * x->h.dim * x->esize(), hipMemcpyDeviceToHost);
+  if (!rc && rows_out && n) rc = (int)hipMemcpy(rows_out, x->rows, (uint64_t)n * x->rowb(), hipMemcpyDeviceToHost);
   return rc;
 }
 
@@ -1237,7 +1286,7 @@ extern "C" {
 int hz_index_read_state(void* h, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n) {
   Index* x = static_cast<Index*>(h);
   if (!x || n < 0) return -1;
-  if (x->fp8) return wrong_dtype(x, "hz_index_read_state", "bf16");
+  if (x->fp8 || x->bin) return wrong_dtype(x, "hz_index_read_state", "bf16");
   return read_state(x, rows_out, nullptr, tags_out, live_out, n);
 }
 
@@ -1249,6 +1298,13 @@ int hz_index_read_state_q(void* h, unsigned char* codes_out, float* scales_out, 
   return read_state(x, codes_out, scales_out, tags_out, live_out, n);
 }
 
+int hz_index_read_state_b(void* h, unsigned* words_out, unsigned* tags_out, unsigned* live_out, long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || n < 0) return -1;
+  if (!x->bin) return wrong_dtype(x, "hz_index_read_state_b", "bin_sign");
+  return read_state(x, words_out, nullptr, tags_out, live_out, n);
+}
+
 // the first n (<= count) rescore rows back to the host (for save)
 int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
   Index* x = static_cast<Index*>(h);
@@ -1256,6 +1312,7 @@ int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
   AllLocked all(*x);
   if (!x->rescore) {
     g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-4 or version-7 file)";
+    if (x->bin) g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-9 file)";
     return -29;
   }
   if ((uint64_t)n > x->rescore_rows(x->count)) return -20;

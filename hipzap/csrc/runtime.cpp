@@ -476,6 +476,10 @@ extern "C" __attribute__((weak)) int hz_search_cmean_launch(const HzSearchCmeanP
 static int hz_search_cmean_op(const HzSearchCmeanParams* p, hipStream_t st) {
   return hz_search_cmean_launch ? hz_search_cmean_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_bscan_launch(const HzSearchBinParams* p, hipStream_t st);
+static int hz_search_bscan_op(const HzSearchBinParams* p, hipStream_t st) {
+  return hz_search_bscan_launch ? hz_search_bscan_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -13,7 +13,9 @@
 //                    search_merge behind a launcher that takes any number of queries
 //   * search_assign — the nearest centroid of every row (kind ASSIGN): the self scan with the roles turned, a running
 //                    top-1 key per row; search_cmean (kind CMEAN): a cluster's mean in a fixed summation order
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t for the reasoning.
+//   * search_bscan — the filtered scan over sign-bit rows (kind BSCAN): one word per 32 columns, the queries binarised
+//                    in the kernel, score = D - 2 popcount(q xor r); its lists go to search_merge like any other
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -112,6 +114,7 @@ __host__ __device__ inline const HzSearchParams& scan_part(const HzSearchFilterP
 __host__ __device__ inline const HzSearchParams& scan_part(const HzSearchQuantParams& a) { return a.f.s; }
 __host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchFilterParams& a) { return a; }
 __host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchQuantParams& a) { return a.f; }
+__host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchBinParams& a) { return a.f; }
 
 // Dynamic LDS of a scan, in the kernel's order: queries [Q][D], scores [Q][T]; filtered: pass bits [T], the
 // tile's live words [T / 32], filters [Q][2]; scaled: the passing rows' scales [T]. At most 144 KiB (Q = 16,
@@ -320,6 +323,81 @@ __global__ __launch_bounds__(T) void search_scan_kernel(const typename Fmt::temp
   scan_rows<Fmt, NC, FILT>(p, qs, sc, pmask, scl, row0, rows, lane, w, nch);
   __syncthreads();
   rank_tile<FILT>(p, sc, tile, row0, rows);
+}
+
+// ------------------------------------------------------------------------------------ binary scan
+// search_bscan_kernel<NCH> (HZ_K_SEARCH_BSCAN): the filtered scan over sign-bit rows of W = D / 32
+// words (D % 128 == 0: whole 16-B chunks). NCH is the 16-B chunks a thread holds, sized to W at launch.
+// CONTRACT (hipzap.h): score(q, r) = (float)(D - 2 * popcount(qbits ^ rbits)), qbits the query's D "sign bit clear"
+// bits in the row's bit order. An integer sum, so no summation order exists: the bits depend on the query's sign
+// bits and the row's words only. The query words past W and the row words that are not loaded are zero and add 0.
+//   * query bits: wave w takes the 64-column blocks w, w + 4, ... of the Q x D fp32 queries; one ballot of "sign
+//     clear" is two words of qb[q][WB] in LDS (WB = 4 NCH). -0.0 gives bit 0, like the rows' writer.
+//   * pass bits: stage_pass_bits as the filtered kinds use it (BinRows: an unscaled format).
+//   * scoring: thread t owns row t of the tile and holds its words in registers (16-B loads, only if some query
+//     passes for the row); a wave whose 64 rows all fail loads nothing and writes its sentinels (a scalar branch).
+//     Per query: xor + popcount against qb[q], whose reads are LDS broadcasts.
+//   * ranking and the candidate lists: rank_tile<true>, then HZ_K_SEARCH_MERGE.
+// Addresses: queries[q*D + i] under q < Q, i < D; corpus words [(row0 + t)*ldc + 4c, + 4) under t < rows, row < N
+// and 4c < W <= ldc; live, tags, filt as in stage_pass_bits; cand through rank_tile (`rank < k`).
+// Static LDS: qb 4 NCH * 16 words, scores [16][T], pass bits, live words and filters: at most 21,664 B.
+struct BinRows {
+  static constexpr bool SCALED = false;
+};
+
+template <int NCH>
+__global__ __launch_bounds__(T) void search_bscan_kernel(const HzSearchBinParams a) {
+  constexpr int WB = NCH * 4;  // words a thread holds; the query words from W to WB are zero
+  const HzSearchParams& p = a.f.s;
+  __shared__ __attribute__((aligned(16))) unsigned qb[HZ_SEARCH_MAX_Q * WB];
+  __shared__ unsigned sc[HZ_SEARCH_MAX_Q * T];
+  __shared__ unsigned pmask[T + T / 32 + 2 * HZ_SEARCH_MAX_Q];  // pass bits, the tile's live words, {mask, value}
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int tile = blockIdx.x;
+  const int W = p.D >> 5;
+  if (!HZ_DCHECK(tile < p.ntile && p.D >= 128 && p.D % 128 == 0 && W <= WB && p.ldc >= W && p.Q >= 1 &&
+                 p.Q <= HZ_SEARCH_MAX_Q && (long)tile * T < (long)p.N))
+    return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  const int nblk = p.D >> 6;  // 64-column blocks of a query: two words each
+  for (int i = w; i < p.Q * nblk; i += T / 64) {  // wave-uniform bounds
+    const int q = i / nblk, c = i - q * nblk;
+    float x = -1.f;
+    if (HZ_DCHECK(q < p.Q && c * 64 + lane < p.D)) x = p.queries[(long)q * p.D + c * 64 + lane];
+    const unsigned long long m = __ballot((__float_as_uint(x) >> 31) == 0u);
+    if (lane == 0) qb[q * WB + 2 * c] = (unsigned)m, qb[q * WB + 2 * c + 1] = (unsigned)(m >> 32);
+  }
+  if (W < WB)
+    for (int i = t; i < p.Q * (WB - W); i += T) qb[i / (WB - W) * WB + W + i % (WB - W)] = 0u;
+  stage_pass_bits<BinRows>(a, pmask, nullptr, row0, rows);
+  __syncthreads();
+
+  const unsigned pm = pmask[t];  // 0 for a row past the tile's end
+  if (__ballot(pm != 0u) != 0ull) {  // scalar: some row of this wave passes for some query
+    const unsigned* corpus = reinterpret_cast<const unsigned*>(p.corpus);
+    u32x4 v[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      v[c] = u32x4{0u, 0u, 0u, 0u};
+      if (pm != 0u && c * 4 < W && HZ_DCHECK(t < rows && row0 + t < (long)p.N))
+        v[c] = *reinterpret_cast<const u32x4*>(corpus + (row0 + t) * p.ldc + c * 4);
+    }
+    for (int q = 0; q < p.Q; ++q) {
+      int pop = 0;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const u32x4 x = *reinterpret_cast<const u32x4*>(qb + q * WB + c * 4);  // every lane reads the same words
+        pop += __popc(v[c][0] ^ x[0]) + __popc(v[c][1] ^ x[1]) + __popc(v[c][2] ^ x[2]) + __popc(v[c][3] ^ x[3]);
+      }
+      sc[q * T + t] = ((pm >> q) & 1u) ? orderable((float)(p.D - 2 * pop)) : 0u;
+    }
+  } else {
+    for (int q = 0; q < p.Q; ++q) sc[q * T + t] = 0u;
+  }
+  __syncthreads();
+  rank_tile<true>(p, sc, tile, row0, rows);
 }
 
 // -------------------------------------------------------------------------------------- list scan
@@ -1144,6 +1222,40 @@ extern "C" int hz_search_qscan_launch(const HzSearchQuantParams* pp, hipStream_t
   if (!qp.scales) return -24;
   if (reinterpret_cast<uintptr_t>(qp.scales) & 3) return -25;
   return scan_launch<E4m3Rows, true>(qp, st);
+}
+
+// The binary scan's own refusal list (hipzap.h): -80 .. -92. Buckets of 16-B chunks per thread: W <= 8, 24, 32, 64.
+extern "C" int hz_search_bscan_launch(const HzSearchBinParams* pp, hipStream_t st) {
+  if (!pp) return -80;
+  HzSearchBinParams a = *pp;
+  HzSearchFilterParams& f = a.f;
+  HzSearchParams& p = f.s;
+  if (!p.corpus || !p.queries || !p.cand || !p.out_score || !p.out_id) return -80;
+  if (p.D % 128) return -81;
+  if (p.D < 128) return -82;
+  if (p.D > 2048) return -83;
+  const int W = p.D / 32;
+  if (p.ldc < W || p.ldc % 4) return -84;
+  if (p.N < 1) return -85;
+  if (p.Q < 1 || p.Q > HZ_SEARCH_MAX_Q) return -86;
+  if (p.k < 1 || p.k > HZ_SEARCH_MAX_K) return -87;
+  if ((reinterpret_cast<uintptr_t>(p.corpus) & 15) || (reinterpret_cast<uintptr_t>(p.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(p.cand) & 7) || (reinterpret_cast<uintptr_t>(p.out_score) & 3) ||
+      (reinterpret_cast<uintptr_t>(p.out_id) & 3) || (reinterpret_cast<uintptr_t>(f.live) & 3) ||
+      (reinterpret_cast<uintptr_t>(f.tags) & 3) || (reinterpret_cast<uintptr_t>(f.filt) & 3))
+    return -88;
+  if (!f.live) return -89;
+  if (f.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -90;
+  if (f.filt && !f.tags) return -91;
+  const unsigned long long need = hz_search_scratch_bytes(p.N, p.Q, p.k);
+  if (!need || p.cand_bytes < need) return -92;
+  p.ntile = (int)(((long)p.N + T - 1) / T);
+  const dim3 grid(p.ntile), block(T);
+  if (W <= 8) hipLaunchKernelGGL(search_bscan_kernel<2>, grid, block, 0, st, a);
+  else if (W <= 24) hipLaunchKernelGGL(search_bscan_kernel<6>, grid, block, 0, st, a);
+  else if (W <= 32) hipLaunchKernelGGL(search_bscan_kernel<8>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(search_bscan_kernel<16>, grid, block, 0, st, a);
+  return (int)hipGetLastError();
 }
 
 namespace {

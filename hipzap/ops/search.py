@@ -6,6 +6,8 @@ query into ``cand``) and ``HZ_K_SEARCH_MERGE`` (one workgroup per query, ``ntile
 ``k``). ``HZ_K_SEARCH_FSCAN`` (``FilterScanParams``: the same block plus a live bitmap, per-row tags and
 per-query ``{mask, value}`` filters) is the scan over the rows that pass. ``HZ_K_SEARCH_QSCAN``
 (``QuantScanParams``: that block plus one fp32 scale per row) is the filtered scan over rows of OCP e4m3fn bytes.
+``HZ_K_SEARCH_BSCAN`` (``BinScanParams``: the filtered block over uint32 sign-bit rows, ``ldc`` in words) scores
+``D - 2 popcount(query bits xor row bits)``, the queries binarised in the kernel.
 ``HZ_K_SEARCH_RESCORE`` (``RescoreParams``) is the second stage of a two-stage search: one workgroup per query
 re-scores the ``R`` bf16 rows that a merge's ``out_id`` names and writes the best ``k`` of them.
 ``HZ_K_SEARCH_LSCAN`` (``ListScanParams``) is the filtered scan over an IVF index's lists: workgroup (j, q) scans
@@ -60,6 +62,19 @@ class QuantScanParams(C.Structure):
 
     def scan_params(self) -> SearchParams:
         return SearchParams.from_buffer_copy(self)
+
+
+@N.params_of("HZ_K_SEARCH_BSCAN")
+class BinScanParams(C.Structure):
+    """HzSearchBinParams: the fields of ``FilterScanParams`` (``corpus``: uint32 sign-bit rows [N][ldc], ``ldc`` in
+    words; ``live`` is required)."""
+    _fields_ = list(FilterScanParams._fields_)
+
+    def scan_params(self) -> SearchParams:
+        """The merge's block: it reads no row, but checks a bf16 pitch, so ``ldc`` = D there."""
+        sp = SearchParams.from_buffer_copy(self)
+        sp.ldc = sp.D
+        return sp
 
 
 @N.params_of("HZ_K_SEARCH_RESCORE")
@@ -146,6 +161,10 @@ def _sigs(lib):
     N._sig(lib, "hz_search_fscan_launch", C.c_int, C.POINTER(FilterScanParams), P)
     N._sig(lib, "hz_search_qscan_launch", C.c_int, C.POINTER(QuantScanParams), P)
     N._sig(lib, "hz_search_rescore_launch", C.c_int, C.POINTER(RescoreParams), P)
+    N._sig(lib, "hz_search_bscan_launch", C.c_int, C.POINTER(BinScanParams), P)
+    N._sig(lib, "hz_index_add_b", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_add_br", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_read_state_b", C.c_int, P, P, P, P, C.c_longlong)
     N._sig(lib, "hz_search_lscan_launch", C.c_int, C.POINTER(ListScanParams), P)
     N._sig(lib, "hz_search_qlscan_launch", C.c_int, C.POINTER(QuantListScanParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
@@ -208,6 +227,16 @@ def launch_quant(prm: QuantScanParams, stream: int = 0) -> tuple:
     """Quantised scan then merge on ``stream``: (scan code, merge code); no merge after a refused scan."""
     lib = N.lib()
     rc = lib.hz_search_qscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    sp = prm.scan_params()
+    return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def launch_bin(prm: BinScanParams, stream: int = 0) -> tuple:
+    """Binary scan then merge on ``stream``: (scan code, merge code); no merge after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_bscan_launch(C.byref(prm), stream)
     if rc:
         return rc, None
     sp = prm.scan_params()

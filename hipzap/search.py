@@ -31,7 +31,14 @@ layout with version 3's rows (``dtype`` ``"fp8_e4m3"``): codes uint8 ``[capacity
 ``ivf`` block as in version 5. Version 7 is version 6 plus ``"rescore": "bf16"`` and ``rescore_off``: bf16
 ``[count][dim]`` in EXTERNAL-ID order (the rows a plain bf16 index of the same vectors holds), the last block of the
 file -- stage one's candidates carry external ids, so the second stage reads ``rows[id]``. Both come from
-:func:`convert_index`, which trains the lists on the bf16 rows and then quantises.
+:func:`convert_index`, which trains the lists on the bf16 rows and then quantises. Version 8 is a binary index
+(``dtype`` ``"bin_sign"``, ``write_index(dtype="bin")``): version 3's rule set over sign-bit rows -- the row block is
+uint32 ``[count][dim / 32]`` (``dim % 128 == 0``, 128..2048), bit ``i & 31`` of word ``i >> 5`` set iff the sign bit
+of column ``i`` is clear (the live bitmap's bit convention; ``-0.0`` gives 0), no scales block, ``capacity`` /
+``tags_off`` / ``live_off`` present exactly when version 3 would have them. Version 9 is version 8 plus ``"rescore":
+"bf16"`` and ``rescore_off`` as in version 4. Stage one of a search scores ``dim - 2 * popcount(query bits xor row
+bits)``, an integer, so ties are the normal case and the order rule decides them; ``search(refine=R)`` re-scores the
+best R against the bf16 rows exactly as version 4 does (:func:`prepare_rows_bin`).
 
 A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
 positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
@@ -62,15 +69,19 @@ VERSION4 = 4  # version 3 plus the JSON keys rescore / rescore_off and the block
 VERSION5 = 5  # version 2 stored list by list plus the JSON block ivf and the four blocks it names
 VERSION6 = 6  # version 5's layout with version 3's rows: e4m3 codes and fp32 scales for `capacity` stored rows
 VERSION7 = 7  # version 6 plus rescore / rescore_off: bf16 rows [count][dim] in external-id order, the last block
+VERSION8 = 8  # sign-bit rows: uint32 [count][dim / 32], no scales; tags / live as in version 3, or absent
+VERSION9 = 9  # version 8 plus rescore / rescore_off, as version 4 adds them to version 3
 FP8_VERSIONS, IVF_VERSIONS, RESCORE_VERSIONS = (VERSION3, VERSION4, VERSION6, VERSION7), (VERSION5, VERSION6, VERSION7), \
-    (VERSION4, VERSION7)
+    (VERSION4, VERSION7, VERSION9)
+BIN_VERSIONS = (VERSION8, VERSION9)
 TILE = 256   # HZ_SEARCH_TILE (csrc/hipzap.h): an IVF list starts on a tile boundary
 IVF_MAX_LISTS = 65536
 IVF_SAMPLE = 256  # k-means trains on at most this many rows per centroid
 NEIGHBORS_BLOCK = 1024  # rows per pass of knn_graph: HZ_INDEX_SELF_MAX_Q (csrc/hipzap.h), one native call
 IVF_KEYS = ("centroids_off", "list_off_off", "list_tiles_off", "rowid_off")
-DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3"}  # write_index(dtype=...) -> the header's "dtype"
+DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3", "bin": "bin_sign"}  # write_index(dtype=...) -> the header's "dtype"
 FP8 = "fp8_e4m3"
+BIN = "bin_sign"
 METRICS = ("cosine", "ip")
 ALIGN = 4096
 HEAD = struct.Struct("<8sIIQQII")  # HzIndexHeader: magic, version, json_len, data_off, count, dim, metric
@@ -168,6 +179,58 @@ def prepare_rows_fp8(vectors, metric: str):
     return quantize_rows(_checked_rows(vectors, metric, 16, "dim of an fp8 index"))
 
 
+def _pack_signs(clear: np.ndarray) -> np.ndarray:
+    """bool [N, D] ("sign bit clear") -> uint32 [N, D / 32]: bit i & 31 of word i >> 5."""
+    return np.packbits(np.ascontiguousarray(clear, np.uint8), axis=1, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def binarize(v) -> np.ndarray:
+    """fp32 [N, D] (D % 32 == 0) -> sign-bit words uint32 [N, D / 32]: bit ``i & 31`` of word ``i >> 5`` is 1 iff
+    the sign bit of column ``i`` is clear. ``-0.0`` gives 0, ``+0.0`` gives 1."""
+    u = np.ascontiguousarray(v, np.float32).view(np.uint32)
+    return _pack_signs((u >> np.uint32(31)) == 0)
+
+
+def binarize_bf16(bits) -> np.ndarray:
+    """bf16 bit patterns uint16 [N, D] -> the words :func:`binarize` gives for the fp32 values they were rounded
+    from: round-to-nearest-even never changes a sign bit (a value that rounds to zero magnitude keeps its sign)."""
+    return _pack_signs((np.ascontiguousarray(bits, np.uint16) >> np.uint16(15)) == 0)
+
+
+def prepare_rows_bin(vectors, metric: str) -> np.ndarray:
+    """fp32 [N, D] -> the sign-bit words (uint32 [N, D / 32]) a binary index of ``metric`` stores: the checks and the
+    cosine normalisation of :func:`prepare_rows` (D % 128 == 0 here, 128..2048), then :func:`binarize`. The same
+    words as ``binarize_bf16(prepare_rows(vectors, metric))``."""
+    return binarize(_checked_rows(vectors, metric, 128, "dim of a binary index"))
+
+
+_POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.int32)
+
+
+def bin_search_ref(words, qbits, dim: int, k: int, allow=None):
+    """The oracle of a binary index's first stage: row words uint32 [N, W] against query words uint32 [Q, W] ->
+    (scores float64 [Q, k], ids int32 [Q, k]); score = ``dim - 2 * popcount(q xor r)``, an exact integer, under
+    the order rule (higher score first, then the lower id). ``allow`` as in :func:`search_ref`."""
+    words = np.ascontiguousarray(words, np.uint32)
+    qbits = np.ascontiguousarray(qbits, np.uint32)
+    n = words.shape[0]
+    if allow is not None:
+        allow = np.asarray(allow, bool)
+    scores = np.full((qbits.shape[0], k), -np.inf)
+    ids = np.full((qbits.shape[0], k), -1, np.int32)
+    for i, row in enumerate(qbits):
+        ham = _POP8[(words ^ row[None, :]).view(np.uint8)].sum(axis=1) if n else np.zeros(0, np.int32)
+        s = (dim - 2 * ham).astype(np.int64)
+        if allow is None:
+            order = np.argsort(-s, kind="stable")[:k]
+        else:
+            rows = np.flatnonzero(allow if allow.ndim == 1 else allow[i])
+            order = rows[np.argsort(-s[rows], kind="stable")[:k]]
+        scores[i, :order.size] = s[order]
+        ids[i, :order.size] = order
+    return scores, ids
+
+
 def check_tags(tags, n: int) -> np.ndarray:
     """``tags`` as uint32 [n]; integers in 0..2^32-1 only."""
     t = np.asarray(tags)
@@ -200,8 +263,13 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
     6, and with ``rescore`` as well (``[hdr["count"], D]``, in id order) version 7, their block after the tables.
     Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
+    binary = hdr.get("dtype") == BIN  # sign-bit rows: uint32 [N, dim / 32], versions 8 and 9
+    if binary and (ivf is not None or scales is not None or rows.dtype != np.uint32 or rows.shape[1] * 32 != hdr["dim"]):
+        raise ValueError("a binary index holds uint32 rows of dim / 32 words, without scales or lists")
     rshape = rows.shape if ivf is None else (hdr["count"], rows.shape[1])
-    if rescore is not None and (scales is None or rescore.shape != rshape or rescore.dtype != np.uint16):
+    if binary:
+        rshape = (n, hdr["dim"])
+    if rescore is not None and ((scales is None and not binary) or rescore.shape != rshape or rescore.dtype != np.uint16):
         raise ValueError("rescore rows go with fp8 rows of the same shape")
 
     def align(x):
@@ -210,12 +278,14 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         raise ValueError("an IVF index holds rows, tags and a live bitmap for whole tiles")
     blocks = tags is not None or live is not None
     tables = ()  # the four blocks of an IVF index
-    if not blocks and scales is None:
+    if not blocks and scales is None and not binary:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
         if ivf is not None:
             version = VERSION5 if scales is None else VERSION6 if rescore is None else VERSION7
+        elif binary:
+            version = VERSION8 if rescore is None else VERSION9
         else:
             version = VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
         if scales is not None:
@@ -258,11 +328,11 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
                 hdr["ivf"].update(ioffs)
     tmp = path + ".tmp"
     with open(tmp, "wb") as f:
-        f.write(HEAD.pack(MAGIC, version, len(js), data_off, n if ivf is None else hdr["count"], rows.shape[1],
-                          METRICS.index(hdr["metric"])))
+        f.write(HEAD.pack(MAGIC, version, len(js), data_off, n if ivf is None else hdr["count"],
+                          hdr["dim"] if binary else rows.shape[1], METRICS.index(hdr["metric"])))
         f.write(js)
         f.write(bytes(data_off - HEAD.size - len(js)))
-        f.write(rows.tobytes())
+        f.write(rows.astype("<u4").tobytes() if binary else rows.tobytes())
         at = data_off + rows.nbytes
         if scales is not None:
             f.write(bytes(hdr["scales_off"] - at))
@@ -364,18 +434,26 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     into ``nlist`` lists by :func:`ivf_kmeans` (``ivf_seed``, ``ivf_iters``) and stored in :func:`ivf_layout`'s order;
     ``nprobe``: the lists a search scans by default, ``min(nlist, 16)`` when None. Ids stay the positions in
     ``vectors``. ``ivf_backend="gpu"``: the lists come from :meth:`Index.cluster` on ``device`` (:func:`cluster_rows`)
-    in place of :func:`ivf_kmeans`; the file has the same layout either way."""
+    in place of :func:`ivf_kmeans`; the file has the same layout either way. ``dtype="bin"``: sign-bit rows
+    (:func:`prepare_rows_bin`), a version-8 file, with ``rescore=True`` version 9."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    if ivf is not None and dtype == "bin":
+        raise ValueError(f"ivf={ivf!r} with dtype='bin': IVF lists over binary rows are not built")
     if ivf is not None and (dtype != "bf16" or rescore):
         raise ValueError(f"ivf={ivf!r} goes with dtype='bf16' without rescore rows, got dtype={dtype!r}, rescore={rescore!r}: "
                          f"an fp8 or two-stage IVF index is convert_index(bf16 IVF file, dst, 'fp8', rescore=...)")
-    if rescore and dtype != "fp8":
+    if rescore and dtype not in ("fp8", "bin"):
         raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
-    rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
+    if dtype == "bin":
+        rows, scales = prepare_rows_bin(vectors, metric), None
+    else:
+        rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
     rrows = prepare_rows(vectors, metric) if rescore else None
     n, d = rows.shape
+    if dtype == "bin":
+        d *= 32
     if labels is not None:
         labels = [str(s) for s in labels]
         if len(labels) != n:
@@ -464,7 +542,7 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7):
+        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7, VERSION8, VERSION9):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
@@ -475,10 +553,17 @@ def read_header(path: str) -> dict:
     if (hdr["dtype"] == FP8) != fp8:
         raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (version 3 means fp8_e4m3 rows, and so do "
                          f"versions 4, 6 and 7)")
+    binary = version in BIN_VERSIONS
+    if (hdr["dtype"] == BIN) != binary:
+        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (versions 8 and 9 mean bin_sign rows, and no "
+                         f"other version does)")
     if version in RESCORE_VERSIONS and (hdr.get("rescore") != "bf16" or "rescore_off" not in hdr):
         raise ValueError(f"{path}: a version-{version} file without rescore / rescore_off")
     if version not in RESCORE_VERSIONS and ("rescore" in hdr or "rescore_off" in hdr):
-        raise ValueError(f"{path}: rescore keys in a version-{version} file (they belong to versions 4 and 7)")
+        raise ValueError(f"{path}: rescore keys in a version-{version} file (they belong to versions "
+                         f"{'4, 7 and 9' if binary else '4 and 7'})")
+    if binary and (dim < 128 or dim % 128 or dim > 2048):
+        raise ValueError(f"{path}: dim of a binary index must be a multiple of 128 in 128..2048, got {dim}")
     if fp8 and (dim < 16 or dim % 16 or dim > 2048):
         raise ValueError(f"{path}: dim of an fp8 index must be a multiple of 16 in 16..2048, got {dim}")
     if hdr.get("labels") is not None and len(hdr["labels"]) != count:
@@ -497,6 +582,12 @@ def read_header(path: str) -> dict:
         if not 1 <= ivf["nlist"] <= min(count, IVF_MAX_LISTS) or not 1 <= ivf["nprobe"] <= min(ivf["nlist"], MAX_K):
             raise ValueError(f"{path}: ivf nlist {ivf['nlist']} / nprobe {ivf['nprobe']} out of range for {count} rows")
     end = data_off + stored * dim * (1 if fp8 else 2)
+    if binary:
+        end = data_off + stored * (dim // 8)
+        if data_off % ALIGN or data_off < HEAD.size + json_len or end > size:
+            raise ValueError(f"{path}: the row block at {data_off} is unaligned, overlaps the header or lies outside the file")
+        if ("tags_off" in hdr) != ("live_off" in hdr):
+            raise ValueError(f"{path}: a version-{version} file with only one of tags_off / live_off")
     if fp8:
         off = hdr.get("scales_off")
         if not isinstance(off, int) or off % ALIGN:
@@ -509,7 +600,7 @@ def read_header(path: str) -> dict:
         if ("tags_off" in hdr) != ("live_off" in hdr):
             raise ValueError(f"{path}: a version-{version} file with only one of tags_off / live_off")
     last = end  # the end of the last block before a rescore block
-    if version == VERSION2 or is_ivf or (fp8 and "tags_off" in hdr):
+    if version == VERSION2 or is_ivf or ((fp8 or binary) and "tags_off" in hdr):
         for key, nbytes in (("tags_off", 4 * stored), ("live_off", 4 * (-(-stored // 32)))):
             off = hdr.get(key)
             if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
@@ -573,12 +664,18 @@ def file_info(path: str) -> dict:
         info.update(version=VERSION4, rescore=hdr["rescore"])
     if "ivf" in hdr and hdr["dtype"] == FP8:
         info.update(version=VERSION7 if "rescore_off" in hdr else VERSION6)
+    if hdr["dtype"] == BIN:
+        info.update(version=VERSION9 if "rescore_off" in hdr else VERSION8, dtype=BIN)
     return info
 
 
 def read_rows(path: str) -> np.ndarray:
-    """The row block: bf16 bit patterns, uint16 [count, dim]; e4m3fn codes, uint8, for an fp8 index."""
+    """The row block: bf16 bit patterns, uint16 [count, dim]; e4m3fn codes, uint8, for an fp8 index; sign-bit
+    words, uint32 [count, dim / 32], for a binary index."""
     hdr = read_header(path)
+    if hdr["dtype"] == BIN:
+        w = hdr["dim"] // 32
+        return np.fromfile(path, "<u4", hdr["count"] * w, offset=hdr["data_off"]).astype(np.uint32).reshape(hdr["count"], w)
     dt = np.uint8 if hdr["dtype"] == FP8 else np.uint16
     n = stored_rows(hdr)
     return np.fromfile(path, dt, n * hdr["dim"], offset=hdr["data_off"]).reshape(n, hdr["dim"])
@@ -753,6 +850,16 @@ class _QRows:
         self.rescore = None if rescore is None else np.ascontiguousarray(rescore, np.uint16)
 
 
+class _BRows:
+    """What ``add`` hands a backend's ``_append`` on a binary index: the sign-bit words; on an index with rescore
+    rows also ``rescore``, the bf16 bit patterns of the same input. ``shape`` is [n, dim]."""
+
+    def __init__(self, words, dim: int, rescore=None):
+        self.words = np.ascontiguousarray(words, np.uint32)
+        self.shape = (self.words.shape[0], dim)
+        self.rescore = None if rescore is None else np.ascontiguousarray(rescore, np.uint16)
+
+
 class _Base:
     """What both backends share: the header, the argument checks of the mutators and ``save``. A backend
     provides ``_append(bits, tags, publish)`` (which calls ``publish(first id)`` before searches may run again), ``_kill(ids) -> int``, ``_retag(ids, tags)`` and ``_state() -> (bits,
@@ -767,7 +874,9 @@ class _Base:
         self.dtype = self.header["dtype"]
         self.rescore = "rescore_off" in self.header  # a version-4 file: bf16 rows for a second stage
         self.ivf = read_ivf(path) if "ivf" in self.header else None  # the validated tables of a version-5 file
-        if self.ivf:
+        if self.dtype == BIN:
+            self.version = VERSION9 if self.rescore else VERSION8
+        elif self.ivf:
             self.version = VERSION5 if self.dtype != FP8 else VERSION7 if self.rescore else VERSION6
         else:
             self.version = (VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
@@ -810,7 +919,8 @@ class _Base:
         ``nlist`` up scans every list, which is exact; anything else must be an integer in 1..min(nlist, MAX_K)."""
         if self.ivf is None:
             if nprobe is not None:
-                raise ValueError(f"nprobe={nprobe!r} needs an IVF index (write_index(ivf=...)), this one is version {self.version}")
+                raise ValueError(f"nprobe={nprobe!r} needs an IVF index (write_index(ivf=...)), this one is "
+                                 f"{self._bin_name()}version {self.version}")
             return 0
         if refine not in (None, 0) and not self.rescore:
             raise ValueError(f"refine={refine!r}: an IVF index has no rescore rows unless it is a version-7 file "
@@ -825,17 +935,23 @@ class _Base:
                              f"got {nprobe!r}")
         return 0 if nprobe >= nlist else int(nprobe)
 
+    def _bin_name(self) -> str:
+        """"a bin_sign index of " on a binary index (the by-name refusals), else nothing."""
+        return f"a {BIN} index of " if self.dtype == BIN else ""
+
     def _check_probes(self, q, nprobe):
         if self.ivf is None:
-            raise ValueError(f"probes needs an IVF index (write_index(ivf=...)), this one is version {self.version}")
+            raise ValueError(f"probes needs an IVF index (write_index(ivf=...)), this one is {self._bin_name()}version "
+                             f"{self.version}")
         if not _is_int(nprobe) or not 1 <= nprobe <= min(self.ivf["nlist"], MAX_K):
             raise ValueError(f"nprobe must be an integer in 1..{min(self.ivf['nlist'], MAX_K)}, got {nprobe!r}")
         return check_queries(q, self.dim), int(nprobe)
 
     def _check_neighbors(self, ids, k):
         """The refusals of :meth:`neighbors` that both backends share -> (ids int32 [n], k)."""
-        if self.dtype == FP8 or self.ivf is not None:
-            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else f"an {FP8} index"
+        if self.dtype in (FP8, BIN) or self.ivf is not None:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
+                f"a {BIN} index" if self.dtype == BIN else f"an {FP8} index"
             raise ValueError(f"neighbors is built for plain bf16 indexes (versions 1 and 2): this one is {what} of version "
                              f"{self.version}")
         if self.dim % 32:
@@ -844,8 +960,9 @@ class _Base:
 
     def _check_cluster_index(self):
         """:meth:`cluster` is built for plain bf16 indexes with ``dim % 32 == 0``."""
-        if self.dtype == FP8 or self.ivf is not None:
-            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else f"an {FP8} index"
+        if self.dtype in (FP8, BIN) or self.ivf is not None:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
+                f"a {BIN} index" if self.dtype == BIN else f"an {FP8} index"
             raise ValueError(f"cluster is built for plain bf16 indexes (versions 1 and 2): this one is {what} of version "
                              f"{self.version}")
         if self.dim % 32:
@@ -921,6 +1038,9 @@ class _Base:
             raise ValueError("IVF indexes do not take add yet: write a new index with write_index(ivf=...)")
         if self.dtype == FP8:
             bits = _QRows(*prepare_rows_fp8(vectors, self.metric),
+                          rescore=prepare_rows(vectors, self.metric) if self.rescore else None)
+        elif self.dtype == BIN:  # binarised here, on the host: the same words write_index stores
+            bits = _BRows(prepare_rows_bin(vectors, self.metric), np.asarray(vectors).shape[1],
                           rescore=prepare_rows(vectors, self.metric) if self.rescore else None)
         else:
             bits = prepare_rows(vectors, self.metric)
@@ -1002,7 +1122,7 @@ class RefIndex(_Base):
         super().__init__(path)
         self._bits = read_rows(path)
         fp8 = self.dtype == FP8
-        self._rows = e4m3_to_f32(self._bits) if fp8 else bf16_to_f32(self._bits)
+        self._rows = None if self.dtype == BIN else e4m3_to_f32(self._bits) if fp8 else bf16_to_f32(self._bits)
         self.scales = read_scales(path) if fp8 else None
         self._rbits = read_rescore_rows(path) if self.rescore else None
         self._rrows = bf16_to_f32(self._rbits) if self.rescore else None
@@ -1040,7 +1160,10 @@ class RefIndex(_Base):
             if lists:
                 near = (self.ivf["list_of"][None, :, None] == self.probes(q, lists)[:, None, :]).any(axis=2)  # [Q, N]
                 allow = near if allow is None else near & allow
-            s, i = search_ref(self._rows, q, R or k, allow, scales=self.scales)
+            if self.dtype == BIN:  # stage one: exact integer scores over the sign bits, ties by the lower id
+                s, i = bin_search_ref(self._bits, binarize(q), self.dim, R or k, allow)
+            else:
+                s, i = search_ref(self._rows, q, R or k, allow, scales=self.scales)
             if R:
                 two = [rescore_ref(self._rrows, q[a], i[a], k) for a in range(q.shape[0])]
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
@@ -1103,6 +1226,17 @@ class RefIndex(_Base):
 
     def _append(self, bits, tags, publish):
         first = self.count
+        if self.dtype == BIN:
+            if self.rescore:
+                self._rbits = np.concatenate([self._rbits, bits.rescore])
+                self._rrows = np.concatenate([self._rrows, bf16_to_f32(bits.rescore)])
+            self._bits = np.concatenate([self._bits, bits.words])
+            self._tags = np.concatenate([self._tags, tags])
+            self._live = np.concatenate([self._live, np.ones(bits.shape[0], bool)])
+            while self._cap < self._bits.shape[0]:
+                self._cap *= 2
+            publish(first)
+            return first
         if self.scales is not None:
             self.scales = np.concatenate([self.scales, bits.scales])
             if self.rescore:
@@ -1138,7 +1272,7 @@ class RefIndex(_Base):
             scales = np.ones(cap, np.float32)  # padding rows: code 0, scale 1, dead
             scales[pos] = self.scales
             return (bits, tags, live, scales, self._rbits) if self.rescore else (bits, tags, live, scales)
-        if self.rescore:
+        if self.rescore:  # scales: None on a binary index
             return self._bits, self._tags, self._live, self.scales, self._rbits
         if self.scales is not None:
             return self._bits, self._tags, self._live, self.scales
@@ -1155,6 +1289,8 @@ class RefIndex(_Base):
 
     def close(self) -> None:
         self._rows = None
+        if self.dtype == BIN:
+            self._bits = None
 
 
 class Index(_Base):
@@ -1335,12 +1471,18 @@ class Index(_Base):
 
     def _append(self, bits, tags, publish):
         first = C.c_longlong(-1)
-        fp8 = self.dtype == FP8
-        if not fp8:
+        fp8, binary = self.dtype == FP8, self.dtype == BIN
+        if not fp8 and not binary:
             bits = np.ascontiguousarray(bits)
 
         def call():
-            if fp8 and self.rescore:
+            if binary and self.rescore:
+                rc = self._lib.hz_index_add_br(self._h, bits.words.ctypes.data, bits.rescore.ctypes.data, bits.shape[0],
+                                               tags.ctypes.data, C.byref(first))
+            elif binary:
+                rc = self._lib.hz_index_add_b(self._h, bits.words.ctypes.data, bits.shape[0], tags.ctypes.data,
+                                              C.byref(first))
+            elif fp8 and self.rescore:
                 rc = self._lib.hz_index_add_qr(self._h, bits.codes.ctypes.data, bits.scales.ctypes.data,
                                                bits.rescore.ctypes.data, bits.shape[0], tags.ctypes.data, C.byref(first))
             elif fp8:
@@ -1367,6 +1509,16 @@ class Index(_Base):
     def _state(self):
         n = self.count if self.ivf is None else int(self.header["capacity"])  # an IVF index: the stored rows
         tags, words = np.empty(n, np.uint32), np.empty(-(-n // 32), np.uint32)
+        if self.dtype == BIN:
+            rows = np.empty((n, self.dim // 32), np.uint32)
+            self._exclusive(lambda: self._lib.hz_index_read_state_b(self._h, rows.ctypes.data, tags.ctypes.data,
+                                                                    words.ctypes.data, n), "hz_index_read_state_b")
+            if self.rescore:
+                rrows = np.empty((n, self.dim), np.uint16)
+                self._exclusive(lambda: self._lib.hz_index_read_rescore(self._h, rrows.ctypes.data, n),
+                                "hz_index_read_rescore")
+                return rows, tags, unpack_live(words, n), None, rrows
+            return rows, tags, unpack_live(words, n)
         if self.dtype == FP8:
             codes, scales = np.empty((n, self.dim), np.uint8), np.empty(n, np.float32)
             self._exclusive(lambda: self._lib.hz_index_read_state_q(self._h, codes.ctypes.data, scales.ctypes.data,
@@ -1433,9 +1585,14 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
-    if rescore and dtype != "fp8":
+    if rescore and dtype not in ("fp8", "bin"):
         raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
+    if dtype == "bin" and ivf is not None:
+        raise ValueError(f"ivf={ivf!r} with dtype='bin': IVF lists over binary rows are not built")
     hdr = read_header(src)
+    if dtype == "bin" and hdr["dtype"] != "bf16":
+        raise ValueError(f"dtype='bin': {src} holds {hdr['dtype']} rows, and a binary index is converted from a plain bf16 "
+                         f"index (its sign bits are the vectors' own)")
     if hdr["dtype"] != "bf16":
         raise ValueError(f"{src}: only a bf16 index can be converted, this one holds {hdr['dtype']}")
     if ivf is None and (nprobe is not None or ivf_seed != 0 or ivf_iters != 10):
@@ -1444,6 +1601,12 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
         raise ValueError(f"ivf={ivf!r}: {src} is an IVF index already (nlist {hdr['ivf']['nlist']}); its lists are kept")
     if dtype == "fp8" and hdr["dim"] % 16:
         raise ValueError(f"dim of an fp8 index must be a multiple of 16 in 16..2048, got {hdr['dim']}")
+    if dtype == "bin":
+        if "ivf" in hdr:
+            raise ValueError(f"dtype='bin': {src} is an IVF index (nlist {hdr['ivf']['nlist']}), and IVF lists over binary "
+                             f"rows are not built")
+        if hdr["dim"] % 128 or hdr["dim"] < 128:
+            raise ValueError(f"dim of a binary index must be a multiple of 128 in 128..2048, got {hdr['dim']}")
     bits, scales = read_rows(src), None
     out = {k: hdr[k] for k in ("dim", "count") if k in hdr}
     out.update(dtype=DTYPES[dtype], metric=hdr["metric"], model=hdr.get("model", ""), embed=hdr.get("embed"))
@@ -1480,5 +1643,7 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     rrows = bits if rescore else None
     if dtype == "fp8":
         bits, scales = quantize_rows(bf16_to_f32(bits))
+    if dtype == "bin":  # the sign bits of the stored rows: what binarising the fp32 vectors gives
+        bits = binarize_bf16(bits)
     return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
                        hdr.get("capacity"), scales=scales, rescore=rrows)
