@@ -2,6 +2,7 @@
 // Every struct here is mirrored field-for-field by a ctypes.Structure; keep them in sync.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -600,6 +601,59 @@ int hz_search_mscan_launch(const HzSearchSelfParams* p, hipStream_t st);
 // cand [ntile][Q][k] -> out_score / out_id [Q][k]. Reads cand, out_*, N, Q, k and cand_bytes of the block only.
 // Refusals: -50 cand, out_score or out_id null; -55; -56; -57; -58 cand not 8-B or out_* not 4-B aligned; -60.
 int hz_search_mergen_launch(const HzSearchSelfParams* p, hipStream_t st);
+// batch scan (HZ_K_SEARCH_XSCAN): the self scan with an EXTERNAL A operand -- fp32 queries [Q][D] in
+// place of `qid`, no skip_self. The grid, the tiles, the live bitmap's rules (a group of 16 rows with no live row is
+// not loaded, a dead row of a mixed group is loaded and scores the sentinel), the candidate layout
+// cand[(tile*Q + q)*k ..], the keys and their total order are HZ_K_SEARCH_MSCAN's. A query slot at or past Q loads
+// nothing and writes nothing. HZ_K_SEARCH_MERGEN reduces the lists and takes THIS block as it stands: the two blocks
+// have the same layout (`queries` where `qid` is, two unused ints where skip_self is) and the merge reads neither.
+// THE SPLIT. A finite fp32 x is the exact sum of three bf16 values: h = the value of (bits(x) & 0xFFFF0000),
+// m = the same truncation of x - h, l = (x - h) - m; both differences are exact in fp32 and l has at most 8
+// significant bits. Then each of h, m, l whose exponent field is zero is replaced by a zero of its own sign, giving
+// h', m', l' and the EFFECTIVE QUERY x' = h' + m' + l'. x' is a function of x alone (it does not depend on whether the
+// matrix unit flushes subnormal inputs); x' == x unless a term is below 2^-126, which needs |x| < 2^-102.
+// hipzap.search.split3 is the same function in numpy.
+// CONTRACT. Every product of a term and a bf16 row value is exact in fp32. There is ONE accumulator per (q, r),
+// starting from +0; per 32-column step s = 0, 1, ... (columns 32s .. 32s+31, ascending) it receives three MFMAs
+// (v_mfma_f32_16x16x32_bf16, the query terms as the A operand) in the fixed order l', m', h'. The bits of score(q, r)
+// depend on the D values of the query and of the row only: not on N, Q, k, the row's tile or position, the query's
+// slot, or the other queries of the block. They are NOT the bits of HZ_K_SEARCH_SCAN (one fmaf chain per lane and a
+// butterfly) or of HZ_K_SEARCH_MSCAN (one MFMA per step over a bf16 query). Error: the 3D additions inside and
+// between the MFMAs are not documented as round-to-nearest, so against the exact sum_i x'_i r_i
+//   |score - exact| <= beta(3D) * sum_i (|h'_i| + |m'_i| + |l'_i|) |r_i|,  beta(n) = n 2^-23 / (1 - n 2^-23).
+// Refusals (nothing is launched; one code per case, the self scan's -50 .. -60 moved to -100 .. -110. They share the
+// numbers -100 and -102 with hz_launch_kernel's "unknown kind" and "launcher not linked", which this kind never
+// returns through a library that holds it): -100 corpus, queries, live or cand null; -101 D % 32; -102 D < 32;
+// -103 D > 2048; -104 ldc < D or ldc % 8; -105 N < 1; -106 Q outside 1..HZ_SEARCH_SELF_MAX_Q; -107 k outside
+// 1..HZ_SEARCH_MAX_K; -108 corpus not 16-B, cand not 8-B or live not 4-B aligned; -109 live_bytes < 4 * ceil(N / 32);
+// -110 cand_bytes < ntile * Q * k * 8; -111 queries not 16-B aligned.
+typedef struct HzSearchBatchParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows (ldc % 8 == 0), ldc >= D
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5 (required)
+  unsigned long long* cand;      // scratch [ntile][Q][k] keys
+  float* out_score;              // fp32 [Q][k]  (HZ_K_SEARCH_MERGEN only)
+  int* out_id;                   // int32 [Q][k] (HZ_K_SEARCH_MERGEN only)
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  unsigned long long cand_bytes; // bytes of `cand`, at least hz_search_self_scratch_bytes(N, Q, k)
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launchers: ceil(N / HZ_SEARCH_TILE)
+  int pad_[2];                   // HzSearchSelfParams' skip_self and pad_: unused
+} HzSearchBatchParams;
+#ifdef __cplusplus
+static_assert(sizeof(HzSearchBatchParams) == sizeof(HzSearchSelfParams) &&
+                  offsetof(HzSearchBatchParams, cand) == offsetof(HzSearchSelfParams, cand) &&
+                  offsetof(HzSearchBatchParams, out_id) == offsetof(HzSearchSelfParams, out_id) &&
+                  offsetof(HzSearchBatchParams, cand_bytes) == offsetof(HzSearchSelfParams, cand_bytes) &&
+                  offsetof(HzSearchBatchParams, ntile) == offsetof(HzSearchSelfParams, ntile),
+              "HZ_K_SEARCH_MERGEN reads a batch block through HzSearchSelfParams");
+#endif
+int hz_search_xscan_launch(const HzSearchBatchParams* p, hipStream_t st);
+// rescore for any number of queries (HZ_K_SEARCH_RESCOREN): search_rescore_kernel as it stands, one workgroup per
+// query, behind a launcher that accepts Q up to HZ_SEARCH_SELF_MAX_Q -- as HZ_K_SEARCH_MERGEN stands to
+// HZ_K_SEARCH_MERGE. The block, the score bits and every other refusal are HZ_K_SEARCH_RESCORE's (-4: Q outside
+// 1..HZ_SEARCH_SELF_MAX_Q).
+int hz_search_rescoren_launch(const HzSearchRescoreParams* p, hipStream_t st);
 // nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
 // of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
 // of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
@@ -772,8 +826,23 @@ int hz_index_read_state_b(void* idx, unsigned* words_out, unsigned* tags_out, un
 // -37: a deleted id (hz_index_last_error names the value in each case).
 #define HZ_INDEX_SELF_MAX_Q 1024
 int hz_index_neighbors(void* idx, int ctx, const int* ids, int n, int k, int skip_self, float* out_score, int* out_id);
-// the ids one hz_index_neighbors call takes; set in 1..HZ_INDEX_SELF_MAX_Q lowers or restores it first (0: only read)
+// the ids one hz_index_neighbors call (and the queries one hz_index_search_batch call) takes; set in
+// 1..HZ_INDEX_SELF_MAX_Q lowers or restores it first (0: only read)
 int hz_index_neighbors_max(void* idx, int set);
+// bulk search (a plain bf16 index, versions 1 and 2, dim % 32 == 0): Q external fp32 queries at once
+// -> out_score fp32 [Q][k], out_id int32 [Q][k], -inf / -1 past the live rows, and out_stage1_last fp32 [Q]. Replays
+// H2D of the queries, HZ_K_SEARCH_XSCAN at k = R, HZ_K_SEARCH_MERGEN (the R best rows of each query by the batch
+// scan's score), HZ_K_SEARCH_RESCOREN of those ids against the index's own rows (R -> k, the bits and the order of
+// hz_index_search) and three D2H; captured per (Q, k, R) under hz_index_neighbors' program rules. out_stage1_last[q]
+// is the batch scan's score of query q's R-th candidate, -inf when fewer than R rows passed: all the host needs to
+// prove that no row outside the candidates can belong to the answer (hipzap.search.batch_certain). One call takes
+// at most hz_index_neighbors_max queries (HZ_INDEX_SELF_MAX_Q unless lowered; the caller splits above it); a
+// context's buffers for it are allocated on first use and the candidate scratch, shared with hz_index_neighbors and
+// grown on demand, is ceil(capacity / HZ_SEARCH_TILE) * Q * R * 8 bytes.
+// -4: Q outside 1..the maximum; -5: k; -28: R outside k..HZ_SEARCH_MAX_K; -44: an fp8, a binary or an IVF index;
+// -45: dim % 32 (hz_index_last_error names the value in each case).
+int hz_index_search_batch(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                          float* out_stage1_last);
 // clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
 // context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
 // and grown on demand (a call that needs no more than an earlier one allocates nothing).
@@ -980,7 +1049,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_MERGEN, 40, HzSearchSelfParams, hz_search_mergen_op, SEARCH)   \
   X(SEARCH_ASSIGN, 41, HzSearchAssignParams, hz_search_assign_op, SEARCH) \
   X(SEARCH_CMEAN, 42, HzSearchCmeanParams, hz_search_cmean_op, SEARCH)   \
-  X(SEARCH_BSCAN, 43, HzSearchBinParams, hz_search_bscan_op, SEARCH)
+  X(SEARCH_BSCAN, 43, HzSearchBinParams, hz_search_bscan_op, SEARCH)     \
+  X(SEARCH_XSCAN, 44, HzSearchBatchParams, hz_search_xscan_op, SEARCH)    \
+  X(SEARCH_RESCOREN, 45, HzSearchRescoreParams, hz_search_rescoren_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -45,6 +45,10 @@
 // HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two D2H, with the filtered programs' N (the rows past the count are dead
 // in the bitmap) and so under their invalidation rules. A context's buffers for it (ids, results, candidate
 // scratch) are allocated on the first such call; the scratch grows to the largest (n, k) asked for.
+//
+// Bulk search (a plain bf16 index): hz_index_search_batch replays H2D of the queries, HZ_K_SEARCH_XSCAN
+// and HZ_K_SEARCH_MERGEN at k = R, HZ_K_SEARCH_RESCOREN of those ids against the index's own rows (R -> k) and three
+// D2H (scores, ids, stage one's scores), with the neighbours programs' N and rules and their candidate scratch.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -96,8 +100,15 @@ struct Ctx {
   int* nid_dev = nullptr;
   char* nout_dev = nullptr;
   char* nout_host = nullptr;
-  unsigned long long* ncand = nullptr;
+  unsigned long long* ncand = nullptr;  // shared with bulk search
   uint64_t ncand_bytes = 0;
+  // bulk search only, allocated on first use: the queries [SELF_MAX_Q][dim] (pinned, device), stage one's results and
+  // the final ones (device, the layout of nout_dev), and pinned: scores, ids, then stage one's scores
+  float* bq_host = nullptr;
+  float* bq_dev = nullptr;
+  char* bmid_dev = nullptr;
+  char* bout_dev = nullptr;
+  char* bout_host = nullptr;
   // clustering only (hz_index_assign / hz_index_cmean), device memory allocated on first use and grown on demand:
   // centroids bf16 [C][dim]; live AND mask, cap / 8 bytes; lists int32 then scores fp32, [scan rows] each; the
   // members int32 [M]; seg_off int32 [C + 1]; the fp32 centroids [C][dim]
@@ -105,7 +116,7 @@ struct Ctx {
   void* cl[kClBufs] = {};
   uint64_t cl_bytes[kClBufs] = {};
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
-  // probes alone; neighbours: (n, k, 3, skip_self, 0)
+  // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
@@ -178,6 +189,11 @@ struct Index {
       if (c->nid_dev) (void)hipFree(c->nid_dev);
       if (c->nout_dev) (void)hipFree(c->nout_dev);
       if (c->ncand) (void)hipFree(c->ncand);
+      if (c->bq_host) (void)hipHostFree(c->bq_host);
+      if (c->bout_host) (void)hipHostFree(c->bout_host);
+      if (c->bq_dev) (void)hipFree(c->bq_dev);
+      if (c->bmid_dev) (void)hipFree(c->bmid_dev);
+      if (c->bout_dev) (void)hipFree(c->bout_dev);
       for (void* b : c->cl)
         if (b) (void)hipFree(b);
       if (c->st) (void)hipStreamDestroy(c->st);
@@ -300,9 +316,90 @@ struct Index {
     return g;
   }
 
+  // The candidate scratch of the neighbours and bulk-search programs for (n, k) (the caller holds c.mu): one too
+  // small is replaced, and with it the context's programs of both sorts, which hold its address by value.
+  bool self_scratch(Ctx& c, int n, int k) {
+    const uint64_t need = hz_search_self_scratch_bytes((long long)scan_rows(), n, k);
+    if (!need) return false;
+    if (need <= c.ncand_bytes) return true;
+    for (auto it = c.progs.begin(); it != c.progs.end();) {
+      if (std::get<2>(it->first) == 3 || std::get<2>(it->first) == 4) {
+        hz_prog_destroy(it->second);
+        it = c.progs.erase(it);
+      } else {
+        ++it;
+      }
+    }
+    if (c.ncand) (void)hipFree(c.ncand);
+    c.ncand = nullptr, c.ncand_bytes = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&c.ncand), need) != hipSuccess) return false;
+    c.ncand_bytes = need;
+    return true;
+  }
+
+  // The bulk-search program of (Q, k, R) (the caller holds c.mu): H2D of the queries, batch scan and merge at k = R
+  // into bmid_dev, rescore of those ids against `rows` into bout_dev, D2H of the scores, the ids and stage one's scores.
+  HzProgram batch_program(Ctx& c, int Q, int k, int R, bool* fresh) {
+    const size_t qbytes = (size_t)HZ_INDEX_SELF_MAX_Q * h.dim * 4;
+    if (!c.bq_host) {
+      bool ok = hipHostMalloc(reinterpret_cast<void**>(&c.bq_host), qbytes, hipHostMallocDefault) == hipSuccess;
+      ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c.bout_host), 3 * kSelfOutHalf, hipHostMallocDefault) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bq_dev), qbytes) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bmid_dev), 2 * kSelfOutHalf) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bout_dev), 2 * kSelfOutHalf) == hipSuccess;
+      if (!ok) {
+        if (c.bq_host) (void)hipHostFree(c.bq_host);
+        if (c.bout_host) (void)hipHostFree(c.bout_host);
+        if (c.bq_dev) (void)hipFree(c.bq_dev);
+        if (c.bmid_dev) (void)hipFree(c.bmid_dev);
+        if (c.bout_dev) (void)hipFree(c.bout_dev);
+        c.bq_host = c.bq_dev = nullptr, c.bout_host = c.bmid_dev = c.bout_dev = nullptr;
+        return nullptr;
+      }
+    }
+    if (!self_scratch(c, Q, R)) return nullptr;
+    const auto key = std::make_tuple(Q, k, 4, R, 0);
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    HzSearchBatchParams p{};
+    p.corpus = rows;
+    p.queries = c.bq_dev;
+    p.live = live;
+    p.cand = c.ncand;
+    p.out_score = reinterpret_cast<float*>(c.bmid_dev);
+    p.out_id = reinterpret_cast<int*>(c.bmid_dev + kSelfOutHalf);
+    p.live_bytes = cap / 8;
+    p.cand_bytes = c.ncand_bytes;
+    p.N = (int)scan_rows();
+    p.D = p.ldc = (int)h.dim;
+    p.Q = Q, p.k = R;
+    HzSearchRescoreParams rp{};
+    rp.rows = rows;
+    rp.queries = c.bq_dev;
+    rp.in_id = p.out_id;
+    rp.out_score = reinterpret_cast<float*>(c.bout_dev);
+    rp.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
+    HzProgram g = hz_prog_create();
+    const size_t qk = (size_t)Q * k * 4;
+    int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_XSCAN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, sizeof(p), 0);  // the same layout: hipzap.h
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
   // The neighbours program of (n, k, skip_self) (the caller holds c.mu): H2D of the ids, self scan, merge, two D2H.
-  // Its buffers come first; candidate scratch too small for (n, k) is replaced, and with it the context's
-  // neighbours programs, which hold its address by value.
+  // Its buffers come first, then the candidate scratch (self_scratch).
   HzProgram self_program(Ctx& c, int n, int k, int skip_self, bool* fresh) {
     if (!c.nid_host) {
       bool ok = hipHostMalloc(reinterpret_cast<void**>(&c.nid_host), (size_t)HZ_INDEX_SELF_MAX_Q * 4, hipHostMallocDefault) == hipSuccess;
@@ -318,22 +415,7 @@ struct Index {
         return nullptr;
       }
     }
-    const uint64_t need = hz_search_self_scratch_bytes((long long)scan_rows(), n, k);
-    if (!need) return nullptr;
-    if (need > c.ncand_bytes) {
-      for (auto it = c.progs.begin(); it != c.progs.end();) {
-        if (std::get<2>(it->first) == 3) {
-          hz_prog_destroy(it->second);
-          it = c.progs.erase(it);
-        } else {
-          ++it;
-        }
-      }
-      if (c.ncand) (void)hipFree(c.ncand);
-      c.ncand = nullptr, c.ncand_bytes = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&c.ncand), need) != hipSuccess) return nullptr;
-      c.ncand_bytes = need;
-    }
+    if (!self_scratch(c, n, k)) return nullptr;
     const auto key = std::make_tuple(n, k, 3, skip_self, 0);
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
@@ -780,6 +862,7 @@ int hz_index_describe(void* h, uint64_t* out) {
     progs += c->progs.size();
     dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf + (c->mid_dev ? 2 * kOutHalf : 0);
     dev += c->ncand_bytes + (c->nid_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 + 2 * kSelfOutHalf : 0);  // neighbours, once used
+    dev += c->bq_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * x->h.dim * 4 + 4 * kSelfOutHalf : 0;  // bulk search, once used
     for (const uint64_t b : c->cl_bytes) dev += b;  // clustering, once used
   }
   const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
@@ -950,6 +1033,55 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
   if (rc) return rc;
   std::memcpy(out_score, c.nout_host, (size_t)n * k * 4);
   std::memcpy(out_id, c.nout_host + kSelfOutHalf, (size_t)n * k * 4);
+  if (fresh) {
+    rc = hz_prog_capture(g, c.st);
+    if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  }
+  return rc;
+}
+
+int hz_index_search_batch(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                          float* out_stage1_last) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (x->fp8 || x->ivf || x->bin) {
+    g_err = std::string("index: search_batch is built for plain bf16 indexes (versions 1 and 2), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin ? "a bin_sign index" : "an fp8_e4m3 index") + " of version " +
+            std::to_string(x->h.version);
+    return -44;
+  }
+  if (x->h.dim % 32) {
+    g_err = "index: search_batch needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -45;
+  }
+  if (k < 1 || k > HZ_SEARCH_MAX_K) {
+    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
+    return -5;
+  }
+  if (R < k || R > HZ_SEARCH_MAX_K) {
+    g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " +
+            std::to_string(k);
+    return -28;
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
+  if (Q < 1 || Q > x->self_max) {
+    g_err = "index: search_batch takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
+    return -4;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->batch_program(c, Q, k, R, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
+  if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  if (rc) return rc;
+  std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
+  std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
+  const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);  // [Q][R], best first
+  for (int q = 0; q < Q; ++q) out_stage1_last[q] = s1[(size_t)q * R + R - 1];
   if (fresh) {
     rc = hz_prog_capture(g, c.st);
     if (!rc) rc = (int)hipStreamSynchronize(c.st);

@@ -480,6 +480,14 @@ extern "C" __attribute__((weak)) int hz_search_bscan_launch(const HzSearchBinPar
 static int hz_search_bscan_op(const HzSearchBinParams* p, hipStream_t st) {
   return hz_search_bscan_launch ? hz_search_bscan_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_xscan_launch(const HzSearchBatchParams* p, hipStream_t st);
+static int hz_search_xscan_op(const HzSearchBatchParams* p, hipStream_t st) {
+  return hz_search_xscan_launch ? hz_search_xscan_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_rescoren_launch(const HzSearchRescoreParams* p, hipStream_t st);
+static int hz_search_rescoren_op(const HzSearchRescoreParams* p, hipStream_t st) {
+  return hz_search_rescoren_launch ? hz_search_rescoren_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -11,11 +11,14 @@
 //   * search_mscan — the self scan (kind MSCAN): the queries are rows of the corpus named by id; workgroup (tile, block
 //                    of 64 queries) scores them with the bf16 MFMA and cuts before it ranks. Kind MERGEN is
 //                    search_merge behind a launcher that takes any number of queries
+//   * search_xscan — the batch scan (kind XSCAN): the self scan over EXTERNAL fp32 queries, each split in registers
+//                    into three bf16 terms that sum to it, so the MFMA scores the unrounded query. Kind RESCOREN is
+//                    search_rescore behind a launcher that takes any number of queries
 //   * search_assign — the nearest centroid of every row (kind ASSIGN): the self scan with the roles turned, a running
 //                    top-1 key per row; search_cmean (kind CMEAN): a cluster's mean in a fixed summation order
 //   * search_bscan — the filtered scan over sign-bit rows (kind BSCAN): one word per 32 columns, the queries binarised
 //                    in the kernel, score = D - 2 popcount(q xor r); its lists go to search_merge like any other
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u for the reasoning.
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -731,6 +734,77 @@ static_assert(QB == 64 && T == 256 && QB % 16 == 0, "the fragment and selection 
 // dynamic LDS: scores [QB][MSCAN_TS] u32, the waves' pools [4][T] u64, the block's ids [QB], live words [T / 32]
 constexpr size_t MSCAN_LDS = (size_t)QB * MSCAN_TS * 4 + 4 * (size_t)T * 8 + QB * 4 + T / 32 * 4;
 
+// The tile's live words -> lv[T / 32] with the bits from N on cleared (threads t < T / 32; the caller's barrier
+// publishes them). live words [row0/32, row0/32 + 8) under word*32 < N: the launchers check live_bytes.
+__device__ __forceinline__ void stage_live_words(const unsigned* live, unsigned long long live_bytes, int N, long row0, int rows,
+                                                 unsigned* lv) {
+  const int t = threadIdx.x;
+  if (t < T / 32) {
+    const long word = (row0 >> 5) + t;
+    unsigned v = 0u;
+    if (word * 32 < (long)N && HZ_DCHECK((word + 1) * 4 <= (long)live_bytes)) v = live[word];
+    const int left = rows - t * 32;  // the tile's rows from this word on
+    if (left < 32) v &= left <= 0 ? 0u : (1u << left) - 1u;
+    lv[t] = v;
+  }
+}
+
+// The selection of the self scan and of the batch scan (the comment above: radix cut, compaction, ranking): the
+// block's nq queries from the score array sc[q][row] into cand[(tile*Q + q0 + q)*k ..], wave w taking the queries
+// w, w + 4, ... one at a time through its pool.
+__device__ __forceinline__ void mscan_select(const unsigned* sc, unsigned long long* pool, unsigned long long* cand,
+                                             unsigned long long cand_bytes, int Q, int k, int tile, int q0, int nq, long row0,
+                                             int w, int lane) {
+  unsigned long long* mine_pool = pool + w * T;
+  for (int i = 0; i * 4 < nq; ++i) {  // block-uniform trips: the barriers below are reached by every wave
+    const int q = i * 4 + w;
+    const bool valid = q < nq;  // wave-uniform
+    int n = 0, npass = 0;
+    if (valid) {
+      unsigned long long key[4];
+      unsigned mx = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned s = sc[q * MSCAN_TS + j * 64 + lane];
+        key[j] = s ? ((unsigned long long)s << 32) | (unsigned)~(unsigned)(row0 + j * 64 + lane) : 0ull;
+        npass += __popcll(__ballot(s != 0u));
+        mx = s > mx ? s : mx;
+      }
+      unsigned thr = 0u;
+      if (k <= 64) {  // the largest prefix that at least k of the lanes' maxima reach; 0: fewer than k lanes pass
+        for (int bit = 31; bit >= 32 - MSCAN_CUT_BITS; --bit) {
+          const unsigned c = thr | (1u << bit);
+          if (__popcll(__ballot(mx >= c)) >= k) thr = c;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool keep = key[j] != 0ull && (unsigned)(key[j] >> 32) >= thr;
+        const unsigned long long m = __ballot(keep);
+        const int at = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (keep && HZ_DCHECK(at < T)) mine_pool[at] = key[j];
+        n += __popcll(m);
+      }
+    }
+    __syncthreads();
+    if (valid) {
+      const long slot = (long)tile * Q + q0 + q;
+      unsigned long long* out = cand + slot * k;
+      const bool slot_ok = HZ_DCHECK(q0 + q < Q && (slot + 1) * k * 8 <= (long)cand_bytes);
+      for (int e = lane; e < n; e += 64) {
+        const unsigned long long mine = mine_pool[e];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += mine_pool[j] > mine;  // every lane reads the same word: a broadcast
+        if (rank < k && slot_ok) out[rank] = mine;
+      }
+      const int filled = min(k, npass);  // n >= filled: the cut keeps at least k keys, or every passing one
+      for (int s = lane; s < k; s += 64)
+        if (s >= filled && slot_ok) out[s] = 0ull;
+    }
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(T) void search_mscan_kernel(const HzSearchSelfParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   unsigned* sc = reinterpret_cast<unsigned*>(lds);                                     // [QB][MSCAN_TS]
@@ -751,14 +825,7 @@ __global__ __launch_bounds__(T) void search_mscan_kernel(const HzSearchSelfParam
     if (t < nq && HZ_DCHECK(q0 + t < p.Q)) id = p.qid[q0 + t];
     qids[t] = (unsigned)id < (unsigned)p.N ? id : -1;
   }
-  if (t < T / 32) {
-    const long word = (row0 >> 5) + t;
-    unsigned v = 0u;
-    if (word * 32 < (long)p.N && HZ_DCHECK((word + 1) * 4 <= (long)p.live_bytes)) v = p.live[word];
-    const int left = rows - t * 32;  // the tile's rows from this word on
-    if (left < 32) v &= left <= 0 ? 0u : (1u << left) - 1u;
-    lv[t] = v;
-  }
+  stage_live_words(p.live, p.live_bytes, p.N, row0, rows, lv);
   __syncthreads();
 
   const int lr = lane & 15, lh = lane >> 4;
@@ -842,54 +909,156 @@ __global__ __launch_bounds__(T) void search_mscan_kernel(const HzSearchSelfParam
     }
   __syncthreads();
 
-  unsigned long long* mine_pool = pool + w * T;
-  for (int i = 0; i * 4 < nq; ++i) {  // block-uniform trips: the barriers below are reached by every wave
-    const int q = i * 4 + w;
-    const bool valid = q < nq;  // wave-uniform
-    int n = 0, npass = 0;
-    if (valid) {
-      unsigned long long key[4];
-      unsigned mx = 0u;
+  mscan_select(sc, pool, p.cand, p.cand_bytes, p.Q, p.k, tile, q0, nq, row0, w, lane);
+}
+
+// ------------------------------------------------------------------------------------- batch scan
+// search_xscan_kernel (HZ_K_SEARCH_XSCAN): the self scan with an EXTERNAL A operand. Workgroup (tile,
+// qb) scores the tile's T rows against the fp32 queries qb*QB .. qb*QB + QB - 1. The grid, the B-operand loads, the
+// live words and the group skip, the score array, the selection and the candidate layout are the self scan's (the
+// shared functions above); there is no qid and no skip_self.
+// A operand: a lane's fragment is 8 consecutive columns of one query, two 16-byte loads of fp32, split in registers
+// into three bf16x8 fragments (split3 below; hipzap.h states the split). A query slot at or past Q loads nothing;
+// a group of 16 slots past Q is neither split nor multiplied (a scalar branch).
+// CONTRACT (hipzap.h): one set of accumulators; per 32-column step the MFMAs of an accumulator are issued in the
+// order l, m, h, the steps in column order from +0. Every product of a bf16 term and a bf16 row value is exact.
+// Registers: the k-steps are loaded ONE at a time, one ahead of the MFMAs -- a step's A operand is 8 VGPRs per query
+// group where the self scan's is 4, so its pairs would not fit beside the 64 accumulators at 2 waves per SIMD.
+// Addresses: queries[q*D + kk*32 + lh*8 .. + 8) under q < Q and kk < D / 32; the tile's rows under row < N; live
+// words through stage_live_words; cand through mscan_select (q < Q, `rank` used only under rank < k).
+// dynamic LDS: scores [QB][MSCAN_TS] u32, the waves' pools [4][T] u64, live words [T / 32]
+constexpr size_t XSCAN_LDS = (size_t)QB * MSCAN_TS * 4 + 4 * (size_t)T * 8 + T / 32 * 4;
+
+// the bits of one term of the split: a term whose exponent field is zero becomes a zero of its sign
+__device__ __forceinline__ unsigned split_term(unsigned b) { return (b & 0x7f800000u) ? b : (b & 0x80000000u); }
+
+// x -> the fp32 bits of h', m', l' (each a bf16 value: the low 16 bits are zero). h = the top 16 bits of x,
+// m = the top 16 bits of x - h, l = (x - h) - m, both differences exact in fp32; then split_term on each.
+__device__ __forceinline__ void split3(float x, unsigned& h, unsigned& m, unsigned& l) {
+  const unsigned hb = __float_as_uint(x) & 0xffff0000u;
+  const float r1 = x - __uint_as_float(hb);
+  const unsigned mb = __float_as_uint(r1) & 0xffff0000u;
+  const unsigned lb = __float_as_uint(r1 - __uint_as_float(mb));
+  h = split_term(hb), m = split_term(mb), l = split_term(lb);
+}
+
+// 8 consecutive columns of a query -> its three MFMA fragments
+__device__ __forceinline__ void split_frag(const f32x4 lo, const f32x4 hi, bf16x8& fh, bf16x8& fm, bf16x8& fl) {
+  const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  u32x4 wh, wm, wl;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const unsigned s = sc[q * MSCAN_TS + j * 64 + lane];
-        key[j] = s ? ((unsigned long long)s << 32) | (unsigned)~(unsigned)(row0 + j * 64 + lane) : 0ull;
-        npass += __popcll(__ballot(s != 0u));
-        mx = s > mx ? s : mx;
-      }
-      unsigned thr = 0u;
-      if (p.k <= 64) {  // the largest prefix that at least k of the lanes' maxima reach; 0: fewer than k lanes pass
-        for (int bit = 31; bit >= 32 - MSCAN_CUT_BITS; --bit) {
-          const unsigned c = thr | (1u << bit);
-          if (__popcll(__ballot(mx >= c)) >= p.k) thr = c;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool keep = key[j] != 0ull && (unsigned)(key[j] >> 32) >= thr;
-        const unsigned long long m = __ballot(keep);
-        const int at = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (keep && HZ_DCHECK(at < T)) mine_pool[at] = key[j];
-        n += __popcll(m);
-      }
-    }
-    __syncthreads();
-    if (valid) {
-      const long slot = (long)tile * p.Q + q0 + q;
-      unsigned long long* out = p.cand + slot * p.k;
-      const bool slot_ok = HZ_DCHECK(q0 + q < p.Q && (slot + 1) * p.k * 8 <= (long)p.cand_bytes);
-      for (int e = lane; e < n; e += 64) {
-        const unsigned long long mine = mine_pool[e];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += mine_pool[j] > mine;  // every lane reads the same word: a broadcast
-        if (rank < p.k && slot_ok) out[rank] = mine;
-      }
-      const int filled = min(p.k, npass);  // n >= filled: the cut keeps at least k keys, or every passing one
-      for (int s = lane; s < p.k; s += 64)
-        if (s >= filled && slot_ok) out[s] = 0ull;
-    }
-    __syncthreads();
+  for (int j = 0; j < 4; ++j) {
+    unsigned h0, m0, l0, h1, m1, l1;
+    split3(x[2 * j], h0, m0, l0);
+    split3(x[2 * j + 1], h1, m1, l1);
+    wh[j] = (h0 >> 16) | h1, wm[j] = (m0 >> 16) | m1, wl[j] = (l0 >> 16) | l1;  // the low halves are zero
   }
+  fh = __builtin_bit_cast(bf16x8, wh), fm = __builtin_bit_cast(bf16x8, wm), fl = __builtin_bit_cast(bf16x8, wl);
+}
+
+__global__ __launch_bounds__(T) void search_xscan_kernel(const HzSearchBatchParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  unsigned* sc = reinterpret_cast<unsigned*>(lds);                                     // [QB][MSCAN_TS]
+  unsigned long long* pool = reinterpret_cast<unsigned long long*>(sc + QB * MSCAN_TS);  // [4][T]
+  unsigned* lv = reinterpret_cast<unsigned*>(pool + 4 * T);                            // [T / 32]
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int tile = blockIdx.x, q0 = blockIdx.y * QB;
+  if (!HZ_DCHECK(tile < p.ntile && (long)tile * T < (long)p.N && q0 < p.Q && p.D >= 32 && p.D % 32 == 0 && p.D <= 2048 &&
+                 p.ldc >= p.D && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K))
+    return;
+  const long row0 = (long)tile * T;
+  const int rows = (int)min((long)T, (long)p.N - row0);
+  const int nq = min(QB, p.Q - q0);
+  stage_live_words(p.live, p.live_bytes, p.N, row0, rows, lv);
+  __syncthreads();
+
+  const int lr = lane & 15, lh = lane >> 4;
+  unsigned gm[4], any = 0u;  // the live bits of this wave's four groups (wave-uniform)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int g = w * 4 + j;
+    gm[j] = (__builtin_amdgcn_readfirstlane(lv[g >> 1]) >> ((g & 1) * 16)) & 0xffffu;
+    any |= gm[j];
+  }
+  f32x4 acc[4][4];  // [query group][row group]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (any != 0u) {
+    const float* arow[4];
+    const bf16_t* brow[4];
+    bool aok[4], gok[4], bok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = i * 16 + lr;
+      gok[i] = i * 16 < nq;  // wave-uniform: the group holds a query
+      aok[i] = q < nq && HZ_DCHECK(q0 + q < p.Q);
+      arow[i] = p.queries + (long)(aok[i] ? q0 + q : 0) * p.D + lh * 8;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = w * 64 + j * 16 + lr;
+      bok[j] = gm[j] != 0u && r < rows && HZ_DCHECK(row0 + r < (long)p.N);
+      brow[j] = p.corpus + (row0 + (bok[j] ? r : 0)) * p.ldc + lh * 8;
+    }
+    const int nk = p.D >> 5;
+    f32x4 a[2][4][2];  // [buffer][query group][half of the 8 columns]
+    bf16x8 b[2][4];    // [buffer][row group]
+    auto load = [&](int buf, int kk) {  // the k-step kk < nk (columns under D: kk*32 + lh*8 + 8 <= D)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        a[buf][i][0] = a[buf][i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        b[buf][i] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+        if (aok[i]) {
+          a[buf][i][0] = *reinterpret_cast<const f32x4*>(arow[i] + kk * 32);
+          a[buf][i][1] = *reinterpret_cast<const f32x4*>(arow[i] + kk * 32 + 4);
+        }
+        if (bok[i]) b[buf][i] = *reinterpret_cast<const bf16x8*>(brow[i] + kk * 32);
+      }
+    };
+    auto mma = [&](int buf) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (gok[i]) {
+          bf16x8 fh, fm, fl;
+          split_frag(a[buf][i][0], a[buf][i][1], fh, fm, fl);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)  // the contract's order for every accumulator: l, then m, then h
+            if (gm[j] != 0u) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl, b[buf][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gm[j] != 0u) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm, b[buf][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gm[j] != 0u) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, b[buf][j], acc[i][j], 0, 0, 0);
+        }
+    };
+    load(0, 0);
+    for (int kk = 0; kk < nk; kk += 2) {  // two steps per trip, so the buffer index is a constant
+      if (kk + 1 < nk) load(1, kk + 1);
+      mma(0);
+      if (kk + 2 < nk) load(0, kk + 2);
+      if (kk + 1 < nk) mma(1);
+    }
+  }
+  // lane holds score(query i*16 + lh*4 + e, row w*64 + j*16 + lr) in acc[i][j][e]
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int q = i * 16 + lh * 4 + e;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = w * 64 + j * 16 + lr;
+        const bool pass = ((gm[j] >> lr) & 1u) && q < nq;
+        sc[q * MSCAN_TS + r] = pass ? orderable(acc[i][j][e]) : 0u;
+      }
+    }
+  __syncthreads();
+
+  mscan_select(sc, pool, p.cand, p.cand_bytes, p.Q, p.k, tile, q0, nq, row0, w, lane);
 }
 
 // ------------------------------------------------------------------------- nearest centroid, means
@@ -1322,13 +1491,12 @@ extern "C" int hz_search_merge_launch(const HzSearchParams* pp, hipStream_t st) 
   return (int)hipGetLastError();
 }
 
-// The scan's D / ldc (-2), N (-3) and Q (-4) rules; then -30 R outside 1..HZ_SEARCH_MAX_K, -31 k outside 1..R,
-// -32 a null pointer, -33 rows or queries not 16-B aligned or in_id / out_* not 4-B aligned.
-extern "C" int hz_search_rescore_launch(const HzSearchRescoreParams* pp, hipStream_t st) {
-  const HzSearchRescoreParams a = *pp;
+// The scan's D / ldc (-2), N (-3) and Q (-4: outside 1..max_q) rules; then -30 R outside 1..HZ_SEARCH_MAX_K, -31 k
+// outside 1..R, -32 a null pointer, -33 rows or queries not 16-B aligned or in_id / out_* not 4-B aligned.
+static int rescore_check(const HzSearchRescoreParams& a, int max_q) {
   if (a.D < 8 || a.D % 8 || a.D > 2048 || a.ldc < a.D || a.ldc % 8) return -2;
   if (a.N < 1) return -3;
-  if (a.Q < 1 || a.Q > HZ_SEARCH_MAX_Q) return -4;
+  if (a.Q < 1 || a.Q > max_q) return -4;
   if (a.R < 1 || a.R > HZ_SEARCH_MAX_K) return -30;
   if (a.k < 1 || a.k > a.R) return -31;
   if (!a.rows || !a.queries || !a.in_id || !a.out_score || !a.out_id) return -32;
@@ -1336,6 +1504,21 @@ extern "C" int hz_search_rescore_launch(const HzSearchRescoreParams* pp, hipStre
       (reinterpret_cast<uintptr_t>(a.in_id) & 3) || (reinterpret_cast<uintptr_t>(a.out_score) & 3) ||
       (reinterpret_cast<uintptr_t>(a.out_id) & 3))
     return -33;
+  return 0;
+}
+
+extern "C" int hz_search_rescore_launch(const HzSearchRescoreParams* pp, hipStream_t st) {
+  const HzSearchRescoreParams a = *pp;
+  if (const int rc = rescore_check(a, HZ_SEARCH_MAX_Q)) return rc;
+  rescore_dispatch(a, st);
+  return (int)hipGetLastError();
+}
+
+// search_rescore_kernel as it stands (one workgroup per query; its body indexes by q in 64 bits and has no limit on
+// Q) behind a launcher that takes Q up to the self scan's limit
+extern "C" int hz_search_rescoren_launch(const HzSearchRescoreParams* pp, hipStream_t st) {
+  const HzSearchRescoreParams a = *pp;
+  if (const int rc = rescore_check(a, HZ_SEARCH_SELF_MAX_Q)) return rc;
   rescore_dispatch(a, st);
   return (int)hipGetLastError();
 }
@@ -1386,6 +1569,44 @@ extern "C" int hz_search_mscan_launch(const HzSearchSelfParams* pp, hipStream_t 
   if (const int rc = self_check(p)) return rc;
   if (const int rc = raise_mscan_lds_limit()) return rc;
   hipLaunchKernelGGL(search_mscan_kernel, dim3(p.ntile, (p.Q + QB - 1) / QB), dim3(T), MSCAN_LDS, st, p);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+int raise_xscan_lds_limit() {  // as raise_mscan_lds_limit
+  static bool done[64];
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
+  if (done[d]) return 0;
+  HZ_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_xscan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)XSCAN_LDS));
+  done[d] = true;
+  return 0;
+}
+
+}  // namespace
+
+// The batch scan's refusals (hipzap.h): the self scan's -50 .. -60 as -100 .. -110, then -111 for the queries.
+extern "C" int hz_search_xscan_launch(const HzSearchBatchParams* pp, hipStream_t st) {
+  HzSearchBatchParams p = *pp;
+  if (!p.corpus || !p.queries || !p.live || !p.cand) return -100;
+  if (p.D % 32) return -101;
+  if (p.D < 32) return -102;
+  if (p.D > 2048) return -103;
+  if (p.ldc < p.D || p.ldc % 8) return -104;
+  if (p.N < 1) return -105;
+  if (p.Q < 1 || p.Q > HZ_SEARCH_SELF_MAX_Q) return -106;
+  if (p.k < 1 || p.k > HZ_SEARCH_MAX_K) return -107;
+  if ((reinterpret_cast<uintptr_t>(p.corpus) & 15) || (reinterpret_cast<uintptr_t>(p.cand) & 7) ||
+      (reinterpret_cast<uintptr_t>(p.live) & 3))
+    return -108;
+  if (p.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -109;
+  if (p.cand_bytes < hz_search_self_scratch_bytes(p.N, p.Q, p.k)) return -110;
+  if (reinterpret_cast<uintptr_t>(p.queries) & 15) return -111;
+  p.ntile = (int)(((long)p.N + T - 1) / T);
+  if (const int rc = raise_xscan_lds_limit()) return rc;
+  hipLaunchKernelGGL(search_xscan_kernel, dim3(p.ntile, (p.Q + QB - 1) / QB), dim3(T), XSCAN_LDS, st, p);
   return (int)hipGetLastError();
 }
 
@@ -1448,5 +1669,6 @@ extern "C" int hz_search_code_warm(void) {
   hipFuncAttributes a;
   if (const int rc = (int)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&hz_search_code_warm_kernel))) return rc;
   if (const int rc = raise_lds_limit()) return rc;
-  return raise_mscan_lds_limit();
+  if (const int rc = raise_mscan_lds_limit()) return rc;
+  return raise_xscan_lds_limit();
 }

@@ -16,6 +16,9 @@ one fp32 scale per stored row) is the list scan over rows of e4m3fn bytes.
 ``HZ_K_SEARCH_MSCAN`` (``SelfScanParams``) scores rows of the corpus, named by ``qid``, against every tile with the
 bf16 MFMA, ``SELF_QB`` queries a workgroup; ``HZ_K_SEARCH_MERGEN`` is the merge for any number of queries over the
 same block.
+``HZ_K_SEARCH_XSCAN`` (``BatchScanParams``: that block with device fp32 ``queries`` where ``qid`` is) is the self scan
+over external queries, each split into three bf16 terms; ``HZ_K_SEARCH_MERGEN`` takes its block as it stands and
+``HZ_K_SEARCH_RESCOREN`` is the rescore (``RescoreParams``) for any number of queries.
 ``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
@@ -77,6 +80,7 @@ class BinScanParams(C.Structure):
         return sp
 
 
+@N.params_of("HZ_K_SEARCH_RESCOREN")
 @N.params_of("HZ_K_SEARCH_RESCORE")
 class RescoreParams(C.Structure):
     """HzSearchRescoreParams: ``rows`` bf16 [N][ldc] (device or mapped pinned host memory), ``queries`` fp32
@@ -125,6 +129,20 @@ class SelfScanParams(C.Structure):
                 ("skip_self", C.c_int), ("pad_", C.c_int)]
 
 
+@N.params_of("HZ_K_SEARCH_XSCAN")
+class BatchScanParams(C.Structure):
+    """HzSearchBatchParams: ``SelfScanParams`` with ``queries`` (device fp32 [Q][D], 16-B aligned) where ``qid`` is and
+    two unused ints where ``skip_self`` is -- the same layout, so ``HZ_K_SEARCH_MERGEN`` takes it as it stands."""
+    _fields_ = [("corpus", C.c_void_p), ("queries", C.c_void_p), ("live", C.c_void_p), ("cand", C.c_void_p),
+                ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("live_bytes", C.c_uint64), ("cand_bytes", C.c_uint64),
+                ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("ntile", C.c_int),
+                ("pad_", C.c_int * 2)]
+
+    def merge_params(self) -> SelfScanParams:
+        """The block as ``HZ_K_SEARCH_MERGEN`` reads it."""
+        return SelfScanParams.from_buffer_copy(self)
+
+
 @N.params_of("HZ_K_SEARCH_ASSIGN")
 class AssignParams(C.Structure):
     """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
@@ -152,6 +170,9 @@ def _sigs(lib):
     N._sig(lib, "hz_search_self_scratch_bytes", U64, C.c_longlong, C.c_longlong, C.c_int)
     N._sig(lib, "hz_search_mscan_launch", C.c_int, C.POINTER(SelfScanParams), P)
     N._sig(lib, "hz_search_mergen_launch", C.c_int, C.POINTER(SelfScanParams), P)
+    N._sig(lib, "hz_search_xscan_launch", C.c_int, C.POINTER(BatchScanParams), P)
+    N._sig(lib, "hz_search_rescoren_launch", C.c_int, C.POINTER(RescoreParams), P)
+    N._sig(lib, "hz_index_search_batch", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_neighbors", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_neighbors_max", C.c_int, P, C.c_int)
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -280,3 +301,19 @@ def launch_self(prm: SelfScanParams, stream: int = 0) -> tuple:
     lib = N.lib()
     rc = lib.hz_search_mscan_launch(C.byref(prm), stream)
     return rc, (lib.hz_search_mergen_launch(C.byref(prm), stream) if rc == 0 else None)
+
+
+def launch_batch(prm: BatchScanParams, stream: int = 0) -> tuple:
+    """Batch scan then ``HZ_K_SEARCH_MERGEN`` over the same block on ``stream``: (scan code, merge code); no merge after
+    a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_xscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    mp = prm.merge_params()
+    return rc, lib.hz_search_mergen_launch(C.byref(mp), stream)
+
+
+def launch_rescore_n(prm: RescoreParams, stream: int = 0) -> int:
+    """The rescore launch for any number of queries (``HZ_K_SEARCH_RESCOREN``) on ``stream`` -> its code."""
+    return int(N.lib().hz_search_rescoren_launch(C.byref(prm), stream))

@@ -794,6 +794,66 @@ def search_ref(corpus, q, k: int, allow=None, scales=None):
     return scores, ids
 
 
+def split3(q):
+    """The batch scan's split of fp32 values (csrc/hipzap.h HZ_K_SEARCH_XSCAN, "THE SPLIT") -> (h', m', l'), three fp32
+    arrays of bf16 values: ``h`` keeps the top 16 bits of ``x``, ``m`` the top 16 bits of ``x - h``, ``l = (x - h) -
+    m`` (both differences are exact in fp32); then every term whose exponent field is zero becomes a zero of its own
+    sign. ``h' + m' + l'`` is the effective query ``x'``: equal to ``x`` unless a term is below 2^-126."""
+    x = np.ascontiguousarray(q, np.float32)
+
+    def top(a):
+        return (a.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+
+    def term(a):
+        b = a.view(np.uint32)
+        return np.where(b & np.uint32(0x7F800000), b, b & np.uint32(0x80000000)).astype(np.uint32).view(np.float32)
+    h = top(x)
+    r1 = x - h
+    m = top(r1)
+    return term(h), term(m), term(r1 - m)
+
+
+def batch_candidates(k: int, candidates=None) -> int:
+    """``search_batch(candidates=...)`` -> R, the stage-one candidates per query: ``None`` means
+    ``min(MAX_K, max(4 k, k + 32))``, else an integer in k..MAX_K."""
+    if candidates is None:
+        return min(MAX_K, max(4 * k, k + 32))
+    if not _is_int(candidates) or not k <= candidates <= MAX_K:
+        raise ValueError(f"candidates must be None or an integer in k..{MAX_K}, got {candidates!r} with k = {k}")
+    return int(candidates)
+
+
+COSINE_RMAX = 1.0 + 2.0 ** -7  # the most a row of a cosine index can measure: normalised in fp32, then rounded to bf16
+
+
+def batch_slack(q, metric: str):
+    """E of the certificate per query (float64 [Q]), or None where no bound on the rows is known (an ``ip`` index).
+    A row outside the candidates has a stage-one score of at most s_R; its score in ``search`` is then at most
+    s_R + E with E = (beta(3D) + gamma(D)) * B: beta(n) = n 2^-23 / (1 - n 2^-23) bounds the batch scan's error
+    (csrc/hipzap.h), gamma(D) = D 2^-24 / (1 - D 2^-24) the fp32 scan's, and B = ||q||_2 * rmax bounds
+    sum |q_i r_i| for both (|x'_i| <= |x_i|). The terms the split flushes (each below 2^-126) add at most
+    3 * 2^-126 * sqrt(D) * rmax, which is included."""
+    if metric != "cosine":
+        return None
+    q64 = np.asarray(q, np.float64)
+    d = q64.shape[1]
+    beta = 3 * d * 2.0 ** -23 / (1 - 3 * d * 2.0 ** -23)
+    gamma = d * 2.0 ** -24 / (1 - d * 2.0 ** -24)
+    return (beta + gamma) * np.sqrt((q64 * q64).sum(axis=1)) * COSINE_RMAX + 3 * 2.0 ** -126 * np.sqrt(d) * COSINE_RMAX
+
+
+def batch_certain(s_last, t_k, slack):
+    """The certificate: ``s_last`` [Q] the stage-one score of each query's R-th candidate (-inf: fewer than R rows
+    passed, so every passing row was a candidate), ``t_k`` [Q] the k-th returned score, ``slack`` from
+    :func:`batch_slack` -> bool [Q]: the answer is proven equal to ``search``'s. Without a slack only the first
+    clause applies."""
+    s_last, t_k = np.asarray(s_last, np.float64), np.asarray(t_k, np.float64)
+    certain = np.isneginf(s_last)
+    if slack is not None:
+        certain = certain | (s_last + slack < t_k)
+    return certain
+
+
 def check_queries(q, dim: int) -> np.ndarray:
     q = np.asarray(q)
     if q.ndim == 1:
@@ -957,6 +1017,18 @@ class _Base:
         if self.dim % 32:
             raise ValueError(f"neighbors needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
         return self._check_ids(ids), check_k(k)
+
+    def _check_batch(self, k, candidates):
+        """The refusals of :meth:`search_batch` that both backends share -> (k, R)."""
+        if self.dtype in (FP8, BIN) or self.ivf is not None:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
+                f"a {BIN} index" if self.dtype == BIN else f"an {FP8} index"
+            raise ValueError(f"search_batch is built for plain bf16 indexes (versions 1 and 2): this one is {what} of "
+                             f"version {self.version}")
+        if self.dim % 32:
+            raise ValueError(f"search_batch needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
+        k = check_k(k)
+        return k, batch_candidates(k, candidates)
 
     def _check_cluster_index(self):
         """:meth:`cluster` is built for plain bf16 indexes with ``dim % 32 == 0``."""
@@ -1169,6 +1241,27 @@ class RefIndex(_Base):
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
         return s.astype(np.float32), i
 
+    def search_batch(self, q, k: int = 10, *, candidates=None, fallback: bool = True, ctx=None):
+        """:meth:`Index.search_batch` on the host, its oracle: stage one is :func:`search_ref` in fp64 over the SPLIT
+        query (:func:`split3`) at k = R, stage two :func:`rescore_ref` of those ids with the query itself, then the
+        same certificate (:func:`batch_certain`) -> (scores float32 [Q, k], ids int32 [Q, k], certain bool [Q])."""
+        k, R = self._check_batch(k, candidates)
+        q = check_queries(q, self.dim)
+        with self._mut:
+            h, m, l = split3(q)
+            eff = h.astype(np.float64) + m.astype(np.float64) + l.astype(np.float64)
+            s1, i1 = search_ref(self._rows, eff, R, None if self._live.all() else self._live)
+            two = [rescore_ref(self._rows, q[a], i1[a], k) for a in range(q.shape[0])]
+            s = np.stack([t[0] for t in two]) if two else np.zeros((0, k))
+            i = np.stack([t[1] for t in two]) if two else np.zeros((0, k), np.int32)
+        s, i = s.astype(np.float32), i.astype(np.int32)
+        certain = batch_certain(s1[:, R - 1], s[:, k - 1], batch_slack(q, self.metric))
+        if fallback and not certain.all():
+            todo = np.flatnonzero(~certain)
+            s[todo], i[todo] = self.search(q[todo], k)
+            certain[:] = True
+        return s, i, certain
+
     def neighbors(self, ids, k: int = 10, *, include_self: bool = False):
         """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]):
         :func:`search_ref` in fp64 over the stored rows with ``allow`` = live and, unless ``include_self``, not the
@@ -1368,6 +1461,47 @@ class Index(_Base):
             if ctx is None:
                 self._free.put(c)
         return scores, ids
+
+    def search_batch(self, q, k: int = 10, *, candidates=None, fallback: bool = True, ctx: int | None = None):
+        """Many fp32 queries at once -> (scores float32 [Q, k], ids int32 [Q, k], certain bool [Q]).
+        Stage one scores every query against every live row with the bf16 MFMA -- each query split into three bf16
+        terms that sum to it, so nothing is rounded away -- and keeps ``candidates`` rows per query (R: ``None`` for
+        ``min(128, max(4 k, k + 32))``, else k..128); stage two re-scores those R with :meth:`search`'s own arithmetic
+        and returns the best k. ``certain[q]``: the answer is PROVEN equal to ``search(q[None], k)`` in ids and score
+        bits -- every row outside the candidates scored at most s_R in stage one, hence at most s_R + E in ``search``,
+        and ``s_R + E < `` the k-th returned score (:func:`batch_slack`; E needs a bound on the rows, which only a
+        ``cosine`` index has), or fewer than R rows passed. On an ``ip`` index only the second clause can certify.
+        ``fallback``: the uncertain queries are re-run through :meth:`search` and are certain afterwards; with
+        ``fallback=False`` they are returned as computed. A plain bf16 index with ``dim % 32 == 0``; Q above the
+        per-call maximum is split here."""
+        k, R = self._check_batch(k, candidates)
+        q = check_queries(q, self.dim)
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        nq = q.shape[0]
+        scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
+        last = np.empty(nq, np.float32)
+        c = self._free.get() if ctx is None else ctx
+        try:
+            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
+            for a in range(0, nq, step):
+                part = q[a:a + step]
+                s, i, e = scores[a:a + step], ids[a:a + step], last[a:a + step]  # contiguous ranges of the outputs
+                rc = self._lib.hz_index_search_batch(self._h, c, part.ctypes.data, part.shape[0], k, R, s.ctypes.data,
+                                                     i.ctypes.data, e.ctypes.data)
+                if rc in (-4, -5, -28, -44, -45):
+                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
+                if rc:
+                    raise RuntimeError(f"hz_index_search_batch failed with code {rc}")
+            certain = batch_certain(last, scores[:, k - 1] if nq else last, batch_slack(q, self.metric))
+            if fallback and not certain.all():
+                todo = np.flatnonzero(~certain)
+                scores[todo], ids[todo] = self.search(q[todo], k, ctx=c)
+                certain[:] = True
+        finally:
+            if ctx is None:
+                self._free.put(c)
+        return scores, ids, certain
 
     def neighbors(self, ids, k: int = 10, *, include_self: bool = False, ctx: int | None = None):
         """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]),

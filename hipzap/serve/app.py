@@ -520,7 +520,11 @@ def search():
     R used, 0 if none. ``"nprobe"`` (an IVF index): the lists each query scans, an integer in 1..min(nlist, 128)
     or ``"all"``; absent: ``extra.index_nprobe``, else the file's default. The answer of an IVF index carries
     ``"ivf": true`` and the ``"nprobe"`` used (``"all"`` when every list was scanned). ``"nprobe"`` and ``"refine"``
-    go together on an fp8 IVF index with rescore rows (a version-7 file): the probed lists give the R candidates."""
+    go together on an fp8 IVF index with rescore rows (a version-7 file): the probed lists give the R candidates.
+    ``"batch": true`` answers through ``search_batch`` (every query in one pass of the MFMA scan, exact
+    rescoring, the unproven queries re-run through ``search``): the same results, plus ``"certain"`` (one boolean per
+    query, all true here) in the JSON answer. 400 on an index kind ``search_batch`` refuses, and with a filter,
+    ``refine`` or ``nprobe``, which the batch path does not take."""
     from ..search import MAX_K, check_k, check_queries, normalize_rows
     s = get_server()
     body = {}
@@ -548,14 +552,25 @@ def search():
     if index.metric == "cosine":
         q = normalize_rows(q)
     filt = _search_filter(body)
+    batch = body.get("batch", False)
+    if not isinstance(batch, bool):
+        raise ValueError(f"batch must be true or false, got {batch!r}")
     nprobe = body.get("nprobe")
+    if batch:
+        index._check_batch(k, None)  # ValueError -> 400: an index kind the batch path refuses
+        if filt is not None or nprobe is not None or body.get("refine") is not None:
+            raise ValueError("batch takes no filter, tag, refine or nprobe")
     if index.ivf is not None and nprobe is not None and nprobe != "all" and (
             isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= min(index.ivf["nlist"], MAX_K)):
         raise ValueError(f"nprobe must be an integer in 1..{min(index.ivf['nlist'], MAX_K)} or \"all\", got {nprobe!r}")
     lists = index._nprobe(nprobe, body.get("refine"))  # ValueError -> 400 (nprobe without lists, refine with them)
     refine = index._refine(body.get("refine"), k)  # ValueError -> 400
+    certain = None
     with phase("search"):
-        scores, ids = index.search(q, k, filter=filt, refine=refine, nprobe=nprobe)
+        if batch:
+            scores, ids, certain = index.search_batch(q, k, fallback=True)
+        else:
+            scores, ids = index.search(q, k, filter=filt, refine=refine, nprobe=nprobe)
     dt = (time.perf_counter() - t0) * 1e3
     if "application/octet-stream" in request.headers.get("Accept", ""):
         out = np.empty(ids.shape, dtype=[("id", "<i4"), ("score", "<f4")])
@@ -572,6 +587,7 @@ def search():
         return h
     return _json({"model": model, "backend": backend.backend, "metric": index.metric, "dtype": index.dtype, "refine": refine, "k": k,
                   "count": int(index.count), **({"ivf": True, "nprobe": lists or "all"} if index.ivf is not None else {}),
+                  **({"batch": True, "certain": [bool(c) for c in certain]} if batch else {}),
                   "results": [[hit(i, sc) for i, sc in zip(ri, rs)] for ri, rs in zip(ids, scores)],
                   "timing_ms": round(dt, 3)})
 
