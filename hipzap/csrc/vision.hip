@@ -294,14 +294,19 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const void* __restrict_
     float f = 0.f;
     if (c < Cin) {
       if (mode == 0) f = reinterpret_cast<const float*>(src)[(n * Cin + c) * HWl + hw];
-      else f = (float)reinterpret_cast<const unsigned char*>(src)[i * Cin + c] * (1.0f / 255.0f);
+      else f = (float)reinterpret_cast<const unsigned char*>(src)[i * Cin + c];
     }
     v[c] = f;
   }
+  // a byte: one fused multiply-add for u / 255 - mean, written out -- preprocess_u8c3_kernel's form, so
+  // both kernels store the same bits for the same pixel whatever the compiler would contract
   if (mean) {
 #pragma unroll
     for (int c = 0; c < 8; ++c)
-      if (c < Cin) v[c] = (v[c] - mean[c]) * inv_std[c];
+      if (c < Cin) v[c] = (mode == 0 ? v[c] - mean[c] : __builtin_fmaf(v[c], 1.0f / 255.0f, -mean[c])) * inv_std[c];
+  } else if (mode != 0) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) v[c] = v[c] * (1.0f / 255.0f);
   }
   bf16_t* o = dst + i * Cpad;
   *reinterpret_cast<u32x4*>(o) = pack8(v);
@@ -350,8 +355,9 @@ __global__ __launch_bounds__(256) void preprocess_u8c3_kernel(const unsigned* __
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int b = 3 * q + c;  // byte within the thread's 12
-      const float f = (float)((w[b >> 2] >> (8 * (b & 3))) & 0xffu) * (1.0f / 255.0f);
-      v[c] = mean ? (f - mu[c]) * is[c] : f;
+      const float u = (float)((w[b >> 2] >> (8 * (b & 3))) & 0xffu);
+      // u / 255 - mean as one fused multiply-add (what the compiler made of it; preprocess_kernel does the same)
+      v[c] = mean ? __builtin_fmaf(u, 1.0f / 255.0f, -mu[c]) * is[c] : u * (1.0f / 255.0f);
     }
     bf16_t* o = dst + (px + q) * Cpad;
     *reinterpret_cast<u32x4*>(o) = pack8(v);
@@ -591,7 +597,11 @@ __global__ void cast_bf16_f32_kernel(const bf16_t* __restrict__ x, float* __rest
 
 extern "C" int hz_maxpool_launch(const HzPoolParams* pp, hipStream_t st) {
   const HzPoolParams& p = *pp;
-  if (p.C % 8) return -1;
+  if (!p.x || !p.out) return -1;
+  if (p.C < 1 || p.C % 8 || p.N < 1 || p.H < 1 || p.W < 1 || p.P < 1 || p.Q < 1) return -1;
+  if (p.k < 1 || p.stride < 1 || p.pad < 0 || p.pad >= p.k) return -1;
+  // every window overlaps the image (with pad < k its first row and column do already)
+  if ((long)(p.P - 1) * p.stride - p.pad >= p.H || (long)(p.Q - 1) * p.stride - p.pad >= p.W) return -1;
   const long total = (long)p.N * p.P * p.Q * (p.C / 8);
   // clamped taps are only inside the window when the padding is smaller than the window
   if (p.k == 3 && p.pad < 3) HZ_LAUNCH(maxpool_kernel<3>, dim3((total + 255) / 256), dim3(256), 0, st, p);
@@ -601,14 +611,15 @@ extern "C" int hz_maxpool_launch(const HzPoolParams* pp, hipStream_t st) {
 
 extern "C" int hz_avgpool_launch(const unsigned short* x, unsigned short* out, int N, int HW, int C, int blocked,
                                  hipStream_t st) {
-  if (C % 64) return -1;
+  if (!x || !out || N < 1 || HW < 1 || C < 1 || C % 64) return -1;
   HZ_LAUNCH(avgpool_kernel, dim3(N * (C / 64)), dim3(256), 0, st, x, out, N, HW, C, blocked);
   return (int)hipGetLastError();
 }
 
 extern "C" int hz_pool_fc_launch(const HzPoolFcParams* pp, hipStream_t st) {
   const HzPoolFcParams& p = *pp;
-  if (p.C % 32 || p.C > 16384 || p.HW < 1 || p.N < 1) return -1;
+  if (!p.x || !p.w || !p.out) return -1;
+  if (p.C < 32 || p.C % 32 || p.C > 16384 || p.HW < 1 || p.N < 1 || p.B < 1 || p.ldo < p.N) return -1;
   const int groups = (p.N + 15) / 16;
   const size_t lds = (size_t)(p.C + 64) * sizeof(float);
   const dim3 grid(groups, p.B);
@@ -640,6 +651,7 @@ extern "C" int hz_pool_norm_launch(const HzPoolNormParams* pp, hipStream_t st) {
 #endif
 extern "C" int hz_preprocess_launch(const void* src, unsigned short* dst, int N, int Cin, int H, int W, int Cpad,
                                     int mode, const float* mean, const float* inv_std, hipStream_t st) {
+  if (!src || !dst || mode < 0 || mode > 2 || N < 1 || H < 1 || W < 1 || (mean && !inv_std)) return -1;
   if (mode == 2) {  // patch rows; Cpad carries the patch size
     if (Cpad != 16 || H % 16 || W % 16 || Cin < 1 || Cin > 8 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15))
       return -1;
@@ -648,7 +660,7 @@ extern "C" int hz_preprocess_launch(const void* src, unsigned short* dst, int N,
                        static_cast<const float*>(src), reinterpret_cast<bf16_t*>(dst), N, Cin, H, W, mean, inv_std);
     return (int)hipGetLastError();
   }
-  if (Cpad % 8 || Cin > 8) return -1;
+  if (Cpad < 8 || Cpad % 8 || Cin < 1 || Cin > 8) return -1;
   const long total = (long)N * H * W;
   if (mode == 1 && Cin == 3 && total % 4 == 0 && ((uintptr_t)src & 15) == 0 && !HZ_PREPROC_GENERIC) {
     HZ_LAUNCH(preprocess_u8c3_kernel, dim3((total + 1023) / 1024), dim3(256), 0, st,
@@ -688,11 +700,15 @@ extern "C" int hz_resize_patchify_launch(const HzResizeParams* pp, hipStream_t s
 }
 
 extern "C" int hz_cast_f32_bf16(const float* x, unsigned short* y, long n, hipStream_t st) {
+  if (n < 1) return 0;  // nothing to convert: no launch (a grid of zero blocks is an error)
+  if (!x || !y) return -1;
   const long threads = (n + 3) / 4;
   HZ_LAUNCH(cast_f32_bf16_kernel, dim3((threads + 255) / 256), dim3(256), 0, st, x, y, n);
   return (int)hipGetLastError();
 }
 extern "C" int hz_cast_bf16_f32(const unsigned short* x, float* y, long n, hipStream_t st) {
+  if (n < 1) return 0;
+  if (!x || !y) return -1;
   HZ_LAUNCH(cast_bf16_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, y, n);
   return (int)hipGetLastError();
 }
