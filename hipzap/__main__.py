@@ -14,6 +14,7 @@
     python -m hipzap index --from-index a.hzidx --dtype fp8 --out b.hzidx  # requantise a bf16 index (ids kept)
     python -m hipzap index --vectors v.npy --dtype fp8 --rescore --out c.hzidx  # fp8 scan + bf16 rescoring (version 4)
     python -m hipzap index --vectors v.npy --dtype bin --rescore --out d.hzidx  # sign-bit scan + bf16 rescoring (version 9)
+    python -m hipzap index --vectors v.npy --dtype pq --pq-m 96 --rescore --out e.hzidx  # product quantisation (version 11)
     python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
@@ -118,7 +119,15 @@ def cmd_index(a):
     from .search import convert_index, write_index
     if a.ivf is not None and a.dtype == "bin":
         raise SystemExit("index: --ivf with --dtype bin: IVF lists over binary rows are not built")
-    if a.rescore and a.dtype not in ("fp8", "bin"):
+    if a.ivf is not None and a.dtype == "pq":
+        raise SystemExit("index: --ivf with --dtype pq: IVF lists over pq8 rows are not built")
+    if a.dtype == "pq" and a.pq_m is None:
+        raise SystemExit("index: --dtype pq needs --pq-m M, the code bytes per row (a multiple of 16 in 16..96 that divides dim)")
+    if a.dtype != "pq" and (a.pq_m is not None or a.pq_iters is not None or a.pq_seed is not None):
+        raise SystemExit("index: --pq-m, --pq-iters and --pq-seed go with --dtype pq")
+    pq = {} if a.dtype != "pq" else {"pq_m": a.pq_m, "pq_iters": 10 if a.pq_iters is None else a.pq_iters,
+                                     "pq_seed": a.pq_seed or 0}
+    if a.rescore and a.dtype not in ("fp8", "bin", "pq"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
     if a.from_index is not None:
@@ -130,7 +139,7 @@ def cmd_index(a):
             raise SystemExit("index: --ivf-backend goes with --ivf NLIST")
         try:
             hdr = convert_index(a.from_index, a.out, a.dtype, rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe,
-                                ivf_seed=a.ivf_seed or 0, ivf_backend=a.ivf_backend, device=a.device)
+                                ivf_seed=a.ivf_seed or 0, ivf_backend=a.ivf_backend, device=a.device, **pq)
         except ValueError as e:
             raise SystemExit(f"index: {e}") from None
         print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": "labels" in hdr}))
@@ -175,9 +184,14 @@ def cmd_index(a):
             if os.path.exists(tmp):
                 os.remove(tmp)
     else:
-        hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
-                          rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0,
-                          ivf_backend=a.ivf_backend, device=a.device)
+        try:
+            hdr = write_index(a.out, vec, a.metric, labels=labels, model=model or "", embed=embed, tags=tags, dtype=a.dtype,
+                              rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0,
+                              ivf_backend=a.ivf_backend, device=a.device, **pq)
+        except ValueError as e:
+            if a.dtype != "pq":
+                raise
+            raise SystemExit(f"index: {e}") from None
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
 
 
@@ -319,7 +333,11 @@ def main(argv=None):
     ix.add_argument("--labels", default=None, help="a JSON list of N strings")
     ix.add_argument("--tags", default=None, help="an .npy of N uint32 tag words (search filters test them): a version-2 file")
     ix.add_argument("--metric", choices=["cosine", "ip"], default="cosine")
-    ix.add_argument("--dtype", choices=["bf16", "fp8", "bin"], default="bf16",
+    ix.add_argument("--pq-m", type=int, default=None, metavar="M",
+                    help="with --dtype pq: code bytes per row (a multiple of 16 in 16..96 that divides dim; dim / M <= 64)")
+    ix.add_argument("--pq-iters", type=int, default=None, help="with --dtype pq: Lloyd iterations of the codebook training (10)")
+    ix.add_argument("--pq-seed", type=int, default=None, help="with --dtype pq: the training seed (0)")
+    ix.add_argument("--dtype", choices=["bf16", "fp8", "bin", "pq"], default="bf16",
                     help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D %% 16 == 0); "
                          "bin: one sign bit per column (a version-8 file, a sixteenth of the bytes; D %% 128 == 0), "
                          "with --rescore version 9")

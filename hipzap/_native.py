@@ -40,7 +40,8 @@ KINDS = {
     "HZ_K_SEARCH_LSCAN": 36, "HZ_K_SEARCH_QLSCAN": 37, "HZ_K_POOL_NORM": 38,
     "HZ_K_SEARCH_MSCAN": 39, "HZ_K_SEARCH_MERGEN": 40,
     "HZ_K_SEARCH_ASSIGN": 41, "HZ_K_SEARCH_CMEAN": 42, "HZ_K_SEARCH_BSCAN": 43,
-    "HZ_K_SEARCH_XSCAN": 44, "HZ_K_SEARCH_RESCOREN": 45,
+    "HZ_K_SEARCH_XSCAN": 44, "HZ_K_SEARCH_RESCOREN": 45, "HZ_K_SEARCH_PQLUT": 46,
+    "HZ_K_SEARCH_PQSCAN": 47,
 }
 globals().update(KINDS)
 KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct

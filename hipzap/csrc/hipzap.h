@@ -512,6 +512,50 @@ typedef struct HzSearchBinParams {
   HzSearchFilterParams f;        // the filtered scan's block, unchanged (live is required; ldc counts words)
 } HzSearchBinParams;
 int hz_search_bscan_launch(const HzSearchBinParams* p, hipStream_t st);
+// product-quantised rows: the D columns are M sub-spaces of dsub = D / M columns; a row is M bytes,
+// code[r][m] naming one of 256 sub-centroids codebook[m][c][0 .. dsub) (fp32 [M][256][dsub]). Shape rules, for both
+// kinds: M % 16 == 0 (a row is whole 16-B chunks), 16 <= M <= HZ_SEARCH_PQ_MAX_M (one query's table is M KiB of
+// LDS), D % M == 0, 1 <= D / M <= HZ_SEARCH_PQ_MAX_DSUB, D <= 2048.
+// CONTRACT. lut[q][m][c] is ONE fp32 fmaf chain over j = 0 .. dsub-1, ascending, from +0, of
+// q[m*dsub + j] * codebook[m][c][j]; score(q, r) is the fp32 sum, PLAIN additions (no FMA), over m = 0 .. M-1,
+// ascending, from +0, of lut[q][m][code[r][m]]. The bits of a score depend on the query, the codebook and the row's
+// M bytes only: not on N, the tile, the row's position, the other queries, the grid or `span`. Keys and the total
+// order are HZ_K_SEARCH_SCAN's. Against the exact inner product of q and the reconstructed row x^:
+//   |score - q.x^| <= gamma(dsub + M) * sum_i |q_i| |x^_i|,  gamma(n) = n 2^-24 / (1 - n 2^-24).
+// table kind (HZ_K_SEARCH_PQLUT): grid (M, Q), 256 threads; thread c writes lut[(q*M + m)*256 + c].
+// scan kind (HZ_K_SEARCH_PQSCAN): `f.s.corpus` points at uint8 [N][ldc] (ldc in bytes, ldc % 16 == 0, ldc >= M).
+// Grid (ceil(ntile / span), Q): a workgroup copies ITS query's M KiB table from `lut` into LDS once and walks `span`
+// consecutive tiles; per tile thread t owns row t, loads its M bytes only if the row passes for this query (a wave
+// whose 64 rows all fail loads nothing), adds the M lookups and the tile is ranked into cand[(tile*Q + q)*k ..], the
+// layout HZ_K_SEARCH_MERGE and HZ_K_SEARCH_RESCORE consume. Filtered only: `live` is required. span = 0: the launcher
+// picks hz_search_pq_span(N, Q, M): about two workgroups per compute unit over the whole grid where the table lets one
+// workgroup live on a compute unit (M >= 80), at most max(2, M / 16) below that. `f.s.queries` is not read
+// by the scan (the merge's checks want it set). Refusals of either launcher (nothing is launched):
+// -112 a null pointer (table kind: queries, codebook, lut; scan kind: corpus, queries, cand, out_score, out_id, lut);
+// -113 D % M; -114 M % 16; -115 M outside 16..96; -116 D / M outside 1..64; -117 D > 2048; -118 ldc < M or ldc % 16;
+// -119 N < 1; -120 Q outside 1..HZ_SEARCH_MAX_Q; -121 k outside 1..HZ_SEARCH_MAX_K; -122 corpus, queries, codebook or
+// lut not 16-B, cand not 8-B or out_* / tags / filt / live not 4-B aligned; -123 a null live bitmap; -124 live_bytes
+// below 4 * ceil(N / 32); -125 filt without tags; -126 cand_bytes below ntile * Q * k * 8; -127 lut_bytes below
+// Q * M * 1024; -128 span < 0.
+#define HZ_SEARCH_PQ_MAX_M 96
+#define HZ_SEARCH_PQ_MAX_DSUB 64
+typedef struct HzSearchPqLutParams {
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const float* codebook;         // device fp32 [M][256][D / M], 16-B aligned
+  float* lut;                    // device fp32 [Q][M][256], 16-B aligned
+  unsigned long long lut_bytes;  // bytes of `lut`, at least Q * M * 1024
+  int D, M, Q, pad_;
+} HzSearchPqLutParams;
+typedef struct HzSearchPqParams {
+  HzSearchFilterParams f;        // the filtered scan's block (live is required; corpus: byte rows, ldc in bytes)
+  const float* lut;              // device fp32 [Q][M][256]: HZ_K_SEARCH_PQLUT's output
+  unsigned long long lut_bytes;  // bytes of `lut`
+  int M, span;                   // span: tiles a workgroup walks, 0 = the launcher's choice
+} HzSearchPqParams;
+int hz_search_pqlut_launch(const HzSearchPqLutParams* p, hipStream_t st);
+int hz_search_pqscan_launch(const HzSearchPqParams* p, hipStream_t st);
+// the span a launch with span = 0 takes for (N, Q, M) on the current device; 0 for a refused N, Q or M
+int hz_search_pq_span(long long N, int Q, int M);
 // rescore (HZ_K_SEARCH_RESCORE): the second stage of a two-stage search. One workgroup per query
 // scores the query against the R bf16 rows that `in_id` names (a merge's out_id of stage one; a slot is real
 // iff (unsigned)id < (unsigned)N, every other value is an empty slot and nothing is loaded for it) and writes
@@ -816,6 +860,27 @@ int hz_index_add_b(void* idx, const unsigned* words, long long n, const unsigned
 int hz_index_add_br(void* idx, const unsigned* words, const unsigned short* rows_bf16, long long n,
                     const unsigned* tags_or_null, long long* first_id_out);
 int hz_index_read_state_b(void* idx, unsigned* words_out, unsigned* tags_out, unsigned* live_out, long long n);
+// A product-quantised index (a version-10 or version-11 .hzidx): version 3's rule set over pq8 rows --
+// "dtype": "pq8", the JSON block "pq": {"m": M, "ksub": 256, "dsub": dim / M, "codebook_off": ...}, the row block uint8
+// [count][M], the codebook fp32 [M][256][dsub] in a 4096-aligned block after it, no scales block, "capacity" /
+// "tags_off" / "live_off" present exactly when version 3 would have them. Version 11 adds "rescore": "bf16" /
+// "rescore_off" as version 4 does, the last block. open3 opens both (either rescore placement), uploads the codebook
+// and gives every context a table scratch [HZ_SEARCH_MAX_Q][M][256] fp32; every search replays H2D,
+// HZ_K_SEARCH_PQLUT, HZ_K_SEARCH_PQSCAN, merge, two D2H, and with refine = R the scan and merge at k = R, then
+// HZ_K_SEARCH_RESCORE: version 4's programs under the same key and invalidation rules. describe2's out[5] is 3;
+// describe4 reports M, dsub and the codebook's bytes. The _p calls are hz_index_add / hz_index_read_state for such an
+// index (-26 on any other dtype, and from the other forms on this one): the codes are encoded by the caller against
+// the index's codebook (hz_index_read_codebook); hz_index_add_pr takes the codes and the bf16 rows together (-29,
+// naming the right call: add_p on a version-11 index, add_pr on a version-10 one). nprobe, probes (-34), neighbors
+// (-35), assign and cmean (-38) and search_batch (-44) refuse it by name: "a pq8 index of version 10".
+int hz_index_add_p(void* idx, const unsigned char* codes, long long n, const unsigned* tags_or_null, long long* first_id_out);
+int hz_index_add_pr(void* idx, const unsigned char* codes, const unsigned short* rows_bf16, long long n,
+                    const unsigned* tags_or_null, long long* first_id_out);
+int hz_index_read_state_p(void* idx, unsigned char* codes_out, unsigned* tags_out, unsigned* live_out, long long n);
+int hz_index_read_codebook(void* idx, float* codebook_out);  // fp32 [M][256][dsub]; -26 on any other dtype
+// out[8] = {M, dsub, codebook bytes, table scratch bytes per context, the span of a Q = 1 scan, 0, 0, 0}; zeros
+// unless the index holds pq8 rows
+int hz_index_describe4(void* idx, uint64_t* out);
 // neighbours of stored rows (a plain bf16 index, versions 1 and 2, dim % 32 == 0): the k nearest live
 // rows of each of the n rows `ids` names, the row itself excluded iff skip_self -> out_score fp32 [n][k], out_id
 // int32 [n][k], -inf / -1 past the live rows. Replays H2D of the ids, HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two
@@ -1051,7 +1116,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_CMEAN, 42, HzSearchCmeanParams, hz_search_cmean_op, SEARCH)   \
   X(SEARCH_BSCAN, 43, HzSearchBinParams, hz_search_bscan_op, SEARCH)     \
   X(SEARCH_XSCAN, 44, HzSearchBatchParams, hz_search_xscan_op, SEARCH)    \
-  X(SEARCH_RESCOREN, 45, HzSearchRescoreParams, hz_search_rescoren_op, SEARCH)
+  X(SEARCH_RESCOREN, 45, HzSearchRescoreParams, hz_search_rescoren_op, SEARCH) \
+  X(SEARCH_PQLUT, 46, HzSearchPqLutParams, hz_search_pqlut_op, SEARCH)    \
+  X(SEARCH_PQSCAN, 47, HzSearchPqParams, hz_search_pqscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -41,6 +41,12 @@
 // carries the pitch in words, the merge's keeps ldc = dim), and version 9 (bf16 rescore rows, either placement)
 // replays version 4's two-stage programs; keys and invalidation rules are the same.
 //
+// A product-quantised index (a version-10 or version-11 file): the rows are M code bytes, beside them
+// lies the fp32 codebook [M][256][dim / M] (device memory, a host mirror for hz_index_read_codebook) and every context
+// holds a table scratch [MAX_Q][M][256] fp32. It replays version 3's programs with HZ_K_SEARCH_PQLUT and
+// HZ_K_SEARCH_PQSCAN in place of the quantised scan (the scan's block carries the pitch in bytes, the merge's keeps
+// ldc = dim), and version 11 replays version 4's two-stage programs; keys and invalidation rules are the same.
+//
 // Neighbours of stored rows (a plain bf16 index): hz_index_neighbors replays H2D of the ids,
 // HZ_K_SEARCH_MSCAN, HZ_K_SEARCH_MERGEN, two D2H, with the filtered programs' N (the rows past the count are dead
 // in the bitmap) and so under their invalidation rules. A context's buffers for it (ids, results, candidate
@@ -90,6 +96,7 @@ struct Ctx {
   uint64_t cand_bytes = 0;
   char* out_dev = nullptr;            // [MAX_Q][MAX_K] fp32 scores, then [MAX_Q][MAX_K] int32 ids
   char* out_host = nullptr;           // pinned, the same layout
+  float* lut = nullptr;               // pq8 only: the queries' tables [MAX_Q][M][256] fp32
   char* mid_dev = nullptr;            // two-stage only: stage one's scores and ids, the layout of out_dev
   char* probe_dev = nullptr;          // IVF only: the coarse stage's scores and list ids, the layout of out_dev
   unsigned long long* ccand = nullptr;  // IVF only: the coarse stage's candidate scratch
@@ -152,6 +159,10 @@ struct Index {
   bool has_tags = false;
   bool fp8 = false;                   // a version-3, 4, 6 or 7 file: e4m3fn byte rows and `scales`
   bool bin = false;                   // a version-8 or 9 file: sign-bit rows, dim / 32 words each (never with fp8 or ivf)
+  bool pq = false;                    // a version-10 or 11 file: pq8 rows, pq_m code bytes each (never with fp8, bin or ivf)
+  int pq_m = 0;                       // sub-spaces = bytes per row; dsub = dim / pq_m
+  float* codebook = nullptr;          // device fp32 [pq_m][256][dim / pq_m]
+  std::vector<float> codebook_host;   // its mirror
   unsigned short* rows = nullptr;     // bf16 [cap][dim], or uint8 [cap][dim] of an fp8 index
   float* scales = nullptr;            // device, cap floats (fp8 only)
   bool rescore = false;               // a version-4, 7 or 9 file: `rrows` beside the fp8 or sign-bit rows
@@ -182,6 +193,7 @@ struct Index {
       if (c->cand) (void)hipFree(c->cand);
       if (c->out_dev) (void)hipFree(c->out_dev);
       if (c->mid_dev) (void)hipFree(c->mid_dev);
+      if (c->lut) (void)hipFree(c->lut);
       if (c->probe_dev) (void)hipFree(c->probe_dev);
       if (c->ccand) (void)hipFree(c->ccand);
       if (c->nid_host) (void)hipHostFree(c->nid_host);
@@ -204,6 +216,7 @@ struct Index {
     if (tags) (void)hipFree(tags);
     if (scales) (void)hipFree(scales);
     if (centroids) (void)hipFree(centroids);
+    if (codebook) (void)hipFree(codebook);
     if (ivf_tables) (void)hipFree(ivf_tables);
   }
 
@@ -213,8 +226,12 @@ struct Index {
     return ivf ? pos_of[id] : id;
   }
 
-  uint64_t rowb() const { return bin ? h.dim / 8 : fp8 ? h.dim : h.dim * 2ull; }  // bytes per stored row
-  const char* dtype_name() const { return bin ? "bin_sign" : fp8 ? "fp8_e4m3" : "bf16"; }
+  uint64_t rowb() const { return pq ? (uint64_t)pq_m : bin ? h.dim / 8 : fp8 ? h.dim : h.dim * 2ull; }  // bytes per stored row
+  const char* dtype_name() const { return pq ? "pq8" : bin ? "bin_sign" : fp8 ? "fp8_e4m3" : "bf16"; }
+  uint64_t codebook_bytes() const { return pq ? 256ull * h.dim * 4 : 0; }  // pq_m * 256 * (dim / pq_m) floats
+  uint64_t lut_bytes() const { return pq ? (uint64_t)HZ_SEARCH_MAX_Q * pq_m * 1024 : 0; }  // per context
+  // what the by-name refusals call a quantised index without lists
+  const char* quant_name() const { return pq ? "a pq8 index" : bin ? "a bin_sign index" : "an fp8_e4m3 index"; }
   uint64_t row_bytes() const { return cap * rowb(); }
   uint64_t scan_rows() const { return round_up(count, kTile); }  // the filtered programs' N
   uint64_t rescore_rows(uint64_t for_cap) const { return ivf ? n_ext : for_cap; }  // an IVF index holds them by id
@@ -292,12 +309,21 @@ struct Index {
     HzSearchBinParams bp{};  // sign-bit rows: the filtered block with the pitch in words (the merge keeps ldc = D)
     bp.f = f;
     bp.f.s.ldc = (int)h.dim / 32;
+    HzSearchPqLutParams lp{};  // pq8 rows: the queries' tables, then the scan over the code bytes (pitch in bytes)
+    lp.queries = c.q_dev, lp.codebook = codebook, lp.lut = c.lut, lp.lut_bytes = lut_bytes();
+    lp.D = (int)h.dim, lp.M = pq_m, lp.Q = Q;
+    HzSearchPqParams pp{};
+    pp.f = f;
+    pp.f.s.ldc = pq_m;
+    pp.lut = c.lut, pp.lut_bytes = lut_bytes(), pp.M = pq_m, pp.span = 0;
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4, qb = (size_t)Q * h.dim * 4;
     int rc;
     if (filtered) {
       rc = hz_prog_add_memcpy(g, c.slot_dev, c.slot_host, kFiltBytes + qb, 0);
-      if (!rc) rc = bin ? hz_prog_add_kernel(g, HZ_K_SEARCH_BSCAN, &bp, sizeof(bp), 0)
+      if (!rc && pq) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_PQLUT, &lp, sizeof(lp), 0);
+      if (!rc) rc = pq  ? hz_prog_add_kernel(g, HZ_K_SEARCH_PQSCAN, &pp, sizeof(pp), 0)
+                  : bin ? hz_prog_add_kernel(g, HZ_K_SEARCH_BSCAN, &bp, sizeof(bp), 0)
                   : fp8 ? hz_prog_add_kernel(g, HZ_K_SEARCH_QSCAN, &qp, sizeof(qp), 0)
                         : hz_prog_add_kernel(g, HZ_K_SEARCH_FSCAN, &f, sizeof(f), 0);
     } else {
@@ -608,29 +634,47 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 9 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 11 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 9) return fail("index: unknown format version " + std::to_string(h.version));
+  if (h.version < 1 || h.version > 11) return fail("index: unknown format version " + std::to_string(h.version));
   const bool ivf = h.version >= 5 && h.version <= 7;
   const bool fp8 = h.version == 3 || h.version == 4 || h.version == 6 || h.version == 7;
   const bool bin = h.version == 8 || h.version == 9;
-  const bool rescore = h.version == 4 || h.version == 7 || h.version == 9;
+  const bool pq = h.version == 10 || h.version == 11;
+  const bool rescore = h.version == 4 || h.version == 7 || h.version == 9 || h.version == 11;
   const std::string vname = "version-" + std::to_string(h.version);
   if (fp8 != (js.rfind("\"dtype\": \"fp8_e4m3\"") != std::string::npos))
     return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
   if (bin != (js.rfind("\"dtype\": \"bin_sign\"") != std::string::npos))
     return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
+  if (pq != (js.rfind("\"dtype\": \"pq8\"") != std::string::npos))
+    return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
   if (!ivf && js.rfind("\"ivf\": {") != std::string::npos)
     return fail("index: an ivf block in a " + vname + " file (it belongs to versions 5, 6 and 7)");
+  uint64_t pq_u[4] = {0, 0, 0, 0};  // m, ksub, dsub, codebook_off
+  if (pq) {
+    static const char* keys[4] = {"m", "ksub", "dsub", "codebook_off"};
+    if (js.rfind("\"pq\": {") == std::string::npos) return fail("index: a " + vname + " file without a pq block");
+    for (int i = 0; i < 4; ++i)
+      if (!json_u64(js, keys[i], &pq_u[i], true)) return fail(std::string("index: the pq block lacks ") + keys[i]);
+    if (pq_u[1] != 256) return fail("index: pq ksub must be 256, got " + std::to_string(pq_u[1]));
+    const uint64_t m = pq_u[0];
+    if (m < 16 || m > HZ_SEARCH_PQ_MAX_M || m % 16 || h.dim < 1 || h.dim > 2048 || h.dim % m || h.dim / m > HZ_SEARCH_PQ_MAX_DSUB ||
+        pq_u[2] != h.dim / m)
+      return fail("index: pq needs m % 16 == 0, 16 <= m <= 96, dim % m == 0, dsub = dim / m in 1..64 and dim <= 2048, got m = " +
+                  std::to_string(m) + ", dsub = " + std::to_string(pq_u[2]) + ", dim = " + std::to_string(h.dim));
+  } else if (js.rfind("\"pq\": {") != std::string::npos) {
+    return fail("index: a pq block in a " + vname + " file (it belongs to versions 10 and 11)");
+  }
   if (fp8 && (h.dim < 16 || h.dim % 16 || h.dim > 2048))
     return fail("index: dim of an fp8 index must be a multiple of 16 in 16..2048");
   if (bin && (h.dim < 128 || h.dim % 128 || h.dim > 2048))
     return fail("index: dim of a binary index must be a multiple of 128 in 128..2048");
-  if (h.dim < 8 || h.dim % 8 || h.dim > 2048) return fail("index: dim must be a multiple of 8 in 8..2048");
+  if (!pq && (h.dim < 8 || h.dim % 8 || h.dim > 2048)) return fail("index: dim must be a multiple of 8 in 8..2048");
   if (h.count < 1 || h.count >= (1ull << 31)) return fail("index: count must be in 1..2^31-1");
   if (h.metric > HZ_INDEX_IP) return fail("index: unknown metric");
   // an IVF file's blocks hold `capacity` stored rows (whole tiles); from here on h.count is that number
@@ -650,7 +694,8 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
       return fail("index: ivf nlist / nprobe out of range");
     h.count = stored;
   }
-  const uint64_t bytes = bin ? h.count * (h.dim / 8) : h.count * h.dim * (fp8 ? 1 : 2), fsize = (uint64_t)sb.st_size;
+  const uint64_t bytes = pq ? h.count * pq_u[0] : bin ? h.count * (h.dim / 8) : h.count * h.dim * (fp8 ? 1 : 2),
+                 fsize = (uint64_t)sb.st_size;
   if (h.data_off % 4096 || h.data_off < sizeof(h) + h.json_len || h.data_off + bytes > fsize)
     return fail("index: row block outside the file");
   uint64_t tags_off = 0, live_off = 0;
@@ -663,7 +708,13 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
       return fail("index: scales block outside the file");
     after_rows = scales_off + h.count * 4;
   }
-  if (fp8 || bin) {
+  const uint64_t cb_off = pq_u[3], cb_len = pq ? 256ull * h.dim * 4 : 0;
+  if (pq) {
+    if (cb_off % 4096 || cb_off < after_rows || cb_off > fsize || cb_len > fsize - cb_off)
+      return fail("index: codebook block unaligned, overlapping the rows or outside the file");
+    after_rows = cb_off + cb_len;
+  }
+  if (fp8 || bin || pq) {
     const bool t = json_u64(js, "tags_off", &tags_off, true), l = json_u64(js, "live_off", &live_off, true);
     if (t != l) return fail("index: a " + vname + " file with only one of tags_off / live_off");
     if (ivf && !t) return fail("index: a " + vname + " file without tags_off / live_off");
@@ -671,14 +722,14 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   }
   uint64_t rescore_off = 0;
   const uint64_t rescore_len = n_ext * h.dim * 2;  // [count][dim]: an IVF file holds them by external id
-  if (fp8 || bin) {
+  if (fp8 || bin || pq) {
     const bool off = json_u64(js, "rescore_off", &rescore_off, true);
     const bool key = js.rfind("\"rescore\": \"bf16\"") != std::string::npos;
     if (rescore && !(off && key)) return fail("index: a " + vname + " file without rescore / rescore_off");
-    if (!rescore && (off || key)) return fail("index: a " + vname + " file with rescore keys (they belong to versions " + (bin ? "4, 7 and 9" : "4 and 7") + ")");
+    if (!rescore && (off || key)) return fail("index: a " + vname + " file with rescore keys (they belong to versions " + (pq ? "4, 7, 9 and 11" : bin ? "4, 7 and 9" : "4 and 7") + ")");
   }
   if (blocks) {
-    if (!fp8 && !bin && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
+    if (!fp8 && !bin && !pq && (!json_u64(js, "tags_off", &tags_off) || !json_u64(js, "live_off", &live_off)))
       return fail("index: a version-2 file without tags_off / live_off");
     if (tags_off % 4096 || live_off % 4096 || tags_off < after_rows || live_off < after_rows ||
         tags_off > fsize || tag_bytes > fsize - tags_off || live_off > fsize || live_bytes > fsize - live_off)
@@ -753,6 +804,8 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   idx->count = h.count;
   idx->fp8 = fp8;
   idx->bin = bin;
+  idx->pq = pq;
+  idx->pq_m = (int)pq_u[0];
   idx->rescore = rescore;
   idx->rescore_host = rescore && rescore_host != 0;
   idx->ivf = ivf;
@@ -770,6 +823,7 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->slot_dev), sb_) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&c->out_dev), 2 * kOutHalf) == hipSuccess;
     if (rescore) ok = ok && hipMalloc(reinterpret_cast<void**>(&c->mid_dev), 2 * kOutHalf) == hipSuccess;
+    if (pq) ok = ok && hipMalloc(reinterpret_cast<void**>(&c->lut), idx->lut_bytes()) == hipSuccess;
     if (ivf) {
       c->ccand_bytes = hz_search_scratch_bytes((long long)ivf_u[0], HZ_SEARCH_MAX_Q, HZ_SEARCH_MAX_K);
       ok = ok && hipMalloc(reinterpret_cast<void**>(&c->probe_dev), 2 * kOutHalf) == hipSuccess;
@@ -828,6 +882,21 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
         return fail("index: upload failed");
     }
   }
+  if (pq) {  // the codebook: file -> host mirror -> device
+    idx->codebook_host.resize(cb_len / 4);
+    const int cfd = open(path, O_RDONLY | O_CLOEXEC);
+    uint64_t done = 0;
+    while (cfd >= 0 && done < cb_len) {
+      const ssize_t n = pread(cfd, reinterpret_cast<char*>(idx->codebook_host.data()) + done, cb_len - done, (off_t)(cb_off + done));
+      if (n <= 0) break;
+      done += (uint64_t)n;
+    }
+    if (cfd >= 0) close(cfd);
+    if (done != cb_len) return fail("index: cannot read the codebook block");
+    if (hipMalloc(reinterpret_cast<void**>(&idx->codebook), cb_len) != hipSuccess ||
+        hipMemcpy(idx->codebook, idx->codebook_host.data(), cb_len, hipMemcpyHostToDevice) != hipSuccess)
+      return fail("index: codebook upload failed");
+  }
   if (rescore && idx->rescore_host) {  // the file's block straight into the pinned rows
     const int rfd = open(path, O_RDONLY | O_CLOEXEC);
     uint64_t done = 0;
@@ -858,8 +927,10 @@ int hz_index_describe(void* h, uint64_t* out) {
   AllLocked all(*x);
   uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4 + (x->fp8 ? x->cap * 4 : 0);
   if (!x->rescore_host) dev += x->rescore_bytes();
+  dev += x->codebook_bytes();
   for (auto& c : x->ctx) {
     progs += c->progs.size();
+    dev += x->lut_bytes();
     dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf + (c->mid_dev ? 2 * kOutHalf : 0);
     dev += c->ncand_bytes + (c->nid_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 + 2 * kSelfOutHalf : 0);  // neighbours, once used
     dev += c->bq_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * x->h.dim * 4 + 4 * kSelfOutHalf : 0;  // bulk search, once used
@@ -874,7 +945,7 @@ int hz_index_describe2(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
-  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->bin ? 2u : x->fp8 ? 1u : 0u,
+  const uint64_t v[8] = {x->cap, x->live_count, x->has_tags, x->mutated, x->scan_rows(), x->pq ? 3u : x->bin ? 2u : x->fp8 ? 1u : 0u,
                        x->rescore ? 1u : 0u, x->rescore_host ? 1u : 0u};
   std::memcpy(out, v, sizeof(v));
   return 0;
@@ -886,6 +957,19 @@ int hz_index_describe3(void* h, uint64_t* out) {
   AllLocked all(*x);
   const uint64_t v[8] = {x->ivf ? 1u : 0u, (uint64_t)x->nlist, (uint64_t)x->nprobe_default, x->ivf ? x->count / kTile : 0,
                          x->ivf ? x->n_ext : x->count, x->h.version, 0, 0};
+  std::memcpy(out, v, sizeof(v));
+  return 0;
+}
+
+int hz_index_describe4(void* h, uint64_t* out) {
+  if (!h || !out) return -1;
+  Index* x = static_cast<Index*>(h);
+  AllLocked all(*x);
+  uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (x->pq) {
+    v[0] = (uint64_t)x->pq_m, v[1] = x->h.dim / (uint64_t)x->pq_m, v[2] = x->codebook_bytes(), v[3] = x->lut_bytes();
+    if (hipSetDevice(x->device) == hipSuccess) v[4] = (uint64_t)hz_search_pq_span((long long)x->scan_rows(), 1, x->pq_m);
+  }
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
@@ -902,7 +986,7 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
     return -34;
   }
   if (refine && !x->rescore) {
-    g_err = std::string("index: refine needs rescore rows (") + (x->bin ? "a version-9 file" : "a version-4 or version-7 file") +
+    g_err = std::string("index: refine needs rescore rows (") + (x->pq ? "a version-11 file" : x->bin ? "a version-9 file" : "a version-4 or version-7 file") +
             "), the index holds " + x->dtype_name() + " rows only";
     return -27;
   }
@@ -912,7 +996,7 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
   }
   if (nprobe && !x->ivf) {
     g_err = "index: nprobe needs an IVF index (a version-5, 6 or 7 file)";
-    if (x->bin) g_err += ", this one is a bin_sign index of version " + std::to_string(x->h.version);
+    if (x->bin || x->pq) g_err += std::string(", this one is ") + x->quant_name() + " of version " + std::to_string(x->h.version);
     return -34;
   }
   if (x->ivf && (nprobe < 0 || (nprobe > HZ_SEARCH_MAX_K && nprobe < x->nlist))) {
@@ -924,7 +1008,7 @@ int hz_index_search3(void* h, int ctx, const float* queries, const unsigned* fil
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);
   if (hipSetDevice(x->device) != hipSuccess) return -10;
-  const bool filtered = x->fp8 || x->bin || x->mutated || filt != nullptr || x->ivf;
+  const bool filtered = x->fp8 || x->bin || x->pq || x->mutated || filt != nullptr || x->ivf;
   bool fresh = false;
   HzProgram g = x->ivf ? x->ivf_program(c, Q, k, nprobe, refine, false, &fresh) : x->program(c, Q, k, filtered, refine, &fresh);
   if (!g) return -11;
@@ -959,7 +1043,8 @@ int hz_index_probes(void* h, int ctx, const float* queries, int Q, int nprobe, i
   if (!x->ivf || nprobe < 1 || nprobe > x->nlist || nprobe > HZ_SEARCH_MAX_K) {
     g_err = x->ivf ? "index: nprobe must be in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " + std::to_string(nprobe)
                    : std::string("index: probes needs an IVF index (a version-5, 6 or 7 file)") +
-                         (x->bin ? ", this one is a bin_sign index of version " + std::to_string(x->h.version) : std::string());
+                         (x->bin || x->pq ? std::string(", this one is ") + x->quant_name() + " of version " + std::to_string(x->h.version)
+                                          : std::string());
     return -34;
   }
   Ctx& c = *x->ctx[ctx];
@@ -992,9 +1077,9 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
   Index* x = static_cast<Index*>(h);
   if (!x || !ids || !out_score || !out_id) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (x->fp8 || x->ivf || x->bin) {
+  if (x->fp8 || x->ivf || x->bin || x->pq) {
     g_err = std::string("index: neighbors is built for plain bf16 indexes (versions 1 and 2), this one is ") +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin ? "a bin_sign index" : "an fp8_e4m3 index") + " of version " +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->quant_name()) + " of version " +
             std::to_string(x->h.version);
     return -35;
   }
@@ -1045,9 +1130,9 @@ int hz_index_search_batch(void* h, int ctx, const float* queries, int Q, int k, 
   Index* x = static_cast<Index*>(h);
   if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (x->fp8 || x->ivf || x->bin) {
+  if (x->fp8 || x->ivf || x->bin || x->pq) {
     g_err = std::string("index: search_batch is built for plain bf16 indexes (versions 1 and 2), this one is ") +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin ? "a bin_sign index" : "an fp8_e4m3 index") + " of version " +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->quant_name()) + " of version " +
             std::to_string(x->h.version);
     return -44;
   }
@@ -1105,9 +1190,9 @@ void* cl_buffer(Ctx& c, int which, uint64_t need) {
 // what both clustering calls refuse: -9 the context, -38 an fp8 or an IVF index, -39 dim % 32, -40 C
 int cluster_check(const Index* x, int ctx, int C, const char* call) {
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (x->fp8 || x->ivf || x->bin) {
+  if (x->fp8 || x->ivf || x->bin || x->pq) {
     g_err = std::string("index: ") + call + " is built for plain bf16 indexes (versions 1 and 2), this one is " +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin ? "a bin_sign index" : "an fp8_e4m3 index") + " of version " +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->quant_name()) + " of version " +
             std::to_string(x->h.version);
     return -38;
   }
@@ -1287,7 +1372,7 @@ int hz_index_add(void* h, const unsigned short* rows_bf16, long long n, const un
   Index* x = static_cast<Index*>(h);
   if (!x || !rows_bf16 || n < 1) return -1;
   if (x->ivf) return no_ivf_add();
-  if (x->fp8 || x->bin) return wrong_dtype(x, "hz_index_add", "bf16");
+  if (x->fp8 || x->bin || x->pq) return wrong_dtype(x, "hz_index_add", "bf16");
   return add_rows(x, rows_bf16, nullptr, nullptr, n, tags, first_id);
 }
 
@@ -1342,6 +1427,33 @@ int hz_index_add_br(void* h, const unsigned* words, const unsigned short* rows_b
     return -29;
   }
   return add_rows(x, words, nullptr, rows_bf16, n, tags, first_id);
+}
+
+// pq8 rows (a version-10 file): n rows of pq_m code bytes, encoded by the caller against the index's codebook
+int hz_index_add_p(void* h, const unsigned char* codes, long long n, const unsigned* tags, long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !codes || n < 1) return -1;
+  if (x->ivf) return no_ivf_add();
+  if (!x->pq) return wrong_dtype(x, "hz_index_add_p", "pq8");
+  if (x->rescore) {
+    g_err = "index: hz_index_add_p adds pq8 rows only; an index with rescore rows takes hz_index_add_pr (codes and bf16 rows)";
+    return -29;
+  }
+  return add_rows(x, codes, nullptr, nullptr, n, tags, first_id);
+}
+
+// a two-stage pq8 index (a version-11 file): codes and bf16 rows together, the live bits set last
+int hz_index_add_pr(void* h, const unsigned char* codes, const unsigned short* rows_bf16, long long n, const unsigned* tags,
+                    long long* first_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !codes || !rows_bf16 || n < 1) return -1;
+  if (x->ivf) return no_ivf_add();
+  if (!x->pq) return wrong_dtype(x, "hz_index_add_pr", "pq8");
+  if (!x->rescore) {
+    g_err = "index: hz_index_add_pr needs an index with rescore rows (a version-11 file); use hz_index_add_p";
+    return -29;
+  }
+  return add_rows(x, codes, nullptr, rows_bf16, n, tags, first_id);
 }
 
 int hz_index_delete(void* h, const int* ids, long long n, long long* newly_deleted) {
@@ -1418,7 +1530,7 @@ extern "C" {
 int hz_index_read_state(void* h, unsigned short* rows_out, unsigned* tags_out, unsigned* live_out, long long n) {
   Index* x = static_cast<Index*>(h);
   if (!x || n < 0) return -1;
-  if (x->fp8 || x->bin) return wrong_dtype(x, "hz_index_read_state", "bf16");
+  if (x->fp8 || x->bin || x->pq) return wrong_dtype(x, "hz_index_read_state", "bf16");
   return read_state(x, rows_out, nullptr, tags_out, live_out, n);
 }
 
@@ -1437,6 +1549,21 @@ int hz_index_read_state_b(void* h, unsigned* words_out, unsigned* tags_out, unsi
   return read_state(x, words_out, nullptr, tags_out, live_out, n);
 }
 
+int hz_index_read_state_p(void* h, unsigned char* codes_out, unsigned* tags_out, unsigned* live_out, long long n) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || n < 0) return -1;
+  if (!x->pq) return wrong_dtype(x, "hz_index_read_state_p", "pq8");
+  return read_state(x, codes_out, nullptr, tags_out, live_out, n);
+}
+
+int hz_index_read_codebook(void* h, float* codebook_out) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !codebook_out) return -1;
+  if (!x->pq) return wrong_dtype(x, "hz_index_read_codebook", "pq8");
+  std::memcpy(codebook_out, x->codebook_host.data(), x->codebook_bytes());
+  return 0;
+}
+
 // the first n (<= count) rescore rows back to the host (for save)
 int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
   Index* x = static_cast<Index*>(h);
@@ -1445,6 +1572,7 @@ int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
   if (!x->rescore) {
     g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-4 or version-7 file)";
     if (x->bin) g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-9 file)";
+    if (x->pq) g_err = "index: hz_index_read_rescore needs an index with rescore rows (a version-11 file)";
     return -29;
   }
   if ((uint64_t)n > x->rescore_rows(x->count)) return -20;

@@ -488,6 +488,14 @@ extern "C" __attribute__((weak)) int hz_search_rescoren_launch(const HzSearchRes
 static int hz_search_rescoren_op(const HzSearchRescoreParams* p, hipStream_t st) {
   return hz_search_rescoren_launch ? hz_search_rescoren_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_pqlut_launch(const HzSearchPqLutParams* p, hipStream_t st);
+static int hz_search_pqlut_op(const HzSearchPqLutParams* p, hipStream_t st) {
+  return hz_search_pqlut_launch ? hz_search_pqlut_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_pqscan_launch(const HzSearchPqParams* p, hipStream_t st);
+static int hz_search_pqscan_op(const HzSearchPqParams* p, hipStream_t st) {
+  return hz_search_pqscan_launch ? hz_search_pqscan_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -18,7 +18,10 @@
 //                    top-1 key per row; search_cmean (kind CMEAN): a cluster's mean in a fixed summation order
 //   * search_bscan — the filtered scan over sign-bit rows (kind BSCAN): one word per 32 columns, the queries binarised
 //                    in the kernel, score = D - 2 popcount(q xor r); its lists go to search_merge like any other
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v for the reasoning.
+//   * search_pqlut / search_pqscan — product-quantised rows (kinds PQLUT, PQSCAN): a per-query table of the query's
+//                    inner products with 256 sub-centroids per sub-space, then the filtered scan over rows of M code
+//                    bytes, a workgroup holding ONE query's table in LDS and adding M lookups per row
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v / 4w for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -118,6 +121,7 @@ __host__ __device__ inline const HzSearchParams& scan_part(const HzSearchQuantPa
 __host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchFilterParams& a) { return a; }
 __host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchQuantParams& a) { return a.f; }
 __host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchBinParams& a) { return a.f; }
+__host__ __device__ inline const HzSearchFilterParams& filter_part(const HzSearchPqParams& a) { return a.f; }
 
 // Dynamic LDS of a scan, in the kernel's order: queries [Q][D], scores [Q][T]; filtered: pass bits [T], the
 // tile's live words [T / 32], filters [Q][2]; scaled: the passing rows' scales [T]. At most 144 KiB (Q = 16,
@@ -401,6 +405,101 @@ __global__ __launch_bounds__(T) void search_bscan_kernel(const HzSearchBinParams
   }
   __syncthreads();
   rank_tile<true>(p, sc, tile, row0, rows);
+}
+
+// ------------------------------------------------------------------------------ product quantisation
+// search_pqlut_kernel (HZ_K_SEARCH_PQLUT): grid (M, Q), PQ_KSUB threads. Thread c of workgroup (m, q)
+// writes lut[(q*M + m)*256 + c]: the contract's fmaf chain over the dsub columns of sub-space m, ascending from +0.
+// Addresses: queries[q*D + m*dsub + j] and codebook[(m*256 + c)*dsub + j] under j < dsub, m < M, q < Q; the one store
+// under ((q*M + m)*256 + c + 1) * 4 <= lut_bytes.
+constexpr int PQ_KSUB = 256;  // sub-centroids per sub-space: one code byte
+__global__ __launch_bounds__(PQ_KSUB) void search_pqlut_kernel(const HzSearchPqLutParams a) {
+  const int m = blockIdx.x, q = blockIdx.y, c = threadIdx.x;
+  if (!HZ_DCHECK(m < a.M && q < a.Q && a.M >= 1 && a.D % a.M == 0)) return;
+  const int dsub = a.D / a.M;
+  const float* qv = a.queries + (long)q * a.D + m * dsub;       // every lane reads the same words
+  const float* cv = a.codebook + ((long)m * PQ_KSUB + c) * dsub;
+  float acc = 0.f;
+  for (int j = 0; j < dsub; ++j) acc = fmaf(qv[j], cv[j], acc);
+  const long at = ((long)q * a.M + m) * PQ_KSUB + c;
+  if (HZ_DCHECK((at + 1) * 4 <= (long)a.lut_bytes)) a.lut[at] = acc;
+}
+
+// search_pqscan_kernel<NCH> (HZ_K_SEARCH_PQSCAN): the filtered scan over rows of M = 16 NCH code bytes against ONE
+// query's table. Grid (ceil(ntile / span), Q); workgroup (g, q) copies lut[q] (M KiB) from global memory into LDS
+// once, with 16-B loads, then walks the tiles g*span .. g*span + span - 1 (those below ntile). Per tile:
+//   * pass bits: stage_pass_bits as the list scan uses it, over this workgroup's query alone (Q = 1, its {mask, value}).
+//   * scoring: thread t owns row t and loads its NCH 16-B chunks only if the row passes for query q; a wave whose 64
+//     rows all fail loads nothing and writes its sentinels (a scalar branch). score = the contract's sum: M plain
+//     fp32 additions, m ascending from +0, of tab[m*256 + code[m]] -- one ds_read_b32 each, at random banks.
+//   * ranking: rank_query<true>, the piece rank_tile is made of, into cand[(tile*Q + q)*k ..]: the layout
+//     HZ_K_SEARCH_MERGE and HZ_K_SEARCH_RESCORE consume.
+// Nothing of a score depends on the tile, on span or on the grid: the table is a function of (query, codebook) and
+// the sum's order is fixed by M.
+// Addresses: lut 16-B words [q*M*64, (q + 1)*M*64) under lut_bytes; corpus bytes [(row0 + t)*ldc + 16c, + 16) under
+// t < rows, row < N and 16c < M <= ldc; live, tags, filt as in stage_pass_bits; cand through rank_query (`rank < k`).
+// LDS: dynamic M KiB (the table), static scores [T], pass bits, live words and one filter: 2,096 B.
+template <int NCH>
+__global__ __launch_bounds__(T) void search_pqscan_kernel(const HzSearchPqParams a) {
+  const HzSearchParams& p = a.f.s;
+  extern __shared__ __attribute__((aligned(16))) float tab[];  // [M][256]
+  __shared__ unsigned sc[T];
+  __shared__ unsigned pmask[T + T / 32 + 2];  // pass bits, the tile's live words, {mask, value}
+  const int t = threadIdx.x;
+  const int q = blockIdx.y;
+  const int M = NCH * 16;
+  if (!HZ_DCHECK(a.M == M && a.span >= 1 && q < p.Q && p.Q >= 1 && p.Q <= HZ_SEARCH_MAX_Q && p.ldc >= M &&
+                 (long)blockIdx.x * a.span < (long)p.ntile))
+    return;
+  {
+    const f32x4* src = reinterpret_cast<const f32x4*>(a.lut) + (long)q * M * (PQ_KSUB / 4);
+    for (int i = t; i < M * (PQ_KSUB / 4); i += T)
+      if (HZ_DCHECK((((long)q * M * (PQ_KSUB / 4)) + i + 1) * 16 <= (long)a.lut_bytes))
+        reinterpret_cast<f32x4*>(tab)[i] = src[i];
+  }
+  const unsigned char* corpus = reinterpret_cast<const unsigned char*>(p.corpus);
+  HzSearchFilterParams f1 = a.f;  // what stage_pass_bits reads: this query and its {mask, value}, as in the list scan
+  f1.s.Q = 1;
+  if (f1.filt) f1.filt += 2 * q;
+#pragma unroll 1
+  for (int s = 0; s < a.span; ++s) {  // workgroup-uniform bounds
+    const int tile = blockIdx.x * a.span + s;
+    if (tile >= p.ntile) break;
+    if (!HZ_DCHECK((long)tile * T < (long)p.N)) break;
+    const long row0 = (long)tile * T;
+    const int rows = (int)min((long)T, (long)p.N - row0);
+    stage_pass_bits<BinRows>(f1, pmask, nullptr, row0, rows);  // its barrier also ends the last tile's reads of sc
+    __syncthreads();                                           // and, in the first round, publishes the table
+
+    const bool pass = pmask[t] & 1u;  // false for a row past the tile's end
+    unsigned key = 0u;
+    if (__ballot(pass) != 0ull) {  // scalar: some row of this wave passes for this query
+      u32x4 v[NCH];
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        v[c] = u32x4{0u, 0u, 0u, 0u};
+        if (pass && HZ_DCHECK(t < rows && row0 + t < (long)p.N))
+          v[c] = *reinterpret_cast<const u32x4*>(corpus + (row0 + t) * p.ldc + c * 16);
+      }
+      float acc = 0.f;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const unsigned code = (v[c][w] >> (8 * b)) & 0xFFu;
+            const int m = c * 16 + w * 4 + b;
+            if (HZ_DCHECK(code < (unsigned)PQ_KSUB)) acc = acc + tab[m * PQ_KSUB + code];
+          }
+      if (pass) key = orderable(acc);
+    }
+    sc[t] = key;
+    __syncthreads();
+    unsigned long long* out = p.cand + ((long)tile * p.Q + q) * p.k;
+    const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
+    rank_query<true>(sc, out, slot_ok, p.k, rows, (unsigned)(row0 + t));
+  }
 }
 
 // -------------------------------------------------------------------------------------- list scan
@@ -1429,6 +1528,119 @@ extern "C" int hz_search_bscan_launch(const HzSearchBinParams* pp, hipStream_t s
 
 namespace {
 
+// the shape rules of product-quantised rows (hipzap.h): -114 M % 16, -115 M outside 16..96, -113 D % M,
+// -116 D / M outside 1..64, -117 D > 2048
+int pq_shape_check(int D, int M) {
+  if (M % 16) return -114;
+  if (M < 16 || M > HZ_SEARCH_PQ_MAX_M) return -115;
+  if (D < 1 || D % M) return -113;
+  if (D / M > HZ_SEARCH_PQ_MAX_DSUB) return -116;
+  if (D > 2048) return -117;
+  return 0;
+}
+
+template <int NCH>
+int raise_pq_lds_limit_of() {
+  HZ_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&search_pqscan_kernel<NCH>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, HZ_SEARCH_PQ_MAX_M * 1024));
+  if constexpr (NCH < HZ_SEARCH_PQ_MAX_M / 16) return raise_pq_lds_limit_of<NCH + 1>();
+  return 0;
+}
+
+// The table of M = 80 or 96 is above 64 KiB of dynamic LDS: allowed once per device, outside any capture, where the
+// device's compute units are counted too (hz_search_code_warm at an index's open; a direct launch here).
+int pq_cus[64];
+int pq_device_setup(int* cus) {
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
+  if (!pq_cus[d]) {
+    int n = 0;
+    if (const int rc = raise_pq_lds_limit_of<1>()) return rc;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 1) return -8;
+    pq_cus[d] = n;
+  }
+  if (cus) *cus = pq_cus[d];
+  return 0;
+}
+
+// Tiles per workgroup. M >= 80: the table lets ONE workgroup live on a compute unit, so nothing hides its copy of
+// the table (M KiB) but the tiles that follow it: the span that leaves about two workgroups per compute unit over the
+// grid (ceil(ntile / span), Q). M <= 64: two or more workgroups share a compute unit, one's copy runs under another's
+// lookups, and more, shorter workgroups balance better: that span, but at most max(2, M / 16) (the sweep over spans in
+// DESIGN.md 4w / profiles/search_pq/span.json). A score's bits do not depend on the choice.
+int pq_auto_span(long ntile, int Q, int cus, int M) {
+  long span = (ntile * Q + 2l * cus - 1) / (2l * cus);
+  if (M < 80) span = min(span, (long)max(2, M / 16));
+  return (int)max(1l, min(span, ntile));
+}
+
+template <int NCH = 1>
+void pqscan_dispatch(const HzSearchPqParams& a, const dim3 grid, hipStream_t st) {
+  if constexpr (NCH < HZ_SEARCH_PQ_MAX_M / 16) {
+    if (a.M > NCH * 16) return pqscan_dispatch<NCH + 1>(a, grid, st);
+  }
+  hipLaunchKernelGGL(search_pqscan_kernel<NCH>, grid, dim3(T), (size_t)a.M * 1024, st, a);
+}
+
+}  // namespace
+
+extern "C" int hz_search_pq_span(long long N, int Q, int M) {
+  if (N < 1 || N >= (1ll << 31) || Q < 1 || Q > HZ_SEARCH_MAX_Q || M < 16 || M > HZ_SEARCH_PQ_MAX_M || M % 16) return 0;
+  int cus = 0;
+  if (pq_device_setup(&cus)) return 0;
+  return pq_auto_span((long)((N + T - 1) / T), Q, cus, M);
+}
+
+// The product-quantised kinds' refusal list (hipzap.h): -112 .. -128.
+extern "C" int hz_search_pqlut_launch(const HzSearchPqLutParams* pp, hipStream_t st) {
+  if (!pp) return -112;
+  const HzSearchPqLutParams a = *pp;
+  if (!a.queries || !a.codebook || !a.lut) return -112;
+  if (const int rc = pq_shape_check(a.D, a.M)) return rc;
+  if (a.Q < 1 || a.Q > HZ_SEARCH_MAX_Q) return -120;
+  if ((reinterpret_cast<uintptr_t>(a.queries) & 15) || (reinterpret_cast<uintptr_t>(a.codebook) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.lut) & 15))
+    return -122;
+  if (a.lut_bytes < (unsigned long long)a.Q * a.M * 1024ull) return -127;
+  hipLaunchKernelGGL(search_pqlut_kernel, dim3(a.M, a.Q), dim3(PQ_KSUB), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_search_pqscan_launch(const HzSearchPqParams* pp, hipStream_t st) {
+  if (!pp) return -112;
+  HzSearchPqParams a = *pp;
+  HzSearchFilterParams& f = a.f;
+  HzSearchParams& p = f.s;
+  if (!p.corpus || !p.queries || !p.cand || !p.out_score || !p.out_id || !a.lut) return -112;
+  if (const int rc = pq_shape_check(p.D, a.M)) return rc;
+  if (p.ldc < a.M || p.ldc % 16) return -118;
+  if (p.N < 1) return -119;
+  if (p.Q < 1 || p.Q > HZ_SEARCH_MAX_Q) return -120;
+  if (p.k < 1 || p.k > HZ_SEARCH_MAX_K) return -121;
+  if ((reinterpret_cast<uintptr_t>(p.corpus) & 15) || (reinterpret_cast<uintptr_t>(p.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.lut) & 15) || (reinterpret_cast<uintptr_t>(p.cand) & 7) ||
+      (reinterpret_cast<uintptr_t>(p.out_score) & 3) || (reinterpret_cast<uintptr_t>(p.out_id) & 3) ||
+      (reinterpret_cast<uintptr_t>(f.live) & 3) || (reinterpret_cast<uintptr_t>(f.tags) & 3) ||
+      (reinterpret_cast<uintptr_t>(f.filt) & 3))
+    return -122;
+  if (!f.live) return -123;
+  if (f.live_bytes < 4ull * (((unsigned long long)p.N + 31) / 32)) return -124;
+  if (f.filt && !f.tags) return -125;
+  const unsigned long long need = hz_search_scratch_bytes(p.N, p.Q, p.k);
+  if (!need || p.cand_bytes < need) return -126;
+  if (a.lut_bytes < (unsigned long long)p.Q * a.M * 1024ull) return -127;
+  if (a.span < 0) return -128;
+  p.ntile = (int)(((long)p.N + T - 1) / T);
+  int cus = 0;
+  if (const int rc = pq_device_setup(&cus)) return rc;
+  if (a.span == 0) a.span = pq_auto_span(p.ntile, p.Q, cus, a.M);
+  if (a.span > p.ntile) a.span = p.ntile;
+  pqscan_dispatch(a, dim3((p.ntile + a.span - 1) / a.span, p.Q), st);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
 template <class Fmt, int NC = 1>
 void lscan_dispatch(const ListArgs<Fmt>& args, hipStream_t st) {
   const HzSearchListParams& a = list_part(args);
@@ -1670,5 +1882,6 @@ extern "C" int hz_search_code_warm(void) {
   if (const int rc = (int)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&hz_search_code_warm_kernel))) return rc;
   if (const int rc = raise_lds_limit()) return rc;
   if (const int rc = raise_mscan_lds_limit()) return rc;
-  return raise_xscan_lds_limit();
+  if (const int rc = raise_xscan_lds_limit()) return rc;
+  return pq_device_setup(nullptr);
 }

@@ -21,6 +21,9 @@ over external queries, each split into three bf16 terms; ``HZ_K_SEARCH_MERGEN`` 
 ``HZ_K_SEARCH_RESCOREN`` is the rescore (``RescoreParams``) for any number of queries.
 ``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
+``HZ_K_SEARCH_PQLUT`` (``PqLutParams``) writes each query's table of inner products with the 256 sub-centroids of every
+sub-space of a product quantiser; ``HZ_K_SEARCH_PQSCAN`` (``PqScanParams``: the filtered block over uint8 code rows,
+``ldc`` in bytes, plus the table) adds M table entries per row, one query's table resident in LDS per workgroup.
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ SELF_MAX_Q = 65535 * SELF_QB     # HZ_SEARCH_SELF_MAX_Q: the self scan's and its
 INDEX_SELF_MAX_Q = 1024          # HZ_INDEX_SELF_MAX_Q: ids per hz_index_neighbors call
 ASSIGN_CB = 64                   # HZ_SEARCH_ASSIGN_CB: centroids per block of the assign kernel
 ASSIGN_MAX_C = 65536             # HZ_SEARCH_ASSIGN_MAX_C: the most centroids (hipzap.search.IVF_MAX_LISTS)
+PQ_MAX_M, PQ_MAX_DSUB, PQ_KSUB = 96, 64, 256  # HZ_SEARCH_PQ_MAX_M, HZ_SEARCH_PQ_MAX_DSUB; sub-centroids per sub-space
 
 
 @N.params_of("HZ_K_SEARCH_MERGE")
@@ -72,6 +76,28 @@ class BinScanParams(C.Structure):
     """HzSearchBinParams: the fields of ``FilterScanParams`` (``corpus``: uint32 sign-bit rows [N][ldc], ``ldc`` in
     words; ``live`` is required)."""
     _fields_ = list(FilterScanParams._fields_)
+
+    def scan_params(self) -> SearchParams:
+        """The merge's block: it reads no row, but checks a bf16 pitch, so ``ldc`` = D there."""
+        sp = SearchParams.from_buffer_copy(self)
+        sp.ldc = sp.D
+        return sp
+
+
+@N.params_of("HZ_K_SEARCH_PQLUT")
+class PqLutParams(C.Structure):
+    """HzSearchPqLutParams: ``queries`` fp32 [Q][D], ``codebook`` fp32 [M][256][D / M], ``lut`` fp32 [Q][M][256] out."""
+    _fields_ = [("queries", C.c_void_p), ("codebook", C.c_void_p), ("lut", C.c_void_p), ("lut_bytes", C.c_uint64),
+                ("D", C.c_int), ("M", C.c_int), ("Q", C.c_int), ("pad_", C.c_int)]
+
+
+@N.params_of("HZ_K_SEARCH_PQSCAN")
+class PqScanParams(C.Structure):
+    """HzSearchPqParams: the fields of ``FilterScanParams`` (``corpus``: uint8 code rows [N][ldc], ``ldc`` in bytes;
+    ``live`` is required), then ``lut`` (the table kind's output), ``lut_bytes``, ``M`` and ``span`` (0: the
+    launcher's choice)."""
+    _fields_ = FilterScanParams._fields_ + [("lut", C.c_void_p), ("lut_bytes", C.c_uint64), ("M", C.c_int),
+                                            ("span", C.c_int)]
 
     def scan_params(self) -> SearchParams:
         """The merge's block: it reads no row, but checks a bf16 pitch, so ``ldc`` = D there."""
@@ -186,6 +212,14 @@ def _sigs(lib):
     N._sig(lib, "hz_index_add_b", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_add_br", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_read_state_b", C.c_int, P, P, P, P, C.c_longlong)
+    N._sig(lib, "hz_search_pqlut_launch", C.c_int, C.POINTER(PqLutParams), P)
+    N._sig(lib, "hz_search_pqscan_launch", C.c_int, C.POINTER(PqScanParams), P)
+    N._sig(lib, "hz_search_pq_span", C.c_int, C.c_longlong, C.c_int, C.c_int)
+    N._sig(lib, "hz_index_add_p", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_add_pr", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
+    N._sig(lib, "hz_index_read_state_p", C.c_int, P, P, P, P, C.c_longlong)
+    N._sig(lib, "hz_index_read_codebook", C.c_int, P, P)
+    N._sig(lib, "hz_index_describe4", C.c_int, P, C.POINTER(U64))
     N._sig(lib, "hz_search_lscan_launch", C.c_int, C.POINTER(ListScanParams), P)
     N._sig(lib, "hz_search_qlscan_launch", C.c_int, C.POINTER(QuantListScanParams), P)
     N._sig(lib, "hz_search_code_warm", C.c_int)
@@ -262,6 +296,28 @@ def launch_bin(prm: BinScanParams, stream: int = 0) -> tuple:
         return rc, None
     sp = prm.scan_params()
     return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def launch_pq_lut(prm: PqLutParams, stream: int = 0) -> int:
+    """The table launch (``HZ_K_SEARCH_PQLUT``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_pqlut_launch(C.byref(prm), stream))
+
+
+def launch_pq(prm: PqScanParams, stream: int = 0) -> tuple:
+    """Product-quantised scan (over a table ``launch_pq_lut`` wrote) then merge on ``stream``: (scan code, merge
+    code); no merge after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_pqscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    sp = prm.scan_params()
+    return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def pq_span(n: int, q: int, m: int) -> int:
+    """The tiles per workgroup a scan of (N, Q) over rows of M codes takes with ``span`` = 0 on the current device; 0
+    for a refused shape."""
+    return int(N.lib().hz_search_pq_span(int(n), int(q), int(m)))
 
 
 def launch_rescore(prm: RescoreParams, stream: int = 0) -> int:

@@ -38,7 +38,14 @@ of column ``i`` is clear (the live bitmap's bit convention; ``-0.0`` gives 0), n
 ``tags_off`` / ``live_off`` present exactly when version 3 would have them. Version 9 is version 8 plus ``"rescore":
 "bf16"`` and ``rescore_off`` as in version 4. Stage one of a search scores ``dim - 2 * popcount(query bits xor row
 bits)``, an integer, so ties are the normal case and the order rule decides them; ``search(refine=R)`` re-scores the
-best R against the bf16 rows exactly as version 4 does (:func:`prepare_rows_bin`).
+best R against the bf16 rows exactly as version 4 does (:func:`prepare_rows_bin`). Version 10 is a
+product-quantised index (``dtype`` ``"pq8"``, ``write_index(dtype="pq", pq_m=M)``): version 3's rule set over rows of M
+code bytes -- the row block is uint8 ``[count][M]``, the JSON block ``"pq": {"m", "ksub": 256, "dsub", "codebook_off"}``
+names a 4096-aligned block after the rows holding the fp32 codebook ``[M][256][dim / M]``, no scales block,
+``capacity`` / ``tags_off`` / ``live_off`` present exactly when version 3 would have them (``M % 16 == 0``, 16..96,
+``dim % M == 0``, ``dim / M`` in 1..64, ``dim <= 2048``). Version 11 is version 10 plus ``"rescore": "bf16"`` and
+``rescore_off`` as in version 4. Stage one scores a row by adding M entries of a per-query table of inner products with
+the sub-centroids (:func:`pq_lut_ref`, :func:`pq_scores_from_lut`).
 
 A live index (:meth:`Index.add`, ``delete``, ``set_tags``, ``search(filter=...)``, ``save``): ids are row
 positions and are never reused; a search returns the top k of the rows that are live and whose tag passes
@@ -71,17 +78,23 @@ VERSION6 = 6  # version 5's layout with version 3's rows: e4m3 codes and fp32 sc
 VERSION7 = 7  # version 6 plus rescore / rescore_off: bf16 rows [count][dim] in external-id order, the last block
 VERSION8 = 8  # sign-bit rows: uint32 [count][dim / 32], no scales; tags / live as in version 3, or absent
 VERSION9 = 9  # version 8 plus rescore / rescore_off, as version 4 adds them to version 3
+VERSION10 = 10  # pq8 rows: uint8 [count][M], the JSON block pq and the codebook block; tags / live as in version 3, or absent
+VERSION11 = 11  # version 10 plus rescore / rescore_off, as version 4 adds them to version 3
 FP8_VERSIONS, IVF_VERSIONS, RESCORE_VERSIONS = (VERSION3, VERSION4, VERSION6, VERSION7), (VERSION5, VERSION6, VERSION7), \
-    (VERSION4, VERSION7, VERSION9)
+    (VERSION4, VERSION7, VERSION9, VERSION11)
 BIN_VERSIONS = (VERSION8, VERSION9)
+PQ_VERSIONS = (VERSION10, VERSION11)
 TILE = 256   # HZ_SEARCH_TILE (csrc/hipzap.h): an IVF list starts on a tile boundary
 IVF_MAX_LISTS = 65536
 IVF_SAMPLE = 256  # k-means trains on at most this many rows per centroid
 NEIGHBORS_BLOCK = 1024  # rows per pass of knn_graph: HZ_INDEX_SELF_MAX_Q (csrc/hipzap.h), one native call
 IVF_KEYS = ("centroids_off", "list_off_off", "list_tiles_off", "rowid_off")
-DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3", "bin": "bin_sign"}  # write_index(dtype=...) -> the header's "dtype"
+DTYPES = {"bf16": "bf16", "fp8": "fp8_e4m3", "bin": "bin_sign", "pq": "pq8"}  # write_index(dtype=...) -> the header's "dtype"
 FP8 = "fp8_e4m3"
 BIN = "bin_sign"
+PQ = "pq8"
+PQ_KSUB, PQ_MAX_M, PQ_MAX_DSUB = 256, 96, 64  # sub-centroids per sub-space; HZ_SEARCH_PQ_MAX_M, HZ_SEARCH_PQ_MAX_DSUB
+PQ_SAMPLE = 65536  # rows pq_train takes at most
 METRICS = ("cosine", "ip")
 ALIGN = 4096
 HEAD = struct.Struct("<8sIIQQII")  # HzIndexHeader: magic, version, json_len, data_off, count, dim, metric
@@ -231,6 +244,183 @@ def bin_search_ref(words, qbits, dim: int, k: int, allow=None):
     return scores, ids
 
 
+def check_pq_shape(dim, m) -> int:
+    """The shape rules of product-quantised rows (csrc/hipzap.h) -> dsub = dim / m, or a ValueError that names them."""
+    if not _is_int(m) or m % 16 or not 16 <= m <= PQ_MAX_M:
+        raise ValueError(f"pq m must be a multiple of 16 in 16..{PQ_MAX_M} (a row is whole 16-byte chunks and one query's "
+                         f"table is m KiB of LDS), got {m!r}")
+    if not _is_int(dim) or dim < m or dim % m or dim > 2048 or dim // m > PQ_MAX_DSUB:
+        raise ValueError(f"dim of a pq index must be a multiple of m = {m} with dim / m in 1..{PQ_MAX_DSUB} and dim <= 2048, "
+                         f"got {dim!r}")
+    return int(dim) // int(m)
+
+
+def check_codebook(codebook, dim: int, m: int) -> np.ndarray:
+    """``codebook`` as finite fp32 [m, 256, dim / m]."""
+    dsub = check_pq_shape(dim, m)
+    cb = np.asarray(codebook)
+    if cb.shape != (m, PQ_KSUB, dsub) or cb.dtype.kind != "f":
+        raise ValueError(f"codebook must be floats [{m}, {PQ_KSUB}, {dsub}], got {cb.dtype} {list(cb.shape)}")
+    cb = np.ascontiguousarray(cb, np.float32)
+    if not np.isfinite(cb).all():
+        raise ValueError("the codebook has a non-finite value")
+    return cb
+
+
+def _pq_nearest(x32: np.ndarray, cent32: np.ndarray):
+    """Rows fp32 [n, dsub] against centroids fp32 [256, dsub] -> (the nearest centroid uint8 [n], its squared distance
+    float64 [n]): ``|x|^2 + |c|^2 - 2 x.c`` evaluated in fp64, the lower index among equal values."""
+    c = cent32.astype(np.float64)
+    cn = (c * c).sum(axis=1)
+    best = np.empty(x32.shape[0], np.uint8)
+    dist = np.empty(x32.shape[0], np.float64)
+    for a in range(0, x32.shape[0], 1 << 16):
+        x = x32[a:a + (1 << 16)].astype(np.float64)
+        d = (x * x).sum(axis=1)[:, None] + cn[None, :] - 2.0 * (x @ c.T)
+        i = np.argmin(d, axis=1)  # the first of equal minima
+        best[a:a + (1 << 16)], dist[a:a + (1 << 16)] = i, d[np.arange(i.size), i]
+    return best, dist
+
+
+def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ_SAMPLE, init=None) -> np.ndarray:
+    """Train a product quantiser on ``rows32`` (fp32 [N, D]) -> the codebook, fp32 [m, 256, D / m]. Per sub-space,
+    Lloyd's k-means under squared L2 over at most ``sample`` rows: the rows are the first ``sample`` of a seeded
+    permutation, in ascending order, the same rows for every sub-space; the first centroids of sub-space j are the
+    sub-vectors of 256 of those rows (one more seeded draw, the same rows for every sub-space; with fewer than 256
+    rows the remaining centroids are zero). Assignment is :func:`pq_encode`'s (fp64, the lower centroid on ties); a
+    centroid becomes its members' mean, accumulated in fp64 in row order and rounded to fp32, and keeps its value
+    when it has no member. Deterministic for a given input and seed. ``init`` (fp32 [m, 256, D / m]) replaces the
+    first centroids; ``iters=0`` with ``init`` returns it unchanged."""
+    x = np.asarray(rows32)
+    if x.ndim != 2 or x.dtype.kind != "f" or x.shape[0] < 1:
+        raise ValueError(f"rows must be a float array [N, D] with N >= 1, got {x.dtype} {list(x.shape)}")
+    x = np.ascontiguousarray(x, np.float32)
+    n, d = x.shape
+    dsub = check_pq_shape(d, m)
+    if not _is_int(iters) or iters < 0 or not _is_int(seed) or seed < 0 or not _is_int(sample) or sample < 1:
+        raise ValueError(f"seed and iters must be integers >= 0 and sample >= 1, got {seed!r}, {iters!r}, {sample!r}")
+    rng = np.random.default_rng(seed)
+    take = np.sort(rng.permutation(n)[:sample])
+    first = np.sort(rng.permutation(take.size)[:PQ_KSUB])
+    xs = x[take].reshape(take.size, m, dsub)
+    if init is None:
+        cb = np.zeros((m, PQ_KSUB, dsub), np.float32)
+        cb[:, :first.size] = xs[first].transpose(1, 0, 2)
+    else:
+        cb = check_codebook(init, d, m).copy()
+    for _ in range(int(iters)):
+        for j in range(m):
+            sub = np.ascontiguousarray(xs[:, j])
+            a = _pq_nearest(sub, cb[j])[0]
+            order = np.argsort(a, kind="stable")  # ascending rows inside a cluster
+            sizes = np.bincount(a, minlength=PQ_KSUB)
+            used = np.flatnonzero(sizes)
+            starts = np.concatenate([[0], np.cumsum(sizes)])[used]
+            sums = np.add.reduceat(sub[order].astype(np.float64), starts, axis=0)
+            cb[j, used] = (sums / sizes[used][:, None]).astype(np.float32)
+    return cb
+
+
+def pq_encode(rows32, codebook) -> np.ndarray:
+    """fp32 rows [N, D] -> codes uint8 [N, M]: per sub-space the nearest centroid of ``codebook`` (fp32 [M, 256, D / M])
+    by squared L2 evaluated in fp64, the lower index on ties. Works through the rows in chunks, one sub-space at a
+    time: 10^6 x 768 needs the input, the codes and a few hundred MB."""
+    cb = np.asarray(codebook, np.float32)
+    x = np.ascontiguousarray(rows32, np.float32)
+    m, _, dsub = cb.shape
+    if x.ndim != 2 or x.shape[1] != m * dsub:
+        raise ValueError(f"rows must be [N, {m * dsub}], got {list(x.shape)}")
+    codes = np.empty((x.shape[0], m), np.uint8)
+    for j in range(m):
+        codes[:, j] = _pq_nearest(x[:, j * dsub:(j + 1) * dsub], cb[j])[0]
+    return codes
+
+
+def pq_distortion(rows32, codebook) -> float:
+    """The mean squared L2 error of ``pq_decode(pq_encode(rows))`` per row, in fp64."""
+    cb = np.asarray(codebook, np.float32)
+    x = np.ascontiguousarray(rows32, np.float32)
+    m, _, dsub = cb.shape
+    return float(sum(_pq_nearest(x[:, j * dsub:(j + 1) * dsub], cb[j])[1].sum() for j in range(m)) / x.shape[0])
+
+
+def pq_decode(codes, codebook) -> np.ndarray:
+    """Codes uint8 [N, M] -> the reconstructed rows, fp32 [N, D]: sub-space m of row r is ``codebook[m][codes[r][m]]``."""
+    cb = np.asarray(codebook, np.float32)
+    codes = np.asarray(codes, np.uint8)
+    m = cb.shape[0]
+    return cb[np.arange(m)[None, :], codes].reshape(codes.shape[0], -1)
+
+
+def pq_lut_ref(q, codebook) -> np.ndarray:
+    """The table of the queries ``q`` (fp32 [Q, D]) in fp64 [Q, M, 256]: entry (q, m, c) is the inner product of the
+    query's sub-space m with ``codebook[m][c]``."""
+    cb = np.asarray(codebook, np.float64)
+    q = np.asarray(q, np.float64)
+    if q.ndim == 1:
+        q = q[None]
+    m, _, dsub = cb.shape
+    return np.einsum("qmj,mcj->qmc", q.reshape(q.shape[0], m, dsub), cb)
+
+
+def pq_scores_from_lut(lut32, codes) -> np.ndarray:
+    """The scan's arithmetic given a table: fp32 ``lut32`` [Q, M, 256] (or [M, 256]) and codes uint8 [N, M] -> fp32
+    scores [Q, N] (or [N]), each the sequential fp32 sum over m = 0 .. M-1 from +0 of ``lut32[q][m][codes[r][m]]`` --
+    plain additions, the bits of HZ_K_SEARCH_PQSCAN for that table."""
+    lut = np.asarray(lut32, np.float32)
+    codes = np.asarray(codes, np.uint8)
+    one = lut.ndim == 2
+    if one:
+        lut = lut[None]
+    acc = np.zeros((lut.shape[0], codes.shape[0]), np.float32)
+    for j in range(lut.shape[1]):
+        acc = acc + lut[:, j, :][:, codes[:, j]]  # float32 + float32: one rounding per addition
+    return acc[0] if one else acc
+
+
+def pq_search_ref(codes, codebook, q, k: int, allow=None):
+    """The oracle of a pq8 index's first stage: the exact inner product of each query with each reconstructed row
+    (the fp64 table, summed in fp64) -> (scores float64 [Q, k], ids int32 [Q, k]) under the order rule. ``allow`` as in
+    :func:`search_ref`."""
+    codes = np.asarray(codes, np.uint8)
+    lut = pq_lut_ref(q, codebook)
+    n, m = codes.shape
+    if allow is not None:
+        allow = np.asarray(allow, bool)
+        if allow.shape not in ((n,), (lut.shape[0], n)):
+            raise ValueError(f"allow must be bool [{n}] or [{lut.shape[0]}, {n}], got {list(allow.shape)}")
+    scores = np.full((lut.shape[0], k), -np.inf)
+    ids = np.full((lut.shape[0], k), -1, np.int32)
+    col = np.arange(m)[None, :]
+    for i in range(lut.shape[0]):
+        s = lut[i][col, codes].sum(axis=1) + 0.0 if n else np.zeros(0)
+        if allow is None:
+            order = np.argsort(-s, kind="stable")[:k]
+        else:
+            rows = np.flatnonzero(allow if allow.ndim == 1 else allow[i])
+            order = rows[np.argsort(-s[rows], kind="stable")[:k]]
+        scores[i, :order.size] = s[order]
+        ids[i, :order.size] = order
+    return scores, ids
+
+
+def prepare_rows_pq(vectors, metric: str, m: int, codebook=None, *, seed: int = 0, iters: int = 10,
+                    sample: int = PQ_SAMPLE):
+    """fp32 [N, D] -> (codes uint8 [N, m], codebook fp32 [m, 256, D / m]), what a pq8 index of ``metric`` stores: the
+    checks and the cosine normalisation of :func:`prepare_rows`, the rounding to bf16, then :func:`pq_train` over the
+    rounded rows (unless ``codebook`` is given) and :func:`pq_encode` against it. Rounding first means that
+    ``convert_index`` from a bf16 index and ``write_index`` from the same vectors see the same rows: with the same
+    codebook they store the same bytes."""
+    check_pq_shape(np.asarray(vectors).shape[1] if np.asarray(vectors).ndim == 2 else 0, m)
+    bits = to_bf16(_checked_rows(vectors, metric, int(m), f"dim of a pq index with m = {m}"))
+    rows = bf16_to_f32(bits)
+    if not np.isfinite(rows).all():
+        raise ValueError("a value overflows bf16")
+    cb = pq_train(rows, m, seed=seed, iters=iters, sample=sample) if codebook is None \
+        else check_codebook(codebook, rows.shape[1], m)
+    return pq_encode(rows, cb), cb
+
+
 def check_tags(tags, n: int) -> np.ndarray:
     """``tags`` as uint32 [n]; integers in 0..2^32-1 only."""
     t = np.asarray(tags)
@@ -254,22 +444,30 @@ def unpack_live(words, n: int) -> np.ndarray:
 
 
 def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None, scales=None,
-                rescore=None, ivf=None) -> dict:
+                rescore=None, ivf=None, pq=None) -> dict:
     """The file of ``hdr`` and ``rows``: version 1 without ``tags`` / ``live``, else version 2 (zero tags / all
     live where one is missing); with ``scales`` (fp8 rows) version 3, whose tags and bitmap are present under
     the same rule; with ``rescore`` as well (bf16 bit patterns [N, D]) version 4, their block last. With ``ivf``
     (:func:`ivf_layout`'s tables; ``rows``, ``tags`` and ``live`` in stored order, ``hdr["count"]`` the number of
     vectors) version 5, the four tables last; with ``ivf`` and ``scales`` (codes and scales in stored order) version
     6, and with ``rescore`` as well (``[hdr["count"], D]``, in id order) version 7, their block after the tables.
+    With ``pq`` (the codebook fp32 [M, 256, dim / M]; ``rows`` uint8 codes [N, M]) version 10, with ``rescore`` as
+    well version 11: the codebook's block follows the rows, where version 3 has its scales.
     Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
     binary = hdr.get("dtype") == BIN  # sign-bit rows: uint32 [N, dim / 32], versions 8 and 9
+    if (hdr.get("dtype") == PQ) != (pq is not None):
+        raise ValueError("a pq8 index goes with a codebook, and only a pq8 index does")
+    if pq is not None:
+        pq = check_codebook(pq, hdr["dim"], rows.shape[1] if rows.ndim == 2 else 0)
+        if ivf is not None or scales is not None or rows.dtype != np.uint8:
+            raise ValueError("a pq8 index holds uint8 rows of m codes, without scales or lists")
     if binary and (ivf is not None or scales is not None or rows.dtype != np.uint32 or rows.shape[1] * 32 != hdr["dim"]):
         raise ValueError("a binary index holds uint32 rows of dim / 32 words, without scales or lists")
     rshape = rows.shape if ivf is None else (hdr["count"], rows.shape[1])
-    if binary:
+    if binary or pq is not None:
         rshape = (n, hdr["dim"])
-    if rescore is not None and ((scales is None and not binary) or rescore.shape != rshape or rescore.dtype != np.uint16):
+    if rescore is not None and ((scales is None and not binary and pq is None) or rescore.shape != rshape or rescore.dtype != np.uint16):
         raise ValueError("rescore rows go with fp8 rows of the same shape")
 
     def align(x):
@@ -278,7 +476,7 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         raise ValueError("an IVF index holds rows, tags and a live bitmap for whole tiles")
     blocks = tags is not None or live is not None
     tables = ()  # the four blocks of an IVF index
-    if not blocks and scales is None and not binary:
+    if not blocks and scales is None and not binary and pq is None:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
@@ -286,6 +484,9 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             version = VERSION5 if scales is None else VERSION6 if rescore is None else VERSION7
         elif binary:
             version = VERSION8 if rescore is None else VERSION9
+        elif pq is not None:
+            version = VERSION10 if rescore is None else VERSION11
+            hdr = dict(hdr, pq={"m": int(pq.shape[0]), "ksub": PQ_KSUB, "dsub": int(pq.shape[2]), "codebook_off": 0})
         else:
             version = VERSION2 if scales is None else VERSION3 if rescore is None else VERSION4
         if scales is not None:
@@ -309,6 +510,9 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             if scales is not None:
                 offs["scales_off"] = align(end)
                 end = offs["scales_off"] + 4 * n
+            if pq is not None:
+                cb_off = align(end)
+                end = cb_off + pq.nbytes
             if blocks:
                 offs["tags_off"] = tags_off = align(end)
                 offs["live_off"] = live_off = align(tags_off + 4 * n)
@@ -321,15 +525,18 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
                 end = ioffs[key] + block.nbytes
             if rescore is not None and ivf is not None:  # version 7: the rescore rows are the last block
                 offs["rescore_off"] = align(end)
-            if all(hdr[k] == v for k, v in offs.items()) and all(hdr["ivf"][k] == v for k, v in ioffs.items()):
+            if all(hdr[k] == v for k, v in offs.items()) and all(hdr["ivf"][k] == v for k, v in ioffs.items()) \
+                    and (pq is None or hdr["pq"]["codebook_off"] == cb_off):
                 break
             hdr.update(offs)
+            if pq is not None:
+                hdr["pq"] = dict(hdr["pq"], codebook_off=cb_off)
             if ioffs:
                 hdr["ivf"].update(ioffs)
     tmp = path + ".tmp"
     with open(tmp, "wb") as f:
         f.write(HEAD.pack(MAGIC, version, len(js), data_off, n if ivf is None else hdr["count"],
-                          hdr["dim"] if binary else rows.shape[1], METRICS.index(hdr["metric"])))
+                          hdr["dim"] if binary or pq is not None else rows.shape[1], METRICS.index(hdr["metric"])))
         f.write(js)
         f.write(bytes(data_off - HEAD.size - len(js)))
         f.write(rows.astype("<u4").tobytes() if binary else rows.tobytes())
@@ -338,6 +545,10 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             f.write(bytes(hdr["scales_off"] - at))
             f.write(np.asarray(scales).astype("<f4").tobytes())
             at = hdr["scales_off"] + 4 * n
+        if pq is not None:
+            f.write(bytes(cb_off - at))
+            f.write(pq.astype("<f4").tobytes())
+            at = cb_off + pq.nbytes
         if blocks:
             f.write(bytes(tags_off - at))
             f.write(tags.astype("<u4").tobytes())
@@ -424,7 +635,8 @@ def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
 
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
-                ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0) -> dict:
+                ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
+                pq_seed: int = 0, pq_iters: int = 10) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -435,18 +647,29 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     ``nprobe``: the lists a search scans by default, ``min(nlist, 16)`` when None. Ids stay the positions in
     ``vectors``. ``ivf_backend="gpu"``: the lists come from :meth:`Index.cluster` on ``device`` (:func:`cluster_rows`)
     in place of :func:`ivf_kmeans`; the file has the same layout either way. ``dtype="bin"``: sign-bit rows
-    (:func:`prepare_rows_bin`), a version-8 file, with ``rescore=True`` version 9."""
+    (:func:`prepare_rows_bin`), a version-8 file, with ``rescore=True`` version 9. ``dtype="pq"``: rows of ``pq_m``
+    code bytes and their codebook (:func:`prepare_rows_pq`: trained with ``pq_seed`` / ``pq_iters`` unless
+    ``pq_codebook`` is given), a version-10 file, with ``rescore=True`` version 11."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
+    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10):
+        raise ValueError(f"pq_m, pq_codebook, pq_seed and pq_iters go with dtype='pq', got dtype={dtype!r}")
+    if ivf is not None and dtype == "pq":
+        raise ValueError(f"ivf={ivf!r} with dtype='pq': IVF lists over pq8 rows are not built")
     if ivf is not None and dtype == "bin":
         raise ValueError(f"ivf={ivf!r} with dtype='bin': IVF lists over binary rows are not built")
     if ivf is not None and (dtype != "bf16" or rescore):
         raise ValueError(f"ivf={ivf!r} goes with dtype='bf16' without rescore rows, got dtype={dtype!r}, rescore={rescore!r}: "
                          f"an fp8 or two-stage IVF index is convert_index(bf16 IVF file, dst, 'fp8', rescore=...)")
-    if rescore and dtype not in ("fp8", "bin"):
+    if rescore and dtype not in ("fp8", "bin", "pq"):
         raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
-    if dtype == "bin":
+    codebook = None
+    if dtype == "pq":
+        if pq_m is None:
+            raise ValueError("dtype='pq' needs pq_m, the code bytes per row (a multiple of 16 in 16..96 that divides dim)")
+        (rows, codebook), scales = prepare_rows_pq(vectors, metric, pq_m, pq_codebook, seed=pq_seed, iters=pq_iters), None
+    elif dtype == "bin":
         rows, scales = prepare_rows_bin(vectors, metric), None
     else:
         rows, scales = (prepare_rows(vectors, metric), None) if dtype == "bf16" else prepare_rows_fp8(vectors, metric)
@@ -454,6 +677,8 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     n, d = rows.shape
     if dtype == "bin":
         d *= 32
+    if dtype == "pq":
+        d = int(np.asarray(vectors).shape[1])
     if labels is not None:
         labels = [str(s) for s in labels]
         if len(labels) != n:
@@ -476,7 +701,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
             stags[real] = tags[lay["rowid"][real]]
         lay.update(centroids=cbits, nlist=nlist, nprobe=int(nprobe), seed=int(ivf_seed), iters=int(ivf_iters))
         return _write_file(path, hdr, srows, stags, real, ivf=lay)
-    return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows)
+    return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows, pq=codebook)
 
 
 IVF_BACKENDS = ("cpu", "gpu")
@@ -542,7 +767,8 @@ def read_header(path: str) -> dict:
         if len(raw) < HEAD.size or raw[:8] != MAGIC:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
-        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7, VERSION8, VERSION9):
+        if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7, VERSION8, VERSION9,
+                           VERSION10, VERSION11):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
@@ -557,11 +783,31 @@ def read_header(path: str) -> dict:
     if (hdr["dtype"] == BIN) != binary:
         raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (versions 8 and 9 mean bin_sign rows, and no "
                          f"other version does)")
+    pq = version in PQ_VERSIONS
+    if (hdr["dtype"] == PQ) != pq:
+        raise ValueError(f"{path}: dtype {hdr['dtype']} in a version-{version} file (versions 10 and 11 mean pq8 rows, and no "
+                         f"other version does)")
+    if pq:
+        blk = hdr.get("pq")
+        if not isinstance(blk, dict) or not all(_is_int(blk.get(k)) for k in ("m", "ksub", "dsub", "codebook_off")):
+            raise ValueError(f"{path}: a version-{version} file without a pq block of integers m, ksub, dsub, codebook_off")
+        if blk["ksub"] != PQ_KSUB:
+            raise ValueError(f"{path}: pq ksub must be {PQ_KSUB}, got {blk['ksub']}")
+        try:
+            dsub = check_pq_shape(dim, blk["m"])
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+        if blk["dsub"] != dsub:
+            raise ValueError(f"{path}: pq dsub {blk['dsub']} is not dim / m = {dsub}")
+        if "ivf" in hdr:
+            raise ValueError(f"{path}: an ivf block in a version-{version} file: IVF lists over pq8 rows are not built")
+    elif "pq" in hdr:
+        raise ValueError(f"{path}: a pq block belongs to the files of versions 10 and 11 and to no other (version {version})")
     if version in RESCORE_VERSIONS and (hdr.get("rescore") != "bf16" or "rescore_off" not in hdr):
         raise ValueError(f"{path}: a version-{version} file without rescore / rescore_off")
     if version not in RESCORE_VERSIONS and ("rescore" in hdr or "rescore_off" in hdr):
         raise ValueError(f"{path}: rescore keys in a version-{version} file (they belong to versions "
-                         f"{'4, 7 and 9' if binary else '4 and 7'})")
+                         f"{'4, 7, 9 and 11' if pq else '4, 7 and 9' if binary else '4 and 7'})")
     if binary and (dim < 128 or dim % 128 or dim > 2048):
         raise ValueError(f"{path}: dim of a binary index must be a multiple of 128 in 128..2048, got {dim}")
     if fp8 and (dim < 16 or dim % 16 or dim > 2048):
@@ -588,6 +834,17 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path}: the row block at {data_off} is unaligned, overlaps the header or lies outside the file")
         if ("tags_off" in hdr) != ("live_off" in hdr):
             raise ValueError(f"{path}: a version-{version} file with only one of tags_off / live_off")
+    if pq:
+        end = data_off + stored * hdr["pq"]["m"]
+        if data_off % ALIGN or data_off < HEAD.size + json_len or end > size:
+            raise ValueError(f"{path}: the row block at {data_off} is unaligned, overlaps the header or lies outside the file")
+        off, nbytes = hdr["pq"]["codebook_off"], 4 * PQ_KSUB * dim
+        if off % ALIGN or off < end or off + nbytes > size:
+            raise ValueError(f"{path}: the codebook block at {off} is unaligned, overlaps the rows (which end at {end}) or lies "
+                             f"outside the file")
+        end = off + nbytes
+        if ("tags_off" in hdr) != ("live_off" in hdr):
+            raise ValueError(f"{path}: a version-{version} file with only one of tags_off / live_off")
     if fp8:
         off = hdr.get("scales_off")
         if not isinstance(off, int) or off % ALIGN:
@@ -600,7 +857,7 @@ def read_header(path: str) -> dict:
         if ("tags_off" in hdr) != ("live_off" in hdr):
             raise ValueError(f"{path}: a version-{version} file with only one of tags_off / live_off")
     last = end  # the end of the last block before a rescore block
-    if version == VERSION2 or is_ivf or ((fp8 or binary) and "tags_off" in hdr):
+    if version == VERSION2 or is_ivf or ((fp8 or binary or pq) and "tags_off" in hdr):
         for key, nbytes in (("tags_off", 4 * stored), ("live_off", 4 * (-(-stored // 32)))):
             off = hdr.get(key)
             if not isinstance(off, int) or off % ALIGN or off < end or off + nbytes > size:
@@ -666,13 +923,19 @@ def file_info(path: str) -> dict:
         info.update(version=VERSION7 if "rescore_off" in hdr else VERSION6)
     if hdr["dtype"] == BIN:
         info.update(version=VERSION9 if "rescore_off" in hdr else VERSION8, dtype=BIN)
+    if hdr["dtype"] == PQ:
+        info.update(version=VERSION11 if "rescore_off" in hdr else VERSION10, dtype=PQ,
+                    pq={"m": hdr["pq"]["m"], "dsub": hdr["pq"]["dsub"], "codebook_bytes": 4 * PQ_KSUB * hdr["dim"]})
     return info
 
 
 def read_rows(path: str) -> np.ndarray:
     """The row block: bf16 bit patterns, uint16 [count, dim]; e4m3fn codes, uint8, for an fp8 index; sign-bit
-    words, uint32 [count, dim / 32], for a binary index."""
+    words, uint32 [count, dim / 32], for a binary index; codes, uint8 [count, M], for a pq8 index."""
     hdr = read_header(path)
+    if hdr["dtype"] == PQ:
+        m = hdr["pq"]["m"]
+        return np.fromfile(path, np.uint8, hdr["count"] * m, offset=hdr["data_off"]).reshape(hdr["count"], m)
     if hdr["dtype"] == BIN:
         w = hdr["dim"] // 32
         return np.fromfile(path, "<u4", hdr["count"] * w, offset=hdr["data_off"]).astype(np.uint32).reshape(hdr["count"], w)
@@ -737,6 +1000,16 @@ def read_scales(path: str) -> np.ndarray:
     if hdr["dtype"] != FP8:
         raise ValueError(f"{path}: a {hdr['dtype']} index has no scales")
     return np.fromfile(path, "<f4", stored_rows(hdr), offset=hdr["scales_off"]).astype(np.float32)
+
+
+def read_codebook(path: str) -> np.ndarray:
+    """The codebook of a pq8 index, float32 [M, 256, dim / M]."""
+    hdr = read_header(path)
+    if hdr["dtype"] != PQ:
+        raise ValueError(f"{path}: a {hdr['dtype']} index has no codebook")
+    blk = hdr["pq"]
+    return np.fromfile(path, "<f4", PQ_KSUB * hdr["dim"], offset=blk["codebook_off"]).astype(np.float32) \
+        .reshape(blk["m"], PQ_KSUB, blk["dsub"])
 
 
 def read_rescore_rows(path: str) -> np.ndarray:
@@ -920,6 +1193,16 @@ class _BRows:
         self.rescore = None if rescore is None else np.ascontiguousarray(rescore, np.uint16)
 
 
+class _PRows:
+    """What ``add`` hands a backend's ``_append`` on a pq8 index: the codes (encoded against the index's codebook); on
+    an index with rescore rows also ``rescore``, the bf16 bit patterns of the same input. ``shape`` is [n, dim]."""
+
+    def __init__(self, codes, dim: int, rescore=None):
+        self.codes = np.ascontiguousarray(codes, np.uint8)
+        self.shape = (self.codes.shape[0], dim)
+        self.rescore = None if rescore is None else np.ascontiguousarray(rescore, np.uint16)
+
+
 class _Base:
     """What both backends share: the header, the argument checks of the mutators and ``save``. A backend
     provides ``_append(bits, tags, publish)`` (which calls ``publish(first id)`` before searches may run again), ``_kill(ids) -> int``, ``_retag(ids, tags)`` and ``_state() -> (bits,
@@ -934,8 +1217,11 @@ class _Base:
         self.dtype = self.header["dtype"]
         self.rescore = "rescore_off" in self.header  # a version-4 file: bf16 rows for a second stage
         self.ivf = read_ivf(path) if "ivf" in self.header else None  # the validated tables of a version-5 file
+        self.codebook = read_codebook(path) if self.dtype == PQ else None  # what add encodes against
         if self.dtype == BIN:
             self.version = VERSION9 if self.rescore else VERSION8
+        elif self.dtype == PQ:
+            self.version = VERSION11 if self.rescore else VERSION10
         elif self.ivf:
             self.version = VERSION5 if self.dtype != FP8 else VERSION7 if self.rescore else VERSION6
         else:
@@ -996,8 +1282,8 @@ class _Base:
         return 0 if nprobe >= nlist else int(nprobe)
 
     def _bin_name(self) -> str:
-        """"a bin_sign index of " on a binary index (the by-name refusals), else nothing."""
-        return f"a {BIN} index of " if self.dtype == BIN else ""
+        """"a bin_sign index of " on a binary index, "a pq8 index of " on a pq8 one (the by-name refusals), else nothing."""
+        return f"a {self.dtype} index of " if self.dtype in (BIN, PQ) else ""
 
     def _check_probes(self, q, nprobe):
         if self.ivf is None:
@@ -1009,9 +1295,9 @@ class _Base:
 
     def _check_neighbors(self, ids, k):
         """The refusals of :meth:`neighbors` that both backends share -> (ids int32 [n], k)."""
-        if self.dtype in (FP8, BIN) or self.ivf is not None:
+        if self.dtype in (FP8, BIN, PQ) or self.ivf is not None:
             what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
-                f"a {BIN} index" if self.dtype == BIN else f"an {FP8} index"
+                f"a {self.dtype} index" if self.dtype in (BIN, PQ) else f"an {FP8} index"
             raise ValueError(f"neighbors is built for plain bf16 indexes (versions 1 and 2): this one is {what} of version "
                              f"{self.version}")
         if self.dim % 32:
@@ -1020,9 +1306,9 @@ class _Base:
 
     def _check_batch(self, k, candidates):
         """The refusals of :meth:`search_batch` that both backends share -> (k, R)."""
-        if self.dtype in (FP8, BIN) or self.ivf is not None:
+        if self.dtype in (FP8, BIN, PQ) or self.ivf is not None:
             what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
-                f"a {BIN} index" if self.dtype == BIN else f"an {FP8} index"
+                f"a {self.dtype} index" if self.dtype in (BIN, PQ) else f"an {FP8} index"
             raise ValueError(f"search_batch is built for plain bf16 indexes (versions 1 and 2): this one is {what} of "
                              f"version {self.version}")
         if self.dim % 32:
@@ -1032,9 +1318,9 @@ class _Base:
 
     def _check_cluster_index(self):
         """:meth:`cluster` is built for plain bf16 indexes with ``dim % 32 == 0``."""
-        if self.dtype in (FP8, BIN) or self.ivf is not None:
+        if self.dtype in (FP8, BIN, PQ) or self.ivf is not None:
             what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
-                f"a {BIN} index" if self.dtype == BIN else f"an {FP8} index"
+                f"a {self.dtype} index" if self.dtype in (BIN, PQ) else f"an {FP8} index"
             raise ValueError(f"cluster is built for plain bf16 indexes (versions 1 and 2): this one is {what} of version "
                              f"{self.version}")
         if self.dim % 32:
@@ -1114,6 +1400,11 @@ class _Base:
         elif self.dtype == BIN:  # binarised here, on the host: the same words write_index stores
             bits = _BRows(prepare_rows_bin(vectors, self.metric), np.asarray(vectors).shape[1],
                           rescore=prepare_rows(vectors, self.metric) if self.rescore else None)
+        elif self.dtype == PQ:  # encoded here, on the host, against the file's codebook: the bytes write_index stores
+            rbits = prepare_rows(vectors, self.metric)
+            if rbits.shape[1] != self.dim:
+                raise ValueError(f"vectors must be [N, {self.dim}], got {list(rbits.shape)}")
+            bits = _PRows(pq_encode(bf16_to_f32(rbits), self.codebook), self.dim, rescore=rbits if self.rescore else None)
         else:
             bits = prepare_rows(vectors, self.metric)
         n = bits.shape[0]
@@ -1182,7 +1473,7 @@ class _Base:
                 hdr["labels"] = list(labels)
             plain = bool(live.all()) and not tags.any()
             return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), None if plain else tags,
-                               None if plain else live, self.capacity(), scales=scales, rescore=rrows)
+                               None if plain else live, self.capacity(), scales=scales, rescore=rrows, pq=self.codebook)
 
 
 class RefIndex(_Base):
@@ -1194,7 +1485,7 @@ class RefIndex(_Base):
         super().__init__(path)
         self._bits = read_rows(path)
         fp8 = self.dtype == FP8
-        self._rows = None if self.dtype == BIN else e4m3_to_f32(self._bits) if fp8 else bf16_to_f32(self._bits)
+        self._rows = None if self.dtype in (BIN, PQ) else e4m3_to_f32(self._bits) if fp8 else bf16_to_f32(self._bits)
         self.scales = read_scales(path) if fp8 else None
         self._rbits = read_rescore_rows(path) if self.rescore else None
         self._rrows = bf16_to_f32(self._rbits) if self.rescore else None
@@ -1234,6 +1525,8 @@ class RefIndex(_Base):
                 allow = near if allow is None else near & allow
             if self.dtype == BIN:  # stage one: exact integer scores over the sign bits, ties by the lower id
                 s, i = bin_search_ref(self._bits, binarize(q), self.dim, R or k, allow)
+            elif self.dtype == PQ:  # stage one: the fp64 table, the exact inner product with the reconstructed rows
+                s, i = pq_search_ref(self._bits, self.codebook, q, R or k, allow)
             else:
                 s, i = search_ref(self._rows, q, R or k, allow, scales=self.scales)
             if R:
@@ -1319,11 +1612,11 @@ class RefIndex(_Base):
 
     def _append(self, bits, tags, publish):
         first = self.count
-        if self.dtype == BIN:
+        if self.dtype in (BIN, PQ):
             if self.rescore:
                 self._rbits = np.concatenate([self._rbits, bits.rescore])
                 self._rrows = np.concatenate([self._rrows, bf16_to_f32(bits.rescore)])
-            self._bits = np.concatenate([self._bits, bits.words])
+            self._bits = np.concatenate([self._bits, bits.words if self.dtype == BIN else bits.codes])
             self._tags = np.concatenate([self._tags, tags])
             self._live = np.concatenate([self._live, np.ones(bits.shape[0], bool)])
             while self._cap < self._bits.shape[0]:
@@ -1378,11 +1671,13 @@ class RefIndex(_Base):
         return {"path": self.path, "backend": "cpu", **{k: v for k, v in self.header.items() if k != "labels"},
                 "labels": self.labels is not None, "capacity": self._cap, "live": int(self._live.sum()),
                 "tags": bool(self._tags.any()) or "tags_off" in self.header,
+                **({"m": int(self.codebook.shape[0]), "dsub": int(self.codebook.shape[2]),
+                    "codebook_bytes": int(self.codebook.nbytes)} if self.dtype == PQ else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
         self._rows = None
-        if self.dtype == BIN:
+        if self.dtype in (BIN, PQ):
             self._bits = None
 
 
@@ -1605,12 +1900,18 @@ class Index(_Base):
 
     def _append(self, bits, tags, publish):
         first = C.c_longlong(-1)
-        fp8, binary = self.dtype == FP8, self.dtype == BIN
-        if not fp8 and not binary:
+        fp8, binary, pq = self.dtype == FP8, self.dtype == BIN, self.dtype == PQ
+        if not fp8 and not binary and not pq:
             bits = np.ascontiguousarray(bits)
 
         def call():
-            if binary and self.rescore:
+            if pq and self.rescore:
+                rc = self._lib.hz_index_add_pr(self._h, bits.codes.ctypes.data, bits.rescore.ctypes.data, bits.shape[0],
+                                               tags.ctypes.data, C.byref(first))
+            elif pq:
+                rc = self._lib.hz_index_add_p(self._h, bits.codes.ctypes.data, bits.shape[0], tags.ctypes.data,
+                                              C.byref(first))
+            elif binary and self.rescore:
                 rc = self._lib.hz_index_add_br(self._h, bits.words.ctypes.data, bits.rescore.ctypes.data, bits.shape[0],
                                                tags.ctypes.data, C.byref(first))
             elif binary:
@@ -1643,10 +1944,15 @@ class Index(_Base):
     def _state(self):
         n = self.count if self.ivf is None else int(self.header["capacity"])  # an IVF index: the stored rows
         tags, words = np.empty(n, np.uint32), np.empty(-(-n // 32), np.uint32)
-        if self.dtype == BIN:
-            rows = np.empty((n, self.dim // 32), np.uint32)
-            self._exclusive(lambda: self._lib.hz_index_read_state_b(self._h, rows.ctypes.data, tags.ctypes.data,
-                                                                    words.ctypes.data, n), "hz_index_read_state_b")
+        if self.dtype in (BIN, PQ):
+            if self.dtype == PQ:
+                rows = np.empty((n, self.header["pq"]["m"]), np.uint8)
+                self._exclusive(lambda: self._lib.hz_index_read_state_p(self._h, rows.ctypes.data, tags.ctypes.data,
+                                                                        words.ctypes.data, n), "hz_index_read_state_p")
+            else:
+                rows = np.empty((n, self.dim // 32), np.uint32)
+                self._exclusive(lambda: self._lib.hz_index_read_state_b(self._h, rows.ctypes.data, tags.ctypes.data,
+                                                                        words.ctypes.data, n), "hz_index_read_state_b")
             if self.rescore:
                 rrows = np.empty((n, self.dim), np.uint16)
                 self._exclusive(lambda: self._lib.hz_index_read_rescore(self._h, rrows.ctypes.data, n),
@@ -1674,14 +1980,18 @@ class Index(_Base):
         return self.describe()["capacity"]
 
     def describe(self) -> dict:
-        out, more = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+        out, more, pq = (C.c_uint64 * 8)(), (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
         self._lib.hz_index_describe(self._h, out)
         self._lib.hz_index_describe2(self._h, more)
+        if self.dtype == PQ:
+            self._lib.hz_index_describe4(self._h, pq)
         return {"path": self.path, "backend": "gpu", "device": self.device,
                 **{k: v for k, v in self.header.items() if k != "labels"}, "labels": self.labels is not None,
                 "contexts": int(out[3]), "tile_rows": int(out[4]), "programs": int(out[5]), "device_bytes": int(out[6]),
                 "capacity": int(more[0]), "live": int(more[1]), "tags": bool(more[2]), "filtered": bool(more[3]),
                 **({"rescore_rows": "host" if more[7] else "device"} if more[6] else {}),
+                **({"m": int(pq[0]), "dsub": int(pq[1]), "codebook_bytes": int(pq[2]), "scan_span": int(pq[4])}
+                   if self.dtype == PQ else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
@@ -1705,7 +2015,8 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 
 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
-                  ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0) -> dict:
+                  ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None,
+                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10) -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -1715,15 +2026,29 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     gathered into id order. ``ivf=nlist`` (a plain ``src``, version 1 or 2) builds the lists over the stored rows
     with :func:`ivf_kmeans` / :func:`ivf_layout` (``nprobe``, ``ivf_seed``, ``ivf_iters`` as in
     :func:`write_index`): version 5 for ``dtype="bf16"``, 6 or 7 for fp8. A deleted row keeps its id, is assigned to
-    a list and stays dead. ``ivf_backend="gpu"``: the lists come from :func:`cluster_rows` on ``device``."""
+    a list and stays dead. ``ivf_backend="gpu"``: the lists come from :func:`cluster_rows` on ``device``.
+    ``dtype="pq"`` (a plain ``src``, ``pq_m`` code bytes per row): the stored rows are trained on (:func:`pq_train` with
+    ``pq_seed`` / ``pq_iters``, unless ``pq_codebook`` is given) and encoded as they stand, which gives the bytes
+    ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
-    if rescore and dtype not in ("fp8", "bin"):
+    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10):
+        raise ValueError(f"pq_m, pq_codebook, pq_seed and pq_iters go with dtype='pq', got dtype={dtype!r}")
+    if dtype == "pq" and ivf is not None:
+        raise ValueError(f"ivf={ivf!r} with dtype='pq': IVF lists over pq8 rows are not built")
+    if dtype == "pq" and pq_m is None:
+        raise ValueError("dtype='pq' needs pq_m, the code bytes per row (a multiple of 16 in 16..96 that divides dim)")
+    if rescore and dtype not in ("fp8", "bin", "pq"):
         raise ValueError(f"rescore rows go with an fp8 index: a {dtype} index already holds its rows in bf16")
     if dtype == "bin" and ivf is not None:
         raise ValueError(f"ivf={ivf!r} with dtype='bin': IVF lists over binary rows are not built")
     hdr = read_header(src)
+    if dtype == "pq":
+        if hdr["dtype"] != "bf16" or "ivf" in hdr:
+            raise ValueError(f"dtype='pq': {src} holds {hdr['dtype']} rows{' in IVF lists' if 'ivf' in hdr else ''}, and a pq8 "
+                             f"index is converted from a plain bf16 index")
+        check_pq_shape(hdr["dim"], pq_m)
     if dtype == "bin" and hdr["dtype"] != "bf16":
         raise ValueError(f"dtype='bin': {src} holds {hdr['dtype']} rows, and a binary index is converted from a plain bf16 "
                          f"index (its sign bits are the vectors' own)")
@@ -1779,5 +2104,11 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
         bits, scales = quantize_rows(bf16_to_f32(bits))
     if dtype == "bin":  # the sign bits of the stored rows: what binarising the fp32 vectors gives
         bits = binarize_bf16(bits)
+    codebook = None
+    if dtype == "pq":  # trained on and encoded from the stored rows as they stand (prepare_rows_pq rounds to bf16 first)
+        rows32 = bf16_to_f32(bits)
+        codebook = pq_train(rows32, pq_m, seed=pq_seed, iters=pq_iters) if pq_codebook is None \
+            else check_codebook(pq_codebook, hdr["dim"], pq_m)
+        bits = pq_encode(rows32, codebook)
     return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
-                       hdr.get("capacity"), scales=scales, rescore=rrows)
+                       hdr.get("capacity"), scales=scales, rescore=rrows, pq=codebook)
