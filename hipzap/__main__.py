@@ -15,6 +15,7 @@
     python -m hipzap index --vectors v.npy --dtype fp8 --rescore --out c.hzidx  # fp8 scan + bf16 rescoring (version 4)
     python -m hipzap index --vectors v.npy --dtype bin --rescore --out d.hzidx  # sign-bit scan + bf16 rescoring (version 9)
     python -m hipzap index --vectors v.npy --dtype pq --pq-m 96 --rescore --out e.hzidx  # product quantisation (version 11)
+    python -m hipzap index --vectors v.npy --dtype pq --pq-m 96 --pq-backend gpu --out f.hzidx  # trained and encoded on the GPU
     python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
@@ -125,8 +126,10 @@ def cmd_index(a):
         raise SystemExit("index: --dtype pq needs --pq-m M, the code bytes per row (a multiple of 16 in 16..96 that divides dim)")
     if a.dtype != "pq" and (a.pq_m is not None or a.pq_iters is not None or a.pq_seed is not None):
         raise SystemExit("index: --pq-m, --pq-iters and --pq-seed go with --dtype pq")
+    if a.dtype != "pq" and a.pq_backend is not None:
+        raise SystemExit("index: --pq-backend goes with --dtype pq")
     pq = {} if a.dtype != "pq" else {"pq_m": a.pq_m, "pq_iters": 10 if a.pq_iters is None else a.pq_iters,
-                                     "pq_seed": a.pq_seed or 0}
+                                     "pq_seed": a.pq_seed or 0, "pq_backend": a.pq_backend or "cpu"}
     if a.rescore and a.dtype not in ("fp8", "bin", "pq"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
@@ -337,6 +340,10 @@ def main(argv=None):
                     help="with --dtype pq: code bytes per row (a multiple of 16 in 16..96 that divides dim; dim / M <= 64)")
     ix.add_argument("--pq-iters", type=int, default=None, help="with --dtype pq: Lloyd iterations of the codebook training (10)")
     ix.add_argument("--pq-seed", type=int, default=None, help="with --dtype pq: the training seed (0)")
+    ix.add_argument("--pq-backend", choices=["cpu", "f32", "gpu"], default=None,
+                    help="with --dtype pq: how training and encoding find the nearest sub-centroids: cpu (fp64 numpy, the "
+                         "default), f32 (the GPU kernel's arithmetic in numpy) or gpu (HZ_K_SEARCH_PQASSIGN on --device; "
+                         "the same bytes as f32)")
     ix.add_argument("--dtype", choices=["bf16", "fp8", "bin", "pq"], default="bf16",
                     help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D %% 16 == 0); "
                          "bin: one sign bit per column (a version-8 file, a sixteenth of the bytes; D %% 128 == 0), "

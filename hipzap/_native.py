@@ -41,7 +41,7 @@ KINDS = {
     "HZ_K_SEARCH_MSCAN": 39, "HZ_K_SEARCH_MERGEN": 40,
     "HZ_K_SEARCH_ASSIGN": 41, "HZ_K_SEARCH_CMEAN": 42, "HZ_K_SEARCH_BSCAN": 43,
     "HZ_K_SEARCH_XSCAN": 44, "HZ_K_SEARCH_RESCOREN": 45, "HZ_K_SEARCH_PQLUT": 46,
-    "HZ_K_SEARCH_PQSCAN": 47,
+    "HZ_K_SEARCH_PQSCAN": 47, "HZ_K_SEARCH_PQASSIGN": 48,
 }
 globals().update(KINDS)
 KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct

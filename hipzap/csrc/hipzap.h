@@ -556,6 +556,37 @@ int hz_search_pqlut_launch(const HzSearchPqLutParams* p, hipStream_t st);
 int hz_search_pqscan_launch(const HzSearchPqParams* p, hipStream_t st);
 // the span a launch with span = 0 takes for (N, Q, M) on the current device; 0 for a refused N, Q or M
 int hz_search_pq_span(long long N, int Q, int M);
+// nearest sub-centroids (HZ_K_SEARCH_PQASSIGN): what training and encoding a product quantiser spend
+// their time in. rows: bf16 [N][ldr]; codebook: fp32 [M][256][dsub], dsub = D / M; codes: uint8 [N][ldc] (ldc in
+// bytes) out; dist: fp32 [N][M] out, may be null.
+// CONTRACT. For row r, sub-space m and centroid c
+//   d(r, m, c) = the fp32 sum over j = 0 .. dsub-1, ascending, from +0, of t_j * t_j,
+//   t_j        = float(rows[r][m*dsub + j]) - codebook[m][c][j],
+// every subtraction, multiplication and addition a SEPARATE fp32 round-to-nearest operation: no FMA (numpy float32
+// reproduces it bit for bit, hipzap.search.pq_assign_f32). codes[r][m] is the c with the smallest d, the lowest c
+// among equal values: a strict d < best walking c upward from best = d(r, m, 0), so a NaN never displaces anything
+// and an all-NaN column gives code 0. dist[r*M + m] holds the winner's d bits. Bytes M .. ldc-1 of a code row are not
+// written; rows from N on are neither read nor written. The bits of a code and of a distance depend on the row's
+// sub-vector and on codebook[m] only: not on N, the row's tile or position, the grid, or how the sub-spaces are
+// grouped into workgroups (the kernel pads dsub to a multiple of 4 with zero columns: t = 0 - 0 = +0 and
+// acc + +0 = acc for every acc the sum can hold, NaN included). Against the exact distance: all terms are
+// non-negative, so |d^ - d| <= gamma(dsub + 2) * d, gamma(n) = n 2^-24 / (1 - n 2^-24), absent underflow.
+// Grid (ceil(N / HZ_SEARCH_TILE), M / 16), HZ_SEARCH_TILE threads; thread t owns row t of the tile, the workgroup
+// stages codebook[m] in LDS (dsub rounded up to a multiple of 4, KiB) for each of its 16 sub-spaces in turn.
+// Refusals (nothing is launched): -129 a null rows, codebook or codes; -130 D % M; -131 M % 16; -132 M outside
+// 16..96; -133 D / M outside 1..64; -134 D > 2048; -135 ldr < D or ldr % 8; -136 ldc < M or ldc % 16; -137 N < 1;
+// -138 rows, codebook, codes or dist not 16-B aligned; -139 dist given with dist_bytes < N * M * 4.
+typedef struct HzSearchPqAssignParams {
+  const unsigned short* rows;     // device bf16 [N][ldr], 16-B aligned
+  const float* codebook;          // device fp32 [M][256][D / M], 16-B aligned
+  unsigned char* codes;           // device uint8 [N][ldc], 16-B aligned
+  float* dist;                    // device fp32 [N][M], 16-B aligned, or null
+  unsigned long long dist_bytes;  // bytes of `dist`, at least N * M * 4 when it is given
+  long long N;
+  int D, M;
+  long long ldr, ldc;             // ldr in elements, ldc in bytes
+} HzSearchPqAssignParams;
+int hz_search_pqassign_launch(const HzSearchPqAssignParams* p, hipStream_t st);
 // rescore (HZ_K_SEARCH_RESCORE): the second stage of a two-stage search. One workgroup per query
 // scores the query against the R bf16 rows that `in_id` names (a merge's out_id of stage one; a slot is real
 // iff (unsigned)id < (unsigned)N, every other value is an empty slot and nothing is loaded for it) and writes
@@ -925,6 +956,15 @@ int hz_index_assign(void* idx, int ctx, const unsigned short* cent_bits, int C, 
                     float* out_score);
 int hz_index_cmean(void* idx, int ctx, const int* order, long long M, const int* seg_off, int C,
                    unsigned short* cent_bits_inout, float* cent32_out);
+// hz_pq_encode: HZ_K_SEARCH_PQASSIGN over n host rows (bf16 [n][dim]) against `codebook` (host fp32
+// [m][256][dim / m]) on `device` -> codes_out uint8 [n][m], dist_out_or_null fp32 [n][m]. Not tied to an open index
+// (a file is usually being built when it runs). A plain batch job on a stream of its own, no captured program: the
+// codebook is uploaded once, the rows go through device buffers `chunk_rows` at a time (0: a default; any other
+// value is honoured, so a chunk edge can sit anywhere) and each chunk's codes (and distances) are copied back.
+// A refused shape returns the launcher's code (-129 .. -137); -140: hipSetDevice, an allocation, a copy or the
+// stream failed, -141: chunk_rows < 0 (hz_index_last_error says which call and why).
+int hz_pq_encode(int device, const unsigned short* rows_bf16, long long n, int dim, int m, const float* codebook,
+                 long long chunk_rows, unsigned char* codes_out, float* dist_out_or_null);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -1118,7 +1158,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_XSCAN, 44, HzSearchBatchParams, hz_search_xscan_op, SEARCH)    \
   X(SEARCH_RESCOREN, 45, HzSearchRescoreParams, hz_search_rescoren_op, SEARCH) \
   X(SEARCH_PQLUT, 46, HzSearchPqLutParams, hz_search_pqlut_op, SEARCH)    \
-  X(SEARCH_PQSCAN, 47, HzSearchPqParams, hz_search_pqscan_op, SEARCH)
+  X(SEARCH_PQSCAN, 47, HzSearchPqParams, hz_search_pqscan_op, SEARCH)  \
+  X(SEARCH_PQASSIGN, 48, HzSearchPqAssignParams, hz_search_pqassign_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

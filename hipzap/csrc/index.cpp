@@ -1585,4 +1585,74 @@ int hz_index_read_rescore(void* h, unsigned short* rows_out, long long n) {
 
 void hz_index_close(void* h) { delete static_cast<Index*>(h); }
 
+// hz_pq_encode (hipzap.h): no index, a stream and four device buffers of its own, all released on
+// every way out. Per chunk: H2D of the rows, HZ_K_SEARCH_PQASSIGN, D2H of the codes (and distances), one synchronise.
+int hz_pq_encode(int device, const unsigned short* rows_bf16, long long n, int dim, int m, const float* codebook,
+                 long long chunk_rows, unsigned char* codes_out, float* dist_out) {
+  if (!rows_bf16 || !codebook || !codes_out) return -129;
+  if (m < 1) return -132;  // before the division
+  if (dim % m) return -130;
+  if (m % 16) return -131;
+  if (m < 16 || m > HZ_SEARCH_PQ_MAX_M) return -132;
+  if (dim / m < 1 || dim / m > HZ_SEARCH_PQ_MAX_DSUB) return -133;
+  if (dim > 2048) return -134;
+  if (n < 1) return -137;
+  if (chunk_rows < 0) {
+    g_err = "pq_encode: chunk_rows must be 0 (the default) or positive, got " + std::to_string(chunk_rows);
+    return -141;
+  }
+  const uint64_t chunk = (uint64_t)std::min<long long>(n, chunk_rows ? chunk_rows : 65536);
+  const uint64_t cb_bytes = (uint64_t)256 * dim * 4;  // [m][256][dim / m] fp32
+  hipStream_t st = nullptr;
+  unsigned short* d_rows = nullptr;
+  float* d_cb = nullptr;
+  unsigned char* d_codes = nullptr;
+  float* d_dist = nullptr;
+  int rc = 0;
+  const auto step = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    g_err = std::string("pq_encode: ") + what + " failed: " + hipGetErrorString(e);
+    rc = -140;
+    return false;
+  };
+  if (step(hipSetDevice(device), "hipSetDevice") && step(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate") &&
+      step(hipMalloc(&d_rows, chunk * dim * 2), "hipMalloc of the row buffer") &&
+      step(hipMalloc(&d_cb, cb_bytes), "hipMalloc of the codebook") &&
+      step(hipMalloc(&d_codes, chunk * m), "hipMalloc of the code buffer") &&
+      (!dist_out || step(hipMalloc(&d_dist, chunk * m * 4), "hipMalloc of the distance buffer")) &&
+      step(hipMemcpyAsync(d_cb, codebook, cb_bytes, hipMemcpyHostToDevice, st), "the codebook's copy")) {
+    for (uint64_t at = 0; at < (uint64_t)n && !rc; at += chunk) {
+      const uint64_t rows = std::min<uint64_t>(chunk, (uint64_t)n - at);
+      if (!step(hipMemcpyAsync(d_rows, rows_bf16 + at * dim, rows * dim * 2, hipMemcpyHostToDevice, st), "a row chunk's copy")) break;
+      HzSearchPqAssignParams p{};
+      p.rows = d_rows;
+      p.codebook = d_cb;
+      p.codes = d_codes;
+      p.dist = d_dist;
+      p.dist_bytes = d_dist ? rows * m * 4 : 0;
+      p.N = (long long)rows;
+      p.D = dim;
+      p.M = m;
+      p.ldr = dim;
+      p.ldc = m;
+      if (const int lrc = hz_search_pqassign_launch(&p, st)) {
+        if (lrc > 0) step((hipError_t)lrc, "the assign launch");
+        else rc = lrc;
+        break;
+      }
+      if (!step(hipMemcpyAsync(codes_out + at * m, d_codes, rows * m, hipMemcpyDeviceToHost, st), "a code chunk's copy")) break;
+      if (d_dist && !step(hipMemcpyAsync(dist_out + at * m, d_dist, rows * m * 4, hipMemcpyDeviceToHost, st), "a distance chunk's copy"))
+        break;
+      if (!step(hipStreamSynchronize(st), "hipStreamSynchronize")) break;
+    }
+  }
+  if (st) (void)hipStreamSynchronize(st);
+  if (d_rows) (void)hipFree(d_rows);
+  if (d_cb) (void)hipFree(d_cb);
+  if (d_codes) (void)hipFree(d_codes);
+  if (d_dist) (void)hipFree(d_dist);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
 }  // extern "C"

@@ -496,6 +496,10 @@ extern "C" __attribute__((weak)) int hz_search_pqscan_launch(const HzSearchPqPar
 static int hz_search_pqscan_op(const HzSearchPqParams* p, hipStream_t st) {
   return hz_search_pqscan_launch ? hz_search_pqscan_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_pqassign_launch(const HzSearchPqAssignParams* p, hipStream_t st);
+static int hz_search_pqassign_op(const HzSearchPqAssignParams* p, hipStream_t st) {
+  return hz_search_pqassign_launch ? hz_search_pqassign_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -21,7 +21,10 @@
 //   * search_pqlut / search_pqscan — product-quantised rows (kinds PQLUT, PQSCAN): a per-query table of the query's
 //                    inner products with 256 sub-centroids per sub-space, then the filtered scan over rows of M code
 //                    bytes, a workgroup holding ONE query's table in LDS and adding M lookups per row
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v / 4w for the reasoning.
+//   * search_pqassign — the nearest of 256 sub-centroids for every row and sub-space (kind PQASSIGN): what training
+//                    and encoding a product quantiser need, in plain fp32 operations numpy reproduces bit for bit
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v / 4w / 4x for the
+// reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -500,6 +503,108 @@ __global__ __launch_bounds__(T) void search_pqscan_kernel(const HzSearchPqParams
     const bool slot_ok = HZ_DCHECK(((long)tile * p.Q + q + 1) * p.k * 8 <= (long)p.cand_bytes);
     rank_query<true>(sc, out, slot_ok, p.k, rows, (unsigned)(row0 + t));
   }
+}
+
+// search_pqassign_kernel<NQ> (HZ_K_SEARCH_PQASSIGN): for every row and sub-space the nearest of the 256
+// sub-centroids under squared L2, in the contract's arithmetic (hipzap.h): plain fp32 subtract, multiply, add, one
+// rounding each, j ascending from +0; contraction is switched off for the whole function. NQ = ceil(dsub / 4): a
+// sub-vector and a centroid are held as DP = 4 NQ columns, the ones from dsub on ZERO in both -- t = 0 - 0 = +0 and
+// acc + +0 = acc for every value acc can hold (never -0: acc starts at +0 and every term is >= +0 or NaN), so the
+// padded sum has the bits of the dsub-term one and every instantiation agrees with every other.
+// Grid (ceil(N / T), M / 16); workgroup (tile, g) walks the sub-spaces m = 16 g .. 16 g + 15. Per sub-space: the
+// workgroup copies codebook[m] (256 x dsub fp32) into LDS as [256][DP] (16-B copies when dsub % 4 == 0, else word by
+// word with the zero columns), thread t loads its row's dsub bf16 values (16-B loads when dsub % 8 == 0, else one
+// element at a time: a sub-vector of an odd dsub is not 16-B aligned) and walks c = 0 .. 255: every lane reads the
+// SAME centroid words (an LDS broadcast, ds_read_b128), 3 DP vector operations per centroid, then the strict
+// `d < best`. Four sub-spaces make one code word and one 16-B store of distances; the four words of a group leave as
+// one 16-B store of codes.
+// Addresses: codebook words [m*256*dsub, (m + 1)*256*dsub) under m < M; rows[(row0 + t)*ldr + m*dsub + j] under
+// row0 + t < N, j < dsub, m*dsub + dsub <= D <= ldr; codes bytes [(row0 + t)*ldc + 16 g, + 16) under 16 g + 16 <= M <=
+// ldc and row < N; dist words [(row0 + t)*M + 16 g + 4 q, + 4) under (that end) * 4 <= dist_bytes.
+// LDS: dynamic DP KiB. Registers: DP floats of the row, no scratch at any NQ (the resource table is in DESIGN.md 4x).
+template <int NQ>
+__global__ __launch_bounds__(T) void search_pqassign_kernel(const HzSearchPqAssignParams a) {
+#pragma clang fp contract(off)
+  constexpr int DP = NQ * 4;
+  extern __shared__ __attribute__((aligned(16))) float cent[];  // [256][DP]
+  const int t = threadIdx.x, g = blockIdx.y;
+  if (!HZ_DCHECK(a.M >= 16 && a.M % 16 == 0 && a.D % a.M == 0 && g * 16 + 16 <= a.M && (a.D / a.M + 3) / 4 == NQ &&
+                 a.ldr >= a.D && a.ldc >= a.M && (long)blockIdx.x * T < (long)a.N))
+    return;
+  const int dsub = a.D / a.M;
+  const long row = (long)blockIdx.x * T + t;
+  const bool real = row < (long)a.N;
+  const long cb_words = (long)a.M * PQ_KSUB * dsub;
+  u32x4 words = {0u, 0u, 0u, 0u};
+#pragma unroll 1
+  for (int q = 0; q < 4; ++q) {
+    unsigned word = 0u;
+    f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = g * 16 + q * 4 + i;
+      __syncthreads();  // the last sub-space's reads of `cent` are done
+      const float* src = a.codebook + (long)m * PQ_KSUB * dsub;
+      if (dsub == DP) {
+        for (int e = t; e < PQ_KSUB * NQ; e += T)
+          if (HZ_DCHECK((long)m * PQ_KSUB * dsub + 4l * e + 4 <= cb_words))
+            reinterpret_cast<f32x4*>(cent)[e] = reinterpret_cast<const f32x4*>(src)[e];
+      } else {
+        for (int e = t; e < PQ_KSUB * DP; e += T) {
+          const int c = e / DP, j = e % DP;
+          float v = 0.f;
+          if (j < dsub && HZ_DCHECK((long)m * PQ_KSUB * dsub + c * dsub + j < cb_words)) v = src[c * dsub + j];
+          cent[e] = v;
+        }
+      }
+      float x[DP];
+#pragma unroll
+      for (int j = 0; j < DP; ++j) x[j] = 0.f;
+      if (real && HZ_DCHECK(row < (long)a.N && m * dsub + dsub <= a.D)) {
+        const unsigned short* rp = a.rows + row * a.ldr + m * dsub;
+        if (NQ % 2 == 0 && dsub == DP) {  // dsub % 8 == 0: the sub-vector is whole 16-B chunks
+#pragma unroll
+          for (int ch = 0; ch < NQ / 2; ++ch) unpack8(*reinterpret_cast<const u32x4*>(rp + ch * 8), x + ch * 8);
+        } else {
+#pragma unroll
+          for (int j = 0; j < DP; ++j)
+            if (j < DP - 4 || j < dsub) x[j] = bf2f(rp[j]);  // DP - 4 < dsub: only the last four columns ask
+        }
+      }
+      __syncthreads();
+      float best = 0.f;
+      unsigned code = 0u;
+#pragma unroll 2
+      for (int c = 0; c < PQ_KSUB; ++c) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) {
+          const f32x4 cv = *reinterpret_cast<const f32x4*>(cent + c * DP + k * 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float tj = x[k * 4 + j] - cv[j];
+            const float sq = tj * tj;
+            acc = acc + sq;
+          }
+        }
+        if (c == 0 || acc < best) {
+          best = acc;
+          code = (unsigned)c;
+        }
+      }
+      word |= code << (8 * i);
+      d4[i] = best;
+    }
+    words[0] = q == 0 ? word : words[0];
+    words[1] = q == 1 ? word : words[1];
+    words[2] = q == 2 ? word : words[2];
+    words[3] = q == 3 ? word : words[3];
+    const long at = row * a.M + g * 16 + q * 4;
+    if (real && a.dist && HZ_DCHECK(row < (long)a.N && (at + 4) * 4 <= (long)a.dist_bytes))
+      *reinterpret_cast<f32x4*>(a.dist + at) = d4;
+  }
+  if (real && HZ_DCHECK(row < (long)a.N && g * 16 + 16 <= a.ldc))
+    *reinterpret_cast<u32x4*>(a.codes + row * a.ldc + g * 16) = words;
 }
 
 // -------------------------------------------------------------------------------------- list scan
@@ -1636,6 +1741,41 @@ extern "C" int hz_search_pqscan_launch(const HzSearchPqParams* pp, hipStream_t s
   if (a.span == 0) a.span = pq_auto_span(p.ntile, p.Q, cus, a.M);
   if (a.span > p.ntile) a.span = p.ntile;
   pqscan_dispatch(a, dim3((p.ntile + a.span - 1) / a.span, p.Q), st);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+template <int NQ = 1>
+void pqassign_dispatch(const HzSearchPqAssignParams& a, const int nq, const dim3 grid, hipStream_t st) {
+  if constexpr (NQ < HZ_SEARCH_PQ_MAX_DSUB / 4) {
+    if (nq > NQ) return pqassign_dispatch<NQ + 1>(a, nq, grid, st);
+  }
+  hipLaunchKernelGGL(search_pqassign_kernel<NQ>, grid, dim3(T), (size_t)NQ * 4 * PQ_KSUB * sizeof(float), st, a);
+}
+
+}  // namespace
+
+// The assign kind's refusal list (hipzap.h): -129 .. -139. At most 64 KiB of dynamic LDS: no attribute to raise.
+extern "C" int hz_search_pqassign_launch(const HzSearchPqAssignParams* pp, hipStream_t st) {
+  if (!pp) return -129;
+  const HzSearchPqAssignParams a = *pp;
+  if (!a.rows || !a.codebook || !a.codes) return -129;
+  if (a.M < 1) return -132;  // before the division
+  if (a.D % a.M) return -130;
+  if (a.M % 16) return -131;
+  if (a.M < 16 || a.M > HZ_SEARCH_PQ_MAX_M) return -132;
+  if (a.D / a.M < 1 || a.D / a.M > HZ_SEARCH_PQ_MAX_DSUB) return -133;
+  if (a.D > 2048) return -134;
+  if (a.ldr < a.D || a.ldr % 8) return -135;
+  if (a.ldc < a.M || a.ldc % 16) return -136;
+  if (a.N < 1) return -137;
+  if ((reinterpret_cast<uintptr_t>(a.rows) & 15) || (reinterpret_cast<uintptr_t>(a.codebook) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.codes) & 15) || (reinterpret_cast<uintptr_t>(a.dist) & 15))
+    return -138;
+  if (a.dist && a.dist_bytes < (unsigned long long)a.N * a.M * 4ull) return -139;
+  const int dsub = a.D / a.M;
+  pqassign_dispatch(a, (dsub + 3) / 4, dim3((unsigned)((a.N + T - 1) / T), a.M / 16), st);
   return (int)hipGetLastError();
 }
 

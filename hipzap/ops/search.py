@@ -24,6 +24,9 @@ same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``o
 ``HZ_K_SEARCH_PQLUT`` (``PqLutParams``) writes each query's table of inner products with the 256 sub-centroids of every
 sub-space of a product quantiser; ``HZ_K_SEARCH_PQSCAN`` (``PqScanParams``: the filtered block over uint8 code rows,
 ``ldc`` in bytes, plus the table) adds M table entries per row, one query's table resident in LDS per workgroup.
+``HZ_K_SEARCH_PQASSIGN`` (``PqAssignParams``) writes, for every bf16 row and sub-space, the nearest of the 256
+sub-centroids under squared L2 in plain fp32 operations (:func:`hipzap.search.pq_assign_f32` is its bits in numpy);
+``pq_encode_rows`` is the batch job over host rows built on it (``hz_pq_encode``).
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -104,6 +107,15 @@ class PqScanParams(C.Structure):
         sp = SearchParams.from_buffer_copy(self)
         sp.ldc = sp.D
         return sp
+
+
+@N.params_of("HZ_K_SEARCH_PQASSIGN")
+class PqAssignParams(C.Structure):
+    """HzSearchPqAssignParams: ``rows`` bf16 [N][ldr], ``codebook`` fp32 [M][256][D / M], ``codes`` uint8 [N][ldc] out
+    (``ldc`` in bytes), ``dist`` fp32 [N][M] out or null with ``dist_bytes``."""
+    _fields_ = [("rows", C.c_void_p), ("codebook", C.c_void_p), ("codes", C.c_void_p), ("dist", C.c_void_p),
+                ("dist_bytes", C.c_uint64), ("N", C.c_longlong), ("D", C.c_int), ("M", C.c_int),
+                ("ldr", C.c_longlong), ("ldc", C.c_longlong)]
 
 
 @N.params_of("HZ_K_SEARCH_RESCOREN")
@@ -215,6 +227,8 @@ def _sigs(lib):
     N._sig(lib, "hz_search_pqlut_launch", C.c_int, C.POINTER(PqLutParams), P)
     N._sig(lib, "hz_search_pqscan_launch", C.c_int, C.POINTER(PqScanParams), P)
     N._sig(lib, "hz_search_pq_span", C.c_int, C.c_longlong, C.c_int, C.c_int)
+    N._sig(lib, "hz_search_pqassign_launch", C.c_int, C.POINTER(PqAssignParams), P)
+    N._sig(lib, "hz_pq_encode", C.c_int, C.c_int, P, C.c_longlong, C.c_int, C.c_int, P, C.c_longlong, P, P)
     N._sig(lib, "hz_index_add_p", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_add_pr", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_read_state_p", C.c_int, P, P, P, P, C.c_longlong)
@@ -318,6 +332,36 @@ def pq_span(n: int, q: int, m: int) -> int:
     """The tiles per workgroup a scan of (N, Q) over rows of M codes takes with ``span`` = 0 on the current device; 0
     for a refused shape."""
     return int(N.lib().hz_search_pq_span(int(n), int(q), int(m)))
+
+
+def launch_pq_assign(prm: PqAssignParams, stream: int = 0) -> int:
+    """The assign launch (``HZ_K_SEARCH_PQASSIGN``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_pqassign_launch(C.byref(prm), stream))
+
+
+def pq_encode_rows(bits, codebook, *, device: int = 0, chunk_rows: int = 0, want_dist: bool = False):
+    """``hz_pq_encode``: bf16 rows ``bits`` (uint16 [n, D], host) against ``codebook`` (fp32 [M, 256, D / M], host) on
+    ``device`` -> (codes uint8 [n, M], dist fp32 [n, M] or None). ``chunk_rows``: rows per device pass, 0 for the
+    default. A refused shape is a ValueError with the launcher's code, a device failure a RuntimeError."""
+    import numpy as np
+    bits = np.ascontiguousarray(bits, np.uint16)
+    cb = np.ascontiguousarray(codebook, np.float32)
+    if bits.ndim != 2 or cb.ndim != 3 or cb.shape[1] != PQ_KSUB or cb.shape[0] * cb.shape[2] != bits.shape[1]:
+        raise ValueError(f"rows must be uint16 [n, D] and the codebook fp32 [M, {PQ_KSUB}, D / M], got {list(bits.shape)} "
+                         f"and {list(cb.shape)}")
+    n, d = bits.shape
+    m = cb.shape[0]
+    codes = np.empty((n, m), np.uint8)
+    dist = np.empty((n, m), np.float32) if want_dist else None
+    lib = N.lib()
+    rc = int(lib.hz_pq_encode(int(device), bits.ctypes.data, n, d, m, cb.ctypes.data, int(chunk_rows), codes.ctypes.data,
+                              dist.ctypes.data if want_dist else None))
+    if rc:
+        msg = (lib.hz_index_last_error() or b"").decode()
+        if rc in (-140, -141):
+            raise (ValueError if rc == -141 else RuntimeError)(msg or f"hz_pq_encode failed ({rc})")
+        raise ValueError(f"hz_pq_encode refused n = {n}, dim = {d}, m = {m} ({rc}: csrc/hipzap.h HZ_K_SEARCH_PQASSIGN)")
+    return codes, dist
 
 
 def launch_rescore(prm: RescoreParams, stream: int = 0) -> int:

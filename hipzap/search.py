@@ -282,7 +282,75 @@ def _pq_nearest(x32: np.ndarray, cent32: np.ndarray):
     return best, dist
 
 
-def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ_SAMPLE, init=None) -> np.ndarray:
+PQ_BACKENDS = ("cpu", "f32", "gpu")
+
+
+def _check_pq_backend(backend, what: str = "backend"):
+    if backend not in PQ_BACKENDS:
+        raise ValueError(f"{what} must be one of {PQ_BACKENDS}, got {backend!r}")
+
+
+def pq_assign_f32(rows32, codebook, *, chunk: int = 4096):
+    """HZ_K_SEARCH_PQASSIGN's arithmetic (csrc/hipzap.h) in numpy float32 -> (codes uint8 [N, M], dist float32 [N, M]):
+    for row r, sub-space m and centroid c the sum over j = 0 .. dsub-1, ascending, from +0, of t * t with
+    t = rows[r][m*dsub + j] - codebook[m][c][j], every subtraction, multiplication and addition one float32 operation
+    (numpy fuses nothing); the code is the first of the smallest values walking c upward under a strict ``<``, so a NaN
+    never displaces anything and a column whose first value is NaN keeps code 0. The kernel's oracle, bit for bit, and
+    the ``"f32"`` backend. ``chunk`` rows at a time: the working set is chunk x 256 floats, whatever N is; the result
+    does not depend on it."""
+    cb = np.ascontiguousarray(codebook, np.float32)
+    x = np.ascontiguousarray(rows32, np.float32)
+    if cb.ndim != 3 or cb.shape[1] != PQ_KSUB:
+        raise ValueError(f"codebook must be floats [M, {PQ_KSUB}, dsub], got {list(cb.shape)}")
+    m, _, dsub = cb.shape
+    if x.ndim != 2 or x.shape[1] != m * dsub:
+        raise ValueError(f"rows must be [N, {m * dsub}], got {list(x.shape)}")
+    if not _is_int(chunk) or chunk < 1:
+        raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
+    n = x.shape[0]
+    codes = np.empty((n, m), np.uint8)
+    dist = np.empty((n, m), np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for a in range(0, n, chunk):
+            xa = x[a:a + chunk]
+            rows = np.arange(xa.shape[0])
+            for j in range(m):
+                ct = np.ascontiguousarray(cb[j].T)  # [dsub, 256]
+                d = np.zeros((xa.shape[0], PQ_KSUB), np.float32)
+                for i in range(dsub):
+                    t = xa[:, j * dsub + i, None] - ct[i][None, :]
+                    d = d + t * t
+                key = d
+                if np.isnan(d).any():  # argmin would pick a NaN; the walk never does, unless it starts on one
+                    key = np.where(np.isnan(d), np.float32(np.inf), d)
+                    key[np.isnan(d[:, 0]), 0] = -np.inf
+                best = np.argmin(key, axis=1)  # the first of equal minima
+                codes[a:a + chunk, j], dist[a:a + chunk, j] = best, d[rows, best]
+    return codes, dist
+
+
+def _bf16_exact(x32: np.ndarray) -> np.ndarray:
+    """fp32 rows -> their bf16 bits, or a ValueError when a value is not a bf16 number (the GPU encoder reads bf16 rows)."""
+    if not np.isfinite(x32).all():
+        raise ValueError("backend='gpu' needs finite rows")
+    bits = to_bf16(x32)
+    if not np.array_equal(bf16_to_f32(bits), x32):
+        raise ValueError("backend='gpu' needs rows that are exactly representable in bf16 (round them with "
+                         "bf16_to_f32(to_bf16(rows)) first, as prepare_rows_pq does)")
+    return bits
+
+
+def _pq_assign(x32: np.ndarray, cb: np.ndarray, backend: str, device: int, chunk_rows: int = 0, bits=None) -> np.ndarray:
+    """Codes uint8 [N, M] of ``x32`` by the ``"f32"`` or the ``"gpu"`` backend (``bits``: the rows' bf16 bits, if the
+    caller has them already)."""
+    if backend == "f32":
+        return pq_assign_f32(x32, cb)[0]
+    from .ops.search import pq_encode_rows
+    return pq_encode_rows(_bf16_exact(x32) if bits is None else bits, cb, device=device, chunk_rows=chunk_rows)[0]
+
+
+def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ_SAMPLE, init=None, backend: str = "cpu",
+             device: int = 0) -> np.ndarray:
     """Train a product quantiser on ``rows32`` (fp32 [N, D]) -> the codebook, fp32 [m, 256, D / m]. Per sub-space,
     Lloyd's k-means under squared L2 over at most ``sample`` rows: the rows are the first ``sample`` of a seeded
     permutation, in ascending order, the same rows for every sub-space; the first centroids of sub-space j are the
@@ -290,7 +358,12 @@ def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ
     rows the remaining centroids are zero). Assignment is :func:`pq_encode`'s (fp64, the lower centroid on ties); a
     centroid becomes its members' mean, accumulated in fp64 in row order and rounded to fp32, and keeps its value
     when it has no member. Deterministic for a given input and seed. ``init`` (fp32 [m, 256, D / m]) replaces the
-    first centroids; ``iters=0`` with ``init`` returns it unchanged."""
+    first centroids; ``iters=0`` with ``init`` returns it unchanged. ``backend`` changes the assignment step alone:
+    ``"f32"`` is :func:`pq_assign_f32`, ``"gpu"`` HZ_K_SEARCH_PQASSIGN on ``device`` over the sample, gathered on the
+    host once (one ``hz_pq_encode`` per iteration; the rows must be bf16 numbers) -- the same bits as ``"f32"``, so
+    the two give the same codebook bit for bit; the sample, the first centroids and the means are the same code for
+    every backend."""
+    _check_pq_backend(backend)
     x = np.asarray(rows32)
     if x.ndim != 2 or x.dtype.kind != "f" or x.shape[0] < 1:
         raise ValueError(f"rows must be a float array [N, D] with N >= 1, got {x.dtype} {list(x.shape)}")
@@ -308,10 +381,15 @@ def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ
         cb[:, :first.size] = xs[first].transpose(1, 0, 2)
     else:
         cb = check_codebook(init, d, m).copy()
+    flat = bits = None
+    if backend != "cpu" and iters:
+        flat = np.ascontiguousarray(xs.reshape(take.size, d))
+        bits = _bf16_exact(flat) if backend == "gpu" else None
     for _ in range(int(iters)):
+        codes = None if backend == "cpu" else _pq_assign(flat, cb, backend, device, bits=bits)
         for j in range(m):
             sub = np.ascontiguousarray(xs[:, j])
-            a = _pq_nearest(sub, cb[j])[0]
+            a = _pq_nearest(sub, cb[j])[0] if codes is None else codes[:, j]
             order = np.argsort(a, kind="stable")  # ascending rows inside a cluster
             sizes = np.bincount(a, minlength=PQ_KSUB)
             used = np.flatnonzero(sizes)
@@ -321,15 +399,24 @@ def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ
     return cb
 
 
-def pq_encode(rows32, codebook) -> np.ndarray:
+def pq_encode(rows32, codebook, *, backend: str = "cpu", device: int = 0, chunk_rows: int = 0) -> np.ndarray:
     """fp32 rows [N, D] -> codes uint8 [N, M]: per sub-space the nearest centroid of ``codebook`` (fp32 [M, 256, D / M])
     by squared L2 evaluated in fp64, the lower index on ties. Works through the rows in chunks, one sub-space at a
-    time: 10^6 x 768 needs the input, the codes and a few hundred MB."""
+    time: 10^6 x 768 needs the input, the codes and a few hundred MB. ``backend="f32"``: the distances in plain
+    float32 operations instead (:func:`pq_assign_f32`); ``"gpu"``: those same bits from HZ_K_SEARCH_PQASSIGN on
+    ``device`` (``hz_pq_encode``, ``chunk_rows`` rows per device pass, 0 for its default) -- the rows must be bf16
+    numbers, anything else is a ValueError. The two agree bit for bit; against the fp64 choice either may pick a
+    centroid whose distance is within (1 + g) / (1 - g), g = gamma(dsub + 2), of the optimum."""
+    _check_pq_backend(backend)
     cb = np.asarray(codebook, np.float32)
     x = np.ascontiguousarray(rows32, np.float32)
     m, _, dsub = cb.shape
     if x.ndim != 2 or x.shape[1] != m * dsub:
         raise ValueError(f"rows must be [N, {m * dsub}], got {list(x.shape)}")
+    if backend != "cpu":
+        if x.shape[0] == 0:
+            return np.empty((0, m), np.uint8)
+        return _pq_assign(x, np.ascontiguousarray(cb), backend, device, chunk_rows)
     codes = np.empty((x.shape[0], m), np.uint8)
     for j in range(m):
         codes[:, j] = _pq_nearest(x[:, j * dsub:(j + 1) * dsub], cb[j])[0]
@@ -405,20 +492,21 @@ def pq_search_ref(codes, codebook, q, k: int, allow=None):
 
 
 def prepare_rows_pq(vectors, metric: str, m: int, codebook=None, *, seed: int = 0, iters: int = 10,
-                    sample: int = PQ_SAMPLE):
+                    sample: int = PQ_SAMPLE, backend: str = "cpu", device: int = 0):
     """fp32 [N, D] -> (codes uint8 [N, m], codebook fp32 [m, 256, D / m]), what a pq8 index of ``metric`` stores: the
     checks and the cosine normalisation of :func:`prepare_rows`, the rounding to bf16, then :func:`pq_train` over the
     rounded rows (unless ``codebook`` is given) and :func:`pq_encode` against it. Rounding first means that
     ``convert_index`` from a bf16 index and ``write_index`` from the same vectors see the same rows: with the same
-    codebook they store the same bytes."""
+    codebook they store the same bytes. ``backend`` / ``device`` go to both (:func:`pq_train`, :func:`pq_encode`)."""
+    _check_pq_backend(backend)
     check_pq_shape(np.asarray(vectors).shape[1] if np.asarray(vectors).ndim == 2 else 0, m)
     bits = to_bf16(_checked_rows(vectors, metric, int(m), f"dim of a pq index with m = {m}"))
     rows = bf16_to_f32(bits)
     if not np.isfinite(rows).all():
         raise ValueError("a value overflows bf16")
-    cb = pq_train(rows, m, seed=seed, iters=iters, sample=sample) if codebook is None \
+    cb = pq_train(rows, m, seed=seed, iters=iters, sample=sample, backend=backend, device=device) if codebook is None \
         else check_codebook(codebook, rows.shape[1], m)
-    return pq_encode(rows, cb), cb
+    return pq_encode(rows, cb, backend=backend, device=device), cb
 
 
 def check_tags(tags, n: int) -> np.ndarray:
@@ -636,7 +724,7 @@ def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
                 ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
-                pq_seed: int = 0, pq_iters: int = 10) -> dict:
+                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu") -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -649,12 +737,15 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     in place of :func:`ivf_kmeans`; the file has the same layout either way. ``dtype="bin"``: sign-bit rows
     (:func:`prepare_rows_bin`), a version-8 file, with ``rescore=True`` version 9. ``dtype="pq"``: rows of ``pq_m``
     code bytes and their codebook (:func:`prepare_rows_pq`: trained with ``pq_seed`` / ``pq_iters`` unless
-    ``pq_codebook`` is given), a version-10 file, with ``rescore=True`` version 11."""
+    ``pq_codebook`` is given), a version-10 file, with ``rescore=True`` version 11; ``pq_backend`` (``"cpu"``,
+    ``"f32"``, ``"gpu"`` on ``device``) picks how training and encoding find the nearest sub-centroids
+    (:func:`pq_encode`): ``"f32"`` and ``"gpu"`` write the same bytes."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
-    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10):
-        raise ValueError(f"pq_m, pq_codebook, pq_seed and pq_iters go with dtype='pq', got dtype={dtype!r}")
+    _check_pq_backend(pq_backend, "pq_backend")
+    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10 or pq_backend != "cpu"):
+        raise ValueError(f"pq_m, pq_codebook, pq_seed, pq_iters and pq_backend go with dtype='pq', got dtype={dtype!r}")
     if ivf is not None and dtype == "pq":
         raise ValueError(f"ivf={ivf!r} with dtype='pq': IVF lists over pq8 rows are not built")
     if ivf is not None and dtype == "bin":
@@ -668,7 +759,8 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     if dtype == "pq":
         if pq_m is None:
             raise ValueError("dtype='pq' needs pq_m, the code bytes per row (a multiple of 16 in 16..96 that divides dim)")
-        (rows, codebook), scales = prepare_rows_pq(vectors, metric, pq_m, pq_codebook, seed=pq_seed, iters=pq_iters), None
+        (rows, codebook), scales = prepare_rows_pq(vectors, metric, pq_m, pq_codebook, seed=pq_seed, iters=pq_iters,
+                                                   backend=pq_backend, device=device), None
     elif dtype == "bin":
         rows, scales = prepare_rows_bin(vectors, metric), None
     else:
@@ -1388,10 +1480,15 @@ class _Base:
             scores[part], ids[part] = self.neighbors(part, k)
         return ids, scores
 
-    def add(self, vectors, tags=None, labels=None) -> np.ndarray:
+    def add(self, vectors, tags=None, labels=None, *, encoder: str = "cpu") -> np.ndarray:
         """Append rows (fp32 [n, dim], through :func:`prepare_rows` or, on an fp8 index, :func:`prepare_rows_fp8`:
         the bits ``write_index`` would store) -> their ids, int32 [n]. ``tags``: uint32 [n], default 0.
-        ``labels``: required iff the index has labels."""
+        ``labels``: required iff the index has labels. ``encoder`` (a pq8 index only): the backend of
+        :func:`pq_encode` that encodes the new rows against the index's codebook, ``"gpu"`` on the index's device."""
+        _check_pq_backend(encoder, "encoder")
+        if encoder != "cpu" and self.dtype != PQ:
+            raise ValueError(f"encoder={encoder!r} goes with a pq8 index (its rows are encoded against a codebook); this "
+                             f"index holds {self.dtype} rows")
         if self.ivf is not None:
             raise ValueError("IVF indexes do not take add yet: write a new index with write_index(ivf=...)")
         if self.dtype == FP8:
@@ -1404,7 +1501,8 @@ class _Base:
             rbits = prepare_rows(vectors, self.metric)
             if rbits.shape[1] != self.dim:
                 raise ValueError(f"vectors must be [N, {self.dim}], got {list(rbits.shape)}")
-            bits = _PRows(pq_encode(bf16_to_f32(rbits), self.codebook), self.dim, rescore=rbits if self.rescore else None)
+            bits = _PRows(pq_encode(bf16_to_f32(rbits), self.codebook, backend=encoder, device=getattr(self, "device", 0)),
+                          self.dim, rescore=rbits if self.rescore else None)
         else:
             bits = prepare_rows(vectors, self.metric)
         n = bits.shape[0]
@@ -2016,7 +2114,7 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
                   ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None,
-                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10) -> dict:
+                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu") -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -2029,12 +2127,14 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     a list and stays dead. ``ivf_backend="gpu"``: the lists come from :func:`cluster_rows` on ``device``.
     ``dtype="pq"`` (a plain ``src``, ``pq_m`` code bytes per row): the stored rows are trained on (:func:`pq_train` with
     ``pq_seed`` / ``pq_iters``, unless ``pq_codebook`` is given) and encoded as they stand, which gives the bytes
-    ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11."""
+    ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11.
+    ``pq_backend`` as in :func:`write_index`."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
-    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10):
-        raise ValueError(f"pq_m, pq_codebook, pq_seed and pq_iters go with dtype='pq', got dtype={dtype!r}")
+    _check_pq_backend(pq_backend, "pq_backend")
+    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10 or pq_backend != "cpu"):
+        raise ValueError(f"pq_m, pq_codebook, pq_seed, pq_iters and pq_backend go with dtype='pq', got dtype={dtype!r}")
     if dtype == "pq" and ivf is not None:
         raise ValueError(f"ivf={ivf!r} with dtype='pq': IVF lists over pq8 rows are not built")
     if dtype == "pq" and pq_m is None:
@@ -2107,8 +2207,8 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     codebook = None
     if dtype == "pq":  # trained on and encoded from the stored rows as they stand (prepare_rows_pq rounds to bf16 first)
         rows32 = bf16_to_f32(bits)
-        codebook = pq_train(rows32, pq_m, seed=pq_seed, iters=pq_iters) if pq_codebook is None \
-            else check_codebook(pq_codebook, hdr["dim"], pq_m)
-        bits = pq_encode(rows32, codebook)
+        codebook = pq_train(rows32, pq_m, seed=pq_seed, iters=pq_iters, backend=pq_backend, device=device) \
+            if pq_codebook is None else check_codebook(pq_codebook, hdr["dim"], pq_m)
+        bits = pq_encode(rows32, codebook, backend=pq_backend, device=device)
     return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
                        hdr.get("capacity"), scales=scales, rescore=rrows, pq=codebook)
