@@ -16,6 +16,7 @@
     python -m hipzap index --vectors v.npy --dtype bin --rescore --out d.hzidx  # sign-bit scan + bf16 rescoring (version 9)
     python -m hipzap index --vectors v.npy --dtype pq --pq-m 96 --rescore --out e.hzidx  # product quantisation (version 11)
     python -m hipzap index --vectors v.npy --dtype pq --pq-m 96 --pq-backend gpu --out f.hzidx  # trained and encoded on the GPU
+    python -m hipzap index --vectors v.npy --dtype pq --pq-m 96 --pq-backend gpu --pq-means gpu --out g.hzidx  # the means too
     python -m hipzap info [x.hzidx]
 """
 from __future__ import annotations
@@ -128,8 +129,13 @@ def cmd_index(a):
         raise SystemExit("index: --pq-m, --pq-iters and --pq-seed go with --dtype pq")
     if a.dtype != "pq" and a.pq_backend is not None:
         raise SystemExit("index: --pq-backend goes with --dtype pq")
+    if a.dtype != "pq" and a.pq_means is not None:
+        raise SystemExit("index: --pq-means goes with --dtype pq")
+    if a.pq_means == "gpu" and a.pq_backend != "gpu":
+        raise SystemExit("index: --pq-means gpu needs --pq-backend gpu")
     pq = {} if a.dtype != "pq" else {"pq_m": a.pq_m, "pq_iters": 10 if a.pq_iters is None else a.pq_iters,
-                                     "pq_seed": a.pq_seed or 0, "pq_backend": a.pq_backend or "cpu"}
+                                     "pq_seed": a.pq_seed or 0, "pq_backend": a.pq_backend or "cpu",
+                                     "pq_means": a.pq_means or "host"}
     if a.rescore and a.dtype not in ("fp8", "bin", "pq"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
@@ -344,6 +350,10 @@ def main(argv=None):
                     help="with --dtype pq: how training and encoding find the nearest sub-centroids: cpu (fp64 numpy, the "
                          "default), f32 (the GPU kernel's arithmetic in numpy) or gpu (HZ_K_SEARCH_PQASSIGN on --device; "
                          "the same bytes as f32)")
+    ix.add_argument("--pq-means", choices=["host", "seq", "gpu"], default=None,
+                    help="with --dtype pq: how training sums a cluster's rows: host (numpy's pairwise reduceat, the "
+                         "default), seq (a strict fp64 chain over ascending rows) or gpu (HZ_K_SEARCH_PQUPDATE, the whole "
+                         "training loop on --device; needs --pq-backend gpu; the same bytes as seq with f32)")
     ix.add_argument("--dtype", choices=["bf16", "fp8", "bin", "pq"], default="bf16",
                     help="fp8: e4m3fn rows with one fp32 scale per row (a version-3 file, half the bytes; D %% 16 == 0); "
                          "bin: one sign bit per column (a version-8 file, a sixteenth of the bytes; D %% 128 == 0), "

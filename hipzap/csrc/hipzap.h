@@ -587,6 +587,41 @@ typedef struct HzSearchPqAssignParams {
   long long ldr, ldc;             // ldr in elements, ldc in bytes
 } HzSearchPqAssignParams;
 int hz_search_pqassign_launch(const HzSearchPqAssignParams* p, hipStream_t st);
+// sub-centroid update (HZ_K_SEARCH_PQUPDATE): the other half of a Lloyd iteration of a product
+// quantiser, from kind 48's codes to the new codebook. rows: bf16 [N][ldr]; codes: uint8 [N][ldc] (ldc in bytes);
+// codebook_in, codebook_out: fp32 [M][256][dsub], dsub = D / M, and they may be the SAME buffer; counts: int32
+// [M][256] out, may be null.
+// CONTRACT. For sub-space m and centroid c let r_1 < r_2 < ... < r_n be the rows with codes[r][m] == c.
+//   n == 0: codebook_out[m][c][:] has the bits of codebook_in[m][c][:].
+//   n >= 1: for every column j, S = -0.0 in fp64, then S = S + double(rows[r_i][m*dsub + j]) for i = 1 .. n IN THAT
+//           ORDER, every addition ONE fp64 round-to-nearest operation, and
+//           codebook_out[m][c][j] = float(S / double(n)): one IEEE fp64 division, one round-to-nearest conversion.
+// S starts at -0.0, not +0.0, so that a cluster whose members are all -0.0 keeps the sign (-0.0 + -0.0 = -0.0, and
+// -0.0 + x = x for every other x): what numpy's np.add.at into an array of -0.0 gives, and
+// hipzap.search.pq_means_seq reproduces the kernel bit for bit. counts[m][c] = n when counts is given. Bytes M ..
+// ldc-1 of a code row and rows from N on are not read. The bits depend on the codes, the rows and codebook_in ALONE:
+// not on the grid, on the row tiles or list batches of the kernel, or on how centroids are grouped into workgroups.
+// No atomics, no scratch buffer, nothing shared between workgroups.
+// Grid (M, 256 / HZ_SEARCH_PQU_CG), 256 threads: a workgroup owns HZ_SEARCH_PQU_CG consecutive centroids of one
+// sub-space, walks the rows HZ_SEARCH_PQU_TILE at a time and adds its members HZ_SEARCH_PQU_BATCH at a time.
+// Refusals (nothing is launched), kind 48's codes for the rules they share: -129 a null rows, codes, codebook_in or
+// codebook_out; -130 D % M; -131 M % 16; -132 M outside 16..96; -133 D / M outside 1..64; -134 D > 2048; -135 ldr < D
+// or ldr % 8; -136 ldc < M or ldc % 16; -137 N < 1; -138 rows, codes, codebook_in or codebook_out not 16-B aligned, or
+// counts not 4-B aligned; -142 N > 2^31 - 1.
+#define HZ_SEARCH_PQU_CG 16      // centroids a workgroup owns
+#define HZ_SEARCH_PQU_TILE 256   // rows whose codes a workgroup reads at a time
+#define HZ_SEARCH_PQU_BATCH 384  // members whose sub-vectors it stages in LDS at a time
+typedef struct HzSearchPqUpdateParams {
+  const unsigned short* rows;   // device bf16 [N][ldr], 16-B aligned
+  const unsigned char* codes;   // device uint8 [N][ldc], 16-B aligned
+  const float* codebook_in;     // device fp32 [M][256][D / M], 16-B aligned
+  float* codebook_out;          // device fp32 [M][256][D / M], 16-B aligned; may be codebook_in
+  int* counts;                  // device int32 [M][256], or null
+  long long N;
+  int D, M;
+  long long ldr, ldc;           // ldr in elements, ldc in bytes
+} HzSearchPqUpdateParams;
+int hz_search_pqupdate_launch(const HzSearchPqUpdateParams* p, hipStream_t st);
 // rescore (HZ_K_SEARCH_RESCORE): the second stage of a two-stage search. One workgroup per query
 // scores the query against the R bf16 rows that `in_id` names (a merge's out_id of stage one; a slot is real
 // iff (unsigned)id < (unsigned)N, every other value is an empty slot and nothing is loaded for it) and writes
@@ -965,6 +1000,16 @@ int hz_index_cmean(void* idx, int ctx, const int* order, long long M, const int*
 // stream failed, -141: chunk_rows < 0 (hz_index_last_error says which call and why).
 int hz_pq_encode(int device, const unsigned short* rows_bf16, long long n, int dim, int m, const float* codebook,
                  long long chunk_rows, unsigned char* codes_out, float* dist_out_or_null);
+// hz_pq_train: `iters` Lloyd iterations of a product quantiser over n host rows (bf16 [n][dim]) on
+// `device`, the whole loop device-resident. `codebook_inout` (host fp32 [m][256][dim / m]) holds the first centroids
+// and receives the last; counts_out_or_null (host int32 [m][256]) the member counts of the LAST iteration. One stream:
+// the rows and the codebook are uploaded once, every iteration is an HZ_K_SEARCH_PQASSIGN launch over all n rows and an
+// HZ_K_SEARCH_PQUPDATE launch in place on the device codebook, then one copy back and one synchronise. iters == 0
+// touches nothing (neither the codebook nor the counts). A refused shape returns the launchers' code (-129 .. -137,
+// -142); -140: hipSetDevice, an allocation, a copy or the stream failed, -141: iters < 0 (hz_index_last_error says
+// which call and why).
+int hz_pq_train(int device, const unsigned short* rows_bf16, long long n, int dim, int m, float* codebook_inout,
+                int iters, int* counts_out_or_null);
 
 // row softmax: out[r][i] = exp(s*x[r][i] + mask[i] - m_r) / sum_i(...), i < D
 typedef struct HzSoftmaxParams {
@@ -1159,7 +1204,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_RESCOREN, 45, HzSearchRescoreParams, hz_search_rescoren_op, SEARCH) \
   X(SEARCH_PQLUT, 46, HzSearchPqLutParams, hz_search_pqlut_op, SEARCH)    \
   X(SEARCH_PQSCAN, 47, HzSearchPqParams, hz_search_pqscan_op, SEARCH)  \
-  X(SEARCH_PQASSIGN, 48, HzSearchPqAssignParams, hz_search_pqassign_op, SEARCH)
+  X(SEARCH_PQASSIGN, 48, HzSearchPqAssignParams, hz_search_pqassign_op, SEARCH) \
+  X(SEARCH_PQUPDATE, 49, HzSearchPqUpdateParams, hz_search_pqupdate_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

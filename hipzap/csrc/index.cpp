@@ -1655,4 +1655,82 @@ int hz_pq_encode(int device, const unsigned short* rows_bf16, long long n, int d
   return rc;
 }
 
+// hz_pq_train (hipzap.h): no index, a stream and four device buffers of its own, all released on every
+// way out. H2D of the rows and the codebook once; per iteration HZ_K_SEARCH_PQASSIGN over all rows, then
+// HZ_K_SEARCH_PQUPDATE in place on the device codebook; D2H of the codebook (and the counts), one synchronise.
+int hz_pq_train(int device, const unsigned short* rows_bf16, long long n, int dim, int m, float* codebook, int iters,
+                int* counts_out) {
+  if (!rows_bf16 || !codebook) return -129;
+  if (m < 1) return -132;  // before the division
+  if (dim % m) return -130;
+  if (m % 16) return -131;
+  if (m < 16 || m > HZ_SEARCH_PQ_MAX_M) return -132;
+  if (dim / m < 1 || dim / m > HZ_SEARCH_PQ_MAX_DSUB) return -133;
+  if (dim > 2048) return -134;
+  if (n < 1) return -137;
+  if (n > 0x7fffffffll) return -142;
+  if (iters < 0) {
+    g_err = "pq_train: iters must be >= 0, got " + std::to_string(iters);
+    return -141;
+  }
+  if (iters == 0) return 0;
+  const uint64_t cb_bytes = (uint64_t)256 * dim * 4;  // [m][256][dim / m] fp32
+  const uint64_t cnt_bytes = (uint64_t)m * 256 * 4;
+  hipStream_t st = nullptr;
+  unsigned short* d_rows = nullptr;
+  float* d_cb = nullptr;
+  unsigned char* d_codes = nullptr;
+  int* d_counts = nullptr;
+  int rc = 0;
+  const auto step = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    g_err = std::string("pq_train: ") + what + " failed: " + hipGetErrorString(e);
+    rc = -140;
+    return false;
+  };
+  if (step(hipSetDevice(device), "hipSetDevice") && step(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate") &&
+      step(hipMalloc(&d_rows, (uint64_t)n * dim * 2), "hipMalloc of the rows") &&
+      step(hipMalloc(&d_cb, cb_bytes), "hipMalloc of the codebook") &&
+      step(hipMalloc(&d_codes, (uint64_t)n * m), "hipMalloc of the codes") &&
+      (!counts_out || step(hipMalloc(&d_counts, cnt_bytes), "hipMalloc of the counts")) &&
+      step(hipMemcpyAsync(d_rows, rows_bf16, (uint64_t)n * dim * 2, hipMemcpyHostToDevice, st), "the rows' copy") &&
+      step(hipMemcpyAsync(d_cb, codebook, cb_bytes, hipMemcpyHostToDevice, st), "the codebook's copy")) {
+    HzSearchPqAssignParams pa{};
+    pa.rows = d_rows;
+    pa.codebook = d_cb;
+    pa.codes = d_codes;
+    pa.N = n;
+    pa.D = dim;
+    pa.M = m;
+    pa.ldr = dim;
+    pa.ldc = m;
+    HzSearchPqUpdateParams pu{};
+    pu.rows = d_rows;
+    pu.codes = d_codes;
+    pu.codebook_in = pu.codebook_out = d_cb;
+    pu.counts = d_counts;
+    pu.N = n;
+    pu.D = dim;
+    pu.M = m;
+    pu.ldr = dim;
+    pu.ldc = m;
+    for (int it = 0; it < iters && !rc; ++it) {
+      const int arc = hz_search_pqassign_launch(&pa, st);
+      const int lrc = arc ? arc : hz_search_pqupdate_launch(&pu, st);
+      if (lrc > 0) step((hipError_t)lrc, arc ? "the assign launch" : "the update launch");
+      else if (lrc) rc = lrc;
+    }
+    if (!rc && step(hipMemcpyAsync(codebook, d_cb, cb_bytes, hipMemcpyDeviceToHost, st), "the codebook's copy back") &&
+        (!d_counts || step(hipMemcpyAsync(counts_out, d_counts, cnt_bytes, hipMemcpyDeviceToHost, st), "the counts' copy back")))
+      step(hipStreamSynchronize(st), "hipStreamSynchronize");
+  }
+  if (st) (void)hipStreamSynchronize(st);
+  if (d_rows) (void)hipFree(d_rows);
+  if (d_cb) (void)hipFree(d_cb);
+  if (d_codes) (void)hipFree(d_codes);
+  if (d_counts) (void)hipFree(d_counts);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
 }  // extern "C"

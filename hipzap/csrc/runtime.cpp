@@ -500,6 +500,10 @@ extern "C" __attribute__((weak)) int hz_search_pqassign_launch(const HzSearchPqA
 static int hz_search_pqassign_op(const HzSearchPqAssignParams* p, hipStream_t st) {
   return hz_search_pqassign_launch ? hz_search_pqassign_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_pqupdate_launch(const HzSearchPqUpdateParams* p, hipStream_t st);
+static int hz_search_pqupdate_op(const HzSearchPqUpdateParams* p, hipStream_t st) {
+  return hz_search_pqupdate_launch ? hz_search_pqupdate_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -23,8 +23,10 @@
 //                    bytes, a workgroup holding ONE query's table in LDS and adding M lookups per row
 //   * search_pqassign — the nearest of 256 sub-centroids for every row and sub-space (kind PQASSIGN): what training
 //                    and encoding a product quantiser need, in plain fp32 operations numpy reproduces bit for bit
-// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v / 4w / 4x for the
-// reasoning.
+//   * search_pqupdate — from those codes to the new sub-centroids (kind PQUPDATE): each mean one fp64 chain over its
+//                    members in ascending row order, found by a stable compaction of the code bytes; no atomics
+// See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v / 4w / 4x / 4y
+// for the reasoning.
 #include <stdio.h>
 
 #include <type_traits>
@@ -605,6 +607,137 @@ __global__ __launch_bounds__(T) void search_pqassign_kernel(const HzSearchPqAssi
   }
   if (real && HZ_DCHECK(row < (long)a.N && g * 16 + 16 <= a.ldc))
     *reinterpret_cast<u32x4*>(a.codes + row * a.ldc + g * 16) = words;
+}
+
+// search_pqupdate_kernel<NC> (HZ_K_SEARCH_PQUPDATE): from kind 48's codes to the new sub-centroids, in the
+// contract's arithmetic (hipzap.h): per (m, c, j) ONE fp64 chain over the members in ascending row order from -0.0,
+// one fp64 division by the count, one conversion to fp32; contraction is switched off for the whole function.
+// Grid (M, 256 / CG), 256 threads. Workgroup (m, g) owns the centroids c = CG g .. CG g + CG - 1 of sub-space m; thread
+// (cl, lane) = (tid / L, tid % L), L = 256 / CG, keeps the sums of centroid CG g + cl for the columns lane, lane + L, ...
+// in NC = ceil(dsub / L) fp64 registers. Nothing leaves the workgroup until the end, so the order of the additions
+// is the order in which the workgroup meets its members -- and that is made the row order:
+//   * find: the rows are walked PQU_T at a time, thread t reading the code byte of row row0 + t (the next tile's byte
+//     is requested before this tile's is used). member = the code lies in the workgroup's range. A wave ballot and a
+//     prefix count place the members of a wave, the four wave totals (LDS, double-buffered by tile parity: one
+//     barrier per tile) place the waves: a stable compaction, so `list_row` / `list_cl` hold the members in ascending
+//     row order whatever the data.
+//   * add: the list is emptied when it could not take another whole tile (count > PQU_B; its capacity is PQU_B +
+//     PQU_T) and at the end, PQU_B entries at a time: the workgroup copies the sub-vectors of those rows into LDS
+//     (16-B chunks when dsub % 8 == 0, else element by element: a sub-vector of an odd dsub is not 16-B aligned), and
+//     every thread walks the entries in order. The entry's centroid byte is a broadcast read; the values are read and
+//     widened unconditionally and the sum is KEPT OR REPLACED by a select, so the loads of later entries do not wait
+//     on a branch and the only serial dependence is the fp64 add itself. A skipped entry leaves the register's bits
+//     alone, so the chain of a centroid is exactly its members' chain.
+// Across the grid every row's sub-vector is read from memory once (N x D x 2 bytes); the code bytes of column m are
+// read by the 256 / CG workgroups of the sub-space. LDS: PQU_B x dsub bf16 dynamic plus 3.2 KiB of list, whatever the
+// codes are; a tile whose rows all belong to one centroid fills PQU_T list entries, an empty one none.
+// Addresses: codes[row*ldc + m] under row < N, m < M <= ldc; rows[r*ldr + m*dsub + j] under r < N (r comes from the
+// list: only rows that passed row < N are written to it), j < dsub, m*dsub + dsub <= D <= ldr; list slots under
+// at < PQU_CAP (count <= PQU_B before a tile adds at most PQU_T); codebook words ((m*256 + c)*dsub + j) under c < 256,
+// j < dsub; counts[m*256 + c]. A lane whose last column is past dsub reads column 0 instead and stores nothing.
+constexpr int PQU_CG = HZ_SEARCH_PQU_CG, PQU_L = 256 / PQU_CG, PQU_T = HZ_SEARCH_PQU_TILE, PQU_B = HZ_SEARCH_PQU_BATCH;
+constexpr int PQU_CAP = PQU_B + PQU_T;
+static_assert(PQU_T == 256 && PQU_CG * PQU_L == 256 && PQU_L * 4 >= HZ_SEARCH_PQ_MAX_DSUB && PQ_KSUB % PQU_CG == 0,
+              "one code byte per thread and tile; at most four columns per thread");
+
+template <int NC>
+__global__ __launch_bounds__(256) void search_pqupdate_kernel(const HzSearchPqUpdateParams a) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned short pqu_stage[];  // [PQU_B][dsub] bf16
+  __shared__ int list_row[PQU_CAP];
+  __shared__ unsigned char list_cl[PQU_CAP];
+  __shared__ int wtot[2][4];
+  const int tid = threadIdx.x, m = blockIdx.x, g = blockIdx.y;
+  if (!HZ_DCHECK(a.M >= 16 && a.D % a.M == 0 && m < a.M && g < PQ_KSUB / PQU_CG && a.ldr >= a.D && a.ldc >= a.M &&
+                 (a.D / a.M + PQU_L - 1) / PQU_L == NC && a.N >= 1 && a.N <= 0x7fffffffll))
+    return;
+  const int dsub = a.D / a.M, nrows = (int)a.N;
+  const int cl = tid / PQU_L, lane = tid % PQU_L, wave = tid / HZ_WAVE;
+  const bool last_ok = lane + (NC - 1) * PQU_L < dsub;
+  const int last_col = last_ok ? lane + (NC - 1) * PQU_L : 0;
+  const unsigned char* cp = a.codes + m;
+  const unsigned short* rp = a.rows + (long)m * dsub;
+  double acc[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) acc[k] = -0.0;
+  int n = 0, count = 0;
+
+  // the PQU_B-entry batches of list[0 .. count): stage, then the ordered walk
+  const auto flush = [&]() {
+    for (int b0 = 0; b0 < count; b0 += PQU_B) {
+      const int nb = min(PQU_B, count - b0);
+      __syncthreads();  // the list is written; the last batch's reads of the staged rows are done
+      if (dsub % 8 == 0) {
+        const int cpr = dsub / 8;
+        for (int i = tid; i < nb * cpr; i += 256) {
+          const int e = i / cpr, ch = i - e * cpr;
+          const long r = list_row[b0 + e];
+          if (HZ_DCHECK(r >= 0 && r < (long)a.N && m * dsub + ch * 8 + 8 <= a.D))
+            *reinterpret_cast<u32x4*>(pqu_stage + e * dsub + ch * 8) =
+                *reinterpret_cast<const u32x4*>(rp + r * a.ldr + ch * 8);
+        }
+      } else {
+        for (int i = tid; i < nb * dsub; i += 256) {
+          const int e = i / dsub, j = i - e * dsub;
+          const long r = list_row[b0 + e];
+          if (HZ_DCHECK(r >= 0 && r < (long)a.N && m * dsub + j < a.D)) pqu_stage[i] = rp[r * a.ldr + j];
+        }
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int e = 0; e < nb; ++e) {
+        const bool hit = (int)list_cl[b0 + e] == cl;
+        const unsigned short* sv = pqu_stage + e * dsub;
+        n += hit ? 1 : 0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          const double s = acc[k] + (double)bf2f(sv[k < NC - 1 ? lane + k * PQU_L : last_col]);
+          acc[k] = hit ? s : acc[k];
+        }
+      }
+    }
+    count = 0;
+  };
+
+  unsigned code = 0u;
+  if (tid < nrows && HZ_DCHECK(m < a.ldc)) code = cp[(long)tid * a.ldc];
+  int par = 0;
+  for (long row0 = 0; row0 < (long)nrows; row0 += PQU_T, par ^= 1) {
+    const long row = row0 + tid, nxt = row + PQU_T;
+    const unsigned mine = code;
+    if (nxt < (long)nrows && HZ_DCHECK(nxt < (long)a.N && m < a.ldc)) code = cp[nxt * a.ldc];  // the next tile's, in flight
+    if (count > PQU_B) flush();  // uniform: every thread holds the same count
+    const bool member = row < (long)nrows && (int)(mine / PQU_CG) == g;
+    const unsigned long long bal = __ballot(member);
+    const int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+    if (tid % HZ_WAVE == 0) wtot[par][wave] = __popcll(bal);
+    __syncthreads();  // also: the walk of a flush above is over before the list is written again
+    int base = count, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int x = wtot[par][w];
+      base += w < wave ? x : 0;
+      total += x;
+    }
+    if (member && HZ_DCHECK(base + before < PQU_CAP)) {
+      list_row[base + before] = (int)row;
+      list_cl[base + before] = (unsigned char)(mine % PQU_CG);
+    }
+    count += total;
+  }
+  flush();
+
+  const int c = g * PQU_CG + cl;
+  const long at = ((long)m * PQ_KSUB + c) * dsub, cb_words = (long)a.M * PQ_KSUB * dsub;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const int j = lane + k * PQU_L;
+    if ((k < NC - 1 || last_ok) && HZ_DCHECK(at + j < cb_words)) {
+      const float v = n ? (float)(acc[k] / (double)n) : a.codebook_in[at + j];
+      a.codebook_out[at + j] = v;
+    }
+  }
+  if (a.counts && lane == 0 && HZ_DCHECK(m * PQ_KSUB + c < a.M * PQ_KSUB)) a.counts[m * PQ_KSUB + c] = n;
 }
 
 // -------------------------------------------------------------------------------------- list scan
@@ -1776,6 +1909,44 @@ extern "C" int hz_search_pqassign_launch(const HzSearchPqAssignParams* pp, hipSt
   if (a.dist && a.dist_bytes < (unsigned long long)a.N * a.M * 4ull) return -139;
   const int dsub = a.D / a.M;
   pqassign_dispatch(a, (dsub + 3) / 4, dim3((unsigned)((a.N + T - 1) / T), a.M / 16), st);
+  return (int)hipGetLastError();
+}
+
+namespace {
+
+template <int NC = 1>
+void pqupdate_dispatch(const HzSearchPqUpdateParams& a, const int nc, const int dsub, hipStream_t st) {
+  if constexpr (NC < HZ_SEARCH_PQ_MAX_DSUB / PQU_L) {
+    if (nc > NC) return pqupdate_dispatch<NC + 1>(a, nc, dsub, st);
+  }
+  hipLaunchKernelGGL(search_pqupdate_kernel<NC>, dim3(a.M, PQ_KSUB / PQU_CG), dim3(256),
+                     (size_t)PQU_B * dsub * sizeof(unsigned short), st, a);
+}
+
+}  // namespace
+
+// The update kind's refusal list (hipzap.h): kind 48's codes for the shared rules, -142 for an N the int32 row list
+// cannot hold. At most 48 KiB of dynamic LDS: no attribute to raise.
+extern "C" int hz_search_pqupdate_launch(const HzSearchPqUpdateParams* pp, hipStream_t st) {
+  if (!pp) return -129;
+  const HzSearchPqUpdateParams a = *pp;
+  if (!a.rows || !a.codes || !a.codebook_in || !a.codebook_out) return -129;
+  if (a.M < 1) return -132;  // before the division
+  if (a.D % a.M) return -130;
+  if (a.M % 16) return -131;
+  if (a.M < 16 || a.M > HZ_SEARCH_PQ_MAX_M) return -132;
+  if (a.D / a.M < 1 || a.D / a.M > HZ_SEARCH_PQ_MAX_DSUB) return -133;
+  if (a.D > 2048) return -134;
+  if (a.ldr < a.D || a.ldr % 8) return -135;
+  if (a.ldc < a.M || a.ldc % 16) return -136;
+  if (a.N < 1) return -137;
+  if ((reinterpret_cast<uintptr_t>(a.rows) & 15) || (reinterpret_cast<uintptr_t>(a.codes) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.codebook_in) & 15) || (reinterpret_cast<uintptr_t>(a.codebook_out) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.counts) & 3))
+    return -138;
+  if (a.N > 0x7fffffffll) return -142;
+  const int dsub = a.D / a.M;
+  pqupdate_dispatch(a, (dsub + PQU_L - 1) / PQU_L, dsub, st);
   return (int)hipGetLastError();
 }
 

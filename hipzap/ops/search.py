@@ -27,6 +27,10 @@ sub-space of a product quantiser; ``HZ_K_SEARCH_PQSCAN`` (``PqScanParams``: the 
 ``HZ_K_SEARCH_PQASSIGN`` (``PqAssignParams``) writes, for every bf16 row and sub-space, the nearest of the 256
 sub-centroids under squared L2 in plain fp32 operations (:func:`hipzap.search.pq_assign_f32` is its bits in numpy);
 ``pq_encode_rows`` is the batch job over host rows built on it (``hz_pq_encode``).
+``HZ_K_SEARCH_PQUPDATE`` (``PqUpdateParams``) turns those codes into new sub-centroids: each mean one fp64 sum over its
+members in ascending row order from -0.0, divided by the count and rounded to fp32
+(:func:`hipzap.search.pq_means_seq` is its bits in numpy); ``pq_train_rows`` is the device-resident training loop over
+the two kinds (``hz_pq_train``).
 torch-free: indexes (:mod:`hipzap.search`) are served without it."""
 from __future__ import annotations
 
@@ -41,6 +45,8 @@ INDEX_SELF_MAX_Q = 1024          # HZ_INDEX_SELF_MAX_Q: ids per hz_index_neighbo
 ASSIGN_CB = 64                   # HZ_SEARCH_ASSIGN_CB: centroids per block of the assign kernel
 ASSIGN_MAX_C = 65536             # HZ_SEARCH_ASSIGN_MAX_C: the most centroids (hipzap.search.IVF_MAX_LISTS)
 PQ_MAX_M, PQ_MAX_DSUB, PQ_KSUB = 96, 64, 256  # HZ_SEARCH_PQ_MAX_M, HZ_SEARCH_PQ_MAX_DSUB; sub-centroids per sub-space
+# HZ_SEARCH_PQU_CG, _TILE, _BATCH: centroids per workgroup of the update kernel, rows per tile, members per list batch
+PQ_UPDATE_CG, PQ_UPDATE_TILE, PQ_UPDATE_BATCH = 16, 256, 384
 
 
 @N.params_of("HZ_K_SEARCH_MERGE")
@@ -115,6 +121,15 @@ class PqAssignParams(C.Structure):
     (``ldc`` in bytes), ``dist`` fp32 [N][M] out or null with ``dist_bytes``."""
     _fields_ = [("rows", C.c_void_p), ("codebook", C.c_void_p), ("codes", C.c_void_p), ("dist", C.c_void_p),
                 ("dist_bytes", C.c_uint64), ("N", C.c_longlong), ("D", C.c_int), ("M", C.c_int),
+                ("ldr", C.c_longlong), ("ldc", C.c_longlong)]
+
+
+@N.params_of("HZ_K_SEARCH_PQUPDATE")
+class PqUpdateParams(C.Structure):
+    """HzSearchPqUpdateParams: ``rows`` bf16 [N][ldr], ``codes`` uint8 [N][ldc] (``ldc`` in bytes), ``codebook_in`` and
+    ``codebook_out`` fp32 [M][256][D / M] (they may be one buffer), ``counts`` int32 [M][256] out or null."""
+    _fields_ = [("rows", C.c_void_p), ("codes", C.c_void_p), ("codebook_in", C.c_void_p), ("codebook_out", C.c_void_p),
+                ("counts", C.c_void_p), ("N", C.c_longlong), ("D", C.c_int), ("M", C.c_int),
                 ("ldr", C.c_longlong), ("ldc", C.c_longlong)]
 
 
@@ -229,6 +244,8 @@ def _sigs(lib):
     N._sig(lib, "hz_search_pq_span", C.c_int, C.c_longlong, C.c_int, C.c_int)
     N._sig(lib, "hz_search_pqassign_launch", C.c_int, C.POINTER(PqAssignParams), P)
     N._sig(lib, "hz_pq_encode", C.c_int, C.c_int, P, C.c_longlong, C.c_int, C.c_int, P, C.c_longlong, P, P)
+    N._sig(lib, "hz_search_pqupdate_launch", C.c_int, C.POINTER(PqUpdateParams), P)
+    N._sig(lib, "hz_pq_train", C.c_int, C.c_int, P, C.c_longlong, C.c_int, C.c_int, P, C.c_int, P)
     N._sig(lib, "hz_index_add_p", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_add_pr", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_read_state_p", C.c_int, P, P, P, P, C.c_longlong)
@@ -362,6 +379,37 @@ def pq_encode_rows(bits, codebook, *, device: int = 0, chunk_rows: int = 0, want
             raise (ValueError if rc == -141 else RuntimeError)(msg or f"hz_pq_encode failed ({rc})")
         raise ValueError(f"hz_pq_encode refused n = {n}, dim = {d}, m = {m} ({rc}: csrc/hipzap.h HZ_K_SEARCH_PQASSIGN)")
     return codes, dist
+
+
+def launch_pq_update(prm: PqUpdateParams, stream: int = 0) -> int:
+    """The update launch (``HZ_K_SEARCH_PQUPDATE``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_pqupdate_launch(C.byref(prm), stream))
+
+
+def pq_train_rows(bits, codebook, iters: int, *, device: int = 0, want_counts: bool = False):
+    """``hz_pq_train``: ``iters`` Lloyd iterations over the bf16 rows ``bits`` (uint16 [n, D], host) from ``codebook``
+    (fp32 [M, 256, D / M], host; not modified) on ``device``, the rows uploaded once and nothing copied back before
+    the end -> the new codebook, or (codebook, counts int32 [M, 256] of the last iteration) with ``want_counts``
+    (zeros when ``iters`` is 0). A refused shape or a negative ``iters`` is a ValueError, a device failure a
+    RuntimeError."""
+    import numpy as np
+    bits = np.ascontiguousarray(bits, np.uint16)
+    cb = np.array(codebook, np.float32, order="C")  # a copy: the job works in place
+    if bits.ndim != 2 or cb.ndim != 3 or cb.shape[1] != PQ_KSUB or cb.shape[0] * cb.shape[2] != bits.shape[1]:
+        raise ValueError(f"rows must be uint16 [n, D] and the codebook fp32 [M, {PQ_KSUB}, D / M], got {list(bits.shape)} "
+                         f"and {list(cb.shape)}")
+    n, d = bits.shape
+    m = cb.shape[0]
+    counts = np.zeros((m, PQ_KSUB), np.int32) if want_counts else None
+    lib = N.lib()
+    rc = int(lib.hz_pq_train(int(device), bits.ctypes.data, n, d, m, cb.ctypes.data, int(iters),
+                             counts.ctypes.data if want_counts else None))
+    if rc:
+        msg = (lib.hz_index_last_error() or b"").decode()
+        if rc in (-140, -141):
+            raise (ValueError if rc == -141 else RuntimeError)(msg or f"hz_pq_train failed ({rc})")
+        raise ValueError(f"hz_pq_train refused n = {n}, dim = {d}, m = {m} ({rc}: csrc/hipzap.h HZ_K_SEARCH_PQUPDATE)")
+    return (cb, counts) if want_counts else cb
 
 
 def launch_rescore(prm: RescoreParams, stream: int = 0) -> int:

@@ -349,21 +349,66 @@ def _pq_assign(x32: np.ndarray, cb: np.ndarray, backend: str, device: int, chunk
     return pq_encode_rows(_bf16_exact(x32) if bits is None else bits, cb, device=device, chunk_rows=chunk_rows)[0]
 
 
+PQ_MEANS = ("host", "seq", "gpu")
+
+
+def _check_pq_means(means, backend, what: str = "means", bwhat: str = "backend"):
+    if means not in PQ_MEANS:
+        raise ValueError(f"{what} must be one of {PQ_MEANS}, got {means!r}")
+    if means == "gpu" and backend != "gpu":
+        raise ValueError(f"{what}='gpu' needs {bwhat}='gpu' (the device-resident loop runs both steps), got {bwhat}={backend!r}")
+
+
+def pq_means_seq(rows32, codes, codebook):
+    """HZ_K_SEARCH_PQUPDATE's contract (csrc/hipzap.h) in numpy -> (codebook_out fp32 [M, 256, dsub], counts int32
+    [M, 256]): for sub-space m and centroid c the members' sub-vectors are added in fp64 in ascending row order,
+    starting from -0.0 (``np.add.at`` applies its updates one by one, in index order), the sum is divided by the count
+    in fp64 and rounded to fp32; a centroid without members keeps the bits of ``codebook``. The kernel's oracle, bit for
+    bit, and the ``means="seq"`` option of :func:`pq_train`."""
+    cb = np.ascontiguousarray(codebook, np.float32)
+    x = np.ascontiguousarray(rows32, np.float32)
+    codes = np.asarray(codes)
+    if cb.ndim != 3 or cb.shape[1] != PQ_KSUB:
+        raise ValueError(f"codebook must be floats [M, {PQ_KSUB}, dsub], got {list(cb.shape)}")
+    m, _, dsub = cb.shape
+    if x.ndim != 2 or x.shape[1] != m * dsub or codes.shape != (x.shape[0], m) or codes.dtype != np.uint8:
+        raise ValueError(f"rows must be [N, {m * dsub}] and codes uint8 [N, {m}], got {list(x.shape)} and {codes.dtype} "
+                         f"{list(codes.shape)}")
+    out = cb.copy()
+    counts = np.empty((m, PQ_KSUB), np.int32)
+    for j in range(m):
+        acc = np.full((PQ_KSUB, dsub), -0.0, np.float64)
+        np.add.at(acc, codes[:, j], x[:, j * dsub:(j + 1) * dsub].astype(np.float64))
+        sizes = np.bincount(codes[:, j], minlength=PQ_KSUB)
+        used = np.flatnonzero(sizes)
+        out[j, used] = (acc[used] / sizes[used][:, None]).astype(np.float32)
+        counts[j] = sizes
+    return out, counts
+
+
 def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ_SAMPLE, init=None, backend: str = "cpu",
-             device: int = 0) -> np.ndarray:
+             device: int = 0, means: str = "host") -> np.ndarray:
     """Train a product quantiser on ``rows32`` (fp32 [N, D]) -> the codebook, fp32 [m, 256, D / m]. Per sub-space,
     Lloyd's k-means under squared L2 over at most ``sample`` rows: the rows are the first ``sample`` of a seeded
     permutation, in ascending order, the same rows for every sub-space; the first centroids of sub-space j are the
     sub-vectors of 256 of those rows (one more seeded draw, the same rows for every sub-space; with fewer than 256
     rows the remaining centroids are zero). Assignment is :func:`pq_encode`'s (fp64, the lower centroid on ties); a
-    centroid becomes its members' mean, accumulated in fp64 in row order and rounded to fp32, and keeps its value
-    when it has no member. Deterministic for a given input and seed. ``init`` (fp32 [m, 256, D / m]) replaces the
+    centroid becomes its members' mean, an fp64 sum divided by the count and rounded to fp32, and keeps its value
+    when it has no member. ``means`` picks the order of that sum: ``"host"`` (the default) gathers a cluster's rows in
+    ascending order and sums them with numpy's ``np.add.reduceat``, which adds each column PAIRWISE, not row after
+    row; ``"seq"`` is :func:`pq_means_seq`, the strict chain over ascending rows from -0.0, with any ``backend``;
+    ``"gpu"`` (with ``backend="gpu"`` only) gives the bits of ``"seq"`` from HZ_K_SEARCH_PQUPDATE, and the whole loop
+    is then ONE ``hz_pq_train`` call: the sample is uploaded once, every iteration is two launches on ``device`` and
+    only the last codebook comes back, so ``pq_train(backend="gpu", means="gpu")`` equals ``pq_train(backend="f32",
+    means="seq")`` bit for bit. The orders differ only where an fp64 sum of the rows is inexact (never on unit-norm
+    bf16 rows at these sizes). Deterministic for a given input and seed. ``init`` (fp32 [m, 256, D / m]) replaces the
     first centroids; ``iters=0`` with ``init`` returns it unchanged. ``backend`` changes the assignment step alone:
     ``"f32"`` is :func:`pq_assign_f32`, ``"gpu"`` HZ_K_SEARCH_PQASSIGN on ``device`` over the sample, gathered on the
     host once (one ``hz_pq_encode`` per iteration; the rows must be bf16 numbers) -- the same bits as ``"f32"``, so
     the two give the same codebook bit for bit; the sample, the first centroids and the means are the same code for
     every backend."""
     _check_pq_backend(backend)
+    _check_pq_means(means, backend)
     x = np.asarray(rows32)
     if x.ndim != 2 or x.dtype.kind != "f" or x.shape[0] < 1:
         raise ValueError(f"rows must be a float array [N, D] with N >= 1, got {x.dtype} {list(x.shape)}")
@@ -385,8 +430,16 @@ def pq_train(rows32, m: int, *, seed: int = 0, iters: int = 10, sample: int = PQ
     if backend != "cpu" and iters:
         flat = np.ascontiguousarray(xs.reshape(take.size, d))
         bits = _bf16_exact(flat) if backend == "gpu" else None
+    if means == "gpu":  # both steps on the device, nothing on the host until the last iteration is done
+        from .ops.search import pq_train_rows
+        return pq_train_rows(bits, cb, int(iters), device=device) if iters else cb
     for _ in range(int(iters)):
         codes = None if backend == "cpu" else _pq_assign(flat, cb, backend, device, bits=bits)
+        if means == "seq":
+            if codes is None:
+                codes = np.stack([_pq_nearest(np.ascontiguousarray(xs[:, j]), cb[j])[0] for j in range(m)], axis=1)
+            cb = pq_means_seq(xs.reshape(take.size, d), codes, cb)[0]
+            continue
         for j in range(m):
             sub = np.ascontiguousarray(xs[:, j])
             a = _pq_nearest(sub, cb[j])[0] if codes is None else codes[:, j]
@@ -492,19 +545,21 @@ def pq_search_ref(codes, codebook, q, k: int, allow=None):
 
 
 def prepare_rows_pq(vectors, metric: str, m: int, codebook=None, *, seed: int = 0, iters: int = 10,
-                    sample: int = PQ_SAMPLE, backend: str = "cpu", device: int = 0):
+                    sample: int = PQ_SAMPLE, backend: str = "cpu", device: int = 0, means: str = "host"):
     """fp32 [N, D] -> (codes uint8 [N, m], codebook fp32 [m, 256, D / m]), what a pq8 index of ``metric`` stores: the
     checks and the cosine normalisation of :func:`prepare_rows`, the rounding to bf16, then :func:`pq_train` over the
     rounded rows (unless ``codebook`` is given) and :func:`pq_encode` against it. Rounding first means that
     ``convert_index`` from a bf16 index and ``write_index`` from the same vectors see the same rows: with the same
-    codebook they store the same bytes. ``backend`` / ``device`` go to both (:func:`pq_train`, :func:`pq_encode`)."""
+    codebook they store the same bytes. ``backend`` / ``device`` go to both (:func:`pq_train`, :func:`pq_encode`),
+    ``means`` to :func:`pq_train`."""
     _check_pq_backend(backend)
+    _check_pq_means(means, backend)
     check_pq_shape(np.asarray(vectors).shape[1] if np.asarray(vectors).ndim == 2 else 0, m)
     bits = to_bf16(_checked_rows(vectors, metric, int(m), f"dim of a pq index with m = {m}"))
     rows = bf16_to_f32(bits)
     if not np.isfinite(rows).all():
         raise ValueError("a value overflows bf16")
-    cb = pq_train(rows, m, seed=seed, iters=iters, sample=sample, backend=backend, device=device) if codebook is None \
+    cb = pq_train(rows, m, seed=seed, iters=iters, sample=sample, backend=backend, device=device, means=means) if codebook is None \
         else check_codebook(codebook, rows.shape[1], m)
     return pq_encode(rows, cb, backend=backend, device=device), cb
 
@@ -724,7 +779,7 @@ def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
                 ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
-                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu") -> dict:
+                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host") -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -739,13 +794,16 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     code bytes and their codebook (:func:`prepare_rows_pq`: trained with ``pq_seed`` / ``pq_iters`` unless
     ``pq_codebook`` is given), a version-10 file, with ``rescore=True`` version 11; ``pq_backend`` (``"cpu"``,
     ``"f32"``, ``"gpu"`` on ``device``) picks how training and encoding find the nearest sub-centroids
-    (:func:`pq_encode`): ``"f32"`` and ``"gpu"`` write the same bytes."""
+    (:func:`pq_encode`): ``"f32"`` and ``"gpu"`` write the same bytes; ``pq_means`` (``"host"``, ``"seq"``, ``"gpu"``)
+    picks how training sums a cluster's rows (:func:`pq_train`'s ``means``)."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")
-    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10 or pq_backend != "cpu"):
-        raise ValueError(f"pq_m, pq_codebook, pq_seed, pq_iters and pq_backend go with dtype='pq', got dtype={dtype!r}")
+    _check_pq_means(pq_means, pq_backend, "pq_means", "pq_backend")
+    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10 or pq_backend != "cpu"
+                          or pq_means != "host"):
+        raise ValueError(f"pq_m, pq_codebook, pq_seed, pq_iters, pq_backend and pq_means go with dtype='pq', got dtype={dtype!r}")
     if ivf is not None and dtype == "pq":
         raise ValueError(f"ivf={ivf!r} with dtype='pq': IVF lists over pq8 rows are not built")
     if ivf is not None and dtype == "bin":
@@ -760,7 +818,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
         if pq_m is None:
             raise ValueError("dtype='pq' needs pq_m, the code bytes per row (a multiple of 16 in 16..96 that divides dim)")
         (rows, codebook), scales = prepare_rows_pq(vectors, metric, pq_m, pq_codebook, seed=pq_seed, iters=pq_iters,
-                                                   backend=pq_backend, device=device), None
+                                                   backend=pq_backend, device=device, means=pq_means), None
     elif dtype == "bin":
         rows, scales = prepare_rows_bin(vectors, metric), None
     else:
@@ -2114,7 +2172,7 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
                   ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None,
-                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu") -> dict:
+                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host") -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -2128,13 +2186,15 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     ``dtype="pq"`` (a plain ``src``, ``pq_m`` code bytes per row): the stored rows are trained on (:func:`pq_train` with
     ``pq_seed`` / ``pq_iters``, unless ``pq_codebook`` is given) and encoded as they stand, which gives the bytes
     ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11.
-    ``pq_backend`` as in :func:`write_index`."""
+    ``pq_backend`` and ``pq_means`` as in :func:`write_index`."""
     _check_ivf_backend(ivf_backend, ivf)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")
-    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10 or pq_backend != "cpu"):
-        raise ValueError(f"pq_m, pq_codebook, pq_seed, pq_iters and pq_backend go with dtype='pq', got dtype={dtype!r}")
+    _check_pq_means(pq_means, pq_backend, "pq_means", "pq_backend")
+    if dtype != "pq" and (pq_m is not None or pq_codebook is not None or pq_seed != 0 or pq_iters != 10 or pq_backend != "cpu"
+                          or pq_means != "host"):
+        raise ValueError(f"pq_m, pq_codebook, pq_seed, pq_iters, pq_backend and pq_means go with dtype='pq', got dtype={dtype!r}")
     if dtype == "pq" and ivf is not None:
         raise ValueError(f"ivf={ivf!r} with dtype='pq': IVF lists over pq8 rows are not built")
     if dtype == "pq" and pq_m is None:
@@ -2207,7 +2267,7 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     codebook = None
     if dtype == "pq":  # trained on and encoded from the stored rows as they stand (prepare_rows_pq rounds to bf16 first)
         rows32 = bf16_to_f32(bits)
-        codebook = pq_train(rows32, pq_m, seed=pq_seed, iters=pq_iters, backend=pq_backend, device=device) \
+        codebook = pq_train(rows32, pq_m, seed=pq_seed, iters=pq_iters, backend=pq_backend, device=device, means=pq_means) \
             if pq_codebook is None else check_codebook(pq_codebook, hdr["dim"], pq_m)
         bits = pq_encode(rows32, codebook, backend=pq_backend, device=device)
     return _write_file(dst, out, bits, read_tags(src) if v2 else None, read_live(src) if v2 else None,
