@@ -764,6 +764,74 @@ int hz_search_xscan_launch(const HzSearchBatchParams* p, hipStream_t st);
 // HZ_K_SEARCH_MERGE. The block, the score bits and every other refusal are HZ_K_SEARCH_RESCORE's (-4: Q outside
 // 1..HZ_SEARCH_SELF_MAX_Q).
 int hz_search_rescoren_launch(const HzSearchRescoreParams* p, hipStream_t st);
+// batch scan over product-quantised rows (HZ_K_SEARCH_PQXSCAN): HZ_K_SEARCH_XSCAN whose B operand is
+// GATHERED from a bf16 copy of the codebook. The grid, the fragment map, the A operand (the split, order l', m', h'), the live bitmap's rules,
+// the selection, the candidate layout cand[(tile*Q + q)*k ..] and the keys are that kind's; HZ_K_SEARCH_MERGEN takes
+// THIS block as it stands (it begins with HzSearchBatchParams' layout, `codes` where `corpus` is).
+// THE TABLE. cb8 is the codebook rounded to bf16 (round to nearest even) and re-laid by 8-column chunk, bf16
+// [D / 8][256][8]: cb8[g][c][j] = bf16(codebook[m][c][8g - m*dsub + j]), m = 8g / dsub; 512 * D bytes. It needs
+// dsub % 8 == 0, so a chunk never straddles two sub-spaces (hipzap.search.pq_table_bf16 builds it in numpy, index.cpp
+// for an open pq8 index). A lane's B fragment of step s -- 8 consecutive columns of one row -- is ONE 16-byte
+// global load at cb8 + ((4s + lh)*256 + code)*16, lh the lane's chunk of the step, code = codes[r][(4s + lh) / (dsub /
+// 8)], issued one step ahead of its MFMAs; the table stays in L2, nothing is staged in LDS and the k loop has no
+// barrier (an LDS ring was measured 7 % slower). A lane takes the code bytes of its four rows in 16-byte
+// loads (one serves 16 * dsub / 32 steps), under row < N and a live group only.
+// CONTRACT. score(q, r) has the bits HZ_K_SEARCH_XSCAN gives for the same query and the bf16 row
+// xr[i] = cb8[i / 8][codes[r][i / dsub]][i % 8]: ONE accumulator from +0, per 32-column step the MFMAs in the order
+// l', m', h', the steps in column order. The bits depend on the query, the row's M bytes and cb8 only.
+// Refusals (nothing is launched, one code per rule): -143 codes, queries, live, cand or cb8 null; -144 D % 32;
+// -145 D > 2048; -146 D % M; -147 M % 16; -148 M outside 16..HZ_SEARCH_PQ_MAX_M; -149 (D / M) % 8; -150 ldc < M or
+// ldc % 16; -151 N < 1; -152 Q outside 1..HZ_INDEX_SELF_MAX_Q; -153 k outside 1..HZ_SEARCH_MAX_K; -154 codes, queries
+// or cb8 not 16-B, cand not 8-B or live not 4-B aligned; -155 live_bytes < 4 * ceil(N / 32); -156 cand_bytes <
+// ntile * Q * k * 8; -157 cb8_bytes < 512 * D.
+typedef struct HzSearchPqBatchParams {
+  const unsigned char* codes;    // uint8 [N][ldc], 16-B aligned rows (ldc in BYTES, ldc % 16 == 0), ldc >= M
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5 (required)
+  unsigned long long* cand;      // scratch [ntile][Q][k] keys
+  float* out_score;              // fp32 [Q][k]  (HZ_K_SEARCH_MERGEN only)
+  int* out_id;                   // int32 [Q][k] (HZ_K_SEARCH_MERGEN only)
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  unsigned long long cand_bytes; // bytes of `cand`, at least hz_search_self_scratch_bytes(N, Q, k)
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launchers: ceil(N / HZ_SEARCH_TILE)
+  int pad_[2];                   // HzSearchSelfParams' skip_self and pad_: unused
+  const unsigned short* cb8;     // device bf16 [D / 8][256][8], 16-B aligned
+  unsigned long long cb8_bytes;  // bytes of `cb8`, at least 512 * D
+  int M, pad2_;
+} HzSearchPqBatchParams;
+#ifdef __cplusplus
+static_assert(offsetof(HzSearchPqBatchParams, cb8) == sizeof(HzSearchBatchParams) &&
+                  offsetof(HzSearchPqBatchParams, cand) == offsetof(HzSearchBatchParams, cand) &&
+                  offsetof(HzSearchPqBatchParams, out_id) == offsetof(HzSearchBatchParams, out_id) &&
+                  offsetof(HzSearchPqBatchParams, cand_bytes) == offsetof(HzSearchBatchParams, cand_bytes) &&
+                  offsetof(HzSearchPqBatchParams, k) == offsetof(HzSearchBatchParams, k) &&
+                  offsetof(HzSearchPqBatchParams, ntile) == offsetof(HzSearchBatchParams, ntile),
+              "HZ_K_SEARCH_MERGEN reads a pq batch block through HzSearchSelfParams");
+#endif
+int hz_search_pqxscan_launch(const HzSearchPqBatchParams* p, hipStream_t st);
+// rescore against the codebook (HZ_K_SEARCH_PQRESCORE): the second stage of a bulk search over a pq8
+// index WITHOUT bf16 rows. Workgroup q recomputes HZ_K_SEARCH_PQSCAN's own score of query q for each of the R rows
+// `in_id` names (a slot is real iff (unsigned)id < (unsigned)N), one thread per candidate, from the fp32 codebook and
+// the row's codes: per m ascending ONE fmaf chain over j = 0 .. dsub-1 from +0 of q[m*dsub + j] * codebook[m][c][j]
+// (a table entry's bits), the M results added with plain fp32 additions from +0 (contraction off). It ranks by the
+// order rule and writes the best k scores and ids in HZ_K_SEARCH_RESCORE's layout (-inf / -1 past the real
+// candidates), and out_last[q] = in_score[q][R - 1], stage one's score of the R-th candidate.
+// Refusals (HZ_K_SEARCH_RESCOREN's rules under their own codes): -158 D, M or ldc (the pq shape rules; ldc < M or
+// ldc % 16); -159 N < 1; -160 Q outside 1..HZ_SEARCH_SELF_MAX_Q; -161 R outside 1..HZ_SEARCH_MAX_K; -162 k outside
+// 1..R; -163 a null pointer; -164 codes, codebook or queries not 16-B aligned or in_* / out_* not 4-B aligned.
+typedef struct HzSearchPqRescoreParams {
+  const unsigned char* codes;    // uint8 [N][ldc], ldc in bytes
+  const float* codebook;         // device fp32 [M][256][D / M], 16-B aligned
+  const float* queries;          // fp32 [Q][D], 16-B aligned
+  const int* in_id;              // int32 [Q][R], -1 in unused slots
+  const float* in_score;         // fp32 [Q][R]: stage one's scores, best first
+  float* out_score;              // fp32 [Q][k]
+  int* out_id;                   // int32 [Q][k]
+  float* out_last;               // fp32 [Q]
+  int N, D, M, Q, R, k, ldc, pad_;
+} HzSearchPqRescoreParams;
+int hz_search_pqrescore_launch(const HzSearchPqRescoreParams* p, hipStream_t st);
 // nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
 // of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
 // of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
@@ -944,7 +1012,8 @@ int hz_index_add_pr(void* idx, const unsigned char* codes, const unsigned short*
                     const unsigned* tags_or_null, long long* first_id_out);
 int hz_index_read_state_p(void* idx, unsigned char* codes_out, unsigned* tags_out, unsigned* live_out, long long n);
 int hz_index_read_codebook(void* idx, float* codebook_out);  // fp32 [M][256][dsub]; -26 on any other dtype
-// out[8] = {M, dsub, codebook bytes, table scratch bytes per context, the span of a Q = 1 scan, 0, 0, 0}; zeros
+// out[8] = {M, dsub, codebook bytes, table scratch bytes per context, the span of a Q = 1 scan, the bytes of the bf16
+// table of hz_index_search_batch_pq (0: dsub % 8 != 0), 1 if that call serves this index, 0}; zeros
 // unless the index holds pq8 rows
 int hz_index_describe4(void* idx, uint64_t* out);
 // neighbours of stored rows (a plain bf16 index, versions 1 and 2, dim % 32 == 0): the k nearest live
@@ -974,6 +1043,18 @@ int hz_index_neighbors_max(void* idx, int set);
 // -45: dim % 32 (hz_index_last_error names the value in each case).
 int hz_index_search_batch(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                           float* out_stage1_last);
+// bulk search over a pq8 index (versions 10 and 11, dsub % 8 == 0, dim % 32 == 0): hz_index_search_batch's
+// arguments and outputs. open3 builds the bf16 table of HZ_K_SEARCH_PQXSCAN from the codebook (a plain loop, round to
+// nearest even) and uploads it once per index. Version 10 replays H2D of the queries, HZ_K_SEARCH_PQXSCAN at k = R,
+// HZ_K_SEARCH_MERGEN, HZ_K_SEARCH_PQRESCORE (R -> k: the bits and the order of hz_index_search on this index) and three
+// D2H; version 11 the same with HZ_K_SEARCH_RESCOREN against the bf16 rows (device or pinned host memory) as stage two,
+// the answer of hz_index_search3 with refine = R over these candidates. Captured per (Q, k, R) under
+// hz_index_search_batch's rules, with its buffers, its candidate scratch and hz_index_neighbors_max.
+// -4: Q outside 1..the maximum; -5: k; -46: not a pq8 index; -47: dsub % 8; -48: dim % 32; -49: R outside
+// k..HZ_SEARCH_MAX_K (hz_index_last_error names the index or the value in each case). hz_index_search_batch keeps
+// refusing a pq8 index (-44).
+int hz_index_search_batch_pq(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                             float* out_stage1_last);
 // clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
 // context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
 // and grown on demand (a call that needs no more than an earlier one allocates nothing).
@@ -1205,7 +1286,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_PQLUT, 46, HzSearchPqLutParams, hz_search_pqlut_op, SEARCH)    \
   X(SEARCH_PQSCAN, 47, HzSearchPqParams, hz_search_pqscan_op, SEARCH)  \
   X(SEARCH_PQASSIGN, 48, HzSearchPqAssignParams, hz_search_pqassign_op, SEARCH) \
-  X(SEARCH_PQUPDATE, 49, HzSearchPqUpdateParams, hz_search_pqupdate_op, SEARCH)
+  X(SEARCH_PQUPDATE, 49, HzSearchPqUpdateParams, hz_search_pqupdate_op, SEARCH) \
+  X(SEARCH_PQXSCAN, 50, HzSearchPqBatchParams, hz_search_pqxscan_op, SEARCH) \
+  X(SEARCH_PQRESCORE, 51, HzSearchPqRescoreParams, hz_search_pqrescore_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

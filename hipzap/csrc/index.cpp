@@ -116,6 +116,7 @@ struct Ctx {
   char* bmid_dev = nullptr;
   char* bout_dev = nullptr;
   char* bout_host = nullptr;
+  float* blast_dev = nullptr;  // pq bulk search on a version-10 index only: stage one's R-th score per query [SELF_MAX_Q]
   // clustering only (hz_index_assign / hz_index_cmean), device memory allocated on first use and grown on demand:
   // centroids bf16 [C][dim]; live AND mask, cap / 8 bytes; lists int32 then scores fp32, [scan rows] each; the
   // members int32 [M]; seg_off int32 [C + 1]; the fp32 centroids [C][dim]
@@ -123,7 +124,7 @@ struct Ctx {
   void* cl[kClBufs] = {};
   uint64_t cl_bytes[kClBufs] = {};
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
-  // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0)
+  // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
@@ -163,6 +164,7 @@ struct Index {
   int pq_m = 0;                       // sub-spaces = bytes per row; dsub = dim / pq_m
   float* codebook = nullptr;          // device fp32 [pq_m][256][dim / pq_m]
   std::vector<float> codebook_host;   // its mirror
+  unsigned short* cb8 = nullptr;      // device bf16 [dim / 8][256][8]: the pq bulk search's table (dsub % 8 == 0), else null
   unsigned short* rows = nullptr;     // bf16 [cap][dim], or uint8 [cap][dim] of an fp8 index
   float* scales = nullptr;            // device, cap floats (fp8 only)
   bool rescore = false;               // a version-4, 7 or 9 file: `rrows` beside the fp8 or sign-bit rows
@@ -206,6 +208,7 @@ struct Index {
       if (c->bq_dev) (void)hipFree(c->bq_dev);
       if (c->bmid_dev) (void)hipFree(c->bmid_dev);
       if (c->bout_dev) (void)hipFree(c->bout_dev);
+      if (c->blast_dev) (void)hipFree(c->blast_dev);
       for (void* b : c->cl)
         if (b) (void)hipFree(b);
       if (c->st) (void)hipStreamDestroy(c->st);
@@ -217,6 +220,7 @@ struct Index {
     if (scales) (void)hipFree(scales);
     if (centroids) (void)hipFree(centroids);
     if (codebook) (void)hipFree(codebook);
+    if (cb8) (void)hipFree(cb8);
     if (ivf_tables) (void)hipFree(ivf_tables);
   }
 
@@ -229,6 +233,7 @@ struct Index {
   uint64_t rowb() const { return pq ? (uint64_t)pq_m : bin ? h.dim / 8 : fp8 ? h.dim : h.dim * 2ull; }  // bytes per stored row
   const char* dtype_name() const { return pq ? "pq8" : bin ? "bin_sign" : fp8 ? "fp8_e4m3" : "bf16"; }
   uint64_t codebook_bytes() const { return pq ? 256ull * h.dim * 4 : 0; }  // pq_m * 256 * (dim / pq_m) floats
+  uint64_t cb8_bytes() const { return cb8 ? 512ull * h.dim : 0; }
   uint64_t lut_bytes() const { return pq ? (uint64_t)HZ_SEARCH_MAX_Q * pq_m * 1024 : 0; }  // per context
   // what the by-name refusals call a quantised index without lists
   const char* quant_name() const { return pq ? "a pq8 index" : bin ? "a bin_sign index" : "an fp8_e4m3 index"; }
@@ -349,7 +354,7 @@ struct Index {
     if (!need) return false;
     if (need <= c.ncand_bytes) return true;
     for (auto it = c.progs.begin(); it != c.progs.end();) {
-      if (std::get<2>(it->first) == 3 || std::get<2>(it->first) == 4) {
+      if (std::get<2>(it->first) >= 3) {  // neighbours, bulk search, pq bulk search
         hz_prog_destroy(it->second);
         it = c.progs.erase(it);
       } else {
@@ -366,23 +371,7 @@ struct Index {
   // The bulk-search program of (Q, k, R) (the caller holds c.mu): H2D of the queries, batch scan and merge at k = R
   // into bmid_dev, rescore of those ids against `rows` into bout_dev, D2H of the scores, the ids and stage one's scores.
   HzProgram batch_program(Ctx& c, int Q, int k, int R, bool* fresh) {
-    const size_t qbytes = (size_t)HZ_INDEX_SELF_MAX_Q * h.dim * 4;
-    if (!c.bq_host) {
-      bool ok = hipHostMalloc(reinterpret_cast<void**>(&c.bq_host), qbytes, hipHostMallocDefault) == hipSuccess;
-      ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c.bout_host), 3 * kSelfOutHalf, hipHostMallocDefault) == hipSuccess;
-      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bq_dev), qbytes) == hipSuccess;
-      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bmid_dev), 2 * kSelfOutHalf) == hipSuccess;
-      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bout_dev), 2 * kSelfOutHalf) == hipSuccess;
-      if (!ok) {
-        if (c.bq_host) (void)hipHostFree(c.bq_host);
-        if (c.bout_host) (void)hipHostFree(c.bout_host);
-        if (c.bq_dev) (void)hipFree(c.bq_dev);
-        if (c.bmid_dev) (void)hipFree(c.bmid_dev);
-        if (c.bout_dev) (void)hipFree(c.bout_dev);
-        c.bq_host = c.bq_dev = nullptr, c.bout_host = c.bmid_dev = c.bout_dev = nullptr;
-        return nullptr;
-      }
-    }
+    if (!batch_buffers(c)) return nullptr;
     if (!self_scratch(c, Q, R)) return nullptr;
     const auto key = std::make_tuple(Q, k, 4, R, 0);
     auto it = c.progs.find(key);
@@ -422,6 +411,93 @@ struct Index {
     }
     c.progs[key] = g;
     return g;
+  }
+
+  // The bulk-search program of a pq8 index for (Q, k, R) (the caller holds c.mu): H2D of the queries,
+  // HZ_K_SEARCH_PQXSCAN and the merge at k = R into bmid_dev, then stage two into bout_dev -- HZ_K_SEARCH_PQRESCORE
+  // against the codebook on a version-10 index (it also leaves stage one's R-th score per query in blast_dev),
+  // HZ_K_SEARCH_RESCOREN against the bf16 rows on a version-11 one -- and three D2H: the scores, the ids and stage
+  // one's last scores [Q] (version 10) or all of its scores [Q][R] (version 11).
+  HzProgram pq_batch_program(Ctx& c, int Q, int k, int R, bool* fresh) {
+    if (!batch_buffers(c)) return nullptr;
+    if (!rescore && !c.blast_dev && hipMalloc(reinterpret_cast<void**>(&c.blast_dev), (size_t)HZ_INDEX_SELF_MAX_Q * 4) != hipSuccess) {
+      c.blast_dev = nullptr;
+      return nullptr;
+    }
+    if (!self_scratch(c, Q, R)) return nullptr;
+    const auto key = std::make_tuple(Q, k, 5, R, 0);
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    HzSearchPqBatchParams p{};
+    p.codes = reinterpret_cast<const unsigned char*>(rows);
+    p.queries = c.bq_dev;
+    p.live = live;
+    p.cand = c.ncand;
+    p.out_score = reinterpret_cast<float*>(c.bmid_dev);
+    p.out_id = reinterpret_cast<int*>(c.bmid_dev + kSelfOutHalf);
+    p.live_bytes = cap / 8;
+    p.cand_bytes = c.ncand_bytes;
+    p.N = (int)scan_rows();
+    p.D = (int)h.dim, p.ldc = p.M = pq_m;
+    p.Q = Q, p.k = R;
+    p.cb8 = cb8, p.cb8_bytes = 512ull * h.dim;
+    float* out_score = reinterpret_cast<float*>(c.bout_dev);
+    int* out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    HzProgram g = hz_prog_create();
+    const size_t qk = (size_t)Q * k * 4;
+    int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_PQXSCAN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, sizeof(p), 0);  // it begins with that block: hipzap.h
+    if (rescore) {
+      HzSearchRescoreParams rp{};
+      rp.rows = rrows_dev;
+      rp.queries = c.bq_dev;
+      rp.in_id = p.out_id;
+      rp.out_score = out_score, rp.out_id = out_id;
+      rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
+      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
+    } else {
+      HzSearchPqRescoreParams rp{};
+      rp.codes = p.codes, rp.codebook = codebook, rp.queries = c.bq_dev;
+      rp.in_id = p.out_id, rp.in_score = p.out_score;
+      rp.out_score = out_score, rp.out_id = out_id;
+      rp.out_last = c.blast_dev;
+      rp.N = p.N, rp.D = p.D, rp.M = rp.ldc = pq_m, rp.Q = Q, rp.R = R, rp.k = k;
+      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_PQRESCORE, &rp, sizeof(rp), 0);
+    }
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
+    if (!rc) rc = rescore ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0)
+                          : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0);
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
+  // A context's bulk-search buffers, allocated on first use (the caller holds c.mu).
+  bool batch_buffers(Ctx& c) {
+    const size_t qbytes = (size_t)HZ_INDEX_SELF_MAX_Q * h.dim * 4;
+    if (!c.bq_host) {
+      bool ok = hipHostMalloc(reinterpret_cast<void**>(&c.bq_host), qbytes, hipHostMallocDefault) == hipSuccess;
+      ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c.bout_host), 3 * kSelfOutHalf, hipHostMallocDefault) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bq_dev), qbytes) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bmid_dev), 2 * kSelfOutHalf) == hipSuccess;
+      ok = ok && hipMalloc(reinterpret_cast<void**>(&c.bout_dev), 2 * kSelfOutHalf) == hipSuccess;
+      if (!ok) {
+        if (c.bq_host) (void)hipHostFree(c.bq_host);
+        if (c.bout_host) (void)hipHostFree(c.bout_host);
+        if (c.bq_dev) (void)hipFree(c.bq_dev);
+        if (c.bmid_dev) (void)hipFree(c.bmid_dev);
+        if (c.bout_dev) (void)hipFree(c.bout_dev);
+        c.bq_host = c.bq_dev = nullptr, c.bout_host = c.bmid_dev = c.bout_dev = nullptr;
+        return false;
+      }
+    }
+    return true;
   }
 
   // The neighbours program of (n, k, skip_self) (the caller holds c.mu): H2D of the ids, self scan, merge, two D2H.
@@ -896,6 +972,24 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     if (hipMalloc(reinterpret_cast<void**>(&idx->codebook), cb_len) != hipSuccess ||
         hipMemcpy(idx->codebook, idx->codebook_host.data(), cb_len, hipMemcpyHostToDevice) != hipSuccess)
       return fail("index: codebook upload failed");
+    const uint64_t dsub = pq_u[2];
+    // the bulk search's table (hipzap.h HZ_K_SEARCH_PQXSCAN): bf16, round to nearest even, by 8-column chunk -- the
+    // integer form of hipzap.search.to_bf16, the same bytes for every FINITE value (the writers refuse a non-finite
+    // codebook; neither form has a rule for NaN)
+    if (dsub % 8 == 0) {
+      std::vector<unsigned short> t((size_t)256 * h.dim);
+      for (uint64_t g = 0; g < h.dim / 8; ++g)
+        for (uint64_t code = 0; code < 256; ++code)
+          for (uint64_t j = 0; j < 8; ++j) {
+            const uint64_t m = 8 * g / dsub;
+            uint32_t u;
+            std::memcpy(&u, &idx->codebook_host[(m * 256 + code) * dsub + 8 * g - m * dsub + j], 4);
+            t[(g * 256 + code) * 8 + j] = (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+          }
+      if (hipMalloc(reinterpret_cast<void**>(&idx->cb8), t.size() * 2) != hipSuccess ||
+          hipMemcpy(idx->cb8, t.data(), t.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
+        return fail("index: upload of the bf16 codebook table failed");
+    }
   }
   if (rescore && idx->rescore_host) {  // the file's block straight into the pinned rows
     const int rfd = open(path, O_RDONLY | O_CLOEXEC);
@@ -927,13 +1021,14 @@ int hz_index_describe(void* h, uint64_t* out) {
   AllLocked all(*x);
   uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4 + (x->fp8 ? x->cap * 4 : 0);
   if (!x->rescore_host) dev += x->rescore_bytes();
-  dev += x->codebook_bytes();
+  dev += x->codebook_bytes() + x->cb8_bytes();
   for (auto& c : x->ctx) {
     progs += c->progs.size();
     dev += x->lut_bytes();
     dev += c->cand_bytes + kFiltBytes + (uint64_t)HZ_SEARCH_MAX_Q * x->h.dim * 4 + 2 * kOutHalf + (c->mid_dev ? 2 * kOutHalf : 0);
     dev += c->ncand_bytes + (c->nid_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 + 2 * kSelfOutHalf : 0);  // neighbours, once used
     dev += c->bq_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * x->h.dim * 4 + 4 * kSelfOutHalf : 0;  // bulk search, once used
+    dev += c->blast_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 : 0;  // pq bulk search on a version-10 index, once used
     for (const uint64_t b : c->cl_bytes) dev += b;  // clustering, once used
   }
   const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
@@ -968,6 +1063,7 @@ int hz_index_describe4(void* h, uint64_t* out) {
   uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (x->pq) {
     v[0] = (uint64_t)x->pq_m, v[1] = x->h.dim / (uint64_t)x->pq_m, v[2] = x->codebook_bytes(), v[3] = x->lut_bytes();
+    v[5] = x->cb8_bytes(), v[6] = x->cb8 && x->h.dim % 32 == 0 ? 1u : 0u;
     if (hipSetDevice(x->device) == hipSuccess) v[4] = (uint64_t)hz_search_pq_span((long long)x->scan_rows(), 1, x->pq_m);
   }
   std::memcpy(out, v, sizeof(v));
@@ -1167,6 +1263,60 @@ int hz_index_search_batch(void* h, int ctx, const float* queries, int Q, int k, 
   std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
   const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);  // [Q][R], best first
   for (int q = 0; q < Q; ++q) out_stage1_last[q] = s1[(size_t)q * R + R - 1];
+  if (fresh) {
+    rc = hz_prog_capture(g, c.st);
+    if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  }
+  return rc;
+}
+
+int hz_index_search_batch_pq(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                             float* out_stage1_last) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (!x->pq) {
+    g_err = std::string("index: search_batch_pq is built for pq8 indexes (versions 10 and 11), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->fp8 || x->bin ? x->quant_name() : "a bf16 index") +
+            " of version " + std::to_string(x->h.version);
+    return -46;
+  }
+  if (!x->cb8) {
+    g_err = "index: search_batch_pq needs dsub % 8 == 0 (a 16-byte chunk of the bf16 table lies in one sub-space), got dsub = " +
+            std::to_string(x->h.dim / (uint64_t)x->pq_m);
+    return -47;
+  }
+  if (x->h.dim % 32) {
+    g_err = "index: search_batch_pq needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -48;
+  }
+  if (k < 1 || k > HZ_SEARCH_MAX_K) {
+    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
+    return -5;
+  }
+  if (R < k || R > HZ_SEARCH_MAX_K) {
+    g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " +
+            std::to_string(k);
+    return -49;
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
+  if (Q < 1 || Q > x->self_max) {
+    g_err = "index: search_batch_pq takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
+    return -4;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->pq_batch_program(c, Q, k, R, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
+  if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  if (rc) return rc;
+  std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
+  std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
+  const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);  // version 11: [Q][R], best first; 10: [Q]
+  for (int q = 0; q < Q; ++q) out_stage1_last[q] = x->rescore ? s1[(size_t)q * R + R - 1] : s1[q];
   if (fresh) {
     rc = hz_prog_capture(g, c.st);
     if (!rc) rc = (int)hipStreamSynchronize(c.st);

@@ -504,6 +504,14 @@ extern "C" __attribute__((weak)) int hz_search_pqupdate_launch(const HzSearchPqU
 static int hz_search_pqupdate_op(const HzSearchPqUpdateParams* p, hipStream_t st) {
   return hz_search_pqupdate_launch ? hz_search_pqupdate_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_pqxscan_launch(const HzSearchPqBatchParams* p, hipStream_t st);
+static int hz_search_pqxscan_op(const HzSearchPqBatchParams* p, hipStream_t st) {
+  return hz_search_pqxscan_launch ? hz_search_pqxscan_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_pqrescore_launch(const HzSearchPqRescoreParams* p, hipStream_t st);
+static int hz_search_pqrescore_op(const HzSearchPqRescoreParams* p, hipStream_t st) {
+  return hz_search_pqrescore_launch ? hz_search_pqrescore_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -19,6 +19,9 @@ same block.
 ``HZ_K_SEARCH_XSCAN`` (``BatchScanParams``: that block with device fp32 ``queries`` where ``qid`` is) is the self scan
 over external queries, each split into three bf16 terms; ``HZ_K_SEARCH_MERGEN`` takes its block as it stands and
 ``HZ_K_SEARCH_RESCOREN`` is the rescore (``RescoreParams``) for any number of queries.
+``HZ_K_SEARCH_PQXSCAN`` (``PqBatchScanParams``: the batch block over uint8 code rows, ``ldc`` in bytes, plus the bf16
+table ``cb8`` of :func:`hipzap.search.pq_table_bf16`) is the batch scan over product-quantised rows, each MFMA fragment
+gathered from that table by a code byte; ``HZ_K_SEARCH_PQRESCORE`` (``PqRescoreParams``) re-scores its candidates with ``HZ_K_SEARCH_PQSCAN``'s bits.
 ``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
 ``HZ_K_SEARCH_PQLUT`` (``PqLutParams``) writes each query's table of inner products with the 256 sub-centroids of every
@@ -196,6 +199,28 @@ class BatchScanParams(C.Structure):
         return SelfScanParams.from_buffer_copy(self)
 
 
+@N.params_of("HZ_K_SEARCH_PQXSCAN")
+class PqBatchScanParams(C.Structure):
+    """HzSearchPqBatchParams: the fields of ``BatchScanParams`` with ``codes`` (uint8 [N][ldc], ``ldc`` in bytes) where
+    ``corpus`` is, then ``cb8`` (device bf16 [D / 8][256][8]), ``cb8_bytes`` and ``M``."""
+    _fields_ = [("codes", C.c_void_p)] + BatchScanParams._fields_[1:] + [("cb8", C.c_void_p), ("cb8_bytes", C.c_uint64),
+                                                                         ("M", C.c_int), ("pad2_", C.c_int)]
+
+    def merge_params(self) -> SelfScanParams:
+        """The block as ``HZ_K_SEARCH_MERGEN`` reads it."""
+        return SelfScanParams.from_buffer_copy(self)
+
+
+@N.params_of("HZ_K_SEARCH_PQRESCORE")
+class PqRescoreParams(C.Structure):
+    """HzSearchPqRescoreParams: ``codes`` uint8 [N][ldc], ``codebook`` fp32 [M][256][D / M], ``queries`` fp32 [Q][D],
+    ``in_id`` / ``in_score`` [Q][R] (a merge's outputs), the outputs [Q][k] and ``out_last`` fp32 [Q]."""
+    _fields_ = [("codes", C.c_void_p), ("codebook", C.c_void_p), ("queries", C.c_void_p), ("in_id", C.c_void_p),
+                ("in_score", C.c_void_p), ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("out_last", C.c_void_p),
+                ("N", C.c_int), ("D", C.c_int), ("M", C.c_int), ("Q", C.c_int), ("R", C.c_int), ("k", C.c_int),
+                ("ldc", C.c_int), ("pad_", C.c_int)]
+
+
 @N.params_of("HZ_K_SEARCH_ASSIGN")
 class AssignParams(C.Structure):
     """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
@@ -226,6 +251,9 @@ def _sigs(lib):
     N._sig(lib, "hz_search_xscan_launch", C.c_int, C.POINTER(BatchScanParams), P)
     N._sig(lib, "hz_search_rescoren_launch", C.c_int, C.POINTER(RescoreParams), P)
     N._sig(lib, "hz_index_search_batch", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
+    N._sig(lib, "hz_search_pqxscan_launch", C.c_int, C.POINTER(PqBatchScanParams), P)
+    N._sig(lib, "hz_search_pqrescore_launch", C.c_int, C.POINTER(PqRescoreParams), P)
+    N._sig(lib, "hz_index_search_batch_pq", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_neighbors", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_neighbors_max", C.c_int, P, C.c_int)
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -460,6 +488,22 @@ def launch_batch(prm: BatchScanParams, stream: int = 0) -> tuple:
         return rc, None
     mp = prm.merge_params()
     return rc, lib.hz_search_mergen_launch(C.byref(mp), stream)
+
+
+def launch_pq_batch(prm: PqBatchScanParams, stream: int = 0) -> tuple:
+    """The pq batch scan then ``HZ_K_SEARCH_MERGEN`` over the same block on ``stream``: (scan code, merge code); no merge
+    after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_pqxscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    mp = prm.merge_params()
+    return rc, lib.hz_search_mergen_launch(C.byref(mp), stream)
+
+
+def launch_pq_rescore(prm: PqRescoreParams, stream: int = 0) -> int:
+    """The codebook rescore (``HZ_K_SEARCH_PQRESCORE``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_pqrescore_launch(C.byref(prm), stream))
 
 
 def launch_rescore_n(prm: RescoreParams, stream: int = 0) -> int:
