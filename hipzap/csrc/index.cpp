@@ -368,68 +368,26 @@ struct Index {
     return true;
   }
 
-  // The bulk-search program of (Q, k, R) (the caller holds c.mu): H2D of the queries, batch scan and merge at k = R
-  // into bmid_dev, rescore of those ids against `rows` into bout_dev, D2H of the scores, the ids and stage one's scores.
-  HzProgram batch_program(Ctx& c, int Q, int k, int R, bool* fresh) {
+  // The bulk-search program of (Q, k, R) (the caller holds c.mu): H2D of the queries, the batch scan
+  // and the merge at k = R into bmid_dev, stage two of those ids into bout_dev, and three D2H: the scores, the ids and
+  // stage one's scores. What varies with the index:
+  //   plain bf16 (key 4): HZ_K_SEARCH_XSCAN; HZ_K_SEARCH_RESCOREN against `rows`; all of stage one's scores [Q][R].
+  //   pq8 (`pq`, key 5):  HZ_K_SEARCH_PQXSCAN; on a version-11 index HZ_K_SEARCH_RESCOREN against the bf16 rows and
+  //     [Q][R] likewise, on a version-10 one HZ_K_SEARCH_PQRESCORE against the codebook, which also leaves stage
+  //     one's R-th score per query in blast_dev: [Q].
+  HzProgram batch_program(Ctx& c, int Q, int k, int R, bool pq, bool* fresh) {
     if (!batch_buffers(c)) return nullptr;
-    if (!self_scratch(c, Q, R)) return nullptr;
-    const auto key = std::make_tuple(Q, k, 4, R, 0);
-    auto it = c.progs.find(key);
-    *fresh = it == c.progs.end();
-    if (!*fresh) return it->second;
-    HzSearchBatchParams p{};
-    p.corpus = rows;
-    p.queries = c.bq_dev;
-    p.live = live;
-    p.cand = c.ncand;
-    p.out_score = reinterpret_cast<float*>(c.bmid_dev);
-    p.out_id = reinterpret_cast<int*>(c.bmid_dev + kSelfOutHalf);
-    p.live_bytes = cap / 8;
-    p.cand_bytes = c.ncand_bytes;
-    p.N = (int)scan_rows();
-    p.D = p.ldc = (int)h.dim;
-    p.Q = Q, p.k = R;
-    HzSearchRescoreParams rp{};
-    rp.rows = rows;
-    rp.queries = c.bq_dev;
-    rp.in_id = p.out_id;
-    rp.out_score = reinterpret_cast<float*>(c.bout_dev);
-    rp.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
-    rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
-    HzProgram g = hz_prog_create();
-    const size_t qk = (size_t)Q * k * 4;
-    int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
-    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_XSCAN, &p, sizeof(p), 0);
-    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, sizeof(p), 0);  // the same layout: hipzap.h
-    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
-    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
-    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
-    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
-    if (rc) {
-      hz_prog_destroy(g);
-      return nullptr;
-    }
-    c.progs[key] = g;
-    return g;
-  }
-
-  // The bulk-search program of a pq8 index for (Q, k, R) (the caller holds c.mu): H2D of the queries,
-  // HZ_K_SEARCH_PQXSCAN and the merge at k = R into bmid_dev, then stage two into bout_dev -- HZ_K_SEARCH_PQRESCORE
-  // against the codebook on a version-10 index (it also leaves stage one's R-th score per query in blast_dev),
-  // HZ_K_SEARCH_RESCOREN against the bf16 rows on a version-11 one -- and three D2H: the scores, the ids and stage
-  // one's last scores [Q] (version 10) or all of its scores [Q][R] (version 11).
-  HzProgram pq_batch_program(Ctx& c, int Q, int k, int R, bool* fresh) {
-    if (!batch_buffers(c)) return nullptr;
-    if (!rescore && !c.blast_dev && hipMalloc(reinterpret_cast<void**>(&c.blast_dev), (size_t)HZ_INDEX_SELF_MAX_Q * 4) != hipSuccess) {
+    const bool by_codebook = pq && !rescore;
+    if (by_codebook && !c.blast_dev && hipMalloc(reinterpret_cast<void**>(&c.blast_dev), (size_t)HZ_INDEX_SELF_MAX_Q * 4) != hipSuccess) {
       c.blast_dev = nullptr;
       return nullptr;
     }
     if (!self_scratch(c, Q, R)) return nullptr;
-    const auto key = std::make_tuple(Q, k, 5, R, 0);
+    const auto key = std::make_tuple(Q, k, pq ? 5 : 4, R, 0);
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
-    HzSearchPqBatchParams p{};
+    HzSearchPqBatchParams p{};  // it begins with HzSearchBatchParams' layout (hipzap.h): the plain scan takes that part
     p.codes = reinterpret_cast<const unsigned char*>(rows);
     p.queries = c.bq_dev;
     p.live = live;
@@ -439,37 +397,34 @@ struct Index {
     p.live_bytes = cap / 8;
     p.cand_bytes = c.ncand_bytes;
     p.N = (int)scan_rows();
-    p.D = (int)h.dim, p.ldc = p.M = pq_m;
+    p.D = (int)h.dim, p.ldc = pq ? pq_m : p.D;
     p.Q = Q, p.k = R;
-    p.cb8 = cb8, p.cb8_bytes = 512ull * h.dim;
-    float* out_score = reinterpret_cast<float*>(c.bout_dev);
-    int* out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    if (pq) p.cb8 = cb8, p.cb8_bytes = 512ull * h.dim, p.M = pq_m;
+    HzSearchRescoreParams rp{};
+    rp.rows = pq ? rrows_dev : rows;
+    rp.queries = c.bq_dev;
+    rp.in_id = p.out_id;
+    rp.out_score = reinterpret_cast<float*>(c.bout_dev);
+    rp.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
+    HzSearchPqRescoreParams cp{};
+    cp.codes = p.codes, cp.codebook = codebook, cp.queries = c.bq_dev;
+    cp.in_id = p.out_id, cp.in_score = p.out_score;
+    cp.out_score = rp.out_score, cp.out_id = rp.out_id;
+    cp.out_last = c.blast_dev;
+    cp.N = p.N, cp.D = p.D, cp.M = cp.ldc = pq_m, cp.Q = Q, cp.R = R, cp.k = k;
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4;
     int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
-    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_PQXSCAN, &p, sizeof(p), 0);
-    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, sizeof(p), 0);  // it begins with that block: hipzap.h
-    if (rescore) {
-      HzSearchRescoreParams rp{};
-      rp.rows = rrows_dev;
-      rp.queries = c.bq_dev;
-      rp.in_id = p.out_id;
-      rp.out_score = out_score, rp.out_id = out_id;
-      rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
-      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
-    } else {
-      HzSearchPqRescoreParams rp{};
-      rp.codes = p.codes, rp.codebook = codebook, rp.queries = c.bq_dev;
-      rp.in_id = p.out_id, rp.in_score = p.out_score;
-      rp.out_score = out_score, rp.out_id = out_id;
-      rp.out_last = c.blast_dev;
-      rp.N = p.N, rp.D = p.D, rp.M = rp.ldc = pq_m, rp.Q = Q, rp.R = R, rp.k = k;
-      if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_PQRESCORE, &rp, sizeof(rp), 0);
-    }
+    const size_t pbytes = pq ? sizeof(p) : sizeof(HzSearchBatchParams);
+    if (!rc) rc = hz_prog_add_kernel(g, pq ? HZ_K_SEARCH_PQXSCAN : HZ_K_SEARCH_XSCAN, &p, pbytes, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, pbytes, 0);  // the same layout: hipzap.h
+    if (!rc) rc = by_codebook ? hz_prog_add_kernel(g, HZ_K_SEARCH_PQRESCORE, &cp, sizeof(cp), 0)
+                              : hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
-    if (!rc) rc = rescore ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0)
-                          : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0);
+    if (!rc) rc = by_codebook ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0)
+                              : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
     if (rc) {
       hz_prog_destroy(g);
       return nullptr;
@@ -1161,6 +1116,101 @@ int hz_index_probes(void* h, int ctx, const float* queries, int Q, int nprobe, i
   return rc;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The common tail of the calls that replay a captured program (the caller holds c.mu and has filled the program's host
+// inputs): run a fresh program or replay a captured one, synchronise, let `copy_out` take the results from the
+// program's host outputs, then capture a fresh program for the calls to come.
+template <class F>
+int run_program(Ctx& c, HzProgram g, bool fresh, F copy_out) {
+  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
+  if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  if (rc) return rc;
+  copy_out();
+  if (fresh) {
+    rc = hz_prog_capture(g, c.st);
+    if (!rc) rc = (int)hipStreamSynchronize(c.st);
+  }
+  return rc;
+}
+
+// which index each bulk-search call serves: 0, or the refusal with g_err set
+int batch_index_check(const Index* x) {
+  if (x->fp8 || x->ivf || x->bin || x->pq) {
+    g_err = std::string("index: search_batch is built for plain bf16 indexes (versions 1 and 2), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->quant_name()) + " of version " +
+            std::to_string(x->h.version);
+    return -44;
+  }
+  if (x->h.dim % 32) {
+    g_err = "index: search_batch needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -45;
+  }
+  return 0;
+}
+int pq_batch_index_check(const Index* x) {
+  if (!x->pq) {
+    g_err = std::string("index: search_batch_pq is built for pq8 indexes (versions 10 and 11), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->fp8 || x->bin ? x->quant_name() : "a bf16 index") +
+            " of version " + std::to_string(x->h.version);
+    return -46;
+  }
+  if (!x->cb8) {
+    g_err = "index: search_batch_pq needs dsub % 8 == 0 (a 16-byte chunk of the bf16 table lies in one sub-space), got dsub = " +
+            std::to_string(x->h.dim / (uint64_t)x->pq_m);
+    return -47;
+  }
+  if (x->h.dim % 32) {
+    g_err = "index: search_batch_pq needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -48;
+  }
+  return 0;
+}
+
+// hz_index_search_batch (pq false) and hz_index_search_batch_pq (pq true): the argument checks, the program of
+// (Q, k, R) and its run. A bad R is -28 for the first and -49 for the second.
+int bulk_search(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                float* out_stage1_last, bool pq) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (const int rc = pq ? pq_batch_index_check(x) : batch_index_check(x)) return rc;
+  if (k < 1 || k > HZ_SEARCH_MAX_K) {
+    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
+    return -5;
+  }
+  if (R < k || R > HZ_SEARCH_MAX_K) {
+    g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " +
+            std::to_string(k);
+    return pq ? -49 : -28;
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
+  if (Q < 1 || Q > x->self_max) {
+    g_err = std::string("index: ") + (pq ? "search_batch_pq" : "search_batch") + " takes 1.." + std::to_string(x->self_max) +
+            " queries a call, got " + std::to_string(Q);
+    return -4;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->batch_program(c, Q, k, R, pq, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  return run_program(c, g, fresh, [&] {
+    std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
+    std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
+    // stage one's scores: [Q][R], best first; [Q] from a pq8 index without bf16 rows (version 10)
+    const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);
+    for (int q = 0; q < Q; ++q) out_stage1_last[q] = pq && !x->rescore ? s1[q] : s1[(size_t)q * R + R - 1];
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
 int hz_index_neighbors_max(void* h, int set) {
   Index* x = static_cast<Index*>(h);
   if (!x || set < 0 || set > HZ_INDEX_SELF_MAX_Q) return -1;
@@ -1209,119 +1259,20 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
   HzProgram g = x->self_program(c, n, k, skip_self, &fresh);
   if (!g) return -11;
   std::memcpy(c.nid_host, ids, (size_t)n * 4);
-  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
-  if (!rc) rc = (int)hipStreamSynchronize(c.st);
-  if (rc) return rc;
-  std::memcpy(out_score, c.nout_host, (size_t)n * k * 4);
-  std::memcpy(out_id, c.nout_host + kSelfOutHalf, (size_t)n * k * 4);
-  if (fresh) {
-    rc = hz_prog_capture(g, c.st);
-    if (!rc) rc = (int)hipStreamSynchronize(c.st);
-  }
-  return rc;
+  return run_program(c, g, fresh, [&] {
+    std::memcpy(out_score, c.nout_host, (size_t)n * k * 4);
+    std::memcpy(out_id, c.nout_host + kSelfOutHalf, (size_t)n * k * 4);
+  });
 }
 
 int hz_index_search_batch(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                           float* out_stage1_last) {
-  Index* x = static_cast<Index*>(h);
-  if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
-  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (x->fp8 || x->ivf || x->bin || x->pq) {
-    g_err = std::string("index: search_batch is built for plain bf16 indexes (versions 1 and 2), this one is ") +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->quant_name()) + " of version " +
-            std::to_string(x->h.version);
-    return -44;
-  }
-  if (x->h.dim % 32) {
-    g_err = "index: search_batch needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
-    return -45;
-  }
-  if (k < 1 || k > HZ_SEARCH_MAX_K) {
-    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
-    return -5;
-  }
-  if (R < k || R > HZ_SEARCH_MAX_K) {
-    g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " +
-            std::to_string(k);
-    return -28;
-  }
-  Ctx& c = *x->ctx[ctx];
-  std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
-  if (Q < 1 || Q > x->self_max) {
-    g_err = "index: search_batch takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
-    return -4;
-  }
-  if (hipSetDevice(x->device) != hipSuccess) return -10;
-  bool fresh = false;
-  HzProgram g = x->batch_program(c, Q, k, R, &fresh);
-  if (!g) return -11;
-  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
-  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
-  if (!rc) rc = (int)hipStreamSynchronize(c.st);
-  if (rc) return rc;
-  std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
-  std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
-  const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);  // [Q][R], best first
-  for (int q = 0; q < Q; ++q) out_stage1_last[q] = s1[(size_t)q * R + R - 1];
-  if (fresh) {
-    rc = hz_prog_capture(g, c.st);
-    if (!rc) rc = (int)hipStreamSynchronize(c.st);
-  }
-  return rc;
+  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, false);
 }
 
 int hz_index_search_batch_pq(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                              float* out_stage1_last) {
-  Index* x = static_cast<Index*>(h);
-  if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
-  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (!x->pq) {
-    g_err = std::string("index: search_batch_pq is built for pq8 indexes (versions 10 and 11), this one is ") +
-            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->fp8 || x->bin ? x->quant_name() : "a bf16 index") +
-            " of version " + std::to_string(x->h.version);
-    return -46;
-  }
-  if (!x->cb8) {
-    g_err = "index: search_batch_pq needs dsub % 8 == 0 (a 16-byte chunk of the bf16 table lies in one sub-space), got dsub = " +
-            std::to_string(x->h.dim / (uint64_t)x->pq_m);
-    return -47;
-  }
-  if (x->h.dim % 32) {
-    g_err = "index: search_batch_pq needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
-    return -48;
-  }
-  if (k < 1 || k > HZ_SEARCH_MAX_K) {
-    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
-    return -5;
-  }
-  if (R < k || R > HZ_SEARCH_MAX_K) {
-    g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " +
-            std::to_string(k);
-    return -49;
-  }
-  Ctx& c = *x->ctx[ctx];
-  std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
-  if (Q < 1 || Q > x->self_max) {
-    g_err = "index: search_batch_pq takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
-    return -4;
-  }
-  if (hipSetDevice(x->device) != hipSuccess) return -10;
-  bool fresh = false;
-  HzProgram g = x->pq_batch_program(c, Q, k, R, &fresh);
-  if (!g) return -11;
-  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
-  int rc = fresh ? hz_prog_run(g, c.st) : hz_prog_replay(g, c.st);
-  if (!rc) rc = (int)hipStreamSynchronize(c.st);
-  if (rc) return rc;
-  std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
-  std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
-  const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);  // version 11: [Q][R], best first; 10: [Q]
-  for (int q = 0; q < Q; ++q) out_stage1_last[q] = x->rescore ? s1[(size_t)q * R + R - 1] : s1[q];
-  if (fresh) {
-    rc = hz_prog_capture(g, c.st);
-    if (!rc) rc = (int)hipStreamSynchronize(c.st);
-  }
-  return rc;
+  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, true);
 }
 
 namespace {

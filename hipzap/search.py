@@ -2012,6 +2012,30 @@ class Index(_Base):
                 self._free.put(c)
         return scores, ids
 
+    @contextlib.contextmanager
+    def _in_parts(self, call: str, refused, x, args, outs, ctx):
+        """The native ``call(handle, context, part, len(part), *args, *outs of the part)`` over ``x`` in parts of at most
+        ``hz_index_neighbors_max`` rows (contiguous row ranges of ``x`` and of every array of ``outs``), on context
+        ``ctx`` or a borrowed one. A code in ``refused`` is a ValueError with the library's text, any other failure a
+        RuntimeError. Yields the context after the last part; a borrowed one is returned when the block ends."""
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        c = self._free.get() if ctx is None else ctx
+        try:
+            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
+            for a in range(0, x.shape[0], step):
+                part = np.ascontiguousarray(x[a:a + step])
+                rc = getattr(self._lib, call)(self._h, c, part.ctypes.data, part.shape[0], *args,
+                                              *(o[a:a + step].ctypes.data for o in outs))
+                if rc in refused:
+                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
+                if rc:
+                    raise RuntimeError(f"{call} failed with code {rc}")
+            yield c
+        finally:
+            if ctx is None:
+                self._free.put(c)
+
     def search_batch(self, q, k: int = 10, *, candidates=None, fallback: bool = True, ctx: int | None = None):
         """Many fp32 queries at once -> (scores float32 [Q, k], ids int32 [Q, k], certain bool [Q]).
         Stage one scores every query against every live row with the bf16 MFMA -- each query split into three bf16
@@ -2026,31 +2050,15 @@ class Index(_Base):
         per-call maximum is split here."""
         k, R = self._check_batch(k, candidates)
         q = check_queries(q, self.dim)
-        if self._h is None:
-            raise RuntimeError("the index is closed")
         nq = q.shape[0]
         scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
         last = np.empty(nq, np.float32)
-        c = self._free.get() if ctx is None else ctx
-        try:
-            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
-            for a in range(0, nq, step):
-                part = q[a:a + step]
-                s, i, e = scores[a:a + step], ids[a:a + step], last[a:a + step]  # contiguous ranges of the outputs
-                rc = self._lib.hz_index_search_batch(self._h, c, part.ctypes.data, part.shape[0], k, R, s.ctypes.data,
-                                                     i.ctypes.data, e.ctypes.data)
-                if rc in (-4, -5, -28, -44, -45):
-                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
-                if rc:
-                    raise RuntimeError(f"hz_index_search_batch failed with code {rc}")
+        with self._in_parts("hz_index_search_batch", (-4, -5, -28, -44, -45), q, (k, R), (scores, ids, last), ctx) as c:
             certain = batch_certain(last, scores[:, k - 1] if nq else last, batch_slack(q, self.metric))
             if fallback and not certain.all():
                 todo = np.flatnonzero(~certain)
                 scores[todo], ids[todo] = self.search(q[todo], k, ctx=c)
                 certain[:] = True
-        finally:
-            if ctx is None:
-                self._free.put(c)
         return scores, ids, certain
 
     def search_batch_pq(self, q, k: int = 10, *, candidates=None, fallback=None, ctx: int | None = None):
@@ -2071,27 +2079,11 @@ class Index(_Base):
         ``search``'s for 99.7 to 100 % of those queries) or call ``search``. Q <= 16 gains nothing over ``search``."""
         k, R, fallback = self._check_batch_pq(k, candidates, fallback)
         q = check_queries(q, self.dim)
-        if self._h is None:
-            raise RuntimeError("the index is closed")
         nq = q.shape[0]
         scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
         last = np.empty(nq, np.float32)
-        c = self._free.get() if ctx is None else ctx
-        try:
-            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
-            for a in range(0, nq, step):
-                part = q[a:a + step]
-                s, i, e = scores[a:a + step], ids[a:a + step], last[a:a + step]  # contiguous ranges of the outputs
-                rc = self._lib.hz_index_search_batch_pq(self._h, c, part.ctypes.data, part.shape[0], k, R, s.ctypes.data,
-                                                        i.ctypes.data, e.ctypes.data)
-                if rc in (-4, -5, -46, -47, -48, -49):
-                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
-                if rc:
-                    raise RuntimeError(f"hz_index_search_batch_pq failed with code {rc}")
+        with self._in_parts("hz_index_search_batch_pq", (-4, -5, -46, -47, -48, -49), q, (k, R), (scores, ids, last), ctx) as c:
             return self._finish_batch_pq(q, k, R, scores, ids, last, fallback, ctx=c)
-        finally:
-            if ctx is None:
-                self._free.put(c)
 
     def neighbors(self, ids, k: int = 10, *, include_self: bool = False, ctx: int | None = None):
         """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]),
@@ -2100,25 +2092,10 @@ class Index(_Base):
         (DESIGN.md 4s), and ``n`` above the per-pass maximum is split here. A plain bf16 index with
         ``dim % 32 == 0``; an id outside [0, count) or a deleted id is a ValueError."""
         ids, k = self._check_neighbors(ids, k)
-        if self._h is None:
-            raise RuntimeError("the index is closed")
         scores = np.empty((ids.size, k), np.float32)
         out = np.empty((ids.size, k), np.int32)
-        c = self._free.get() if ctx is None else ctx
-        try:
-            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
-            for a in range(0, ids.size, step):
-                part = np.ascontiguousarray(ids[a:a + step])
-                s, i = scores[a:a + step], out[a:a + step]  # contiguous row ranges of the outputs
-                rc = self._lib.hz_index_neighbors(self._h, c, part.ctypes.data, part.size, k, int(not include_self),
-                                                  s.ctypes.data, i.ctypes.data)
-                if rc in (-4, -5, -20, -35, -36, -37):
-                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
-                if rc:
-                    raise RuntimeError(f"hz_index_neighbors failed with code {rc}")
-        finally:
-            if ctx is None:
-                self._free.put(c)
+        with self._in_parts("hz_index_neighbors", (-4, -5, -20, -35, -36, -37), ids, (k, int(not include_self)), (scores, out), ctx):
+            pass
         return scores, out
 
     def _live_now(self) -> np.ndarray:
