@@ -832,6 +832,76 @@ typedef struct HzSearchPqRescoreParams {
   int N, D, M, Q, R, k, ldc, pad_;
 } HzSearchPqRescoreParams;
 int hz_search_pqrescore_launch(const HzSearchPqRescoreParams* p, hipStream_t st);
+// batch scan over fp8 rows (HZ_K_SEARCH_QXSCAN): HZ_K_SEARCH_XSCAN whose B operand is DECODED IN
+// REGISTERS from rows of OCP e4m3fn bytes with one fp32 scale per row (the rows of HZ_K_SEARCH_QSCAN). The grid, the
+// fragment map, the A operand (the split, order l', m', h'), the live bitmap's rules, the selection, the candidate
+// layout cand[(tile*Q + q)*k ..] and the keys are that kind's; HZ_K_SEARCH_MERGEN takes THIS block as it stands (it
+// begins with HzSearchBatchParams' layout, `codes` where `corpus` is).
+// THE B OPERAND. A lane's fragment of step s -- 8 consecutive columns of one row -- is the 8 bytes at
+// codes + row*ldc + 32s + 8 lh, ONE 8-byte global load issued one step ahead of its MFMAs, turned into a bf16x8 by four
+// v_cvt_scalef32_pk_bf16_fp8 at scale 1.0. Every finite e4m3 value (4 significant bits, exponents -9 .. 8) is a bf16
+// value, so the decode is exact and every product of a query term and a row value is exact in fp32, as over bf16
+// rows. Bytes are loaded only for a row below N of a group of 16 rows with a live row; a group with none is neither
+// loaded, decoded nor multiplied. Nothing is staged in LDS but the tile's scales and the k loop has no barrier.
+// THE SCALE. Thread t stages scales[row0 + t] into LDS iff row row0 + t is below N and live; every other slot holds
+// 0, so the scale of a dead row (NaN, inf) is never read. The score is ONE fp32 multiply of the accumulator by it.
+// CONTRACT. bits(score(q, r)) = bits(fl32(scales[r] * a)), a being the accumulator HZ_K_SEARCH_XSCAN gives for the same
+// query over the bf16 row decode(codes[r]): ONE accumulator from +0, per 32-column step the MFMAs in the order l', m',
+// h', the steps in column order. The bits depend on the query's D values, the row's D codes and its scale, and on
+// nothing else: not on N, Q, k, the row's tile or position, the query's slot, or the other queries, rows and scales.
+// Against the exact sum over the effective query, |score - scale * exact| <= (beta(3D)(1 + 2^-24) + 2^-24) * |scale| *
+// sum_i |q'_i| |decode(code_i)| while the result is normal.
+// Refusals (nothing is launched, one code per rule; HZ_K_SEARCH_XSCAN's rules, `ldc` counting bytes): -165 codes,
+// queries, live or cand null; -166 D % 32; -167 D < 32; -168 D > 2048; -169 ldc < D or ldc % 16; -170 N < 1; -171 Q
+// outside 1..HZ_SEARCH_SELF_MAX_Q; -172 k outside 1..HZ_SEARCH_MAX_K; -173 codes not 16-B, cand not 8-B or live not 4-B
+// aligned; -174 live_bytes < 4 * ceil(N / 32); -175 cand_bytes < ntile * Q * k * 8; -176 queries not 16-B aligned;
+// -177 scales null or not 4-B aligned; -178 scales_bytes < 4 * N.
+typedef struct HzSearchQuantBatchParams {
+  const unsigned char* codes;    // e4m3fn uint8 [N][ldc], 16-B aligned rows (ldc in BYTES, ldc % 16 == 0), ldc >= D
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5 (required)
+  unsigned long long* cand;      // scratch [ntile][Q][k] keys
+  float* out_score;              // fp32 [Q][k]  (HZ_K_SEARCH_MERGEN only)
+  int* out_id;                   // int32 [Q][k] (HZ_K_SEARCH_MERGEN only)
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  unsigned long long cand_bytes; // bytes of `cand`, at least hz_search_self_scratch_bytes(N, Q, k)
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launchers: ceil(N / HZ_SEARCH_TILE)
+  int pad_[2];                   // HzSearchSelfParams' skip_self and pad_: unused
+  const float* scales;           // device fp32 [N], 4-B aligned
+  unsigned long long scales_bytes;  // bytes of `scales`, at least 4 * N
+} HzSearchQuantBatchParams;
+#ifdef __cplusplus
+static_assert(offsetof(HzSearchQuantBatchParams, scales) == sizeof(HzSearchBatchParams) &&
+                  offsetof(HzSearchQuantBatchParams, cand) == offsetof(HzSearchBatchParams, cand) &&
+                  offsetof(HzSearchQuantBatchParams, out_id) == offsetof(HzSearchBatchParams, out_id) &&
+                  offsetof(HzSearchQuantBatchParams, cand_bytes) == offsetof(HzSearchBatchParams, cand_bytes) &&
+                  offsetof(HzSearchQuantBatchParams, k) == offsetof(HzSearchBatchParams, k) &&
+                  offsetof(HzSearchQuantBatchParams, ntile) == offsetof(HzSearchBatchParams, ntile),
+              "HZ_K_SEARCH_MERGEN reads an fp8 batch block through HzSearchSelfParams");
+#endif
+int hz_search_qxscan_launch(const HzSearchQuantBatchParams* p, hipStream_t st);
+// rescore of fp8 rows (HZ_K_SEARCH_QRESCORE): the second stage of a bulk search over an fp8 index
+// WITHOUT bf16 rows. search_rescore_kernel over the e4m3 rows: workgroup q scores query q against the R rows `in_id`
+// names (a slot is real iff (unsigned)id < (unsigned)N; nothing is loaded for any other) with HZ_K_SEARCH_QSCAN's own
+// arithmetic -- the fmaf chains, the butterfly and the multiply by the row's scale -- so a real (q, r) has that kind's
+// bits. It ranks by the order rule and writes the best k in HZ_K_SEARCH_RESCORE's layout (-inf / -1 past the real
+// candidates), and out_last[q] = in_score[q][R - 1], stage one's score of the R-th candidate.
+// Refusals (HZ_K_SEARCH_RESCOREN's rules under their own codes): -179 D % 16, D outside 16..2048, ldc < D or
+// ldc % 16; -180 N < 1; -181 Q outside 1..HZ_SEARCH_SELF_MAX_Q; -182 R outside 1..HZ_SEARCH_MAX_K; -183 k outside
+// 1..R; -184 a null pointer; -185 codes or queries not 16-B aligned or scales / in_* / out_* not 4-B aligned.
+typedef struct HzSearchQuantRescoreParams {
+  const unsigned char* codes;    // e4m3fn uint8 [N][ldc], ldc in bytes, 16-B aligned rows
+  const float* scales;           // fp32 [N]
+  const float* queries;          // fp32 [Q][D], 16-B aligned
+  const int* in_id;              // int32 [Q][R], -1 in unused slots
+  const float* in_score;         // fp32 [Q][R]: stage one's scores, best first
+  float* out_score;              // fp32 [Q][k]
+  int* out_id;                   // int32 [Q][k]
+  float* out_last;               // fp32 [Q]
+  int N, D, Q, R, k, ldc;
+} HzSearchQuantRescoreParams;
+int hz_search_qrescore_launch(const HzSearchQuantRescoreParams* p, hipStream_t st);
 // nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
 // of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
 // of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
@@ -1055,6 +1125,17 @@ int hz_index_search_batch(void* idx, int ctx, const float* queries, int Q, int k
 // refusing a pq8 index (-44).
 int hz_index_search_batch_pq(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                              float* out_stage1_last);
+// bulk search over an fp8 index (versions 3 and 4, dim % 32 == 0): hz_index_search_batch's arguments and
+// outputs. Version 3 replays H2D of the queries, HZ_K_SEARCH_QXSCAN at k = R, HZ_K_SEARCH_MERGEN, HZ_K_SEARCH_QRESCORE
+// (R -> k: the bits and the order of hz_index_search on this index) and three D2H; version 4 the same with
+// HZ_K_SEARCH_RESCOREN against the bf16 rescore rows (device or pinned host memory) as stage two, the answer of
+// hz_index_search3 with refine = R over these candidates. Captured per (Q, k, R) under hz_index_search_batch's rules,
+// with its buffers, its candidate scratch and hz_index_neighbors_max.
+// -4: Q outside 1..the maximum; -5: k; -186: not an fp8 index without lists (an fp8 IVF index included); -187:
+// dim % 32; -188: R outside k..HZ_SEARCH_MAX_K (hz_index_last_error names the index or the value in each case).
+// hz_index_search_batch and hz_index_search_batch_pq keep refusing an fp8 index (-44, -46).
+int hz_index_search_batch_q(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                            float* out_stage1_last);
 // clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
 // context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
 // and grown on demand (a call that needs no more than an earlier one allocates nothing).
@@ -1288,7 +1369,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_PQASSIGN, 48, HzSearchPqAssignParams, hz_search_pqassign_op, SEARCH) \
   X(SEARCH_PQUPDATE, 49, HzSearchPqUpdateParams, hz_search_pqupdate_op, SEARCH) \
   X(SEARCH_PQXSCAN, 50, HzSearchPqBatchParams, hz_search_pqxscan_op, SEARCH) \
-  X(SEARCH_PQRESCORE, 51, HzSearchPqRescoreParams, hz_search_pqrescore_op, SEARCH)
+  X(SEARCH_PQRESCORE, 51, HzSearchPqRescoreParams, hz_search_pqrescore_op, SEARCH) \
+  X(SEARCH_QXSCAN, 52, HzSearchQuantBatchParams, hz_search_qxscan_op, SEARCH) \
+  X(SEARCH_QRESCORE, 53, HzSearchQuantRescoreParams, hz_search_qrescore_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -55,6 +55,8 @@
 // Bulk search (a plain bf16 index): hz_index_search_batch replays H2D of the queries, HZ_K_SEARCH_XSCAN
 // and HZ_K_SEARCH_MERGEN at k = R, HZ_K_SEARCH_RESCOREN of those ids against the index's own rows (R -> k) and three
 // D2H (scores, ids, stage one's scores), with the neighbours programs' N and rules and their candidate scratch.
+// hz_index_search_batch_pq (4z, a pq8 index) and hz_index_search_batch_q (4aa, an fp8 index) are the same program over
+// HZ_K_SEARCH_PQXSCAN and HZ_K_SEARCH_QXSCAN, with a stage two of their own where the index has no bf16 rows.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -116,7 +118,7 @@ struct Ctx {
   char* bmid_dev = nullptr;
   char* bout_dev = nullptr;
   char* bout_host = nullptr;
-  float* blast_dev = nullptr;  // pq bulk search on a version-10 index only: stage one's R-th score per query [SELF_MAX_Q]
+  float* blast_dev = nullptr;  // bulk search on a version-10 or version-3 index only: stage one's R-th score per query [SELF_MAX_Q]
   // clustering only (hz_index_assign / hz_index_cmean), device memory allocated on first use and grown on demand:
   // centroids bf16 [C][dim]; live AND mask, cap / 8 bytes; lists int32 then scores fp32, [scan rows] each; the
   // members int32 [M]; seg_off int32 [C + 1]; the fp32 centroids [C][dim]
@@ -124,7 +126,8 @@ struct Ctx {
   void* cl[kClBufs] = {};
   uint64_t cl_bytes[kClBufs] = {};
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
-  // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0)
+  // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0), on
+  // fp8 rows (Q, k, 6, R, 0)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
@@ -354,7 +357,7 @@ struct Index {
     if (!need) return false;
     if (need <= c.ncand_bytes) return true;
     for (auto it = c.progs.begin(); it != c.progs.end();) {
-      if (std::get<2>(it->first) >= 3) {  // neighbours, bulk search, pq bulk search
+      if (std::get<2>(it->first) >= 3) {  // neighbours and every bulk search
         hz_prog_destroy(it->second);
         it = c.progs.erase(it);
       } else {
@@ -375,15 +378,19 @@ struct Index {
   //   pq8 (`pq`, key 5):  HZ_K_SEARCH_PQXSCAN; on a version-11 index HZ_K_SEARCH_RESCOREN against the bf16 rows and
   //     [Q][R] likewise, on a version-10 one HZ_K_SEARCH_PQRESCORE against the codebook, which also leaves stage
   //     one's R-th score per query in blast_dev: [Q].
-  HzProgram batch_program(Ctx& c, int Q, int k, int R, bool pq, bool* fresh) {
+  //   fp8 (`rows_kind` kBatchFp8, key 6): HZ_K_SEARCH_QXSCAN; on a version-4 index HZ_K_SEARCH_RESCOREN
+  //     against the bf16 rows and [Q][R], on a version-3 one HZ_K_SEARCH_QRESCORE against the codes and scales, and [Q].
+  enum { kBatchBf16 = 0, kBatchPq = 1, kBatchFp8 = 2 };
+  HzProgram batch_program(Ctx& c, int Q, int k, int R, int rows_kind, bool* fresh) {
     if (!batch_buffers(c)) return nullptr;
-    const bool by_codebook = pq && !rescore;
-    if (by_codebook && !c.blast_dev && hipMalloc(reinterpret_cast<void**>(&c.blast_dev), (size_t)HZ_INDEX_SELF_MAX_Q * 4) != hipSuccess) {
+    const bool pq = rows_kind == kBatchPq, q8 = rows_kind == kBatchFp8;
+    const bool by_codebook = pq && !rescore, by_codes = q8 && !rescore;
+    if ((by_codebook || by_codes) && !c.blast_dev && hipMalloc(reinterpret_cast<void**>(&c.blast_dev), (size_t)HZ_INDEX_SELF_MAX_Q * 4) != hipSuccess) {
       c.blast_dev = nullptr;
       return nullptr;
     }
     if (!self_scratch(c, Q, R)) return nullptr;
-    const auto key = std::make_tuple(Q, k, pq ? 5 : 4, R, 0);
+    const auto key = std::make_tuple(Q, k, 4 + rows_kind, R, 0);
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
@@ -401,7 +408,7 @@ struct Index {
     p.Q = Q, p.k = R;
     if (pq) p.cb8 = cb8, p.cb8_bytes = 512ull * h.dim, p.M = pq_m;
     HzSearchRescoreParams rp{};
-    rp.rows = pq ? rrows_dev : rows;
+    rp.rows = pq || q8 ? rrows_dev : rows;
     rp.queries = c.bq_dev;
     rp.in_id = p.out_id;
     rp.out_score = reinterpret_cast<float*>(c.bout_dev);
@@ -413,17 +420,27 @@ struct Index {
     cp.out_score = rp.out_score, cp.out_id = rp.out_id;
     cp.out_last = c.blast_dev;
     cp.N = p.N, cp.D = p.D, cp.M = cp.ldc = pq_m, cp.Q = Q, cp.R = R, cp.k = k;
+    HzSearchQuantBatchParams qp{};  // the same leading layout, then the row scales
+    std::memcpy(&qp, &p, sizeof(HzSearchBatchParams));
+    qp.scales = scales, qp.scales_bytes = cap * 4;
+    HzSearchQuantRescoreParams qr{};
+    qr.codes = p.codes, qr.scales = scales, qr.queries = c.bq_dev;
+    qr.in_id = p.out_id, qr.in_score = p.out_score;
+    qr.out_score = rp.out_score, qr.out_id = rp.out_id, qr.out_last = c.blast_dev;
+    qr.N = p.N, qr.D = qr.ldc = p.D, qr.Q = Q, qr.R = R, qr.k = k;
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4;
     int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
     const size_t pbytes = pq ? sizeof(p) : sizeof(HzSearchBatchParams);
-    if (!rc) rc = hz_prog_add_kernel(g, pq ? HZ_K_SEARCH_PQXSCAN : HZ_K_SEARCH_XSCAN, &p, pbytes, 0);
+    if (!rc) rc = q8 ? hz_prog_add_kernel(g, HZ_K_SEARCH_QXSCAN, &qp, sizeof(qp), 0)
+                     : hz_prog_add_kernel(g, pq ? HZ_K_SEARCH_PQXSCAN : HZ_K_SEARCH_XSCAN, &p, pbytes, 0);
     if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, pbytes, 0);  // the same layout: hipzap.h
     if (!rc) rc = by_codebook ? hz_prog_add_kernel(g, HZ_K_SEARCH_PQRESCORE, &cp, sizeof(cp), 0)
+                  : by_codes  ? hz_prog_add_kernel(g, HZ_K_SEARCH_QRESCORE, &qr, sizeof(qr), 0)
                               : hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
-    if (!rc) rc = by_codebook ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0)
+    if (!rc) rc = by_codebook || by_codes ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0)
                               : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
     if (rc) {
       hz_prog_destroy(g);
@@ -1169,14 +1186,29 @@ int pq_batch_index_check(const Index* x) {
   return 0;
 }
 
-// hz_index_search_batch (pq false) and hz_index_search_batch_pq (pq true): the argument checks, the program of
-// (Q, k, R) and its run. A bad R is -28 for the first and -49 for the second.
+int q_batch_index_check(const Index* x) {
+  if (!x->fp8 || x->ivf) {
+    g_err = std::string("index: search_batch_fp8 is built for fp8 indexes (versions 3 and 4), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->bin || x->pq ? x->quant_name() : "a bf16 index") +
+            " of version " + std::to_string(x->h.version);
+    return -186;
+  }
+  if (x->h.dim % 32) {
+    g_err = "index: search_batch_fp8 needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -187;
+  }
+  return 0;
+}
+
+// hz_index_search_batch (rows_kind kBatchBf16), hz_index_search_batch_pq (kBatchPq) and hz_index_search_batch_q
+// (kBatchFp8): the argument checks, the program of (Q, k, R) and its run. A bad R is -28, -49 and -188.
 int bulk_search(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
-                float* out_stage1_last, bool pq) {
+                float* out_stage1_last, int rows_kind) {
+  const bool pq = rows_kind == Index::kBatchPq, q8 = rows_kind == Index::kBatchFp8;
   Index* x = static_cast<Index*>(h);
   if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
-  if (const int rc = pq ? pq_batch_index_check(x) : batch_index_check(x)) return rc;
+  if (const int rc = pq ? pq_batch_index_check(x) : q8 ? q_batch_index_check(x) : batch_index_check(x)) return rc;
   if (k < 1 || k > HZ_SEARCH_MAX_K) {
     g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
     return -5;
@@ -1184,26 +1216,26 @@ int bulk_search(void* h, int ctx, const float* queries, int Q, int k, int R, flo
   if (R < k || R > HZ_SEARCH_MAX_K) {
     g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " +
             std::to_string(k);
-    return pq ? -49 : -28;
+    return pq ? -49 : q8 ? -188 : -28;
   }
   Ctx& c = *x->ctx[ctx];
   std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
   if (Q < 1 || Q > x->self_max) {
-    g_err = std::string("index: ") + (pq ? "search_batch_pq" : "search_batch") + " takes 1.." + std::to_string(x->self_max) +
+    g_err = std::string("index: ") + (pq ? "search_batch_pq" : q8 ? "search_batch_fp8" : "search_batch") + " takes 1.." + std::to_string(x->self_max) +
             " queries a call, got " + std::to_string(Q);
     return -4;
   }
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   bool fresh = false;
-  HzProgram g = x->batch_program(c, Q, k, R, pq, &fresh);
+  HzProgram g = x->batch_program(c, Q, k, R, rows_kind, &fresh);
   if (!g) return -11;
   std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
   return run_program(c, g, fresh, [&] {
     std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
     std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
-    // stage one's scores: [Q][R], best first; [Q] from a pq8 index without bf16 rows (version 10)
+    // stage one's scores: [Q][R], best first; [Q] from a pq8 or fp8 index without bf16 rows (versions 10 and 3)
     const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);
-    for (int q = 0; q < Q; ++q) out_stage1_last[q] = pq && !x->rescore ? s1[q] : s1[(size_t)q * R + R - 1];
+    for (int q = 0; q < Q; ++q) out_stage1_last[q] = (pq || q8) && !x->rescore ? s1[q] : s1[(size_t)q * R + R - 1];
   });
 }
 
@@ -1267,12 +1299,17 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
 
 int hz_index_search_batch(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                           float* out_stage1_last) {
-  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, false);
+  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, Index::kBatchBf16);
 }
 
 int hz_index_search_batch_pq(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                              float* out_stage1_last) {
-  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, true);
+  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, Index::kBatchPq);
+}
+
+int hz_index_search_batch_q(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
+                            float* out_stage1_last) {
+  return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, Index::kBatchFp8);
 }
 
 namespace {

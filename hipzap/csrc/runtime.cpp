@@ -512,6 +512,14 @@ extern "C" __attribute__((weak)) int hz_search_pqrescore_launch(const HzSearchPq
 static int hz_search_pqrescore_op(const HzSearchPqRescoreParams* p, hipStream_t st) {
   return hz_search_pqrescore_launch ? hz_search_pqrescore_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_qxscan_launch(const HzSearchQuantBatchParams* p, hipStream_t st);
+static int hz_search_qxscan_op(const HzSearchQuantBatchParams* p, hipStream_t st) {
+  return hz_search_qxscan_launch ? hz_search_qxscan_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_qrescore_launch(const HzSearchQuantRescoreParams* p, hipStream_t st);
+static int hz_search_qrescore_op(const HzSearchQuantRescoreParams* p, hipStream_t st) {
+  return hz_search_qrescore_launch ? hz_search_qrescore_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -22,6 +22,9 @@ over external queries, each split into three bf16 terms; ``HZ_K_SEARCH_MERGEN`` 
 ``HZ_K_SEARCH_PQXSCAN`` (``PqBatchScanParams``: the batch block over uint8 code rows, ``ldc`` in bytes, plus the bf16
 table ``cb8`` of :func:`hipzap.search.pq_table_bf16`) is the batch scan over product-quantised rows, each MFMA fragment
 gathered from that table by a code byte; ``HZ_K_SEARCH_PQRESCORE`` (``PqRescoreParams``) re-scores its candidates with ``HZ_K_SEARCH_PQSCAN``'s bits.
+``HZ_K_SEARCH_QXSCAN`` (``QuantBatchScanParams``: the batch block over e4m3 byte rows, ``ldc`` in bytes, plus ``scales``)
+is the batch scan over fp8 rows, decoded to bf16 in registers; ``HZ_K_SEARCH_QRESCORE`` (``QuantRescoreParams``) re-scores
+its candidates with ``HZ_K_SEARCH_QSCAN``'s bits.
 ``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
 ``HZ_K_SEARCH_PQLUT`` (``PqLutParams``) writes each query's table of inner products with the 256 sub-centroids of every
@@ -221,6 +224,26 @@ class PqRescoreParams(C.Structure):
                 ("ldc", C.c_int), ("pad_", C.c_int)]
 
 
+@N.params_of("HZ_K_SEARCH_QXSCAN")
+class QuantBatchScanParams(C.Structure):
+    """HzSearchQuantBatchParams: the fields of ``BatchScanParams`` with ``codes`` (e4m3 uint8 [N][ldc], ``ldc`` in bytes)
+    where ``corpus`` is, then ``scales`` (device fp32 [N]) and ``scales_bytes``."""
+    _fields_ = [("codes", C.c_void_p)] + BatchScanParams._fields_[1:] + [("scales", C.c_void_p), ("scales_bytes", C.c_uint64)]
+
+    def merge_params(self) -> SelfScanParams:
+        """The block as ``HZ_K_SEARCH_MERGEN`` reads it."""
+        return SelfScanParams.from_buffer_copy(self)
+
+
+@N.params_of("HZ_K_SEARCH_QRESCORE")
+class QuantRescoreParams(C.Structure):
+    """HzSearchQuantRescoreParams: ``codes`` e4m3 uint8 [N][ldc], ``scales`` fp32 [N], ``queries`` fp32 [Q][D],
+    ``in_id`` / ``in_score`` [Q][R] (a merge's outputs), the outputs [Q][k] and ``out_last`` fp32 [Q]."""
+    _fields_ = [("codes", C.c_void_p), ("scales", C.c_void_p), ("queries", C.c_void_p), ("in_id", C.c_void_p),
+                ("in_score", C.c_void_p), ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("out_last", C.c_void_p),
+                ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("R", C.c_int), ("k", C.c_int), ("ldc", C.c_int)]
+
+
 @N.params_of("HZ_K_SEARCH_ASSIGN")
 class AssignParams(C.Structure):
     """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
@@ -254,6 +277,9 @@ def _sigs(lib):
     N._sig(lib, "hz_search_pqxscan_launch", C.c_int, C.POINTER(PqBatchScanParams), P)
     N._sig(lib, "hz_search_pqrescore_launch", C.c_int, C.POINTER(PqRescoreParams), P)
     N._sig(lib, "hz_index_search_batch_pq", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
+    N._sig(lib, "hz_search_qxscan_launch", C.c_int, C.POINTER(QuantBatchScanParams), P)
+    N._sig(lib, "hz_search_qrescore_launch", C.c_int, C.POINTER(QuantRescoreParams), P)
+    N._sig(lib, "hz_index_search_batch_q", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_neighbors", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_neighbors_max", C.c_int, P, C.c_int)
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -504,6 +530,22 @@ def launch_pq_batch(prm: PqBatchScanParams, stream: int = 0) -> tuple:
 def launch_pq_rescore(prm: PqRescoreParams, stream: int = 0) -> int:
     """The codebook rescore (``HZ_K_SEARCH_PQRESCORE``) on ``stream`` -> its code (0, or negative: nothing ran)."""
     return int(N.lib().hz_search_pqrescore_launch(C.byref(prm), stream))
+
+
+def launch_quant_batch(prm: QuantBatchScanParams, stream: int = 0) -> tuple:
+    """The fp8 batch scan then ``HZ_K_SEARCH_MERGEN`` over the same block on ``stream``: (scan code, merge code); no merge
+    after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_qxscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    mp = prm.merge_params()
+    return rc, lib.hz_search_mergen_launch(C.byref(mp), stream)
+
+
+def launch_quant_rescore(prm: QuantRescoreParams, stream: int = 0) -> int:
+    """The fp8 rescore (``HZ_K_SEARCH_QRESCORE``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_qrescore_launch(C.byref(prm), stream))
 
 
 def launch_rescore_n(prm: RescoreParams, stream: int = 0) -> int:

@@ -1323,6 +1323,40 @@ def pq_batch_slack(q, codebook):
     return (2.0 ** -8 + beta + gamma) * qn * xmax + np.sqrt(d) * (3 * 2.0 ** -126 * xmax + 2.0 ** -134 * qn)
 
 
+def fp8_cosine_rmax(d: int) -> float:
+    """The most a decoded row ``x = scale * decode(code)`` of a ``cosine`` fp8 index can measure. The quantiser's input
+    ``v`` is a row normalised in fp32 (``write_index``, ``add``: within a few 2^-24 D of 1) or a stored bf16 row widened
+    as it stands (``convert_index``: at most ``COSINE_RMAX`` = 1 + 2^-7), so ``||v|| <= 1 + 2^-7`` either way. Per
+    element (:func:`prepare_rows_fp8`) ``|v_i - x_i| <= (|v_i| 2^-4 + scale 2^-10)(1 + 2^-10)`` with ``scale = max|v| /
+    448 <= ||v|| / 448``, hence ``||x|| <= ||v|| (1 + (2^-4 + sqrt(D) / 448 * 2^-10)(1 + 2^-10))``. Below 1 + 2^-3 for
+    every D <= 2048."""
+    return COSINE_RMAX * (1 + (2.0 ** -4 + np.sqrt(d) / E4M3_MAX * 2.0 ** -10) * (1 + 2.0 ** -10))
+
+
+def fp8_batch_slack(q, metric: str):
+    """E of :meth:`Index.search_batch_fp8`'s certificate on an index without bf16 rows, per query (float64 [Q]), or None
+    where no bound on the rows is known (an ``ip`` index). Both stages score the SAME decoded row ``x = scale *
+    decode(code)``; let S be its score in ``search`` (csrc/hipzap.h HZ_K_SEARCH_QSCAN), s1 its stage-one score
+    (HZ_K_SEARCH_QXSCAN), q' = h' + m' + l' the split's effective query and u = 2^-24. Then
+      |s1 - q'.x| <= (beta(3D)(1 + u) + u) sum |q'_i x_i| + 2^-149  (the batch scan's accumulator, then ONE fp32 multiply by
+                                                                  the scale: relative u, or absolute when it underflows),
+      |q'.x - q.x| <= 3 * 2^-126 sum |x_i|                         (the terms the split flushes),
+      |q.x - S|    <= gamma(D + 1) sum |q_i x_i|                   (the fmaf chains, the butterfly, the multiply: 4n),
+    and by Cauchy-Schwarz sum |q_i x_i| <= ||q|| rmax, sum |x_i| <= sqrt(D) rmax, |q'_i| <= |q_i|, with ``rmax`` from
+    :func:`fp8_cosine_rmax`. A row outside the candidates has s1 <= s_R, hence S <= s_R + E with
+    ``E = (beta(3D)(1 + u) + u + gamma(D + 1)) ||q|| rmax + 3 * 2^-126 sqrt(D) rmax + 2^-149``.
+    beta(n) = n 2^-23 / (1 - n 2^-23), gamma(n) = n 2^-24 / (1 - n 2^-24)."""
+    if metric != "cosine":
+        return None
+    q64 = np.asarray(q, np.float64)
+    d = q64.shape[1]
+    u = 2.0 ** -24
+    beta = 3 * d * 2.0 ** -23 / (1 - 3 * d * 2.0 ** -23)
+    gamma = (d + 1) * u / (1 - (d + 1) * u)
+    rmax = fp8_cosine_rmax(d)
+    return (beta * (1 + u) + u + gamma) * np.sqrt((q64 * q64).sum(axis=1)) * rmax + 3 * 2.0 ** -126 * np.sqrt(d) * rmax + 2.0 ** -149
+
+
 def check_queries(q, dim: int) -> np.ndarray:
     q = np.asarray(q)
     if q.ndim == 1:
@@ -1531,6 +1565,29 @@ class _Base:
     def _finish_batch_pq(self, q, k, R, s, i, last, fallback, ctx=None):
         """The certificate of :meth:`search_batch_pq` and its fallback over the uncertain queries."""
         slack = None if self.rescore else pq_batch_slack(q, self.codebook)
+        certain = batch_certain(last, s[:, k - 1] if len(q) else last, slack)
+        if fallback and not certain.all():
+            todo = np.flatnonzero(~certain)
+            kw = {} if ctx is None else {"ctx": ctx}
+            s[todo], i[todo] = self.search(q[todo], k, refine=R, **kw) if self.rescore else self.search(q[todo], k, **kw)
+            certain[:] = True
+        return s, i, certain
+
+    def _check_batch_fp8(self, k, candidates, fallback):
+        """The refusals of :meth:`search_batch_fp8` that both backends share -> (k, R, fallback)."""
+        if self.dtype != FP8 or self.ivf is not None:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
+                f"a {self.dtype} index" if self.dtype in (BIN, PQ) else "a bf16 index"
+            raise ValueError(f"search_batch_fp8 is built for fp8 indexes (versions 3 and 4): this one is {what} of "
+                             f"version {self.version}")
+        if self.dim % 32:
+            raise ValueError(f"search_batch_fp8 needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
+        k = check_k(k)
+        return k, batch_candidates(k, candidates), (not self.rescore) if fallback is None else bool(fallback)
+
+    def _finish_batch_fp8(self, q, k, R, s, i, last, fallback, ctx=None):
+        """The certificate of :meth:`search_batch_fp8` and its fallback over the uncertain queries."""
+        slack = None if self.rescore else fp8_batch_slack(q, self.metric)
         certain = batch_certain(last, s[:, k - 1] if len(q) else last, slack)
         if fallback and not certain.all():
             todo = np.flatnonzero(~certain)
@@ -1810,6 +1867,27 @@ class RefIndex(_Base):
         s, i = s.astype(np.float32), i.astype(np.int32)
         return self._finish_batch_pq(q, k, R, s, i, s1[:, R - 1], fallback)
 
+    def search_batch_fp8(self, q, k: int = 10, *, candidates=None, fallback=None, ctx=None):
+        """:meth:`Index.search_batch_fp8` on the host, its oracle: stage one :func:`search_ref` in fp64 over the SPLIT
+        query times ``scales[r] * e4m3_to_f32(codes)`` at k = R; stage two ``search_ref(scales=...)`` over those R on a
+        version-3 index, :func:`rescore_ref` over the bf16 rows on a version-4 one; then the same certificate."""
+        k, R, fallback = self._check_batch_fp8(k, candidates, fallback)
+        q = check_queries(q, self.dim)
+        with self._mut:
+            h, m, l = split3(q)
+            eff = h.astype(np.float64) + m.astype(np.float64) + l.astype(np.float64)
+            s1, i1 = search_ref(self._rows, eff, R, None if self._live.all() else self._live, scales=self.scales)
+            s, i = np.full((q.shape[0], k), -np.inf), np.full((q.shape[0], k), -1, np.int32)
+            for a in range(q.shape[0]):
+                if self.rescore:
+                    s[a], i[a] = rescore_ref(self._rrows, q[a], i1[a], k)
+                else:
+                    ids = np.sort(i1[a][i1[a] >= 0])  # ascending: search_ref breaks ties by position
+                    sa, at = (x[0] for x in search_ref(self._rows[ids], q[a], k, scales=self.scales[ids]))
+                    s[a], i[a] = sa, np.where(at >= 0, ids[np.maximum(at, 0)] if ids.size else -1, -1)
+        s, i = s.astype(np.float32), i.astype(np.int32)
+        return self._finish_batch_fp8(q, k, R, s, i, s1[:, R - 1], fallback)
+
     def neighbors(self, ids, k: int = 10, *, include_self: bool = False):
         """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]):
         :func:`search_ref` in fp64 over the stored rows with ``allow`` = live and, unless ``include_self``, not the
@@ -2085,6 +2163,26 @@ class Index(_Base):
         with self._in_parts("hz_index_search_batch_pq", (-4, -5, -46, -47, -48, -49), q, (k, R), (scores, ids, last), ctx) as c:
             return self._finish_batch_pq(q, k, R, scores, ids, last, fallback, ctx=c)
 
+    def search_batch_fp8(self, q, k: int = 10, *, candidates=None, fallback=None, ctx: int | None = None):
+        """Many fp32 queries at once over an fp8 index -> (scores float32 [Q, k], ids int32 [Q, k],
+        certain bool [Q]). Stage one is the batch scan of :meth:`search_batch` over the e4m3 rows DECODED IN REGISTERS to
+        bf16 -- exact, so every product with a term of the split query is exact -- times the row's scale, ``candidates``
+        rows per query (R: ``None`` for ``min(128, max(4 k, k + 32))``). Stage two, version 3: ``search``'s own fp8 score
+        of those R, so the returned scores are ``search``'s bits; ``certain[q]`` is ``s_R == -inf or s_R + E < t_k`` with
+        E from :func:`fp8_batch_slack` (a ``cosine`` index; on an ``ip`` index only the first clause), and then the answer
+        equals ``search(q[None], k)`` in ids and score bits; ``fallback=None`` means True: the uncertain queries are
+        re-run through :meth:`search`. Version 4: the exact bf16 rescoring of ``search(refine=R)``; no useful bound relates
+        the fp8 order to the bf16 order, so ``certain[q]`` holds only when fewer than R rows passed, and ``fallback=None``
+        means False (``True`` re-runs the uncertain queries through ``search(refine=R)``). Needs ``dim % 32 == 0``; Q above
+        the per-call maximum is split here. Q <= 16 gains nothing over ``search``."""
+        k, R, fallback = self._check_batch_fp8(k, candidates, fallback)
+        q = check_queries(q, self.dim)
+        nq = q.shape[0]
+        scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
+        last = np.empty(nq, np.float32)
+        with self._in_parts("hz_index_search_batch_q", (-4, -5, -186, -187, -188), q, (k, R), (scores, ids, last), ctx) as c:
+            return self._finish_batch_fp8(q, k, R, scores, ids, last, fallback, ctx=c)
+
     def neighbors(self, ids, k: int = 10, *, include_self: bool = False, ctx: int | None = None):
         """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]),
         best first; the row itself is left out unless ``include_self`` (other rows with the same bits stay and tie
@@ -2265,6 +2363,7 @@ class Index(_Base):
                 **({"m": int(pq[0]), "dsub": int(pq[1]), "codebook_bytes": int(pq[2]), "scan_span": int(pq[4]),
                     "cb8_bytes": int(pq[5]), "batch_pq": bool(pq[6])}
                    if self.dtype == PQ else {}),
+                **({"batch_fp8": self.ivf is None and self.dim % 32 == 0} if self.dtype == FP8 else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
