@@ -902,6 +902,76 @@ typedef struct HzSearchQuantRescoreParams {
   int N, D, Q, R, k, ldc;
 } HzSearchQuantRescoreParams;
 int hz_search_qrescore_launch(const HzSearchQuantRescoreParams* p, hipStream_t st);
+// batch scan over a work list (HZ_K_SEARCH_LXSCAN): HZ_K_SEARCH_XSCAN over the probed tiles of an IVF
+// index (version 5: bf16 rows stored list by list, N = ntile * HZ_SEARCH_TILE stored rows, padding rows dead in
+// `live`). The grid is the WORK LIST: workgroup i takes item i, ONE stored tile and the up-to-HZ_SEARCH_SELF_QB queries
+// of the call that probe the tile's list, so a tile that n queries probe is read ceil(n / 64) times, not n times. The
+// fragment map, the A operand's split (order l', m', h'), the B operand, the live bitmap's rules and the selection's
+// algorithm are HZ_K_SEARCH_XSCAN's; the A operand is GATHERED: query group i's lane reads the row of `queries` that the
+// item names.
+// THE WORK LIST is two int32 tables the host builds:
+//   items   [nwork][4] = {tile, add, first, nq}: the stored tile, a slot offset, and the entries [first, first + nq),
+//                        1 <= nq <= HZ_SEARCH_SELF_QB
+//   entries [nent][2]  = {query, base}: a query of the call and the first candidate slot it owns in the item's list
+// Query `query` of item i owns candidate slot j = base + add. The host numbers a query's probed tiles 0, 1, ... in the
+// list scan's probe order (probe after probe, a list's tiles in list_tiles order): base = the tiles of the query's
+// earlier probes, add = the tile's ordinal in its list -- so the tiles of one list share their entries, and a list that
+// more than 64 queries probe is several blocks of entries and as many items per tile. Every list for every query: one
+// block of entries {q, 0} per 64 queries and add = the tile's ordinal over all lists.
+// Keys and slots. The key's id field is ~rowid[stored row], the EXTERNAL id, so ties break on the external id inside a
+// tile and across lists; query q writes the tile's best min(k, passing rows) keys, best first, then key 0, to
+// cand[(j*Q + q)*k ..] -- the layout of HZ_K_SEARCH_LSCAN, which HZ_K_SEARCH_MERGEN reduces through a block with
+// N = P * HZ_SEARCH_TILE. The launcher first clears all P*Q*k keys (a small kernel of its own, no memset), so every
+// slot that the merge reads is written in the same call whatever the list holds.
+// Device checks: an item whose tile is outside [0, ntile), whose nq is outside 1..64 or whose entries are not inside
+// [0, nent) is skipped whole; an entry whose query is outside [0, Q) or whose slot base + add is outside [0, P) takes no
+// part: nothing is read through any of them and no candidate is written for them.
+// CONTRACT. score(q, r) has exactly the bits HZ_K_SEARCH_XSCAN gives for that query and that bf16 row.
+// Refusals (nothing is launched, one code per rule): -189 corpus, queries, live, cand, rowid, items or entries null;
+// -190 D % 32; -191 D < 32; -192 D > 2048; -193 ldc < D or ldc % 8; -194 N < 1 or N % HZ_SEARCH_TILE; -195 Q outside
+// 1..HZ_SEARCH_SELF_MAX_Q; -196 k outside 1..HZ_SEARCH_MAX_K; -197 corpus or queries not 16-B, cand not 8-B or live,
+// rowid, items or entries not 4-B aligned; -198 live_bytes < 4 * ceil(N / 32); -199 P < 1 or P * HZ_SEARCH_TILE >= 2^31;
+// -200 cand_bytes < P * Q * k * 8; -201 nwork < 1 or nent < 1; -202 items_bytes < nwork * 16; -203 entries_bytes <
+// nent * 8.
+#define HZ_SEARCH_LX_ITEM 4   // int32 words of an item
+#define HZ_SEARCH_LX_ENTRY 2  // int32 words of an entry
+typedef struct HzSearchListBatchParams {
+  const unsigned short* corpus;  // bf16 [N][ldc] in stored order, 16-B aligned rows (ldc % 8 == 0), ldc >= D
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const unsigned* live;          // 1 bit per stored row (required)
+  unsigned long long* cand;      // scratch [P][Q][k] keys
+  float* out_score;              // unused: HzSearchBatchParams' layout up to pad_
+  int* out_id;                   // unused
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  unsigned long long cand_bytes; // bytes of `cand`, at least P * Q * k * 8
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launcher: N / HZ_SEARCH_TILE
+  int pad_[2];
+  const int* rowid;              // device int32 [N]: the external id of each stored row
+  const int* items;              // device int32 [nwork][HZ_SEARCH_LX_ITEM]
+  const int* entries;            // device int32 [nent][HZ_SEARCH_LX_ENTRY]
+  unsigned long long items_bytes, entries_bytes;
+  int nwork, nent, P, pad2_;
+} HzSearchListBatchParams;
+int hz_search_lxscan_launch(const HzSearchListBatchParams* p, hipStream_t st);
+// rescore of rows held in stored order (HZ_K_SEARCH_RESCOREP): HZ_K_SEARCH_RESCOREN whose candidates are
+// EXTERNAL ids and whose rows lie by stored position. A slot is real iff (unsigned)id < (unsigned)npos and
+// (unsigned)pos[id] < (unsigned)N; the row scored is rows[pos[id]], with HZ_K_SEARCH_SCAN's bits, and the ranking and
+// the ids written are the external ids': higher score first, then the lower external id, then the lower slot. Nothing
+// is loaded for any other slot. The kernel is search_rescore_kernel's body; kinds 35 and 45 keep their block and code.
+// Refusals (HZ_K_SEARCH_RESCOREN's rules under their own codes): -205 D % 8, D outside 8..2048, ldc < D or ldc % 8;
+// -206 N < 1; -207 Q outside 1..HZ_SEARCH_SELF_MAX_Q; -208 R outside 1..HZ_SEARCH_MAX_K; -209 k outside 1..R; -210 a
+// null pointer; -211 rows or queries not 16-B aligned or pos / in_id / out_* not 4-B aligned; -212 npos < 1.
+typedef struct HzSearchRescorePosParams {
+  const unsigned short* rows;    // bf16 [N][ldc] in stored order, 16-B aligned rows
+  const float* queries;          // fp32 [Q][D], 16-B aligned
+  const int* in_id;              // int32 [Q][R] external ids, -1 in unused slots
+  float* out_score;              // fp32 [Q][k]
+  int* out_id;                   // int32 [Q][k] external ids
+  const int* pos;                // device int32 [npos]: external id -> stored row, -1: none
+  int N, D, Q, R, k, ldc, npos, pad_;
+} HzSearchRescorePosParams;
+int hz_search_rescorep_launch(const HzSearchRescorePosParams* p, hipStream_t st);
 // nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
 // of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
 // of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
@@ -1136,6 +1206,30 @@ int hz_index_search_batch_pq(void* idx, int ctx, const float* queries, int Q, in
 // hz_index_search_batch and hz_index_search_batch_pq keep refusing an fp8 index (-44, -46).
 int hz_index_search_batch_q(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                             float* out_stage1_last);
+// bulk search over an IVF index (version 5: bf16 rows stored list by list, dim % 32 == 0). Both calls
+// take at most hz_index_neighbors_max queries (the caller splits above it), run under the context's mutex and share
+// hz_index_search_batch's buffers and candidate scratch, grown on demand; the id-to-stored-row table, the centroids'
+// all-ones bitmap and the work-list buffers are made on first use and counted by hz_index_describe.
+// hz_index_probes_batch: the coarse stage for Q queries at once -- hz_index_search_batch's program (HZ_K_SEARCH_XSCAN
+// and HZ_K_SEARCH_MERGEN at k = Rc, HZ_K_SEARCH_RESCOREN Rc -> nprobe) over the centroid table as a bf16 corpus of nlist
+// rows, captured per (Q, nprobe, Rc). out_list int32 [Q][nprobe] in hz_index_probes' order, out_score_last[q] the
+// nprobe-th list's score (HZ_K_SEARCH_SCAN's bits), out_stage1_last[q] the batch scan's score of the Rc-th candidate,
+// -inf when nlist < Rc.
+// hz_index_search_batch_ivf: `probes` int32 [Q][nprobe] (what hz_index_probes_batch or hz_index_probes returned), or
+// NULL: every list for every query. The host inverts the probes into the work list of HZ_K_SEARCH_LXSCAN (group by
+// list, blocks of 64 queries, a query's tiles numbered in probe order; P = the largest tile total of a query), uploads
+// it and launches HZ_K_SEARCH_LXSCAN at k = R, HZ_K_SEARCH_MERGEN over the P slots, HZ_K_SEARCH_RESCOREP (R -> k: the
+// bits and the order of hz_index_search3 on this index) and three D2H -- plain launches, the work list changes with
+// every call. Outputs as hz_index_search_batch's.
+// -4: Q outside 1..the maximum; -5: k; -213: not a version-5 index (an fp8 IVF index of version 6 or 7 included);
+// -214: dim % 32; -215: R (Rc) outside k (nprobe)..HZ_SEARCH_MAX_K; -216: nprobe outside 1..min(nlist,
+// HZ_SEARCH_MAX_K); -217: a probe id outside [0, nlist) (hz_index_last_error names the index or the value in each case).
+int hz_index_probes_batch(void* idx, int ctx, const float* queries, int Q, int nprobe, int Rc, int* out_list,
+                          float* out_score_last, float* out_stage1_last);
+int hz_index_search_batch_ivf(void* idx, int ctx, const float* queries, int Q, const int* probes, int nprobe, int k, int R,
+                              float* out_score, int* out_id, float* out_stage1_last);
+// microseconds the host inversion of the context's last hz_index_search_batch_ivf call took (measurement only)
+double hz_index_search_batch_ivf_invert_us(void* idx, int ctx);
 // clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
 // context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
 // and grown on demand (a call that needs no more than an earlier one allocates nothing).
@@ -1371,7 +1465,9 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_PQXSCAN, 50, HzSearchPqBatchParams, hz_search_pqxscan_op, SEARCH) \
   X(SEARCH_PQRESCORE, 51, HzSearchPqRescoreParams, hz_search_pqrescore_op, SEARCH) \
   X(SEARCH_QXSCAN, 52, HzSearchQuantBatchParams, hz_search_qxscan_op, SEARCH) \
-  X(SEARCH_QRESCORE, 53, HzSearchQuantRescoreParams, hz_search_qrescore_op, SEARCH)
+  X(SEARCH_QRESCORE, 53, HzSearchQuantRescoreParams, hz_search_qrescore_op, SEARCH) \
+  X(SEARCH_LXSCAN, 54, HzSearchListBatchParams, hz_search_lxscan_op, SEARCH) \
+  X(SEARCH_RESCOREP, 55, HzSearchRescorePosParams, hz_search_rescorep_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

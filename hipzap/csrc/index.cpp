@@ -57,12 +57,20 @@
 // D2H (scores, ids, stage one's scores), with the neighbours programs' N and rules and their candidate scratch.
 // hz_index_search_batch_pq (4z, a pq8 index) and hz_index_search_batch_q (4aa, an fp8 index) are the same program over
 // HZ_K_SEARCH_PQXSCAN and HZ_K_SEARCH_QXSCAN, with a stage two of their own where the index has no bf16 rows.
+//
+// Bulk search over an IVF index (a version-5 index): hz_index_probes_batch is the bulk program above over
+// the centroid table (nlist bf16 rows, an all-ones bitmap), captured per (Q, nprobe, Rc). hz_index_search_batch_ivf
+// inverts the probes on the host into the work list of HZ_K_SEARCH_LXSCAN (group by list, blocks of 64 queries, a
+// query's tiles numbered in probe order), uploads it and launches the list batch scan at k = R, HZ_K_SEARCH_MERGEN over
+// the P candidate slots and HZ_K_SEARCH_RESCOREP against the stored rows through the id-to-position table: plain
+// launches on the context's stream, since the work list and its size change with every call.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -118,6 +126,12 @@ struct Ctx {
   char* bmid_dev = nullptr;
   char* bout_dev = nullptr;
   char* bout_host = nullptr;
+  // bulk search over an IVF index only: the work list (pinned, device), grown on demand, and what the last call's
+  // host inversion took
+  int* wl_host = nullptr;
+  int* wl_dev = nullptr;
+  uint64_t wl_bytes = 0;
+  double invert_us = 0;
   float* blast_dev = nullptr;  // bulk search on a version-10 or version-3 index only: stage one's R-th score per query [SELF_MAX_Q]
   // clustering only (hz_index_assign / hz_index_cmean), device memory allocated on first use and grown on demand:
   // centroids bf16 [C][dim]; live AND mask, cap / 8 bytes; lists int32 then scores fp32, [scan rows] each; the
@@ -127,7 +141,7 @@ struct Ctx {
   uint64_t cl_bytes[kClBufs] = {};
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
   // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0), on
-  // fp8 rows (Q, k, 6, R, 0)
+  // fp8 rows (Q, k, 6, R, 0); the coarse stage of a bulk search over an IVF index: (Q, nprobe, 7, Rc, 0)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
@@ -185,6 +199,9 @@ struct Index {
   int* ivf_tables = nullptr;          // device: list_off [nlist + 1], list_tiles [tiles], rowid [count], one block
   std::vector<int32_t> pos_of;        // external id -> stored row
   std::vector<int> tiles_desc;        // the lists' tile counts, largest first
+  std::vector<int32_t> lists_host;    // list_off [nlist + 1], then list_tiles [tiles]: the host's copy for the bulk search
+  int* pos_dev = nullptr;             // device int32 [n_ext]: pos_of, uploaded on the first bulk search
+  unsigned* cent_live = nullptr;      // device, ceil(nlist / 32) words of ones: the centroid table's bitmap, likewise
   std::vector<std::unique_ptr<Ctx>> ctx;
 
   ~Index() {
@@ -212,6 +229,8 @@ struct Index {
       if (c->bmid_dev) (void)hipFree(c->bmid_dev);
       if (c->bout_dev) (void)hipFree(c->bout_dev);
       if (c->blast_dev) (void)hipFree(c->blast_dev);
+      if (c->wl_host) (void)hipHostFree(c->wl_host);
+      if (c->wl_dev) (void)hipFree(c->wl_dev);
       for (void* b : c->cl)
         if (b) (void)hipFree(b);
       if (c->st) (void)hipStreamDestroy(c->st);
@@ -225,6 +244,8 @@ struct Index {
     if (codebook) (void)hipFree(codebook);
     if (cb8) (void)hipFree(cb8);
     if (ivf_tables) (void)hipFree(ivf_tables);
+    if (pos_dev) (void)hipFree(pos_dev);
+    if (cent_live) (void)hipFree(cent_live);
   }
 
   // the stored row of a public id, -1 for an id outside the index
@@ -352,8 +373,9 @@ struct Index {
 
   // The candidate scratch of the neighbours and bulk-search programs for (n, k) (the caller holds c.mu): one too
   // small is replaced, and with it the context's programs of both sorts, which hold its address by value.
-  bool self_scratch(Ctx& c, int n, int k) {
-    const uint64_t need = hz_search_self_scratch_bytes((long long)scan_rows(), n, k);
+  bool self_scratch(Ctx& c, int n, int k) { return bulk_scratch(c, hz_search_self_scratch_bytes((long long)scan_rows(), n, k)); }
+  // ... for `need` bytes (0: a refused shape)
+  bool bulk_scratch(Ctx& c, uint64_t need) {
     if (!need) return false;
     if (need <= c.ncand_bytes) return true;
     for (auto it = c.progs.begin(); it != c.progs.end();) {
@@ -442,6 +464,91 @@ struct Index {
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
     if (!rc) rc = by_codebook || by_codes ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0)
                               : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
+  // What a bulk search over an IVF index needs of the index, made on first use (the caller holds a context's mutex;
+  // two contexts may race here, so the pointers are published under a mutex of their own).
+  std::mutex bulk_mu;
+  bool ivf_bulk_tables() {
+    std::lock_guard<std::mutex> lk(bulk_mu);
+    if (pos_dev && cent_live) return true;
+    const std::vector<uint32_t> ones(((size_t)nlist + 31) / 32, 0xffffffffu);  // the scans clear the bits from N on themselves
+    int* pd = nullptr;
+    unsigned* cl = nullptr;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&pd), n_ext * 4) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&cl), ones.size() * 4) == hipSuccess;
+    ok = ok && hipMemcpy(pd, pos_of.data(), n_ext * 4, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(cl, ones.data(), ones.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+      if (pd) (void)hipFree(pd);
+      if (cl) (void)hipFree(cl);
+      return false;
+    }
+    pos_dev = pd, cent_live = cl;
+    return true;
+  }
+  uint64_t ivf_bulk_bytes() const { return pos_dev ? n_ext * 4 + ((uint64_t)nlist + 31) / 32 * 4 : 0; }
+
+  // A context's work-list buffers for `bytes` (the caller holds c.mu): replaced when too small.
+  bool work_list(Ctx& c, uint64_t bytes) {
+    if (bytes <= c.wl_bytes) return true;
+    if (c.wl_host) (void)hipHostFree(c.wl_host);
+    if (c.wl_dev) (void)hipFree(c.wl_dev);
+    c.wl_host = c.wl_dev = nullptr, c.wl_bytes = 0;
+    const uint64_t grown = round_up(bytes + bytes / 2, 4096);
+    if (hipHostMalloc(reinterpret_cast<void**>(&c.wl_host), grown, hipHostMallocDefault) != hipSuccess) return false;
+    if (hipMalloc(reinterpret_cast<void**>(&c.wl_dev), grown) != hipSuccess) {
+      (void)hipHostFree(c.wl_host);
+      c.wl_host = nullptr;
+      return false;
+    }
+    c.wl_bytes = grown;
+    return true;
+  }
+
+  // The coarse program of a bulk search over an IVF index for (Q, nprobe, Rc) (the caller holds c.mu):
+  // batch_program's plain bf16 program over the centroid table -- H2D of the queries, HZ_K_SEARCH_XSCAN and
+  // HZ_K_SEARCH_MERGEN at k = Rc into bmid_dev, HZ_K_SEARCH_RESCOREN Rc -> nprobe into bout_dev, and three D2H: the
+  // lists' scores, the list ids and stage one's scores [Q][Rc].
+  HzProgram coarse_program(Ctx& c, int Q, int nprobe, int Rc, bool* fresh) {
+    if (!batch_buffers(c) || !ivf_bulk_tables()) return nullptr;
+    if (!bulk_scratch(c, hz_search_self_scratch_bytes(nlist, Q, Rc))) return nullptr;
+    const auto key = std::make_tuple(Q, nprobe, 7, Rc, 0);
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    HzSearchBatchParams p{};
+    p.corpus = centroids;
+    p.queries = c.bq_dev;
+    p.live = cent_live;
+    p.cand = c.ncand;
+    p.out_score = reinterpret_cast<float*>(c.bmid_dev);
+    p.out_id = reinterpret_cast<int*>(c.bmid_dev + kSelfOutHalf);
+    p.live_bytes = ((uint64_t)nlist + 31) / 32 * 4;
+    p.cand_bytes = c.ncand_bytes;
+    p.N = nlist, p.D = p.ldc = (int)h.dim, p.Q = Q, p.k = Rc;
+    HzSearchRescoreParams rp{};
+    rp.rows = centroids;
+    rp.queries = c.bq_dev;
+    rp.in_id = p.out_id;
+    rp.out_score = reinterpret_cast<float*>(c.bout_dev);
+    rp.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    rp.N = nlist, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = Rc, rp.k = nprobe;
+    HzProgram g = hz_prog_create();
+    const size_t qn = (size_t)Q * nprobe * 4;
+    int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_XSCAN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qn, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qn, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * Rc * 4, 0);
     if (rc) {
       hz_prog_destroy(g);
       return nullptr;
@@ -861,6 +968,7 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   idx->nlist = (int)ivf_u[0], idx->nprobe_default = (int)ivf_u[1];
   idx->pos_of = std::move(pos_of);
   idx->tiles_desc = std::move(tiles_desc);
+  if (ivf) idx->lists_host.assign(tables_host.begin(), tables_host.begin() + (ivf_u[0] + 1 + ntile));
   if (hz_search_code_warm()) return fail("index: device code load failed");
   for (int i = 0; i < nctx; ++i) {
     auto c = std::make_unique<Ctx>();
@@ -993,7 +1101,7 @@ int hz_index_describe(void* h, uint64_t* out) {
   AllLocked all(*x);
   uint64_t progs = 0, dev = x->row_bytes() + x->cap / 8 + x->cap * 4 + (x->fp8 ? x->cap * 4 : 0);
   if (!x->rescore_host) dev += x->rescore_bytes();
-  dev += x->codebook_bytes() + x->cb8_bytes();
+  dev += x->codebook_bytes() + x->cb8_bytes() + x->ivf_bulk_bytes();
   for (auto& c : x->ctx) {
     progs += c->progs.size();
     dev += x->lut_bytes();
@@ -1001,6 +1109,7 @@ int hz_index_describe(void* h, uint64_t* out) {
     dev += c->ncand_bytes + (c->nid_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 + 2 * kSelfOutHalf : 0);  // neighbours, once used
     dev += c->bq_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * x->h.dim * 4 + 4 * kSelfOutHalf : 0;  // bulk search, once used
     dev += c->blast_dev ? (uint64_t)HZ_INDEX_SELF_MAX_Q * 4 : 0;  // pq bulk search on a version-10 index, once used
+    dev += c->wl_bytes;  // the work list of a bulk search over an IVF index, once used
     for (const uint64_t b : c->cl_bytes) dev += b;  // clustering, once used
   }
   const uint64_t v[8] = {x->count, x->h.dim, x->h.metric, x->ctx.size(), (uint64_t)hz_search_tile_rows(), progs, dev, x->cap};
@@ -1310,6 +1419,201 @@ int hz_index_search_batch_pq(void* h, int ctx, const float* queries, int Q, int 
 int hz_index_search_batch_q(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                             float* out_stage1_last) {
   return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, Index::kBatchFp8);
+}
+
+}  // extern "C"
+
+namespace {
+
+// what both bulk calls over an IVF index refuse of the index: 0, or the refusal with g_err set
+int ivf_batch_index_check(const Index* x, const char* call) {
+  if (!x->ivf || x->fp8) {
+    g_err = std::string("index: ") + call + " is built for IVF indexes over bf16 rows (version 5; not the fp8 IVF indexes of versions 6 "
+            "and 7), this one is " + (x->ivf ? "an fp8 IVF index" : x->fp8 || x->bin || x->pq ? x->quant_name() : "a bf16 index without lists") +
+            " of version " + std::to_string(x->h.version);
+    return -213;
+  }
+  if (x->h.dim % 32) {
+    g_err = std::string("index: ") + call + " needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = " + std::to_string(x->h.dim);
+    return -214;
+  }
+  return 0;
+}
+int ivf_batch_nprobe_check(const Index* x, int nprobe) {
+  if (nprobe < 1 || nprobe > x->nlist || nprobe > HZ_SEARCH_MAX_K) {
+    g_err = "index: nprobe must be in 1..min(nlist, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " + std::to_string(nprobe);
+    return -216;
+  }
+  return 0;
+}
+int ivf_batch_q_check(const Index* x, const char* call, int Q) {  // under a context's mutex
+  if (Q < 1 || Q > x->self_max) {
+    g_err = std::string("index: ") + call + " takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
+    return -4;
+  }
+  return 0;
+}
+
+// The inversion of hz_index_search_batch_ivf (hipzap.h HZ_K_SEARCH_LXSCAN, "THE WORK LIST"): probes [Q][nprobe], or null
+// for every list -> items, entries and P, the largest tile total of a query. -217 with g_err set for a probe id outside
+// [0, nlist) or named twice by one query.
+int invert_probes(const Index* x, const int* probes, int Q, int nprobe, std::vector<int>& items, std::vector<int>& entries, int* P) {
+  const int nlist = x->nlist;
+  const int32_t* loff = x->lists_host.data();
+  const int32_t* ltiles = loff + nlist + 1;
+  items.clear(), entries.clear();
+  *P = 0;
+  if (!probes) {  // one block of entries {q, 0} per 64 queries; the slot is the tile's ordinal over all lists
+    for (int q = 0; q < Q; ++q) entries.push_back(q), entries.push_back(0);
+    const int ntile = loff[nlist];
+    for (int at = 0; at < ntile; ++at)
+      for (int q0 = 0; q0 < Q; q0 += HZ_SEARCH_SELF_QB) items.insert(items.end(), {ltiles[at], at, q0, std::min(HZ_SEARCH_SELF_QB, Q - q0)});
+    *P = ntile;
+    return 0;
+  }
+  std::vector<std::vector<int>> of_list(nlist);  // per list: {query, base} of every query that probes it, queries ascending
+  std::vector<int> seen(nlist, -1);
+  for (int q = 0; q < Q; ++q) {
+    int base = 0;
+    for (int i = 0; i < nprobe; ++i) {
+      const int l = probes[(size_t)q * nprobe + i];
+      if (l < 0 || l >= nlist || seen[l] == q) {
+        g_err = "index: probe " + std::to_string(l) + " of query " + std::to_string(q) +
+                (l < 0 || l >= nlist ? " is outside [0, " + std::to_string(nlist) + ")" : " is named twice");
+        return -217;
+      }
+      seen[l] = q;
+      const int nt = loff[l + 1] - loff[l];
+      if (nt > 0) of_list[l].push_back(q), of_list[l].push_back(base);
+      base += nt;
+    }
+    *P = std::max(*P, base);
+  }
+  for (int l = 0; l < nlist; ++l) {
+    const std::vector<int>& e = of_list[l];
+    const int n = (int)e.size() / 2, first = (int)entries.size() / 2;
+    if (!n) continue;
+    entries.insert(entries.end(), e.begin(), e.end());
+    for (int t = 0; t < loff[l + 1] - loff[l]; ++t)
+      for (int b = 0; b < n; b += HZ_SEARCH_SELF_QB)
+        items.insert(items.end(), {ltiles[loff[l] + t], t, first + b, std::min(HZ_SEARCH_SELF_QB, n - b)});
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hz_index_probes_batch(void* h, int ctx, const float* queries, int Q, int nprobe, int Rc, int* out_list, float* out_score_last,
+                          float* out_stage1_last) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_list || !out_score_last || !out_stage1_last) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (const int rc = ivf_batch_index_check(x, "probes_batch")) return rc;
+  if (const int rc = ivf_batch_nprobe_check(x, nprobe)) return rc;
+  if (Rc < nprobe || Rc > HZ_SEARCH_MAX_K) {
+    g_err = "index: candidates must be in nprobe.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(Rc) + " with nprobe = " +
+            std::to_string(nprobe);
+    return -215;
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);
+  if (const int rc = ivf_batch_q_check(x, "probes_batch", Q)) return rc;
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->coarse_program(c, Q, nprobe, Rc, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  return run_program(c, g, fresh, [&] {
+    std::memcpy(out_list, c.bout_host + kSelfOutHalf, (size_t)Q * nprobe * 4);
+    const float* s2 = reinterpret_cast<const float*>(c.bout_host);
+    const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);
+    for (int q = 0; q < Q; ++q) out_score_last[q] = s2[(size_t)q * nprobe + nprobe - 1], out_stage1_last[q] = s1[(size_t)q * Rc + Rc - 1];
+  });
+}
+
+int hz_index_search_batch_ivf(void* h, int ctx, const float* queries, int Q, const int* probes, int nprobe, int k, int R,
+                              float* out_score, int* out_id, float* out_stage1_last) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_score || !out_id || !out_stage1_last) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (const int rc = ivf_batch_index_check(x, "search_batch_ivf")) return rc;
+  if (k < 1 || k > HZ_SEARCH_MAX_K) {
+    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
+    return -5;
+  }
+  if (R < k || R > HZ_SEARCH_MAX_K) {
+    g_err = "index: candidates must be in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R) + " with k = " + std::to_string(k);
+    return -215;
+  }
+  if (probes)
+    if (const int rc = ivf_batch_nprobe_check(x, nprobe)) return rc;
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);
+  if (const int rc = ivf_batch_q_check(x, "search_batch_ivf", Q)) return rc;
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<int> items, entries;
+  int P = 0;
+  if (const int rc = invert_probes(x, probes, Q, nprobe, items, entries, &P)) return rc;
+  c.invert_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  if (items.empty()) {  // every probed list is empty: no candidate at all
+    std::fill(out_score, out_score + (size_t)Q * k, -__builtin_inff());
+    std::fill(out_id, out_id + (size_t)Q * k, -1);
+    std::fill(out_stage1_last, out_stage1_last + Q, -__builtin_inff());
+    return 0;
+  }
+  const uint64_t ib = items.size() * 4, eb = entries.size() * 4;
+  if (!x->batch_buffers(c) || !x->ivf_bulk_tables() || !x->work_list(c, ib + eb)) return -11;
+  if (!x->bulk_scratch(c, (uint64_t)P * (uint64_t)Q * (uint64_t)R * 8ull)) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  std::memcpy(c.wl_host, items.data(), ib);
+  std::memcpy(c.wl_host + items.size(), entries.data(), eb);
+  const int ntile = (int)(x->count / kTile);
+  HzSearchListBatchParams p{};
+  p.corpus = x->rows, p.queries = c.bq_dev, p.live = x->live, p.cand = c.ncand;
+  p.live_bytes = x->cap / 8, p.cand_bytes = c.ncand_bytes;
+  p.N = (int)x->count, p.D = p.ldc = (int)x->h.dim, p.Q = Q, p.k = R;
+  p.rowid = x->ivf_tables + x->nlist + 1 + ntile;
+  p.items = c.wl_dev, p.entries = c.wl_dev + items.size();
+  p.items_bytes = ib, p.entries_bytes = eb;
+  p.nwork = (int)(items.size() / HZ_SEARCH_LX_ITEM), p.nent = (int)(entries.size() / HZ_SEARCH_LX_ENTRY), p.P = P;
+  HzSearchSelfParams mp{};  // the merge over the P candidate slots
+  mp.cand = c.ncand, mp.cand_bytes = c.ncand_bytes;
+  mp.out_score = reinterpret_cast<float*>(c.bmid_dev), mp.out_id = reinterpret_cast<int*>(c.bmid_dev + kSelfOutHalf);
+  mp.N = P * (int)kTile, mp.D = mp.ldc = p.D, mp.Q = Q, mp.k = R;
+  HzSearchRescorePosParams rp{};
+  rp.rows = x->rows, rp.queries = c.bq_dev, rp.in_id = mp.out_id, rp.pos = x->pos_dev;
+  rp.out_score = reinterpret_cast<float*>(c.bout_dev), rp.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+  rp.N = (int)x->count, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k, rp.npos = (int)x->n_ext;
+  const size_t qk = (size_t)Q * k * 4;
+  int rc = (int)hipMemcpyAsync(c.bq_dev, c.bq_host, (size_t)Q * x->h.dim * 4, hipMemcpyHostToDevice, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(c.wl_dev, c.wl_host, ib + eb, hipMemcpyHostToDevice, c.st);
+  if (!rc) rc = hz_launch_kernel(HZ_K_SEARCH_LXSCAN, &p, c.st);
+  if (!rc) rc = hz_launch_kernel(HZ_K_SEARCH_MERGEN, &mp, c.st);
+  if (!rc) rc = hz_launch_kernel(HZ_K_SEARCH_RESCOREP, &rp, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(c.bout_host, c.bout_dev, qk, hipMemcpyDeviceToHost, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, hipMemcpyDeviceToHost, c.st);
+  if (!rc) rc = (int)hipMemcpyAsync(c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, hipMemcpyDeviceToHost, c.st);
+  const int src = (int)hipStreamSynchronize(c.st);  // also after a failed launch: nothing of this call stays in flight
+  if (rc || src) {
+    if (rc < 0) g_err = "index: search_batch_ivf: a launcher refused its block (" + std::to_string(rc) + ": csrc/hipzap.h)";
+    return rc ? rc : src;
+  }
+  std::memcpy(out_score, c.bout_host, qk);
+  std::memcpy(out_id, c.bout_host + kSelfOutHalf, qk);
+  const float* s1 = reinterpret_cast<const float*>(c.bout_host + 2 * kSelfOutHalf);
+  for (int q = 0; q < Q; ++q) out_stage1_last[q] = s1[(size_t)q * R + R - 1];
+  return 0;
+}
+
+// microseconds the host inversion of the context's last hz_index_search_batch_ivf call took (measurement only)
+double hz_index_search_batch_ivf_invert_us(void* h, int ctx) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || ctx < 0 || ctx >= (int)x->ctx.size()) return -1.0;
+  std::lock_guard<std::mutex> lk(x->ctx[ctx]->mu);
+  return x->ctx[ctx]->invert_us;
 }
 
 namespace {

@@ -520,6 +520,14 @@ extern "C" __attribute__((weak)) int hz_search_qrescore_launch(const HzSearchQua
 static int hz_search_qrescore_op(const HzSearchQuantRescoreParams* p, hipStream_t st) {
   return hz_search_qrescore_launch ? hz_search_qrescore_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_lxscan_launch(const HzSearchListBatchParams* p, hipStream_t st);
+static int hz_search_lxscan_op(const HzSearchListBatchParams* p, hipStream_t st) {
+  return hz_search_lxscan_launch ? hz_search_lxscan_launch(p, st) : -102;
+}
+extern "C" __attribute__((weak)) int hz_search_rescorep_launch(const HzSearchRescorePosParams* p, hipStream_t st);
+static int hz_search_rescorep_op(const HzSearchRescorePosParams* p, hipStream_t st) {
+  return hz_search_rescorep_launch ? hz_search_rescorep_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

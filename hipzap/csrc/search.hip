@@ -31,8 +31,12 @@
 //   * search_qxscan — the batch scan over fp8 rows (kind QXSCAN): search_xscan whose B operand is 8 e4m3 bytes per lane
 //                    and step, decoded exactly to bf16 in registers, the row's scale one multiply at the end;
 //                    search_qrescore (kind QRESCORE) is search_rescore's body over e4m3 rows: search_scan's fp8 bits
+//   * search_lxscan — the batch scan over a work list (kind LXSCAN): search_xscan over the probed tiles of an IVF index,
+//                    one workgroup per (stored tile, up to 64 queries that probe its list), the A operand gathered by
+//                    query index, keys by external id; search_rescorep (kind RESCOREP) is search_rescore's body over rows
+//                    held in stored order, the candidates external ids
 // See HzSearchParams (hipzap.h) for the order rule and DESIGN.md 4l / 4m / 4n / 4p / 4q / 4s / 4t / 4u / 4v / 4w / 4x / 4y / 4z /
-// 4aa for the reasoning.
+// 4aa / 4ab for the reasoning.
 #include <stdio.h>
 
 #include <initializer_list>
@@ -976,6 +980,13 @@ static_assert(HZ_SEARCH_MAX_K % ROWS == 0 && HZ_SEARCH_MAX_K <= T, "a group neve
 __device__ __forceinline__ void pqx_sync();
 __host__ __device__ inline const unsigned short* rescore_rows_of(const HzSearchRescoreParams& a) { return a.rows; }
 __host__ __device__ inline const unsigned char* rescore_rows_of(const HzSearchQuantRescoreParams& a) { return a.codes; }
+__host__ __device__ inline const unsigned short* rescore_rows_of(const HzSearchRescorePosParams& a) { return a.rows; }
+// HzSearchRescorePosParams (HZ_K_SEARCH_RESCOREP): the candidates are external ids and the rows lie by
+// stored position. Thread t < R stages rowat[t] = pos[in_id[q][t]] under (unsigned)id < npos beside the id; a slot is real
+// iff (unsigned)rowat < N, the row loaded is rows[rowat*ldc ..], and the ranking and the ids written stay the external
+// ids'. Every other block: rowat IS ids, the statement above.
+template <class A>
+constexpr bool RESCORE_BY_POS = std::is_same_v<A, HzSearchRescorePosParams>;
 
 template <class Fmt, int NC, class A>
 __device__ __forceinline__ void rescore_body(const A& a) {
@@ -987,6 +998,11 @@ __device__ __forceinline__ void rescore_body(const A& a) {
   if constexpr (Fmt::SCALED) {
     __shared__ float scales_of[HZ_SEARCH_MAX_K];
     scl = scales_of;
+  }
+  int* rowat = ids;                                         // the stored row of each slot
+  if constexpr (RESCORE_BY_POS<A>) {
+    __shared__ int pos_of_slot[HZ_SEARCH_MAX_K];
+    rowat = pos_of_slot;
   }
   const int q = blockIdx.x, t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -1001,9 +1017,10 @@ __device__ __forceinline__ void rescore_body(const A& a) {
     int id = -1;
     if (t < a.R && HZ_DCHECK((long)q * a.R + t < (long)a.Q * a.R)) id = a.in_id[(long)q * a.R + t];
     ids[t] = id;
+    if constexpr (RESCORE_BY_POS<A>) rowat[t] = (unsigned)id < (unsigned)a.npos ? a.pos[id] : -1;
     if constexpr (Fmt::SCALED) scl[t] = (unsigned)id < (unsigned)a.N && HZ_DCHECK(id >= 0 && id < a.N) ? a.scales[id] : 0.f;
   }
-  if constexpr (Fmt::SCALED) pqx_sync();  // the kind carries HZ_NO_PK_F32 (below): the header's barrier is not inlined there
+  if constexpr (Fmt::SCALED || RESCORE_BY_POS<A>) pqx_sync();  // the kind carries HZ_NO_PK_F32 (below): the header's barrier is not inlined there
   else __syncthreads();
 
   HzSearchParams one{};  // what score_group reads of the scan's block: one query of D values
@@ -1015,7 +1032,7 @@ __device__ __forceinline__ void rescore_body(const A& a) {
     unsigned any = 0u;
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {  // r0 + r < HZ_SEARCH_MAX_K: the slots past R hold -1
-      id[r] = __builtin_amdgcn_readfirstlane(ids[r0 + r]);
+      id[r] = __builtin_amdgcn_readfirstlane(rowat[r0 + r]);
       pass.pm[r] = (unsigned)id[r] < (unsigned)a.N ? 1u : 0u;
       any |= pass.pm[r];
     }
@@ -1035,7 +1052,7 @@ __device__ __forceinline__ void rescore_body(const A& a) {
       }
     score_group<Fmt, NC>(one, qs, sc, scl, v, pass, lane, nch, r0, a.R);
   }
-  if constexpr (Fmt::SCALED) pqx_sync();
+  if constexpr (Fmt::SCALED || RESCORE_BY_POS<A>) pqx_sync();
   else __syncthreads();
 
   if (t < a.R) {
@@ -1143,13 +1160,32 @@ __device__ __forceinline__ void stage_live_words(const unsigned* live, unsigned 
   }
 }
 
+// Where a selection writes, as a hook of mscan_select: id(j) is the id field of this lane's row j*64 + lane of the
+// tile, out(q, ok) the k keys of the block's query q, with ok false where nothing may be written. TileSlots is the
+// hook of the four kinds whose grid is (tile, query block): the row's position, cand[(tile*Q + q0 + q)*k ..].
+struct TileSlots {
+  unsigned long long* cand;
+  unsigned long long cand_bytes;
+  int Q, k, tile, q0, lane;
+  long row0;
+  __device__ __forceinline__ unsigned id(int j) const { return (unsigned)(row0 + j * 64 + lane); }
+  __device__ __forceinline__ unsigned long long* out(int q, bool& ok) const {
+    const long slot = (long)tile * Q + q0 + q;
+    ok = HZ_DCHECK(q0 + q < Q && (slot + 1) * k * 8 <= (long)cand_bytes);
+    return cand + slot * k;
+  }
+};
+
 // The selection of the batch scans (the comment above: radix cut, compaction, ranking): the block's nq queries from
-// the score array sc[q][row] into cand[(tile*Q + q0 + q)*k ..], wave w taking the queries w, w + 4, ... one at a time
-// through its pool.
-__device__ __forceinline__ void mscan_select(const unsigned* sc, unsigned long long* pool, unsigned long long* cand,
-                                             unsigned long long cand_bytes, int Q, int k, int tile, int q0, int nq, long row0,
-                                             int w, int lane) {
+// the score array sc[q][row] into the k keys that the hook `to` names for each, wave w taking the queries w, w + 4, ...
+// one at a time through its pool.
+template <class Out>
+__device__ __forceinline__ void mscan_select(const unsigned* sc, unsigned long long* pool, const Out& to, int k, int nq, int w,
+                                             int lane) {
   unsigned long long* mine_pool = pool + w * T;
+  unsigned ids[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ids[j] = to.id(j);
   for (int i = 0; i * 4 < nq; ++i) {  // block-uniform trips: the barriers below are reached by every wave
     const int q = i * 4 + w;
     const bool valid = q < nq;  // wave-uniform
@@ -1160,7 +1196,7 @@ __device__ __forceinline__ void mscan_select(const unsigned* sc, unsigned long l
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const unsigned s = sc[q * MSCAN_TS + j * 64 + lane];
-        key[j] = s ? ((unsigned long long)s << 32) | (unsigned)~(unsigned)(row0 + j * 64 + lane) : 0ull;
+        key[j] = s ? ((unsigned long long)s << 32) | (unsigned)~ids[j] : 0ull;
         npass += __popcll(__ballot(s != 0u));
         mx = s > mx ? s : mx;
       }
@@ -1182,9 +1218,8 @@ __device__ __forceinline__ void mscan_select(const unsigned* sc, unsigned long l
     }
     __syncthreads();
     if (valid) {
-      const long slot = (long)tile * Q + q0 + q;
-      unsigned long long* out = cand + slot * k;
-      const bool slot_ok = HZ_DCHECK(q0 + q < Q && (slot + 1) * k * 8 <= (long)cand_bytes);
+      bool slot_ok;
+      unsigned long long* out = to.out(q, slot_ok);
       for (int e = lane; e < n; e += 64) {
         const unsigned long long mine = mine_pool[e];
         int rank = 0;
@@ -1210,25 +1245,31 @@ struct BatchTile {
 };
 
 // The LDS carve-up, the entry checks common to the kinds (`kind_ok`: the kind's own) and the tile's live words, staged
-// for the barrier of batch_groups. false: the workgroup returns. P is any of the four parameter blocks, which
-// share the fields read here (hipzap.h).
+// for the barrier of batch_groups, for a workgroup that scores `tile` against the nq queries from q0 on. false: the
+// workgroup returns. P is any of the parameter blocks, which share the fields read here (hipzap.h).
 template <class P>
-__device__ __forceinline__ bool batch_begin(const P& p, bool kind_ok, float* lds, BatchTile& c) {
+__device__ __forceinline__ bool batch_place(const P& p, bool kind_ok, float* lds, BatchTile& c, int tile, int q0, int nq) {
   c.sc = reinterpret_cast<unsigned*>(lds);
   c.pool = reinterpret_cast<unsigned long long*>(c.sc + QB * MSCAN_TS);
   c.lv = reinterpret_cast<unsigned*>(c.pool + 4 * T);
   const int t = threadIdx.x;
   c.lane = t & 63, c.lr = c.lane & 15, c.lh = c.lane >> 4;
   c.w = __builtin_amdgcn_readfirstlane(t >> 6);
-  c.tile = blockIdx.x, c.q0 = blockIdx.y * QB;
-  if (!HZ_DCHECK(c.tile < p.ntile && (long)c.tile * T < (long)p.N && c.q0 < p.Q && p.D >= 32 && p.D % 32 == 0 && p.D <= 2048 &&
-                 p.k >= 1 && p.k <= HZ_SEARCH_MAX_K && kind_ok))
+  c.tile = tile, c.q0 = q0;
+  if (!HZ_DCHECK(c.tile >= 0 && c.tile < p.ntile && (long)c.tile * T < (long)p.N && c.q0 < p.Q && p.D >= 32 && p.D % 32 == 0 &&
+                 p.D <= 2048 && p.k >= 1 && p.k <= HZ_SEARCH_MAX_K && kind_ok))
     return false;
   c.row0 = (long)c.tile * T;
   c.rows = (int)min((long)T, (long)p.N - c.row0);
-  c.nq = min(QB, p.Q - c.q0);
+  c.nq = nq;
   stage_live_words(p.live, p.live_bytes, p.N, c.row0, c.rows, c.lv);
   return true;
+}
+// ... on the grid (tile, block of QB queries)
+template <class P>
+__device__ __forceinline__ bool batch_begin(const P& p, bool kind_ok, float* lds, BatchTile& c) {
+  const int q0 = blockIdx.y * QB;
+  return batch_place(p, kind_ok, lds, c, (int)blockIdx.x, q0, min(QB, p.Q - q0));
 }
 
 // The barrier that publishes what the workgroup staged, then the wave's live-group masks and its accumulators at +0.
@@ -1270,9 +1311,9 @@ __device__ __forceinline__ void batch_brows(const P& p, const BatchTile& c, cons
 struct NoRowScale {
   __device__ __forceinline__ float operator()(float s, int) const { return s; }
 };
-template <class P, class SelfOf, class ScaleOf = NoRowScale>
-__device__ __forceinline__ void batch_finish(const P& p, const BatchTile& c, const f32x4 (&acc)[4][4], SelfOf self_of,
-                                             ScaleOf scale_of = ScaleOf{}) {
+template <class SelfOf, class ScaleOf, class Out>
+__device__ __forceinline__ void batch_finish_to(const BatchTile& c, int k, const f32x4 (&acc)[4][4], SelfOf self_of, ScaleOf scale_of,
+                                                const Out& to) {
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1286,7 +1327,13 @@ __device__ __forceinline__ void batch_finish(const P& p, const BatchTile& c, con
       }
     }
   pqx_sync();
-  mscan_select(c.sc, c.pool, p.cand, p.cand_bytes, p.Q, p.k, c.tile, c.q0, c.nq, c.row0, c.w, c.lane);
+  mscan_select(c.sc, c.pool, to, k, c.nq, c.w, c.lane);
+}
+// ... into cand[(tile*Q + q)*k ..], the key's id the row's position
+template <class P, class SelfOf, class ScaleOf = NoRowScale>
+__device__ __forceinline__ void batch_finish(const P& p, const BatchTile& c, const f32x4 (&acc)[4][4], SelfOf self_of,
+                                             ScaleOf scale_of = ScaleOf{}) {
+  batch_finish_to(c, p.k, acc, self_of, scale_of, TileSlots{p.cand, p.cand_bytes, p.Q, p.k, c.tile, c.q0, c.lane, c.row0});
 }
 
 // search_mscan_kernel (HZ_K_SEARCH_MSCAN): the queries are the QB rows that qid[qb*QB ..] names. Both
@@ -1442,6 +1489,31 @@ __device__ __forceinline__ void query_mma(const f32x4 (&a)[4][2], const bool (&g
     }
 }
 
+// The k loop of XSCAN and LXSCAN: fp32 query rows `arow` against the bf16 rows `brow`, one k-step loaded ahead of the
+// MFMAs, two steps per trip so that the buffer index is a constant.
+__device__ __forceinline__ void xscan_load(const float* const (&arow)[4], const bool (&aok)[4], const bf16_t* const (&brow)[4],
+                                           const bool (&bok)[4], int kk, f32x4 (&a)[4][2], bf16x8 (&b)[4]) {  // the k-step kk < nk
+  query_load(arow, aok, kk, a);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    b[j] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+    if (bok[j]) b[j] = *reinterpret_cast<const bf16x8*>(brow[j] + kk * 32);
+  }
+}
+__device__ __forceinline__ void xscan_steps(const float* const (&arow)[4], const bool (&aok)[4], const bool (&gok)[4],
+                                            const bf16_t* const (&brow)[4], const bool (&bok)[4], int nk, const BatchTile& c,
+                                            f32x4 (&acc)[4][4]) {
+  f32x4 a[2][4][2];  // [buffer][query group][half of the 8 columns]
+  bf16x8 b[2][4];    // [buffer][row group]
+  xscan_load(arow, aok, brow, bok, 0, a[0], b[0]);
+  for (int kk = 0; kk < nk; kk += 2) {
+    if (kk + 1 < nk) xscan_load(arow, aok, brow, bok, kk + 1, a[1], b[1]);
+    query_mma(a[0], gok, b[0], c, acc);
+    if (kk + 2 < nk) xscan_load(arow, aok, brow, bok, kk + 2, a[0], b[0]);
+    if (kk + 1 < nk) query_mma(a[1], gok, b[1], c, acc);
+  }
+}
+
 // search_xscan_kernel (HZ_K_SEARCH_XSCAN): the self scan with an EXTERNAL A operand, the fp32 queries
 // qb*QB .. qb*QB + QB - 1 through query_load and query_mma; the B operand is the self scan's. There is no qid and no skip_self:
 // a query passes under q < Q.
@@ -1457,26 +1529,97 @@ __global__ __launch_bounds__(T) void search_xscan_kernel(const HzSearchBatchPara
     bool aok[4], gok[4], bok[4];
     query_setup(p, c, arow, aok, gok);
     batch_brows(p, c, brow, bok);
-    const int nk = p.D >> 5;
-    f32x4 a[2][4][2];  // [buffer][query group][half of the 8 columns]
-    bf16x8 b[2][4];    // [buffer][row group]
-    auto load = [&](int buf, int kk) {  // the k-step kk < nk
-      query_load(arow, aok, kk, a[buf]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        b[buf][j] = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
-        if (bok[j]) b[buf][j] = *reinterpret_cast<const bf16x8*>(brow[j] + kk * 32);
-      }
-    };
-    load(0, 0);
-    for (int kk = 0; kk < nk; kk += 2) {  // two steps per trip, so the buffer index is a constant
-      if (kk + 1 < nk) load(1, kk + 1);
-      query_mma(a[0], gok, b[0], c, acc);
-      if (kk + 2 < nk) load(0, kk + 2);
-      if (kk + 1 < nk) query_mma(a[1], gok, b[1], c, acc);
-    }
+    xscan_steps(arow, aok, gok, brow, bok, p.D >> 5, c, acc);
   }
   batch_finish(p, c, acc, [&](int q) { return q < c.nq ? -1 : -2; });
+}
+
+// search_lxscan_kernel (HZ_K_SEARCH_LXSCAN): search_xscan_kernel over a WORK LIST (hipzap.h). Workgroup i
+// takes item i = {tile, add, first, nq}: one stored tile of an IVF index and the nq <= QB queries entries[first ..]
+// names, each {query, base}. One workgroup per item and no striding grid: two items share neither their tile nor their
+// queries, so a workgroup that walked several would re-stage everything behind a barrier and save only its launch,
+// while the dispatcher balances thousands of near-equal items (one tile, at most 64 queries) by itself.
+//   * staging: thread t < QB range-checks entry first + t and writes qix[t] = its query (-1: a slot past nq or a bad
+//     entry) and slt[t] = base + add, the candidate slot j that (query, tile) owns; the tile's live words as in every
+//     batch scan (batch_place). batch_groups' barrier publishes all three.
+//   * A operand: gathered. Lane (lr, lh) of query group i reads the 8 fp32 columns lh*8 .. of row qix[i*16 + lr] of
+//     `queries` through query_load, and query_mma splits them: three bf16 terms, l', m', h', one accumulator from +0.
+//     A group past nq is neither split nor multiplied (gok); a bad entry loads nothing and its pairs score the sentinel.
+//   * B operand and k loop: search_xscan_kernel's (batch_brows, xscan_steps): 16-byte fragments one step ahead; a row
+//     group with no live row is neither loaded nor multiplied.
+//   * selection: mscan_select through the hook ListSlots: the key's id field is ~rowid[stored row], read once per lane
+//     and row (coalesced; N = ntile * T, so the tile is whole), and query q of the item writes cand[(slt[q]*Q + qix[q])*k ..].
+// CONTRACT (hipzap.h): the bits of search_xscan_kernel for the same query and row -- the same statements in the same order.
+// Addresses: items words [4i, 4i + 4) under i < nwork (the launcher checks items_bytes); entries words [2e, 2e + 2)
+// under first <= e < first + nq <= nent (entries_bytes likewise); queries[q*D ..] under (unsigned)q < Q; the tile's rows,
+// live words and rowid[row0 + r] under (unsigned)tile < ntile and N = ntile * T; cand[(j*Q + q)*k + s] under
+// (unsigned)j < P, q < Q, s < k and the end of the slot inside cand_bytes.
+// LDS: XSCAN_LDS + 2 QB ints = 75,296 B dynamic.
+struct ListSlots {
+  unsigned long long* cand;
+  unsigned long long cand_bytes;
+  const int* qix;  // LDS [QB]
+  const int* slt;  // LDS [QB]
+  int Q, k, P;
+  unsigned rid[4];
+  __device__ __forceinline__ unsigned id(int j) const { return rid[j]; }
+  __device__ __forceinline__ unsigned long long* out(int q, bool& ok) const {
+    const int qi = qix[q], j = slt[q];  // every lane reads the same words: LDS broadcasts
+    const long slot = (long)j * Q + qi;
+    ok = qi >= 0 && HZ_DCHECK(qi < Q && j >= 0 && j < P && (slot + 1) * k * 8 <= (long)cand_bytes);
+    return cand + (ok ? slot : 0) * k;
+  }
+};
+
+HZ_NO_PK_F32 __global__ __launch_bounds__(T) void search_lxscan_kernel(const HzSearchListBatchParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  BatchTile c;
+  f32x4 acc[4][4];
+  const int item = blockIdx.x, t = threadIdx.x;
+  if (!HZ_DCHECK(item < p.nwork && ((long)item + 1) * HZ_SEARCH_LX_ITEM * 4 <= (long)p.items_bytes && p.P >= 1 && p.nent >= 1 &&
+                 (long)p.nent * HZ_SEARCH_LX_ENTRY * 4 <= (long)p.entries_bytes && p.N == p.ntile * T))
+    return;
+  const int* it = p.items + (long)item * HZ_SEARCH_LX_ITEM;  // every thread reads the same four words
+  const int tile = it[0], add = it[1], first = it[2], nq = it[3];
+  // a bad item is skipped whole (block-uniform): nothing is read through it, its slots keep the launcher's zero keys
+  if ((unsigned)tile >= (unsigned)p.ntile || nq < 1 || nq > QB || first < 0 || first > p.nent - nq || add < 0 || add >= p.P) return;
+  if (!batch_place(p, p.ldc >= p.D, lds, c, tile, 0, nq)) return;
+  int* qix = reinterpret_cast<int*>(c.lv + T / 32);  // [QB] the item's queries, -1: none
+  int* slt = qix + QB;                               // [QB] their candidate slots
+  if (t < QB) {
+    int q = -1, j = -1;
+    if (t < nq && HZ_DCHECK(first + t < p.nent)) {
+      const int* e = p.entries + (long)(first + t) * HZ_SEARCH_LX_ENTRY;
+      const int eq = e[0], base = e[1];
+      if ((unsigned)eq < (unsigned)p.Q && base >= 0 && base < p.P - add) q = eq, j = base + add;
+    }
+    qix[t] = q, slt[t] = j;
+  }
+  batch_groups(c, acc);
+  if (c.any != 0u) {
+    const float* arow[4];
+    const bf16_t* brow[4];
+    bool aok[4], gok[4], bok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = qix[i * 16 + c.lr];
+      gok[i] = i * 16 < nq;
+      aok[i] = q >= 0 && HZ_DCHECK(q < p.Q);
+      arow[i] = p.queries + (long)(aok[i] ? q : 0) * p.D + c.lh * 8;
+    }
+    batch_brows(p, c, brow, bok);
+    xscan_steps(arow, aok, gok, brow, bok, p.D >> 5, c, acc);
+  }
+  ListSlots to{p.cand, p.cand_bytes, qix, slt, p.Q, p.k, p.P, {0u, 0u, 0u, 0u}};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (HZ_DCHECK(c.row0 + j * 64 + c.lane < (long)p.N)) to.rid[j] = (unsigned)p.rowid[c.row0 + j * 64 + c.lane];
+  batch_finish_to(c, p.k, acc, [&](int q) __attribute__((always_inline)) { return qix[q] >= 0 ? -1 : -2; }, NoRowScale{}, to);
+}
+
+// the launcher's first kernel: key 0 into all n keys of cand (a captured program may hold no memset)
+__global__ __launch_bounds__(T) void search_lxclear_kernel(unsigned long long* cand, long n) {
+  for (long i = (long)blockIdx.x * T + threadIdx.x; i < n; i += (long)gridDim.x * T) cand[i] = 0ull;
 }
 
 // search_pqxscan_kernel (HZ_K_SEARCH_PQXSCAN): the batch scan whose B operand is GATHERED from a bf16
@@ -1728,6 +1871,13 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(T) void search_qxscan_kernel(const HzS
 template <int NC>
 HZ_NO_PK_F32 __global__ __launch_bounds__(RESCORE_THREADS) void search_qrescore_kernel(const HzSearchQuantRescoreParams a) {
   rescore_body<E4m3Rows, NC>(a);
+}
+
+// search_rescorep_kernel (HZ_K_SEARCH_RESCOREP): rescore_body over bf16 rows held in stored order, the
+// candidates external ids. A kernel of its own for its block and for the attribute.
+template <int NC>
+HZ_NO_PK_F32 __global__ __launch_bounds__(RESCORE_THREADS) void search_rescorep_kernel(const HzSearchRescorePosParams a) {
+  rescore_body<Bf16Rows, NC>(a);
 }
 
 // ------------------------------------------------------------------------- nearest centroid, means
@@ -2446,8 +2596,9 @@ int batch_launch(void (*kernel)(P), P& p, size_t lds_bytes, bool (&raised)[64], 
   hipLaunchKernelGGL(kernel, dim3(p.ntile, (p.Q + QB - 1) / QB), dim3(T), lds_bytes, st, p);
   return (int)hipGetLastError();
 }
-bool mscan_raised[64], xscan_raised[64], pqxscan_raised[64], qxscan_raised[64];
+bool mscan_raised[64], xscan_raised[64], pqxscan_raised[64], qxscan_raised[64], lxscan_raised[64];
 constexpr size_t QXSCAN_LDS = XSCAN_LDS + (size_t)T * 4;  // the tile's scales after the live words
+constexpr size_t LXSCAN_LDS = XSCAN_LDS + 2 * (size_t)QB * 4;  // the item's queries and slots after the live words
 
 }  // namespace
 
@@ -2544,6 +2695,54 @@ extern "C" int hz_search_qrescore_launch(const HzSearchQuantRescoreParams* pp, h
   return (int)hipGetLastError();
 }
 
+// The list batch scan's refusals (hipzap.h), one code per rule; then the clear of all P*Q*k keys and the scan, one
+// workgroup per item.
+extern "C" int hz_search_lxscan_launch(const HzSearchListBatchParams* pp, hipStream_t st) {
+  HzSearchListBatchParams p = *pp;
+  unsigned bad = batch_rules(p, p.corpus, p.queries, 15, p.D, 8, HZ_SEARCH_SELF_MAX_Q);
+  if (!p.rowid || !p.items || !p.entries) bad |= R_NULL;
+  if ((reinterpret_cast<uintptr_t>(p.rowid) & 3) || (reinterpret_cast<uintptr_t>(p.items) & 3) || (reinterpret_cast<uintptr_t>(p.entries) & 3))
+    bad |= R_ALIGN;
+  if (p.N >= 1 && p.N % T) bad |= R_N;
+  if (const int rc = batch_refusal(bad, {{R_NULL, -189}, {R_DMOD, -190}, {R_DMIN, -191}, {R_DMAX, -192}, {R_LDC, -193}, {R_N, -194},
+                                         {R_Q, -195}, {R_K, -196}, {R_ALIGN, -197}, {R_LIVE, -198}}))
+    return rc;
+  if (p.P < 1 || (long long)p.P * T >= (1ll << 31)) return -199;
+  const unsigned long long keys = (unsigned long long)p.P * (unsigned long long)p.Q * (unsigned long long)p.k;
+  if (p.cand_bytes < keys * 8ull) return -200;
+  if (p.nwork < 1 || p.nent < 1) return -201;
+  if (p.items_bytes < (unsigned long long)p.nwork * HZ_SEARCH_LX_ITEM * 4ull) return -202;
+  if (p.entries_bytes < (unsigned long long)p.nent * HZ_SEARCH_LX_ENTRY * 4ull) return -203;
+  p.ntile = p.N / T;
+  if (const int rc = once_per_device(lxscan_raised, [&] { return raise_lds_limit_of(&search_lxscan_kernel, LXSCAN_LDS); })) return rc;
+  const unsigned clear_blocks = (unsigned)((keys + T - 1) / T < 4096ull ? (keys + T - 1) / T : 4096ull);
+  hipLaunchKernelGGL(search_lxclear_kernel, dim3(clear_blocks), dim3(T), 0, st, p.cand, (long)keys);
+  hipLaunchKernelGGL(search_lxscan_kernel, dim3(p.nwork), dim3(T), LXSCAN_LDS, st, p);
+  return (int)hipGetLastError();
+}
+
+// The stored-order rescore's refusals (hipzap.h): HZ_K_SEARCH_RESCOREN's rules under their own codes, then the table's.
+extern "C" int hz_search_rescorep_launch(const HzSearchRescorePosParams* pp, hipStream_t st) {
+  const HzSearchRescorePosParams a = *pp;
+  if (a.D < 8 || a.D % 8 || a.D > 2048 || a.ldc < a.D || a.ldc % 8) return -205;
+  if (a.N < 1) return -206;
+  if (a.Q < 1 || a.Q > HZ_SEARCH_SELF_MAX_Q) return -207;
+  if (a.R < 1 || a.R > HZ_SEARCH_MAX_K) return -208;
+  if (a.k < 1 || a.k > a.R) return -209;
+  if (!a.rows || !a.queries || !a.in_id || !a.out_score || !a.out_id || !a.pos) return -210;
+  if ((reinterpret_cast<uintptr_t>(a.rows) & 15) || (reinterpret_cast<uintptr_t>(a.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.in_id) & 3) || (reinterpret_cast<uintptr_t>(a.out_score) & 3) ||
+      (reinterpret_cast<uintptr_t>(a.out_id) & 3) || (reinterpret_cast<uintptr_t>(a.pos) & 3))
+    return -211;
+  if (a.npos < 1) return -212;
+  const int nc = (a.D + 64 * Bf16Rows::E - 1) / (64 * Bf16Rows::E);
+  if (nc == 1) hipLaunchKernelGGL(search_rescorep_kernel<1>, dim3(a.Q), dim3(RESCORE_THREADS), 0, st, a);
+  else if (nc == 2) hipLaunchKernelGGL(search_rescorep_kernel<2>, dim3(a.Q), dim3(RESCORE_THREADS), 0, st, a);
+  else if (nc == 3) hipLaunchKernelGGL(search_rescorep_kernel<3>, dim3(a.Q), dim3(RESCORE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(search_rescorep_kernel<4>, dim3(a.Q), dim3(RESCORE_THREADS), 0, st, a);
+  return (int)hipGetLastError();
+}
+
 // search_merge_kernel as it stands (its body has no limit on Q: one workgroup per query) behind the self scan's block
 extern "C" int hz_search_mergen_launch(const HzSearchSelfParams* pp, hipStream_t st) {
   HzSearchSelfParams s = *pp;
@@ -2606,5 +2805,6 @@ extern "C" int hz_search_code_warm(void) {
   if (const int rc = once_per_device(mscan_raised, [] { return raise_lds_limit_of(&search_mscan_kernel, MSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(xscan_raised, [] { return raise_lds_limit_of(&search_xscan_kernel, XSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(pqxscan_raised, [] { return raise_lds_limit_of(&search_pqxscan_kernel, XSCAN_LDS); })) return rc;
+  if (const int rc = once_per_device(lxscan_raised, [] { return raise_lds_limit_of(&search_lxscan_kernel, LXSCAN_LDS); })) return rc;
   return pq_device_setup(nullptr);
 }

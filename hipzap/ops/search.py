@@ -23,7 +23,9 @@ over external queries, each split into three bf16 terms; ``HZ_K_SEARCH_MERGEN`` 
 table ``cb8`` of :func:`hipzap.search.pq_table_bf16`) is the batch scan over product-quantised rows, each MFMA fragment
 gathered from that table by a code byte; ``HZ_K_SEARCH_PQRESCORE`` (``PqRescoreParams``) re-scores its candidates with ``HZ_K_SEARCH_PQSCAN``'s bits.
 ``HZ_K_SEARCH_QXSCAN`` (``QuantBatchScanParams``: the batch block over e4m3 byte rows, ``ldc`` in bytes, plus ``scales``)
-is the batch scan over fp8 rows, decoded to bf16 in registers; ``HZ_K_SEARCH_QRESCORE`` (``QuantRescoreParams``) re-scores
+is the batch scan over fp8 rows, decoded to bf16 in registers; ``HZ_K_SEARCH_LXSCAN`` (``ListBatchScanParams``) is the batch
+scan over a work list of (stored tile, up to 64 queries) items of an IVF index and ``HZ_K_SEARCH_RESCOREP``
+(``RescorePosParams``) the rescore of external ids against rows in stored order; ``HZ_K_SEARCH_QRESCORE`` (``QuantRescoreParams``) re-scores
 its candidates with ``HZ_K_SEARCH_QSCAN``'s bits.
 ``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
@@ -244,6 +246,32 @@ class QuantRescoreParams(C.Structure):
                 ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("R", C.c_int), ("k", C.c_int), ("ldc", C.c_int)]
 
 
+@N.params_of("HZ_K_SEARCH_LXSCAN")
+class ListBatchScanParams(C.Structure):
+    """HzSearchListBatchParams: the fields of ``BatchScanParams`` over the stored rows of an IVF index (``N`` a whole
+    number of tiles; ``cand`` holds [P][Q][k] keys), then ``rowid`` (int32 [N]), the work list -- ``items`` (device int32
+    [nwork][4]: tile, slot offset, first entry, nq) and ``entries`` (device int32 [nent][2]: query, base slot) with their
+    byte counts -- and ``nwork``, ``nent``, ``P``."""
+    _fields_ = BatchScanParams._fields_ + [("rowid", C.c_void_p), ("items", C.c_void_p), ("entries", C.c_void_p),
+                                           ("items_bytes", C.c_uint64), ("entries_bytes", C.c_uint64),
+                                           ("nwork", C.c_int), ("nent", C.c_int), ("P", C.c_int), ("pad2_", C.c_int)]
+
+    def merge_params(self) -> SelfScanParams:
+        """``HZ_K_SEARCH_MERGEN``'s block for this scan's candidates: ``ntile`` = P, so N = P * 256."""
+        mp = SelfScanParams.from_buffer_copy(self)
+        mp.N = self.P * 256
+        return mp
+
+
+@N.params_of("HZ_K_SEARCH_RESCOREP")
+class RescorePosParams(C.Structure):
+    """HzSearchRescorePosParams: ``RescoreParams`` over rows in stored order -- ``in_id`` / ``out_id`` are external ids
+    and ``pos`` (device int32 [npos]) maps an id to its stored row."""
+    _fields_ = [("rows", C.c_void_p), ("queries", C.c_void_p), ("in_id", C.c_void_p), ("out_score", C.c_void_p),
+                ("out_id", C.c_void_p), ("pos", C.c_void_p), ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int),
+                ("R", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("npos", C.c_int), ("pad_", C.c_int)]
+
+
 @N.params_of("HZ_K_SEARCH_ASSIGN")
 class AssignParams(C.Structure):
     """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
@@ -280,6 +308,11 @@ def _sigs(lib):
     N._sig(lib, "hz_search_qxscan_launch", C.c_int, C.POINTER(QuantBatchScanParams), P)
     N._sig(lib, "hz_search_qrescore_launch", C.c_int, C.POINTER(QuantRescoreParams), P)
     N._sig(lib, "hz_index_search_batch_q", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
+    N._sig(lib, "hz_search_lxscan_launch", C.c_int, C.POINTER(ListBatchScanParams), P)
+    N._sig(lib, "hz_search_rescorep_launch", C.c_int, C.POINTER(RescorePosParams), P)
+    N._sig(lib, "hz_index_probes_batch", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
+    N._sig(lib, "hz_index_search_batch_ivf", C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
+    N._sig(lib, "hz_index_search_batch_ivf_invert_us", C.c_double, P, C.c_int)
     N._sig(lib, "hz_index_neighbors", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_neighbors_max", C.c_int, P, C.c_int)
     N._sig(lib, "hz_search_tile_rows", C.c_int)
@@ -546,6 +579,22 @@ def launch_quant_batch(prm: QuantBatchScanParams, stream: int = 0) -> tuple:
 def launch_quant_rescore(prm: QuantRescoreParams, stream: int = 0) -> int:
     """The fp8 rescore (``HZ_K_SEARCH_QRESCORE``) on ``stream`` -> its code (0, or negative: nothing ran)."""
     return int(N.lib().hz_search_qrescore_launch(C.byref(prm), stream))
+
+
+def launch_list_batch(prm: ListBatchScanParams, stream: int = 0) -> tuple:
+    """The list batch scan (``HZ_K_SEARCH_LXSCAN``) then ``HZ_K_SEARCH_MERGEN`` over its P candidate slots on ``stream``:
+    (scan code, merge code); no merge after a refused scan."""
+    lib = N.lib()
+    rc = lib.hz_search_lxscan_launch(C.byref(prm), stream)
+    if rc:
+        return rc, None
+    mp = prm.merge_params()
+    return rc, lib.hz_search_mergen_launch(C.byref(mp), stream)
+
+
+def launch_rescore_pos(prm: RescorePosParams, stream: int = 0) -> int:
+    """The stored-order rescore (``HZ_K_SEARCH_RESCOREP``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_rescorep_launch(C.byref(prm), stream))
 
 
 def launch_rescore_n(prm: RescoreParams, stream: int = 0) -> int:

@@ -800,7 +800,7 @@ def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
                 ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
-                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host") -> dict:
+                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host", ivf_init=None) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -810,7 +810,8 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     into ``nlist`` lists by :func:`ivf_kmeans` (``ivf_seed``, ``ivf_iters``) and stored in :func:`ivf_layout`'s order;
     ``nprobe``: the lists a search scans by default, ``min(nlist, 16)`` when None. Ids stay the positions in
     ``vectors``. ``ivf_backend="gpu"``: the lists come from :meth:`Index.cluster` on ``device`` (:func:`cluster_rows`)
-    in place of :func:`ivf_kmeans`; the file has the same layout either way. ``dtype="bin"``: sign-bit rows
+    in place of :func:`ivf_kmeans`; the file has the same layout either way. ``ivf_init`` (fp32 [nlist, D], the ``"cpu"``
+    backend): :func:`ivf_kmeans`' starting centroids; with ``ivf_iters=0`` they ARE the index's centroids. ``dtype="bin"``: sign-bit rows
     (:func:`prepare_rows_bin`), a version-8 file, with ``rescore=True`` version 9. ``dtype="pq"``: rows of ``pq_m``
     code bytes and their codebook (:func:`prepare_rows_pq`: trained with ``pq_seed`` / ``pq_iters`` unless
     ``pq_codebook`` is given), a version-10 file, with ``rescore=True`` version 11; ``pq_backend`` (``"cpu"``,
@@ -862,7 +863,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
         hdr["labels"] = labels
     if ivf is not None:
         nlist, nprobe = _check_ivf_args(n, ivf, nprobe, ivf_seed, ivf_iters)
-        cbits, assign = _ivf_lists(rows, nlist, metric, int(ivf_seed), int(ivf_iters), ivf_backend, device, path)
+        cbits, assign = _ivf_lists(rows, nlist, metric, int(ivf_seed), int(ivf_iters), ivf_backend, device, path, ivf_init)
         lay = ivf_layout(assign, nlist)
         real = lay["rowid"] >= 0
         srows = np.zeros((real.size, d), np.uint16)
@@ -872,6 +873,8 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
             stags[real] = tags[lay["rowid"][real]]
         lay.update(centroids=cbits, nlist=nlist, nprobe=int(nprobe), seed=int(ivf_seed), iters=int(ivf_iters))
         return _write_file(path, hdr, srows, stags, real, ivf=lay)
+    if ivf_init is not None:
+        raise ValueError("ivf_init goes with ivf=nlist")
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows, pq=codebook)
 
 
@@ -907,10 +910,12 @@ def cluster_rows(bits: np.ndarray, nlist: int, metric: str, seed: int = 0, iters
     return cbits, assign
 
 
-def _ivf_lists(bits, nlist, metric, seed, iters, backend, device, near):
+def _ivf_lists(bits, nlist, metric, seed, iters, backend, device, near, init=None):
     if backend == "gpu":
+        if init is not None:
+            raise ValueError("ivf_init goes with ivf_backend='cpu'")
         return cluster_rows(bits, nlist, metric, seed, iters, device, near)
-    return ivf_kmeans(bf16_to_f32(bits), nlist, metric, seed, iters)
+    return ivf_kmeans(bf16_to_f32(bits), nlist, metric, seed, iters, init=init)
 
 
 def _check_ivf_args(n: int, ivf, nprobe, ivf_seed, ivf_iters):
@@ -1298,6 +1303,25 @@ def batch_certain(s_last, t_k, slack):
     return certain
 
 
+def centroid_norm_max(centroids) -> float:
+    """``cmax`` of :func:`probes_slack`: the largest 2-norm of a stored centroid (the widened bf16 table [nlist, D]), in
+    fp64."""
+    c64 = np.asarray(centroids, np.float64)
+    return float(np.sqrt((c64 * c64).sum(axis=1)).max())
+
+
+def probes_slack(q, cmax: float):
+    """E of :meth:`Index.probes_batch`'s certificate per query (float64 [Q]): :func:`batch_slack` with the rows' bound
+    taken from the table itself, ``cmax`` from :func:`centroid_norm_max`. It needs no normalisation, so it holds for
+    ``ip`` indexes and for centroids the caller gave (``ivf_init``) as well:
+    E = (beta(3D) + gamma(D)) * ||q||_2 * cmax + 3 * 2^-126 * sqrt(D) * cmax."""
+    q64 = np.asarray(q, np.float64)
+    d = q64.shape[1]
+    beta = 3 * d * 2.0 ** -23 / (1 - 3 * d * 2.0 ** -23)
+    gamma = d * 2.0 ** -24 / (1 - d * 2.0 ** -24)
+    return (beta + gamma) * np.sqrt((q64 * q64).sum(axis=1)) * cmax + 3 * 2.0 ** -126 * np.sqrt(d) * cmax
+
+
 def pq_batch_slack(q, codebook):
     """E of :meth:`Index.search_batch_pq`'s certificate on an index without bf16 rows, per query (float64 [Q]). Let x^ be
     a row's reconstruction from the fp32 codebook, xb the same row from the bf16 table (:func:`pq_table_bf16`), S its
@@ -1545,6 +1569,33 @@ class _Base:
             raise ValueError(f"search_batch needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
         k = check_k(k)
         return k, batch_candidates(k, candidates)
+
+    def _check_batch_ivf(self, what: str):
+        """The refusals that :meth:`probes_batch` and :meth:`search_batch_ivf` (``what``) share, on both backends."""
+        if self.ivf is None or self.dtype != "bf16":
+            this = "an fp8 IVF index" if self.ivf is not None else f"a {self.dtype} index without lists"
+            raise ValueError(f"{what} is built for IVF indexes over bf16 rows (version 5; not the fp8 IVF indexes of "
+                             f"versions 6 and 7): this one is {this} of version {self.version}")
+        if self.dim % 32:
+            raise ValueError(f"{what} needs dim % 32 == 0 (one MFMA step is 32 columns), got dim = {self.dim}")
+
+    def _cmax(self) -> float:
+        """:func:`centroid_norm_max` of the stored table, computed once: the centroids of an open index never change."""
+        if getattr(self, "_cmax_value", None) is None:
+            self._cmax_value = centroid_norm_max(bf16_to_f32(self.ivf["centroids"]))
+        return self._cmax_value
+
+    def _finish_batch_ivf(self, q, k, lists, s, i, last, pcertain, fallback, ctx=None):
+        """The certificate of :meth:`search_batch_ivf` and its fallback over the uncertain queries."""
+        certain = batch_certain(last, s[:, k - 1] if len(q) else last, batch_slack(q, self.metric))
+        if pcertain is not None:
+            certain &= pcertain
+        if fallback and not certain.all():
+            todo = np.flatnonzero(~certain)
+            kw = {} if ctx is None else {"ctx": ctx}
+            s[todo], i[todo] = self.search(q[todo], k, nprobe=lists or "all", **kw)
+            certain[:] = True
+        return s, i, certain
 
     def _check_batch_pq(self, k, candidates, fallback):
         """The refusals of :meth:`search_batch_pq` that both backends share -> (k, R, fallback)."""
@@ -1840,6 +1891,48 @@ class RefIndex(_Base):
             s[todo], i[todo] = self.search(q[todo], k)
             certain[:] = True
         return s, i, certain
+
+    def probes_batch(self, q, nprobe: int, *, candidates=None, fallback: bool = True, ctx=None):
+        """:meth:`Index.probes_batch` on the host, its oracle: :meth:`search_batch`'s two stages over the centroid table
+        (fp64 over the SPLIT query at k = Rc, then :func:`rescore_ref` Rc -> nprobe) and the same certificate ->
+        (lists int32 [Q, nprobe], certain bool [Q])."""
+        self._check_batch_ivf("probes_batch")
+        q, nprobe = self._check_probes(q, nprobe)
+        Rc = batch_candidates(nprobe, candidates)
+        h, m, l = split3(q)
+        eff = h.astype(np.float64) + m.astype(np.float64) + l.astype(np.float64)
+        s1, i1 = search_ref(self._cent, eff, Rc)
+        two = [rescore_ref(self._cent, q[a], i1[a], nprobe) for a in range(q.shape[0])]
+        s = np.stack([t[0] for t in two]) if two else np.zeros((0, nprobe))
+        lists = (np.stack([t[1] for t in two]) if two else np.zeros((0, nprobe))).astype(np.int32)
+        certain = batch_certain(s1[:, Rc - 1], s[:, nprobe - 1].astype(np.float32), probes_slack(q, self._cmax()))
+        if fallback and not certain.all():
+            todo = np.flatnonzero(~certain)
+            lists[todo] = self.probes(q[todo], nprobe)
+            certain[:] = True
+        return lists, certain
+
+    def search_batch_ivf(self, q, k: int = 10, *, nprobe=None, candidates=None, fallback: bool = True, ctx=None):
+        """:meth:`Index.search_batch_ivf` on the host, its oracle: :meth:`probes_batch`, then :meth:`search_batch`'s two
+        stages over the live rows of the probed lists (every list in the exhaustive mode) and both certificates."""
+        self._check_batch_ivf("search_batch_ivf")
+        k = check_k(k)
+        R = batch_candidates(k, candidates)
+        q = check_queries(q, self.dim)
+        lists = self._nprobe(nprobe)
+        pcertain = None
+        with self._mut:
+            allow = np.broadcast_to(self._live, (q.shape[0], self._live.shape[0]))
+            if lists:
+                probes, pcertain = self.probes_batch(q, lists, fallback=fallback)
+                allow = allow & (self.ivf["list_of"][None, :, None] == probes[:, None, :]).any(axis=2)
+            h, m, l = split3(q)
+            eff = h.astype(np.float64) + m.astype(np.float64) + l.astype(np.float64)
+            s1, i1 = search_ref(self._rows, eff, R, allow)
+            two = [rescore_ref(self._rows, q[a], i1[a], k) for a in range(q.shape[0])]
+            s = (np.stack([t[0] for t in two]) if two else np.zeros((0, k))).astype(np.float32)
+            i = (np.stack([t[1] for t in two]) if two else np.zeros((0, k))).astype(np.int32)
+        return self._finish_batch_ivf(q, k, lists, s, i, s1[:, R - 1], pcertain, fallback)
 
     def search_batch_pq(self, q, k: int = 10, *, candidates=None, fallback=None, ctx=None):
         """:meth:`Index.search_batch_pq` on the host, its oracle: the rows decoded through :func:`pq_table_bf16`, stage
@@ -2138,6 +2231,71 @@ class Index(_Base):
                 scores[todo], ids[todo] = self.search(q[todo], k, ctx=c)
                 certain[:] = True
         return scores, ids, certain
+
+    def probes_batch(self, q, nprobe: int, *, candidates=None, fallback: bool = True, ctx: int | None = None):
+        """The coarse stage for many queries at once -> (lists int32 [Q, nprobe], certain bool [Q]):
+        :meth:`search_batch`'s program over the centroid table -- the MFMA batch scan keeps ``candidates`` lists per query
+        (Rc: ``None`` for ``min(128, max(4 nprobe, nprobe + 32))``, else nprobe..128), :meth:`probes`' own arithmetic
+        re-scores them and returns the best ``nprobe``, best first. ``certain[q]``: the lists are PROVEN equal to
+        ``probes(q[None], nprobe)`` -- ``s_Rc == -inf`` (fewer than Rc lists) or ``s_Rc + E <`` the nprobe-th returned
+        score, E from :func:`probes_slack`: its bound on the rows is the largest norm of a stored centroid, so it holds
+        on ``ip`` indexes and for ``init`` centroids too. ``fallback``: the uncertain queries are re-run through
+        :meth:`probes`. A version-5 index with ``dim % 32 == 0``; Q above the per-call maximum is split here."""
+        self._check_batch_ivf("probes_batch")
+        q, nprobe = self._check_probes(q, nprobe)
+        Rc = batch_candidates(nprobe, candidates)
+        nq = q.shape[0]
+        lists = np.empty((nq, nprobe), np.int32)
+        t_n, last = np.empty(nq, np.float32), np.empty(nq, np.float32)
+        with self._in_parts("hz_index_probes_batch", (-4, -213, -214, -215, -216), q, (nprobe, Rc), (lists, t_n, last), ctx) as c:
+            certain = batch_certain(last, t_n, probes_slack(q, self._cmax()))
+            if fallback and not certain.all():
+                todo = np.flatnonzero(~certain)
+                lists[todo] = self.probes(q[todo], nprobe, ctx=c)
+                certain[:] = True
+        return lists, certain
+
+    def search_batch_ivf(self, q, k: int = 10, *, nprobe=None, candidates=None, fallback: bool = True, ctx: int | None = None):
+        """Many fp32 queries at once over an IVF index -> (scores float32 [Q, k], ids int32 [Q, k],
+        certain bool [Q]). ``nprobe`` as in :meth:`search`: ``None`` for ``self.nprobe``, ``"all"`` or a value from
+        nlist up for every list (the exhaustive mode, no coarse stage). The lists come from :meth:`probes_batch`; the
+        host groups the queries by probed list and the MFMA batch scan scores each stored tile ONCE against up to 64
+        queries that probe its list, keeping ``candidates`` rows per query (R as in :meth:`search_batch`); stage two
+        re-scores those R with :meth:`search`'s own arithmetic and order (score, then the lower id). ``certain[q]``: the
+        lists are certain AND :meth:`search_batch`'s row certificate holds (:func:`batch_slack`: ``cosine`` only; on
+        ``ip`` only "fewer than R live rows in the probed lists" certifies) -- then the answer equals
+        ``search(q[None], k, nprobe=nprobe)`` in ids and score bits. ``fallback``: the uncertain queries are re-run
+        through :meth:`search`. A version-5 index with ``dim % 32 == 0``; no ``filter``; Q above the per-call maximum
+        is split here."""
+        self._check_batch_ivf("search_batch_ivf")
+        k = check_k(k)
+        R = batch_candidates(k, candidates)
+        q = check_queries(q, self.dim)
+        lists = self._nprobe(nprobe)
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        nq = q.shape[0]
+        scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
+        last = np.empty(nq, np.float32)
+        c = self._free.get() if ctx is None else ctx
+        try:
+            probes, pcertain = self.probes_batch(q, lists, fallback=fallback, ctx=c) if lists else (None, None)
+            step = int(self._lib.hz_index_neighbors_max(self._h, 0))
+            for a in range(0, nq, step):
+                part = np.ascontiguousarray(q[a:a + step])
+                pr = None if probes is None else np.ascontiguousarray(probes[a:a + step])
+                rc = self._lib.hz_index_search_batch_ivf(self._h, c, part.ctypes.data, part.shape[0],
+                                                         None if pr is None else pr.ctypes.data, lists, k, R,
+                                                         scores[a:a + step].ctypes.data, ids[a:a + step].ctypes.data,
+                                                         last[a:a + step].ctypes.data)
+                if rc in (-4, -5, -213, -214, -215, -216, -217):
+                    raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
+                if rc:
+                    raise RuntimeError(f"hz_index_search_batch_ivf failed with code {rc}")
+            return self._finish_batch_ivf(q, k, lists, scores, ids, last, pcertain, fallback, ctx=c)
+        finally:
+            if ctx is None:
+                self._free.put(c)
 
     def search_batch_pq(self, q, k: int = 10, *, candidates=None, fallback=None, ctx: int | None = None):
         """Many fp32 queries at once over a pq8 index -> (scores float32 [Q, k], ids int32 [Q, k], certain
