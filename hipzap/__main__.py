@@ -136,6 +136,10 @@ def cmd_index(a):
     pq = {} if a.dtype != "pq" else {"pq_m": a.pq_m, "pq_iters": 10 if a.pq_iters is None else a.pq_iters,
                                      "pq_seed": a.pq_seed or 0, "pq_backend": a.pq_backend or "cpu",
                                      "pq_means": a.pq_means or "host"}
+    if a.graph is None and a.graph_backend != "cpu":
+        raise SystemExit("index: --graph-backend goes with --graph DEG")
+    if a.graph is not None:
+        pq = dict(pq, graph=a.graph, graph_backend=a.graph_backend)  # the writers' further keywords
     if a.rescore and a.dtype not in ("fp8", "bin", "pq"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
@@ -198,7 +202,7 @@ def cmd_index(a):
                               rescore=a.rescore, ivf=a.ivf, nprobe=a.nprobe, ivf_seed=a.ivf_seed or 0,
                               ivf_backend=a.ivf_backend, device=a.device, **pq)
         except ValueError as e:
-            if a.dtype != "pq":
+            if a.dtype != "pq" and a.graph is None:
                 raise
             raise SystemExit(f"index: {e}") from None
     print(json.dumps({"out": a.out, **{k: v for k, v in hdr.items() if k != "labels"}, "labels": labels is not None}))
@@ -368,6 +372,11 @@ def main(argv=None):
     ix.add_argument("--ivf-seed", type=int, default=None, help="with --ivf: the k-means seed (0)")
     ix.add_argument("--ivf-backend", choices=["cpu", "gpu"], default="cpu",
                     help="with --ivf: where k-means runs; gpu: Index.cluster on --device (dim %% 32 == 0)")
+    ix.add_argument("--graph", type=int, default=None, metavar="DEG",
+                    help="a version-12 file: plain bf16 rows plus their neighbour graph of degree DEG (a multiple of 8 in "
+                         "8..64) for Index.search_graph")
+    ix.add_argument("--graph-backend", choices=["cpu", "gpu"], default="cpu",
+                    help="with --graph: where the kNN lists come from; gpu: Index.knn_graph on --device (dim %% 32 == 0)")
     ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept); an IVF file keeps its lists "
                          "(versions 6 and 7), --ivf NLIST builds lists over a plain file's stored rows")
     ix.add_argument("--model", default=None, help="free text kept in the header")

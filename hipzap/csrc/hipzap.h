@@ -972,6 +972,44 @@ typedef struct HzSearchRescorePosParams {
   int N, D, Q, R, k, ldc, npos, pad_;
 } HzSearchRescorePosParams;
 int hz_search_rescorep_launch(const HzSearchRescorePosParams* p, hipStream_t st);
+// graph search (HZ_K_SEARCH_GRAPH): a beam search over a fixed-degree neighbour graph of the corpus. One
+// workgroup of 256 threads per query walks the graph and writes the final out_score / out_id [Q][k] itself: no candidate
+// scratch, no merge launch. graph[r][0..deg) are the neighbours of row r; an entry outside [0, N) is padding and is
+// skipped, duplicate edges and self-loops are legal. `entries` are the E starting rows, shared by all queries.
+// THE WALK is stated over sets, so the answer is a function of the inputs alone. Keys are the project's:
+// (orderable(score) << 32) | ~id, higher score first, then the lower id. State: the visited set V and the beam B of at
+// most `beam` keys, each with an "expanded" flag.
+//   start:     V = the distinct valid entry ids; score them; B = the best `beam` of them, all unexpanded.
+//   iteration (at most `iters` times): the parents are the best `width` unexpanded keys of B -- none: stop. Mark them
+//              expanded. C = the valid ids in the parents' graph rows that are not in V. V = V u C. Score every row of
+//              C. B = the best `beam` of B u C; flags travel with their keys, new keys are unexpanded.
+//   answer:    the best k of B; the slots past |B| hold -inf / -1 (HZ_K_SEARCH_RESCORE's layout).
+// out_stats (may be null): int32 [Q][2] = {iterations that found a parent, rows scored (the entries included)}.
+// CONTRACT. score(q, r) has exactly the bits of HZ_K_SEARCH_SCAN for that query and that bf16 row (the scan template's
+// own statements at Q = 1), so a graph search, a scan and a rescore agree on every score they share.
+// V is an open-addressing table in LDS of HZ_SEARCH_GRAPH_CAP_SMALL or HZ_SEARCH_GRAPH_CAP_LARGE slots; the launcher
+// takes the smallest whose HALF holds the bound E + iters * width * deg on |V| and refuses a search above half of the
+// large one: the walk is never truncated.
+// Refusals (nothing is launched, one code per rule): -218 D % 8, D outside 8..2048, ldc < D or ldc % 8; -219 N < 1 (N
+// is an int: below 2^31); -220 Q outside 1..HZ_SEARCH_SELF_MAX_Q; -221 k outside 1..min(beam, HZ_SEARCH_MAX_K); -222
+// beam outside 32..HZ_SEARCH_GRAPH_MAX_BEAM or beam % 32; -223 deg outside 8..64 or deg % 8; -224 width outside
+// 1..256 / deg; -225 iters < 1; -226 E outside 1..256; -227 E + iters * width * deg > HZ_SEARCH_GRAPH_CAP_LARGE / 2;
+// -228 corpus, queries, graph, entries, out_score or out_id null; -229 corpus or queries not 16-B aligned or graph,
+// entries, out_score, out_id or out_stats not 4-B aligned.
+#define HZ_SEARCH_GRAPH_MAX_BEAM 256
+#define HZ_SEARCH_GRAPH_CAP_SMALL 4096
+#define HZ_SEARCH_GRAPH_CAP_LARGE 16384
+typedef struct HzSearchGraphParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows (ldc % 8 == 0), ldc >= D
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const int* graph;              // device int32 [N][deg]
+  const int* entries;            // device int32 [E]
+  float* out_score;              // fp32 [Q][k]
+  int* out_id;                   // int32 [Q][k]
+  int* out_stats;                // int32 [Q][2] or null
+  int N, D, Q, k, ldc, beam, deg, width, iters, E;
+} HzSearchGraphParams;
+int hz_search_graph_launch(const HzSearchGraphParams* p, hipStream_t st);
 // nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
 // of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
 // of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
@@ -1230,6 +1268,22 @@ int hz_index_search_batch_ivf(void* idx, int ctx, const float* queries, int Q, c
                               float* out_score, int* out_id, float* out_stage1_last);
 // microseconds the host inversion of the context's last hz_index_search_batch_ivf call took (measurement only)
 double hz_index_search_batch_ivf_invert_us(void* idx, int ctx);
+// graph search over an open index (a plain bf16 index, versions 1 and 2, every row live and the rows as
+// the file holds them). hz_index_set_graph uploads a neighbour graph (host int32 [n][deg], n = the index's rows; an
+// entry outside [0, n) is padding) and its E entry rows once, replacing an earlier one; it takes every context's mutex.
+// -230: not a plain bf16 index; -231: n is not the index's row count, or rows were added or deleted; -232: deg outside
+// 8..64 or deg % 8, or E outside 1..256.
+// hz_index_search_graph replays, per (Q, k, beam, width, iters), H2D of the queries, HZ_K_SEARCH_GRAPH and three D2H:
+// out_score fp32 [Q][k], out_id int32 [Q][k] (-inf / -1 past the rows the walk reached) and out_stats int32 [Q][2].
+// -4: Q outside 1..the maximum; -5: k outside 1..min(beam, HZ_SEARCH_MAX_K); -233: no graph; -234: rows were added or
+// deleted since the graph was attached; -235: beam; -236: width outside 1..256 / deg; -237: iters < 1 or the visited
+// bound (hz_index_last_error names the value in each case).
+// A version-12 file (version 1 plus "graph_deg", "graph_off", "entries", "entries_off": int32 graph [count][graph_deg] and the
+// entry rows, two 4096-aligned blocks after the rows) is opened by hz_index_open* with its graph attached;
+// hz_index_describe3's out[6] is the attached graph's degree (0: none) and out[7] its number of entries.
+int hz_index_set_graph(void* idx, const int* graph, long long n, int deg, const int* entries, int E);
+int hz_index_search_graph(void* idx, int ctx, const float* queries, int Q, int k, int beam, int width, int iters,
+                          float* out_score, int* out_id, int* out_stats);
 // clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
 // context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
 // and grown on demand (a call that needs no more than an earlier one allocates nothing).
@@ -1467,7 +1521,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_QXSCAN, 52, HzSearchQuantBatchParams, hz_search_qxscan_op, SEARCH) \
   X(SEARCH_QRESCORE, 53, HzSearchQuantRescoreParams, hz_search_qrescore_op, SEARCH) \
   X(SEARCH_LXSCAN, 54, HzSearchListBatchParams, hz_search_lxscan_op, SEARCH) \
-  X(SEARCH_RESCOREP, 55, HzSearchRescorePosParams, hz_search_rescorep_op, SEARCH)
+  X(SEARCH_RESCOREP, 55, HzSearchRescorePosParams, hz_search_rescorep_op, SEARCH) \
+  X(SEARCH_GRAPH, 56, HzSearchGraphParams, hz_search_graph_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -95,6 +95,8 @@ std::nullptr_t fail(const std::string& m) {
 constexpr uint64_t kTile = HZ_SEARCH_TILE;
 constexpr size_t kFiltBytes = (size_t)HZ_SEARCH_MAX_Q * 2 * 4;  // [MAX_Q][2] u32 in front of the queries
 
+enum { kProgGraph = 8 };  // the third field of a program key; 0 .. 7 are listed at Ctx::progs
+
 struct Ctx {
   std::mutex mu;
   hipStream_t st = nullptr;
@@ -142,6 +144,7 @@ struct Ctx {
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
   // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0), on
   // fp8 rows (Q, k, 6, R, 0); the coarse stage of a bulk search over an IVF index: (Q, nprobe, 7, Rc, 0)
+  // graph search: (Q, k, kProgGraph, beam * 1024 + width, iters)
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
@@ -202,6 +205,11 @@ struct Index {
   std::vector<int32_t> lists_host;    // list_off [nlist + 1], then list_tiles [tiles]: the host's copy for the bulk search
   int* pos_dev = nullptr;             // device int32 [n_ext]: pos_of, uploaded on the first bulk search
   unsigned* cent_live = nullptr;      // device, ceil(nlist / 32) words of ones: the centroid table's bitmap, likewise
+  // a neighbour graph attached with hz_index_set_graph: device int32 graph [graph_n][graph_deg], then
+  // the graph_e entry rows; null: none
+  int* graph_dev = nullptr;
+  uint64_t graph_n = 0;
+  int graph_deg = 0, graph_e = 0;
   std::vector<std::unique_ptr<Ctx>> ctx;
 
   ~Index() {
@@ -246,6 +254,7 @@ struct Index {
     if (ivf_tables) (void)hipFree(ivf_tables);
     if (pos_dev) (void)hipFree(pos_dev);
     if (cent_live) (void)hipFree(cent_live);
+    if (graph_dev) (void)hipFree(graph_dev);
   }
 
   // the stored row of a public id, -1 for an id outside the index
@@ -464,6 +473,39 @@ struct Index {
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
     if (!rc) rc = by_codebook || by_codes ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0)
                               : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
+  // The graph-search program of (Q, k, beam, width, iters) (the caller holds c.mu): H2D of the queries,
+  // HZ_K_SEARCH_GRAPH -- one launch, a static grid of Q workgroups -- into bout_dev, the stats into bmid_dev, three D2H.
+  HzProgram graph_program(Ctx& c, int Q, int k, int beam, int width, int iters, bool* fresh) {
+    if (!batch_buffers(c)) return nullptr;
+    const auto key = std::make_tuple(Q, k, (int)kProgGraph, beam * 1024 + width, iters);  // beam <= 256, width <= 32
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    HzSearchGraphParams p{};
+    p.corpus = rows;
+    p.queries = c.bq_dev;
+    p.graph = graph_dev;
+    p.entries = graph_dev + graph_n * (uint64_t)graph_deg;
+    p.out_score = reinterpret_cast<float*>(c.bout_dev);
+    p.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    p.out_stats = reinterpret_cast<int*>(c.bmid_dev);
+    p.N = (int)graph_n, p.D = p.ldc = (int)h.dim, p.Q = Q, p.k = k;
+    p.beam = beam, p.deg = graph_deg, p.width = width, p.iters = iters, p.E = graph_e;
+    HzProgram g = hz_prog_create();
+    const size_t qk = (size_t)Q * k * 4;
+    int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_GRAPH, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * 8, 0);
     if (rc) {
       hz_prog_destroy(g);
       return nullptr;
@@ -777,6 +819,7 @@ int push_words(unsigned* dev, const std::vector<uint32_t>& host, uint64_t w0, ui
 extern "C" {
 
 const char* hz_index_last_error(void) { return g_err.c_str(); }
+int hz_index_set_graph(void* h, const int* graph, long long n, int deg, const int* entries, int E);
 
 void* hz_index_open3(const char* path, int device, int nctx, long long reserve_rows, int rescore_host) {
   g_err.clear();
@@ -789,13 +832,13 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 11 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 12 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 11) return fail("index: unknown format version " + std::to_string(h.version));
+  if (h.version < 1 || h.version > 12) return fail("index: unknown format version " + std::to_string(h.version));
   const bool ivf = h.version >= 5 && h.version <= 7;
   const bool fp8 = h.version == 3 || h.version == 4 || h.version == 6 || h.version == 7;
   const bool bin = h.version == 8 || h.version == 9;
@@ -810,6 +853,18 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
   if (!ivf && js.rfind("\"ivf\": {") != std::string::npos)
     return fail("index: an ivf block in a " + vname + " file (it belongs to versions 5, 6 and 7)");
+  const bool with_graph = h.version == 12;  // version 1 plus the graph and entries blocks
+  uint64_t gr_u[4] = {0, 0, 0, 0};  // graph_deg, graph_off, entries, entries_off
+  if (with_graph) {
+    static const char* keys[4] = {"graph_deg", "graph_off", "entries", "entries_off"};
+    for (int i = 0; i < 4; ++i)
+      if (!json_u64(js, keys[i], &gr_u[i], true)) return fail(std::string("index: a version-12 file without ") + keys[i]);
+    if (gr_u[0] < 8 || gr_u[0] > 64 || gr_u[0] % 8 || gr_u[2] < 1 || gr_u[2] > 256)
+      return fail("index: a graph needs graph_deg % 8 == 0 in 8..64 and 1..256 entries, got graph_deg = " + std::to_string(gr_u[0]) +
+                  ", entries = " + std::to_string(gr_u[2]));
+  } else if (js.rfind("\"graph_off\":") != std::string::npos) {
+    return fail("index: graph keys in a " + vname + " file (they belong to version 12)");
+  }
   uint64_t pq_u[4] = {0, 0, 0, 0};  // m, ksub, dsub, codebook_off
   if (pq) {
     static const char* keys[4] = {"m", "ksub", "dsub", "codebook_off"};
@@ -890,6 +945,31 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
         tags_off > fsize || tag_bytes > fsize - tags_off || live_off > fsize || live_bytes > fsize - live_off)
       return fail("index: tags or live block outside the file");
     after_rows = std::max(after_rows, std::max(tags_off + tag_bytes, live_off + live_bytes));
+  }
+  std::vector<int32_t> graph_host;  // graph [count][deg], then the entries
+  if (with_graph) {
+    const uint64_t len[2] = {h.count * gr_u[0] * 4, gr_u[2] * 4}, off[2] = {gr_u[1], gr_u[3]};
+    graph_host.resize(h.count * gr_u[0] + gr_u[2]);
+    char* dst = reinterpret_cast<char*>(graph_host.data());
+    const int gfd = open(path, O_RDONLY | O_CLOEXEC);
+    bool ok = gfd >= 0;
+    for (int i = 0; i < 2; ++i) {
+      if (off[i] % 4096 || off[i] < after_rows || off[i] > fsize || len[i] > fsize - off[i]) {
+        if (gfd >= 0) close(gfd);
+        return fail("index: the graph or entries block is unaligned, overlaps another block or lies outside the file");
+      }
+      after_rows = off[i] + len[i];
+      uint64_t done = 0;
+      while (ok && done < len[i]) {
+        const ssize_t n = pread(gfd, dst + done, len[i] - done, (off_t)(off[i] + done));
+        if (n <= 0) break;
+        done += (uint64_t)n;
+      }
+      ok = ok && done == len[i];
+      dst += len[i];
+    }
+    if (gfd >= 0) close(gfd);
+    if (!ok) return fail("index: cannot read the graph blocks");
   }
   // the IVF tables: read, and checked before anything reaches the device -- the list scan trusts them
   const uint64_t ntile = h.count / kTile;
@@ -1086,6 +1166,9 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     if (hz_upload_file(path, 1, &rescore_off, &rescore_len, dst, st) || hipStreamSynchronize(st) != hipSuccess)
       return fail(std::string("index: rescore upload failed: ") + hz_plan_last_error());
   }
+  if (with_graph && hz_index_set_graph(idx.get(), graph_host.data(), (long long)h.count, (int)gr_u[0],
+                                       graph_host.data() + h.count * gr_u[0], (int)gr_u[2]))
+    return fail("index: graph upload failed" + (g_err.empty() ? std::string() : ": " + g_err));
   return idx.release();
 }
 
@@ -1132,7 +1215,7 @@ int hz_index_describe3(void* h, uint64_t* out) {
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
   const uint64_t v[8] = {x->ivf ? 1u : 0u, (uint64_t)x->nlist, (uint64_t)x->nprobe_default, x->ivf ? x->count / kTile : 0,
-                         x->ivf ? x->n_ext : x->count, x->h.version, 0, 0};
+                         x->ivf ? x->n_ext : x->count, x->h.version, (uint64_t)x->graph_deg, (uint64_t)x->graph_e};
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
@@ -1409,6 +1492,103 @@ int hz_index_neighbors(void* h, int ctx, const int* ids, int n, int k, int skip_
 int hz_index_search_batch(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                           float* out_stage1_last) {
   return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, Index::kBatchBf16);
+}
+
+// hz_index_set_graph / hz_index_search_graph (hipzap.h)
+int hz_index_set_graph(void* h, const int* graph, long long n, int deg, const int* entries, int E) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !graph || !entries) return -1;
+  AllLocked all(*x);
+  if (x->fp8 || x->ivf || x->bin || x->pq) {
+    g_err = std::string("index: a graph is searched over plain bf16 rows (versions 1 and 2), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->quant_name()) + " of version " +
+            std::to_string(x->h.version);
+    return -230;
+  }
+  if (x->mutated || n < 1 || (uint64_t)n != x->count) {
+    g_err = "index: a graph covers every row of an index whose rows are all live and unchanged since it was opened (" +
+            std::to_string(x->count) + " rows here), got a graph of " + std::to_string(n) + " rows";
+    return -231;
+  }
+  if (deg < 8 || deg > 64 || deg % 8 || E < 1 || E > 256) {
+    g_err = "index: a graph needs deg % 8 == 0 in 8..64 and 1..256 entries, got deg = " + std::to_string(deg) + ", " +
+            std::to_string(E) + " entries";
+    return -232;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  for (auto& c : x->ctx)  // the programs of an earlier graph hold its address by value
+    for (auto it = c->progs.begin(); it != c->progs.end();) {
+      if (std::get<2>(it->first) == kProgGraph) {
+        hz_prog_destroy(it->second);
+        it = c->progs.erase(it);
+      } else {
+        ++it;
+      }
+    }
+  if (x->graph_dev) (void)hipFree(x->graph_dev);
+  x->graph_dev = nullptr, x->graph_n = 0, x->graph_deg = x->graph_e = 0;
+  const size_t gwords = (size_t)n * deg;
+  if (hipMalloc(reinterpret_cast<void**>(&x->graph_dev), (gwords + E) * 4) != hipSuccess) {
+    x->graph_dev = nullptr;
+    return -11;
+  }
+  if (hipMemcpy(x->graph_dev, graph, gwords * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(x->graph_dev + gwords, entries, (size_t)E * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(x->graph_dev);
+    x->graph_dev = nullptr;
+    return -11;
+  }
+  x->graph_n = (uint64_t)n, x->graph_deg = deg, x->graph_e = E;
+  return 0;
+}
+
+int hz_index_search_graph(void* h, int ctx, const float* queries, int Q, int k, int beam, int width, int iters,
+                          float* out_score, int* out_id, int* out_stats) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_score || !out_id || !out_stats) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // the graph, count and self_max change only under every context's mutex
+  if (!x->graph_dev) {
+    g_err = "index: search_graph needs a graph (hz_index_set_graph), this index has none";
+    return -233;
+  }
+  if (x->mutated || x->count != x->graph_n) {
+    g_err = "index: the index changed since its graph was attached (add, delete): attach a graph of the rows it holds now";
+    return -234;
+  }
+  if (Q < 1 || Q > x->self_max) {
+    g_err = "index: search_graph takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
+    return -4;
+  }
+  if (beam < 32 || beam > HZ_SEARCH_GRAPH_MAX_BEAM || beam % 32) {
+    g_err = "index: beam must be a multiple of 32 in 32.." + std::to_string(HZ_SEARCH_GRAPH_MAX_BEAM) + ", got " + std::to_string(beam);
+    return -235;
+  }
+  if (k < 1 || k > HZ_SEARCH_MAX_K || k > beam) {
+    g_err = "index: k must be in 1..min(beam, " + std::to_string(HZ_SEARCH_MAX_K) + "), got " + std::to_string(k) + " with beam = " +
+            std::to_string(beam);
+    return -5;
+  }
+  if (width < 1 || width > 256 / x->graph_deg) {
+    g_err = "index: width must be in 1.." + std::to_string(256 / x->graph_deg) + " (256 / the graph's degree), got " + std::to_string(width);
+    return -236;
+  }
+  if (iters < 1 || (long long)x->graph_e + (long long)iters * width * x->graph_deg > HZ_SEARCH_GRAPH_CAP_LARGE / 2) {
+    g_err = "index: iters must be at least 1 with entries + iters * width * deg at most " + std::to_string(HZ_SEARCH_GRAPH_CAP_LARGE / 2) +
+            " (half the visited table), got iters = " + std::to_string(iters);
+    return -237;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->graph_program(c, Q, k, beam, width, iters, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  return run_program(c, g, fresh, [&] {
+    std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
+    std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
+    std::memcpy(out_stats, c.bout_host + 2 * kSelfOutHalf, (size_t)Q * 8);
+  });
 }
 
 int hz_index_search_batch_pq(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,

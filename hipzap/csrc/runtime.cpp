@@ -528,6 +528,10 @@ extern "C" __attribute__((weak)) int hz_search_rescorep_launch(const HzSearchRes
 static int hz_search_rescorep_op(const HzSearchRescorePosParams* p, hipStream_t st) {
   return hz_search_rescorep_launch ? hz_search_rescorep_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_graph_launch(const HzSearchGraphParams* p, hipStream_t st);
+static int hz_search_graph_op(const HzSearchGraphParams* p, hipStream_t st) {
+  return hz_search_graph_launch ? hz_search_graph_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

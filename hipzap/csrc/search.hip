@@ -1880,6 +1880,187 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(RESCORE_THREADS) void search_rescorep_
   rescore_body<Bf16Rows, NC>(a);
 }
 
+// ----------------------------------------------------------------------------------- graph search
+// search_graph_kernel<NC, CAP> (HZ_K_SEARCH_GRAPH): the beam search of hipzap.h over a fixed-degree
+// neighbour graph, one workgroup of GRAPH_THREADS per query, the whole walk in one launch. NC is the scan's 16-B chunks
+// per lane, CAP the slots of the visited table. The walk is a chain of dependent gathers (beam -> graph row -> corpus
+// rows -> beam), so a step is built to be short, not wide:
+//   * visited set: vt[CAP] int32 ids in LDS (dynamic), -1 = free, open addressing with linear probing from a
+//     multiplicative hash. An id is inserted with ONE compare-and-swap per probed slot: free -> the thread wins; the id
+//     itself -> another thread (of this step or an earlier one) holds it; any other id -> next slot. Slots are never
+//     freed, so two threads holding the same id probe the same slots and exactly one wins. WHICH one is not
+//     deterministic; the set of winners' ids is. The launcher keeps the table at most half full.
+//   * one thread per neighbour slot: thread t < npar * deg reads graph[parent t / deg][t % deg] (deg consecutive ints per
+//     parent: coalesced), inserts it, and the winners are compacted (ballot, wave counts) into lst[]: the rows to score.
+//   * scoring: wave w takes lst[] ROWS at a time from w * ROWS in steps of 4 ROWS, the rows' 16-byte loads in flight
+//     together, through score_group<Bf16Rows, NC> with one query: the scan's bits.
+//   * beam: two arrays of `beam` keys, best first, zeros past the count. A key is (orderable(score) << 32) | low,
+//     low = ((2^31 - 1 - id) << 1) | unexpanded: the project's order on (score, id), and since every id enters the beam
+//     at most once the flag bit never decides a comparison. Update: beam key i lands at i + (new keys above it), new key
+//     j at (beam keys above it: a binary search) + (new keys above it): a function of the key set alone. Keys ranked
+//     at or past `beam` are dropped.
+//   * parents: thread t holds beam slot t; the first `width` unexpanded slots in beam order (ballot, wave counts) are
+//     the parents, and their flag is cleared in place.
+// Addresses: queries[q*D + i] under i < D; entries[t] under t < E; graph[p*deg + j] under (unsigned)p < N (p was a
+// scored row) and j < deg; corpus rows lst[i]*ldc + chunk*8 under (unsigned)id < N -- checked before an id is inserted,
+// so everything in vt, lst and the beam is a row --; vt slots under the mask CAP - 1; beam slots under rank < beam;
+// lst / sk slots under pos < GRAPH_THREADS; out_*[q*k + t] under t < k; out_stats[2q], [2q + 1].
+// LDS: 8 KiB query, 2 x 2 KiB beam, 2 KiB new keys, 1 KiB scores, 1 KiB rows, 4 CAP bytes of table: 32.3 KiB or
+// 80.3 KiB, so at least two workgroups per CU.
+constexpr int GRAPH_THREADS = 256, GRAPH_MAX_BEAM = HZ_SEARCH_GRAPH_MAX_BEAM;
+static_assert(GRAPH_THREADS == T && GRAPH_MAX_BEAM <= GRAPH_THREADS, "score_group's row stride; one thread per beam slot");
+
+__device__ __forceinline__ unsigned graph_low(int id, bool unexpanded) {
+  return ((0x7fffffffu - (unsigned)id) << 1) | (unexpanded ? 1u : 0u);
+}
+__device__ __forceinline__ int graph_id_of(unsigned long long key) { return (int)(0x7fffffffu - ((unsigned)key >> 1)); }
+
+// flag per thread -> this thread's position among the workgroup's flagged threads (thread order) and their number.
+// One barrier; `wcnt` must not be written again before another barrier.
+__device__ __forceinline__ int graph_compact(bool flag, int lane, int w, int* wcnt, int& total) {
+  const unsigned long long bal = __ballot(flag);
+  int at = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+  if (lane == 0) wcnt[w] = __popcll(bal);
+  pqx_sync();
+  total = 0;
+#pragma unroll
+  for (int i = 0; i < GRAPH_THREADS / 64; ++i) {
+    const int c = wcnt[i];
+    at += i < w ? c : 0;
+    total += c;
+  }
+  return at;
+}
+
+// id into the visited table -> true iff this thread put it there
+template <int CAP>
+__device__ __forceinline__ bool graph_visit(int* vt, int id) {
+  unsigned s = ((unsigned)id * 2654435761u) >> (32 - __builtin_ctz(CAP));
+  for (int i = 0; i < CAP; ++i) {  // ends at a free slot: the table is at most half full
+    int seen = -1;
+    if (__hip_atomic_compare_exchange_strong(&vt[s & (CAP - 1)], &seen, id, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP))
+      return true;
+    if (seen == id) return false;
+    s = (s + 1) & (CAP - 1);
+  }
+  return HZ_DCHECK(false) && false;
+}
+
+template <int NC, int CAP>
+HZ_NO_PK_F32 __global__ __launch_bounds__(GRAPH_THREADS) void search_graph_kernel(const HzSearchGraphParams a) {
+  extern __shared__ int vt[];                                // [CAP] visited ids
+  __shared__ __attribute__((aligned(16))) float qs[2048];    // the query
+  __shared__ unsigned long long beam[2][GRAPH_MAX_BEAM];     // best first, 0 past the count
+  __shared__ unsigned long long sk[GRAPH_THREADS];           // the step's new keys
+  __shared__ unsigned sc[GRAPH_THREADS];                     // their orderable scores
+  __shared__ int lst[GRAPH_THREADS];                         // their rows
+  __shared__ int par[GRAPH_THREADS / 8];                     // the step's parents
+  __shared__ int wsel[GRAPH_THREADS / 64], wnew[GRAPH_THREADS / 64];
+  const int q = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int L = a.beam, nch = a.D >> 3;
+  if (!HZ_DCHECK(q < a.Q && a.D >= 8 && a.D % 8 == 0 && a.D <= NC * 64 * Bf16Rows::E && a.D <= 2048 && a.ldc >= a.D &&
+                 a.N >= 1 && L >= 32 && L <= GRAPH_MAX_BEAM && a.k >= 1 && a.k <= L && a.k <= HZ_SEARCH_MAX_K && a.deg >= 8 &&
+                 a.width >= 1 && a.width * a.deg <= GRAPH_THREADS && a.E >= 1 && a.E <= GRAPH_THREADS && a.iters >= 1 &&
+                 (long)a.E + (long)a.iters * a.width * a.deg <= CAP / 2))
+    return;
+  for (int i = t; i < a.D >> 2; i += GRAPH_THREADS)
+    reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(a.queries + (long)q * a.D)[i];
+  for (int i = t; i < CAP; i += GRAPH_THREADS) vt[i] = -1;
+  beam[0][t] = 0ull;
+  pqx_sync();
+
+  HzSearchParams one{};  // what score_group reads of the scan's block: one query of D values
+  one.Q = 1, one.D = a.D;
+  int cur = 0, cnt = 0, it = 0, scored = 0;
+  // The step's candidate row of each thread (anything outside [0, N): none) -> visited, scored, merged into the beam.
+  const auto admit = [&](int cand) __attribute__((always_inline)) {
+    bool won = false;
+    if ((unsigned)cand < (unsigned)a.N) won = graph_visit<CAP>(vt, cand);
+    int n;
+    const int at = graph_compact(won, lane, w, wnew, n);
+    if (won && HZ_DCHECK(at < GRAPH_THREADS)) lst[at] = cand;
+    pqx_sync();
+    if (n == 0) return;  // workgroup-uniform
+    for (int r0 = w * ROWS; r0 < n; r0 += GRAPH_THREADS / 64 * ROWS) {  // wave-uniform bounds; r0 + ROWS <= GRAPH_THREADS
+      GroupPass<false> pass;
+      pass.r0 = r0, pass.rows = n;
+      u32x4 v[ROWS][NC];  // this lane's chunks of the group's rows, zeros where nothing is loaded
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const int id = __builtin_amdgcn_readfirstlane(lst[r0 + r]);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          v[r][c] = u32x4{0u, 0u, 0u, 0u};
+          if (pass.row(r) && c * 64 + lane < nch && HZ_DCHECK((unsigned)id < (unsigned)a.N))
+            v[r][c] = *reinterpret_cast<const u32x4*>(a.corpus + (long)id * a.ldc + (c * 64 + lane) * Bf16Rows::E);
+        }
+      }
+      score_group<Bf16Rows, NC>(one, qs, sc, nullptr, v, pass, lane, nch, r0, n);
+    }
+    pqx_sync();
+    if (t < n) sk[t] = ((unsigned long long)sc[t] << 32) | graph_low(lst[t], true);
+    pqx_sync();
+    const unsigned long long* B = beam[cur];
+    unsigned long long* O = beam[cur ^ 1];
+    if (t < cnt) {  // beam slot t: its place among the beam is t
+      const unsigned long long key = B[t];
+      int rank = t;
+      for (int j = 0; j < n; ++j) rank += sk[j] > key;  // every lane reads the same word: an LDS broadcast
+      if (rank < L) O[rank] = key;
+    }
+    if (t < n) {
+      const unsigned long long key = sk[t];
+      int lo = 0, hi = cnt;  // the beam keys above this one: B is sorted, best first
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (B[mid] > key) lo = mid + 1;
+        else hi = mid;
+      }
+      int rank = lo;
+      for (int j = 0; j < n; ++j) rank += sk[j] > key;
+      if (rank < L) O[rank] = key;
+    }
+    cnt = min(L, cnt + n);
+    if (t >= cnt && t < L) O[t] = 0ull;
+    cur ^= 1, scored += n;
+    pqx_sync();
+  };
+
+  int cand = -1;
+  if (t < a.E) cand = a.entries[t];
+  admit(cand);
+  for (; it < a.iters; ++it) {
+    unsigned long long key = 0ull;
+    if (t < cnt) key = beam[cur][t];
+    const bool open = key & 1ull;
+    int nopen;
+    const int at = graph_compact(open, lane, w, wsel, nopen);
+    if (nopen == 0) break;  // workgroup-uniform
+    const int npar = min(a.width, nopen);
+    if (open && at < npar) {
+      par[at] = graph_id_of(key);
+      beam[cur][t] = key & ~1ull;
+    }
+    pqx_sync();
+    cand = -1;
+    if (t < npar * a.deg) {
+      const int p = par[t / a.deg];
+      if (HZ_DCHECK((unsigned)p < (unsigned)a.N)) cand = a.graph[(long)p * a.deg + t % a.deg];
+    }
+    admit(cand);
+  }
+
+  if (t < a.k) {
+    const unsigned long long key = t < cnt ? beam[cur][t] : 0ull;
+    const long at = (long)q * a.k + t;
+    a.out_score[at] = key ? unorderable((unsigned)(key >> 32)) : -__builtin_inff();
+    a.out_id[at] = key ? graph_id_of(key) : -1;
+  }
+  if (a.out_stats && t == 0) a.out_stats[2 * q] = it, a.out_stats[2 * q + 1] = scored;
+}
+
 // ------------------------------------------------------------------------- nearest centroid, means
 // search_assign_kernel (HZ_K_SEARCH_ASSIGN): the self scan with the roles turned. Workgroup `tile`
 // scores its T rows against all C centroids, CB at a time: the A operand is the centroid block (every workgroup
@@ -2600,7 +2781,56 @@ bool mscan_raised[64], xscan_raised[64], pqxscan_raised[64], qxscan_raised[64], 
 constexpr size_t QXSCAN_LDS = XSCAN_LDS + (size_t)T * 4;  // the tile's scales after the live words
 constexpr size_t LXSCAN_LDS = XSCAN_LDS + 2 * (size_t)QB * 4;  // the item's queries and slots after the live words
 
+// The graph search's instantiations: chunks per lane by D, table by the bound on the visited set. The large table is
+// 64 KiB of dynamic LDS: its limit is raised like the batch scans' (here or, for an index, in hz_search_code_warm).
+bool graph_raised[64];
+template <int NC = 1>
+int raise_graph_lds_limit() {
+  if (const int rc = raise_lds_limit_of(&search_graph_kernel<NC, HZ_SEARCH_GRAPH_CAP_LARGE>, HZ_SEARCH_GRAPH_CAP_LARGE * 4)) return rc;
+  if constexpr (NC < Bf16Rows::MAX_NC) return raise_graph_lds_limit<NC + 1>();
+  return 0;
+}
+template <int NC = 1>
+void graph_dispatch(const HzSearchGraphParams& a, bool large, hipStream_t st) {
+  if constexpr (NC < Bf16Rows::MAX_NC) {
+    if (a.D > NC * 64 * Bf16Rows::E) return graph_dispatch<NC + 1>(a, large, st);
+  }
+  if (large)
+    hipLaunchKernelGGL((search_graph_kernel<NC, HZ_SEARCH_GRAPH_CAP_LARGE>), dim3(a.Q), dim3(GRAPH_THREADS),
+                       HZ_SEARCH_GRAPH_CAP_LARGE * 4, st, a);
+  else
+    hipLaunchKernelGGL((search_graph_kernel<NC, HZ_SEARCH_GRAPH_CAP_SMALL>), dim3(a.Q), dim3(GRAPH_THREADS),
+                       HZ_SEARCH_GRAPH_CAP_SMALL * 4, st, a);
+}
+
 }  // namespace
+
+// The graph search's refusals (hipzap.h), one code per rule; then the smallest table whose half holds the visited bound.
+extern "C" int hz_search_graph_launch(const HzSearchGraphParams* pp, hipStream_t st) {
+  const HzSearchGraphParams a = *pp;
+  if (a.D < 8 || a.D % 8 || a.D > 2048 || a.ldc < a.D || a.ldc % 8) return -218;
+  if (a.N < 1) return -219;
+  if (a.Q < 1 || a.Q > HZ_SEARCH_SELF_MAX_Q) return -220;
+  if (a.k < 1 || a.k > a.beam || a.k > HZ_SEARCH_MAX_K) return -221;
+  if (a.beam < 32 || a.beam > HZ_SEARCH_GRAPH_MAX_BEAM || a.beam % 32) return -222;
+  if (a.deg < 8 || a.deg > 64 || a.deg % 8) return -223;
+  if (a.width < 1 || a.width > GRAPH_THREADS / a.deg) return -224;
+  if (a.iters < 1) return -225;
+  if (a.E < 1 || a.E > GRAPH_THREADS) return -226;
+  const long long bound = (long long)a.E + (long long)a.iters * a.width * a.deg;
+  if (bound > HZ_SEARCH_GRAPH_CAP_LARGE / 2) return -227;
+  if (!a.corpus || !a.queries || !a.graph || !a.entries || !a.out_score || !a.out_id) return -228;
+  if ((reinterpret_cast<uintptr_t>(a.corpus) & 15) || (reinterpret_cast<uintptr_t>(a.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.graph) & 3) || (reinterpret_cast<uintptr_t>(a.entries) & 3) ||
+      (reinterpret_cast<uintptr_t>(a.out_score) & 3) || (reinterpret_cast<uintptr_t>(a.out_id) & 3) ||
+      (reinterpret_cast<uintptr_t>(a.out_stats) & 3))
+    return -229;
+  const bool large = bound > HZ_SEARCH_GRAPH_CAP_SMALL / 2;
+  if (large)
+    if (const int rc = once_per_device(graph_raised, [] { return raise_graph_lds_limit(); })) return rc;
+  graph_dispatch(a, large, st);
+  return (int)hipGetLastError();
+}
 
 extern "C" unsigned long long hz_search_self_scratch_bytes(long long N, long long Q, int k) {
   if (N < 1 || N >= (1ll << 31) || Q < 1 || Q > HZ_SEARCH_SELF_MAX_Q || k < 1 || k > HZ_SEARCH_MAX_K) return 0;
@@ -2806,5 +3036,6 @@ extern "C" int hz_search_code_warm(void) {
   if (const int rc = once_per_device(xscan_raised, [] { return raise_lds_limit_of(&search_xscan_kernel, XSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(pqxscan_raised, [] { return raise_lds_limit_of(&search_pqxscan_kernel, XSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(lxscan_raised, [] { return raise_lds_limit_of(&search_lxscan_kernel, LXSCAN_LDS); })) return rc;
+  if (const int rc = once_per_device(graph_raised, [] { return raise_graph_lds_limit(); })) return rc;
   return pq_device_setup(nullptr);
 }

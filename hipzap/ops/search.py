@@ -29,6 +29,8 @@ scan over a work list of (stored tile, up to 64 queries) items of an IVF index a
 its candidates with ``HZ_K_SEARCH_QSCAN``'s bits.
 ``HZ_K_SEARCH_ASSIGN`` (``AssignParams``) writes the nearest of ``C`` bf16 centroids for every row of a tile with the
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
+``HZ_K_SEARCH_GRAPH`` (``GraphParams``) is the beam search over a fixed-degree neighbour graph of the corpus, one workgroup
+per query and the whole walk in one launch; its scores are ``HZ_K_SEARCH_SCAN``'s bits.
 ``HZ_K_SEARCH_PQLUT`` (``PqLutParams``) writes each query's table of inner products with the 256 sub-centroids of every
 sub-space of a product quantiser; ``HZ_K_SEARCH_PQSCAN`` (``PqScanParams``: the filtered block over uint8 code rows,
 ``ldc`` in bytes, plus the table) adds M table entries per row, one query's table resident in LDS per workgroup.
@@ -55,6 +57,9 @@ ASSIGN_MAX_C = 65536             # HZ_SEARCH_ASSIGN_MAX_C: the most centroids (h
 PQ_MAX_M, PQ_MAX_DSUB, PQ_KSUB = 96, 64, 256  # HZ_SEARCH_PQ_MAX_M, HZ_SEARCH_PQ_MAX_DSUB; sub-centroids per sub-space
 # HZ_SEARCH_PQU_CG, _TILE, _BATCH: centroids per workgroup of the update kernel, rows per tile, members per list batch
 PQ_UPDATE_CG, PQ_UPDATE_TILE, PQ_UPDATE_BATCH = 16, 256, 384
+# HZ_SEARCH_GRAPH_MAX_BEAM, _CAP_SMALL, _CAP_LARGE: the graph search's beam limit and its two visited tables (slots)
+GRAPH_MAX_BEAM, GRAPH_CAP_SMALL, GRAPH_CAP_LARGE = 256, 4096, 16384
+GRAPH_THREADS = 256              # one thread per entry and per neighbour slot: E <= 256, width * deg <= 256
 
 
 @N.params_of("HZ_K_SEARCH_MERGE")
@@ -272,6 +277,17 @@ class RescorePosParams(C.Structure):
                 ("R", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("npos", C.c_int), ("pad_", C.c_int)]
 
 
+@N.params_of("HZ_K_SEARCH_GRAPH")
+class GraphParams(C.Structure):
+    """HzSearchGraphParams: ``corpus`` bf16 [N][ldc], ``queries`` device fp32 [Q][D], ``graph`` device int32 [N][deg]
+    (an entry outside [0, N) is padding), ``entries`` device int32 [E], the outputs [Q][k] and ``out_stats`` (int32
+    [Q][2]: iterations, rows scored; or null)."""
+    _fields_ = [("corpus", C.c_void_p), ("queries", C.c_void_p), ("graph", C.c_void_p), ("entries", C.c_void_p),
+                ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("out_stats", C.c_void_p), ("N", C.c_int),
+                ("D", C.c_int), ("Q", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("beam", C.c_int), ("deg", C.c_int),
+                ("width", C.c_int), ("iters", C.c_int), ("E", C.c_int)]
+
+
 @N.params_of("HZ_K_SEARCH_ASSIGN")
 class AssignParams(C.Structure):
     """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
@@ -310,6 +326,9 @@ def _sigs(lib):
     N._sig(lib, "hz_index_search_batch_q", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_search_lxscan_launch", C.c_int, C.POINTER(ListBatchScanParams), P)
     N._sig(lib, "hz_search_rescorep_launch", C.c_int, C.POINTER(RescorePosParams), P)
+    N._sig(lib, "hz_search_graph_launch", C.c_int, C.POINTER(GraphParams), P)
+    N._sig(lib, "hz_index_set_graph", C.c_int, P, P, C.c_longlong, C.c_int, P, C.c_int)
+    N._sig(lib, "hz_index_search_graph", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_probes_batch", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_search_batch_ivf", C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_search_batch_ivf_invert_us", C.c_double, P, C.c_int)
@@ -600,3 +619,13 @@ def launch_rescore_pos(prm: RescorePosParams, stream: int = 0) -> int:
 def launch_rescore_n(prm: RescoreParams, stream: int = 0) -> int:
     """The rescore launch for any number of queries (``HZ_K_SEARCH_RESCOREN``) on ``stream`` -> its code."""
     return int(N.lib().hz_search_rescoren_launch(C.byref(prm), stream))
+
+
+def graph_max_iters(entries: int, width: int, deg: int) -> int:
+    """The most iterations the large visited table allows (``entries + iters * width * deg`` at most half its slots)."""
+    return (GRAPH_CAP_LARGE // 2 - int(entries)) // (int(width) * int(deg))
+
+
+def launch_graph(prm: GraphParams, stream: int = 0) -> int:
+    """The graph search (``HZ_K_SEARCH_GRAPH``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_search_graph_launch(C.byref(prm), stream))

@@ -66,7 +66,7 @@ import threading
 
 import numpy as np
 
-from .ops.search import MAX_K, MAX_Q
+from .ops.search import GRAPH_CAP_LARGE, GRAPH_MAX_BEAM, MAX_K, MAX_Q
 
 MAGIC = b"HZIDX\0\0\1"
 VERSION = 1
@@ -80,6 +80,8 @@ VERSION8 = 8  # sign-bit rows: uint32 [count][dim / 32], no scales; tags / live 
 VERSION9 = 9  # version 8 plus rescore / rescore_off, as version 4 adds them to version 3
 VERSION10 = 10  # pq8 rows: uint8 [count][M], the JSON block pq and the codebook block; tags / live as in version 3, or absent
 VERSION11 = 11  # version 10 plus rescore / rescore_off, as version 4 adds them to version 3
+VERSION12 = 12  # version 1 plus graph_deg / graph_off / entries / entries_off: a neighbour graph and its entry rows
+GRAPH_KEYS = ("graph_deg", "graph_off", "entries", "entries_off")
 FP8_VERSIONS, IVF_VERSIONS, RESCORE_VERSIONS = (VERSION3, VERSION4, VERSION6, VERSION7), (VERSION5, VERSION6, VERSION7), \
     (VERSION4, VERSION7, VERSION9, VERSION11)
 BIN_VERSIONS = (VERSION8, VERSION9)
@@ -608,7 +610,7 @@ def unpack_live(words, n: int) -> np.ndarray:
 
 
 def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, capacity=None, scales=None,
-                rescore=None, ivf=None, pq=None) -> dict:
+                rescore=None, ivf=None, pq=None, graph=None) -> dict:
     """The file of ``hdr`` and ``rows``: version 1 without ``tags`` / ``live``, else version 2 (zero tags / all
     live where one is missing); with ``scales`` (fp8 rows) version 3, whose tags and bitmap are present under
     the same rule; with ``rescore`` as well (bf16 bit patterns [N, D]) version 4, their block last. With ``ivf``
@@ -617,8 +619,13 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
     6, and with ``rescore`` as well (``[hdr["count"], D]``, in id order) version 7, their block after the tables.
     With ``pq`` (the codebook fp32 [M, 256, dim / M]; ``rows`` uint8 codes [N, M]) version 10, with ``rescore`` as
     well version 11: the codebook's block follows the rows, where version 3 has its scales.
+    With ``graph`` ((int32 [N, deg], int32 [E]): :func:`check_graph`'s pair; plain bf16 rows without tags) version 12:
+    version 1 plus the graph's and the entries' blocks after the rows.
     Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
+    if graph is not None and (tags is not None or live is not None or scales is not None or ivf is not None or pq is not None
+                              or hdr.get("dtype") != "bf16"):
+        raise ValueError("a graph goes with plain bf16 rows, all live, without tags")
     binary = hdr.get("dtype") == BIN  # sign-bit rows: uint32 [N, dim / 32], versions 8 and 9
     if (hdr.get("dtype") == PQ) != (pq is not None):
         raise ValueError("a pq8 index goes with a codebook, and only a pq8 index does")
@@ -640,7 +647,18 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         raise ValueError("an IVF index holds rows, tags and a live bitmap for whole tiles")
     blocks = tags is not None or live is not None
     tables = ()  # the four blocks of an IVF index
-    if not blocks and scales is None and not binary and pq is None:
+    if graph is not None:
+        version = VERSION12
+        hdr = dict(hdr, graph_deg=int(graph[0].shape[1]), graph_off=0, entries=int(graph[1].size), entries_off=0)
+        while True:  # the offsets follow the JSON's own length
+            js = json.dumps(hdr).encode()
+            data_off = align(HEAD.size + len(js))
+            goff = align(data_off + rows.nbytes)
+            eoff = align(goff + graph[0].nbytes)
+            if (hdr["graph_off"], hdr["entries_off"]) == (goff, eoff):
+                break
+            hdr.update(graph_off=goff, entries_off=eoff)
+    elif not blocks and scales is None and not binary and pq is None:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
     else:
@@ -726,6 +744,11 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         if rescore is not None:
             f.write(bytes(hdr["rescore_off"] - at))
             f.write(np.ascontiguousarray(rescore).astype("<u2").tobytes())
+        if graph is not None:
+            f.write(bytes(hdr["graph_off"] - at))
+            f.write(graph[0].astype("<i4").tobytes())
+            f.write(bytes(hdr["entries_off"] - hdr["graph_off"] - graph[0].nbytes))
+            f.write(graph[1].astype("<i4").tobytes())
     os.replace(tmp, path)
     return hdr
 
@@ -800,7 +823,8 @@ def ivf_layout(assign: np.ndarray, nlist: int) -> dict:
 def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: str = "", embed=None, tags=None,
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
                 ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
-                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host", ivf_init=None) -> dict:
+                pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host", ivf_init=None, graph=None,
+                graph_backend: str = "cpu") -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -817,8 +841,12 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     ``pq_codebook`` is given), a version-10 file, with ``rescore=True`` version 11; ``pq_backend`` (``"cpu"``,
     ``"f32"``, ``"gpu"`` on ``device``) picks how training and encoding find the nearest sub-centroids
     (:func:`pq_encode`): ``"f32"`` and ``"gpu"`` write the same bytes; ``pq_means`` (``"host"``, ``"seq"``, ``"gpu"``)
-    picks how training sums a cluster's rows (:func:`pq_train`'s ``means``)."""
+    picks how training sums a cluster's rows (:func:`pq_train`'s ``means``). ``graph=DEG`` (plain bf16 rows without
+    tags): a version-12 file, which also holds the neighbour graph :meth:`Index.search_graph` walks --
+    :func:`graph_build` over the kNN lists of the stored rows, from ``RefIndex`` (``graph_backend="cpu"``) or from
+    :meth:`Index.knn_graph` on ``device`` (``"gpu"``) -- and :func:`graph_entries`' entry rows."""
     _check_ivf_backend(ivf_backend, ivf)
+    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and tags is None and not rescore)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")
@@ -875,7 +903,34 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
         return _write_file(path, hdr, srows, stags, real, ivf=lay)
     if ivf_init is not None:
         raise ValueError("ivf_init goes with ivf=nlist")
+    if graph is not None:
+        return _write_file(path, hdr, rows, graph=_graph_of(hdr, rows, graph, graph_backend, device, path))
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows, pq=codebook)
+
+
+def _check_graph_args(graph, graph_backend, plain: bool):
+    if graph_backend not in IVF_BACKENDS:
+        raise ValueError(f"graph_backend must be one of {IVF_BACKENDS}, got {graph_backend!r}")
+    if graph is None and graph_backend != "cpu":
+        raise ValueError("graph_backend goes with graph=DEG")
+    if graph is not None and (not _is_int(graph) or not 8 <= graph <= 64 or graph % 8):
+        raise ValueError(f"graph must be a degree, a multiple of 8 in 8..64, got {graph!r}")
+    if graph is not None and not plain:
+        raise ValueError(f"graph={graph!r} goes with a plain bf16 index: no tags, lists, rescore rows or other dtype")
+
+
+def _graph_of(hdr: dict, bits, deg: int, backend: str, device: int, near: str):
+    """The stored graph of degree ``deg`` over the bf16 rows ``bits`` and its entry rows: the kNN lists come from a
+    temporary plain index beside ``near``, opened on the chosen backend."""
+    tmp = near + ".graph-knn.tmp"
+    try:
+        _write_file(tmp, {k: hdr[k] for k in ("dim", "count", "dtype", "metric")}, bits)
+        with (Index(tmp, device=device) if backend == "gpu" else RefIndex(tmp)) as ix:
+            knn = ix.knn_graph(deg)[0]
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return check_graph(graph_build(knn, deg), hdr["count"])
 
 
 IVF_BACKENDS = ("cpu", "gpu")
@@ -944,7 +999,7 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
         if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7, VERSION8, VERSION9,
-                           VERSION10, VERSION11):
+                           VERSION10, VERSION11, VERSION12):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
@@ -1057,7 +1112,33 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path}: the rescore block at {off} overlaps another block, which ends at {last}")
         if off + 2 * count * dim > size:
             raise ValueError(f"{path}: the rescore block lies outside the file")
+    if version == VERSION12:  # version 1's rows, then the graph's and the entries' blocks
+        if hdr["dtype"] != "bf16" or "tags_off" in hdr or "live_off" in hdr:
+            raise ValueError(f"{path}: a version-12 file holds plain bf16 rows without tags")
+        if not all(_is_int(hdr.get(k)) for k in GRAPH_KEYS):
+            raise ValueError(f"{path}: a version-12 file without integers {', '.join(GRAPH_KEYS)}")
+        deg, ne = hdr["graph_deg"], hdr["entries"]
+        if not 8 <= deg <= 64 or deg % 8 or not 1 <= ne <= 256:
+            raise ValueError(f"{path}: graph_deg {deg} must be a multiple of 8 in 8..64 and entries {ne} in 1..256")
+        for key, nbytes in (("graph_off", 4 * count * deg), ("entries_off", 4 * ne)):
+            off = hdr[key]
+            if off % ALIGN or off < last or off + nbytes > size:
+                raise ValueError(f"{path}: the block at {key} = {off} is unaligned, overlaps another block or lies outside "
+                                 f"the file")
+            last = off + nbytes
+    elif any(k in hdr for k in GRAPH_KEYS):
+        raise ValueError(f"{path}: graph keys in a version-{version} file (they belong to version 12)")
     return dict(hdr, data_off=int(data_off))
+
+
+def read_graph(path: str):
+    """The graph of a version-12 file -> (graph int32 [count, graph_deg], entries int32 [E])."""
+    hdr = read_header(path)
+    if "graph_off" not in hdr:
+        raise ValueError(f"{path} holds no graph (a version-12 file does: write_index(graph=DEG))")
+    n, deg = hdr["count"], hdr["graph_deg"]
+    return (np.fromfile(path, "<i4", n * deg, offset=hdr["graph_off"]).astype(np.int32).reshape(n, deg),
+            np.fromfile(path, "<i4", hdr["entries"], offset=hdr["entries_off"]).astype(np.int32))
 
 
 def stored_rows(hdr: dict) -> int:
@@ -1089,6 +1170,8 @@ def file_info(path: str) -> dict:
     v2 = "tags_off" in hdr
     info = {"version": VERSION2 if v2 else VERSION, "capacity": hdr.get("capacity", hdr["count"]),
             "live": int(read_live(path).sum()), "tags": v2}
+    if "graph_off" in hdr:
+        info.update(version=VERSION12, graph={k: hdr[k] for k in GRAPH_KEYS})
     if "ivf" in hdr:
         info.update(version=VERSION5, ivf=ivf_facts(hdr, read_ivf(path)))
     if hdr["dtype"] == FP8:
@@ -1241,6 +1324,126 @@ def search_ref(corpus, q, k: int, allow=None, scales=None):
         scores[i, :order.size] = s[order]
         ids[i, :order.size] = order
     return scores, ids
+
+
+GRAPH_ENTRIES = 64       # entry rows of a graph search, evenly spaced over the ids
+GRAPH_VISITED = GRAPH_CAP_LARGE // 2  # the most rows one walk may visit: half of the large visited table
+GRAPH_MAX_ITERS = 256    # what search_graph(iters=None) asks for at the most
+
+
+def graph_entries(n: int) -> np.ndarray:
+    """The entry rows of a graph over ``n`` rows: ``min(n, GRAPH_ENTRIES)`` ids evenly spaced over [0, n), int32."""
+    e = min(int(n), GRAPH_ENTRIES)
+    return (np.arange(e, dtype=np.int64) * int(n) // e).astype(np.int32)
+
+
+def graph_build(knn_ids, deg: int) -> np.ndarray:
+    """A kNN list (int [N, >= deg / 2], best first; -1, an id outside [0, N), the row itself and a repeated id are
+    skipped) -> the searched graph, int32 [N, deg] padded with -1. Row r takes its first ``deg / 2``
+    forward neighbours; then every forward edge s -> r among those halves adds the REVERSE edge r -> s, in ascending s,
+    while the row has room -- reverse edges are what makes a kNN graph navigable --; then the row is topped up with its
+    further forward neighbours. No edge twice. Deterministic, a function of ``knn_ids`` alone; whole-array numpy."""
+    knn = np.asarray(knn_ids)
+    if not _is_int(deg) or not 8 <= deg <= 64 or deg % 8:
+        raise ValueError(f"deg must be a multiple of 8 in 8..64, got {deg!r}")
+    if knn.ndim != 2 or knn.dtype.kind not in "iu" or knn.shape[1] < deg // 2:
+        raise ValueError(f"knn_ids must be integers [N, >= {deg // 2}], got {knn.dtype} {list(knn.shape)}")
+    (n, w), half = knn.shape, deg // 2
+    knn = knn.astype(np.int64)
+    row = np.broadcast_to(np.arange(n)[:, None], (n, w))
+    ok = (knn >= 0) & (knn < n) & (knn != row)
+    order = np.argsort(knn, axis=1, kind="stable")  # a repeated id: every occurrence after the first
+    srt = np.take_along_axis(knn, order, axis=1)
+    again = np.zeros((n, w), bool)
+    np.put_along_axis(again, order[:, 1:], srt[:, 1:] == srt[:, :-1], axis=1)
+    ok &= ~again
+    rank = np.cumsum(ok, axis=1) - 1  # a valid entry's place among its row's valid entries
+    first, later = ok & (rank < half), ok & (rank >= half)
+    src, dst = row[first], knn[first]  # the halves' edges, in ascending source id
+    nfirst = first.sum(axis=1)
+    fkey = src * n + dst
+    rev = ~np.isin(dst * n + src, fkey)  # dst does not hold src already
+    rsrc, rdst = src[rev], dst[rev]
+    by = np.lexsort((rsrc, rdst))
+    rsrc, rdst = rsrc[by], rdst[by]
+    start = np.searchsorted(rdst, np.arange(n))
+    take = np.arange(rdst.size) - start[rdst] < (deg - nfirst)[rdst]
+    rsrc, rdst = rsrc[take], rdst[take]
+    nrev = np.bincount(rdst, minlength=n)
+    fresh = later & ~np.isin(row * n + knn, rdst * n + rsrc)  # a further forward neighbour that no reverse edge gave
+    fresh &= np.cumsum(fresh, axis=1) <= (deg - nfirst - nrev)[:, None]
+    graph = np.full((n, deg), -1, np.int32)
+    graph[row[first], rank[first]] = knn[first]
+    graph[rdst, nfirst[rdst] + np.arange(rdst.size) - np.searchsorted(rdst, rdst)] = rsrc
+    graph[row[fresh], (nfirst + nrev)[row[fresh]] + (np.cumsum(fresh, axis=1) - 1)[fresh]] = knn[fresh]
+    return graph
+
+
+def check_graph(graph, n: int, entries=None):
+    """A graph for ``n`` rows -> (graph int32 [n, deg] contiguous, entries int32 [E]); ``entries`` None:
+    :func:`graph_entries`. An entry of the graph outside [0, n) is padding."""
+    g = np.asarray(graph)
+    if g.ndim != 2 or g.dtype.kind not in "iu" or g.shape[0] != n or not 8 <= g.shape[1] <= 64 or g.shape[1] % 8:
+        raise ValueError(f"graph must be integers [{n}, deg] with deg a multiple of 8 in 8..64, got {g.dtype} {list(g.shape)}")
+    e = graph_entries(n) if entries is None else np.asarray(entries)
+    if e.ndim != 1 or e.dtype.kind not in "iu" or not 1 <= e.size <= 256:
+        raise ValueError(f"entries must be 1..256 integers, got {e.dtype} {list(e.shape)}")
+    return np.ascontiguousarray(g, np.int32), np.ascontiguousarray(e, np.int32)
+
+
+def check_graph_args(k, beam, width, iters, deg: int, nentries: int):
+    """``search_graph``'s arguments -> (k, beam, width, iters). ``iters`` None: the most the visited bound
+    ``entries + iters * width * deg <= GRAPH_VISITED`` allows, capped at ``GRAPH_MAX_ITERS``."""
+    k = check_k(k)
+    if not _is_int(beam) or not 32 <= beam <= GRAPH_MAX_BEAM or beam % 32:
+        raise ValueError(f"beam must be a multiple of 32 in 32..{GRAPH_MAX_BEAM}, got {beam!r}")
+    if k > beam:
+        raise ValueError(f"k must be in 1..min(beam, {MAX_K}), got {k} with beam = {beam}")
+    if not _is_int(width) or not 1 <= width <= 256 // deg:
+        raise ValueError(f"width must be in 1..{256 // deg} (256 / the graph's degree), got {width!r}")
+    most = (GRAPH_VISITED - nentries) // (width * deg)
+    if iters is None:
+        iters = min(most, GRAPH_MAX_ITERS)
+    if not _is_int(iters) or not 1 <= iters <= most:
+        raise ValueError(f"iters must be in 1..{most} (entries + iters * width * deg at most {GRAPH_VISITED} visited rows), "
+                         f"got {iters!r}")
+    return k, int(beam), int(width), int(iters)
+
+
+def search_graph_ref(corpus, q, graph, entries, k: int, beam: int = 64, width: int = 1, iters: int = 1):
+    """The oracle of the graph search (csrc/hipzap.h HZ_K_SEARCH_GRAPH, "THE WALK"): the same walk over sets with fp64
+    scores of ``corpus`` (the bf16 rows widened, [N, D]) -> (scores float64 [Q, k], ids int32 [Q, k], stats int32
+    [Q, 2] = iterations that found a parent, rows scored). Order rule: higher score first, then the lower id."""
+    c, q = np.asarray(corpus, np.float64), np.asarray(q, np.float64)
+    graph, entries = np.asarray(graph), np.asarray(entries)
+    n = c.shape[0]
+    scores, ids = np.full((q.shape[0], k), -np.inf), np.full((q.shape[0], k), -1, np.int32)
+    stats = np.zeros((q.shape[0], 2), np.int32)
+    for a, row in enumerate(q):
+        new = np.unique(entries[(entries >= 0) & (entries < n)])
+        seen = np.zeros(n, bool)
+        b_id, b_s, b_done = np.zeros(0, np.int64), np.zeros(0), np.zeros(0, bool)
+        it = 0
+        while True:
+            seen[new] = True
+            stats[a, 1] += new.size
+            b_id = np.concatenate([b_id, new])
+            b_s = np.concatenate([b_s, (c[new] * row[None, :]).sum(axis=1) + 0.0])
+            b_done = np.concatenate([b_done, np.zeros(new.size, bool)])
+            keep = np.lexsort((b_id, -b_s))[:beam]
+            b_id, b_s, b_done = b_id[keep], b_s[keep], b_done[keep]
+            parents = np.flatnonzero(~b_done)[:width]  # the beam is sorted: the best unexpanded keys
+            if it == iters or parents.size == 0:
+                break
+            it += 1
+            b_done[parents] = True
+            new = graph[b_id[parents]].ravel()
+            new = np.unique(new[(new >= 0) & (new < n)])
+            new = new[~seen[new]]
+        stats[a, 0] = it
+        m = min(k, b_id.size)
+        scores[a, :m], ids[a, :m] = b_s[:m], b_id[:m]
+    return scores, ids, stats
 
 
 def split3(q):
@@ -1480,9 +1683,11 @@ class _Base:
             self.version = VERSION5 if self.dtype != FP8 else VERSION7 if self.rescore else VERSION6
         else:
             self.version = (VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
-                            else VERSION2 if "tags_off" in self.header else VERSION)
+                            else VERSION2 if "tags_off" in self.header else VERSION12 if "graph_off" in self.header else VERSION)
         self.nprobe = self.ivf["nprobe"] if self.ivf else None  # what search(nprobe=None) scans; settable
         self._mut = threading.Lock()  # one mutator at a time
+        # the neighbour graph search_graph walks and its entry rows: a version-12 file's, or set_graph's
+        self.graph, self.graph_entries = read_graph(path) if "graph_off" in self.header else (None, None)
 
     def __enter__(self):
         return self
@@ -1649,6 +1854,7 @@ class _Base:
 
     def _check_cluster_index(self):
         """:meth:`cluster` is built for plain bf16 indexes with ``dim % 32 == 0``."""
+        self._no_graph("cluster")
         if self.dtype in (FP8, BIN, PQ) or self.ivf is not None:
             what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
                 f"a {self.dtype} index" if self.dtype in (BIN, PQ) else f"an {FP8} index"
@@ -1705,6 +1911,41 @@ class _Base:
     def _cluster_hold(self, ctx):
         yield ctx
 
+    def _check_graph_index(self, what: str):
+        if self.ivf is not None or self.dtype != "bf16":
+            raise ValueError(f"{what} is built for plain bf16 indexes (versions 1 and 2), {self.path} is "
+                             f"{'an IVF' if self.ivf is not None else 'a ' + self.dtype} index of version {self.version}")
+
+    def _no_graph(self, what: str):
+        """An index with a graph is read-only: the graph covers the rows as they are, all live, without tags."""
+        if self.graph is not None:
+            raise ValueError(f"{what} is refused on an index with a graph ({self.path}, version {self.version}): it is read-only; "
+                             f"write the vectors to a plain index to change them")
+
+    def set_graph(self, graph, entries=None) -> None:
+        """Attach the neighbour graph :meth:`search_graph` walks: int [count, deg], an entry outside
+        [0, count) padding (:func:`graph_build` makes one from :meth:`knn_graph`), and its entry rows (None:
+        :func:`graph_entries`). A plain bf16 index whose rows are all live. From then on the index is read-only, like one
+        opened from a version-12 file: ``add``, ``delete``, ``set_tags``, ``filter=`` and ``cluster`` refuse it by name."""
+        self._check_graph_index("set_graph")
+        g, e = check_graph(graph, self.count, entries)
+        with self._mut:
+            self._attach_graph(g, e)
+            self.graph, self.graph_entries = g, e
+
+    def build_graph(self, deg: int = 32) -> np.ndarray:
+        """:meth:`knn_graph` at k = ``deg``, :func:`graph_build`, :meth:`set_graph` -> the graph."""
+        self._check_graph_index("build_graph")
+        g = graph_build(self.knn_graph(deg)[0], deg)
+        self.set_graph(g)
+        return g
+
+    def _check_graph_search(self, q, k, beam, width, iters):
+        if self.graph is None:
+            raise ValueError(f"search_graph needs a graph and {self.path} has none (set_graph, build_graph)")
+        k, beam, width, iters = check_graph_args(k, beam, width, iters, self.graph.shape[1], self.graph_entries.size)
+        return check_queries(q, self.dim), k, beam, width, iters
+
     def knn_graph(self, k: int = 10, *, block: int = NEIGHBORS_BLOCK):
         """The kNN graph of the index: :meth:`neighbors` of every live row (itself excluded), ``block`` rows a pass
         -> (ids int32 [count, k], scores float32 [count, k]). A deleted row's lists hold -1 / -inf."""
@@ -1756,6 +1997,7 @@ class _Base:
                 raise ValueError(f"{len(labels)} labels for {n} rows")
         tags = np.zeros(n, np.uint32) if tags is None else check_tags(tags, n)
         with self._mut:
+            self._no_graph("add")
             if self.count + n >= 2 ** 31:
                 raise ValueError("count must stay below 2^31")
 
@@ -1770,10 +2012,12 @@ class _Base:
     def delete(self, ids) -> int:
         """Hide rows for good -> how many were live until now. An id outside [0, count) is a ValueError."""
         with self._mut:
+            self._no_graph("delete")
             return int(self._kill(self._check_ids(ids)))
 
     def set_tags(self, ids, tags) -> None:
         with self._mut:
+            self._no_graph("set_tags")
             ids = self._check_ids(ids)
             self._retag(ids, check_tags(tags, ids.size))
 
@@ -1810,7 +2054,8 @@ class _Base:
                 hdr["labels"] = list(labels)
             plain = bool(live.all()) and not tags.any()
             return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), None if plain else tags,
-                               None if plain else live, self.capacity(), scales=scales, rescore=rrows, pq=self.codebook)
+                               None if plain else live, self.capacity(), scales=scales, rescore=rrows, pq=self.codebook,
+                               graph=None if self.graph is None else (self.graph, self.graph_entries))  # version 12 again
 
 
 class RefIndex(_Base):
@@ -1853,6 +2098,8 @@ class RefIndex(_Base):
         (:meth:`_Base._nprobe`, an IVF index): only rows of the lists :meth:`probes` names may be returned."""
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
+        if filt is not None:
+            self._no_graph("filter=")
         lists = self._nprobe(nprobe, refine)
         R = self._refine(refine, k)
         with self._mut:  # the mutators replace the arrays one by one
@@ -1870,6 +2117,17 @@ class RefIndex(_Base):
                 two = [rescore_ref(self._rrows, q[a], i[a], k) for a in range(q.shape[0])]
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
         return s.astype(np.float32), i
+
+    def _attach_graph(self, g, e):
+        if not self._live.all() or g.shape[0] != self._rows.shape[0]:
+            raise ValueError(f"a graph covers every row of an index whose rows are all live, {self.path} has deleted rows")
+
+    def search_graph(self, q, k: int = 10, *, beam: int = 64, width: int = 1, iters=None, stats: bool = False, ctx=None):
+        """:meth:`Index.search_graph` on the host, its oracle: :func:`search_graph_ref`, the walk with fp64 scores."""
+        q, k, beam, width, iters = self._check_graph_search(q, k, beam, width, iters)
+        with self._mut:
+            s, i, st = search_graph_ref(self._rows, q, self.graph, self.graph_entries, k, beam, width, iters)
+        return (s.astype(np.float32), i, st) if stats else (s.astype(np.float32), i)
 
     def search_batch(self, q, k: int = 10, *, candidates=None, fallback: bool = True, ctx=None):
         """:meth:`Index.search_batch` on the host, its oracle: stage one is :func:`search_ref` in fp64 over the SPLIT
@@ -2099,6 +2357,7 @@ class RefIndex(_Base):
                 "tags": bool(self._tags.any()) or "tags_off" in self.header,
                 **({"m": int(self.codebook.shape[0]), "dsub": int(self.codebook.shape[2]),
                     "codebook_bytes": int(self.codebook.nbytes)} if self.dtype == PQ else {}),
+                **({"graph_deg": int(self.graph.shape[1])} if self.graph is not None else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
@@ -2162,6 +2421,8 @@ class Index(_Base):
         (:meth:`_Base._nprobe`)."""
         q, k = check_queries(q, self.dim), check_k(k)
         filt = check_filter(filter, q.shape[0])
+        if filt is not None:
+            self._no_graph("filter=")
         lists = self._nprobe(nprobe, refine)
         R = self._refine(refine, k)
         if self._h is None:
@@ -2206,6 +2467,37 @@ class Index(_Base):
         finally:
             if ctx is None:
                 self._free.put(c)
+
+    def _attach_graph(self, g, e):
+        if self._h is None:
+            raise RuntimeError("the index is closed")
+        code = []  # a refusal is a ValueError with the library's text, not _exclusive's RuntimeError
+        self._exclusive(lambda: code.append(self._lib.hz_index_set_graph(self._h, g.ctypes.data, g.shape[0], g.shape[1],
+                                                                         e.ctypes.data, e.size)), "hz_index_set_graph")
+        rc = code[0]
+        if rc in (-230, -231, -232):
+            raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
+        if rc:
+            raise RuntimeError(f"hz_index_set_graph failed with code {rc}")
+
+    def search_graph(self, q, k: int = 10, *, beam: int = 64, width: int = 1, iters=None, stats: bool = False,
+                     ctx: int | None = None):
+        """Approximate top-k by a beam search over the attached neighbour graph (:meth:`set_graph`,
+        :meth:`build_graph`): fp32 queries [Q, dim] -> (scores float32 [Q, k], ids int32 [Q, k]), best first, -inf / -1
+        past the rows a walk reached; with ``stats`` also int32 [Q, 2] = (iterations, rows scored). One workgroup per
+        query walks from the entry rows: each iteration expands the best ``width`` unexpanded rows of a beam of ``beam``
+        rows (a multiple of 32 in 32..256, k <= beam), for at most ``iters`` iterations (``None``: as many as the visited
+        table allows, at most 256). A query touches a few hundred rows, not all of them: nothing certifies the answer,
+        recall is bought with ``beam``. Every score returned has the bits :meth:`search` gives that row, and the walk is
+        :meth:`RefIndex.search_graph`'s. Q above the per-call maximum is split here."""
+        q, k, beam, width, iters = self._check_graph_search(q, k, beam, width, iters)
+        nq = q.shape[0]
+        scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
+        st = np.empty((nq, 2), np.int32)
+        with self._in_parts("hz_index_search_graph", (-4, -5, -233, -234, -235, -236, -237), q, (k, beam, width, iters),
+                            (scores, ids, st), ctx):
+            pass
+        return (scores, ids, st) if stats else (scores, ids)
 
     def search_batch(self, q, k: int = 10, *, candidates=None, fallback: bool = True, ctx: int | None = None):
         """Many fp32 queries at once -> (scores float32 [Q, k], ids int32 [Q, k], certain bool [Q]).
@@ -2522,7 +2814,13 @@ class Index(_Base):
                     "cb8_bytes": int(pq[5]), "batch_pq": bool(pq[6])}
                    if self.dtype == PQ else {}),
                 **({"batch_fp8": self.ivf is None and self.dim % 32 == 0} if self.dtype == FP8 else {}),
+                **({"graph_deg": int(self._describe3()[6])} if self.graph is not None else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
+
+    def _describe3(self):
+        out = (C.c_uint64 * 8)()
+        self._lib.hz_index_describe3(self._h, out)
+        return out
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -2546,7 +2844,8 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
                   ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None,
-                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host") -> dict:
+                  pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host",
+                  graph=None, graph_backend: str = "cpu") -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -2560,8 +2859,16 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     ``dtype="pq"`` (a plain ``src``, ``pq_m`` code bytes per row): the stored rows are trained on (:func:`pq_train` with
     ``pq_seed`` / ``pq_iters``, unless ``pq_codebook`` is given) and encoded as they stand, which gives the bytes
     ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11.
-    ``pq_backend`` and ``pq_means`` as in :func:`write_index`."""
+    ``pq_backend`` and ``pq_means`` as in :func:`write_index`. ``graph=DEG`` (``dtype="bf16"``, a plain version-1 ``src``): the
+    same rows plus their neighbour graph, a version-12 file (``graph_backend`` as in :func:`write_index`)."""
     _check_ivf_backend(ivf_backend, ivf)
+    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and not rescore)
+    if graph is not None:
+        hdr = read_header(src)
+        if hdr["dtype"] != "bf16" or any(k in hdr for k in ("ivf", "tags_off", "graph_off")):
+            raise ValueError(f"graph={graph!r}: {src} is not a plain bf16 index of version 1")
+        out, bits = {k: v for k, v in hdr.items() if k != "data_off"}, read_rows(src)
+        return _write_file(dst, out, bits, graph=_graph_of(out, bits, graph, graph_backend, device, dst))
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")

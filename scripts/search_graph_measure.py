@@ -1,0 +1,85 @@
+"""Graph search against the exact scan and an IVF index of the same vectors: recall@10 against fp64
+truth and milliseconds per call, launch to sync, the routes interleaved.
+
+    python scripts/search_graph_measure.py --n 100000 --out profiles/search_graph/measure.jsonl
+"""
+import argparse
+import json
+import os
+import tempfile
+import time
+
+import numpy as np
+
+from hipzap import search as S
+
+
+def corpus(kind, n, d, nq, rng):
+    if kind == "isotropic":
+        return rng.standard_normal((n, d), np.float32), rng.standard_normal((nq, d), np.float32)
+    cent = rng.standard_normal((1024, d), np.float32)
+    return (cent[rng.integers(0, 1024, n)] + rng.standard_normal((n, d), np.float32),
+            cent[rng.integers(0, 1024, nq)] + rng.standard_normal((nq, d), np.float32))
+
+
+def recall(ids, truth):
+    return sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(ids, truth)) / truth.size
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=100000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--deg", type=int, default=32)
+    ap.add_argument("--nlist", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--truth-queries", type=int, default=256)
+    ap.add_argument("--out", default="search_graph.jsonl")
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    out = open(a.out, "w")
+
+    def emit(**kv):
+        print(json.dumps(kv), flush=True)
+        out.write(json.dumps(kv) + "\n")
+        out.flush()
+
+    with tempfile.TemporaryDirectory() as d:
+        for kind in ("isotropic", "clustered"):
+            rows, q = corpus(kind, a.n, a.dim, 1024, rng)
+            plain, graph, ivf = (os.path.join(d, f"{kind}-{x}.hzidx") for x in ("plain", "graph", "ivf"))
+            S.write_index(plain, rows, "cosine")
+            t = time.perf_counter()
+            S.convert_index(plain, graph, "bf16", graph=a.deg, graph_backend="gpu")
+            t_graph = time.perf_counter() - t
+            t = time.perf_counter()
+            S.convert_index(plain, ivf, "bf16", ivf=a.nlist, ivf_backend="gpu")
+            t_ivf = time.perf_counter() - t
+            emit(corpus=kind, n=a.n, dim=a.dim, build_graph_s=round(t_graph, 2), build_ivf_s=round(t_ivf, 2), deg=a.deg, nlist=a.nlist)
+            tq = q[:a.truth_queries]
+            truth = S.search_ref(S.bf16_to_f32(S.read_rows(plain)), tq, 10)[1]
+            del rows
+            with S.Index(plain) as px, S.Index(graph) as gx, S.Index(ivf) as vx:
+                routes = {"search (plain scan)": lambda x: px.search(x, 10)}
+                for beam, width in ((32, 1), (64, 1), (64, 2), (128, 2), (256, 4)):
+                    routes[f"search_graph beam={beam} width={width}"] = lambda x, b=beam, w=width: gx.search_graph(x, 10, beam=b, width=w)
+                for nprobe in (1, 2, 4, 8, 16, 32, 64):
+                    routes[f"ivf nprobe={nprobe}"] = lambda x, p=nprobe: vx.search(x, 10, nprobe=p)
+                rec = {name: recall(f(tq)[1], truth) for name, f in routes.items()}
+                stats = gx.search_graph(tq, 10, beam=64, width=1, stats=True)[2]
+                emit(corpus=kind, rows_scored_beam64=float(stats[:, 1].mean()), iterations_beam64=float(stats[:, 0].mean()))
+                for nq in (1, 16, 1024):
+                    part, ms = q[:nq], {name: [] for name in routes}
+                    for f in routes.values():
+                        f(part)  # capture
+                    for _ in range(a.reps):  # interleaved: every route once per round
+                        for name, f in routes.items():
+                            t = time.perf_counter()
+                            f(part)
+                            ms[name].append((time.perf_counter() - t) * 1e3)
+                    for name in routes:
+                        emit(corpus=kind, Q=nq, route=name, ms=round(float(np.median(ms[name])), 3), recall_at_10=round(rec[name], 4))
+
+
+if __name__ == "__main__":
+    main()
