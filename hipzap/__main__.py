@@ -138,8 +138,10 @@ def cmd_index(a):
                                      "pq_means": a.pq_means or "host"}
     if a.graph is None and a.graph_backend != "cpu":
         raise SystemExit("index: --graph-backend goes with --graph DEG")
+    if a.graph is None and a.graph_prune:
+        raise SystemExit("index: --graph-prune goes with --graph DEG")
     if a.graph is not None:
-        pq = dict(pq, graph=a.graph, graph_backend=a.graph_backend)  # the writers' further keywords
+        pq = dict(pq, graph=a.graph, graph_backend=a.graph_backend, graph_prune=a.graph_prune)  # the writers' further keywords
     if a.rescore and a.dtype not in ("fp8", "bin", "pq"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
@@ -377,6 +379,8 @@ def main(argv=None):
                          "8..64) for Index.search_graph")
     ix.add_argument("--graph-backend", choices=["cpu", "gpu"], default="cpu",
                     help="with --graph: where the kNN lists come from; gpu: Index.knn_graph on --device (dim %% 32 == 0)")
+    ix.add_argument("--graph-prune", action="store_true",
+                    help="with --graph: take kNN lists of width 2 DEG and keep the edges that the fewest two-edge detours replace")
     ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept); an IVF file keeps its lists "
                          "(versions 6 and 7), --ivf NLIST builds lists over a plain file's stored rows")
     ix.add_argument("--model", default=None, help="free text kept in the header")

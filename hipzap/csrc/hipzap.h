@@ -1010,6 +1010,25 @@ typedef struct HzSearchGraphParams {
   int N, D, Q, k, ldc, beam, deg, width, iters, E;
 } HzSearchGraphParams;
 int hz_search_graph_launch(const HzSearchGraphParams* p, hipStream_t st);
+// rank-based pruning of kNN lists (HZ_K_GRAPH_PRUNE): reorders every row's list so that the edges no
+// short detour replaces come first; graph_build (hipzap/search.py) then keeps those. Integers only, exact.
+// THE RULE is stated over the input alone. knn is int32 [N][W], best first, W a multiple of 8 in 16..128. Column j of
+// row x is VALID iff 0 <= knn[x][j] < N, knn[x][j] != x and no column j' < j of the row holds the same id (graph_build's
+// rule). For a valid column j with b = knn[x][j]:
+//   detours[x][j] = #{ (i, r) : i < j, r < j, column i of row x valid, a = knn[x][i], knn[a][r] == b }
+// -- the edge x -> b at rank j has a detour x -> a -> b whose two edges both rank better than j. Row a is read as it
+// lies: its columns need not be valid, and an id it holds twice below j counts twice. An invalid column has detours 0.
+//   order[x] = the row's valid ids sorted by (detours ascending, column ascending), then -1 up to W.
+// One wave per row, four rows per workgroup of 256 threads; `detours` may be null.
+// Refusals (nothing is launched, one code per rule): -238 W outside 16..128 or W % 8; -239 N < 1 or N * W >= 2^31;
+// -240 knn or order null; -241 knn, order or detours not 4-B aligned.
+typedef struct HzGraphPruneParams {
+  const int* knn;                // device int32 [N][W]
+  int* order;                    // device int32 [N][W]
+  int* detours;                  // device int32 [N][W] or null
+  int N, W;
+} HzGraphPruneParams;
+int hz_graph_prune_launch(const HzGraphPruneParams* p, hipStream_t st);
 // nearest centroid of every row (HZ_K_SEARCH_ASSIGN): one workgroup of HZ_SEARCH_TILE threads per tile
 // of HZ_SEARCH_TILE rows. The centroids are walked in blocks of HZ_SEARCH_ASSIGN_CB; a block's rows are the A operand
 // of v_mfma_f32_16x16x32_bf16 and the tile's rows the B operand, both read with plain 16-byte loads (the fragment
@@ -1284,6 +1303,11 @@ double hz_index_search_batch_ivf_invert_us(void* idx, int ctx);
 int hz_index_set_graph(void* idx, const int* graph, long long n, int deg, const int* entries, int E);
 int hz_index_search_graph(void* idx, int ctx, const float* queries, int Q, int k, int beam, int width, int iters,
                           float* out_score, int* out_id, int* out_stats);
+// hz_graph_prune: HZ_K_GRAPH_PRUNE over host lists `knn` (int32 [n][W]) on `device` -> `order_out`
+// and, unless null, `detours_out` (both int32 [n][W]). No index: a stream and three device buffers of its own, H2D,
+// the launch, D2H, one synchronise, all released on every way out. The launcher's refusals -238 .. -241 pass through
+// (-239 also for n above the int range); -242: a device call failed (hz_index_last_error names it).
+int hz_graph_prune(int device, const int* knn, long long n, int W, int* order_out, int* detours_out);
 // clustering (a plain bf16 index, versions 1 and 2, dim % 32 == 0). Batch jobs: plain launches on the
 // context's stream under its mutex, no captured program; a context's buffers for them are allocated on first use
 // and grown on demand (a call that needs no more than an earlier one allocates nothing).
@@ -1522,7 +1546,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_QRESCORE, 53, HzSearchQuantRescoreParams, hz_search_qrescore_op, SEARCH) \
   X(SEARCH_LXSCAN, 54, HzSearchListBatchParams, hz_search_lxscan_op, SEARCH) \
   X(SEARCH_RESCOREP, 55, HzSearchRescorePosParams, hz_search_rescorep_op, SEARCH) \
-  X(SEARCH_GRAPH, 56, HzSearchGraphParams, hz_search_graph_op, SEARCH)
+  X(SEARCH_GRAPH, 56, HzSearchGraphParams, hz_search_graph_op, SEARCH)   \
+  X(GRAPH_PRUNE, 57, HzGraphPruneParams, hz_graph_prune_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -2277,6 +2277,45 @@ int hz_pq_encode(int device, const unsigned short* rows_bf16, long long n, int d
   return rc;
 }
 
+// hz_graph_prune (hipzap.h): no index, a stream and three device buffers of its own, all released on
+// every way out. H2D of the lists, HZ_K_GRAPH_PRUNE, D2H of the order (and the counts), one synchronise.
+int hz_graph_prune(int device, const int* knn, long long n, int W, int* order_out, int* detours_out) {
+  if (W < 16 || W > 128 || W % 8) return -238;  // the launcher's rules, before anything is allocated
+  if (n < 1 || n > 0x7fffffffll / W) return -239;
+  if (!knn || !order_out) return -240;
+  const size_t bytes = (size_t)n * W * 4;
+  hipStream_t st = nullptr;
+  int *d_knn = nullptr, *d_order = nullptr, *d_det = nullptr;
+  int rc = 0;
+  const auto step = [&](hipError_t e, const char* what) {
+    if (e == hipSuccess) return true;
+    g_err = std::string("graph_prune: ") + what + " failed: " + hipGetErrorString(e);
+    rc = -242;
+    return false;
+  };
+  if (step(hipSetDevice(device), "hipSetDevice") && step(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate") &&
+      step(hipMalloc(&d_knn, bytes), "hipMalloc of the lists") && step(hipMalloc(&d_order, bytes), "hipMalloc of the order") &&
+      (!detours_out || step(hipMalloc(&d_det, bytes), "hipMalloc of the counts")) &&
+      step(hipMemcpyAsync(d_knn, knn, bytes, hipMemcpyHostToDevice, st), "the lists' copy")) {
+    HzGraphPruneParams p{};
+    p.knn = d_knn, p.order = d_order, p.detours = d_det;
+    p.N = (int)n, p.W = W;
+    if (const int lrc = hz_launch_kernel(HZ_K_GRAPH_PRUNE, &p, st)) {
+      if (lrc > 0) step((hipError_t)lrc, "the prune launch");
+      else rc = lrc;
+    } else if (step(hipMemcpyAsync(order_out, d_order, bytes, hipMemcpyDeviceToHost, st), "the order's copy") &&
+               (!d_det || step(hipMemcpyAsync(detours_out, d_det, bytes, hipMemcpyDeviceToHost, st), "the counts' copy"))) {
+      step(hipStreamSynchronize(st), "hipStreamSynchronize");
+    }
+  }
+  if (st) (void)hipStreamSynchronize(st);
+  if (d_knn) (void)hipFree(d_knn);
+  if (d_order) (void)hipFree(d_order);
+  if (d_det) (void)hipFree(d_det);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
 // hz_pq_train (hipzap.h): no index, a stream and four device buffers of its own, all released on every
 // way out. H2D of the rows and the codebook once; per iteration HZ_K_SEARCH_PQASSIGN over all rows, then
 // HZ_K_SEARCH_PQUPDATE in place on the device codebook; D2H of the codebook (and the counts), one synchronise.

@@ -532,6 +532,10 @@ extern "C" __attribute__((weak)) int hz_search_graph_launch(const HzSearchGraphP
 static int hz_search_graph_op(const HzSearchGraphParams* p, hipStream_t st) {
   return hz_search_graph_launch ? hz_search_graph_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_graph_prune_launch(const HzGraphPruneParams* p, hipStream_t st);
+static int hz_graph_prune_op(const HzGraphPruneParams* p, hipStream_t st) {
+  return hz_graph_prune_launch ? hz_graph_prune_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -2061,6 +2061,143 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(GRAPH_THREADS) void search_graph_kerne
   if (a.out_stats && t == 0) a.out_stats[2 * q] = it, a.out_stats[2 * q + 1] = scored;
 }
 
+// ----------------------------------------------------------------------------------- graph pruning
+// graph_prune_kernel (HZ_K_GRAPH_PRUNE): THE RULE of hipzap.h, one wave per row x, PRUNE_WAVES rows per
+// workgroup, integers only. A wave without a row (N % 4) does nothing but reach the barriers; every barrier below is
+// reached by all four waves the same number of times. Lane l owns columns l and l + 64 of its row. Per wave in LDS:
+//   * L[W]: the row, then -1 in its invalid columns. The duplicate test reads every earlier column: W LDS reads per
+//     owned column, all lanes the same word (a broadcast).
+//   * tab[PRUNE_SLOTS]: id -> column, open addressing with linear probing from a multiplicative hash. A slot holds a
+//     COLUMN (-1 = free) and the key is L[column], so a slot is one int. Only valid columns are inserted: their ids are
+//     distinct, so one compare-and-swap per probed slot places each, and W <= 128 keeps the table at most half full.
+//     Which slot a column lands in depends on the lanes' order; what a lookup returns does not.
+//   * det[W]: the detour counts, LDS atomicAdd -- integer adds commute.
+// Gather: the W rows knn[L[i]] are independent; they are read PRUNE_GROUP at a time, each lane taking columns l and
+// l + 64 of a row as 4-byte loads (coalesced per row), all of a group's loads issued before the first lookup. A row is
+// read only under validity of column i, which implies (unsigned)a < N.
+// Rank: by counting, as the beam update ranks: the owner of valid column j counts the valid columns j' with
+// (det[j'], j') < (det[j], j) and writes order[x][rank] = L[j]; the columns from the number of valid ones on get -1.
+// Addresses: knn[x*W + j] under x < N, j < W; knn[a*W + r] under (unsigned)a < N, r < W; order / detours [x*W + p]
+// under p < W; L / det under column < W; tab under the mask PRUNE_SLOTS - 1. Offsets are long.
+// LDS: 4 x (512 + 1024 + 512) B = 8 KiB.
+constexpr int PRUNE_WAVES = 4, PRUNE_MAX_W = 128, PRUNE_SLOTS = 256, PRUNE_GROUP = 8;
+static_assert(PRUNE_MAX_W <= 128 && PRUNE_SLOTS >= 2 * PRUNE_MAX_W && (PRUNE_SLOTS & (PRUNE_SLOTS - 1)) == 0,
+              "two columns per lane; the table at most half full");
+
+__device__ __forceinline__ unsigned prune_slot(int id) { return ((unsigned)id * 2654435761u) >> (32 - __builtin_ctz(PRUNE_SLOTS)); }
+
+// id -> its valid column in L, or -1
+__device__ __forceinline__ int prune_find(const int* L, const int* tab, int id) {
+  unsigned s = prune_slot(id);
+  for (int i = 0; i < PRUNE_SLOTS; ++i) {  // ends at a free slot: the table is at most half full
+    const int c = tab[s];
+    if (c < 0) return -1;
+    if (L[c] == id) return c;
+    s = (s + 1) & (PRUNE_SLOTS - 1);
+  }
+  return -1;
+}
+
+HZ_NO_PK_F32 __global__ __launch_bounds__(PRUNE_WAVES * 64) void graph_prune_kernel(const HzGraphPruneParams a) {
+  __shared__ int Ls[PRUNE_WAVES][PRUNE_MAX_W];
+  __shared__ int dets[PRUNE_WAVES][PRUNE_MAX_W];
+  __shared__ int tabs[PRUNE_WAVES][PRUNE_SLOTS];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int W = a.W;
+  if (!HZ_DCHECK(a.N >= 1 && W >= 16 && W <= PRUNE_MAX_W && W % 8 == 0 && (long)a.N * W <= 0x7fffffffl &&
+                 (long)blockIdx.x * PRUNE_WAVES < a.N))
+    return;
+  const long x = (long)blockIdx.x * PRUNE_WAVES + w;
+  const bool have = x < a.N;  // wave-uniform
+  int* L = Ls[w];
+  int* det = dets[w];
+  int* tab = tabs[w];
+
+  int id[2] = {-1, -1};
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int j = lane + 64 * c;
+    if (have && j < W && HZ_DCHECK(x < a.N)) id[c] = a.knn[x * W + j];
+    L[j] = id[c];
+    det[j] = 0;
+  }
+  for (int s = lane; s < PRUNE_SLOTS; s += 64) tab[s] = -1;
+  pqx_sync();
+
+  bool ok[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int j = lane + 64 * c;
+    ok[c] = have && j < W && (unsigned)id[c] < (unsigned)a.N && id[c] != (int)x;
+    if (ok[c])
+      for (int e = 0; e < j; ++e) ok[c] &= L[e] != id[c];  // the raw row: an earlier column with this id, valid or not
+  }
+  pqx_sync();
+
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int j = lane + 64 * c;
+    if (!ok[c]) {
+      L[j] = -1;
+      continue;
+    }
+    unsigned s = prune_slot(id[c]);
+    bool placed = false;
+    for (int i = 0; i < PRUNE_SLOTS && !placed; ++i) {  // at most W <= PRUNE_SLOTS / 2 columns are inserted
+      int seen = -1;
+      placed = __hip_atomic_compare_exchange_strong(&tab[s], &seen, j, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      s = (s + 1) & (PRUNE_SLOTS - 1);
+    }
+    (void)HZ_DCHECK(placed);
+  }
+  pqx_sync();
+
+  if (have) {
+    for (int i0 = 0; i0 < W; i0 += PRUNE_GROUP) {  // W % 8 == 0: whole groups
+      int v[PRUNE_GROUP][2];
+#pragma unroll
+      for (int g = 0; g < PRUNE_GROUP; ++g) {
+        const int nb = __builtin_amdgcn_readfirstlane(L[i0 + g]);  // -1: column i0 + g is invalid, nothing is read
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          v[g][c] = -1;
+          if (nb >= 0 && lane + 64 * c < W && HZ_DCHECK((unsigned)nb < (unsigned)a.N))
+            v[g][c] = a.knn[(long)nb * W + lane + 64 * c];
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < PRUNE_GROUP; ++g)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          if (v[g][c] < 0) continue;  // nothing loaded, or padding: no valid column holds a negative id
+          const int j = prune_find(L, tab, v[g][c]);
+          if (j > max(i0 + g, lane + 64 * c)) __hip_atomic_fetch_add(&det[j], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+  }
+  pqx_sync();
+
+  if (!have) return;
+  int nvalid = 0, rank[2] = {0, 0};
+  const int d0 = ok[0] ? det[lane] : 0, d1 = ok[1] ? det[lane + 64] : 0;
+  for (int e = 0; e < W; ++e) {  // every lane reads the same words: LDS broadcasts
+    if (L[e] < 0) continue;
+    const int de = det[e];
+    ++nvalid;
+    rank[0] += de < d0 || (de == d0 && e < lane);
+    rank[1] += de < d1 || (de == d1 && e < lane + 64);
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int j = lane + 64 * c;
+    if (j >= W) continue;
+    if (ok[c] && HZ_DCHECK(rank[c] < nvalid)) a.order[x * W + rank[c]] = id[c];
+    if (j >= nvalid) a.order[x * W + j] = -1;
+    if (a.detours) a.detours[x * W + j] = c ? d1 : d0;
+  }
+}
+
 // ------------------------------------------------------------------------- nearest centroid, means
 // search_assign_kernel (HZ_K_SEARCH_ASSIGN): the self scan with the roles turned. Workgroup `tile`
 // scores its T rows against all C centroids, CB at a time: the A operand is the centroid block (every workgroup
@@ -2829,6 +2966,18 @@ extern "C" int hz_search_graph_launch(const HzSearchGraphParams* pp, hipStream_t
   if (large)
     if (const int rc = once_per_device(graph_raised, [] { return raise_graph_lds_limit(); })) return rc;
   graph_dispatch(a, large, st);
+  return (int)hipGetLastError();
+}
+
+// The pruning kernel's refusals (hipzap.h), one code per rule; then one wave per row.
+extern "C" int hz_graph_prune_launch(const HzGraphPruneParams* pp, hipStream_t st) {
+  const HzGraphPruneParams a = *pp;
+  if (a.W < 16 || a.W > PRUNE_MAX_W || a.W % 8) return -238;
+  if (a.N < 1 || (long long)a.N * a.W > 0x7fffffffll) return -239;
+  if (!a.knn || !a.order) return -240;
+  if ((reinterpret_cast<uintptr_t>(a.knn) & 3) || (reinterpret_cast<uintptr_t>(a.order) & 3) || (reinterpret_cast<uintptr_t>(a.detours) & 3))
+    return -241;
+  hipLaunchKernelGGL(graph_prune_kernel, dim3((unsigned)((a.N + PRUNE_WAVES - 1) / PRUNE_WAVES)), dim3(PRUNE_WAVES * 64), 0, st, a);
   return (int)hipGetLastError();
 }
 

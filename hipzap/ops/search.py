@@ -31,6 +31,9 @@ its candidates with ``HZ_K_SEARCH_QSCAN``'s bits.
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
 ``HZ_K_SEARCH_GRAPH`` (``GraphParams``) is the beam search over a fixed-degree neighbour graph of the corpus, one workgroup
 per query and the whole walk in one launch; its scores are ``HZ_K_SEARCH_SCAN``'s bits.
+``HZ_K_GRAPH_PRUNE`` (``GraphPruneParams``) reorders kNN lists by their detour counts, one wave per row, integers only
+(:func:`hipzap.search.graph_prune_ref` is its result in numpy); ``graph_prune_lists`` is the job over host lists
+(``hz_graph_prune``).
 ``HZ_K_SEARCH_PQLUT`` (``PqLutParams``) writes each query's table of inner products with the 256 sub-centroids of every
 sub-space of a product quantiser; ``HZ_K_SEARCH_PQSCAN`` (``PqScanParams``: the filtered block over uint8 code rows,
 ``ldc`` in bytes, plus the table) adds M table entries per row, one query's table resident in LDS per workgroup.
@@ -288,6 +291,13 @@ class GraphParams(C.Structure):
                 ("width", C.c_int), ("iters", C.c_int), ("E", C.c_int)]
 
 
+@N.params_of("HZ_K_GRAPH_PRUNE")
+class GraphPruneParams(C.Structure):
+    """HzGraphPruneParams: ``knn`` device int32 [N][W] (best first), ``order`` and ``detours`` (or null) device int32
+    [N][W]."""
+    _fields_ = [("knn", C.c_void_p), ("order", C.c_void_p), ("detours", C.c_void_p), ("N", C.c_int), ("W", C.c_int)]
+
+
 @N.params_of("HZ_K_SEARCH_ASSIGN")
 class AssignParams(C.Structure):
     """HzSearchAssignParams: ``corpus`` bf16 [N][ldc], ``cent`` bf16 [C][ldk], the required ``live`` bitmap (any
@@ -327,6 +337,8 @@ def _sigs(lib):
     N._sig(lib, "hz_search_lxscan_launch", C.c_int, C.POINTER(ListBatchScanParams), P)
     N._sig(lib, "hz_search_rescorep_launch", C.c_int, C.POINTER(RescorePosParams), P)
     N._sig(lib, "hz_search_graph_launch", C.c_int, C.POINTER(GraphParams), P)
+    N._sig(lib, "hz_graph_prune_launch", C.c_int, C.POINTER(GraphPruneParams), P)
+    N._sig(lib, "hz_graph_prune", C.c_int, C.c_int, P, C.c_longlong, C.c_int, P, P)
     N._sig(lib, "hz_index_set_graph", C.c_int, P, P, C.c_longlong, C.c_int, P, C.c_int)
     N._sig(lib, "hz_index_search_graph", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_probes_batch", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
@@ -629,3 +641,28 @@ def graph_max_iters(entries: int, width: int, deg: int) -> int:
 def launch_graph(prm: GraphParams, stream: int = 0) -> int:
     """The graph search (``HZ_K_SEARCH_GRAPH``) on ``stream`` -> its code (0, or negative: nothing ran)."""
     return int(N.lib().hz_search_graph_launch(C.byref(prm), stream))
+
+
+def launch_graph_prune(prm: GraphPruneParams, stream: int = 0) -> int:
+    """The pruning kernel (``HZ_K_GRAPH_PRUNE``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_graph_prune_launch(C.byref(prm), stream))
+
+
+def graph_prune_lists(knn, *, device: int = 0, want_detours: bool = False):
+    """``hz_graph_prune``: kNN lists ``knn`` (int32 [N, W], host, best first) on ``device`` -> (order int32 [N, W],
+    detours int32 [N, W] or None) by the rule of ``HZ_K_GRAPH_PRUNE``. A refused shape is a ValueError with the
+    launcher's code, a device failure a RuntimeError."""
+    import numpy as np
+    knn = np.ascontiguousarray(knn, np.int32)
+    if knn.ndim != 2:
+        raise ValueError(f"knn must be int32 [N, W], got {list(knn.shape)}")
+    n, w = knn.shape
+    order = np.empty((n, w), np.int32)
+    det = np.empty((n, w), np.int32) if want_detours else None
+    lib = N.lib()
+    rc = int(lib.hz_graph_prune(int(device), knn.ctypes.data, n, w, order.ctypes.data, det.ctypes.data if want_detours else None))
+    if rc == -242 or rc > 0:
+        raise RuntimeError((lib.hz_index_last_error() or b"").decode() or f"hz_graph_prune failed ({rc})")
+    if rc:
+        raise ValueError(f"hz_graph_prune refused N = {n}, W = {w} ({rc}: csrc/hipzap.h HZ_K_GRAPH_PRUNE)")
+    return order, det

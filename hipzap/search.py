@@ -824,7 +824,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
                 ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
                 pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host", ivf_init=None, graph=None,
-                graph_backend: str = "cpu") -> dict:
+                graph_backend: str = "cpu", graph_prune: bool = False) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -844,9 +844,11 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     picks how training sums a cluster's rows (:func:`pq_train`'s ``means``). ``graph=DEG`` (plain bf16 rows without
     tags): a version-12 file, which also holds the neighbour graph :meth:`Index.search_graph` walks --
     :func:`graph_build` over the kNN lists of the stored rows, from ``RefIndex`` (``graph_backend="cpu"``) or from
-    :meth:`Index.knn_graph` on ``device`` (``"gpu"``) -- and :func:`graph_entries`' entry rows."""
+    :meth:`Index.knn_graph` on ``device`` (``"gpu"``) -- and :func:`graph_entries`' entry rows. ``graph_prune=True``:
+    the lists are taken at twice the width and reordered by :func:`graph_prune` on that backend first (the file
+    format is the same: a pruned graph is a graph)."""
     _check_ivf_backend(ivf_backend, ivf)
-    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and tags is None and not rescore)
+    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and tags is None and not rescore, graph_prune)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")
@@ -904,29 +906,31 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     if ivf_init is not None:
         raise ValueError("ivf_init goes with ivf=nlist")
     if graph is not None:
-        return _write_file(path, hdr, rows, graph=_graph_of(hdr, rows, graph, graph_backend, device, path))
+        return _write_file(path, hdr, rows, graph=_graph_of(hdr, rows, graph, graph_backend, device, path, graph_prune))
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows, pq=codebook)
 
 
-def _check_graph_args(graph, graph_backend, plain: bool):
+def _check_graph_args(graph, graph_backend, plain: bool, graph_prune: bool = False):
     if graph_backend not in IVF_BACKENDS:
         raise ValueError(f"graph_backend must be one of {IVF_BACKENDS}, got {graph_backend!r}")
     if graph is None and graph_backend != "cpu":
         raise ValueError("graph_backend goes with graph=DEG")
+    if graph is None and graph_prune:
+        raise ValueError("graph_prune goes with graph=DEG")
     if graph is not None and (not _is_int(graph) or not 8 <= graph <= 64 or graph % 8):
         raise ValueError(f"graph must be a degree, a multiple of 8 in 8..64, got {graph!r}")
     if graph is not None and not plain:
         raise ValueError(f"graph={graph!r} goes with a plain bf16 index: no tags, lists, rescore rows or other dtype")
 
 
-def _graph_of(hdr: dict, bits, deg: int, backend: str, device: int, near: str):
-    """The stored graph of degree ``deg`` over the bf16 rows ``bits`` and its entry rows: the kNN lists come from a
-    temporary plain index beside ``near``, opened on the chosen backend."""
+def _graph_of(hdr: dict, bits, deg: int, backend: str, device: int, near: str, prune: bool = False):
+    """The stored graph of degree ``deg`` over the bf16 rows ``bits`` and its entry rows: the kNN lists (``prune``: the
+    pruned lists of twice the width) come from a temporary plain index beside ``near``, opened on the chosen backend."""
     tmp = near + ".graph-knn.tmp"
     try:
         _write_file(tmp, {k: hdr[k] for k in ("dim", "count", "dtype", "metric")}, bits)
         with (Index(tmp, device=device) if backend == "gpu" else RefIndex(tmp)) as ix:
-            knn = ix.knn_graph(deg)[0]
+            knn = ix._graph_lists(deg, prune)
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
@@ -1377,6 +1381,61 @@ def graph_build(knn_ids, deg: int) -> np.ndarray:
     graph[rdst, nfirst[rdst] + np.arange(rdst.size) - np.searchsorted(rdst, rdst)] = rsrc
     graph[row[fresh], (nfirst + nrev)[row[fresh]] + (np.cumsum(fresh, axis=1) - 1)[fresh]] = knn[fresh]
     return graph
+
+
+PRUNE_MIN_W, PRUNE_MAX_W = 16, 128  # HZ_K_GRAPH_PRUNE's list widths (csrc/hipzap.h), multiples of 8
+
+
+def _check_prune_lists(knn) -> np.ndarray:
+    k = np.asarray(knn)
+    if k.ndim != 2 or k.dtype.kind not in "iu" or k.shape[0] < 1 or not PRUNE_MIN_W <= k.shape[1] <= PRUNE_MAX_W or k.shape[1] % 8:
+        raise ValueError(f"knn must be integers [N >= 1, W] with W a multiple of 8 in {PRUNE_MIN_W}..{PRUNE_MAX_W}, got "
+                         f"{k.dtype} {list(k.shape)}")
+    return k
+
+
+def graph_prune_ref(knn, *, chunk: int = 1024):
+    """The oracle of the pruning kernel (csrc/hipzap.h HZ_K_GRAPH_PRUNE, "THE RULE"): kNN lists (int [N, W], best
+    first) -> (order int32 [N, W], detours int32 [N, W]). Column j of row x is valid as in :func:`graph_build` (an id in
+    [0, N) that is not x and that no earlier column holds); ``detours[x, j]`` counts the pairs (i, r), both below j, with
+    column i valid and ``knn[knn[x, i], r] == knn[x, j]`` -- the two-edge routes to that neighbour through a better one;
+    ``order[x]`` is the valid ids by (detours, column) ascending, then -1. Chunked numpy, one column i at a time."""
+    k = _check_prune_lists(knn).astype(np.int64)
+    n, w = k.shape
+    col = np.arange(w)
+    ok = (k >= 0) & (k < n) & (k != np.arange(n)[:, None])
+    by = np.argsort(k, axis=1, kind="stable")  # a repeated id: every occurrence after the first
+    srt = np.take_along_axis(k, by, axis=1)
+    again = np.zeros((n, w), bool)
+    np.put_along_axis(again, by[:, 1:], srt[:, 1:] == srt[:, :-1], axis=1)
+    ok &= ~again
+    det = np.zeros((n, w), np.int32)
+    below = col[:, None] > col[None, :]  # [j, r]: r < j
+    for a in range(0, n, chunk):
+        lst, v = k[a:a + chunk], ok[a:a + chunk]
+        for i in range(w):
+            via = k[np.where(v[:, i], lst[:, i], 0)]  # [chunk, r]: the row of neighbour i as it lies
+            hits = ((via[:, None, :] == lst[:, :, None]) & below[None]).sum(axis=2)  # [chunk, j]
+            det[a:a + chunk] += hits * (v & v[:, i:i + 1] & (col > i)[None])
+    key = np.where(ok, det.astype(np.int64) * w + col, np.iinfo(np.int64).max)
+    order = np.take_along_axis(np.where(ok, k, -1), np.argsort(key, axis=1, kind="stable"), axis=1)
+    return order.astype(np.int32), det
+
+
+def graph_prune(knn, backend: str = "cpu", device: int = 0) -> np.ndarray:
+    """kNN lists (int [N, W], best first, W a multiple of 8 in 16..128) -> the lists reordered for :func:`graph_build`
+    (DESIGN.md 4ad): each row's valid ids, the ones fewest two-edge detours through better neighbours replace first,
+    then -1. ``backend="cpu"``: :func:`graph_prune_ref`; ``"gpu"``: HZ_K_GRAPH_PRUNE on ``device`` -- the same ints.
+    A pruned graph of degree ``deg`` is ``graph_build(graph_prune(lists of width 2 * deg), deg)``."""
+    if backend not in IVF_BACKENDS:
+        raise ValueError(f"backend must be one of {IVF_BACKENDS}, got {backend!r}")
+    k = _check_prune_lists(knn)
+    if backend == "cpu":
+        return graph_prune_ref(k)[0]
+    if k.shape[0] * k.shape[1] >= 2 ** 31 or (k.size and (k.min() < -2 ** 31 or k.max() >= 2 ** 31)):
+        raise ValueError(f"backend='gpu' takes int32 lists of fewer than 2^31 entries, got {k.dtype} {list(k.shape)}")
+    from .ops import search as OS
+    return OS.graph_prune_lists(k, device=device)[0]
 
 
 def check_graph(graph, n: int, entries=None):
@@ -1933,12 +1992,22 @@ class _Base:
             self._attach_graph(g, e)
             self.graph, self.graph_entries = g, e
 
-    def build_graph(self, deg: int = 32) -> np.ndarray:
-        """:meth:`knn_graph` at k = ``deg``, :func:`graph_build`, :meth:`set_graph` -> the graph."""
+    def build_graph(self, deg: int = 32, *, prune: bool = False) -> np.ndarray:
+        """:meth:`knn_graph` at k = ``deg``, :func:`graph_build`, :meth:`set_graph` -> the graph. ``prune=True``: the
+        lists are taken at k = 2 ``deg`` and reordered by :func:`graph_prune` on this index's backend first."""
         self._check_graph_index("build_graph")
-        g = graph_build(self.knn_graph(deg)[0], deg)
+        g = graph_build(self._graph_lists(deg, prune), deg)
         self.set_graph(g)
         return g
+
+    def _graph_lists(self, deg: int, prune: bool) -> np.ndarray:
+        """What :func:`graph_build` takes for a graph of degree ``deg``: the kNN lists, or the pruned lists of twice
+        the width (HZ_K_GRAPH_PRUNE on an :class:`Index`'s device, :func:`graph_prune_ref` on a :class:`RefIndex`)."""
+        if not prune:
+            return self.knn_graph(deg)[0]
+        if not _is_int(deg) or not 8 <= deg <= 64 or deg % 8:
+            raise ValueError(f"deg must be a multiple of 8 in 8..64, got {deg!r}")
+        return graph_prune(self.knn_graph(2 * deg)[0], self.backend, getattr(self, "device", 0))
 
     def _check_graph_search(self, q, k, beam, width, iters):
         if self.graph is None:
@@ -2845,7 +2914,7 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
                   ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None,
                   pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host",
-                  graph=None, graph_backend: str = "cpu") -> dict:
+                  graph=None, graph_backend: str = "cpu", graph_prune: bool = False) -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -2860,15 +2929,15 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     ``pq_seed`` / ``pq_iters``, unless ``pq_codebook`` is given) and encoded as they stand, which gives the bytes
     ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11.
     ``pq_backend`` and ``pq_means`` as in :func:`write_index`. ``graph=DEG`` (``dtype="bf16"``, a plain version-1 ``src``): the
-    same rows plus their neighbour graph, a version-12 file (``graph_backend`` as in :func:`write_index`)."""
+    same rows plus their neighbour graph, a version-12 file (``graph_backend`` and ``graph_prune`` as in :func:`write_index`)."""
     _check_ivf_backend(ivf_backend, ivf)
-    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and not rescore)
+    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and not rescore, graph_prune)
     if graph is not None:
         hdr = read_header(src)
         if hdr["dtype"] != "bf16" or any(k in hdr for k in ("ivf", "tags_off", "graph_off")):
             raise ValueError(f"graph={graph!r}: {src} is not a plain bf16 index of version 1")
         out, bits = {k: v for k, v in hdr.items() if k != "data_off"}, read_rows(src)
-        return _write_file(dst, out, bits, graph=_graph_of(out, bits, graph, graph_backend, device, dst))
+        return _write_file(dst, out, bits, graph=_graph_of(out, bits, graph, graph_backend, device, dst, graph_prune))
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")

@@ -4,6 +4,7 @@ truth and milliseconds per call, launch to sync, the routes interleaved.
     python scripts/search_graph_measure.py --n 100000 --out profiles/search_graph/measure.jsonl
 """
 import argparse
+import contextlib
 import json
 import os
 import tempfile
@@ -26,6 +27,26 @@ def recall(ids, truth):
     return sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(ids, truth)) / truth.size
 
 
+def prune_kernel_ms(knn, launches=20):
+    """HZ_K_GRAPH_PRUNE alone over device lists: device events around ``launches`` back-to-back launches after a warm-up
+    one, milliseconds per launch."""
+    import torch
+    from hipzap.ops import search as OS
+    src = torch.from_numpy(np.ascontiguousarray(knn, np.int32)).to("cuda:0")
+    order, det = torch.empty_like(src), torch.empty_like(src)
+    p = OS.GraphPruneParams(src.data_ptr(), order.data_ptr(), det.data_ptr(), *knn.shape)
+    st = torch.cuda.current_stream().cuda_stream
+    assert OS.launch_graph_prune(p, st) == 0
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(launches):
+        OS.launch_graph_prune(p, st)
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / launches
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=100000)
@@ -35,6 +56,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--truth-queries", type=int, default=256)
     ap.add_argument("--out", default="search_graph.jsonl")
+    ap.add_argument("--prune", action="store_true",
+                    help="add the pruned graph (DESIGN.md 4ad): its build time, its search_graph rows, HZ_K_GRAPH_PRUNE's time")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     out = open(a.out, "w")
@@ -56,18 +79,34 @@ def main():
             S.convert_index(plain, ivf, "bf16", ivf=a.nlist, ivf_backend="gpu")
             t_ivf = time.perf_counter() - t
             emit(corpus=kind, n=a.n, dim=a.dim, build_graph_s=round(t_graph, 2), build_ivf_s=round(t_ivf, 2), deg=a.deg, nlist=a.nlist)
+            if a.prune:
+                pruned = os.path.join(d, f"{kind}-pruned.hzidx")
+                t = time.perf_counter()
+                S.convert_index(plain, pruned, "bf16", graph=a.deg, graph_backend="gpu", graph_prune=True)
+                emit(corpus=kind, n=a.n, dim=a.dim, deg=a.deg, build_graph_s=round(t_graph, 2),
+                     build_pruned_graph_s=round(time.perf_counter() - t, 2))
             tq = q[:a.truth_queries]
             truth = S.search_ref(S.bf16_to_f32(S.read_rows(plain)), tq, 10)[1]
             del rows
-            with S.Index(plain) as px, S.Index(graph) as gx, S.Index(ivf) as vx:
+            with S.Index(plain) as px, S.Index(graph) as gx, S.Index(ivf) as vx, \
+                    (S.Index(pruned) if a.prune else contextlib.nullcontext()) as rx:
+                for w in (64, 128) if a.prune else ():
+                    emit(corpus=kind, n=a.n, kernel="HZ_K_GRAPH_PRUNE", W=w, ms=round(prune_kernel_ms(px.knn_graph(w)[0]), 3))
                 routes = {"search (plain scan)": lambda x: px.search(x, 10)}
                 for beam, width in ((32, 1), (64, 1), (64, 2), (128, 2), (256, 4)):
                     routes[f"search_graph beam={beam} width={width}"] = lambda x, b=beam, w=width: gx.search_graph(x, 10, beam=b, width=w)
+                    if a.prune:
+                        routes[f"search_graph pruned beam={beam} width={width}"] = \
+                            lambda x, b=beam, w=width: rx.search_graph(x, 10, beam=b, width=w)
                 for nprobe in (1, 2, 4, 8, 16, 32, 64):
                     routes[f"ivf nprobe={nprobe}"] = lambda x, p=nprobe: vx.search(x, 10, nprobe=p)
                 rec = {name: recall(f(tq)[1], truth) for name, f in routes.items()}
                 stats = gx.search_graph(tq, 10, beam=64, width=1, stats=True)[2]
                 emit(corpus=kind, rows_scored_beam64=float(stats[:, 1].mean()), iterations_beam64=float(stats[:, 0].mean()))
+                if a.prune:
+                    stats = rx.search_graph(tq, 10, beam=64, width=1, stats=True)[2]
+                    emit(corpus=kind, graph="pruned", rows_scored_beam64=float(stats[:, 1].mean()),
+                         iterations_beam64=float(stats[:, 0].mean()))
                 for nq in (1, 16, 1024):
                     part, ms = q[:nq], {name: [] for name in routes}
                     for f in routes.values():
