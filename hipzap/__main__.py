@@ -140,8 +140,12 @@ def cmd_index(a):
         raise SystemExit("index: --graph-backend goes with --graph DEG")
     if a.graph is None and a.graph_prune:
         raise SystemExit("index: --graph-prune goes with --graph DEG")
+    if a.graph is None and a.graph_seeds is not None:
+        raise SystemExit("index: --graph-seeds goes with --graph DEG")
     if a.graph is not None:
         pq = dict(pq, graph=a.graph, graph_backend=a.graph_backend, graph_prune=a.graph_prune)  # the writers' further keywords
+    if a.graph_seeds is not None:
+        pq = dict(pq, graph_seeds=a.graph_seeds)
     if a.rescore and a.dtype not in ("fp8", "bin", "pq"):
         raise SystemExit(f"index: --rescore goes with --dtype fp8: a {a.dtype} index already holds its rows in bf16, "
                          f"there is nothing to re-score against")
@@ -379,6 +383,9 @@ def main(argv=None):
                          "8..64) for Index.search_graph")
     ix.add_argument("--graph-backend", choices=["cpu", "gpu"], default="cpu",
                     help="with --graph: where the kNN lists come from; gpu: Index.knn_graph on --device (dim %% 32 == 0)")
+    ix.add_argument("--graph-seeds", type=int, default=None, metavar="S",
+                    help="with --graph: a version-13 file, which also holds S evenly spaced seed rows (1..8192) that "
+                         "search_graph(seeds=E) picks each query's entry rows from")
     ix.add_argument("--graph-prune", action="store_true",
                     help="with --graph: take kNN lists of width 2 DEG and keep the edges that the fewest two-edge detours replace")
     ix.add_argument("--from-index", default=None, help="a bf16 .hzidx to rewrite in --dtype (rows requantised as stored, ids kept); an IVF file keeps its lists "

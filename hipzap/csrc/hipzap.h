@@ -996,6 +996,9 @@ int hz_search_rescorep_launch(const HzSearchRescorePosParams* p, hipStream_t st)
 // 1..256 / deg; -225 iters < 1; -226 E outside 1..256; -227 E + iters * width * deg > HZ_SEARCH_GRAPH_CAP_LARGE / 2;
 // -228 corpus, queries, graph, entries, out_score or out_id null; -229 corpus or queries not 16-B aligned or graph,
 // entries, out_score, out_id or out_stats not 4-B aligned.
+// ENTRIES PER QUERY: estride = 0: `entries` is [E], shared, as above. estride > 0: `entries` is
+// [Q][estride] with estride >= E and query q starts from entries + q * estride (HZ_K_GRAPH_SEED writes such rows; its
+// -1 padding is skipped like any id outside [0, N)). Nothing else of the walk changes. -251: estride < 0 or in 1..E-1.
 #define HZ_SEARCH_GRAPH_MAX_BEAM 256
 #define HZ_SEARCH_GRAPH_CAP_SMALL 4096
 #define HZ_SEARCH_GRAPH_CAP_LARGE 16384
@@ -1003,13 +1006,42 @@ typedef struct HzSearchGraphParams {
   const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows (ldc % 8 == 0), ldc >= D
   const float* queries;          // device fp32 [Q][D], 16-B aligned
   const int* graph;              // device int32 [N][deg]
-  const int* entries;            // device int32 [E]
+  const int* entries;            // device int32 [E], or [Q][estride]
   float* out_score;              // fp32 [Q][k]
   int* out_id;                   // int32 [Q][k]
   int* out_stats;                // int32 [Q][2] or null
   int N, D, Q, k, ldc, beam, deg, width, iters, E;
+  int estride, pad_;             // 0: shared entries; else the ints between two queries' entry rows
 } HzSearchGraphParams;
 int hz_search_graph_launch(const HzSearchGraphParams* p, hipStream_t st);
+// entry rows per query from a seed table (HZ_K_GRAPH_SEED): scores a query batch against the S seed
+// rows corpus[seeds[j]] with v_mfma_f32_16x16x32_bf16 and writes each query's best E seed ids, which HZ_K_SEARCH_GRAPH
+// then starts from (estride above). One workgroup of 256 threads per 16 queries, one launch, no scratch.
+// THE RULE is stated over the inputs alone. Seed position j is VALID iff (unsigned)seeds[j] < N. qb = the query rounded
+// to bf16, round to nearest even (hipzap.search.to_bf16's rounding). score(q, j) is the fp32 accumulator of the MFMAs over
+// columns 0..31, 32..63, ... in that order from +0, the seed row being the A operand and qb the B operand, the columns
+// past D in the last step zero: HZ_K_SEARCH_ASSIGN's contract, so the bits depend on the D values of qb and of the row
+// only, not on S, Q or which block or wave held them. key = (orderable(score) << 32) | ~j: the higher score wins and,
+// among equal score bits, the lower seed POSITION. out[q][0..E) = seeds[j] of the best E valid keys, best first, then
+// -1; out[q][E..estride) is not written. An id that `seeds` holds twice may be written twice (the index refuses such
+// a table; the walk's visited set would absorb it).
+// SELECTION ONLY: these scores choose rows and nothing else. HZ_K_SEARCH_GRAPH rescores its entries with the scan's own
+// statements, so every published score keeps HZ_K_SEARCH_SCAN's bits; that is why ONE bf16 part of the query suffices
+// here, where the bulk search needs THE SPLIT into three for exactness.
+// Refusals (nothing is launched, one code per rule): -243 D % 8, D outside 8..2048, ldc < D or ldc % 8; -244 N < 1;
+// -245 Q outside 1..HZ_SEARCH_SELF_MAX_Q; -246 S outside 1..HZ_GRAPH_SEED_MAX; -247 E outside 1..HZ_GRAPH_SEED_MAX_E;
+// -248 estride < E; -249 corpus, queries, seeds or out null; -250 corpus or queries not 16-B aligned or seeds or out
+// not 4-B aligned.
+#define HZ_GRAPH_SEED_MAX 8192
+#define HZ_GRAPH_SEED_MAX_E 64
+typedef struct HzGraphSeedParams {
+  const unsigned short* corpus;  // bf16 [N][ldc], 16-B aligned rows (ldc % 8 == 0), ldc >= D
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const int* seeds;              // device int32 [S]
+  int* out;                      // device int32 [Q][estride]
+  int N, D, Q, S, E, ldc, estride, pad_;
+} HzGraphSeedParams;
+int hz_graph_seed_launch(const HzGraphSeedParams* p, hipStream_t st);
 // rank-based pruning of kNN lists (HZ_K_GRAPH_PRUNE): reorders every row's list so that the edges no
 // short detour replaces come first; graph_build (hipzap/search.py) then keeps those. Integers only, exact.
 // THE RULE is stated over the input alone. knn is int32 [N][W], best first, W a multiple of 8 in 16..128. Column j of
@@ -1300,9 +1332,21 @@ double hz_index_search_batch_ivf_invert_us(void* idx, int ctx);
 // A version-12 file (version 1 plus "graph_deg", "graph_off", "entries", "entries_off": int32 graph [count][graph_deg] and the
 // entry rows, two 4096-aligned blocks after the rows) is opened by hz_index_open* with its graph attached;
 // hz_index_describe3's out[6] is the attached graph's degree (0: none) and out[7] its number of entries.
+// SEED TABLE. hz_index_set_graph_seeds uploads S seed ids (host int32) to an index that has a graph,
+// replacing an earlier table; it takes every context's mutex. -252: no graph; -253: S outside 1..HZ_GRAPH_SEED_MAX;
+// -254: an id outside [0, n) or an id held twice. hz_index_set_graph drops the table with the graph it replaces.
+// hz_index_search_graph2 is hz_index_search_graph with `nseed` (that call forwards 0: the shared entries). nseed > 0:
+// the program, per (Q, k, beam, width, iters, nseed), is H2D, HZ_K_GRAPH_SEED into a [Q][nseed] device buffer,
+// HZ_K_SEARCH_GRAPH with E = estride = nseed, D2H; the visited bound takes nseed for E. -255: nseed > 0 and the index
+// has no seed table; -256: nseed outside 0..HZ_GRAPH_SEED_MAX_E.
+// A version-13 file is version 12 plus "seeds" and "seeds_off": one more 4096-aligned int32 block after the entries,
+// uploaded by hz_index_open*. hz_index_describe3's out[3] is the table's size on an index without lists (0: none).
 int hz_index_set_graph(void* idx, const int* graph, long long n, int deg, const int* entries, int E);
+int hz_index_set_graph_seeds(void* idx, const int* seeds, int S);
 int hz_index_search_graph(void* idx, int ctx, const float* queries, int Q, int k, int beam, int width, int iters,
                           float* out_score, int* out_id, int* out_stats);
+int hz_index_search_graph2(void* idx, int ctx, const float* queries, int Q, int k, int beam, int width, int iters, int nseed,
+                           float* out_score, int* out_id, int* out_stats);
 // hz_graph_prune: HZ_K_GRAPH_PRUNE over host lists `knn` (int32 [n][W]) on `device` -> `order_out`
 // and, unless null, `detours_out` (both int32 [n][W]). No index: a stream and three device buffers of its own, H2D,
 // the launch, D2H, one synchronise, all released on every way out. The launcher's refusals -238 .. -241 pass through
@@ -1547,7 +1591,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_LXSCAN, 54, HzSearchListBatchParams, hz_search_lxscan_op, SEARCH) \
   X(SEARCH_RESCOREP, 55, HzSearchRescorePosParams, hz_search_rescorep_op, SEARCH) \
   X(SEARCH_GRAPH, 56, HzSearchGraphParams, hz_search_graph_op, SEARCH)   \
-  X(GRAPH_PRUNE, 57, HzGraphPruneParams, hz_graph_prune_op, SEARCH)
+  X(GRAPH_PRUNE, 57, HzGraphPruneParams, hz_graph_prune_op, SEARCH)      \
+  X(GRAPH_SEED, 58, HzGraphSeedParams, hz_graph_seed_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

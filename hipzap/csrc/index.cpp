@@ -135,6 +135,7 @@ struct Ctx {
   uint64_t wl_bytes = 0;
   double invert_us = 0;
   float* blast_dev = nullptr;  // bulk search on a version-10 or version-3 index only: stage one's R-th score per query [SELF_MAX_Q]
+  int* gentry_dev = nullptr;   // graph search with seeds only: the queries' entry rows [SELF_MAX_Q][HZ_GRAPH_SEED_MAX_E]
   // clustering only (hz_index_assign / hz_index_cmean), device memory allocated on first use and grown on demand:
   // centroids bf16 [C][dim]; live AND mask, cap / 8 bytes; lists int32 then scores fp32, [scan rows] each; the
   // members int32 [M]; seg_off int32 [C + 1]; the fp32 centroids [C][dim]
@@ -144,7 +145,7 @@ struct Ctx {
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
   // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0), on
   // fp8 rows (Q, k, 6, R, 0); the coarse stage of a bulk search over an IVF index: (Q, nprobe, 7, Rc, 0)
-  // graph search: (Q, k, kProgGraph, beam * 1024 + width, iters)
+  // graph search: (Q, k, kProgGraph + 16 * nseed, beam * 1024 + width, iters); nseed <= 64
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
 
@@ -210,6 +211,9 @@ struct Index {
   int* graph_dev = nullptr;
   uint64_t graph_n = 0;
   int graph_deg = 0, graph_e = 0;
+  // the graph's seed table (hz_index_set_graph_seeds): device int32 [seed_n]; null: none
+  int* seed_dev = nullptr;
+  int seed_n = 0;
   std::vector<std::unique_ptr<Ctx>> ctx;
 
   ~Index() {
@@ -237,6 +241,7 @@ struct Index {
       if (c->bmid_dev) (void)hipFree(c->bmid_dev);
       if (c->bout_dev) (void)hipFree(c->bout_dev);
       if (c->blast_dev) (void)hipFree(c->blast_dev);
+      if (c->gentry_dev) (void)hipFree(c->gentry_dev);
       if (c->wl_host) (void)hipHostFree(c->wl_host);
       if (c->wl_dev) (void)hipFree(c->wl_dev);
       for (void* b : c->cl)
@@ -255,6 +260,7 @@ struct Index {
     if (pos_dev) (void)hipFree(pos_dev);
     if (cent_live) (void)hipFree(cent_live);
     if (graph_dev) (void)hipFree(graph_dev);
+    if (seed_dev) (void)hipFree(seed_dev);
   }
 
   // the stored row of a public id, -1 for an id outside the index
@@ -483,9 +489,16 @@ struct Index {
 
   // The graph-search program of (Q, k, beam, width, iters) (the caller holds c.mu): H2D of the queries,
   // HZ_K_SEARCH_GRAPH -- one launch, a static grid of Q workgroups -- into bout_dev, the stats into bmid_dev, three D2H.
-  HzProgram graph_program(Ctx& c, int Q, int k, int beam, int width, int iters, bool* fresh) {
+  // nseed > 0: HZ_K_GRAPH_SEED first writes each query's nseed entry rows into gentry_dev, and the walk
+  // reads them per query (E = estride = nseed): one more launch in the same program, no scratch, no second index.
+  HzProgram graph_program(Ctx& c, int Q, int k, int beam, int width, int iters, int nseed, bool* fresh) {
     if (!batch_buffers(c)) return nullptr;
-    const auto key = std::make_tuple(Q, k, (int)kProgGraph, beam * 1024 + width, iters);  // beam <= 256, width <= 32
+    if (nseed > 0 && !c.gentry_dev &&
+        hipMalloc(reinterpret_cast<void**>(&c.gentry_dev), (size_t)HZ_INDEX_SELF_MAX_Q * HZ_GRAPH_SEED_MAX_E * 4) != hipSuccess) {
+      c.gentry_dev = nullptr;
+      return nullptr;
+    }
+    const auto key = std::make_tuple(Q, k, (int)kProgGraph + 16 * nseed, beam * 1024 + width, iters);  // beam <= 256, width <= 32
     auto it = c.progs.find(key);
     *fresh = it == c.progs.end();
     if (!*fresh) return it->second;
@@ -499,9 +512,16 @@ struct Index {
     p.out_stats = reinterpret_cast<int*>(c.bmid_dev);
     p.N = (int)graph_n, p.D = p.ldc = (int)h.dim, p.Q = Q, p.k = k;
     p.beam = beam, p.deg = graph_deg, p.width = width, p.iters = iters, p.E = graph_e;
+    HzGraphSeedParams sp{};
+    if (nseed > 0) {
+      sp.corpus = rows, sp.queries = c.bq_dev, sp.seeds = seed_dev, sp.out = c.gentry_dev;
+      sp.N = (int)graph_n, sp.D = sp.ldc = (int)h.dim, sp.Q = Q, sp.S = seed_n, sp.E = sp.estride = nseed;
+      p.entries = c.gentry_dev, p.E = p.estride = nseed;
+    }
     HzProgram g = hz_prog_create();
     const size_t qk = (size_t)Q * k * 4;
     int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
+    if (!rc && nseed > 0) rc = hz_prog_add_kernel(g, HZ_K_GRAPH_SEED, &sp, sizeof(sp), 0);
     if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_GRAPH, &p, sizeof(p), 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
@@ -820,6 +840,7 @@ extern "C" {
 
 const char* hz_index_last_error(void) { return g_err.c_str(); }
 int hz_index_set_graph(void* h, const int* graph, long long n, int deg, const int* entries, int E);
+int hz_index_set_graph_seeds(void* h, const int* seeds, int S);
 
 void* hz_index_open3(const char* path, int device, int nctx, long long reserve_rows, int rescore_host) {
   g_err.clear();
@@ -832,13 +853,13 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   struct stat sb {};
   bool got = fstat(fd, &sb) == 0 && pread(fd, &h, sizeof(h), 0) == (ssize_t)sizeof(h);
   std::string js;
-  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 12 && h.json_len < (1u << 30)) {
+  if (got && std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) == 0 && h.version >= 2 && h.version <= 13 && h.json_len < (1u << 30)) {
     js.resize(h.json_len);
     got = pread(fd, &js[0], h.json_len, sizeof(h)) == (ssize_t)h.json_len;
   }
   close(fd);
   if (!got || std::memcmp(h.magic, HZ_INDEX_MAGIC, 8) != 0) return fail(std::string("index: not a .hzidx file: ") + path);
-  if (h.version < 1 || h.version > 12) return fail("index: unknown format version " + std::to_string(h.version));
+  if (h.version < 1 || h.version > 13) return fail("index: unknown format version " + std::to_string(h.version));
   const bool ivf = h.version >= 5 && h.version <= 7;
   const bool fp8 = h.version == 3 || h.version == 4 || h.version == 6 || h.version == 7;
   const bool bin = h.version == 8 || h.version == 9;
@@ -853,17 +874,22 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
     return fail("index: the dtype of the JSON header disagrees with a " + vname + " file");
   if (!ivf && js.rfind("\"ivf\": {") != std::string::npos)
     return fail("index: an ivf block in a " + vname + " file (it belongs to versions 5, 6 and 7)");
-  const bool with_graph = h.version == 12;  // version 1 plus the graph and entries blocks
-  uint64_t gr_u[4] = {0, 0, 0, 0};  // graph_deg, graph_off, entries, entries_off
+  const bool with_seeds = h.version == 13;  // version 12 plus the seed table's block
+  const bool with_graph = h.version == 12 || with_seeds;  // version 1 plus the graph and entries blocks
+  uint64_t gr_u[6] = {0, 0, 0, 0, 0, 0};  // graph_deg, graph_off, entries, entries_off, seeds, seeds_off
   if (with_graph) {
-    static const char* keys[4] = {"graph_deg", "graph_off", "entries", "entries_off"};
-    for (int i = 0; i < 4; ++i)
-      if (!json_u64(js, keys[i], &gr_u[i], true)) return fail(std::string("index: a version-12 file without ") + keys[i]);
+    static const char* keys[6] = {"graph_deg", "graph_off", "entries", "entries_off", "seeds", "seeds_off"};
+    for (int i = 0; i < (with_seeds ? 6 : 4); ++i)
+      if (!json_u64(js, keys[i], &gr_u[i], true)) return fail("index: a " + vname + " file without " + keys[i]);
+    if (with_seeds && (gr_u[4] < 1 || gr_u[4] > HZ_GRAPH_SEED_MAX))
+      return fail("index: a seed table holds 1.." + std::to_string(HZ_GRAPH_SEED_MAX) + " ids, got seeds = " + std::to_string(gr_u[4]));
+    if (!with_seeds && js.rfind("\"seeds_off\":") != std::string::npos)
+      return fail("index: seed keys in a " + vname + " file (they belong to version 13)");
     if (gr_u[0] < 8 || gr_u[0] > 64 || gr_u[0] % 8 || gr_u[2] < 1 || gr_u[2] > 256)
       return fail("index: a graph needs graph_deg % 8 == 0 in 8..64 and 1..256 entries, got graph_deg = " + std::to_string(gr_u[0]) +
                   ", entries = " + std::to_string(gr_u[2]));
   } else if (js.rfind("\"graph_off\":") != std::string::npos) {
-    return fail("index: graph keys in a " + vname + " file (they belong to version 12)");
+    return fail("index: graph keys in a " + vname + " file (they belong to versions 12 and 13)");
   }
   uint64_t pq_u[4] = {0, 0, 0, 0};  // m, ksub, dsub, codebook_off
   if (pq) {
@@ -946,17 +972,17 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
       return fail("index: tags or live block outside the file");
     after_rows = std::max(after_rows, std::max(tags_off + tag_bytes, live_off + live_bytes));
   }
-  std::vector<int32_t> graph_host;  // graph [count][deg], then the entries
+  std::vector<int32_t> graph_host;  // graph [count][deg], then the entries, then the seeds
   if (with_graph) {
-    const uint64_t len[2] = {h.count * gr_u[0] * 4, gr_u[2] * 4}, off[2] = {gr_u[1], gr_u[3]};
-    graph_host.resize(h.count * gr_u[0] + gr_u[2]);
+    const uint64_t len[3] = {h.count * gr_u[0] * 4, gr_u[2] * 4, gr_u[4] * 4}, off[3] = {gr_u[1], gr_u[3], gr_u[5]};
+    graph_host.resize(h.count * gr_u[0] + gr_u[2] + gr_u[4]);
     char* dst = reinterpret_cast<char*>(graph_host.data());
     const int gfd = open(path, O_RDONLY | O_CLOEXEC);
     bool ok = gfd >= 0;
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < (with_seeds ? 3 : 2); ++i) {
       if (off[i] % 4096 || off[i] < after_rows || off[i] > fsize || len[i] > fsize - off[i]) {
         if (gfd >= 0) close(gfd);
-        return fail("index: the graph or entries block is unaligned, overlaps another block or lies outside the file");
+        return fail("index: the graph, entries or seeds block is unaligned, overlaps another block or lies outside the file");
       }
       after_rows = off[i] + len[i];
       uint64_t done = 0;
@@ -1169,6 +1195,8 @@ void* hz_index_open3(const char* path, int device, int nctx, long long reserve_r
   if (with_graph && hz_index_set_graph(idx.get(), graph_host.data(), (long long)h.count, (int)gr_u[0],
                                        graph_host.data() + h.count * gr_u[0], (int)gr_u[2]))
     return fail("index: graph upload failed" + (g_err.empty() ? std::string() : ": " + g_err));
+  if (with_seeds && hz_index_set_graph_seeds(idx.get(), graph_host.data() + h.count * gr_u[0] + gr_u[2], (int)gr_u[4]))
+    return fail("index: seed table upload failed" + (g_err.empty() ? std::string() : ": " + g_err));
   return idx.release();
 }
 
@@ -1214,7 +1242,7 @@ int hz_index_describe3(void* h, uint64_t* out) {
   if (!h || !out) return -1;
   Index* x = static_cast<Index*>(h);
   AllLocked all(*x);
-  const uint64_t v[8] = {x->ivf ? 1u : 0u, (uint64_t)x->nlist, (uint64_t)x->nprobe_default, x->ivf ? x->count / kTile : 0,
+  const uint64_t v[8] = {x->ivf ? 1u : 0u, (uint64_t)x->nlist, (uint64_t)x->nprobe_default, x->ivf ? x->count / kTile : (uint64_t)x->seed_n,
                          x->ivf ? x->n_ext : x->count, x->h.version, (uint64_t)x->graph_deg, (uint64_t)x->graph_e};
   std::memcpy(out, v, sizeof(v));
   return 0;
@@ -1518,7 +1546,7 @@ int hz_index_set_graph(void* h, const int* graph, long long n, int deg, const in
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   for (auto& c : x->ctx)  // the programs of an earlier graph hold its address by value
     for (auto it = c->progs.begin(); it != c->progs.end();) {
-      if (std::get<2>(it->first) == kProgGraph) {
+      if (std::get<2>(it->first) % 16 == kProgGraph) {
         hz_prog_destroy(it->second);
         it = c->progs.erase(it);
       } else {
@@ -1526,7 +1554,8 @@ int hz_index_set_graph(void* h, const int* graph, long long n, int deg, const in
       }
     }
   if (x->graph_dev) (void)hipFree(x->graph_dev);
-  x->graph_dev = nullptr, x->graph_n = 0, x->graph_deg = x->graph_e = 0;
+  if (x->seed_dev) (void)hipFree(x->seed_dev);  // a seed table belongs to the graph it was set for
+  x->graph_dev = x->seed_dev = nullptr, x->graph_n = 0, x->graph_deg = x->graph_e = x->seed_n = 0;
   const size_t gwords = (size_t)n * deg;
   if (hipMalloc(reinterpret_cast<void**>(&x->graph_dev), (gwords + E) * 4) != hipSuccess) {
     x->graph_dev = nullptr;
@@ -1542,8 +1571,59 @@ int hz_index_set_graph(void* h, const int* graph, long long n, int deg, const in
   return 0;
 }
 
+int hz_index_set_graph_seeds(void* h, const int* seeds, int S) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !seeds) return -1;
+  AllLocked all(*x);
+  if (!x->graph_dev) {
+    g_err = "index: a seed table goes with a graph (hz_index_set_graph), this index has none";
+    return -252;
+  }
+  if (S < 1 || S > HZ_GRAPH_SEED_MAX) {
+    g_err = "index: a seed table holds 1.." + std::to_string(HZ_GRAPH_SEED_MAX) + " ids, got " + std::to_string(S);
+    return -253;
+  }
+  std::vector<bool> held(x->graph_n, false);
+  for (int j = 0; j < S; ++j) {
+    if (seeds[j] < 0 || (uint64_t)seeds[j] >= x->graph_n || held[seeds[j]]) {
+      g_err = "index: seed " + std::to_string(j) + " is " + std::to_string(seeds[j]) + ": " +
+              (seeds[j] < 0 || (uint64_t)seeds[j] >= x->graph_n ? "outside [0, " + std::to_string(x->graph_n) + ")" : "held twice");
+      return -254;
+    }
+    held[seeds[j]] = true;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  for (auto& c : x->ctx)  // the programs of an earlier table hold its address and size by value
+    for (auto it = c->progs.begin(); it != c->progs.end();) {
+      if (std::get<2>(it->first) % 16 == kProgGraph && std::get<2>(it->first) != kProgGraph) {
+        hz_prog_destroy(it->second);
+        it = c->progs.erase(it);
+      } else {
+        ++it;
+      }
+    }
+  if (x->seed_dev) (void)hipFree(x->seed_dev);
+  x->seed_dev = nullptr, x->seed_n = 0;
+  if (hipMalloc(reinterpret_cast<void**>(&x->seed_dev), (size_t)S * 4) != hipSuccess) {
+    x->seed_dev = nullptr;
+    return -11;
+  }
+  if (hipMemcpy(x->seed_dev, seeds, (size_t)S * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(x->seed_dev);
+    x->seed_dev = nullptr;
+    return -11;
+  }
+  x->seed_n = S;
+  return 0;
+}
+
 int hz_index_search_graph(void* h, int ctx, const float* queries, int Q, int k, int beam, int width, int iters,
                           float* out_score, int* out_id, int* out_stats) {
+  return hz_index_search_graph2(h, ctx, queries, Q, k, beam, width, iters, 0, out_score, out_id, out_stats);
+}
+
+int hz_index_search_graph2(void* h, int ctx, const float* queries, int Q, int k, int beam, int width, int iters, int nseed,
+                           float* out_score, int* out_id, int* out_stats) {
   Index* x = static_cast<Index*>(h);
   if (!x || !queries || !out_score || !out_id || !out_stats) return -1;
   if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
@@ -1574,14 +1654,23 @@ int hz_index_search_graph(void* h, int ctx, const float* queries, int Q, int k, 
     g_err = "index: width must be in 1.." + std::to_string(256 / x->graph_deg) + " (256 / the graph's degree), got " + std::to_string(width);
     return -236;
   }
-  if (iters < 1 || (long long)x->graph_e + (long long)iters * width * x->graph_deg > HZ_SEARCH_GRAPH_CAP_LARGE / 2) {
+  if (nseed < 0 || nseed > HZ_GRAPH_SEED_MAX_E) {
+    g_err = "index: seeds must be in 1.." + std::to_string(HZ_GRAPH_SEED_MAX_E) + " entry rows per query, got " + std::to_string(nseed);
+    return -256;
+  }
+  if (nseed > 0 && !x->seed_dev) {
+    g_err = "index: search_graph(seeds=) needs a seed table (hz_index_set_graph_seeds, a version-13 file), this index has none";
+    return -255;
+  }
+  const int ne = nseed > 0 ? nseed : x->graph_e;  // the entries a walk starts from
+  if (iters < 1 || (long long)ne + (long long)iters * width * x->graph_deg > HZ_SEARCH_GRAPH_CAP_LARGE / 2) {
     g_err = "index: iters must be at least 1 with entries + iters * width * deg at most " + std::to_string(HZ_SEARCH_GRAPH_CAP_LARGE / 2) +
             " (half the visited table), got iters = " + std::to_string(iters);
     return -237;
   }
   if (hipSetDevice(x->device) != hipSuccess) return -10;
   bool fresh = false;
-  HzProgram g = x->graph_program(c, Q, k, beam, width, iters, &fresh);
+  HzProgram g = x->graph_program(c, Q, k, beam, width, iters, nseed, &fresh);
   if (!g) return -11;
   std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
   return run_program(c, g, fresh, [&] {

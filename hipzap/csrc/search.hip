@@ -1901,7 +1901,7 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(RESCORE_THREADS) void search_rescorep_
 //     at or past `beam` are dropped.
 //   * parents: thread t holds beam slot t; the first `width` unexpanded slots in beam order (ballot, wave counts) are
 //     the parents, and their flag is cleared in place.
-// Addresses: queries[q*D + i] under i < D; entries[t] under t < E; graph[p*deg + j] under (unsigned)p < N (p was a
+// Addresses: queries[q*D + i] under i < D; entries[q*estride + t] under t < E (estride 0 or >= E); graph[p*deg + j] under (unsigned)p < N (p was a
 // scored row) and j < deg; corpus rows lst[i]*ldc + chunk*8 under (unsigned)id < N -- checked before an id is inserted,
 // so everything in vt, lst and the beam is a row --; vt slots under the mask CAP - 1; beam slots under rank < beam;
 // lst / sk slots under pos < GRAPH_THREADS; out_*[q*k + t] under t < k; out_stats[2q], [2q + 1].
@@ -1963,7 +1963,7 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(GRAPH_THREADS) void search_graph_kerne
   if (!HZ_DCHECK(q < a.Q && a.D >= 8 && a.D % 8 == 0 && a.D <= NC * 64 * Bf16Rows::E && a.D <= 2048 && a.ldc >= a.D &&
                  a.N >= 1 && L >= 32 && L <= GRAPH_MAX_BEAM && a.k >= 1 && a.k <= L && a.k <= HZ_SEARCH_MAX_K && a.deg >= 8 &&
                  a.width >= 1 && a.width * a.deg <= GRAPH_THREADS && a.E >= 1 && a.E <= GRAPH_THREADS && a.iters >= 1 &&
-                 (long)a.E + (long)a.iters * a.width * a.deg <= CAP / 2))
+                 (long)a.E + (long)a.iters * a.width * a.deg <= CAP / 2 && (a.estride == 0 || a.estride >= a.E)))
     return;
   for (int i = t; i < a.D >> 2; i += GRAPH_THREADS)
     reinterpret_cast<f32x4*>(qs)[i] = reinterpret_cast<const f32x4*>(a.queries + (long)q * a.D)[i];
@@ -2029,7 +2029,7 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(GRAPH_THREADS) void search_graph_kerne
   };
 
   int cand = -1;
-  if (t < a.E) cand = a.entries[t];
+  if (t < a.E) cand = a.entries[(long)q * a.estride + t];  // estride 0: the shared entries
   admit(cand);
   for (; it < a.iters; ++it) {
     unsigned long long key = 0ull;
@@ -2195,6 +2195,207 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(PRUNE_WAVES * 64) void graph_prune_ker
     if (ok[c] && HZ_DCHECK(rank[c] < nvalid)) a.order[x * W + rank[c]] = id[c];
     if (j >= nvalid) a.order[x * W + j] = -1;
     if (a.detours) a.detours[x * W + j] = c ? d1 : d0;
+  }
+}
+
+// ----------------------------------------------------------------------------------- graph seeds
+// graph_seed_kernel (HZ_K_GRAPH_SEED): THE RULE of hipzap.h -- each query's best E of the S seed rows, the
+// entry rows its walk starts from. SELECTION ONLY: the scores made here are compared and dropped; the walk rescores.
+// Split: one workgroup of T threads per SEED_QT = 16 queries (one MFMA column block), grid ceil(Q / 16). The seed
+// table is cut into blocks of 16 seeds, dealt to the four waves: wave w takes blocks w, w + 4, ... and runs them
+// without a barrier; the waves meet once, before the merge.
+//   * B operand: the tile's queries are rounded to bf16 once and staged as qb[16][pitch]; pitch is an ODD number of
+//     16-byte chunks ((D / 8) | 1), so the 16 lanes that read one k-chunk of the 16 queries land on 16 different
+//     chunks modulo 16 -- all 64 banks, no conflict. Lane (lr, lh) reads query lr, columns 32 ks + 8 lh .. + 7, with one
+//     16-byte LDS load per k-step. A query from Q on is staged as zeros and never selected or written.
+//   * A operand, by gather: lane (lr, lh) reads row seeds[16 blk + lr], the same columns, with plain 16-byte loads (the
+//     fragment map of search_mscan_kernel / search_assign_kernel). SEED_KG k-steps form a load group; the group after
+//     the one being multiplied is always in flight, across the block boundary too, and the ids of block blk + 4 are read
+//     before block blk's last group is multiplied. An invalid or absent seed loads zeros and its column is dropped.
+//   * running top-E per (wave, query): E keys best first, SEED_STG staging slots, a threshold (the E-th best key, 0
+//     until E are held) and two counters, all in LDS. After a block lane (lr, lh) holds score(seed 16 blk + 4 lh + e,
+//     query lr) in acc[e]; a valid key above the threshold takes a staging slot from an LDS atomic counter. When a
+//     query's staging could overflow on the next block (count > SEED_STG - 16) the wave folds all its queries: every key
+//     of list and staging is ranked by counting the keys above it (the beam update of search_graph_kernel), ranks below
+//     E are written back, the E-th becomes the threshold. Which slot a key is staged in depends on lane order; the set
+//     kept does not -- the keys are distinct (they hold the position j).
+//   * merge: one barrier; wave w takes queries w, w + 4, ...: the four lists of a query (at most 4 E = 256 keys, four
+//     a lane) are ranked by counting and rank r < E writes out[q][r] = seeds[j]; the slots from the number of valid
+//     keys on get -1.
+// Addresses: queries[(q0 + qi)*D + 8c ..] under qi < nq and c < D / 8; seeds[j] under j < S; corpus[id*ldc + 32 ks + 8 lh ..]
+// under (unsigned)id < N and 32 ks + 8 lh < D; qb under the same column bound (pitch >= D); list / staging slots under
+// rank < E and slot < SEED_STG; out[(q0 + qi)*estride + r] under qi < nq, r < E <= estride. Offsets are long.
+// LDS (dynamic; D = 2048, E = 64): queries 16 x 2056 x 2 = 64.25 KiB, keys 64 x (E + 64) x 8 = 64 KiB, thresholds 0.5 KiB,
+// counters 0.5 KiB: 129.25 KiB of 160. At D = 768, E = 16: 24.25 + 40 + 1 = 65.25 KiB.
+constexpr int SEED_QT = 16, SEED_STG = 64, SEED_KG = 8, SEED_SLOTS = 4 * SEED_QT;
+static_assert(T == 256 && SEED_SLOTS == 64 && HZ_GRAPH_SEED_MAX_E <= 64 && SEED_STG <= 64 && SEED_STG >= 32,
+              "a lane per (wave, query) slot; a lane per list key and per staging key; a block adds at most 16 keys a query");
+
+__host__ __device__ inline int seed_pitch(int D) { return ((D >> 3) | 1) * 8; }  // bf16 per staged query
+inline size_t seed_lds_bytes(int D, int E) {
+  return (size_t)SEED_QT * seed_pitch(D) * 2 + (size_t)SEED_SLOTS * (E + SEED_STG) * 8 + SEED_SLOTS * 8 + 2 * SEED_SLOTS * 4;
+}
+
+// orders one wave's LDS accesses across its lanes (the wave runs in lockstep: no s_barrier)
+__device__ __forceinline__ void seed_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// wave w folds the staging buffers of its 16 queries into their lists (the comment above). Lane l holds list key l and
+// staging key l; every lane reads the same word in the counting loops: LDS broadcasts.
+__device__ __forceinline__ void seed_fold(unsigned long long* keys, unsigned long long* thr, int* cnt, int* len, int w, int lane, int E) {
+  for (int qi = 0; qi < SEED_QT; ++qi) {
+    const int slot = w * SEED_QT + qi;
+    const int ns = min(__builtin_amdgcn_readfirstlane(cnt[slot]), SEED_STG);
+    if (ns == 0) continue;  // wave-uniform
+    const int nl = min(__builtin_amdgcn_readfirstlane(len[slot]), E);
+    unsigned long long* L = keys + (long)slot * (E + SEED_STG);
+    const unsigned long long* G = L + E;
+    const unsigned long long k0 = lane < nl ? L[lane] : 0ull, k1 = lane < ns ? G[lane] : 0ull;
+    int r0 = 0, r1 = 0;
+    for (int j = 0; j < nl; ++j) {
+      const unsigned long long kj = L[j];
+      r0 += kj > k0, r1 += kj > k1;
+    }
+    for (int j = 0; j < ns; ++j) {
+      const unsigned long long kj = G[j];
+      r0 += kj > k0, r1 += kj > k1;
+    }
+    seed_wave_sync();  // every lane has read the list before any lane writes it
+    if (k0 != 0ull && r0 < E) L[r0] = k0;
+    if (k1 != 0ull && r1 < E) L[r1] = k1;
+    if (k0 != 0ull && r0 == E - 1) thr[slot] = k0;
+    if (k1 != 0ull && r1 == E - 1) thr[slot] = k1;
+    if (lane == 0) len[slot] = min(E, nl + ns), cnt[slot] = 0;
+    seed_wave_sync();
+  }
+}
+
+HZ_NO_PK_F32 __global__ __launch_bounds__(T) void graph_seed_kernel(const HzGraphSeedParams a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char seed_lds[];
+  const int t = threadIdx.x, lane = t & 63, lr = lane & 15, lh = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int E = a.E, S = a.S, D = a.D;
+  const int q0 = blockIdx.x * SEED_QT;
+  if (!HZ_DCHECK(q0 < a.Q && D >= 8 && D % 8 == 0 && D <= 2048 && a.ldc >= D && a.N >= 1 && S >= 1 && S <= HZ_GRAPH_SEED_MAX &&
+                 E >= 1 && E <= HZ_GRAPH_SEED_MAX_E && a.estride >= E))
+    return;
+  const int pitch = seed_pitch(D), nch = D >> 3, nq = min(SEED_QT, a.Q - q0);
+  bf16_t* qb = reinterpret_cast<bf16_t*>(seed_lds);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(qb + SEED_QT * pitch);  // [slot][E list, SEED_STG staging]
+  unsigned long long* thr = keys + (long)SEED_SLOTS * (E + SEED_STG);
+  int* cnt = reinterpret_cast<int*>(thr + SEED_SLOTS);
+  int* len = cnt + SEED_SLOTS;
+  for (int i = t; i < SEED_QT * nch; i += T) {
+    const int qi = i / nch, c = i - qi * nch;
+    u32x4 v = u32x4{0u, 0u, 0u, 0u};
+    if (qi < nq && HZ_DCHECK(q0 + qi < a.Q)) {
+      const f32x4* src = reinterpret_cast<const f32x4*>(a.queries + (long)(q0 + qi) * D + c * 8);
+      const f32x4 lo = src[0], hi = src[1];
+      const float f[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      v = pack8(f);  // round to nearest even: to_bf16's rounding
+    }
+    *reinterpret_cast<u32x4*>(qb + qi * pitch + c * 8) = v;
+  }
+  if (t < SEED_SLOTS) thr[t] = 0ull, cnt[t] = 0, len[t] = 0;
+  pqx_sync();
+
+  const int nk = (D + 31) >> 5, ng = (nk + SEED_KG - 1) / SEED_KG, nblk = (S + 15) >> 4;
+  const bf16x8 zero = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+  const auto seed_id = [&](int blk) __attribute__((always_inline)) {  // this lane's row of block blk; -1: none
+    int id = -1;
+    if (blk < nblk && blk * 16 + lr < S) id = a.seeds[blk * 16 + lr];
+    return id;
+  };
+  const auto load = [&](bf16x8(&v)[SEED_KG], int id, int kg) __attribute__((always_inline)) {
+    const bool ok = (unsigned)id < (unsigned)a.N;
+    const bf16_t* row = a.corpus + (long)(ok ? id : 0) * a.ldc + lh * 8;
+#pragma unroll
+    for (int s = 0; s < SEED_KG; ++s) {
+      const int ks = kg * SEED_KG + s;
+      v[s] = zero;
+      if (ok && ks * 32 + lh * 8 < D && HZ_DCHECK((unsigned)id < (unsigned)a.N)) v[s] = *reinterpret_cast<const bf16x8*>(row + ks * 32);
+    }
+  };
+  const bf16_t* brow = qb + lr * pitch + lh * 8;
+  const int slot = w * SEED_QT + lr;
+  unsigned long long* stg = keys + (long)slot * (E + SEED_STG) + E;
+
+  int blk = w;  // wave-uniform
+  if (blk < nblk) {
+    int id_cur = seed_id(blk), id_nxt = seed_id(blk + 4);
+    bf16x8 cur[SEED_KG], nxt[SEED_KG];
+    load(cur, id_cur, 0);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    int kg = 0;
+    while (true) {
+      const bool last = kg + 1 == ng;  // of the block's groups
+      const int nb = last ? blk + 4 : blk, nkg = last ? 0 : kg + 1;
+      const bool more = nb < nblk;
+      if (more) load(nxt, last ? id_nxt : id_cur, nkg);
+#pragma unroll
+      for (int s = 0; s < SEED_KG; ++s) {
+        const int ks = kg * SEED_KG + s;
+        if (ks < nk) {
+          bf16x8 b = zero;
+          if (ks * 32 + lh * 8 < D) b = *reinterpret_cast<const bf16x8*>(brow + ks * 32);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cur[s], b, acc, 0, 0, 0);
+        }
+      }
+      if (last) {  // acc[e] = score(seed position 16 blk + 4 lh + e, query lr)
+        const unsigned vmask = (unsigned)__ballot((unsigned)id_cur < (unsigned)a.N) & 0xffffu;  // lanes 0..15: rows 0..15
+        const unsigned long long th = thr[slot];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = lh * 4 + e;
+          const unsigned long long key = ((unsigned long long)orderable(acc[e]) << 32) | (unsigned)~(unsigned)(blk * 16 + r);
+          if (lr < nq && ((vmask >> r) & 1u) && key > th) {
+            const int at = __hip_atomic_fetch_add(&cnt[slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (HZ_DCHECK(at < SEED_STG) && at < SEED_STG) stg[at] = key;
+          }
+        }
+        seed_wave_sync();
+        const bool full = lane < SEED_QT && cnt[w * SEED_QT + lane] > SEED_STG - 16;
+        if (__ballot(full) != 0ull) seed_fold(keys, thr, cnt, len, w, lane, E);
+        acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        id_cur = id_nxt, id_nxt = seed_id(nb + 4);
+      }
+      if (!more) break;
+#pragma unroll
+      for (int s = 0; s < SEED_KG; ++s) cur[s] = nxt[s];
+      blk = nb, kg = nkg;
+    }
+    seed_fold(keys, thr, cnt, len, w, lane, E);
+  }
+  pqx_sync();
+
+  for (int qi = w; qi < nq; qi += 4) {  // wave-uniform
+    unsigned long long mine[4];
+    int rank[4] = {0, 0, 0, 0}, total = 0;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const int n = min(__builtin_amdgcn_readfirstlane(len[x * SEED_QT + qi]), E);
+      mine[x] = lane < n ? keys[(long)(x * SEED_QT + qi) * (E + SEED_STG) + lane] : 0ull;
+      total += n;
+    }
+    for (int x = 0; x < 4; ++x) {
+      const int n = min(__builtin_amdgcn_readfirstlane(len[x * SEED_QT + qi]), E);
+      const unsigned long long* L = keys + (long)(x * SEED_QT + qi) * (E + SEED_STG);
+      for (int j = 0; j < n; ++j) {
+        const unsigned long long kj = L[j];
+#pragma unroll
+        for (int y = 0; y < 4; ++y) rank[y] += kj > mine[y];
+      }
+    }
+    int* out = a.out + (long)(q0 + qi) * a.estride;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      const unsigned j = ~(unsigned)mine[x];
+      if (mine[x] != 0ull && rank[x] < E && HZ_DCHECK(j < (unsigned)S) && j < (unsigned)S) out[rank[x]] = a.seeds[j];
+    }
+    if (lane < E && lane >= min(E, total)) out[lane] = -1;
   }
 }
 
@@ -2940,6 +3141,12 @@ void graph_dispatch(const HzSearchGraphParams& a, bool large, hipStream_t st) {
                        HZ_SEARCH_GRAPH_CAP_SMALL * 4, st, a);
 }
 
+// the seed kernel's dynamic LDS reaches 129.25 KiB (D = 2048, E = 64): raised once per device to that, outside any capture
+bool seed_raised[64];
+int raise_seed_lds_limit() {
+  return once_per_device(seed_raised, [] { return raise_lds_limit_of(&graph_seed_kernel, seed_lds_bytes(2048, HZ_GRAPH_SEED_MAX_E)); });
+}
+
 }  // namespace
 
 // The graph search's refusals (hipzap.h), one code per rule; then the smallest table whose half holds the visited bound.
@@ -2962,6 +3169,7 @@ extern "C" int hz_search_graph_launch(const HzSearchGraphParams* pp, hipStream_t
       (reinterpret_cast<uintptr_t>(a.out_score) & 3) || (reinterpret_cast<uintptr_t>(a.out_id) & 3) ||
       (reinterpret_cast<uintptr_t>(a.out_stats) & 3))
     return -229;
+  if (a.estride < 0 || (a.estride > 0 && a.estride < a.E)) return -251;
   const bool large = bound > HZ_SEARCH_GRAPH_CAP_SMALL / 2;
   if (large)
     if (const int rc = once_per_device(graph_raised, [] { return raise_graph_lds_limit(); })) return rc;
@@ -2978,6 +3186,24 @@ extern "C" int hz_graph_prune_launch(const HzGraphPruneParams* pp, hipStream_t s
   if ((reinterpret_cast<uintptr_t>(a.knn) & 3) || (reinterpret_cast<uintptr_t>(a.order) & 3) || (reinterpret_cast<uintptr_t>(a.detours) & 3))
     return -241;
   hipLaunchKernelGGL(graph_prune_kernel, dim3((unsigned)((a.N + PRUNE_WAVES - 1) / PRUNE_WAVES)), dim3(PRUNE_WAVES * 64), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// The seed kernel's refusals (hipzap.h), one code per rule; then one workgroup per 16 queries, the LDS sized to (D, E).
+extern "C" int hz_graph_seed_launch(const HzGraphSeedParams* pp, hipStream_t st) {
+  const HzGraphSeedParams a = *pp;
+  if (a.D < 8 || a.D % 8 || a.D > 2048 || a.ldc < a.D || a.ldc % 8) return -243;
+  if (a.N < 1) return -244;
+  if (a.Q < 1 || a.Q > HZ_SEARCH_SELF_MAX_Q) return -245;
+  if (a.S < 1 || a.S > HZ_GRAPH_SEED_MAX) return -246;
+  if (a.E < 1 || a.E > HZ_GRAPH_SEED_MAX_E) return -247;
+  if (a.estride < a.E) return -248;
+  if (!a.corpus || !a.queries || !a.seeds || !a.out) return -249;
+  if ((reinterpret_cast<uintptr_t>(a.corpus) & 15) || (reinterpret_cast<uintptr_t>(a.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.seeds) & 3) || (reinterpret_cast<uintptr_t>(a.out) & 3))
+    return -250;
+  if (const int rc = raise_seed_lds_limit()) return rc;
+  hipLaunchKernelGGL(graph_seed_kernel, dim3((unsigned)((a.Q + SEED_QT - 1) / SEED_QT)), dim3(T), seed_lds_bytes(a.D, a.E), st, a);
   return (int)hipGetLastError();
 }
 
@@ -3186,5 +3412,6 @@ extern "C" int hz_search_code_warm(void) {
   if (const int rc = once_per_device(pqxscan_raised, [] { return raise_lds_limit_of(&search_pqxscan_kernel, XSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(lxscan_raised, [] { return raise_lds_limit_of(&search_lxscan_kernel, LXSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(graph_raised, [] { return raise_graph_lds_limit(); })) return rc;
+  if (const int rc = raise_seed_lds_limit()) return rc;
   return pq_device_setup(nullptr);
 }

@@ -31,6 +31,8 @@ its candidates with ``HZ_K_SEARCH_QSCAN``'s bits.
 same MFMA, ``HZ_K_SEARCH_CMEAN`` (``CmeanParams``) the means of the clusters ``order`` / ``seg_off`` describe.
 ``HZ_K_SEARCH_GRAPH`` (``GraphParams``) is the beam search over a fixed-degree neighbour graph of the corpus, one workgroup
 per query and the whole walk in one launch; its scores are ``HZ_K_SEARCH_SCAN``'s bits.
+``HZ_K_GRAPH_SEED`` (``GraphSeedParams``) scores a query batch against a table of seed rows with the bf16 MFMA and writes
+each query's best ``E`` seed ids: the entry rows the walk reads per query (``GraphParams.estride``).
 ``HZ_K_GRAPH_PRUNE`` (``GraphPruneParams``) reorders kNN lists by their detour counts, one wave per row, integers only
 (:func:`hipzap.search.graph_prune_ref` is its result in numpy); ``graph_prune_lists`` is the job over host lists
 (``hz_graph_prune``).
@@ -63,6 +65,7 @@ PQ_UPDATE_CG, PQ_UPDATE_TILE, PQ_UPDATE_BATCH = 16, 256, 384
 # HZ_SEARCH_GRAPH_MAX_BEAM, _CAP_SMALL, _CAP_LARGE: the graph search's beam limit and its two visited tables (slots)
 GRAPH_MAX_BEAM, GRAPH_CAP_SMALL, GRAPH_CAP_LARGE = 256, 4096, 16384
 GRAPH_THREADS = 256              # one thread per entry and per neighbour slot: E <= 256, width * deg <= 256
+GRAPH_SEED_MAX, GRAPH_SEED_MAX_E = 8192, 64  # HZ_GRAPH_SEED_MAX, HZ_GRAPH_SEED_MAX_E: seed ids a table holds, entries per query
 
 
 @N.params_of("HZ_K_SEARCH_MERGE")
@@ -284,11 +287,20 @@ class RescorePosParams(C.Structure):
 class GraphParams(C.Structure):
     """HzSearchGraphParams: ``corpus`` bf16 [N][ldc], ``queries`` device fp32 [Q][D], ``graph`` device int32 [N][deg]
     (an entry outside [0, N) is padding), ``entries`` device int32 [E], the outputs [Q][k] and ``out_stats`` (int32
-    [Q][2]: iterations, rows scored; or null)."""
+    [Q][2]: iterations, rows scored; or null). ``estride`` > 0: ``entries`` is [Q][estride], a row per query."""
     _fields_ = [("corpus", C.c_void_p), ("queries", C.c_void_p), ("graph", C.c_void_p), ("entries", C.c_void_p),
                 ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("out_stats", C.c_void_p), ("N", C.c_int),
                 ("D", C.c_int), ("Q", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("beam", C.c_int), ("deg", C.c_int),
-                ("width", C.c_int), ("iters", C.c_int), ("E", C.c_int)]
+                ("width", C.c_int), ("iters", C.c_int), ("E", C.c_int), ("estride", C.c_int), ("pad_", C.c_int)]
+
+
+@N.params_of("HZ_K_GRAPH_SEED")
+class GraphSeedParams(C.Structure):
+    """HzGraphSeedParams: ``corpus`` bf16 [N][ldc], ``queries`` device fp32 [Q][D], ``seeds`` device int32 [S], ``out``
+    device int32 [Q][estride]: each query's best ``E`` seed ids, best first, then -1."""
+    _fields_ = [("corpus", C.c_void_p), ("queries", C.c_void_p), ("seeds", C.c_void_p), ("out", C.c_void_p),
+                ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("S", C.c_int), ("E", C.c_int), ("ldc", C.c_int),
+                ("estride", C.c_int), ("pad_", C.c_int)]
 
 
 @N.params_of("HZ_K_GRAPH_PRUNE")
@@ -341,6 +353,9 @@ def _sigs(lib):
     N._sig(lib, "hz_graph_prune", C.c_int, C.c_int, P, C.c_longlong, C.c_int, P, P)
     N._sig(lib, "hz_index_set_graph", C.c_int, P, P, C.c_longlong, C.c_int, P, C.c_int)
     N._sig(lib, "hz_index_search_graph", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P)
+    N._sig(lib, "hz_graph_seed_launch", C.c_int, C.POINTER(GraphSeedParams), P)
+    N._sig(lib, "hz_index_set_graph_seeds", C.c_int, P, P, C.c_int)
+    N._sig(lib, "hz_index_search_graph2", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_probes_batch", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_search_batch_ivf", C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P, P)
     N._sig(lib, "hz_index_search_batch_ivf_invert_us", C.c_double, P, C.c_int)
@@ -641,6 +656,11 @@ def graph_max_iters(entries: int, width: int, deg: int) -> int:
 def launch_graph(prm: GraphParams, stream: int = 0) -> int:
     """The graph search (``HZ_K_SEARCH_GRAPH``) on ``stream`` -> its code (0, or negative: nothing ran)."""
     return int(N.lib().hz_search_graph_launch(C.byref(prm), stream))
+
+
+def launch_graph_seed(prm: GraphSeedParams, stream: int = 0) -> int:
+    """The seed kernel (``HZ_K_GRAPH_SEED``) on ``stream`` -> its code (0, or negative: nothing ran)."""
+    return int(N.lib().hz_graph_seed_launch(C.byref(prm), stream))
 
 
 def launch_graph_prune(prm: GraphPruneParams, stream: int = 0) -> int:

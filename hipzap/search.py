@@ -66,7 +66,7 @@ import threading
 
 import numpy as np
 
-from .ops.search import GRAPH_CAP_LARGE, GRAPH_MAX_BEAM, MAX_K, MAX_Q
+from .ops.search import GRAPH_CAP_LARGE, GRAPH_MAX_BEAM, GRAPH_SEED_MAX, GRAPH_SEED_MAX_E, MAX_K, MAX_Q
 
 MAGIC = b"HZIDX\0\0\1"
 VERSION = 1
@@ -81,7 +81,9 @@ VERSION9 = 9  # version 8 plus rescore / rescore_off, as version 4 adds them to 
 VERSION10 = 10  # pq8 rows: uint8 [count][M], the JSON block pq and the codebook block; tags / live as in version 3, or absent
 VERSION11 = 11  # version 10 plus rescore / rescore_off, as version 4 adds them to version 3
 VERSION12 = 12  # version 1 plus graph_deg / graph_off / entries / entries_off: a neighbour graph and its entry rows
+VERSION13 = 13  # version 12 plus seeds / seeds_off: the graph's seed table, one more int32 block after the entries
 GRAPH_KEYS = ("graph_deg", "graph_off", "entries", "entries_off")
+SEED_KEYS = ("seeds", "seeds_off")
 FP8_VERSIONS, IVF_VERSIONS, RESCORE_VERSIONS = (VERSION3, VERSION4, VERSION6, VERSION7), (VERSION5, VERSION6, VERSION7), \
     (VERSION4, VERSION7, VERSION9, VERSION11)
 BIN_VERSIONS = (VERSION8, VERSION9)
@@ -620,7 +622,8 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
     With ``pq`` (the codebook fp32 [M, 256, dim / M]; ``rows`` uint8 codes [N, M]) version 10, with ``rescore`` as
     well version 11: the codebook's block follows the rows, where version 3 has its scales.
     With ``graph`` ((int32 [N, deg], int32 [E]): :func:`check_graph`'s pair; plain bf16 rows without tags) version 12:
-    version 1 plus the graph's and the entries' blocks after the rows.
+    version 1 plus the graph's and the entries' blocks after the rows. A third member (int32 [S], :func:`check_seeds`'
+    seed table) makes it version 13: its block follows the entries.
     Atomic: a temporary file, then a rename. Returns the JSON header written."""
     n = rows.shape[0]
     if graph is not None and (tags is not None or live is not None or scales is not None or ivf is not None or pq is not None
@@ -647,17 +650,23 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
         raise ValueError("an IVF index holds rows, tags and a live bitmap for whole tiles")
     blocks = tags is not None or live is not None
     tables = ()  # the four blocks of an IVF index
+    seeds = graph[2] if graph is not None and len(graph) > 2 else None
     if graph is not None:
-        version = VERSION12
+        version = VERSION12 if seeds is None else VERSION13
         hdr = dict(hdr, graph_deg=int(graph[0].shape[1]), graph_off=0, entries=int(graph[1].size), entries_off=0)
+        if seeds is not None:
+            hdr.update(seeds=int(seeds.size), seeds_off=0)
         while True:  # the offsets follow the JSON's own length
             js = json.dumps(hdr).encode()
             data_off = align(HEAD.size + len(js))
             goff = align(data_off + rows.nbytes)
             eoff = align(goff + graph[0].nbytes)
-            if (hdr["graph_off"], hdr["entries_off"]) == (goff, eoff):
+            offs = dict(graph_off=goff, entries_off=eoff)
+            if seeds is not None:
+                offs["seeds_off"] = align(eoff + graph[1].nbytes)
+            if all(hdr[k] == v for k, v in offs.items()):
                 break
-            hdr.update(graph_off=goff, entries_off=eoff)
+            hdr.update(offs)
     elif not blocks and scales is None and not binary and pq is None:
         version, js = VERSION, json.dumps(hdr).encode()
         data_off = align(HEAD.size + len(js))
@@ -749,6 +758,9 @@ def _write_file(path: str, hdr: dict, rows: np.ndarray, tags=None, live=None, ca
             f.write(graph[0].astype("<i4").tobytes())
             f.write(bytes(hdr["entries_off"] - hdr["graph_off"] - graph[0].nbytes))
             f.write(graph[1].astype("<i4").tobytes())
+            if seeds is not None:
+                f.write(bytes(hdr["seeds_off"] - hdr["entries_off"] - graph[1].nbytes))
+                f.write(seeds.astype("<i4").tobytes())
     os.replace(tmp, path)
     return hdr
 
@@ -824,7 +836,7 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
                 dtype: str = "bf16", rescore: bool = False, ivf=None, nprobe=None, ivf_seed: int = 0,
                 ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None, pq_codebook=None,
                 pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host", ivf_init=None, graph=None,
-                graph_backend: str = "cpu", graph_prune: bool = False) -> dict:
+                graph_backend: str = "cpu", graph_prune: bool = False, graph_seeds=None) -> dict:
     """Write ``vectors`` (fp32 [N, D]) as a ``.hzidx`` file and return its JSON header. ``cosine`` rows are
     divided by max(||v||, 1e-12) in fp32 and then rounded to bf16; ``ip`` rows are only rounded. Without
     ``tags`` the file is version 1; with them (uint32 [N]) version 2. ``dtype="fp8"``: e4m3fn rows with one
@@ -846,9 +858,11 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     :func:`graph_build` over the kNN lists of the stored rows, from ``RefIndex`` (``graph_backend="cpu"``) or from
     :meth:`Index.knn_graph` on ``device`` (``"gpu"``) -- and :func:`graph_entries`' entry rows. ``graph_prune=True``:
     the lists are taken at twice the width and reordered by :func:`graph_prune` on that backend first (the file
-    format is the same: a pruned graph is a graph)."""
+    format is the same: a pruned graph is a graph). ``graph_seeds=S`` (with ``graph``): a version-13 file, which also
+    holds :func:`graph_seeds`' table of ``min(N, S)`` seed rows for ``search_graph(seeds=E)``."""
     _check_ivf_backend(ivf_backend, ivf)
-    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and tags is None and not rescore, graph_prune)
+    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and tags is None and not rescore, graph_prune,
+                      graph_seeds)
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")
@@ -906,11 +920,16 @@ def write_index(path: str, vectors, metric: str = "cosine", labels=None, model: 
     if ivf_init is not None:
         raise ValueError("ivf_init goes with ivf=nlist")
     if graph is not None:
-        return _write_file(path, hdr, rows, graph=_graph_of(hdr, rows, graph, graph_backend, device, path, graph_prune))
+        return _write_file(path, hdr, rows, graph=_graph_of(hdr, rows, graph, graph_backend, device, path, graph_prune,
+                                                            graph_seeds))
     return _write_file(path, hdr, rows, tags, scales=scales, rescore=rrows, pq=codebook)
 
 
-def _check_graph_args(graph, graph_backend, plain: bool, graph_prune: bool = False):
+def _check_graph_args(graph, graph_backend, plain: bool, graph_prune: bool = False, graph_seeds=None):
+    if graph_seeds is not None and graph is None:
+        raise ValueError("graph_seeds goes with graph=DEG")
+    if graph_seeds is not None and (not _is_int(graph_seeds) or not 1 <= graph_seeds <= GRAPH_SEED_MAX):
+        raise ValueError(f"graph_seeds must be a table size in 1..{GRAPH_SEED_MAX}, got {graph_seeds!r}")
     if graph_backend not in IVF_BACKENDS:
         raise ValueError(f"graph_backend must be one of {IVF_BACKENDS}, got {graph_backend!r}")
     if graph is None and graph_backend != "cpu":
@@ -923,9 +942,10 @@ def _check_graph_args(graph, graph_backend, plain: bool, graph_prune: bool = Fal
         raise ValueError(f"graph={graph!r} goes with a plain bf16 index: no tags, lists, rescore rows or other dtype")
 
 
-def _graph_of(hdr: dict, bits, deg: int, backend: str, device: int, near: str, prune: bool = False):
+def _graph_of(hdr: dict, bits, deg: int, backend: str, device: int, near: str, prune: bool = False, nseeds=None):
     """The stored graph of degree ``deg`` over the bf16 rows ``bits`` and its entry rows: the kNN lists (``prune``: the
-    pruned lists of twice the width) come from a temporary plain index beside ``near``, opened on the chosen backend."""
+    pruned lists of twice the width) come from a temporary plain index beside ``near``, opened on the chosen backend.
+    ``nseeds``: :func:`graph_seeds`' table of that size as a third member."""
     tmp = near + ".graph-knn.tmp"
     try:
         _write_file(tmp, {k: hdr[k] for k in ("dim", "count", "dtype", "metric")}, bits)
@@ -934,7 +954,8 @@ def _graph_of(hdr: dict, bits, deg: int, backend: str, device: int, near: str, p
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
-    return check_graph(graph_build(knn, deg), hdr["count"])
+    pair = check_graph(graph_build(knn, deg), hdr["count"])
+    return pair if nseeds is None else pair + (graph_seeds(hdr["count"], nseeds),)
 
 
 IVF_BACKENDS = ("cpu", "gpu")
@@ -1003,7 +1024,7 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path} is not a .hzidx file")
         _, version, json_len, data_off, count, dim, metric = HEAD.unpack(raw)
         if version not in (VERSION, VERSION2, VERSION3, VERSION4, VERSION5, VERSION6, VERSION7, VERSION8, VERSION9,
-                           VERSION10, VERSION11, VERSION12):
+                           VERSION10, VERSION11, VERSION12, VERSION13):
             raise ValueError(f"{path}: unknown .hzidx version {version}")
         hdr = json.loads(f.read(json_len))
         size = os.fstat(f.fileno()).st_size
@@ -1116,11 +1137,11 @@ def read_header(path: str) -> dict:
             raise ValueError(f"{path}: the rescore block at {off} overlaps another block, which ends at {last}")
         if off + 2 * count * dim > size:
             raise ValueError(f"{path}: the rescore block lies outside the file")
-    if version == VERSION12:  # version 1's rows, then the graph's and the entries' blocks
+    if version in (VERSION12, VERSION13):  # version 1's rows, then the graph's and the entries' blocks (13: and the seeds')
         if hdr["dtype"] != "bf16" or "tags_off" in hdr or "live_off" in hdr:
-            raise ValueError(f"{path}: a version-12 file holds plain bf16 rows without tags")
+            raise ValueError(f"{path}: a version-{version} file holds plain bf16 rows without tags")
         if not all(_is_int(hdr.get(k)) for k in GRAPH_KEYS):
-            raise ValueError(f"{path}: a version-12 file without integers {', '.join(GRAPH_KEYS)}")
+            raise ValueError(f"{path}: a version-{version} file without integers {', '.join(GRAPH_KEYS)}")
         deg, ne = hdr["graph_deg"], hdr["entries"]
         if not 8 <= deg <= 64 or deg % 8 or not 1 <= ne <= 256:
             raise ValueError(f"{path}: graph_deg {deg} must be a multiple of 8 in 8..64 and entries {ne} in 1..256")
@@ -1130,8 +1151,23 @@ def read_header(path: str) -> dict:
                 raise ValueError(f"{path}: the block at {key} = {off} is unaligned, overlaps another block or lies outside "
                                  f"the file")
             last = off + nbytes
-    elif any(k in hdr for k in GRAPH_KEYS):
-        raise ValueError(f"{path}: graph keys in a version-{version} file (they belong to version 12)")
+        if version == VERSION13:
+            if not all(_is_int(hdr.get(k)) for k in SEED_KEYS):
+                raise ValueError(f"{path}: a version-13 file without integers {', '.join(SEED_KEYS)}")
+            ns, off = hdr["seeds"], hdr["seeds_off"]
+            if not 1 <= ns <= GRAPH_SEED_MAX:
+                raise ValueError(f"{path}: seeds {ns} must be in 1..{GRAPH_SEED_MAX}")
+            if off % ALIGN or off < last or off + 4 * ns > size:
+                raise ValueError(f"{path}: the block at seeds_off = {off} is unaligned, overlaps another block or lies "
+                                 f"outside the file")
+            try:
+                check_seeds(np.fromfile(path, "<i4", ns, offset=off), count)
+            except ValueError as e:
+                raise ValueError(f"{path}: {e}") from None
+        elif any(k in hdr for k in SEED_KEYS):
+            raise ValueError(f"{path}: seed keys in a version-12 file (they belong to version 13)")
+    elif any(k in hdr for k in GRAPH_KEYS + SEED_KEYS):
+        raise ValueError(f"{path}: graph keys in a version-{version} file (they belong to versions 12 and 13)")
     return dict(hdr, data_off=int(data_off))
 
 
@@ -1143,6 +1179,14 @@ def read_graph(path: str):
     n, deg = hdr["count"], hdr["graph_deg"]
     return (np.fromfile(path, "<i4", n * deg, offset=hdr["graph_off"]).astype(np.int32).reshape(n, deg),
             np.fromfile(path, "<i4", hdr["entries"], offset=hdr["entries_off"]).astype(np.int32))
+
+
+def read_seeds(path: str) -> np.ndarray:
+    """The seed table of a version-13 file -> int32 [S]."""
+    hdr = read_header(path)
+    if "seeds_off" not in hdr:
+        raise ValueError(f"{path} holds no seed table (a version-13 file does: write_index(graph=DEG, graph_seeds=S))")
+    return np.fromfile(path, "<i4", hdr["seeds"], offset=hdr["seeds_off"]).astype(np.int32)
 
 
 def stored_rows(hdr: dict) -> int:
@@ -1176,6 +1220,8 @@ def file_info(path: str) -> dict:
             "live": int(read_live(path).sum()), "tags": v2}
     if "graph_off" in hdr:
         info.update(version=VERSION12, graph={k: hdr[k] for k in GRAPH_KEYS})
+    if "seeds_off" in hdr:
+        info.update(version=VERSION13, graph_seeds=hdr["seeds"])
     if "ivf" in hdr:
         info.update(version=VERSION5, ivf=ivf_facts(hdr, read_ivf(path)))
     if hdr["dtype"] == FP8:
@@ -1339,6 +1385,44 @@ def graph_entries(n: int) -> np.ndarray:
     """The entry rows of a graph over ``n`` rows: ``min(n, GRAPH_ENTRIES)`` ids evenly spaced over [0, n), int32."""
     e = min(int(n), GRAPH_ENTRIES)
     return (np.arange(e, dtype=np.int64) * int(n) // e).astype(np.int32)
+
+
+def graph_seeds(n: int, s: int) -> np.ndarray:
+    """The seed table of a graph over ``n`` rows: ``min(n, s)`` ids evenly spaced over [0, n), int32."""
+    if not _is_int(s) or not 1 <= s <= GRAPH_SEED_MAX:
+        raise ValueError(f"a seed table holds 1..{GRAPH_SEED_MAX} ids, got {s!r}")
+    s = min(int(n), int(s))
+    return (np.arange(s, dtype=np.int64) * int(n) // s).astype(np.int32)
+
+
+def check_seeds(seeds, n: int) -> np.ndarray:
+    """A seed table for ``n`` rows -> int32 [S] contiguous: 1..GRAPH_SEED_MAX distinct ids in [0, n) (e.g. cluster
+    medoids; :func:`graph_seeds` spaces them evenly)."""
+    s = np.asarray(seeds)
+    if s.ndim != 1 or s.dtype.kind not in "iu" or not 1 <= s.size <= GRAPH_SEED_MAX:
+        raise ValueError(f"seeds must be 1..{GRAPH_SEED_MAX} integers, got {s.dtype} {list(s.shape)}")
+    if (s < 0).any() or (s >= n).any():
+        raise ValueError(f"a seed id lies outside [0, {n})")
+    if np.unique(s).size != s.size:
+        raise ValueError("a seed id is held twice")
+    return np.ascontiguousarray(s, np.int32)
+
+
+def graph_seed_ref(corpus, q, seeds, E: int) -> np.ndarray:
+    """The oracle of the seed kernel (csrc/hipzap.h HZ_K_GRAPH_SEED, "THE RULE"): ``corpus`` (the bf16 rows widened,
+    [N, D]), fp32 queries [Q, D], seed ids [S] -> int32 [Q, E], each query's best ``E`` valid seeds, best first, then -1.
+    The query is rounded to bf16, the score is the fp64 dot with the row; the higher score wins, then the lower seed
+    POSITION. A seed outside [0, N) is invalid; a repeated id stays (it is another position)."""
+    c, seeds = np.asarray(corpus, np.float64), np.asarray(seeds).astype(np.int64)
+    qb = bf16_to_f32(to_bf16(np.asarray(q, np.float32))).astype(np.float64)
+    pos = np.flatnonzero((seeds >= 0) & (seeds < c.shape[0]))
+    out = np.full((qb.shape[0], E), -1, np.int32)
+    if pos.size:
+        score = qb @ c[seeds[pos]].T + 0.0  # [Q, valid]
+        for a in range(qb.shape[0]):
+            best = np.lexsort((pos, -score[a]))[:E]
+            out[a, :best.size] = seeds[pos[best]]
+    return out
 
 
 def graph_build(knn_ids, deg: int) -> np.ndarray:
@@ -1742,11 +1826,15 @@ class _Base:
             self.version = VERSION5 if self.dtype != FP8 else VERSION7 if self.rescore else VERSION6
         else:
             self.version = (VERSION4 if self.rescore else VERSION3 if self.dtype == FP8
-                            else VERSION2 if "tags_off" in self.header else VERSION12 if "graph_off" in self.header else VERSION)
+                            else VERSION2 if "tags_off" in self.header else VERSION13 if "seeds_off" in self.header
+                            else VERSION12 if "graph_off" in self.header else VERSION)
         self.nprobe = self.ivf["nprobe"] if self.ivf else None  # what search(nprobe=None) scans; settable
         self._mut = threading.Lock()  # one mutator at a time
         # the neighbour graph search_graph walks and its entry rows: a version-12 file's, or set_graph's
         self.graph, self.graph_entries = read_graph(path) if "graph_off" in self.header else (None, None)
+        # the graph's seed table, which search_graph(seeds=E) picks each query's entry rows from: a version-13 file's, or
+        # set_graph(seeds=)'s
+        self.graph_seed_table = read_seeds(path) if "seeds_off" in self.header else None
 
     def __enter__(self):
         return self
@@ -1981,23 +2069,28 @@ class _Base:
             raise ValueError(f"{what} is refused on an index with a graph ({self.path}, version {self.version}): it is read-only; "
                              f"write the vectors to a plain index to change them")
 
-    def set_graph(self, graph, entries=None) -> None:
+    def set_graph(self, graph, entries=None, seeds=None) -> None:
         """Attach the neighbour graph :meth:`search_graph` walks: int [count, deg], an entry outside
         [0, count) padding (:func:`graph_build` makes one from :meth:`knn_graph`), and its entry rows (None:
         :func:`graph_entries`). A plain bf16 index whose rows are all live. From then on the index is read-only, like one
-        opened from a version-12 file: ``add``, ``delete``, ``set_tags``, ``filter=`` and ``cluster`` refuse it by name."""
+        opened from a version-12 file: ``add``, ``delete``, ``set_tags``, ``filter=`` and ``cluster`` refuse it by name.
+        ``seeds``: the seed table ``search_graph(seeds=E)`` picks entry rows from -- a size S
+        (:func:`graph_seeds`) or an explicit array of distinct ids, e.g. cluster medoids; None: no table."""
         self._check_graph_index("set_graph")
         g, e = check_graph(graph, self.count, entries)
+        if seeds is not None:
+            seeds = graph_seeds(self.count, seeds) if _is_int(seeds) else check_seeds(seeds, self.count)
         with self._mut:
-            self._attach_graph(g, e)
-            self.graph, self.graph_entries = g, e
+            self._attach_graph(g, e, seeds)
+            self.graph, self.graph_entries, self.graph_seed_table = g, e, seeds
 
-    def build_graph(self, deg: int = 32, *, prune: bool = False) -> np.ndarray:
+    def build_graph(self, deg: int = 32, *, prune: bool = False, seeds=None) -> np.ndarray:
         """:meth:`knn_graph` at k = ``deg``, :func:`graph_build`, :meth:`set_graph` -> the graph. ``prune=True``: the
-        lists are taken at k = 2 ``deg`` and reordered by :func:`graph_prune` on this index's backend first."""
+        lists are taken at k = 2 ``deg`` and reordered by :func:`graph_prune` on this index's backend first. ``seeds``:
+        :meth:`set_graph`'s."""
         self._check_graph_index("build_graph")
         g = graph_build(self._graph_lists(deg, prune), deg)
-        self.set_graph(g)
+        self.set_graph(g, seeds=seeds)
         return g
 
     def _graph_lists(self, deg: int, prune: bool) -> np.ndarray:
@@ -2009,10 +2102,17 @@ class _Base:
             raise ValueError(f"deg must be a multiple of 8 in 8..64, got {deg!r}")
         return graph_prune(self.knn_graph(2 * deg)[0], self.backend, getattr(self, "device", 0))
 
-    def _check_graph_search(self, q, k, beam, width, iters):
+    def _check_graph_search(self, q, k, beam, width, iters, seeds=None):
         if self.graph is None:
             raise ValueError(f"search_graph needs a graph and {self.path} has none (set_graph, build_graph)")
-        k, beam, width, iters = check_graph_args(k, beam, width, iters, self.graph.shape[1], self.graph_entries.size)
+        if seeds is not None:
+            if not _is_int(seeds) or not 1 <= seeds <= GRAPH_SEED_MAX_E:
+                raise ValueError(f"seeds must be in 1..{GRAPH_SEED_MAX_E} entry rows per query, got {seeds!r}")
+            if self.graph_seed_table is None:
+                raise ValueError(f"search_graph(seeds=) needs a seed table and {self.path} has none (a version-13 file, "
+                                 f"set_graph(seeds=), build_graph(seeds=))")
+        k, beam, width, iters = check_graph_args(k, beam, width, iters, self.graph.shape[1],
+                                                 self.graph_entries.size if seeds is None else int(seeds))
         return check_queries(q, self.dim), k, beam, width, iters
 
     def knn_graph(self, k: int = 10, *, block: int = NEIGHBORS_BLOCK):
@@ -2124,7 +2224,8 @@ class _Base:
             plain = bool(live.all()) and not tags.any()
             return _write_file(path or self.path, hdr, np.ascontiguousarray(bits), None if plain else tags,
                                None if plain else live, self.capacity(), scales=scales, rescore=rrows, pq=self.codebook,
-                               graph=None if self.graph is None else (self.graph, self.graph_entries))  # version 12 again
+                               graph=None if self.graph is None else (self.graph, self.graph_entries) if self.graph_seed_table
+                               is None else (self.graph, self.graph_entries, self.graph_seed_table))  # version 12 or 13 again
 
 
 class RefIndex(_Base):
@@ -2187,15 +2288,22 @@ class RefIndex(_Base):
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
         return s.astype(np.float32), i
 
-    def _attach_graph(self, g, e):
+    def _attach_graph(self, g, e, seeds=None):
         if not self._live.all() or g.shape[0] != self._rows.shape[0]:
             raise ValueError(f"a graph covers every row of an index whose rows are all live, {self.path} has deleted rows")
 
-    def search_graph(self, q, k: int = 10, *, beam: int = 64, width: int = 1, iters=None, stats: bool = False, ctx=None):
-        """:meth:`Index.search_graph` on the host, its oracle: :func:`search_graph_ref`, the walk with fp64 scores."""
-        q, k, beam, width, iters = self._check_graph_search(q, k, beam, width, iters)
+    def search_graph(self, q, k: int = 10, *, beam: int = 64, width: int = 1, iters=None, stats: bool = False, ctx=None,
+                     seeds=None):
+        """:meth:`Index.search_graph` on the host, its oracle: :func:`search_graph_ref`, the walk with fp64 scores;
+        with ``seeds=E`` each query walks from its own row of :func:`graph_seed_ref`."""
+        q, k, beam, width, iters = self._check_graph_search(q, k, beam, width, iters, seeds)
         with self._mut:
-            s, i, st = search_graph_ref(self._rows, q, self.graph, self.graph_entries, k, beam, width, iters)
+            if seeds is None:
+                s, i, st = search_graph_ref(self._rows, q, self.graph, self.graph_entries, k, beam, width, iters)
+            else:
+                ent = graph_seed_ref(self._rows, q, self.graph_seed_table, seeds)
+                per = [search_graph_ref(self._rows, q[a:a + 1], self.graph, ent[a], k, beam, width, iters) for a in range(q.shape[0])]
+                s, i, st = (np.concatenate([p[x] for p in per]) for x in range(3))
         return (s.astype(np.float32), i, st) if stats else (s.astype(np.float32), i)
 
     def search_batch(self, q, k: int = 10, *, candidates=None, fallback: bool = True, ctx=None):
@@ -2427,6 +2535,7 @@ class RefIndex(_Base):
                 **({"m": int(self.codebook.shape[0]), "dsub": int(self.codebook.shape[2]),
                     "codebook_bytes": int(self.codebook.nbytes)} if self.dtype == PQ else {}),
                 **({"graph_deg": int(self.graph.shape[1])} if self.graph is not None else {}),
+                **({"graph_seeds": int(self.graph_seed_table.size)} if self.graph_seed_table is not None else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def close(self) -> None:
@@ -2537,20 +2646,25 @@ class Index(_Base):
             if ctx is None:
                 self._free.put(c)
 
-    def _attach_graph(self, g, e):
+    def _attach_graph(self, g, e, seeds=None):
         if self._h is None:
             raise RuntimeError("the index is closed")
         code = []  # a refusal is a ValueError with the library's text, not _exclusive's RuntimeError
-        self._exclusive(lambda: code.append(self._lib.hz_index_set_graph(self._h, g.ctypes.data, g.shape[0], g.shape[1],
-                                                                         e.ctypes.data, e.size)), "hz_index_set_graph")
+
+        def attach():
+            rc = self._lib.hz_index_set_graph(self._h, g.ctypes.data, g.shape[0], g.shape[1], e.ctypes.data, e.size)
+            if not rc and seeds is not None:
+                rc = self._lib.hz_index_set_graph_seeds(self._h, seeds.ctypes.data, seeds.size)
+            code.append(rc)
+        self._exclusive(attach, "hz_index_set_graph")
         rc = code[0]
-        if rc in (-230, -231, -232):
+        if rc in (-230, -231, -232, -252, -253, -254):
             raise ValueError((self._lib.hz_index_last_error() or b"").decode().replace("index: ", "", 1))
         if rc:
             raise RuntimeError(f"hz_index_set_graph failed with code {rc}")
 
     def search_graph(self, q, k: int = 10, *, beam: int = 64, width: int = 1, iters=None, stats: bool = False,
-                     ctx: int | None = None):
+                     ctx: int | None = None, seeds=None):
         """Approximate top-k by a beam search over the attached neighbour graph (:meth:`set_graph`,
         :meth:`build_graph`): fp32 queries [Q, dim] -> (scores float32 [Q, k], ids int32 [Q, k]), best first, -inf / -1
         past the rows a walk reached; with ``stats`` also int32 [Q, 2] = (iterations, rows scored). One workgroup per
@@ -2558,13 +2672,15 @@ class Index(_Base):
         rows (a multiple of 32 in 32..256, k <= beam), for at most ``iters`` iterations (``None``: as many as the visited
         table allows, at most 256). A query touches a few hundred rows, not all of them: nothing certifies the answer,
         recall is bought with ``beam``. Every score returned has the bits :meth:`search` gives that row, and the walk is
-        :meth:`RefIndex.search_graph`'s. Q above the per-call maximum is split here."""
-        q, k, beam, width, iters = self._check_graph_search(q, k, beam, width, iters)
+        :meth:`RefIndex.search_graph`'s. Q above the per-call maximum is split here. ``seeds=E`` (1..64; DESIGN.md
+        4ae): each query starts from ITS best E rows of the index's seed table, chosen by HZ_K_GRAPH_SEED in the same
+        replay, instead of the shared entry rows -- on clustered rows that is what lets a walk reach the query's cluster."""
+        q, k, beam, width, iters = self._check_graph_search(q, k, beam, width, iters, seeds)
         nq = q.shape[0]
         scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int32)
         st = np.empty((nq, 2), np.int32)
-        with self._in_parts("hz_index_search_graph", (-4, -5, -233, -234, -235, -236, -237), q, (k, beam, width, iters),
-                            (scores, ids, st), ctx):
+        with self._in_parts("hz_index_search_graph2", (-4, -5, -233, -234, -235, -236, -237, -255, -256), q,
+                            (k, beam, width, iters, 0 if seeds is None else int(seeds)), (scores, ids, st), ctx):
             pass
         return (scores, ids, st) if stats else (scores, ids)
 
@@ -2884,6 +3000,7 @@ class Index(_Base):
                    if self.dtype == PQ else {}),
                 **({"batch_fp8": self.ivf is None and self.dim % 32 == 0} if self.dtype == FP8 else {}),
                 **({"graph_deg": int(self._describe3()[6])} if self.graph is not None else {}),
+                **({"graph_seeds": int(self._describe3()[3])} if self.graph_seed_table is not None else {}),
                 **({"ivf": ivf_facts(self.header, self.ivf)} if self.ivf is not None else {})}
 
     def _describe3(self):
@@ -2914,7 +3031,7 @@ def open_index(path: str, backend: str = "gpu", device: int = 0, reserve: int = 
 def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False, ivf=None, nprobe=None,
                   ivf_seed: int = 0, ivf_iters: int = 10, ivf_backend: str = "cpu", device: int = 0, pq_m=None,
                   pq_codebook=None, pq_seed: int = 0, pq_iters: int = 10, pq_backend: str = "cpu", pq_means: str = "host",
-                  graph=None, graph_backend: str = "cpu", graph_prune: bool = False) -> dict:
+                  graph=None, graph_backend: str = "cpu", graph_prune: bool = False, graph_seeds=None) -> dict:
     """Write the bf16 index ``src`` as ``dst`` in ``dtype`` -> the JSON header written. The stored rows are
     widened to fp32 and requantised as they stand (NOT renormalised: they are what the index searches);
     labels, model, embed, tags, the live bitmap and the capacity are carried over, so ids stay valid.
@@ -2929,15 +3046,16 @@ def convert_index(src: str, dst: str, dtype: str = "fp8", rescore: bool = False,
     ``pq_seed`` / ``pq_iters``, unless ``pq_codebook`` is given) and encoded as they stand, which gives the bytes
     ``write_index(dtype="pq")`` stores for the same vectors and codebook: version 10, with ``rescore=True`` 11.
     ``pq_backend`` and ``pq_means`` as in :func:`write_index`. ``graph=DEG`` (``dtype="bf16"``, a plain version-1 ``src``): the
-    same rows plus their neighbour graph, a version-12 file (``graph_backend`` and ``graph_prune`` as in :func:`write_index`)."""
+    same rows plus their neighbour graph, a version-12 file (``graph_backend`` and ``graph_prune`` as in :func:`write_index`);
+    with ``graph_seeds=S`` a version-13 file, as there."""
     _check_ivf_backend(ivf_backend, ivf)
-    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and not rescore, graph_prune)
+    _check_graph_args(graph, graph_backend, dtype == "bf16" and ivf is None and not rescore, graph_prune, graph_seeds)
     if graph is not None:
         hdr = read_header(src)
         if hdr["dtype"] != "bf16" or any(k in hdr for k in ("ivf", "tags_off", "graph_off")):
             raise ValueError(f"graph={graph!r}: {src} is not a plain bf16 index of version 1")
         out, bits = {k: v for k, v in hdr.items() if k != "data_off"}, read_rows(src)
-        return _write_file(dst, out, bits, graph=_graph_of(out, bits, graph, graph_backend, device, dst, graph_prune))
+        return _write_file(dst, out, bits, graph=_graph_of(out, bits, graph, graph_backend, device, dst, graph_prune, graph_seeds))
     if dtype not in DTYPES:
         raise ValueError(f"dtype must be one of {tuple(DTYPES)}, got {dtype!r}")
     _check_pq_backend(pq_backend, "pq_backend")
