@@ -44,7 +44,7 @@ KINDS = {
     "HZ_K_SEARCH_PQSCAN": 47, "HZ_K_SEARCH_PQASSIGN": 48, "HZ_K_SEARCH_PQUPDATE": 49,
     "HZ_K_SEARCH_PQXSCAN": 50, "HZ_K_SEARCH_PQRESCORE": 51, "HZ_K_SEARCH_QXSCAN": 52, "HZ_K_SEARCH_QRESCORE": 53,
     "HZ_K_SEARCH_LXSCAN": 54, "HZ_K_SEARCH_RESCOREP": 55, "HZ_K_SEARCH_GRAPH": 56,
-    "HZ_K_GRAPH_PRUNE": 57, "HZ_K_GRAPH_SEED": 58,
+    "HZ_K_GRAPH_PRUNE": 57, "HZ_K_GRAPH_SEED": 58, "HZ_K_SEARCH_BXSCAN": 59,
 }
 globals().update(KINDS)
 KIND_STRUCT: dict = {}  # kind -> the ctypes mirror of its parameter struct

@@ -512,6 +512,42 @@ typedef struct HzSearchBinParams {
   HzSearchFilterParams f;        // the filtered scan's block, unchanged (live is required; ldc counts words)
 } HzSearchBinParams;
 int hz_search_bscan_launch(const HzSearchBinParams* p, hipStream_t st);
+// bulk binary scan (HZ_K_SEARCH_BXSCAN): HZ_K_SEARCH_BSCAN's rows, query rule, score and keys for any
+// number of queries, with a running top-R per (slab, query) in place of a ranking of every tile.
+// THE RULE is stated over the inputs alone. The rows are cut into slabs of `span` consecutive tiles of HZ_SEARCH_TILE
+// rows, nslab = ceil(ntile / span). cand[(slab * Q + q) * k ..] holds the best min(k, live rows of the slab) keys of that
+// slab for query q, best first, then key 0 -- the layout HZ_K_SEARCH_MERGEN reads when it is given N = nslab *
+// HZ_SEARCH_TILE (it reads no row). The merged answer is a function of the inputs: it does not depend on span, on the
+// grid or on the order in which threads stage keys. The words of a dead row, and of the rows between count and
+// capacity, are never loaded; a wave whose 64 rows are all dead loads nothing.
+// Why a threshold is exact: the scores are integers in [-D, D] and a slab is walked in ascending id order, so a row
+// whose Hamming distance EQUALS that of the k-th best key held so far has the higher id and loses to it under the
+// order rule; only ham < thr can enter. Grid (nslab, ceil(Q / HZ_SEARCH_BX_QG)), 256 threads.
+// span = 0: the launcher picks hz_search_bxscan_span(N, Q, k): about two workgroups per compute unit over the whole grid
+// where two fit its LDS (k <= 79), else one.
+// Refusals (nothing is launched): HZ_K_SEARCH_BSCAN's -80 (a null corpus, queries, cand, out_score or out_id), -81,
+// -82, -83, -84, -85, -87, -88 (without tags and filt), -89, -90; then -257 span < 0; -258 Q outside
+// 1..HZ_SEARCH_SELF_MAX_Q; -259 cand_bytes below nslab * Q * k * 8. -8: span = 0 without a device.
+#define HZ_SEARCH_BX_QG 32
+typedef struct HzSearchBinBatchParams {
+  const unsigned* corpus;        // uint32 [N][ldc] sign words, 16-B aligned rows (ldc in WORDS, ldc % 4 == 0, ldc >= D / 32)
+  const float* queries;          // device fp32 [Q][D], 16-B aligned
+  const unsigned* live;          // 1 bit per row: bit r & 31 of word r >> 5 (required)
+  unsigned long long* cand;      // scratch [nslab][Q][k] keys
+  float* out_score;              // fp32 [Q][k]  (the merge's; the scan checks it and writes nothing there)
+  int* out_id;                   // int32 [Q][k] (likewise)
+  unsigned long long live_bytes; // bytes of `live`, at least 4 * ceil(N / 32)
+  unsigned long long cand_bytes; // bytes of `cand`, at least hz_search_bxscan_scratch_bytes(N, Q, k, span)
+  int N, D, Q, k, ldc;
+  int ntile;                     // filled by the launcher: ceil(N / HZ_SEARCH_TILE)
+  int span;                      // tiles a workgroup walks, 0 = the launcher's choice
+  int nslab;                     // filled by the launcher: ceil(ntile / span)
+} HzSearchBinBatchParams;
+int hz_search_bxscan_launch(const HzSearchBinBatchParams* p, hipStream_t st);
+// the span a launch with span = 0 takes for (N, Q, k) on the current device; 0 for a refused shape, or without a device
+int hz_search_bxscan_span(long long N, long long Q, int k);
+// nslab * Q * k * 8 (span = 0: at the launcher's choice); 0 for a refused shape
+unsigned long long hz_search_bxscan_scratch_bytes(long long N, long long Q, int k, int span);
 // product-quantised rows: the D columns are M sub-spaces of dsub = D / M columns; a row is M bytes,
 // code[r][m] naming one of 256 sub-centroids codebook[m][c][0 .. dsub) (fp32 [M][256][dsub]). Shape rules, for both
 // kinds: M % 16 == 0 (a row is whole 16-B chunks), 16 <= M <= HZ_SEARCH_PQ_MAX_M (one query's table is M KiB of
@@ -1295,6 +1331,15 @@ int hz_index_search_batch_pq(void* idx, int ctx, const float* queries, int Q, in
 // hz_index_search_batch and hz_index_search_batch_pq keep refusing an fp8 index (-44, -46).
 int hz_index_search_batch_q(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                             float* out_stage1_last);
+// bulk search over a binary index (versions 8 and 9). R > 0 (version 9): replays H2D of the queries,
+// HZ_K_SEARCH_BXSCAN at k = R, HZ_K_SEARCH_MERGEN over the slab lists, HZ_K_SEARCH_RESCOREN (R -> k) against the bf16
+// rescore rows (device or pinned host memory) and two D2H; R = 0: the scan and the merge at k, stage one alone. Stage
+// one returns exactly the candidates of hz_index_search3, so the answer is that call's with refine = R in ids and score
+// bits: no certificate, no fallback. Captured per (Q, k, R) under hz_index_search_batch's rules, with its buffers,
+// hz_index_neighbors_max and its candidate scratch, which needs nslab * Q * max(R, k) * 8 bytes here.
+// -4: Q outside 1..the maximum; -5: k; -260: not a binary index; -27: R > 0 without rescore rows; -28: R > 0 outside
+// k..HZ_SEARCH_MAX_K (hz_index_last_error names the index or the value in each case).
+int hz_index_search_batch_b(void* idx, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id);
 // bulk search over an IVF index (version 5: bf16 rows stored list by list, dim % 32 == 0). Both calls
 // take at most hz_index_neighbors_max queries (the caller splits above it), run under the context's mutex and share
 // hz_index_search_batch's buffers and candidate scratch, grown on demand; the id-to-stored-row table, the centroids'
@@ -1592,7 +1637,8 @@ enum { HZ_UNIT_CONV = 1, HZ_UNIT_VISION = 2, HZ_UNIT_GEMM = 4, HZ_UNIT_TRANSFORM
   X(SEARCH_RESCOREP, 55, HzSearchRescorePosParams, hz_search_rescorep_op, SEARCH) \
   X(SEARCH_GRAPH, 56, HzSearchGraphParams, hz_search_graph_op, SEARCH)   \
   X(GRAPH_PRUNE, 57, HzGraphPruneParams, hz_graph_prune_op, SEARCH)      \
-  X(GRAPH_SEED, 58, HzGraphSeedParams, hz_graph_seed_op, SEARCH)
+  X(GRAPH_SEED, 58, HzGraphSeedParams, hz_graph_seed_op, SEARCH)        \
+  X(SEARCH_BXSCAN, 59, HzSearchBinBatchParams, hz_search_bxscan_op, SEARCH)
 #define HZ_KERNEL_ENUM(NAME, value, T, fn, unit) HZ_K_##NAME = value,
 enum { HZ_KERNELS(HZ_KERNEL_ENUM) };
 #undef HZ_KERNEL_ENUM

@@ -95,7 +95,10 @@ std::nullptr_t fail(const std::string& m) {
 constexpr uint64_t kTile = HZ_SEARCH_TILE;
 constexpr size_t kFiltBytes = (size_t)HZ_SEARCH_MAX_Q * 2 * 4;  // [MAX_Q][2] u32 in front of the queries
 
-enum { kProgGraph = 8 };  // the third field of a program key; 0 .. 7 are listed at Ctx::progs
+// The third field of a program key; the others (0 .. 7 and 9) are listed at Ctx::progs. Graph keys are 8 + 16 * nseed
+// and are told apart by `% 16 == kProgGraph`, so a new kind of program takes the next value with another remainder
+// (10 .. 15, then 17 ..): never 24, 40, ...
+enum { kProgGraph = 8 };
 
 struct Ctx {
   std::mutex mu;
@@ -144,7 +147,8 @@ struct Ctx {
   uint64_t cl_bytes[kClBufs] = {};
   // (Q, k, filtered, R, 0; R = 0: one stage); IVF: (Q, k, 1, R, nprobe; 0: every list) and (Q, nprobe, 2, 0, 0):
   // probes alone; neighbours: (n, k, 3, skip_self, 0); bulk search: (Q, k, 4, R, 0), on pq8 rows (Q, k, 5, R, 0), on
-  // fp8 rows (Q, k, 6, R, 0); the coarse stage of a bulk search over an IVF index: (Q, nprobe, 7, Rc, 0)
+  // fp8 rows (Q, k, 6, R, 0); the coarse stage of a bulk search over an IVF index: (Q, nprobe, 7, Rc, 0); bulk search
+  // over sign-bit rows: (Q, k, 9, R, 0)
   // graph search: (Q, k, kProgGraph + 16 * nseed, beam * 1024 + width, iters); nseed <= 64
   std::map<std::tuple<int, int, int, int, int>, HzProgram> progs;
 };
@@ -479,6 +483,59 @@ struct Index {
     if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
     if (!rc) rc = by_codebook || by_codes ? hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.blast_dev, (size_t)Q * 4, 0)
                               : hz_prog_add_memcpy(g, c.bout_host + 2 * kSelfOutHalf, c.bmid_dev, (size_t)Q * R * 4, 0);
+    if (rc) {
+      hz_prog_destroy(g);
+      return nullptr;
+    }
+    c.progs[key] = g;
+    return g;
+  }
+
+  // The bulk-search program of (Q, k, R) over sign-bit rows (key 9; the caller holds c.mu): H2D of the
+  // queries, HZ_K_SEARCH_BXSCAN at k = R into the candidate scratch [nslab][Q][R], HZ_K_SEARCH_MERGEN over those lists
+  // (N = nslab tiles) into bmid_dev, HZ_K_SEARCH_RESCOREN R -> k against the rescore rows into bout_dev, two D2H. R = 0:
+  // the scan and the merge at k straight into bout_dev. The span is fixed here, so the scan and the merge agree on nslab.
+  HzProgram bin_batch_program(Ctx& c, int Q, int k, int R, bool* fresh) {
+    if (!batch_buffers(c)) return nullptr;
+    const int K1 = R ? R : k;
+    const int span = hz_search_bxscan_span((long long)scan_rows(), Q, K1);
+    if (!span || !bulk_scratch(c, hz_search_bxscan_scratch_bytes((long long)scan_rows(), Q, K1, span))) return nullptr;
+    const auto key = std::make_tuple(Q, k, 9, R, 0);
+    auto it = c.progs.find(key);
+    *fresh = it == c.progs.end();
+    if (!*fresh) return it->second;
+    char* stage1 = R ? c.bmid_dev : c.bout_dev;
+    HzSearchBinBatchParams p{};
+    p.corpus = reinterpret_cast<const unsigned*>(rows);
+    p.queries = c.bq_dev;
+    p.live = live;
+    p.cand = c.ncand;
+    p.out_score = reinterpret_cast<float*>(stage1);
+    p.out_id = reinterpret_cast<int*>(stage1 + kSelfOutHalf);
+    p.live_bytes = cap / 8;
+    p.cand_bytes = c.ncand_bytes;
+    p.N = (int)scan_rows();
+    p.D = (int)h.dim, p.ldc = p.D / 32;
+    p.Q = Q, p.k = K1, p.span = span;
+    const int nslab = (int)((scan_rows() / kTile + span - 1) / span);
+    HzSearchSelfParams mp{};  // the merge reads cand, out_*, N, Q, k and cand_bytes only
+    mp.cand = p.cand, mp.out_score = p.out_score, mp.out_id = p.out_id, mp.cand_bytes = p.cand_bytes;
+    mp.N = nslab * (int)kTile, mp.D = mp.ldc = p.D, mp.Q = Q, mp.k = K1;
+    HzSearchRescoreParams rp{};
+    rp.rows = rrows_dev;
+    rp.queries = c.bq_dev;
+    rp.in_id = p.out_id;
+    rp.out_score = reinterpret_cast<float*>(c.bout_dev);
+    rp.out_id = reinterpret_cast<int*>(c.bout_dev + kSelfOutHalf);
+    rp.N = p.N, rp.D = rp.ldc = p.D, rp.Q = Q, rp.R = R, rp.k = k;
+    HzProgram g = hz_prog_create();
+    const size_t qk = (size_t)Q * k * 4;
+    int rc = hz_prog_add_memcpy(g, c.bq_dev, c.bq_host, (size_t)Q * h.dim * 4, 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_BXSCAN, &p, sizeof(p), 0);
+    if (!rc) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_MERGEN, &mp, sizeof(mp), 0);
+    if (!rc && R) rc = hz_prog_add_kernel(g, HZ_K_SEARCH_RESCOREN, &rp, sizeof(rp), 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host, c.bout_dev, qk, 0);
+    if (!rc) rc = hz_prog_add_memcpy(g, c.bout_host + kSelfOutHalf, c.bout_dev + kSelfOutHalf, qk, 0);
     if (rc) {
       hz_prog_destroy(g);
       return nullptr;
@@ -1688,6 +1745,46 @@ int hz_index_search_batch_pq(void* h, int ctx, const float* queries, int Q, int 
 int hz_index_search_batch_q(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id,
                             float* out_stage1_last) {
   return bulk_search(h, ctx, queries, Q, k, R, out_score, out_id, out_stage1_last, Index::kBatchFp8);
+}
+
+// hz_index_search_batch_b (hipzap.h): the argument checks, the program of (Q, k, R) and its run
+int hz_index_search_batch_b(void* h, int ctx, const float* queries, int Q, int k, int R, float* out_score, int* out_id) {
+  Index* x = static_cast<Index*>(h);
+  if (!x || !queries || !out_score || !out_id) return -1;
+  if (ctx < 0 || ctx >= (int)x->ctx.size()) return -9;
+  if (!x->bin) {
+    g_err = std::string("index: search_batch_bin needs a bin_sign index (versions 8 and 9), this one is ") +
+            (x->ivf ? (x->fp8 ? "an fp8 IVF index" : "an IVF index") : x->fp8 || x->pq ? x->quant_name() : "a bf16 index") +
+            " of version " + std::to_string(x->h.version);
+    return -260;
+  }
+  if (k < 1 || k > HZ_SEARCH_MAX_K) {
+    g_err = "index: k must be in 1.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(k);
+    return -5;
+  }
+  if (R && !x->rescore) {
+    g_err = std::string("index: refine needs rescore rows (a version-9 file), the index holds ") + x->dtype_name() + " rows only";
+    return -27;
+  }
+  if (R && (R < k || R > HZ_SEARCH_MAX_K)) {
+    g_err = "index: refine must be 0 or in k.." + std::to_string(HZ_SEARCH_MAX_K) + ", got " + std::to_string(R);
+    return -28;
+  }
+  Ctx& c = *x->ctx[ctx];
+  std::lock_guard<std::mutex> lk(c.mu);  // count and self_max change only under every context's mutex
+  if (Q < 1 || Q > x->self_max) {
+    g_err = "index: search_batch_bin takes 1.." + std::to_string(x->self_max) + " queries a call, got " + std::to_string(Q);
+    return -4;
+  }
+  if (hipSetDevice(x->device) != hipSuccess) return -10;
+  bool fresh = false;
+  HzProgram g = x->bin_batch_program(c, Q, k, R, &fresh);
+  if (!g) return -11;
+  std::memcpy(c.bq_host, queries, (size_t)Q * x->h.dim * 4);
+  return run_program(c, g, fresh, [&] {
+    std::memcpy(out_score, c.bout_host, (size_t)Q * k * 4);
+    std::memcpy(out_id, c.bout_host + kSelfOutHalf, (size_t)Q * k * 4);
+  });
 }
 
 }  // extern "C"

@@ -540,6 +540,10 @@ extern "C" __attribute__((weak)) int hz_graph_seed_launch(const HzGraphSeedParam
 static int hz_graph_seed_op(const HzGraphSeedParams* p, hipStream_t st) {
   return hz_graph_seed_launch ? hz_graph_seed_launch(p, st) : -102;
 }
+extern "C" __attribute__((weak)) int hz_search_bxscan_launch(const HzSearchBinBatchParams* p, hipStream_t st);
+static int hz_search_bxscan_op(const HzSearchBinBatchParams* p, hipStream_t st) {
+  return hz_search_bxscan_launch ? hz_search_bxscan_launch(p, st) : -102;
+}
 
 // everything below is generated from the kernel table (hipzap.h HZ_KERNELS)
 extern "C" int hz_launch_kernel(int kind, const void* prm, hipStream_t st) {

@@ -39,6 +39,7 @@
 // 4aa / 4ab for the reasoning.
 #include <stdio.h>
 
+#include <atomic>
 #include <initializer_list>
 #include <type_traits>
 
@@ -2399,6 +2400,182 @@ HZ_NO_PK_F32 __global__ __launch_bounds__(T) void graph_seed_kernel(const HzGrap
   }
 }
 
+// ------------------------------------------------------------------------------- bulk binary scan
+// search_bxscan_kernel<NCH> (HZ_K_SEARCH_BXSCAN): THE RULE of hipzap.h -- per (slab, query) the best R = a.k
+// keys of the slab's live rows, HZ_K_SEARCH_BSCAN's score and keys. Grid (nslab, ceil(Q / BX_QG)), T threads: a
+// workgroup owns one slab of `span` tiles and BX_QG = 32 queries, so a row is read once per 32 queries (16 would double
+// the reads and the barriers per query for nothing: the workgroup is LDS-bound to one or two per compute unit at
+// either size, and 32 still fits R = 128 at D = 2048 in 104.5 KiB).
+//   * query bits: search_bscan_kernel's ballots into qb[BX_QG][WB] (WB = 4 NCH; words from W on are zero), once.
+//   * a tile: thread t owns row t and holds its W words in registers (16-B loads, only under the row's live bit, which the
+//     thread reads itself: no staging, no barrier); the NEXT tile's words, and the bit of the tile after it, are in
+//     flight while this tile is scored.
+//     Per query: xor + popcount against qb[q] (16-B LDS broadcasts), then pass = live && ham < thr[q].
+//   * staging: a wave's passing lanes take consecutive slots of stg[q][T] from ONE LDS atomic add per (wave, query) on
+//     cnt[q] (the ballot's count; a lane's offset is its rank in the ballot). A slot is (ham << 8) | t, 32 bits: the id
+//     is the tile's base plus t. With no passing lane -- nearly every (tile, query) after the warm-up -- the wave
+//     spends the ballot and a scalar branch.
+//   * folding: one barrier, then wave w takes queries w, w + 4, ... with cnt[q] != 0 (one LDS read for the others).
+//     Every held and staged key is ranked by counting, on the full 64-bit key: a held key at position j has rank j + the
+//     staged keys above it, a staged key the held and staged keys above it. Ranks below R go to the query's OTHER list
+//     (keys[2][BX_QG][R]; sel[q] names the current one), so no key is overwritten before it is read; thr[q] becomes the
+//     Hamming distance of rank R - 1 once R keys are held (D + 1 before: every live row passes). A second barrier.
+//   * after the last tile: cand[(slab*Q + q)*R + s] = the list, then key 0; coalesced 8-byte stores.
+// Addresses: queries[(q0 + q)*D + i] under q0 + q < Q, i < D; live word row >> 5 under row < N (the launcher checks
+// live_bytes); corpus words [row*ldc + 4c, + 4) under the live bit, row < N and 4c < W <= ldc; stg slot under at < T;
+// list slots under rank < R; cand under q0 + q < Q, s < R and cand_bytes. Offsets are long.
+// Dynamic LDS: qb 32 WB words, keys 2 x 32 x R x 8, stg 32 x T x 4, four ints a query: 55.5 KiB at D = 768, R = 40 (two
+// workgroups a compute unit), 99.5 KiB at R = 128, 104.5 KiB at D = 2048.
+constexpr int BX_QG = HZ_SEARCH_BX_QG;
+static_assert(T == 256 && HZ_SEARCH_MAX_K <= 128 && BX_QG % 4 == 0, "two list keys and four staged keys a lane; a slot's low 8 bits are t");
+inline size_t bx_lds_bytes(int WB, int R) {
+  return (size_t)BX_QG * WB * 4 + 2 * (size_t)BX_QG * R * 8 + (size_t)BX_QG * T * 4 + 4 * BX_QG * 4;
+}
+__device__ __forceinline__ unsigned long long bx_key(int D, unsigned ham, unsigned id) {
+  return ((unsigned long long)orderable((float)(D - 2 * (int)ham)) << 32) | (unsigned)~id;
+}
+
+template <int NCH>
+HZ_NO_PK_F32 __global__ __launch_bounds__(T) void search_bxscan_kernel(const HzSearchBinBatchParams a) {
+  constexpr int WB = NCH * 4;
+  extern __shared__ __attribute__((aligned(16))) unsigned char bx_lds[];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int slab = blockIdx.x, q0 = blockIdx.y * BX_QG;
+  const int D = a.D, W = D >> 5, R = a.k;
+  if (!HZ_DCHECK(D >= 128 && D % 128 == 0 && W <= WB && a.ldc >= W && R >= 1 && R <= HZ_SEARCH_MAX_K && a.span >= 1 &&
+                 slab < a.nslab && (long)slab * a.span < (long)a.ntile && q0 < a.Q && (long)a.ntile * T >= (long)a.N))
+    return;
+  const int nq = min(BX_QG, a.Q - q0);
+  unsigned* qb = reinterpret_cast<unsigned*>(bx_lds);                                  // [BX_QG][WB]
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(qb + BX_QG * WB);    // [2][BX_QG][R]
+  unsigned* stg = reinterpret_cast<unsigned*>(keys + 2 * BX_QG * R);                    // [BX_QG][T]
+  int* thr = reinterpret_cast<int*>(stg + BX_QG * T);
+  int* cnt = thr + BX_QG;
+  int* len = cnt + BX_QG;
+  int* sel = len + BX_QG;
+  const int nblk = D >> 6;  // 64-column blocks of a query: two words each
+  for (int i = w; i < nq * nblk; i += T / 64) {  // wave-uniform bounds
+    const int q = i / nblk, c = i - q * nblk;
+    float x = -1.f;
+    if (HZ_DCHECK(q0 + q < a.Q && c * 64 + lane < D)) x = a.queries[(long)(q0 + q) * D + c * 64 + lane];
+    const unsigned long long m = __ballot((__float_as_uint(x) >> 31) == 0u);
+    if (lane == 0) qb[q * WB + 2 * c] = (unsigned)m, qb[q * WB + 2 * c + 1] = (unsigned)(m >> 32);
+  }
+  if (W < WB)
+    for (int i = t; i < nq * (WB - W); i += T) qb[i / (WB - W) * WB + W + i % (WB - W)] = 0u;
+  if (t < BX_QG) thr[t] = D + 1, cnt[t] = 0, len[t] = 0, sel[t] = 0;
+
+  const int tile0 = slab * a.span, tile1 = min(a.ntile, tile0 + a.span);
+  // row t of `tile`: its live bit (a tile from tile1 on: none), and under that bit its words
+  const auto live_bit = [&](int tile) __attribute__((always_inline)) {
+    const long row = (long)tile * T + t;
+    bool lv = false;
+    if (tile < tile1 && row < (long)a.N && HZ_DCHECK(((row >> 5) + 1) * 4 <= (long)a.live_bytes))
+      lv = (a.live[row >> 5] >> (unsigned)(row & 31)) & 1u;
+    return lv;
+  };
+  const auto load = [&](u32x4(&v)[NCH], int tile, bool lv) __attribute__((always_inline)) {
+    const long row = (long)tile * T + t;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      v[c] = u32x4{0u, 0u, 0u, 0u};
+      if (lv && c * 4 < W && HZ_DCHECK(tile < tile1 && row < (long)a.N && c * 4 + 4 <= a.ldc))
+        v[c] = *reinterpret_cast<const u32x4*>(a.corpus + row * a.ldc + c * 4);
+    }
+  };
+  // in flight while tile `tile` is scored: the words of tile + 1 (under the bit read a tile earlier) and the bit of tile + 2
+  u32x4 cur[NCH], nxt[NCH];
+  bool lcur = live_bit(tile0), lnxt = live_bit(tile0 + 1);
+  load(cur, tile0, lcur);
+  pqx_sync();
+
+#pragma unroll 1
+  for (int tile = tile0; tile < tile1; ++tile) {  // workgroup-uniform bounds
+    load(nxt, tile + 1, lnxt);
+    const bool lnn = live_bit(tile + 2);
+    const unsigned row0 = (unsigned)tile * T;  // N < 2^31
+    if (__ballot(lcur) != 0ull) {  // scalar: some row of this wave is live
+      for (int q = 0; q < nq; ++q) {
+        int ham = 0;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const u32x4 x = *reinterpret_cast<const u32x4*>(qb + q * WB + c * 4);  // every lane reads the same words
+          ham += __builtin_popcount(cur[c][0] ^ x[0]) + __builtin_popcount(cur[c][1] ^ x[1]) +
+                 __builtin_popcount(cur[c][2] ^ x[2]) + __builtin_popcount(cur[c][3] ^ x[3]);
+        }
+        const bool pass = lcur && ham < thr[q];
+        const unsigned long long pm = __ballot(pass);
+        if (pm != 0ull) {  // scalar
+          int base = 0;
+          if (lane == 0) base = __hip_atomic_fetch_add(&cnt[q], __builtin_popcountll(pm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          base = __builtin_amdgcn_readfirstlane(base);
+          const int at = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(pm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)pm, 0u));
+          if (pass && HZ_DCHECK(at >= 0 && at < T)) stg[q * T + at] = ((unsigned)ham << 8) | (unsigned)t;
+        }
+      }
+    }
+    pqx_sync();
+    for (int q = w; q < nq; q += T / 64) {  // wave-uniform
+      const int ns = min(__builtin_amdgcn_readfirstlane(cnt[q]), T);
+      if (ns == 0) continue;
+      const int nl = min(__builtin_amdgcn_readfirstlane(len[q]), R);
+      const int s = __builtin_amdgcn_readfirstlane(sel[q]) & 1;
+      const unsigned long long* L = keys + ((long)s * BX_QG + q) * R;
+      unsigned long long* O = keys + ((long)(s ^ 1) * BX_QG + q) * R;
+      const unsigned* G = stg + q * T;
+      unsigned long long lk[2], sk[4];
+      int lr[2], sr[4];
+#pragma unroll
+      for (int x = 0; x < 2; ++x) lk[x] = lane + 64 * x < nl ? L[lane + 64 * x] : 0ull, lr[x] = lane + 64 * x;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        sk[x] = 0ull, sr[x] = 0;
+        if (lane + 64 * x < ns) {
+          const unsigned g = G[lane + 64 * x];
+          sk[x] = bx_key(D, g >> 8, row0 + (g & 255u));
+        }
+      }
+      for (int j = 0; j < nl; ++j) {  // every lane reads the same word: LDS broadcasts
+        const unsigned long long kj = L[j];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) sr[x] += kj > sk[x];
+      }
+      for (int j = 0; j < ns; ++j) {
+        const unsigned g = G[j];
+        const unsigned long long kj = bx_key(D, g >> 8, row0 + (g & 255u));
+#pragma unroll
+        for (int x = 0; x < 2; ++x) lr[x] += kj > lk[x];
+#pragma unroll
+        for (int x = 0; x < 4; ++x) sr[x] += kj > sk[x];
+      }
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+        if (lk[x] != 0ull && lr[x] < R) O[lr[x]] = lk[x];
+#pragma unroll
+      for (int x = 0; x < 4; ++x)
+        if (sk[x] != 0ull && sr[x] < R) O[sr[x]] = sk[x];
+      seed_wave_sync();
+      if (lane == 0) {
+        const int n = min(R, nl + ns);
+        len[q] = n, cnt[q] = 0, sel[q] = s ^ 1;
+        if (n == R) thr[q] = (D - (int)unorderable((unsigned)(O[R - 1] >> 32))) / 2;
+      }
+    }
+    pqx_sync();
+    lcur = lnxt, lnxt = lnn;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) cur[c] = nxt[c];
+  }
+
+  for (int i = t; i < nq * R; i += T) {
+    const int q = i / R, s = i - q * R;
+    const unsigned long long key = s < len[q] ? keys[((long)(sel[q] & 1) * BX_QG + q) * R + s] : 0ull;
+    const long at = ((long)slab * a.Q + q0 + q) * R + s;
+    if (HZ_DCHECK(q0 + q < a.Q && (at + 1) * 8 <= (long)a.cand_bytes)) a.cand[at] = key;
+  }
+}
+
 // ------------------------------------------------------------------------- nearest centroid, means
 // search_assign_kernel (HZ_K_SEARCH_ASSIGN): the self scan with the roles turned. Workgroup `tile`
 // scores its T rows against all C centroids, CB at a time: the A operand is the centroid block (every workgroup
@@ -3147,6 +3324,35 @@ int raise_seed_lds_limit() {
   return once_per_device(seed_raised, [] { return raise_lds_limit_of(&graph_seed_kernel, seed_lds_bytes(2048, HZ_GRAPH_SEED_MAX_E)); });
 }
 
+// the bulk binary scan's dynamic LDS reaches 104.5 KiB (D = 2048, R = 128): raised once per device for every bucket,
+// outside any capture, where the device's compute units are counted too (the launcher's span)
+std::atomic<int> bx_cus[64];  // 0: not set up yet; two contexts may meet here on a device's first call and store the same count
+int bx_device_setup(int* cus) {
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return -8;
+  if (!bx_cus[d].load(std::memory_order_acquire)) {
+    int n = 0;
+    if (const int rc = raise_lds_limit_of(&search_bxscan_kernel<2>, bx_lds_bytes(8, HZ_SEARCH_MAX_K))) return rc;
+    if (const int rc = raise_lds_limit_of(&search_bxscan_kernel<6>, bx_lds_bytes(24, HZ_SEARCH_MAX_K))) return rc;
+    if (const int rc = raise_lds_limit_of(&search_bxscan_kernel<8>, bx_lds_bytes(32, HZ_SEARCH_MAX_K))) return rc;
+    if (const int rc = raise_lds_limit_of(&search_bxscan_kernel<16>, bx_lds_bytes(64, HZ_SEARCH_MAX_K))) return rc;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 1) return -8;
+    bx_cus[d].store(n, std::memory_order_release);
+  }
+  if (cus) *cus = bx_cus[d].load(std::memory_order_acquire);
+  return 0;
+}
+// Tiles per workgroup: the span that leaves about two workgroups per compute unit over the grid (ceil(ntile / span),
+// ceil(Q / BX_QG)) where two fit a compute unit's 160 KiB of LDS at any D (k <= 79), else one: a second workgroup that
+// must wait for the first only adds a slab's warm-up (its first tiles stage every row) and a list to merge (DESIGN.md
+// 4af measured the doubled span 11 to 23 % faster at k = 128). The answer does not depend on the choice.
+int bx_auto_span(long ntile, long Q, int cus, int k) {
+  const long nqg = (Q + BX_QG - 1) / BX_QG;
+  const long wgs = (2 * bx_lds_bytes(64, k) <= 160u * 1024u ? 2l : 1l) * cus;
+  const long span = (ntile * nqg + wgs - 1) / wgs;
+  return (int)max(1l, min(span, ntile));
+}
+
 }  // namespace
 
 // The graph search's refusals (hipzap.h), one code per rule; then the smallest table whose half holds the visited bound.
@@ -3204,6 +3410,58 @@ extern "C" int hz_graph_seed_launch(const HzGraphSeedParams* pp, hipStream_t st)
     return -250;
   if (const int rc = raise_seed_lds_limit()) return rc;
   hipLaunchKernelGGL(graph_seed_kernel, dim3((unsigned)((a.Q + SEED_QT - 1) / SEED_QT)), dim3(T), seed_lds_bytes(a.D, a.E), st, a);
+  return (int)hipGetLastError();
+}
+
+extern "C" int hz_search_bxscan_span(long long N, long long Q, int k) {
+  if (N < 1 || N >= (1ll << 31) || Q < 1 || Q > HZ_SEARCH_SELF_MAX_Q || k < 1 || k > HZ_SEARCH_MAX_K) return 0;
+  int cus = 0;
+  if (bx_device_setup(&cus)) return 0;
+  return bx_auto_span((long)((N + T - 1) / T), (long)Q, cus, k);
+}
+
+extern "C" unsigned long long hz_search_bxscan_scratch_bytes(long long N, long long Q, int k, int span) {
+  if (N < 1 || N >= (1ll << 31) || Q < 1 || Q > HZ_SEARCH_SELF_MAX_Q || k < 1 || k > HZ_SEARCH_MAX_K || span < 0) return 0;
+  if (!span) span = hz_search_bxscan_span(N, Q, k);
+  if (!span) return 0;
+  const unsigned long long ntile = (unsigned long long)((N + T - 1) / T);
+  return (ntile + span - 1) / span * (unsigned long long)Q * k * 8ull;
+}
+
+// The bulk binary scan's refusals (hipzap.h): the binary scan's -80 .. -90 without the filter cases, then -257 .. -259.
+// Buckets of 16-B chunks per thread as in hz_search_bscan_launch: W <= 8, 24, 32, 64.
+extern "C" int hz_search_bxscan_launch(const HzSearchBinBatchParams* pp, hipStream_t st) {
+  if (!pp) return -80;
+  HzSearchBinBatchParams a = *pp;
+  if (!a.corpus || !a.queries || !a.cand || !a.out_score || !a.out_id) return -80;
+  if (a.D % 128) return -81;
+  if (a.D < 128) return -82;
+  if (a.D > 2048) return -83;
+  const int W = a.D / 32;
+  if (a.ldc < W || a.ldc % 4) return -84;
+  if (a.N < 1) return -85;
+  if (a.k < 1 || a.k > HZ_SEARCH_MAX_K) return -87;
+  if ((reinterpret_cast<uintptr_t>(a.corpus) & 15) || (reinterpret_cast<uintptr_t>(a.queries) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.cand) & 7) || (reinterpret_cast<uintptr_t>(a.out_score) & 3) ||
+      (reinterpret_cast<uintptr_t>(a.out_id) & 3) || (reinterpret_cast<uintptr_t>(a.live) & 3))
+    return -88;
+  if (!a.live) return -89;
+  if (a.live_bytes < 4ull * (((unsigned long long)a.N + 31) / 32)) return -90;
+  if (a.span < 0) return -257;
+  if (a.Q < 1 || a.Q > HZ_SEARCH_SELF_MAX_Q) return -258;
+  a.ntile = (int)(((long)a.N + T - 1) / T);
+  if (a.span > 0 && a.cand_bytes < hz_search_bxscan_scratch_bytes(a.N, a.Q, a.k, a.span)) return -259;  // before any device call
+  int cus = 0;
+  if (const int rc = bx_device_setup(&cus)) return rc;
+  if (!a.span) a.span = bx_auto_span(a.ntile, a.Q, cus, a.k);
+  a.span = min(a.span, a.ntile);
+  a.nslab = (a.ntile + a.span - 1) / a.span;
+  if (a.cand_bytes < (unsigned long long)a.nslab * (unsigned long long)a.Q * a.k * 8ull) return -259;
+  const dim3 grid(a.nslab, (a.Q + BX_QG - 1) / BX_QG), block(T);
+  if (W <= 8) hipLaunchKernelGGL(search_bxscan_kernel<2>, grid, block, bx_lds_bytes(8, a.k), st, a);
+  else if (W <= 24) hipLaunchKernelGGL(search_bxscan_kernel<6>, grid, block, bx_lds_bytes(24, a.k), st, a);
+  else if (W <= 32) hipLaunchKernelGGL(search_bxscan_kernel<8>, grid, block, bx_lds_bytes(32, a.k), st, a);
+  else hipLaunchKernelGGL(search_bxscan_kernel<16>, grid, block, bx_lds_bytes(64, a.k), st, a);
   return (int)hipGetLastError();
 }
 
@@ -3413,5 +3671,6 @@ extern "C" int hz_search_code_warm(void) {
   if (const int rc = once_per_device(lxscan_raised, [] { return raise_lds_limit_of(&search_lxscan_kernel, LXSCAN_LDS); })) return rc;
   if (const int rc = once_per_device(graph_raised, [] { return raise_graph_lds_limit(); })) return rc;
   if (const int rc = raise_seed_lds_limit()) return rc;
+  if (const int rc = bx_device_setup(nullptr)) return rc;
   return pq_device_setup(nullptr);
 }

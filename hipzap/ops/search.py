@@ -8,6 +8,8 @@ per-query ``{mask, value}`` filters) is the scan over the rows that pass. ``HZ_K
 (``QuantScanParams``: that block plus one fp32 scale per row) is the filtered scan over rows of OCP e4m3fn bytes.
 ``HZ_K_SEARCH_BSCAN`` (``BinScanParams``: the filtered block over uint32 sign-bit rows, ``ldc`` in words) scores
 ``D - 2 popcount(query bits xor row bits)``, the queries binarised in the kernel.
+``HZ_K_SEARCH_BXSCAN`` (``BinBatchScanParams``) is that scan for any number of queries: a workgroup walks a slab of
+``span`` tiles for 32 queries with a running top-k and a threshold, and ``HZ_K_SEARCH_MERGEN`` reduces the slab lists.
 ``HZ_K_SEARCH_RESCORE`` (``RescoreParams``) is the second stage of a two-stage search: one workgroup per query
 re-scores the ``R`` bf16 rows that a merge's ``out_id`` names and writes the best ``k`` of them.
 ``HZ_K_SEARCH_LSCAN`` (``ListScanParams``) is the filtered scan over an IVF index's lists: workgroup (j, q) scans
@@ -110,6 +112,23 @@ class BinScanParams(C.Structure):
         sp = SearchParams.from_buffer_copy(self)
         sp.ldc = sp.D
         return sp
+
+
+@N.params_of("HZ_K_SEARCH_BXSCAN")
+class BinBatchScanParams(C.Structure):
+    """HzSearchBinBatchParams: ``corpus`` uint32 sign-bit rows [N][ldc] (``ldc`` in words), device fp32 ``queries``
+    [Q][D], the required ``live`` bitmap, ``cand`` [nslab][Q][k] keys, the merge's outputs, the byte counts and shape,
+    then ``span`` (tiles a workgroup walks; 0: the launcher's choice) and ``nslab``."""
+    _fields_ = [("corpus", C.c_void_p), ("queries", C.c_void_p), ("live", C.c_void_p), ("cand", C.c_void_p),
+                ("out_score", C.c_void_p), ("out_id", C.c_void_p), ("live_bytes", C.c_uint64), ("cand_bytes", C.c_uint64),
+                ("N", C.c_int), ("D", C.c_int), ("Q", C.c_int), ("k", C.c_int), ("ldc", C.c_int), ("ntile", C.c_int),
+                ("span", C.c_int), ("nslab", C.c_int)]
+
+    def merge_params(self, nslab: int) -> "SelfScanParams":
+        """The block ``HZ_K_SEARCH_MERGEN`` takes over the ``nslab`` slab lists: N = nslab tiles (it reads no row)."""
+        mp = SelfScanParams(cand=self.cand, out_score=self.out_score, out_id=self.out_id, cand_bytes=self.cand_bytes,
+                            N=int(nslab) * tile_rows(), D=self.D, Q=self.Q, k=self.k, ldc=self.D)
+        return mp
 
 
 @N.params_of("HZ_K_SEARCH_PQLUT")
@@ -369,6 +388,10 @@ def _sigs(lib):
     N._sig(lib, "hz_search_qscan_launch", C.c_int, C.POINTER(QuantScanParams), P)
     N._sig(lib, "hz_search_rescore_launch", C.c_int, C.POINTER(RescoreParams), P)
     N._sig(lib, "hz_search_bscan_launch", C.c_int, C.POINTER(BinScanParams), P)
+    N._sig(lib, "hz_search_bxscan_launch", C.c_int, C.POINTER(BinBatchScanParams), P)
+    N._sig(lib, "hz_search_bxscan_span", C.c_int, C.c_longlong, C.c_longlong, C.c_int)
+    N._sig(lib, "hz_search_bxscan_scratch_bytes", U64, C.c_longlong, C.c_longlong, C.c_int, C.c_int)
+    N._sig(lib, "hz_index_search_batch_b", C.c_int, P, C.c_int, P, C.c_int, C.c_int, C.c_int, P, P)
     N._sig(lib, "hz_index_add_b", C.c_int, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_add_br", C.c_int, P, P, P, C.c_longlong, P, C.POINTER(C.c_longlong))
     N._sig(lib, "hz_index_read_state_b", C.c_int, P, P, P, P, C.c_longlong)
@@ -460,6 +483,18 @@ def launch_bin(prm: BinScanParams, stream: int = 0) -> tuple:
         return rc, None
     sp = prm.scan_params()
     return rc, lib.hz_search_merge_launch(C.byref(sp), stream)
+
+
+def bin_batch_span(n: int, q: int, k: int) -> int:
+    """The tiles per workgroup a bulk binary scan of (N, Q, k) takes with ``span`` = 0 on the current device; 0 for a
+    refused shape."""
+    return int(N.lib().hz_search_bxscan_span(int(n), int(q), int(k)))
+
+
+def bin_batch_scratch_bytes(n: int, q: int, k: int, span: int = 0) -> int:
+    """Bytes of candidate scratch a bulk binary scan of (N, Q, k) needs at ``span``: nslab * Q * k * 8; 0 for a refused
+    shape."""
+    return int(N.lib().hz_search_bxscan_scratch_bytes(int(n), int(q), int(k), int(span)))
 
 
 def launch_pq_lut(prm: PqLutParams, stream: int = 0) -> int:

@@ -1922,6 +1922,16 @@ class _Base:
         k = check_k(k)
         return k, batch_candidates(k, candidates)
 
+    def _check_batch_bin(self, q, k, refine):
+        """The refusals of :meth:`search_batch_bin` that both backends share -> (queries, k, R)."""
+        if self.dtype != BIN:
+            what = ("an fp8 IVF index" if self.dtype == FP8 else "an IVF index") if self.ivf is not None else \
+                f"a {self.dtype} index" if self.dtype == PQ else f"an {FP8} index" if self.dtype == FP8 else "a bf16 index"
+            raise ValueError(f"search_batch_bin needs a {BIN} index (versions 8 and 9), this one is {what} of version "
+                             f"{self.version}")
+        q, k = check_queries(q, self.dim), check_k(k)
+        return q, k, self._refine(refine, k)
+
     def _check_batch_ivf(self, what: str):
         """The refusals that :meth:`probes_batch` and :meth:`search_batch_ivf` (``what``) share, on both backends."""
         if self.ivf is None or self.dtype != "bf16":
@@ -2283,6 +2293,17 @@ class RefIndex(_Base):
                 s, i = pq_search_ref(self._bits, self.codebook, q, R or k, allow)
             else:
                 s, i = search_ref(self._rows, q, R or k, allow, scales=self.scales)
+            if R:
+                two = [rescore_ref(self._rrows, q[a], i[a], k) for a in range(q.shape[0])]
+                s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
+        return s.astype(np.float32), i
+
+    def search_batch_bin(self, q, k: int = 10, *, refine=None, ctx=None):
+        """:meth:`Index.search_batch_bin` on the host, its oracle: :func:`bin_search_ref` at R, then :func:`rescore_ref`
+        -- the computation :meth:`search` runs on a binary index, so the two agree exactly."""
+        q, k, R = self._check_batch_bin(q, k, refine)
+        with self._mut:
+            s, i = bin_search_ref(self._bits, binarize(q), self.dim, R or k, None if self._live.all() else self._live)
             if R:
                 two = [rescore_ref(self._rrows, q[a], i[a], k) for a in range(q.shape[0])]
                 s, i = np.stack([t[0] for t in two]), np.stack([t[1] for t in two])
@@ -2817,6 +2838,20 @@ class Index(_Base):
         last = np.empty(nq, np.float32)
         with self._in_parts("hz_index_search_batch_q", (-4, -5, -186, -187, -188), q, (k, R), (scores, ids, last), ctx) as c:
             return self._finish_batch_fp8(q, k, R, scores, ids, last, fallback, ctx=c)
+
+    def search_batch_bin(self, q, k: int = 10, *, refine=None, ctx: int | None = None):
+        """Many fp32 queries at once over a binary index -> (scores float32 [Q, k], ids int32 [Q, k]).
+        The result equals ``self.search(q, k, refine=refine)`` in ids and score bits: stage one is the popcount scan of
+        :meth:`search` with a running top-R and an integer threshold per query in place of a ranking of every tile --
+        exact, since a row that ties with the R-th best key held has the higher id and loses -- and stage two the same
+        bf16 rescoring. Nothing is approximate: no certificate, no fallback. ``refine`` goes through
+        :meth:`_Base._refine` as in :meth:`search`; Q above the per-call maximum is split here. Q <= 16 gains nothing
+        over :meth:`search`."""
+        q, k, R = self._check_batch_bin(q, k, refine)
+        scores, ids = np.empty((q.shape[0], k), np.float32), np.empty((q.shape[0], k), np.int32)
+        with self._in_parts("hz_index_search_batch_b", (-4, -5, -27, -28, -260), q, (k, R), (scores, ids), ctx):
+            pass
+        return scores, ids
 
     def neighbors(self, ids, k: int = 10, *, include_self: bool = False, ctx: int | None = None):
         """The ``k`` nearest live rows of each stored row ``ids`` names -> (scores float32 [n, k], ids int32 [n, k]),
